@@ -6,8 +6,12 @@ chunks, then decode it, inputs and outputs resident in HBM.  Default workload is
 BASELINE.json configs[1]: 1M x 7000 int16 Gaussian(sigma=10), m=8, framed as 500
 HDF5 chunks of 2000 x 7000 (the reference's Nab chunk shape, docs/Performance.md:16).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs: it sets up, warms up, times exactly K steps, checks the round trip of the
+last one, writes its outputs with --dump-outputs, and prints the line (`value`, `ms_per_step`, ratio, configuration).
+`--full` adds the per-kernel times, the rooflines, the in-run PMC passes and the CPU baseline described below.
 
 N > 1: weak scaling -- every rank encodes/decodes its own 1M-waveform shard on its own
 GPU; the only collective is the all-gather of encoded sizes (deltarice_amd/dist.py).
@@ -17,7 +21,7 @@ WORLD_SIZE/MASTER_* in the environment, rendezvous on 127.0.0.1) and exits with 
 Every rank verifies the group's world size against --gpus; the JSON line carries
 `ranks_seen`, each rank's device and each rank's encoded size.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the decode kernel (north_star's
+Rank 0 prints ONE JSON line.  With --full: `roofline` is for the decode kernel (north_star's
 target): algorithmic bytes = 2*(1+ratio) per sample over the kernel's mean duration
 measured with HIP events on the codec's stream.  `cpu_baseline` times the reference's
 own filter (oracle/_ref, built from src/deltaRice.c) -- or this repo's port of it when
@@ -62,11 +66,22 @@ def parse_args():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; "
                     "gloo only to rehearse the multi-rank flow on one GPU)")
     ap.add_argument("--debug-flags", type=int, default=0, help="kernel ablation switches (profiling only; results invalid)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times and the rooflines, the in-run PMC "
+                         "passes, the CPU baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; fixed seeded samples "
+                         "of the decoded batch, of the encoded stream and of the chunk offsets; under 64 MB)")
     ap.add_argument("--collect-traffic", dest="collect_traffic", action="store_true", default=None,
-                    help="measure roofline.traffic in THIS run: two rocprofv3 --pmc passes of this command as child processes "
-                         "before this process touches the GPU (default: on for --gpus 1 with the default workload)")
-    ap.add_argument("--no-collect", dest="collect_traffic", action="store_false", help="do not run the PMC passes")
-    return ap.parse_args()
+                    help="with --full: measure roofline.traffic in THIS run: two rocprofv3 --pmc passes of this command as child "
+                         "processes before this process touches the GPU (default: on for --gpus 1 with the default workload)")
+    ap.add_argument("--no-collect", dest="collect_traffic", action="store_false", help="with --full: do not run the PMC passes")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.collect_traffic and not a.full:
+        ap.error("--collect-traffic needs --full")
+    return a
 
 
 def _traffic_tools():
@@ -136,6 +151,30 @@ def synth(device, n_waves, L, kind, seed):
                 e[:, t].add_(e[:, t - 1], alpha=rho)
             out[w0 * L:w1 * L] = torch.round(e).to(torch.int16).reshape(-1)
     return out
+
+
+def dump_outputs(out_dir, suffix, seed, y, words, off, total_words):
+    """What the caller of a step receives -- the decoded batch y, the encoded stream words[:total_words] and the chunk offsets
+    off -- as .npy files.  Arrays beyond a cap are a sorted sample of positions drawn from `seed` alone (the stream's
+    positions also from its length), so two builds given the same arguments are compared position for position.  At most
+    2^23 decoded samples (float32), 2^21 words and 2^20 offsets (float64): 56 MiB."""
+    def sample(n, cap, salt):
+        if n <= cap:
+            return None
+        return np.sort(np.random.default_rng([seed, salt]).integers(0, n, cap))
+
+    def take(t, n, cap, salt):
+        idx = sample(n, cap, salt)
+        t = t[:n] if idx is None else t.index_select(0, torch.from_numpy(idx).to(t.device))
+        return t.cpu().numpy()
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"decoded": take(y, y.numel(), 1 << 23, 1).astype(np.float32),  # int16 samples, exact in float32
+              # the stream's uint32 words, exact in float64
+              "encoded_words": take(words, total_words, 1 << 21, 2).view(np.uint32).astype(np.float64),
+              "chunk_word_offsets": take(off, off.numel(), 1 << 20, 3).astype(np.float64)}  # < 2^53
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
 
 
 def cpu_baseline(x_host_chunks, opts, budget_s):
@@ -271,7 +310,7 @@ def main():
     traffic_kernels = traffic_note = None
     default_workload = (a.waves, a.wave_len, a.chunk_waves, a.m, a.dist) == (1_000_000, 7000, 2000, 8, "gauss")
     want = a.collect_traffic if a.collect_traffic is not None else (world == 1 and default_workload and not a.debug_flags)
-    if want and world == 1:
+    if a.full and want and world == 1:
         traffic_kernels, traffic_note = collect_traffic(a)
     import deltarice_amd as dr
     from deltarice_amd import dist as drdist
@@ -312,9 +351,6 @@ def main():
     for _ in range(a.warmup):
         step()
     plan.finish()
-    total_words = int(off[-1].item())
-    assert a.debug_flags or torch.equal(x, y), "round trip failed"  # gating, not timed
-    ratio = total_words * 4 / raw_bytes
 
     def barrier():
         if world > 1:
@@ -334,7 +370,62 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev if a.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    # what the last timed step computed: gating, not timed
+    total_words = int(off[-1].item())
+    assert a.debug_flags or torch.equal(x, y), "round trip failed"
+    ratio = total_words * 4 / raw_bytes
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, f"_rank{rank}" if rank else "", a.seed, y, words, off, total_words)
 
+    rank_row = [rank, local, total_words * 4]
+    if a.full:
+        enc_us, dec_us, full_fields = full_measurements(a, ctx, plan, step, x, ratio, raw_bytes, n_waves, L, traffic_kernels,
+                                                        traffic_note)
+        rank_row += [enc_us, dec_us]
+    # every rank reports its device, encoded size (and with --full its kernel times in microseconds): rank 0 prints what it
+    # SAW, not what it was told
+    rank_info = [rank_row]
+    if world > 1:
+        t = torch.tensor(rank_row, dtype=torch.int64, device=dev if a.backend == "nccl" else "cpu")
+        allr = torch.empty(world * t.numel(), dtype=torch.int64, device=t.device)
+        dist.all_gather_into_tensor(allr, t)
+        rank_info = allr.cpu().reshape(world, t.numel()).tolist()
+        if sorted(r[0] for r in rank_info) != list(range(world)):
+            raise SystemExit(f"bench.py: ranks seen {rank_info}, expected 0..{world - 1}")
+
+    if rank == 0:
+        res = {
+            "metric": "encode+decode GB/s (int16 in)",
+            "value": world * raw_bytes * a.steps / dt / 1e9,
+            "unit": "GB/s",
+            "n_gpus": world, "ranks_seen": len(rank_info), "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": dt / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "int16", "data": "synthetic", "full": a.full,
+            "config": {"workload": f"{n_waves}x{L} int16 {'Gaussian(sigma=10)' if a.dist == 'gauss' else 'AR(1) rho=0.95 sigma=32'}, "
+                                   f"m={a.m}, {n_chunks} chunks of {W}x{L} per GPU, encode then decode, HBM resident",
+                       "waveforms_per_gpu": n_waves, "wave_len": L, "rice_m": a.m, "chunks_per_gpu": n_chunks,
+                       "decode_impl": a.decode_impl},
+            "compression_ratio": ratio, "decode_path": plan.last_decode_path(), "encode_path": plan.last_encode_path(),
+            "rank_devices": [r[1] for r in rank_info], "rank_encoded_bytes": [r[2] for r in rank_info],
+            "backend": (a.backend if world > 1 else None),
+        }
+        if a.full:
+            # per-GPU kernel times next to the wall time: what every rank measured with HIP events on its own stream
+            res["rank_kernel_ms"] = {"encode": [r[3] / 1e3 for r in rank_info], "decode": [r[4] / 1e3 for r in rank_info]}
+            res.update(full_fields)
+            if world == 1 and a.cpu_seconds > 0:
+                nsamp = min(n_chunks, 64)
+                chunks = [x[c * W * L:(c + 1) * W * L].cpu().numpy() for c in range(nsamp)]
+                res["cpu_baseline"] = cpu_baseline(chunks, opts, a.cpu_seconds)
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(a, ctx, plan, step, x, ratio, raw_bytes, n_waves, L, traffic_kernels, traffic_note):
+    """--full: per-kernel durations and the rooflines, after the timed region (the steps run here overwrite the buffers).
+    Returns (encode kernel us, decode kernel us, the result line's fields)."""
     # --- per-kernel durations (HIP events on the codec's stream), outside the timed region
     coll = {"enc": [], "dec": []}
     for _ in range(max(3, min(a.steps, 10))):
@@ -372,62 +463,29 @@ def main():
                               + ("; dropped: the kernel sources have changed since" if stale else "")
                               + (f"; in-run collection: {traffic_note}" if traffic_note else ""))
 
-    # every rank reports its device, encoded size and kernel times (microseconds): rank 0 prints what it SAW, not what it was told
-    rank_info = [[rank, local, total_words * 4, int(round(pack_ms * 1e3)), int(round(dec_kernel_ms * 1e3))]]
-    if world > 1:
-        t = torch.tensor(rank_info[0], dtype=torch.int64, device=dev if a.backend == "nccl" else "cpu")
-        allr = torch.empty(world * 5, dtype=torch.int64, device=t.device)
-        dist.all_gather_into_tensor(allr, t)
-        rank_info = allr.cpu().reshape(world, 5).tolist()
-        if sorted(r[0] for r in rank_info) != list(range(world)):
-            raise SystemExit(f"bench.py: ranks seen {rank_info}, expected 0..{world - 1}")
-
-    if rank == 0:
-        res = {
-            "metric": "encode+decode GB/s (int16 in)",
-            "value": world * raw_bytes * a.steps / dt / 1e9,
-            "unit": "GB/s",
-            "n_gpus": world, "ranks_seen": len(rank_info), "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": dt / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "int16", "data": "synthetic",
-            "config": {"workload": f"{n_waves}x{L} int16 {'Gaussian(sigma=10)' if a.dist == 'gauss' else 'AR(1) rho=0.95 sigma=32'}, "
-                                   f"m={a.m}, {n_chunks} chunks of {W}x{L} per GPU, encode then decode, HBM resident",
-                       "waveforms_per_gpu": n_waves, "wave_len": L, "rice_m": a.m, "chunks_per_gpu": n_chunks,
-                       "decode_impl": a.decode_impl},
-            "compression_ratio": ratio, "decode_path": plan.last_decode_path(), "encode_path": plan.last_encode_path(),
-            "rank_devices": [r[1] for r in rank_info], "rank_encoded_bytes": [r[2] for r in rank_info],
-            # per-GPU kernel times next to the wall time: what every rank measured with HIP events on its own stream
-            "rank_kernel_ms": {"encode": [r[3] / 1e3 for r in rank_info], "decode": [r[4] / 1e3 for r in rank_info]},
-            "backend": (a.backend if world > 1 else None),
-            "encode_GBps": raw_bytes / (enc_ms[3] * 1e-3) / 1e9,
-            "decode_GBps": raw_bytes / (dec_ms[3] * 1e-3) / 1e9,
-            # HIP events on the codec's stream.  encode: [state memset | - | k_encode_stream];
-            # decode: [the header-chain walk, k_walk_sparse: 64 chains per chunk | k_decode_lanes]  (decode_path says which
-            # decoders ran: DRX_PATH_LANES = behind a separate walk, DRX_PATH_LANES_FUSED = the walk inside the launch)
-            "kernel_ms": {"encode_prepare": float(enc_ms[0] + enc_ms[1]), "encode_kernel": float(enc_ms[2]),
-                          "decode_prepare": float(dec_ms[0]), "decode_kernel": float(dec_ms[1])},
-            "roofline": {"bound": "hbm", "kernel": "k_decode_lanes", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
-                         # true: the two rocprofv3 --pmc child passes ran in this session BEFORE the timed region (A/B scripts
-                         # pass --no-collect; profiles/r04_notes.md has both forms measured on one box)
-                         "traffic_collected_in_run": traffic_kernels is not None,
-                         "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": dec_kernel_ms,
-                         # the same with the walk kernel in front of it counted in (it moves ~0.1 % of the bytes)
-                         "walk_ms": float(np.mean(np.array(coll["dec"])[:, 0])),
-                         "frac_with_walk": algo_bytes / ((dec_kernel_ms + float(np.mean(np.array(coll["dec"])[:, 0]))) * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-            "roofline_encode": {"bound": "hbm", "kernel": enc_kernel, "achieved": algo_bytes / (pack_ms * 1e-3) / 1e9,
-                                "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                "frac": algo_bytes / (pack_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": traffic_enc, "traffic_source": traffic_source,
-                                "kernel_ms": pack_ms},
-        }
-        if world == 1 and a.cpu_seconds > 0:
-            nsamp = min(n_chunks, 64)
-            chunks = [x[c * W * L:(c + 1) * W * L].cpu().numpy() for c in range(nsamp)]
-            res["cpu_baseline"] = cpu_baseline(chunks, opts, a.cpu_seconds)
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    fields = {
+        "encode_GBps": raw_bytes / (enc_ms[3] * 1e-3) / 1e9,
+        "decode_GBps": raw_bytes / (dec_ms[3] * 1e-3) / 1e9,
+        # HIP events on the codec's stream.  encode: [state memset | - | k_encode_stream];
+        # decode: [the header-chain walk, k_walk_sparse: 64 chains per chunk | k_decode_lanes]  (decode_path says which
+        # decoders ran: DRX_PATH_LANES = behind a separate walk, DRX_PATH_LANES_FUSED = the walk inside the launch)
+        "kernel_ms": {"encode_prepare": float(enc_ms[0] + enc_ms[1]), "encode_kernel": float(enc_ms[2]),
+                      "decode_prepare": float(dec_ms[0]), "decode_kernel": float(dec_ms[1])},
+        "roofline": {"bound": "hbm", "kernel": "k_decode_lanes", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+                     # true: the two rocprofv3 --pmc child passes ran in this session BEFORE the timed region (A/B scripts
+                     # pass --no-collect; profiles/r04_notes.md has both forms measured on one box)
+                     "traffic_collected_in_run": traffic_kernels is not None,
+                     "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": dec_kernel_ms,
+                     # the same with the walk kernel in front of it counted in (it moves ~0.1 % of the bytes)
+                     "walk_ms": float(np.mean(np.array(coll["dec"])[:, 0])),
+                     "frac_with_walk": algo_bytes / ((dec_kernel_ms + float(np.mean(np.array(coll["dec"])[:, 0]))) * 1e-3) / 1e9 / HBM_PEAK_GBPS},
+        "roofline_encode": {"bound": "hbm", "kernel": enc_kernel, "achieved": algo_bytes / (pack_ms * 1e-3) / 1e9,
+                            "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                            "frac": algo_bytes / (pack_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "traffic": traffic_enc, "traffic_source": traffic_source,
+                            "kernel_ms": pack_ms},
+    }
+    return int(round(pack_ms * 1e3)), int(round(dec_kernel_ms * 1e3)), fields
 
 
 if __name__ == "__main__":

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generates tests/golden/golden.npz from the REFERENCE's own filter.
 
-Run in the container that holds /root/reference (it needs oracle/_ref, built by
-`make -C oracle ref` from /root/reference/src/deltaRice.c, unmodified):
+Run where the reference tree is present (it needs oracle/_ref, built by
+`make -C oracle ref` from the reference's src/deltaRice.c, unmodified):
 
     python tests/golden/make_golden.py
 
@@ -108,6 +108,39 @@ def cases():
     return c
 
 
+def random_trials():
+    """The random chunks of tests/test_oracle_golden.py::test_against_compiled_reference_random, in its order."""
+    rng = np.random.default_rng(2024)
+    for trial in range(40):
+        n = int(rng.integers(200, 9000))
+        k = int(rng.integers(1, 16))
+        L = int(rng.integers(150, n + 50))
+        sigma = float(rng.choice([1, 5, 30, 300, 6000]))
+        x = rng.normal(0, sigma, n).clip(-32768, 32767).astype(np.int16)
+        opts = (1 << k, L)
+        # stay inside the reference's own allocation (SURVEY Appendix B5)
+        W = -(-n // L)
+        if W > 1 and L < 4 * W:
+            continue
+        yield x, opts
+
+
+def write_random_trials():
+    """ref_random.json: the reference's bytes for random_trials(), as hashes (the inputs are regenerated from the seed)."""
+    trials = []
+    for x, opts in random_trials():
+        words = O.ref_encode_chunk(x, opts, "omp")
+        assert np.array_equal(O.ref_decode_chunk(words, opts, "omp"), x), opts
+        trials.append({"n_samples": int(x.size), "opts": list(opts), "n_words": int(words.size),
+                       "sha256_input": hashlib.sha256(x.tobytes()).hexdigest(),
+                       "sha256_words": hashlib.sha256(words.tobytes()).hexdigest()})
+    with open(os.path.join(HERE, "ref_random.json"), "w") as f:
+        json.dump({"generator": "tests/golden/make_golden.py (write_random_trials)",
+                   "source": "reference src/deltaRice.c compiled unmodified (oracle/Makefile, -fopenmp build)",
+                   "trials": trials}, f, indent=1)
+    print(f"{len(trials)} random trials")
+
+
 def main():
     if not O.have_ref("omp"):
         sys.exit("oracle/_ref missing: run `make -C oracle ref` where /root/reference exists")
@@ -134,6 +167,7 @@ def main():
                    "source": "reference src/deltaRice.c compiled unmodified (oracle/Makefile, -fopenmp build)",
                    "cases": manifest}, f, indent=1)
     print(f"{len(manifest)} cases, {os.path.getsize(os.path.join(HERE, 'golden.npz'))} bytes")
+    write_random_trials()
 
 
 if __name__ == "__main__":

@@ -110,9 +110,17 @@ def test_install_plugin_target(tmp_path):
     assert f"Installed HDF5 filter plugins to {dest}" in r.stdout
     so = dest / "libh5deltarice.so"
     assert so.exists() and (dest.parent / "libdeltarice_hip.so").exists()
-    p = C.CDLL(str(so))  # finds the codec library through its $ORIGIN/.. run path
-    p.H5PLget_plugin_info.restype = C.c_void_p
-    assert p.H5PLget_plugin_info() == C.addressof(C.c_void_p.in_dll(p, "H5Z_DELTARICE"))
+    # in a fresh process: a plugin copy loaded earlier into this one (the GPU tests load the tree's) would provide
+    # H5Z_DELTARICE to the installed copy's H5PLget_plugin_info
+    code = textwrap.dedent(f"""
+        import ctypes as C
+        p = C.CDLL({str(so)!r})  # finds the codec library through its $ORIGIN/.. run path
+        p.H5PLget_plugin_info.restype = C.c_void_p
+        assert p.H5PLget_plugin_info() == C.addressof(C.c_void_p.in_dll(p, "H5Z_DELTARICE"))
+        print("ok")
+    """)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-3000:]
 
 
 # ---- the reference's own six tests (tests/test.py:8-83), where h5py exists -------------------------------------------

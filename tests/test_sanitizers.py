@@ -50,8 +50,9 @@ def test_filter_callback_failure_paths_under_asan_lsan(san):
     supp = os.path.join(san, "lsan.supp")
     with open(supp, "w") as f:
         f.write("leak:libamdhip64\nleak:libhsa-runtime64\nleak:libdeltarice_hip\nleak:libdrm\nleak:libnuma\nleak:libstdc++\n")
+    # the paths need a device the callback cannot use: DELTARICE_DEVICE=-1 is none on any machine, with a GPU or without
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", LSAN_OPTIONS=f"suppressions={supp}:print_suppressions=0",
-               UBSAN_OPTIONS="halt_on_error=1")
+               UBSAN_OPTIONS="halt_on_error=1", DELTARICE_DEVICE="-1")
     r = subprocess.run([os.path.join(san, "filter_failpath_asan")], env=env, capture_output=True, text=True, timeout=300)
     out = r.stdout + r.stderr
     assert r.returncode == 0 and "failpath ok" in r.stdout, out[-4000:]

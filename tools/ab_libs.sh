@@ -3,7 +3,7 @@
 A=$1; B=$2; N=${3:-3}
 for r in $(seq 1 $N); do
   for L in "$A" "$B"; do
-    DRX_LIB_PATH=$PWD/$L timeout -k 5 200 python bench.py --cpu-seconds 0 --steps 4 --warmup 1 > /tmp/abl.json || exit 1
+    DRX_LIB_PATH=$PWD/$L timeout -k 5 200 python bench.py --full --cpu-seconds 0 --steps 4 --warmup 1 > /tmp/abl.json || exit 1
     python - "$L" <<'PY'
 import sys, json
 d = json.loads(open("/tmp/abl.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ O=$R/gpurun_out/r02
 mkdir -p $O
 cd $R
 timeout -k 10 900 python3 -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest_gpu.log
-timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/bench.log | cut -c1-1500
+timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/bench.log | cut -c1-1500
 gcc -O2 -Iinclude -I/opt/rocm/include tools/host_path_bench.c -o /tmp/host_path_bench -Ldeltarice_amd -ldeltarice_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$R/deltarice_amd -Wl,-rpath,/opt/rocm/lib -lm -D__HIP_PLATFORM_AMD__ \
   && timeout -k 10 300 /tmp/host_path_bench > $O/r02_host_path_bench.txt 2>&1; cat $O/r02_host_path_bench.txt
 HDF5=${HDF5_DIR:-/opt/conda}

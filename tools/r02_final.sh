@@ -10,7 +10,7 @@ gcc -O2 tools/h5_filter_bench.c -o /tmp/h5_filter_bench -I$HDF5/include -L$HDF5/
 # ---- A: timings ----
 timeout -k 10 300 /tmp/host_path_bench > $O/r02_host_path_bench_final.txt 2>&1; cat $O/r02_host_path_bench_final.txt
 HDF5_PLUGIN_PATH=$R/deltarice_amd/plugin timeout -k 10 300 /tmp/h5_filter_bench /dev/shm/drx_bench.h5 > $O/r02_h5_filter_bench_final.txt 2>&1; cat $O/r02_h5_filter_bench_final.txt; rm -f /dev/shm/drx_bench.h5
-timeout -k 10 400 python3 bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/r02_bench.json; cut -c1-600 $O/r02_bench.json
+timeout -k 10 400 python3 bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/r02_bench.json; cut -c1-600 $O/r02_bench.json
 for w in nab1 small20 small100; do timeout -k 10 200 python3 tools/workload.py $w 2>/dev/null >> $O/r02_small_batches_final.txt; done; cut -c1-400 $O/r02_small_batches_final.txt
 for w in config5 long25 nedm noptrex; do timeout -k 10 300 python3 tools/workload.py $w 2>/dev/null > $O/r02f_$w.json; cut -c1-400 $O/r02f_$w.json; done
 timeout -k 10 500 python3 tools/bench_configs.py 2>/dev/null > $O/r02_bench_configs.txt; cat $O/r02_bench_configs.txt

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/r02h; mkdir -p $O; cd $R
 for rep in 1 2 3; do for v in "$@"; do
   echo "== $v" >> $O/ab.txt
-  DRX_LIB_PATH=$R/deltarice_amd/variants/lib_$v.so timeout -k 10 120 python3 bench.py --cpu-seconds 0 --steps 10 --warmup 3 $EXTRA 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(json.dumps({'dec_ms': d['kernel_ms']['decode_kernel'], 'enc_ms': d['kernel_ms']['encode_kernel'], 'frac': d['roofline']['frac']}))" >> $O/ab.txt
+  DRX_LIB_PATH=$R/deltarice_amd/variants/lib_$v.so timeout -k 10 120 python3 bench.py --full --cpu-seconds 0 --steps 10 --warmup 3 $EXTRA 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(json.dumps({'dec_ms': d['kernel_ms']['decode_kernel'], 'enc_ms': d['kernel_ms']['encode_kernel'], 'frac': d['roofline']['frac']}))" >> $O/ab.txt
 done; done
 python3 - <<'PY'
 import json,os,collections

@@ -7,8 +7,8 @@ R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; O=$R/gpurun_out/r04f; mkdir -p $O
 if [ "$1" = "A" ]; then
   # the headline without and with the in-run PMC passes, twice each, before any profiler has run in this session
   for i in 1 2; do
-    timeout -k 10 200 python3 bench.py --no-collect --cpu-seconds 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print('no-collect  value %.1f GB/s  encode %.3f ms  decode %.3f ms' % (d['value'], d['kernel_ms']['encode_kernel'], d['kernel_ms']['decode_kernel']))"
-    timeout -k 10 300 python3 bench.py --cpu-seconds 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print('collect     value %.1f GB/s  encode %.3f ms  decode %.3f ms  (traffic collected in run: %s)' % (d['value'], d['kernel_ms']['encode_kernel'], d['kernel_ms']['decode_kernel'], d['roofline']['traffic_collected_in_run']))"
+    timeout -k 10 200 python3 bench.py --full --no-collect --cpu-seconds 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print('no-collect  value %.1f GB/s  encode %.3f ms  decode %.3f ms' % (d['value'], d['kernel_ms']['encode_kernel'], d['kernel_ms']['decode_kernel']))"
+    timeout -k 10 300 python3 bench.py --full --cpu-seconds 0 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print('collect     value %.1f GB/s  encode %.3f ms  decode %.3f ms  (traffic collected in run: %s)' % (d['value'], d['kernel_ms']['encode_kernel'], d['kernel_ms']['decode_kernel'], d['roofline']['traffic_collected_in_run']))"
   done > $O/r04_collect_effect.txt 2>&1
   cat $O/r04_collect_effect.txt
   tools/refresh_profiles.sh r04 > $O/refresh.log 2>&1; tail -12 $O/refresh.log | cut -c1-600
