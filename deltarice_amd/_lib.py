@@ -15,6 +15,25 @@ STATUS_NAMES = {0: "DRX_OK", 1: "DRX_ERR_ARG", 2: "DRX_ERR_DEVICE", 3: "DRX_ERR_
                 4: "DRX_ERR_CORRUPT", 5: "DRX_ERR_UNSUPPORTED", 6: "DRX_ERR_NOMEM"}
 DRX_MAX_TAPS = 64
 
+# DRX_PATH_*, DRX_ENC_* and DRX_DBG_* of include/deltarice_hip.h (tests/test_abi_surface.py holds them equal)
+PATH_LANES_FUSED, PATH_LANES, PATH_BLOCKS, PATH_LONG, PATH_SIMPLE, PATH_IIR, PATH_IIR_FUSED = 1, 2, 4, 8, 16, 32, 64
+ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
+DBG_NO_LONG_PATHS = 256
+DBG_LONG_NOT_BLOCKS = 512
+DBG_NO_PARALLEL_WALKS = 2048
+DBG_NO_PIECES = 4096
+DBG_FORCE_SEGMENTS = 8192
+DBG_FORCE_PIECES = 32768
+DBG_NO_WIDE_FUSED = 65536
+DBG_RAGGED_ONE_LANES_LAUNCH = 131072
+DBG_STREAM_THREE_WGS = 262144
+DBG_FORCE_STREAM = 524288
+DBG_NW_ONE_WAVE = 1048576
+DBG_IIR_SEPARATE = 2097152
+DBG_FORCE_STREAM_SEGS = 4194304
+DBG_WALK_BY_SCAN = 8388608
+DBG_WALK_BY_CHAINS = 16777216
+
 
 class DrxOpts(C.Structure):
     _fields_ = [("rice_k", C.c_uint32), ("wave_len", C.c_int64), ("n_taps", C.c_uint32),

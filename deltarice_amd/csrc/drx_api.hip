@@ -26,9 +26,8 @@ struct drx_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     SideStream side{nullptr, nullptr, nullptr};  // independent kernels of one call (launch_decode)
-    int decode_impl = 8;   // launch_decode(): 8 = walk fused into the staged kernel, two samples per ring access
-                           // (default), 7 = the same with a separate walk kernel, 5 / 1 = one sample per ring access
-                           // (fused / separate walk), 0 = simple kernel
+    int decode_impl = 8;   // launch_decode(): 8 = walk fused into the staged kernel (default), 7 = the same with a separate
+                           // walk kernel, 0 = simple kernel
     int encode_impl = 2;  // 2: single pass, persistent (k_encode_stream) where the standard geometry applies; 1: single pass with
                           // look-back (k_encode_fused) everywhere; 0: size pass + scan + pack pass
     int profile = 0;      // bracket kernels with HIP events (drx_plan_last_timings)
@@ -78,10 +77,10 @@ struct drx_plan {
     uint32_t *d_wave_rel = nullptr;    // encode: header position relative to chunk start
     uint64_t *d_wave_off = nullptr;    // decode: absolute header position
     uint64_t *d_chunk_words = nullptr;
-    uint64_t *d_scan = nullptr;        // look-back state of the single-pass encoder + ticket
+    uint64_t *d_scan = nullptr;        // look-back state of the single-pass encoders + ticket; the decoder's granules
+    size_t scan_bytes = 0;             // ... its size
     uint32_t last_enc_path = 0;         // DRX_ENC_* of the last drx_encode
     uint64_t enc_words_per_wave = 0;   // of the plan's last encode (0: none yet)
-    bool es_segs_ok = false;           // d_scan holds k_encode_stream_segs' state for this geometry (plan_alloc)
     int32_t *d_taps = nullptr;         // general prediction filter (nullptr: delta)
     uint32_t *d_seg_bits = nullptr;    // few long waveforms: bits and bit position of every 8192-sample segment,
     uint64_t *d_seg_pos = nullptr;     // allocated by the first encode that needs them
@@ -252,11 +251,7 @@ int drx_ctx_device(const drx_ctx *c) { return c ? c->device : -1; }
 drx_status drx_ctx_set_option(drx_ctx *c, const char *key, int64_t value) {
     if (!c || !key) return DRX_ERR_ARG;
     if (!strcmp(key, "decode_impl")) {
-#ifdef DRX_LEGACY
-        if (value != 0 && value != 1 && value != 5 && value != 7 && value != 8) return DRX_ERR_ARG;
-#else
-        if (value != 0 && value != 7 && value != 8) return DRX_ERR_ARG;  // (1 / 5: one sample per ring access, -DDRX_LEGACY builds)
-#endif
+        if (value != 0 && value != 7 && value != 8) return DRX_ERR_ARG;
         c->decode_impl = (int)value;
         return DRX_OK;
     }
@@ -274,6 +269,16 @@ drx_status drx_ctx_set_option(drx_ctx *c, const char *key, int64_t value) {
         return DRX_OK;
     }
     return DRX_ERR_ARG;
+}
+
+static drx_status grow(drx_ctx *ctx, void **ptr, size_t *cap, size_t need, bool pinned) {
+    if (*cap >= need) return DRX_OK;
+    size_t want = need + need / 4 + 4096;
+    if (*ptr) { if (pinned) (void)hipHostFree(*ptr); else (void)hipFree(*ptr); *ptr = nullptr; *cap = 0; }
+    hipError_t e = pinned ? hipHostMalloc(ptr, want, hipHostMallocDefault) : hipMalloc(ptr, want);
+    if (e != hipSuccess) return fail(ctx, DRX_ERR_DEVICE, "allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
+    *cap = want;
+    return DRX_OK;
 }
 
 static void plan_free(drx_plan *p) {
@@ -312,18 +317,11 @@ static drx_status plan_alloc(drx_ctx *ctx, drx_plan *p) {  // (callers hold the 
     DRX_HIP(ctx, hipMalloc((void **)&p->d_wave_rel, W * sizeof(uint32_t)));
     DRX_HIP(ctx, hipMalloc((void **)&p->d_wave_off, W * sizeof(uint64_t)));
     DRX_HIP(ctx, hipMalloc((void **)&p->d_chunk_words, (p->G.n_chunks + 1) * sizeof(uint64_t)));
-    // (k_encode_stream: size[W] | place[W] | control; its segment form: size[T] | place[2 T] | control with T tickets, at most
-    // those of the shortest segments the dispatch may choose)
-    uint64_t scan_words = 2 * W + 192;
-    if (p->G.uniform && p->G.u_wave_len >= 64u) {
-        const uint64_t tickets = W * es_seg_shape(p->G.u_wave_len, kEsSegMinLen).tpw;
-        if (tickets < 0xffff0000ull) {
-            p->es_segs_ok = true;
-            if (3 * tickets + 192 > scan_words) scan_words = 3 * tickets + 192;
-        }
-    }
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_scan, scan_words * sizeof(uint64_t)));
-    DRX_HIP(ctx, hipMemset(p->d_scan, 0, scan_words * sizeof(uint64_t)));
+    // (every user clears what it reads on the stream before its launch.  k_encode_stream: size[W] | place[W] | control; its
+    // segment form, where it is the default choice: size[T] | place[2 T] | control with T tickets at the shortest segments)
+    uint64_t words = 2 * W + 192;
+    if (stream_segs_admits(p->G) && p->G.u_wave_len >= kEsSegsFromLen) words = std::max(words, segs_scan_words(p->G, kEsSegMinLen));
+    DRX_HIP(ctx, hipMalloc((void **)&p->d_scan, p->scan_bytes = words * sizeof(uint64_t)));
     DRX_HIP(ctx, hipMalloc((void **)&p->d_status, sizeof(DevStatus)));
     DRX_HIP(ctx, hipHostMalloc((void **)&p->h_status, sizeof(DevStatus), hipHostMallocDefault));
     memset(p->h_status, 0, sizeof(DevStatus));
@@ -350,13 +348,7 @@ static drx_status plan_alloc_scratch(drx_ctx *ctx, drx_plan *p) {
         DRX_HIP(ctx, hipMalloc((void **)&p->d_iir_state, (p->G.iir_n_tiles + 1) * sizeof(uint64_t)));
         p->G.iir_state = p->d_iir_state;
     }
-    if (p->G.uniform) {  // the pieces encoder's workgroups, where the geometry is one it can take (pieces_batch() decides per call)
-        const uint32_t L = p->G.u_wave_len;
-        const PieceShape sh = piece_shape(L, p->G.u_n_waves, p->G.k, piece_packable(L));
-        const uint64_t wgs = (uint64_t)sh.wgs * p->G.n_chunks;
-        if ((L >= kPcMinLen || piece_packable(L)) && (uint64_t)p->G.u_n_waves * sh.parts <= 0x7fffffffull && wgs <= 0x7fffffffull && p->total_samples >= 512u)
-            p->pc_wgs = wgs;
-    }
+    if (p->G.uniform && pieces_admits(p->G)) p->pc_wgs = pieces_workgroups(p->G, nullptr);  // (ragged: drx_plan_create)
     if (p->pc_wgs) DRX_HIP(ctx, hipMalloc((void **)&p->d_pc_scan, pieces_scan_words(p->G, p->pc_wgs) * sizeof(uint64_t)));
     return DRX_OK;
 }
@@ -631,9 +623,9 @@ drx_status drx_plan_read_wave_words(drx_plan *p, uint32_t *host_out) {
 // next waveform cannot start) 1.72 / 1.25; AR(1) under m = 4 (1740 words, 11 % escapes) 6.44 / 5.70; one chunk of 2000
 // waveforms 0.031 / 0.023, ten chunks 0.126 / 0.137.  A waveform's words are not known before it is coded: the plan's last
 // encode says (the same data shape comes again), and before that k + 3.5 bits per sample (the RiceParameter that suits).
-static bool stream_encoder_suits(const drx_plan *p) {
+static bool stream_encoder_suits(const drx_plan *p, int wide) {
     const Geom &G = p->G;
-    if (fused_wide(G) != 0 || G.total_waves < 8192u) return false;
+    if (wide != 0 || G.total_waves < 8192u) return false;
     const uint64_t L = G.uniform ? G.u_wave_len : G.max_wave_len64 / 64u;
     const uint64_t words = p->enc_words_per_wave ? p->enc_words_per_wave : (L * (2u * G.k + 7u)) / 64u;
     return words <= (uint64_t)kEsRingWords * 67u / 100u;
@@ -642,12 +634,9 @@ static bool stream_encoder_suits(const drx_plan *p) {
 // k_encode_stream_segs or k_encode_pieces?  Long waveforms in a batch that feeds the persistent grid's 4096 wavefronts a few
 // segments each; returns the segment length to aim at (0: not this encoder) -- what leaves a ring room for most of the next
 // segment (57 % of it, as a 7000-sample waveform of the headline does), from the bits per sample of the plan's last encode or,
-// before that, k + 3.5.  Debug flag 4194304: wherever the geometry allows, in segments of kEsSegMinLen samples (tests).
-constexpr uint64_t kEsSegsFromLen = 20480;  // WaveformLengths from here on take the segment form (16 384: k_encode_pieces 0.61 ms, this 0.66; 24 000: 0.69 / 0.61)
-static uint32_t stream_segs_target(const drx_plan *p, uint32_t dbg, int encode_impl) {
+// before that, k + 3.5.
+static uint32_t stream_segs_target(const drx_plan *p) {
     const Geom &G = p->G;
-    if (encode_impl != 2 || !p->es_segs_ok || !(G.n_taps == 0 || G.enc_fast) || (dbg & 4096u)) return 0u;
-    if (dbg & 4194304u) return kEsSegMinLen;
     const uint64_t L = G.u_wave_len;
     uint64_t min_len = kEsSegsFromLen;
 #ifdef DRX_ABLATION
@@ -662,6 +651,41 @@ static uint32_t stream_segs_target(const drx_plan *p, uint32_t dbg, int encode_i
     return (uint32_t)t;
 }
 
+// ---------------------------------------------------------------------------
+// How an encode call is routed: ONE table, first matching row wins (route_encode()).  An encoder admits the batches it can run
+// (geometry, filter, encode_impl); its default row takes those it is the best choice for.
+//   encoder     | admits                                               | default choice
+//   ------------+------------------------------------------------------+-------------------------------------------------------
+//   STREAM_SEGS | impl 2, stream_segs_admits()                         | L >= kEsSegsFromLen, 8192 segments (stream_segs_target())
+//   PIECES      | impl >= 1, pieces_admits()                           | pieces_batch(): runs of short / segments of long waveforms
+//   SEGMENTS    | impl >= 1, long_batch_admits()                       | long_batch(): short, long or few long waveforms
+//   STREAM      | impl 2, delta or fast filter                         | stream_encoder_suits(): >= 8192 waveforms, code fits a ring
+//   FUSED       | impl >= 1, delta or fast filter                      | always (fused_wide(): larger buffers for m above 8)
+//   TWO_PASS    | always                                               | always
+// Forced rows come first, in this order: DRX_DBG_FORCE_STREAM_SEGS (segments of kEsSegMinLen samples), FORCE_SEGMENTS,
+// FORCE_PIECES, FORCE_STREAM take their encoder wherever it admits the batch.  Exclusions: NO_PIECES drops the default
+// PIECES and STREAM_SEGS rows, NO_LONG_PATHS the default SEGMENTS and STREAM_SEGS rows; NO_WIDE_FUSED sets fused_wide to 0.
+// ---------------------------------------------------------------------------
+struct EncodeRoute { uint32_t enc, seg_target; int wide; };  // DRX_ENC_*, STREAM_SEGS: segment length to aim at, FUSED: fused_wide()
+
+static EncodeRoute route_encode(const drx_plan *p, int impl, uint32_t dbg) {
+    const Geom &G = p->G;
+    const int wide = (dbg & DRX_DBG_NO_WIDE_FUSED) ? 0 : fused_wide(G);
+    const bool fast = G.n_taps == 0 || G.enc_fast, single = impl >= 1;
+    const bool segs_in = impl == 2 && stream_segs_admits(G), pieces_in = single && pieces_admits(G);
+    const bool long_in = single && long_batch_admits(G), stream_in = impl == 2 && fast;
+    if ((dbg & DRX_DBG_FORCE_STREAM_SEGS) && segs_in) return {DRX_ENC_STREAM_SEGS, kEsSegMinLen, wide};
+    if ((dbg & DRX_DBG_FORCE_SEGMENTS) && long_in) return {DRX_ENC_SEGMENTS, 0, wide};
+    if ((dbg & DRX_DBG_FORCE_PIECES) && pieces_in) return {DRX_ENC_PIECES, 0, wide};
+    if ((dbg & DRX_DBG_FORCE_STREAM) && stream_in) return {DRX_ENC_STREAM, 0, wide};
+    if (segs_in && !(dbg & (DRX_DBG_NO_PIECES | DRX_DBG_NO_LONG_PATHS)))
+        if (const uint32_t t = stream_segs_target(p)) return {DRX_ENC_STREAM_SEGS, t, wide};
+    if (pieces_in && !(dbg & DRX_DBG_NO_PIECES) && pieces_batch(G, wide)) return {DRX_ENC_PIECES, 0, wide};
+    if (long_in && !(dbg & DRX_DBG_NO_LONG_PATHS) && long_batch(G)) return {DRX_ENC_SEGMENTS, 0, wide};
+    if (stream_in && stream_encoder_suits(p, wide)) return {DRX_ENC_STREAM, 0, wide};
+    return {single && fast ? DRX_ENC_FUSED : DRX_ENC_TWO_PASS, 0, wide};
+}
+
 drx_status drx_encode(drx_plan *p, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap_words,
                       uint64_t *d_chunk_word_off) {
     if (!p || !d_in || !d_out || !d_chunk_word_off) return DRX_ERR_ARG;
@@ -672,39 +696,35 @@ drx_status drx_encode(drx_plan *p, const int16_t *d_in, uint32_t *d_out, uint64_
     // what the plan's last encode measured decides this one's kernel -- read from the word the encoders write to pinned host
     // memory, so that callers that never wait for an encode (bench.py's steps) are covered without a copy or an event
     if (const uint64_t w = *(volatile uint64_t *)p->h_enc_words) p->enc_words_per_wave = p->G.total_waves ? w / p->G.total_waves : 0;
-    const bool single = ctx->encode_impl >= 1;
-    if (const uint32_t seg_target = stream_segs_target(p, ctx->debug_flags, ctx->encode_impl)) {
-        DRX_HIP(ctx, launch_encode_stream_segs(p->G, seg_target, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                               p->d_scan, p->d_status, ctx->profile ? p->ev : nullptr, ctx->stream));
-        p->last_enc_path = DRX_ENC_STREAM_SEGS;
-    } else if (single && p->d_pc_scan && pieces_batch(p->G)) {
+    const EncodeRoute R = route_encode(p, ctx->encode_impl, ctx->debug_flags);
+    hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
+    switch (R.enc) {
+    case DRX_ENC_STREAM_SEGS:  // (shorter segments than the plan was sized for: a forced route; hipFree waits for the device)
+        if (const drx_status st = grow(ctx, (void **)&p->d_scan, &p->scan_bytes, segs_scan_words(p->G, R.seg_target) * sizeof(uint64_t), false)) return st;
+        DRX_HIP(ctx, launch_encode_stream_segs(p->G, R.seg_target, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
+                                               p->d_scan, p->d_status, ev, ctx->stream)); break;
+    case DRX_ENC_PIECES:
         DRX_HIP(ctx, launch_encode_pieces(p->G, d_in, p->total_samples, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                          p->d_pc_scan, p->pc_wgs, p->d_status, ctx->profile ? p->ev : nullptr, ctx->stream));
-        p->last_enc_path = DRX_ENC_PIECES;
-    } else if (single && long_batch(p->G) && !(ctx->debug_flags & 256u)) {
-        if (!p->d_seg_bits) {  // only when a diagnostic debug_flags value forces this path on a geometry that does not take it
+                                          p->d_pc_scan, p->pc_wgs, p->d_status, ev, ctx->stream)); break;
+    case DRX_ENC_SEGMENTS:
+        if (!p->d_seg_bits) {  // (a route the plan was not sized for)
             const uint64_t units = long_batch_units(p->G);
             DRX_HIP(ctx, hipMalloc((void **)&p->d_seg_bits, units * sizeof(uint32_t)));
             DRX_HIP(ctx, hipMalloc((void **)&p->d_seg_pos, units * sizeof(uint64_t)));
         }
         DRX_HIP(ctx, launch_encode_long(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words, p->d_wave_rel,
-                                        p->d_chunk_words, p->d_seg_bits, p->d_seg_pos, p->d_status,
-                                        ctx->profile ? p->ev : nullptr, ctx->stream));
-        p->last_enc_path = DRX_ENC_SEGMENTS;
-    } else if (ctx->encode_impl == 2 && (p->G.n_taps == 0 || p->G.enc_fast) && (stream_encoder_suits(p) || (ctx->debug_flags & 524288u))) {
+                                        p->d_chunk_words, p->d_seg_bits, p->d_seg_pos, p->d_status, ev, ctx->stream)); break;
+    case DRX_ENC_STREAM:
         DRX_HIP(ctx, launch_encode_stream(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                          p->d_scan, p->d_status, ctx->profile ? p->ev : nullptr, ctx->stream));
-        p->last_enc_path = DRX_ENC_STREAM;
-    } else if (single && (p->G.n_taps == 0 || p->G.enc_fast)) {
-        DRX_HIP(ctx, launch_encode_fused(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                         p->d_scan, p->d_status, ctx->profile ? p->ev : nullptr, ctx->stream));
-        p->last_enc_path = DRX_ENC_FUSED;
-    } else {
+                                          p->d_scan, p->d_status, ev, ctx->stream)); break;
+    case DRX_ENC_FUSED:
+        DRX_HIP(ctx, launch_encode_fused(p->G, R.wide, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
+                                         p->d_scan, p->d_status, ev, ctx->stream)); break;
+    default:
         DRX_HIP(ctx, launch_encode(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                   p->d_wave_rel, p->d_chunk_words, p->d_status, ctx->profile ? p->ev : nullptr,
-                                   ctx->stream));
-        p->last_enc_path = DRX_ENC_TWO_PASS;
+                                   p->d_wave_rel, p->d_chunk_words, p->d_status, ev, ctx->stream));
     }
+    p->last_enc_path = R.enc;
     p->ev_valid = ctx->profile != 0;
     p->last_was_encode = true;
     return DRX_OK;
@@ -810,16 +830,6 @@ drx_status drx_plan_finish(drx_plan *p, uint64_t *total_words) {
 // ---------------------------------------------------------------------------
 // one chunk through host memory: the body of the H5Z callback
 // ---------------------------------------------------------------------------
-static drx_status grow(drx_ctx *ctx, void **ptr, size_t *cap, size_t need, bool pinned) {
-    if (*cap >= need) return DRX_OK;
-    size_t want = need + need / 4 + 4096;
-    if (*ptr) { if (pinned) (void)hipHostFree(*ptr); else (void)hipFree(*ptr); *ptr = nullptr; *cap = 0; }
-    hipError_t e = pinned ? hipHostMalloc(ptr, want, hipHostMallocDefault) : hipMalloc(ptr, want);
-    if (e != hipSuccess) return fail(ctx, DRX_ERR_DEVICE, "allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
-    *cap = want;
-    return DRX_OK;
-}
-
 drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts, const unsigned *cd_values,
                                  const void *in, size_t nbytes, void **out, size_t *out_bytes) {
     if (!ctx || !in || !out || !out_bytes) return DRX_ERR_ARG;

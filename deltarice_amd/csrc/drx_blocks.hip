@@ -1103,12 +1103,12 @@ hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in
 #endif
     // General filters: the inverse filter inside this kernel (FUSE) where its state can pass from a run's last block to the next
     // run's first without a chain of waits, i.e. where every launch has at least as many waveforms as resident workgroups (the
-    // condition under which runs are longer than one block); else residuals now and k_iir_tiles behind (debug flag 2097152: always).
+    // condition under which runs are longer than one block); else residuals now and k_iir_tiles behind (DRX_DBG_IIR_SEPARATE: always).
     auto resident_of = [](int nt) { return 256u * (nt == 64 ? 12u : (nt == 128 ? 6u : 3u)); };
     // (General filters run at 128 or 256 lanes per block when fused and at 256 when not: 12 of the 36 instantiations of the
     // kernel are not built; a block larger than the class's choice costs short waveforms some empty lanes, nothing else.)
     auto nt_gen = [](int nt) { return nt < 128 ? 128 : nt; };
-    bool fuse = resid && G.blk_iir_tab != nullptr && !(G.dbg & 2097152u);
+    bool fuse = resid && G.blk_iir_tab != nullptr && !(G.dbg & DRX_DBG_IIR_SEPARATE);
     if (fuse) {
         if (G.uniform) fuse = G.total_waves >= resident_of(nt_gen(blocks_nt(G)));
         else

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kLongThreads) void k_decode_long(Geom G, const uint
                 const uint32_t d = (z >> 1) ^ (0u - (z & 1u));
                 const uint32_t s2 = sacc + d;
                 if (EMIT) {
-                    if (act && idx + c < len && !(kAblate && (G.dbg & 16384u))) {  // (16384: ablation, no stores)
+                    if (act && idx + c < len && !(kAblate && (G.dbg & kAbLongNoStores))) {
                         const uint32_t i = idx + c;
                         if (((i + par4) & 1u) == 0u) {  // low half of an aligned dword: wait for the next sample
                             held = s2 & 0xffffu;
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(kLongThreads) void k_decode_long(Geom G, const uint
 //               128-byte lines (T = 64).  tools/ubench_store.hip: 16-byte stores reach 5.5 TB/s only
 //               when every contiguous run is a whole line; 64-byte aligned runs give 4.2 TB/s and
 //               runs that straddle lines 2.6-3.3 TB/s whatever their length.
-//   PAIR        two samples per ring access: three words = a 64-bit window always hold two codes
+//   pairs       two samples per ring access: three words = a 64-bit window always hold two codes
 //               (2 x 25 bits); the second sample's window is v_alignbit(winA, winB, -len1).  One LDS
 //               round trip on the dependent chain per two samples.
 //   FUSED       the header-chain walk runs inside the same launch: workgroups take a ticket; the first
@@ -360,7 +360,7 @@ __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
-template <int RW, int LW, int T, int GS, bool FUSED, bool PAIR = false, bool GEN = false, int NW = 1>
+template <int RW, int LW, int T, int GS, bool FUSED, bool GEN = false, int NW = 1>
 __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_decode_lanes(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
                                                      const uint64_t *__restrict__ chunk_word_off,
                                                      uint64_t *__restrict__ wave_off,
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
 #define DRX_DEC_OPAD 4
 #endif
     constexpr bool STG = NW > 1;
-    static_assert(!STG || (PAIR && T == 64 && GS == 16), "the staged flush is built for two samples per access and 64-sample rounds");
+    static_assert(!STG || (T == 64 && GS == 16), "the staged flush is built for 64-sample rounds");
     constexpr int OSW = T / 2 + (STG ? 0 : DRX_DEC_OPAD);  // output row stride in words (16- or 8-byte aligned rows)
     static_assert(OSW % 2 == 0, "rows are read in 8- or 16-byte pieces");
     constexpr int PPS = T / 8;      // 16-byte pieces per stream per round
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
     constexpr uint32_t WMASK = (1u << 27) - 1u;
     constexpr uint32_t NEED_AT = GS + 2;                                   // must refill below this many words
     static_assert(T % GS == 0 && RW - LW >= GS + 2, "round length / ring slack");
-    // row r: word w with RW - (w mod RW) == r; row 0 mirrors row RW and row -1 mirrors row RW - 1 (PAIR reads
+    // row r: word w with RW - (w mod RW) == r; row 0 mirrors row RW and row -1 mirrors row RW - 1 (a pair reads
     // three consecutive words: rows r + 1, r, r - 1)
     __shared__ uint32_t ring_mem[NW][(RW + 2) * 64];
     const int wv = STG ? (int)(threadIdx.x >> 6) : 0;
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
     // order, so the holder's reads are done once its s_waitcnt has passed; the holder never waits for another wavefront.
     auto flush_lock = [&]() __attribute__((always_inline)) {
         if constexpr (STG) {
-            if (kAblate && (G.dbg & 8u)) return;  // (ablation: no lock -- the samples of neighbouring wavefronts mix)
+            if (kAblate && (G.dbg & kAbNoLock)) return;  // (ablation: no lock -- the samples of neighbouring wavefronts mix)
             for (;;) {
                 uint32_t got = 1u;
                 if (lane == 0) {
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
     };
     auto flush_unlock = [&]() __attribute__((always_inline)) {
         if constexpr (STG) {
-            if (kAblate && (G.dbg & 8u)) return;
+            if (kAblate && (G.dbg & kAbNoLock)) return;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of the buffer has returned
             if (lane == 0) __hip_atomic_store(&fl_lock, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -648,7 +648,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
         }
         if (r0 == (uint32_t)RW) {
             myring[0] = v[0].x;
-            if (PAIR) myring[-64] = v[0].y;
+            myring[-64] = v[0].y;
         }
         flw += (uint32_t)LW;
     };
@@ -668,7 +668,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
             const uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
             const bool more = flw < endw;
             if (!__any(more && avail < NEED_AT)) break;
-            if (more && avail <= (uint32_t)(RW - LW) && !(kAblate && (G.dbg & 2u))) {
+            if (more && avail <= (uint32_t)(RW - LW) && !(kAblate && (G.dbg & kAbNoLoads))) {
                 uint4 v[NV];
                 load_piece(v);
                 store_piece(v);
@@ -684,7 +684,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
         for (int i = 0; i < RW / LW; ++i) {
             if (__ballot(flw < endw && flw + (uint32_t)LW <= s0 + (uint32_t)RW) == 0) break;
             if (flw < endw && flw + (uint32_t)LW <= s0 + (uint32_t)RW) {
-                if (!(kAblate && (G.dbg & 2u))) { load_piece(v); store_piece(v); } else flw += (uint32_t)LW;
+                if (!(kAblate && (G.dbg & kAbNoLoads))) { load_piece(v); store_piece(v); } else flw += (uint32_t)LW;
             }
         }
         wave_sync();
@@ -721,7 +721,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
         constexpr bool FIRST = decltype(first_tag)::value;
         constexpr bool EDGE = decltype(edge_tag)::value;  // tcur + u is the step index; capture Q_end
         constexpr int TGC = decltype(stg_tag)::value;     // >= 0: tg at compile time, samples go to stg[] (interior rounds of STG)
-        if (PAIR && !FIRST) {
+        if (!FIRST) {
             // two samples per ring access: a 64-bit window (three words) always holds two codes (2 x 25 bits),
             // so the second sample's window is one v_alignbit away from the first one's length -- one LDS
             // round trip on the dependent chain per two samples instead of one per sample
@@ -771,18 +771,13 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
             const uint32_t rem = __builtin_amdgcn_ubfe(win, 32u - used, kk);
             const uint32_t z = (q << kk) + rem;  // escape: 8 << 16 stays above bit 15
             const int32_t d = (int32_t)(z >> 1) ^ -(int32_t)(z & 1u);
-            if (FIRST) {
-                const bool act = (uint32_t)(tg + u) >= phi;
-                const int32_t o1 = acc, o2 = y2, o3 = y3;
-                advance(d);
-                acc = act ? acc : o1;
-                y2 = act ? y2 : o2;
-                y3 = act ? y3 : o3;
-                Q = act ? Q - used : Q;
-            } else {
-                advance(d);
-                Q -= used;
-            }
+            const bool act = (uint32_t)(tg + u) >= phi;  // (the first round: one sample per access, lanes start at phi)
+            const int32_t o1 = acc, o2 = y2, o3 = y3;
+            advance(d);
+            acc = act ? acc : o1;
+            y2 = act ? y2 : o2;
+            y3 = act ? y3 : o3;
+            Q = act ? Q - used : Q;
             if constexpr (EDGE) Q_end = (tcur + (uint32_t)u + 1u == hi_step) ? Q : Q_end;
             if constexpr (TGC >= 0) {  // (two steps fill a staging dword)
                 if ((u & 1) == 0) stg[(TGC + u) / 2] = (uint32_t)acc & 0xffffu;
@@ -810,7 +805,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
         }
     };
     auto write_out = [&](uint32_t t0) __attribute__((always_inline)) {
-        if (kNoObuf || (kAblate && (G.dbg & 1u))) return;
+        if (kNoObuf || (kAblate && (G.dbg & kAbNoStores))) return;
         if (t0 >= lo_max && t0 + T <= hi_min) {  // interior round: whole aligned lines only
 #pragma unroll
             for (int i = 0; i < PPS; ++i) {
@@ -859,7 +854,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
     auto stg_edge_out = [&](uint32_t t0) __attribute__((always_inline)) {  // STG: an edge round's masked write-out
         uint4 ov[PPS];
         flush_exchange(ov);
-        if (kAblate && (G.dbg & 1u)) return;
+        if (kAblate && (G.dbg & kAbNoStores)) return;
         if (t0 >= lo_max && t0 + T <= hi_min) {
 #pragma unroll
             for (int i = 0; i < PPS; ++i) store16(stg_line(i, t0), ov[i]);
@@ -928,7 +923,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
     uint32_t t0 = T;
     for (; t0 < steps && !(t0 >= lo_max && t0 + T <= hi_min); t0 += T) edge_round(t0);
 
-    const uint32_t min_words = (kAblate && (G.dbg & 4u)) ? 0u : ((uint32_t)T * (k + 1u)) >> 5;
+    const uint32_t min_words = (kAblate && (G.dbg & kAbNoMinConsume)) ? 0u : ((uint32_t)T * (k + 1u)) >> 5;
     uint4 pv0[NV], pv1[NV];               // pieces in flight
     bool pneed0 = false, pneed1 = false;  // this lane has them in flight
     set_limits();
@@ -983,7 +978,7 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
             // samples of at least k + 1 bits each, i.e. consumed min_words more words
             const uint32_t mc = (t0 + 2u * T <= hi_min && t0 + T < steps) ? min_words : 0u;
             const uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
-            pneed0 = (flw < endw) && avail + (uint32_t)LW <= (uint32_t)RW + mc && !(kAblate && (G.dbg & 2u));
+            pneed0 = (flw < endw) && avail + (uint32_t)LW <= (uint32_t)RW + mc && !(kAblate && (G.dbg & kAbNoLoads));
             pneed1 = pneed0 && (flw + (uint32_t)LW < endw) && avail + 2u * (uint32_t)LW <= (uint32_t)RW + mc;
             if (pneed0) load_piece(pv0);
             if (pneed1) load_piece(pv1, (uint32_t)LW);
@@ -991,11 +986,11 @@ __global__ __launch_bounds__(64 * NW, NW == 1 ? 1 : (NW == 4 ? 2 : 3)) void k_de
         if constexpr (STG) {
             uint4 ov[PPS];
             flush_exchange(ov);
-            if (!(kAblate && (G.dbg & 1u))) {
+            if (!(kAblate && (G.dbg & kAbNoStores))) {
 #pragma unroll
                 for (int i = 0; i < PPS; ++i) store16(stg_line(i, t0), ov[i]);
             }
-        } else if (!(kNoObuf || (kAblate && (G.dbg & 1u)))) {
+        } else if (!(kNoObuf || (kAblate && (G.dbg & kAbNoStores)))) {
 #pragma unroll
             for (int i = 0; i < PPS; ++i) {  // whole aligned lines only
                 const int st = i * SPI + lane / PPS, p = lane % PPS;
@@ -1094,8 +1089,8 @@ static unsigned dec_lds_pad() {
 //   --------------+-----------------------------------------------------------------------------------+--------------------------------
 //   SIMPLE        | decode_impl 0; a filter the fast kernels do not take (> 4 taps, taps[0] != +-1)   | parallel walks / serial
 //   BLOCKS (+IIR) | few long waveforms (blocks_batch(): geometry and cost), delta or a fast filter    | parallel walks / serial
-//   LONG          | uniform, delta, long_waveform_batch() and not BLOCKS; flag 512                    | parallel walks / serial
-//   LANES fused   | decode_impl 8 (5), not a batch the parallel walks take (short waveforms in many    | inside the launch
+//   LONG          | uniform, delta, long_waveform_batch() and not BLOCKS; LONG_NOT_BLOCKS             | parallel walks / serial
+//   LANES fused   | decode_impl 8, not a batch the parallel walks take (short waveforms in many    | inside the launch
 //                 | chunks, chunks of more than 8192 or fewer than 8 waveforms), grid not mostly idle |
 //   LANES         | everything else; ragged batches behind both parallel walks: two launches          | parallel walks / serial
 //
@@ -1105,30 +1100,29 @@ static unsigned dec_lds_pad() {
 //                 | chunk without reading it -- the headline batch too), the long-waveform chunks of a small ragged batch
 //   block-parallel| bw_walk_blocks_max(): few chunks of many short waveforms (uniform), the short-waveform chunks of a small ragged batch
 //   serial        | otherwise: LDS block walkers (WaveformLength <= 2048) / scalar chains, one launch in front of the decoder
-// Flags: 256 never BLOCKS / LONG, 512 LONG instead of BLOCKS, 2048 never the parallel walks, 131072 one lanes launch behind both walks.
+//   chunk-wide by chains (k_walk_sparse), or by reading the chunks (k_pw_scan + k_walk_parallel) for one to four chunks of 64 ...
+//   kPwMaxWaves waveforms.  Ragged batches behind both walks: a lanes launch behind each (split).
+// Flags (DRX_DBG_*): NO_LONG_PATHS never BLOCKS / LONG, LONG_NOT_BLOCKS LONG instead of BLOCKS, NO_PARALLEL_WALKS, WALK_BY_SCAN
+// and WALK_BY_CHAINS (where the other form is the default), RAGGED_ONE_LANES_LAUNCH.
 // ---------------------------------------------------------------------------
 enum class Dec { Simple, Blocks, Long, LanesFused, Lanes };
 enum class Walk { None, InLaunch, Parallel, Serial };
 struct DecodeRoute {
     Dec dec;
     Walk walk;
-    bool pair;            // two samples per ring access (decode_impl 7 / 8; 1 / 5 are legacy builds')
     bool gen;             // a general prediction filter
     bool use_pw, use_bw;  // Walk::Parallel: the chunk-wide walk, the block-parallel walk
+    bool pw_chains;       // ... the chunk-wide walk by chains, not by reading the chunks
+    bool split;           // ... ragged, behind both walks: two lanes launches
     uint32_t bw_blocks_max;
 };
 
-static DecodeRoute route_decode(const Geom &G, int impl, bool tables_ready, bool have_pw, bool have_blk) {
+static DecodeRoute route_decode(const Geom &G, int impl, bool tables_ready, bool have_pw, bool have_blk, bool have_side) {
     DecodeRoute R{};
     R.gen = G.n_taps != 0;
     const bool simple = impl == 0 || (R.gen && !G.fast_taps);
-#ifdef DRX_LEGACY
-    R.pair = R.gen ? true : (impl == 7 || impl == 8);  // (general filters exist in the two-samples form only)
-#else
-    R.pair = true;
-#endif
-    const bool want_fused = !tables_ready && (impl == 5 || impl == 8);
-    const bool no_par = tables_ready || !have_pw || (G.dbg & 2048u);
+    const bool want_fused = !tables_ready && impl == 8;
+    const bool no_par = tables_ready || !have_pw || (G.dbg & DRX_DBG_NO_PARALLEL_WALKS);
     const bool par_walk = !no_par && G.uniform && G.n_chunks <= kSwMaxChunks && G.u_n_waves <= kSwMaxWaves && G.u_n_waves >= kSwMinWaves &&
                           G.u_wave_len > kWalkShortLen;
     R.bw_blocks_max = bw_walk_blocks_max(G);
@@ -1136,14 +1130,21 @@ static DecodeRoute route_decode(const Geom &G, int impl, bool tables_ready, bool
     const bool rag_par = !no_par && !G.uniform && G.rag_par;
     R.use_pw = par_walk || (rag_par && G.n_long);
     R.use_bw = bw_walk || (rag_par && G.n_short);
-    const bool blocks = !simple && !(G.dbg & (256u | 512u)) && have_blk && blocks_batch(G) && (!R.gen || (G.iir_tab && G.iir_state));
-    const bool longp = !simple && !blocks && !R.gen && !(G.dbg & 256u) && G.uniform && long_waveform_batch(G.total_waves, G.u_wave_len);
+    const bool blocks = !simple && !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS)) && have_blk && blocks_batch(G) && (!R.gen || (G.iir_tab && G.iir_state));
+    const bool longp = !simple && !blocks && !R.gen && !(G.dbg & DRX_DBG_NO_LONG_PATHS) && G.uniform && long_waveform_batch(G.total_waves, G.u_wave_len);
     // ragged: the group-major grid of the fused launch has max_groups tickets per chunk; not when most of them would be idle
     const bool sparse = !G.uniform && (uint64_t)G.n_chunks * G.max_groups > 8ull * ((G.total_waves + 63u) / 64u) + 4096ull;
     R.dec = simple ? Dec::Simple : (blocks ? Dec::Blocks : (longp ? Dec::Long : Dec::Lanes));
     const bool parallel = par_walk || bw_walk || rag_par;
     if (R.dec == Dec::Lanes && want_fused && !sparse && !parallel) R.dec = Dec::LanesFused;
     R.walk = tables_ready ? Walk::None : (R.dec == Dec::LanesFused ? Walk::InLaunch : (parallel ? Walk::Parallel : Walk::Serial));
+    // (up to four chunks the scan form is quicker: 128 workgroups read one chunk in 11 us, where a chain is 31 dependent loads;
+    // so for ragged chunks of a few very long waveforms: a start costs half a waveform's code in reads)
+    const bool few_waves = G.uniform && (G.u_n_waves < 64u || G.u_n_waves > kPwMaxWaves);  // (outside the scan form's range)
+    const bool chains_suit = (G.dbg & DRX_DBG_WALK_BY_CHAINS) || few_waves || ((G.uniform ? G.n_chunks : G.n_long) > 4u && (G.uniform || G.rag_pw_min_waves >= 64u));
+    R.pw_chains = (!(G.dbg & DRX_DBG_WALK_BY_SCAN) && chains_suit) || G.n_chunks > kPwMaxChunks || few_waves;
+    R.split = R.walk == Walk::Parallel && R.use_pw && R.use_bw && have_side && R.dec == Dec::Lanes && G.rag_order && G.rag_groups_long &&
+              G.rag_groups_long < G.rag_groups && !(G.dbg & DRX_DBG_RAGGED_ONE_LANES_LAUNCH);
     return R;
 }
 
@@ -1161,7 +1162,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
     // the chunk is in flight to the device; the side-band decode derives them from the caller's table): no walk
     const bool tables_ready = impl >= 100;
     if (tables_ready) impl -= 100;
-    const DecodeRoute R = route_decode(G, impl, tables_ready, d_pw != nullptr, d_blk != nullptr);
+    const DecodeRoute R = route_decode(G, impl, tables_ready, d_pw != nullptr, d_blk != nullptr, side && side->s);
     const bool gen = R.gen;
     const unsigned nb_plain = blocks_for(G.total_waves, 64);
 
@@ -1169,13 +1170,9 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
     auto launch_lanes = [&](const Geom &Gv, unsigned nb, hipStream_t st_) {
         path |= 2u;  // DRX_PATH_LANES
         if (gen)
-            k_decode_lanes<64, DRX_DEC_LW, DRX_DEC_T, 16, false, true, true><<<nb, 64, lpad, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
-        else if (R.pair)
             k_decode_lanes<64, DRX_DEC_LW, DRX_DEC_T, 16, false, true><<<nb, 64, lpad, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
-#ifdef DRX_LEGACY
         else
             k_decode_lanes<64, DRX_DEC_LW, DRX_DEC_T, 16, false><<<nb, 64, lpad, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
-#endif
     };
 
     // ---- the walk ----
@@ -1187,12 +1184,11 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
     } else if (R.walk == Walk::Parallel) {
         // scratch: uint2 cand[n_chunks * kPwCap] | uint32 count[n_chunks] | pw_fail[n_chunks] | bw_fail[n_chunks] |
         //          BwBlock info[n_bw * bw_blocks]   (cand .. pw_fail only where the chunk-wide walk is used)
-        const bool use_pw = R.use_pw, use_bw = R.use_bw;
         const uint32_t *pw_list = G.uniform ? nullptr : G.walk_long, *bw_list = G.uniform ? nullptr : G.walk_short;
         const uint32_t n_pw = G.uniform ? (uint32_t)G.n_chunks : G.n_long, n_bw = G.uniform ? (uint32_t)G.n_chunks : G.n_short;
         const uint32_t bwb = G.uniform ? R.bw_blocks_max : G.rag_bw_blocks_max;
         uint2 *cand = reinterpret_cast<uint2 *>(d_pw);
-        const bool have_cand = use_pw && G.n_chunks <= kPwMaxChunks;  // (par_walk_scratch_bytes())
+        const bool have_cand = R.use_pw && G.n_chunks <= kPwMaxChunks;  // (par_walk_scratch_bytes())
         uint32_t *cnt = reinterpret_cast<uint32_t *>(cand + (have_cand ? G.n_chunks * kPwStride : 0));
         uint32_t *pw_fail = cnt + G.n_chunks, *bw_fail = pw_fail + G.n_chunks;
         BwBlock *info = reinterpret_cast<BwBlock *>(bw_fail + G.n_chunks + (G.n_chunks & 1u));
@@ -1200,19 +1196,14 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         if (e != hipSuccess) return e;
         // a ragged batch has both kinds of chunk and the two walks touch different chunks: the chunk-wide walk goes to the
         // context's side stream while the block walk runs here (config 5: 0.18 ms of 0.6 off the critical path)
-        const bool forked = use_pw && use_bw && side && side->s;
+        const bool forked = R.use_pw && R.use_bw && side && side->s;
         hipStream_t spw = forked ? side->s : s;
         if (forked) {
             if ((e = hipEventRecord(side->fork, s)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(side->s, side->fork, 0)) != hipSuccess) return e;
         }
-        if (use_pw) {
-            // (up to four chunks the scan form is quicker: 128 workgroups read one chunk in 11 us, where a chain is 31 dependent loads)
-            // ... and chunks of a few very long waveforms (ragged batches): a start costs half a waveform's code in reads
-            // (debug flag 16777216: chains whatever the batch -- the tests' small batches)
-            const bool few_waves = G.uniform && (G.u_n_waves < 64u || G.u_n_waves > kPwMaxWaves);  // (outside the scan form's range)
-            const bool chains_suit = (G.dbg & 16777216u) || few_waves || (n_pw > 4u && (G.uniform || G.rag_pw_min_waves >= 64u));
-            if ((!(G.dbg & 8388608u) && chains_suit) || !have_cand || few_waves) {
+        if (R.use_pw) {
+            if (R.pw_chains) {
                 // 64 chains per chunk chased in parallel from starts found by looking forward from 64 cuts (drx_walk.h): the chunk is
                 // not read
                 const unsigned sw_threads = (G.uniform && G.u_n_waves < 256u) ? 256u : (unsigned)kSwThreads;  // (few chains: few wavefronts)
@@ -1228,9 +1219,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         // ... and so does the decoding of the long-waveform chunks, whose tables are complete long before the block walk is
         // through: their wavefronts (the first rag_groups_long of the longest-first order) are launched behind the
         // chunk-wide walk on the side stream, the rest here behind the block walk
-        const bool split = forked && R.dec == Dec::Lanes && G.rag_order && G.rag_groups_long && G.rag_groups_long < G.rag_groups &&
-                           !(G.dbg & 131072u);
-        if (split) {
+        if (R.split) {
             Geom Gl = G;
             Gl.rag_groups = G.rag_groups_long;
             launch_lanes(Gl, Gl.rag_groups, spw);
@@ -1240,7 +1229,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
             (void)hipStreamSynchronize(side->s);
             return e;
         }
-        if (use_bw) {
+        if (R.use_bw) {
             // block size: the smallest that exceeds every listed chunk's max_words; wavefronts: what the LDS lets the chip hold
             const uint32_t max_len = G.uniform ? G.u_wave_len : kWalkShortLen;
             const uint32_t max_full = (uint32_t)(((uint64_t)max_len * 25u + 31u) >> 5);
@@ -1267,7 +1256,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
             else run_bw(std::integral_constant<uint32_t, 4096>{}, 7u);
             k_walk_block_only<<<(unsigned)G.n_chunks, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, bw_fail);
         }
-        if (split) {
+        if (R.split) {
             mark(ev, 1, s);  // (the block walk's end; the other stream is decoding already)
             Geom Gs = G;
             Gs.rag_order = G.rag_order + G.rag_groups_long;
@@ -1323,20 +1312,16 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         constexpr int NWs = DRX_DEC_NW;
         const bool short_walk = G.uniform ? G.u_wave_len <= kWalkShortLen : G.n_short != 0;
         const bool lines_near = G.uniform ? (uint64_t)G.u_wave_len * 64u < (1ull << 31) : G.max_wave_len64 < (1ull << 31);
-        if (NWs > 1 && R.pair && !short_walk && lines_near && !(G.dbg & 1048576u)) {
+        if (NWs > 1 && !short_walk && lines_near && !(G.dbg & DRX_DBG_NW_ONE_WAVE)) {
             const unsigned nwg = (nb + NWs - 1u) / NWs;
             if (gen)
-                k_decode_lanes<64, DRX_DEC_LW, 64, 16, true, true, true, NWs><<<nwg, 64 * NWs, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
+                k_decode_lanes<64, DRX_DEC_LW, 64, 16, true, true, NWs><<<nwg, 64 * NWs, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
             else
-                k_decode_lanes<64, DRX_DEC_LW, 64, 16, true, true, false, NWs><<<nwg, 64 * NWs, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
+                k_decode_lanes<64, DRX_DEC_LW, 64, 16, true, false, NWs><<<nwg, 64 * NWs, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
         } else if (gen)
-            k_decode_lanes<64, DRX_DEC_LW, DRX_DEC_T, 16, true, true, true><<<nb, 64, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
-        else if (R.pair)
             k_decode_lanes<64, DRX_DEC_LW, DRX_DEC_T, 16, true, true><<<nb, 64, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
-#ifdef DRX_LEGACY
         else
             k_decode_lanes<64, DRX_DEC_LW, DRX_DEC_T, 16, true><<<nb, 64, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
-#endif
         break;
     }
     case Dec::Blocks: {
@@ -1355,7 +1340,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         }
         break;
     }
-    case Dec::Long:  // (flag 512, or a long-waveform batch the block decoder does not take: one workgroup per waveform)
+    case Dec::Long:  // (LONG_NOT_BLOCKS, or a long-waveform batch the block decoder does not take: one workgroup per waveform)
         path |= 8u;  // DRX_PATH_LONG
         k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, nullptr, nullptr, 0u);
         break;

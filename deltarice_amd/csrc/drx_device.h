@@ -9,13 +9,16 @@
 
 namespace drx {
 
-// Ablation switches inside the hot loops (Geom::dbg bits 1, 2, 4, 16, 32, 64, 128) exist only in builds made with
-// -DDRX_ABLATION (loaded through DRX_LIB_PATH for A/B timing); the shipped kernels carry none of those branches.
+// Ablation switches inside the hot loops (Geom::dbg bits beside DRX_DBG_*; results invalid), only in -DDRX_ABLATION builds (A/B
+// timing through DRX_LIB_PATH).  decode: no output / long-waveform stores, no stream loads, pieces requested without counting on a
+// round's minimum consumption, no lock of the shared buffer; encode: per-code LDS emission, no emission, no copy-out, no look-back.
 #ifdef DRX_ABLATION
 constexpr bool kAblate = true;
 #else
 constexpr bool kAblate = false;
 #endif
+constexpr uint32_t kAbNoStores = 1, kAbLongNoStores = 16384, kAbNoLoads = 2, kAbNoMinConsume = 4, kAbNoLock = 8;
+constexpr uint32_t kAbLdsEmit = 16, kAbNoEmit = 32, kAbNoCopyOut = 64, kAbNoLookback = 128, kAbSparsePlace = 1024;
 
 // ---------------------------------------------------------------------------
 // small device helpers

@@ -417,9 +417,9 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
         if (FULLT) concat_codes(c, cw);  // independent of the scan: fills its DPP wait states
         const uint32_t incl = wave_incl_scan_dpp(lane_bits);
         const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        if (kAblate && (G.dbg & 32u)) {  // ablation: no emission
+        if (kAblate && (G.dbg & kAbNoEmit)) {  // ablation: no emission
         } else if (fits && ((P + tile_bits + 31u) >> 5) < (uint64_t)kEncCapWords) {
-            if (FULLT && !(kAblate && (G.dbg & 16u)) && !__any(lane_bits > 128u))
+            if (FULLT && !(kAblate && (G.dbg & kAbLdsEmit)) && !__any(lane_bits > 128u))
                 place_words(cw, buf_bits + (uint32_t)P + incl);
             else
                 emit_tile<FULLT>(c, buf_bits + (uint32_t)P + incl - lane_bits);
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
         for (int i = 0; i < kEncWaves; ++i) block_sum += s_mine[i];
         const uint64_t T = s_ticket;
         uint64_t excl_blk = 0;
-        if (T == 0 || (kAblate && (G.dbg & 128u))) {  // dbg 128: ablation, no look-back (positions are wrong)
+        if (T == 0 || (kAblate && (G.dbg & kAbNoLookback))) {  // (ablation: positions are wrong)
             if (lane == 0) __hip_atomic_store(scan_state + T, kScanPrefix | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (T) excl_blk = T * 2048ull * kEncWaves;
         } else {
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
             if (lane == 0)
                 __hip_atomic_store(scan_state + T, kScanPrefix | (excl_blk + block_sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (kAblate && (G.dbg & 1024u)) excl_blk = T * 2048ull * kEncWaves;  // ablation: look-back done, sparse placement all the same
+        if (kAblate && (G.dbg & kAbSparsePlace)) excl_blk = T * 2048ull * kEncWaves;  // ablation: look-back done, sparse placement all the same
         if (lane == 0) s_excl = excl_blk;
         ENC_STAMP(2);
     }
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
     }
     uint32_t *__restrict__ outp = out + pos + 1;
     if (fits) {
-        if (!(kAblate && (G.dbg & 64u))) {
+        if (!(kAblate && (G.dbg & kAbNoCopyOut))) {
             // 16 bytes per lane: 1 KB per store instruction instead of 256 bytes.  The waveform's place in the stream is
             // only word aligned; unaligned vector stores are on for HSA queues, and a wavefront's 64 pieces are contiguous
             // whatever their alignment (round 3: 22 store instructions per waveform became 6)
@@ -874,7 +874,7 @@ static unsigned enc_lds_pad() {
 
 // Single-pass encode (k_encode_fused).  d_scan: uint64[total_waves] + one uint32 ticket
 // word after it, zeroed here on the stream before every launch.
-hipError_t launch_encode_fused(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
+hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
     if (G.total_waves == 0) return hipSuccess;
@@ -895,7 +895,7 @@ hipError_t launch_encode_fused(const Geom &G, const int16_t *d_in, uint32_t *d_o
     const std::true_type T;
     const std::false_type F;
     auto pick = [&](auto wv_tag, auto cap_tag) { if (G.n_taps) go(T, wv_tag, cap_tag); else go(F, wv_tag, cap_tag); };
-    switch (fused_wide(G)) {
+    switch (wide) {
         case 1: pick(integral_constant<int, 8>{}, integral_constant<uint32_t, kEncWide1Words>{}); break;
         case 2: pick(integral_constant<int, 4>{}, integral_constant<uint32_t, kEncWide2Words>{}); break;
         case 3: pick(integral_constant<int, 4>{}, integral_constant<uint32_t, kEncWide3Words>{}); break;
@@ -941,14 +941,14 @@ hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, ui
 // (200 chunks of 14 M samples: L = 512 0.57 -> 0.95 TB/s, 1024 0.97 -> 1.33, 2048 1.51 -> 1.68), and waveforms
 // long enough to outgrow the single pass's LDS buffer; in between the single pass is better
 // block-parallel walk of short waveforms: blocks per chunk at 25 bits per sample (0: the batch does not take it)
+// (delta; ragged: decided when the plan was made, some chunk is short or long)
+bool long_batch_admits(const Geom &G) { return !G.n_taps && (G.uniform || G.seg_unit_base != nullptr); }
 bool long_batch(const Geom &G) {
-    if (G.n_taps) return false;
-    if (!G.uniform) return G.seg_unit_base != nullptr;  // decided when the plan was made (some chunk is short or long)
     // measured at 100 chunks of 14 M samples (single pass / segments, TB/s): L = 2049 0.95 / 1.06, 3000 1.57 / 1.64,
     // 4096 1.93 / 1.85, 7000 2.16 / 1.87, 12000 1.33 / 1.63 (the single pass outgrows its 8 KB LDS buffer at
     // ~6.5 bits per sample and encodes such waveforms twice)
-    return long_waveform_batch(G.total_waves, G.u_wave_len) || G.u_wave_len <= kSegShortLenHost || G.u_wave_len >= kSegLongLenHost ||
-           (G.dbg & 8192u);
+    return long_batch_admits(G) && (!G.uniform || long_waveform_batch(G.total_waves, G.u_wave_len) ||
+                                    G.u_wave_len <= kSegShortLenHost || G.u_wave_len >= kSegLongLenHost);
 }
 static uint32_t uniform_segments(const Geom &G) { return (G.u_wave_len + kSegSamples - 1u) / kSegSamples; }
 uint64_t long_batch_units(const Geom &G) { return G.uniform ? G.total_waves * uniform_segments(G) : G.seg_units; }

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     };
     // the same, waiting for it (bounded; a wait that expires reports kErrInternal and returns a place nothing is written to)
     auto wait_place = [&]() -> uint64_t {
-        if (kAblate && (G.dbg & 128u)) return (uint64_t)TA * WV * 2048ull;  // ablation: no waiting at all (positions are wrong)
+        if (kAblate && (G.dbg & kAbNoLookback)) return (uint64_t)TA * WV * 2048ull;  // ablation: no waiting at all (positions are wrong)
         uint32_t spins = 0;
 #ifdef DRX_ENC_STAMPS
         const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
@@ -528,7 +528,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         bool polling = false;
         auto between = [&]() {
             if (!pend) return;
-            if (kAblate && (G.dbg & 128u)) { place_to_lds(wait_place()); return; }
+            if (kAblate && (G.dbg & kAbNoLookback)) { place_to_lds(wait_place()); return; }
             if (polling) {
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pollv >> 32));
                 polling = false;
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         return true;
     };
     auto wait_place = [&]() -> EsPlace2 {
-        if (kAblate && (G.dbg & 128u)) return EsPlace2{(uint64_t)TA * WV * 2048ull, 0ull};  // ablation: no waiting at all (positions are wrong)
+        if (kAblate && (G.dbg & kAbNoLookback)) return EsPlace2{(uint64_t)TA * WV * 2048ull, 0ull};  // ablation: no waiting at all (positions are wrong)
         uint32_t spins = 0;
         for (;;) {
             EsPlace2 pl;
@@ -1086,7 +1086,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         bool polling = false;
         auto between = [&]() {
             if (!pend) return;
-            if (kAblate && (G.dbg & 128u)) { place_to_lds(wait_place()); return; }
+            if (kAblate && (G.dbg & kAbNoLookback)) { place_to_lds(wait_place()); return; }
             if (polling) {
                 polling = false;
                 EsPlace2 pl;
@@ -1168,7 +1168,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
 // launcher
 // ---------------------------------------------------------------------------
 // d_scan: uint64[2 * tickets + kEsCtrlWords + 16] (tickets <= total_waves): total[tickets] | place[tickets] | control, zeroed
-// here on the stream before every launch | the diagnostic build's counters (left alone).
+// here on the stream before every launch | the diagnostic build's counters.
 hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                 uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
                                 DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
@@ -1191,12 +1191,13 @@ hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_es_trace), &d_trace, sizeof d_trace);
     }
     if (d_trace) (void)hipMemsetAsync(d_trace, 0, 5 * W * sizeof(uint64_t), s);
+    (void)hipMemsetAsync(prof, 0, 12 * sizeof(unsigned long long), s);
 #endif
     // persistent: 16 wavefronts per CU, one workgroup of them the scanner's; never more than the batch can feed
-    // (debug flag 262144: three workgroups -- a scanner and two coders -- so that a small test batch takes every wavefront
+    // (DRX_DBG_STREAM_THREE_WGS: three workgroups -- a scanner and two coders -- so that a small test batch takes every wavefront
     // through many waveforms, i.e. around its ring)
     const unsigned full = 256u * (16u / kEsWaves);
-    const unsigned grid = (G.dbg & 262144u) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
+    const unsigned grid = (G.dbg & DRX_DBG_STREAM_THREE_WGS) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
     if (G.n_taps)
         k_encode_stream<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words, size,
                                                                               place, ctrl, d_status, prof);
@@ -1216,7 +1217,6 @@ hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_
             free(ht);
         }
         (void)hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost);
-        (void)hipMemset(prof, 0, sizeof h);
         const double wf = h[3] ? (double)h[3] : 1.0;
         fprintf(stderr, "enc stream stamps: %llu waveforms: %llu placed between tile groups without waiting, %llu waits (%.2f us each), %llu streamed; "
                 "per waveform: %.2f us in all, %.2f us waiting for the place, %.2f us at the rendezvous\n",
@@ -1245,7 +1245,7 @@ hipError_t launch_encode_stream_segs(const Geom &G, uint32_t seg_target, const i
     uint64_t *size = d_scan, *place = d_scan + tickets;
     uint32_t *ctrl = reinterpret_cast<uint32_t *>(d_scan + 3 * tickets);
     const unsigned full = 256u * (16u / kEsWaves);
-    const unsigned grid = (G.dbg & 262144u) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
+    const unsigned grid = (G.dbg & DRX_DBG_STREAM_THREE_WGS) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
     if (G.n_taps)
         k_encode_stream_segs<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, sh.seg_len, sh.tpw, d_in, d_out, out_cap, d_chunk_word_off,
                                                                                    d_wave_words, size, place, ctrl, d_status);

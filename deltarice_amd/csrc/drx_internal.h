@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/deltarice_hip.h"
+
 namespace drx {
 
 // One HDF5 chunk of the batch (device resident table, ragged batches only).
@@ -41,23 +43,7 @@ struct Geom {
     // pinned host word (device-visible) that every encoder writes the batch's encoded word count to beside DevStatus: the host
     // reads it -- without waiting for anything -- when it chooses the NEXT encode's kernel (drx_api.hip, stream_encoder_suits())
     uint64_t *host_words;
-    uint32_t dbg;  // "debug_flags" context option; 0 in normal use.  Dispatch overrides (host side, always available, every
-                   // forced path is bit-exact and the tests use them to reach it):
-                   //   256 never take the long-waveform paths   512 long waveforms: one workgroup per waveform only
-                   //  2048 never take the parallel header walks of small batches   8192 always the segment encoder
-                   //  4096 never the pieces encoder   32768 the pieces encoder wherever its geometry allows
-                   //  131072 ragged batches: one decode launch behind both header walks instead of one behind each
-                   //  262144 k_encode_stream on three workgroups (tests: every wavefront goes around its ring)
-                   //  524288 k_encode_stream (encode_impl 2) whatever the batch (else: where stream_encoder_suits())
-                   //  2097152 general filters behind the block decoder: always the separate k_iir_tiles pass
-                   //  4194304 k_encode_stream_segs wherever the batch is uniform, segments of kEsSegMinLen samples
-                   //  8388608 the chunk-wide walk by reading the chunk (k_pw_scan + k_walk_parallel) instead of k_walk_sparse
-                   // 16777216 k_walk_sparse also for one to four chunks and for ragged chunks of few long waveforms
-                   // Ablation switches INSIDE the kernels, compiled only with -DDRX_ABLATION (results invalid):
-                   //   decode:   1 skip the output stores   2 skip the stream loads
-                   //             4 request pieces without counting on the round's minimum consumption   16384 long: no stores
-                   //   encode:  16 per-code LDS emission instead of the lane-local concatenation
-                   //            32 no emission   64 no copy-out   128 no look-back (positions wrong)
+    uint32_t dbg;  // "debug_flags" context option (DRX_DBG_* of include/deltarice_hip.h; -DDRX_ABLATION builds: drx_device.h); 0 in normal use
     // ragged batches, walk inside the decode launch: chunk indices, short-waveform chunks first
     // (walk_short[n_short], then walk_long[n_long]), and the largest ceil(n_waves / 64) of any chunk
     const uint32_t *walk_short, *walk_long;
@@ -128,12 +114,13 @@ hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t 
                                   const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 
-hipError_t launch_encode_fused(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
+// wide: fused_wide() as the route decided it
+hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 
 // the persistent form of the single pass (drx_encode_stream.hip): a ring of kEsRingWords LDS words per wavefront, a scanner
-// wavefront.  d_scan: uint64[2 * total_waves + 48]
+// wavefront.  d_scan: uint64[2 * tickets + 48], tickets <= total_waves (32 words of control, 16 of the stamp build's counters)
 #ifndef DRX_ES_RING
 #define DRX_ES_RING 2496
 #endif
@@ -144,8 +131,9 @@ hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_
 
 // ... and its form for LONG waveforms (k_encode_stream_segs): the unit a wavefront codes into its ring is a SEGMENT of a
 // waveform, a ticket is kEsSegWaves consecutive segments of ONE waveform, places are bit positions.
-// d_scan: uint64[3 * tickets + 48].  The shape is a function of WaveformLength and the segment length the caller aims at
-// (what a ring holds with room for most of the next segment, from the bits per sample the plan expects).
+// d_scan: uint64[3 * tickets + 32], tickets = total_waves x es_seg_shape().tpw.  The shape is a function of WaveformLength and
+// the segment length the caller aims at (what a ring holds with room for most of the next segment, from the bits per sample
+// the plan expects).
 constexpr uint32_t kEsSegWaves = 4;
 constexpr uint32_t kEsSegMinLen = 1024, kEsSegMaxLen = 7168;  // samples per segment the host may aim at
 struct EsSegShape { uint32_t seg_len, nseg, tpw; };           // samples per segment (a multiple of 8), segments and tickets per waveform
@@ -169,11 +157,19 @@ __host__ __device__ inline EsSegShape es_seg_shape(uint32_t L, uint32_t seg_targ
     sh.tpw = (sh.nseg + kEsSegWaves - 1u) / kEsSegWaves;
     return sh;
 }
+// the segment form can run the batch: uniform, delta or a forward filter of up to four taps, tickets of the shortest segments
+// below 2^32 - 2^16; it is the default choice from kEsSegsFromLen on (16 384: k_encode_pieces 0.61 ms, this 0.66; 24 000: 0.69 / 0.61)
+inline bool stream_segs_admits(const Geom &G) { return G.uniform && (G.n_taps == 0 || G.enc_fast) && G.u_wave_len >= 64u &&
+                                                       G.total_waves * es_seg_shape(G.u_wave_len, kEsSegMinLen).tpw < 0xffff0000ull; }
+constexpr uint32_t kEsSegsFromLen = 20480;
+inline uint64_t segs_scan_words(const Geom &G, uint32_t seg_target) { return 3 * G.total_waves * es_seg_shape(G.u_wave_len, seg_target).tpw + 192; }
 hipError_t launch_encode_stream_segs(const Geom &G, uint32_t seg_target, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                      uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
                                      DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 
-// few long waveforms (WaveformLength = -1): a wavefront per 8192-sample segment, see drx_encode_kernels.hip
+// few long waveforms (WaveformLength = -1): a wavefront per 8192-sample segment, see drx_encode_kernels.hip.  Admission (the
+// encoder can run the batch) and preference (it is the default choice)
+bool long_batch_admits(const Geom &G);
 bool long_batch(const Geom &G);
 uint64_t long_batch_units(const Geom &G);
 hipError_t launch_encode_long(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
@@ -290,13 +286,14 @@ __host__ __device__ inline PieceShape piece_shape(uint32_t L, uint32_t W, uint32
 // (9.5 bits per sample): coded twice 2.17 ms, two segments 1.87, 4 x 3072 1.56, 8 x 3072 (one workgroup per CU) 1.64, 6 x 3072 2.08.
 constexpr uint32_t kEncWide1Words = 2496, kEncWide2Words = 3072, kEncWide3Words = 4096;
 inline int fused_wide(const Geom &G) {
-    if (!G.uniform || G.k <= 3u || (G.dbg & 65536u)) return 0;
+    if (!G.uniform || G.k <= 3u) return 0;
     const uint32_t L = G.u_wave_len;
     if (L <= kPcRunSamples / 2u || L > kPcWholeLen || L <= pc_whole_len(G.k)) return 0;
     const uint64_t bits10 = (uint64_t)L * (10u * G.k + 44u);
     return bits10 <= 320ull * kEncWide1Words ? 1 : (bits10 <= 320ull * kEncWide2Words ? 2 : (bits10 <= 320ull * kEncWide3Words ? 3 : 0));
 }
-bool pieces_batch(const Geom &G);       // the batch takes this encoder
+bool pieces_admits(const Geom &G);            // the encoder can run the batch (delta or a forward filter of up to four taps)
+bool pieces_batch(const Geom &G, int wide);   // ... and is its default choice
 uint64_t pieces_workgroups(const Geom &G, const ChunkDesc *host_chunks);
 uint64_t pieces_scan_words(const Geom &G, uint64_t total_wgs);  // uint64 words of its look-back state
 hipError_t launch_encode_pieces(const Geom &G, const int16_t *d_in, uint64_t in_samples, uint32_t *d_out, uint64_t out_cap,
@@ -327,7 +324,7 @@ constexpr uint32_t kPwMaxWaves = 3584;   // waveforms per chunk the chunk-wide w
 #define DRX_PW_MAX_CHUNKS 224
 #endif
 constexpr uint64_t kPwMaxChunks = DRX_PW_MAX_CHUNKS;  // the walks that READ the chunks (block-parallel; the chunk-wide walk's scan form,
-                                                      // debug flag 8388608): more chunks hide the serial walk behind the decoding
+                                                      // DRX_DBG_WALK_BY_SCAN): more chunks hide the serial walk behind the decoding
 // the chunk-wide walk by chains (k_walk_sparse) costs ~60 us per 512 chunks whatever their size: every uniform batch of
 // long waveforms takes it, the headline's 500 chunks included (4.74 + 0.08 ms against 5.33 with the walk inside the launch)
 constexpr uint64_t kSwMaxChunks = 1u << 20;

@@ -684,25 +684,24 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
 // 1629 / 1237 / 511 (profiles/r02_notes.md): no lower bound on the batch size.  A batch whose WaveformLengths are ALL above
 // kPcMaxLen (the reference's default, one waveform per chunk) takes the SUPER form; one that mixes the two kinds stays with
 // the segment encoder.
-// debug_flags: 4096 never this encoder, 8192 always the segment encoder, 32768 this encoder also where WaveformLength is in
-// k_encode_fused's own range (one waveform per wavefront; the tests compare the two that way).
 static bool pieces_packed(const Geom &G) { return G.uniform ? piece_packable(G.u_wave_len) : G.pc_packed != 0; }
 static bool pieces_super(const Geom &G) { return G.uniform ? G.u_wave_len > pc_max_len(G.k) : G.pc_super != 0; }
 
-bool pieces_batch(const Geom &G) {
-    if ((G.n_taps && !G.enc_fast) || (G.dbg & (8192u | 4096u))) return false;  // delta, or a forward filter of up to four taps
-    const bool force = (G.dbg & 32768u) != 0;
-    if (G.uniform) {
-        const uint32_t L = G.u_wave_len;
-        const bool packed = piece_packable(L);
-        if (L < kPcMinLen && !packed) return false;
-        if ((uint64_t)G.n_chunks * G.u_n_samples < (uint64_t)kTile) return false;
-        const PieceShape sh = piece_shape(L, G.u_n_waves, G.k, packed);
-        if ((uint64_t)G.u_n_waves * sh.parts > 0x7fffffffull || (uint64_t)sh.wgs * G.n_chunks > 0x7fffffffull) return false;
-        if (!force && fused_wide(G)) return false;  // k_encode_fused with a larger buffer per waveform
-        return force || packed || sh.run > 1u || sh.segs > 1u;
-    }
-    return G.pc_wg_base != nullptr;  // decided when the plan was made
+bool pieces_admits(const Geom &G) {  // (the plan allocates the encoder's look-back state where this holds)
+    if (G.n_taps && !G.enc_fast) return false;       // delta, or a forward filter of up to four taps
+    if (!G.uniform) return G.pc_wg_base != nullptr;  // decided when the plan was made
+    const uint32_t L = G.u_wave_len;
+    const bool packed = piece_packable(L);
+    if ((L < kPcMinLen && !packed) || (uint64_t)G.n_chunks * G.u_n_samples < (uint64_t)kTile) return false;
+    const PieceShape sh = piece_shape(L, G.u_n_waves, G.k, packed);
+    return (uint64_t)G.u_n_waves * sh.parts <= 0x7fffffffull && (uint64_t)sh.wgs * G.n_chunks <= 0x7fffffffull;
+}
+
+bool pieces_batch(const Geom &G, int wide) {
+    if (!G.uniform) return true;
+    if (wide) return false;  // k_encode_fused with a larger buffer per waveform
+    const PieceShape sh = piece_shape(G.u_wave_len, G.u_n_waves, G.k, piece_packable(G.u_wave_len));
+    return piece_packable(G.u_wave_len) || sh.run > 1u || sh.segs > 1u;
 }
 
 uint64_t pieces_workgroups(const Geom &G, const ChunkDesc *host_chunks) {

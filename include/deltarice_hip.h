@@ -194,17 +194,23 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
  *                     otherwise the header walk inside the launch where the batch is large enough to hide it
  *        7            always behind a separate walk kernel
  *        0            simple kernel (also: general filters the staged kernel does not take)
- *        (5 / 1: one sample per ring access, the form 8 / 7 superseded in round 1 -- only in builds made with -DDRX_LEGACY)
- *   "debug_flags"  dispatch overrides that force an alternative (still bit-exact) path, for tests and A/B timing:
- *        256 never the long-waveform paths, 512 long waveforms one workgroup each, 2048 never the parallel header walks,
- *        4096 never the pieces encoder, 8192 always the segment encoder, 32768 the pieces encoder also where one wavefront per
- *        waveform is the default, 65536 never the single-pass encoder's larger-buffer geometries (RiceParameter above 8),
- *        262144 the persistent encoder on three workgroups (every wavefront codes many waveforms of a small batch),
- *        524288 the persistent encoder (encode_impl 2) whatever the batch's size and expected code length,
- *        2097152 general filters behind the block decoder: always the separate inverse-filter pass,
- *        4194304 the persistent encoder's segment form (long waveforms) wherever the batch is uniform, in segments of ~1024
- *        samples, 8388608 the chunk-wide header walk by reading the whole chunk instead of chasing 64 chains, 16777216 by
- *        chains also where the scan form is the default (one to four chunks).  (Ablation switches inside the kernels exist only in -DDRX_ABLATION builds.) */
+ *   "debug_flags"  DRX_DBG_* bits: dispatch overrides that force an alternative (still bit-exact) path, for tests and A/B timing;
+ *                  a forcing flag takes its encoder wherever that encoder can run the batch */
+#define DRX_DBG_NO_LONG_PATHS 256u              /* never the long-waveform paths (segment encoders, block and long decoders) */
+#define DRX_DBG_LONG_NOT_BLOCKS 512u            /* long waveforms: one workgroup per waveform, never the block decoder */
+#define DRX_DBG_NO_PARALLEL_WALKS 2048u         /* never the parallel header walks */
+#define DRX_DBG_NO_PIECES 4096u                 /* never the pieces encoder nor the segment form by default */
+#define DRX_DBG_FORCE_SEGMENTS 8192u            /* the two-pass segment encoder */
+#define DRX_DBG_FORCE_PIECES 32768u             /* the pieces encoder, also where a wavefront per waveform is the default */
+#define DRX_DBG_NO_WIDE_FUSED 65536u            /* never the single-pass encoder's larger-buffer geometries (m above 8) */
+#define DRX_DBG_RAGGED_ONE_LANES_LAUNCH 131072u /* ragged batches: one decode launch behind both header walks */
+#define DRX_DBG_STREAM_THREE_WGS 262144u        /* the persistent encoders on three workgroups (every wavefront goes around its ring) */
+#define DRX_DBG_FORCE_STREAM 524288u            /* the persistent encoder (encode_impl 2) whatever the batch's size and code length */
+#define DRX_DBG_NW_ONE_WAVE 1048576u            /* -DDRX_DEC_NW builds: the staged flush's kernel off, one wavefront per workgroup */
+#define DRX_DBG_IIR_SEPARATE 2097152u           /* general filters behind the block decoder: always the separate inverse-filter pass */
+#define DRX_DBG_FORCE_STREAM_SEGS 4194304u      /* the persistent encoder's segment form (encode_impl 2, uniform), segments of ~1024 samples */
+#define DRX_DBG_WALK_BY_SCAN 8388608u           /* the chunk-wide header walk by reading the whole chunk instead of chasing 64 chains */
+#define DRX_DBG_WALK_BY_CHAINS 16777216u        /* the chunk-wide header walk by chains also where the scan form is the default */
 drx_status drx_ctx_set_option(drx_ctx *ctx, const char *key, int64_t value);
 
 #ifdef __cplusplus

@@ -13,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import deltarice_amd as dr  # noqa: E402
+from deltarice_amd import _lib as D  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
 
@@ -100,14 +101,13 @@ def main():
                 opts = (1 << k, Ls[0]) + ((len(taps),) + tuple(t & 0xFFFFFFFF for t in taps) if taps else ())
                 plan = ctx.plan_uniform(n_chunks, Ns[0], opts)
             xd = dev(ctx, x)
-            # (256: no long-waveform paths; 4096: no pieces encoder; 8192: the segment encoder; 32768: the pieces encoder
-            # wherever its geometry allows; 65536: the single-pass encoder's standard geometry only)
-            # 4194304: the persistent encoder's segment form wherever the batch is uniform (with 262144: on three workgroups)
-            for flags in (0, 256, 4096, 8192, 32768, 65536, 4194304, 4194304 | 262144):
-                for eimpl in ((2, 1, 0) if flags in (0, 256) else (2,)):
+            # (every forcing flag takes its encoder wherever that encoder can run the batch; include/deltarice_hip.h)
+            for flags in (0, D.DBG_NO_LONG_PATHS, D.DBG_NO_PIECES, D.DBG_FORCE_SEGMENTS, D.DBG_FORCE_PIECES, D.DBG_NO_WIDE_FUSED,
+                          D.DBG_FORCE_STREAM_SEGS, D.DBG_FORCE_STREAM_SEGS | D.DBG_STREAM_THREE_WGS):
+                for eimpl in ((2, 1, 0) if flags in (0, D.DBG_NO_LONG_PATHS) else (2,)):
                     ctx.set_option("encode_impl", eimpl)
-                    # (524288: the persistent encoder whatever the batch's size, where the flags leave the choice to it)
-                    ctx.set_option("debug_flags", flags | (524288 if eimpl == 2 and flags in (0, 256) else 0))
+                    # (and the persistent encoder whatever the batch's size)
+                    ctx.set_option("debug_flags", flags | (D.DBG_FORCE_STREAM if eimpl == 2 and flags in (0, D.DBG_NO_LONG_PATHS) else 0))
                     log(f"  encode flags {flags} impl {eimpl}")
                     w, off = plan.encode(xd).to_numpy()
                     assert np.array_equal(off, ref_off), f"offsets (flags {flags}, encoder {eimpl})"
@@ -118,8 +118,8 @@ def main():
             expect = x
             if not lossless:
                 expect = np.concatenate([O.decode_chunk(ww, oo) for ww, oo in zip(words, copts)])
-            # (16777216: the chunk-wide walk by chains also for these few chunks; 8388608: by reading the chunks)
-            for flags, impl in ((0, 8), (256, 8), (512, 8), (0, 7), (256, 7), (0, 0), (131072, 8), (256 | 16777216, 8), (256 | 8388608, 8)):
+            # (WALK_BY_CHAINS: the chunk-wide walk by chains also for these few chunks; WALK_BY_SCAN: by reading the chunks)
+            for flags, impl in ((0, 8), (D.DBG_NO_LONG_PATHS, 8), (D.DBG_LONG_NOT_BLOCKS, 8), (0, 7), (D.DBG_NO_LONG_PATHS, 7), (0, 0), (D.DBG_RAGGED_ONE_LANES_LAUNCH, 8), (D.DBG_NO_LONG_PATHS | D.DBG_WALK_BY_CHAINS, 8), (D.DBG_NO_LONG_PATHS | D.DBG_WALK_BY_SCAN, 8)):
                 ctx.set_option("debug_flags", flags)
                 ctx.set_option("decode_impl", impl)
                 log(f"  decode flags {flags} impl {impl}")
@@ -150,7 +150,7 @@ def main():
                     if j not in hdr:
                         bad[j] ^= np.uint32(1 << int(rng.integers(0, 32)))
                 encb = dr.EncodedBatch(dev(ctx, bad.view(np.int32)), dev(ctx, ref_off.astype(np.int64)), bad.size)
-                for flags, impl in ((0, 8), (256, 8), (512, 8), (0, 7), (0, 0), (256 | 16777216, 8)):
+                for flags, impl in ((0, 8), (D.DBG_NO_LONG_PATHS, 8), (D.DBG_LONG_NOT_BLOCKS, 8), (0, 7), (0, 0), (D.DBG_NO_LONG_PATHS | D.DBG_WALK_BY_CHAINS, 8)):
                     ctx.set_option("debug_flags", flags)
                     ctx.set_option("decode_impl", impl)
                     log(f"  corrupt decode flags {flags} impl {impl}")

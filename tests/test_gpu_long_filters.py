@@ -2,10 +2,11 @@
 recommends for NOPTREX (32 x 500 000 samples per chunk, taps [1,-1,1,-1]: /root/reference/docs/Optimization.md:21,
 docs/Performance.md:38, src/deltaRice.c:91-102).  They take the block-parallel decoder (drx_blocks.hip); a general filter's
 inverse then runs in place over the residuals, parallel inside a waveform (drx_iir.hip).  Every case is held to the oracle's
-bytes and to the lane-per-waveform decoder (debug flag 256), and the path a decode took is read back from the plan."""
+bytes and to the lane-per-waveform decoder (DBG_NO_LONG_PATHS), and the path a decode took is read back from the plan."""
 import numpy as np
 import pytest
 
+from deltarice_amd import _lib as D
 from test_gpu_parity import dev, make_data
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +54,7 @@ def test_general_filter_few_long_waveforms_uniform(ctx, O):
             ref_w, ref_off = O.encode_batch(x, N, opts)
             plan = ctx.plan_uniform(n_chunks, N, opts)
             enc = dr.EncodedBatch(dev(ctx, ref_w.view(np.int32)), dev(ctx, ref_off.astype(np.int64)), ref_w.size)
-            for flags in (0, 256):
+            for flags in (0, D.DBG_NO_LONG_PATHS):
                 ctx.set_option("debug_flags", flags)
                 y = plan.decode(enc).cpu().numpy()
                 path = plan.last_decode_path()
@@ -99,14 +100,14 @@ def test_general_filter_many_long_waveforms_fused(ctx, O):
                 w, off = enc.to_numpy()
                 assert np.array_equal(off, ref_off) and np.array_equal(w, ref_w), (si, taps)
             outs = {}
-            for flags in (0, 2097152, 256):
+            for flags in (0, D.DBG_IIR_SEPARATE, D.DBG_NO_LONG_PATHS):
                 ctx.set_option("debug_flags", flags)
                 outs[flags] = plan.decode(enc).cpu().numpy()
                 path = plan.last_decode_path()
                 ctx.set_option("debug_flags", 0)
                 if flags == 0:
                     assert path & BLOCKS and path & IIR_FUSED and not path & IIR, (path, W, L)
-                elif flags == 2097152:
+                elif flags == D.DBG_IIR_SEPARATE:
                     assert path & BLOCKS and path & IIR and not path & IIR_FUSED, (path, W, L)
                 else:
                     assert path & LANES_ANY and not path & BLOCKS, (path, W, L)
@@ -147,7 +148,7 @@ def test_ragged_few_long_waveforms_delta_and_general(ctx, O):
         enc = plan.encode(dev(ctx, x))
         w, off = enc.to_numpy()
         assert np.array_equal(off.astype(np.int64), ref_off) and np.array_equal(w, ref_w), taps
-        for flags in (0, 256):
+        for flags in (0, D.DBG_NO_LONG_PATHS):
             ctx.set_option("debug_flags", flags)
             y = plan.decode(enc).cpu().numpy()
             path = plan.last_decode_path()

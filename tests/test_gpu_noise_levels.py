@@ -8,6 +8,7 @@ class of each of them is held to the oracle's bytes here (reference: compressWit
 import numpy as np
 import pytest
 
+from deltarice_amd import _lib as D
 from test_gpu_parity import dev
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +38,7 @@ def noise(rng, sigma, n):
     return np.clip(rng.normal(0, sigma, n), -32768, 32767).astype(np.int16)
 
 
-def check(ctx, O, x, n_chunks, N, opts, enc_flags=(0,), dec_flags=(0, 256), want_blocks=None):
+def check(ctx, O, x, n_chunks, N, opts, enc_flags=(0,), dec_flags=(0, D.DBG_NO_LONG_PATHS), want_blocks=None):
     import deltarice_amd as dr
     ref_w, ref_off = O.encode_batch(x, N, opts)
     plan = ctx.plan_uniform(n_chunks, N, opts)
@@ -96,17 +97,17 @@ def test_quiet_stretches_in_noisy_waveforms_take_the_second_parse(ctx, O):
 
 def test_single_pass_encoder_buffer_classes(ctx, O):
     """WaveformLength 7000: 8 waveforms x 2048 LDS words per workgroup while the RiceParameter says a waveform fits, then
-    8 x 2496, 4 x 3072, 4 x 4096, then the pieces encoder's segments; flag 65536 = never the larger buffers, 32768 = the pieces
-    encoder, 4096 = never the pieces encoder (so that what does not fit is coded twice)."""
+    8 x 2496, 4 x 3072, 4 x 4096, then the pieces encoder's segments; DBG_NO_WIDE_FUSED = never the larger buffers,
+    DBG_FORCE_PIECES = the pieces encoder, DBG_NO_PIECES = never the pieces encoder (so that what does not fit is coded twice)."""
     rng = np.random.default_rng(43)
     for sigma, m in LEVELS + [(30000, 32768), (30000, 8)]:
         N = 20 * 7000 - 411  # (a shorter last waveform)
         x = noise(rng, sigma, 3 * N)
-        check(ctx, O, x, 3, N, (m, 7000), enc_flags=(0, 65536, 32768, 4096), dec_flags=(0,))
+        check(ctx, O, x, 3, N, (m, 7000), enc_flags=(0, D.DBG_NO_WIDE_FUSED, D.DBG_FORCE_PIECES, D.DBG_NO_PIECES), dec_flags=(0,))
     # a forward filter through the same geometries
     for sigma, m in [(80, 64), (320, 256), (3000, 2048)]:
         x = noise(rng, sigma, 2 * 9 * 8191)
-        check(ctx, O, x, 2, 9 * 8191, (m, 8191, 3, 1, 0xFFFFFFFE, 1), enc_flags=(0, 65536, 32768), dec_flags=(0,))
+        check(ctx, O, x, 2, 9 * 8191, (m, 8191, 3, 1, 0xFFFFFFFE, 1), enc_flags=(0, D.DBG_NO_WIDE_FUSED, D.DBG_FORCE_PIECES), dec_flags=(0,))
 
 
 def test_pieces_encoder_sizes_follow_the_rice_parameter(ctx, O):
@@ -118,7 +119,7 @@ def test_pieces_encoder_sizes_follow_the_rice_parameter(ctx, O):
         for sigma, m in [(10, 8), (80, 64), (1000, 1024), (30000, 32768), (30000, 16), (1, 4096)]:
             N = W * L - L // 3
             x = noise(rng, sigma, n_chunks * N)
-            check(ctx, O, x, n_chunks, N, (m, L), enc_flags=(0, 8192), dec_flags=(0,))
+            check(ctx, O, x, n_chunks, N, (m, L), enc_flags=(0, D.DBG_FORCE_SEGMENTS), dec_flags=(0,))
 
 
 def test_streams_of_equal_length_codes(ctx, O):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import delta_only, golden_case_names
+from deltarice_amd import _lib as D
 
 pytestmark = pytest.mark.gpu
 
@@ -31,39 +32,50 @@ def dev(ctx, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
 
 
-def gpu_encode(ctx, plan, x):
+def gpu_encode(ctx, plan, x, wave_len=None):
     """Encodes with every encoder (the simple size/scan/pack passes; the single pass with a look-back per workgroup and
-    its persistent form, both forced with debug flag 256; the pieces encoder wherever its geometry allows, flag 32768; and
-    whatever the batch shape selects by default), checks they agree, returns the default one's result."""
+    its persistent form, forced with DBG_FORCE_STREAM, and its segment form, DBG_FORCE_STREAM_SEGS; the pieces encoder
+    wherever its geometry allows, DBG_FORCE_PIECES; and whatever the batch shape selects by default), checks they agree and
+    that every forcing flag reached its encoder, returns the default one's result.  wave_len: the uniform plan's
+    WaveformLength (None: a ragged plan)."""
     xd = dev(ctx, x.reshape(-1).view(np.int16))
-    ctx.set_option("encode_impl", 0)
-    enc0 = plan.encode(xd)
+    paths = {}
+
+    def encode(impl, flags):
+        ctx.set_option("encode_impl", impl)
+        ctx.set_option("debug_flags", flags)
+        enc = plan.encode(xd)
+        paths[impl, flags] = plan.last_encode_path()
+        return enc
+
+    enc0 = encode(0, 0)
     w0, off0 = enc0.to_numpy()
-    ctx.set_option("encode_impl", 1)
-    ctx.set_option("debug_flags", 256)
-    w1, off1 = plan.encode(xd).to_numpy()
-    ctx.set_option("encode_impl", 2)
-    ctx.set_option("debug_flags", 256 | 524288)  # (524288: the persistent form whatever the batch's size)
-    ws, offs = plan.encode(xd).to_numpy()
+    w1, off1 = encode(1, D.DBG_NO_LONG_PATHS).to_numpy()
+    ws, offs = encode(2, D.DBG_NO_LONG_PATHS | D.DBG_FORCE_STREAM).to_numpy()
     assert np.array_equal(offs, off0) and np.array_equal(ws, w0), "persistent single-pass encoder disagrees"
-    ctx.set_option("debug_flags", 256 | 4194304)  # (its segment form wherever the batch is uniform)
-    wg, offg = plan.encode(xd).to_numpy()
+    wg, offg = encode(2, D.DBG_NO_LONG_PATHS | D.DBG_FORCE_STREAM_SEGS).to_numpy()
     assert np.array_equal(offg, off0) and np.array_equal(wg, w0), "segment form of the persistent encoder disagrees"
-    ctx.set_option("debug_flags", 32768)
-    w2, off2 = plan.encode(xd).to_numpy()
-    ctx.set_option("debug_flags", 4096)
-    w3, off3 = plan.encode(xd).to_numpy()
+    w2, off2 = encode(2, D.DBG_FORCE_PIECES).to_numpy()
+    w3, off3 = encode(2, D.DBG_NO_PIECES).to_numpy()
+    enc = encode(2, 0)
     ctx.set_option("debug_flags", 0)
-    enc = plan.encode(xd)
     w, off = enc.to_numpy()
     assert np.array_equal(off, off0) and np.array_equal(w, w0), "encoder implementations disagree"
     assert np.array_equal(off1, off0) and np.array_equal(w1, w0), "single-pass encoder disagrees"
     assert np.array_equal(off2, off0) and np.array_equal(w2, w0), "pieces encoder disagrees"
     assert np.array_equal(off3, off0) and np.array_equal(w3, w0), "encoder without the pieces path disagrees"
+    # where the flags led (the single-pass encoders take delta and forward filters of up to four taps)
+    single = paths[1, D.DBG_NO_LONG_PATHS] != D.ENC_TWO_PASS
+    assert paths[0, 0] == D.ENC_TWO_PASS, paths
+    assert paths[2, D.DBG_NO_LONG_PATHS | D.DBG_FORCE_STREAM] == (D.ENC_STREAM if single else D.ENC_TWO_PASS), paths
+    segs = single and wave_len is not None and wave_len >= 64
+    assert (paths[2, D.DBG_NO_LONG_PATHS | D.DBG_FORCE_STREAM_SEGS] == D.ENC_STREAM_SEGS) == segs, paths
+    assert paths[2, D.DBG_FORCE_PIECES] in (D.ENC_PIECES, paths[2, 0]), paths  # (where it cannot run: the default route)
+    assert paths[2, D.DBG_NO_PIECES] not in (D.ENC_PIECES, D.ENC_STREAM_SEGS), paths
     return enc, w, off
 
 
-IMPLS = [0, 7, 8]  # every decode_impl the default build offers (include/deltarice_hip.h; 1 / 5 are -DDRX_LEGACY builds')
+IMPLS = [0, 7, 8]  # every decode_impl (include/deltarice_hip.h)
 
 
 # --------------------------------------------------------------------------- golden
@@ -72,7 +84,8 @@ def test_golden_batch_api(ctx, O, golden, name):
     g = golden[name]
     x = O.decode_chunk(g["words"], g["opts"])
     plan = ctx.plan_uniform(1, x.size, g["opts"])
-    enc, w, off = gpu_encode(ctx, plan, x)
+    o = g["opts"]
+    enc, w, off = gpu_encode(ctx, plan, x, o[1] if len(o) > 1 and 0 < o[1] < 0x80000000 else x.size)
     assert off.tolist() == [0, g["n_words"]]
     assert np.array_equal(w, g["words"]), "GPU encode differs from the reference's bytes"
     for impl in IMPLS:
@@ -148,7 +161,7 @@ def test_random_vs_oracle(ctx, O, n_chunks, chunk_samples, L, k, kind):
     opts = (1 << k,) if L == 0 else (1 << k, L)
     ref_w, ref_off = O.encode_batch(x, chunk_samples, opts)
     plan = ctx.plan_uniform(n_chunks, chunk_samples, opts)
-    enc, w, off = gpu_encode(ctx, plan, x)
+    enc, w, off = gpu_encode(ctx, plan, x, L or chunk_samples)
     assert np.array_equal(off, ref_off)
     assert np.array_equal(w, ref_w)
     # n_i table
@@ -244,7 +257,7 @@ def test_pieces_encoder_vs_oracle(ctx, O, n_chunks, chunk_samples, L, k, kind):
     opts = (1 << k, L) if L else (1 << k,)
     ref_w, ref_off = O.encode_batch(x, chunk_samples, opts)
     plan = ctx.plan_uniform(n_chunks, chunk_samples, opts)
-    ctx.set_option("debug_flags", 32768)
+    ctx.set_option("debug_flags", D.DBG_FORCE_PIECES)
     try:
         enc = plan.encode(dev(ctx, x))
         w, off = enc.to_numpy()
@@ -265,7 +278,7 @@ def test_pieces_encoder_ragged_and_capacity(ctx, O):
     xs = [make_data(rng, "uniform" if c == 2 else "gauss10", n) for c, n in enumerate(Ns)]
     x = np.concatenate(xs)
     plan = ctx.plan(Ns, Ls, 8)
-    ctx.set_option("debug_flags", 32768)
+    ctx.set_option("debug_flags", D.DBG_FORCE_PIECES)
     try:
         enc = plan.encode(dev(ctx, x))
         w, off = enc.to_numpy()
@@ -545,7 +558,7 @@ def test_general_prediction_filters_vs_oracle(ctx, O):
         plan = ctx.plan_uniform(3, 5000, opts)
         for eimpl in (0, 1, 2):  # two-pass encoder; single-pass encoders (take up to 4 taps): per workgroup, persistent
             ctx.set_option("encode_impl", eimpl)
-            ctx.set_option("debug_flags", 524288 if eimpl == 2 else 0)
+            ctx.set_option("debug_flags", D.DBG_FORCE_STREAM if eimpl == 2 else 0)
             enc = plan.encode(dev(ctx, x))
             w, off = enc.to_numpy()
             assert np.array_equal(off, ref_off) and np.array_equal(w, ref_w), (taps, eimpl)
@@ -573,7 +586,7 @@ def test_general_filters_through_the_pieces_encoder(ctx, O):
             opts = (8, L if L else N, len(taps)) + tuple(t & 0xFFFFFFFF for t in taps)
             ref_w, ref_off = O.encode_batch(x, N, opts)
             plan = ctx.plan_uniform(n_chunks, N, opts)
-            for flags in (0, 32768, 4096):
+            for flags in (0, D.DBG_FORCE_PIECES, D.DBG_NO_PIECES):
                 ctx.set_option("debug_flags", flags)
                 enc = plan.encode(dev(ctx, x))
                 w, off = enc.to_numpy()
@@ -587,7 +600,7 @@ def test_general_filters_through_the_pieces_encoder(ctx, O):
 
 def test_persistent_encoder_rings_and_streaming(ctx, O):
     """k_encode_stream (encode_impl 2, round 4): wavefronts on their own, a ring of LDS per wavefront, a scanner workgroup.
-    With debug flag 262144 the launch has two coding workgroups, so every wavefront takes many waveforms around its ring:
+    With DBG_STREAM_THREE_WGS the launch has two coding workgroups, so every wavefront takes many waveforms around its ring:
     code that wraps at the ring's end, waveforms that must wait for the one in front (short behind long), waveforms that
     outgrow the ring (incompressible, or simply long: the streaming path), a shorter last waveform, a general filter, ragged
     chunks, a capacity error -- all held to the oracle's bytes, and to the encoder of round 3."""
@@ -638,9 +651,10 @@ def test_persistent_encoder_rings_and_streaming(ctx, O):
             at += N
         ref_w, ref_off = np.concatenate(words), np.array(offs, np.uint64)
         xd = dev(ctx, x)
-        for flags in (256 | 4096 | 524288, 256 | 4096 | 524288 | 262144, 256 | 4194304, 256 | 4194304 | 262144):
+        stream, segs = D.DBG_NO_LONG_PATHS | D.DBG_NO_PIECES | D.DBG_FORCE_STREAM, D.DBG_NO_LONG_PATHS | D.DBG_FORCE_STREAM_SEGS
+        for flags in (stream, stream | D.DBG_STREAM_THREE_WGS, segs, segs | D.DBG_STREAM_THREE_WGS):
             ctx.set_option("debug_flags", flags)
-            for eimpl in ((2, 1) if flags & 4096 else (2,)):
+            for eimpl in ((2, 1) if flags & D.DBG_NO_PIECES else (2,)):
                 ctx.set_option("encode_impl", eimpl)
                 enc = plan.encode(xd)
                 w, off = enc.to_numpy()
@@ -666,7 +680,7 @@ def test_encoder_dispatch_follows_the_measured_code_length(ctx, O):
     so also for callers that never wait for an encode and hand the decoder the buffer's capacity as in_words (bench.py does:
     for a while that capacity was taken for the stream's length, and the headline batch went to k_encode_fused); the
     single pass with a look-back per workgroup where the code is long; the segment form for long waveforms."""
-    ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_SEGS = 3, 4, 5, 6
+    ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_SEGS = D.ENC_FUSED, D.ENC_PIECES, D.ENC_STREAM, D.ENC_STREAM_SEGS
     rng = np.random.default_rng(77)
     W, L, n_chunks = 2100, 7000, 4  # 8400 waveforms: enough for the persistent grid
     for sigma, k, want in ((10, 3, ENC_STREAM), (400, 3, ENC_FUSED)):  # (sigma 400 under m = 8: ~16 bits per sample, 3500 words)
@@ -812,7 +826,7 @@ def test_few_waveforms_take_the_block_decoder(ctx, O):
         ref_w, ref_off = O.encode_batch(x, N, opts)
         plan = ctx.plan_uniform(n_chunks, N, opts)
         enc = dr.EncodedBatch(dev(ctx, ref_w.view(np.int32)), dev(ctx, ref_off.astype(np.int64)), ref_w.size)
-        for flags in (0, 256, 512):
+        for flags in (0, D.DBG_NO_LONG_PATHS, D.DBG_LONG_NOT_BLOCKS):
             ctx.set_option("debug_flags", flags)
             y = plan.decode(enc).cpu().numpy()
             assert np.array_equal(y, x), (n_chunks, W, L, k, kind, flags)
@@ -855,7 +869,7 @@ def test_few_long_waveforms_take_the_wave_per_waveform_decoder(ctx, O):
             # 256: lane-per-waveform decoder / single-pass encoder; 512: one workgroup per waveform (the block decoder's
             # fallback); 0: the defaults for such batches (a workgroup per block of the stream -- drx_blocks.hip --,
             # a wavefront per 8192-sample segment)
-            for flags in (256, 512, 0):
+            for flags in (D.DBG_NO_LONG_PATHS, D.DBG_LONG_NOT_BLOCKS, 0):
                 ctx.set_option("debug_flags", flags)
                 assert np.array_equal(plan.decode(enc).cpu().numpy(), x), (name, opts, flags)
                 w, off = plan.encode(dev(ctx, x)).to_numpy()
@@ -968,7 +982,7 @@ def test_corrupt_headers_through_the_parallel_walks(ctx, O):
         ref_w, ref_off = O.encode_batch(x, W * L, opts)
         plan = ctx.plan_uniform(n_chunks, W * L, opts)
         good = dr.EncodedBatch(dev(ctx, ref_w.view(np.int32)), dev(ctx, ref_off.astype(np.int64)), ref_w.size)
-        for flags in (0, 16777216, 8388608, 2048):  # parallel walks (chunk-wide: 64 chains chased / the chunk read) / the serial walkers
+        for flags in (0, D.DBG_WALK_BY_CHAINS, D.DBG_WALK_BY_SCAN, D.DBG_NO_PARALLEL_WALKS):  # parallel walks (chunk-wide: 64 chains chased / the chunk read) / the serial walkers
             ctx.set_option("debug_flags", flags)
             assert np.array_equal(plan.decode(good).cpu().numpy(), x)
         ctx.set_option("debug_flags", 0)
@@ -980,7 +994,7 @@ def test_corrupt_headers_through_the_parallel_walks(ctx, O):
             bad = ref_w.copy()
             bad[pos[which]] = (int(bad[pos[which]]) + delta) & 0xFFFFFFFF
             enc = dr.EncodedBatch(dev(ctx, bad.view(np.int32)), dev(ctx, ref_off.astype(np.int64)), bad.size)
-            for flags in (0, 16777216, 8388608, 2048):
+            for flags in (0, D.DBG_WALK_BY_CHAINS, D.DBG_WALK_BY_SCAN, D.DBG_NO_PARALLEL_WALKS):
                 ctx.set_option("debug_flags", flags)
                 with pytest.raises(dr.DeltaRiceError) as e:
                     plan.decode(enc)
@@ -1027,7 +1041,7 @@ def test_chunk_wide_walk_by_chains(ctx, O):
         enc = dr_batch(ctx, ref_w, ref_off)
         # (256: the lane-per-waveform decoder behind the walk, whatever the shape; the other flags: the walks that read the chunks,
         # the serial walkers)
-        for flags in (256, 256 | 16777216, 256 | 8388608, 256 | 2048):
+        for flags in (D.DBG_NO_LONG_PATHS, D.DBG_NO_LONG_PATHS | D.DBG_WALK_BY_CHAINS, D.DBG_NO_LONG_PATHS | D.DBG_WALK_BY_SCAN, D.DBG_NO_LONG_PATHS | D.DBG_NO_PARALLEL_WALKS):
             ctx.set_option("debug_flags", flags)
             assert np.array_equal(plan.decode(enc).cpu().numpy(), x), (L, W, kind, flags)
             nw = plan.wave_words()
