@@ -28,7 +28,6 @@ DBG_NO_WIDE_FUSED = 65536
 DBG_RAGGED_ONE_LANES_LAUNCH = 131072
 DBG_STREAM_THREE_WGS = 262144
 DBG_FORCE_STREAM = 524288
-DBG_NW_ONE_WAVE = 1048576
 DBG_IIR_SEPARATE = 2097152
 DBG_FORCE_STREAM_SEGS = 4194304
 DBG_WALK_BY_SCAN = 8388608

@@ -753,7 +753,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                     const int64_t first = (int64_t)sidx - (int64_t)blk;  // block 0 of this waveform
                     int64_t base = (int64_t)sidx - 1;
                     uint32_t spins = 0;
-#ifndef DRX_BLK_NO_GATE
                     // the nearest predecessor alone first (one 8-byte load per poll, not a window from every waiting workgroup)
                     for (;;) {
                         uint64_t v = 0;
@@ -762,7 +761,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                         __builtin_amdgcn_s_sleep(4);
                         if (++spins > (1u << 22)) break;  // (the window loop below reports it)
                     }
-#endif
                     for (;;) {
                         // lane l looks at predecessors base - l (nearer) and base - 64 - l (farther)
                         const int64_t i0 = base - lane, i1 = base - 64 - lane;
@@ -874,17 +872,13 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                     rr[i] = 0;
                     if (2u * (uint32_t)i < wmax) rr[i] = my_stage[i];
                 }
-#ifndef DRX_BLK_REORDER16
                 if (RESID) s_e[tid] = sum;  // (a lane's last residual: what the next lane puts in front of its first one, below)
-#endif
                 blk_barrier();  // every lane holds its samples: the buffer may now be rewritten in output order
                 const uint32_t base16 = RESID ? 0u : (acc_base + pre_s + incl_s - sum) & 0xffffu;  // the running sum in front of my first sample
-                // both halves of a dword take the base in one packed add; the two 16-bit stores have immediate offsets from one
-                // address and are masked by the lane's count (an exec mask costs a compare, a dump slot a compare and a select)
+                // both halves of a dword take the base in one packed add
                 typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
                 const u16x2 b2 = {(uint16_t)base16, (uint16_t)base16};
                 uint16_t *const op = obuf + (a0 + rel0);
-#ifndef DRX_BLK_REORDER16
                 {
                     // WHOLE dwords: a lane whose first sample sits in the high half of a dword (odd position) writes that dword
                     // with the sample in front of its first one in the low half -- which is the running sum in front of it, base16,
@@ -909,16 +903,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                     }
                     if (cnt != 0u) op[cnt - 1u] = (uint16_t)(base16 + sum);  // (my last sample = the running sum behind my codes; residual mode: my last residual)
                 }
-#else
-#pragma unroll
-                for (int i = 0; i < NR; ++i) {
-                    if (2u * (uint32_t)i < wmax) {
-                        const u16x2 v = __builtin_bit_cast(u16x2, rr[i]) + b2;
-                        if (2u * (uint32_t)i < cnt) op[2 * i] = v.x;
-                        if (2u * (uint32_t)i + 1u < cnt) op[2 * i + 1] = v.y;
-                    }
-                }
-#endif
                 blk_barrier();
                 BLK_STAMP(6);  // reorder
                 if (FUSE) iir_lds(a0, blk_count);

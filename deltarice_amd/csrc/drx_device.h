@@ -11,13 +11,13 @@ namespace drx {
 
 // Ablation switches inside the hot loops (Geom::dbg bits beside DRX_DBG_*; results invalid), only in -DDRX_ABLATION builds (A/B
 // timing through DRX_LIB_PATH).  decode: no output / long-waveform stores, no stream loads, pieces requested without counting on a
-// round's minimum consumption, no lock of the shared buffer; encode: per-code LDS emission, no emission, no copy-out, no look-back.
+// round's minimum consumption; encode: per-code LDS emission, no emission, no copy-out, no look-back.
 #ifdef DRX_ABLATION
 constexpr bool kAblate = true;
 #else
 constexpr bool kAblate = false;
 #endif
-constexpr uint32_t kAbNoStores = 1, kAbLongNoStores = 16384, kAbNoLoads = 2, kAbNoMinConsume = 4, kAbNoLock = 8;
+constexpr uint32_t kAbNoStores = 1, kAbLongNoStores = 16384, kAbNoLoads = 2, kAbNoMinConsume = 4;
 constexpr uint32_t kAbLdsEmit = 16, kAbNoEmit = 32, kAbNoCopyOut = 64, kAbNoLookback = 128, kAbSparsePlace = 1024;
 
 // ---------------------------------------------------------------------------
@@ -66,19 +66,10 @@ __host__ __device__ __forceinline__ uint32_t min_payload_words(uint32_t len, uin
 
 // count-leading-zeros with the ISA's result for 0 (-1) instead of the source language's undefined behaviour: the
 // decoders meet an all-zero window only past the end of a corrupt stream, where any value will do, but it has to BE a value
-#ifndef DRX_FFBH_MODE
-#define DRX_FFBH_MODE 0
-#endif
 __device__ __forceinline__ uint32_t ffbh(uint32_t x) {
-#if DRX_FFBH_MODE == 0
     uint32_t r;
     asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(x));
     return r;
-#elif DRX_FFBH_MODE == 1
-    return (uint32_t)__builtin_clz(x | 1u);
-#else
-    return (uint32_t)__builtin_clz(x);  // (A/B only: undefined for 0 in the source language)
-#endif
 }
 
 struct WaveRef {

@@ -506,7 +506,6 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
             if (lane == 0) __hip_atomic_store(scan_state + T, kScanAgg | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             int64_t base = (int64_t)T - 1;
             uint32_t spins = 0;
-#ifndef DRX_ENC_NO_GATE
             // Wait for the NEAREST predecessor alone first: one 8-byte load per poll instead of a whole window from every
             // waiting workgroup.  Workgroups finish roughly in ticket order, so when T - 1 has published, the window behind it
             // has too; and ~500 workgroups polling 128 entries each were a fabric load of their own beside the encoder's
@@ -518,7 +517,6 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
                 __builtin_amdgcn_s_sleep(DRX_ENC_GATE_SLEEP);
                 if (++spins > (1u << 22)) break;  // (the window loop below reports it)
             }
-#endif
             ENC_STAMP(1);
             // kLbWin x 64 entries per poll.  The frontier of known prefixes advances one window per hop (a hop = an
             // agent-scope store becoming visible + an agent-scope load, 3-5 us under the encoder's own streaming loads), so

@@ -51,9 +51,6 @@ constexpr uint32_t kEsCtrlWords = 32;  // uint64 words of control state: 128 byt
 // ring words per wavefront: 16 x (2496 + 16) x 4 bytes = 157 KB, 16 wavefronts per CU (the geometry fused_wide() = 1 already
 // runs); a 1414-word waveform (the headline's) leaves the next one 1072 words = nine tiles before it has to know its place
 constexpr uint32_t kEsRing = kEsRingWords;  // (drx_internal.h: the dispatch needs it too)
-#ifndef DRX_ES_PRIO
-#define DRX_ES_PRIO 1
-#endif
 #ifndef DRX_ES_POLL_SLEEP
 #define DRX_ES_POLL_SLEEP 4
 #endif
@@ -486,14 +483,12 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                 const bool must = fits && ((P + tile_bits + 31u) >> 5) >= (uint64_t)limit;
                 if (seen || must) {
                     if (seen) ES_COUNT(2, 1);
-#if DRX_ES_PRIO
                     // A wavefront that has to wait for its place is AHEAD of the stream's frontier; one that finds the place of
                     // its last waveform almost as soon as it looks is what the others are waiting for.  Issue priority on
                     // the SIMD follows (4.96-5.02 -> 4.79-4.83 ms on the headline; more levels or other thresholds: the same).
                     if (!seen) __builtin_amdgcn_s_setprio(0);
                     else if (P < (uint64_t)(4u * kTile * 7u)) __builtin_amdgcn_s_setprio(2);
                     else __builtin_amdgcn_s_setprio(1);
-#endif
                     copy_out(seen ? ex : wait_place());
                     limit = gap();
                 }
@@ -1044,11 +1039,9 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
                 const bool seen = place_in_lds(pl);
                 const bool must = fits && ((P + tile_bits + 31u) >> 5) >= (uint64_t)limit;
                 if (seen || must) {
-#if DRX_ES_PRIO
                     if (!seen) __builtin_amdgcn_s_setprio(0);
                     else if (P < (uint64_t)(4u * kTile * 7u)) __builtin_amdgcn_s_setprio(2);
                     else __builtin_amdgcn_s_setprio(1);
-#endif
                     copy_out(seen ? pl : wait_place());
                     limit = gap();
                 }

@@ -206,7 +206,6 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 #define DRX_DBG_RAGGED_ONE_LANES_LAUNCH 131072u /* ragged batches: one decode launch behind both header walks */
 #define DRX_DBG_STREAM_THREE_WGS 262144u        /* the persistent encoders on three workgroups (every wavefront goes around its ring) */
 #define DRX_DBG_FORCE_STREAM 524288u            /* the persistent encoder (encode_impl 2) whatever the batch's size and code length */
-#define DRX_DBG_NW_ONE_WAVE 1048576u            /* -DDRX_DEC_NW builds: the staged flush's kernel off, one wavefront per workgroup */
 #define DRX_DBG_IIR_SEPARATE 2097152u           /* general filters behind the block decoder: always the separate inverse-filter pass */
 #define DRX_DBG_FORCE_STREAM_SEGS 4194304u      /* the persistent encoder's segment form (encode_impl 2, uniform), segments of ~1024 samples */
 #define DRX_DBG_WALK_BY_SCAN 8388608u           /* the chunk-wide header walk by reading the whole chunk instead of chasing 64 chains */

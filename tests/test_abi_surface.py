@@ -26,12 +26,14 @@ def test_hip_library_exports_declared_abi():
     assert b"gfx950" in lib.drx_version()
 
 
-def test_python_constants_match_header_defines():
+def test_python_constants_match_every_header_define():
     # DRX_DBG_* / DRX_ENC_* / DRX_PATH_* of include/deltarice_hip.h, as deltarice_amd._lib exports them (DBG_*, ENC_*, PATH_*)
     from deltarice_amd import _lib
     txt = open(os.path.join(ROOT, "include", "deltarice_hip.h")).read()
     defs = dict(re.findall(r"^#define DRX_((?:DBG|ENC|PATH)_\w+) (\d+)u\b", txt, flags=re.M))
-    assert len(defs) >= 28
+    # every such define is parsed (none escapes the pattern), and none of the 27 goes missing
+    assert len(defs) == len(re.findall(r"^#define DRX_(?:DBG|ENC|PATH)_", txt, flags=re.M))
+    assert len(defs) >= 27
     for name, value in defs.items():
         assert getattr(_lib, name) == int(value), name
     assert {n for n in dir(_lib) if re.fullmatch(r"(DBG|ENC|PATH)_\w+", n)} == set(defs)
