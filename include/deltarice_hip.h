@@ -31,6 +31,13 @@
  * context's stream and returns without waiting.  Errors found on the device
  * (capacity, corrupt stream) are collected by drx_plan_finish().
  * There is no CPU fallback anywhere behind this ABI.
+ *
+ * Buffers.  A device pointer may have any alignment of its element type (int16 samples: 2 bytes, uint32 words: 4,
+ * uint64 offsets: 8), such as a view at any element of a larger tensor or a stream that starts at any word of a larger
+ * encoded buffer.  A call writes nothing outside [ptr, ptr + n) of the buffers it writes: out_cap_words words of an
+ * encode's output, also when it fails with DRX_ERR_CAPACITY; n_chunks + 1 offsets; total_samples decoded samples.  Its
+ * results depend neither on what those buffers held before the call nor on the words outside [0, in_words) of a decoder's
+ * input.  tests/test_gpu_placement.py holds every encoder and decoder route to this.
  */
 #ifndef DELTARICE_HIP_H
 #define DELTARICE_HIP_H

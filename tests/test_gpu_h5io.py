@@ -111,3 +111,29 @@ def test_direct_read_rejects_what_it_does_not_handle(env, h5tool, tmp_path):
     with pytest.raises(dr.DeltaRiceError) as e:
         h5io.read(ctx, str(f), "test", y[:100])
     assert e.value.status in (3, 5)
+
+
+def test_direct_path_with_unaligned_guarded_views(env, h5tool, tmp_path):
+    """Write from and read into views at an odd sample offset of guarded tensors: 12 whole chunks (no edge chunk, whose copy
+    through a buffer of its own would hide a store past the output), read into a view longer than the dataset."""
+    from oracle import oracle as O
+    ctx, h5io = env
+    rows, cols, crows, M, L = 96, 1000, 8, 8, 1000
+    n, g = rows * cols, 2048  # (g: 4 KiB of sentinel on each side)
+    x = np.random.default_rng(96).normal(0, 10, n).astype(np.int16)
+    src = torch.full((g + 1 + n + g,), -0x8000, dtype=torch.int16, device=ctx.device)
+    src[g + 1:g + 1 + n] = torch.from_numpy(x).to(ctx.device)
+    f = tmp_path / "views.h5"
+    h5io.write(ctx, str(f), "test", src[g + 1:g + 1 + n], rows, cols, crows, M, L)
+    assert bool((src[:g + 1] == -0x8000).all()) and bool((src[g + 1 + n:] == -0x8000).all())
+    nc = int(h5tool("chunks", f, tmp_path / "chunk").stdout)
+    assert nc == rows // crows
+    for c in range(nc):
+        want = O.encode_chunk(x[c * crows * cols:(c + 1) * crows * cols], (M, L))
+        assert np.array_equal(np.fromfile(f"{tmp_path}/chunk.{c}", np.uint32), want), c
+    extra = 777  # samples of the view behind the dataset
+    for off in (1, 7):
+        dst = torch.full((g + off + n + extra + g,), 0x5A5A, dtype=torch.int16, device=ctx.device)
+        h5io.read(ctx, str(f), "test", dst[g + off:g + off + n + extra])
+        assert np.array_equal(dst[g + off:g + off + n].cpu().numpy(), x), off
+        assert bool((dst[:g + off] == 0x5A5A).all()) and bool((dst[g + off + n:] == 0x5A5A).all()), off

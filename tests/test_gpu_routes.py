@@ -22,6 +22,8 @@ BATCHES = {
     "fir4": ([5000 * 100] * 3, [5000] * 3, 8, (1, -1, 1, -1), 20),
     "fir5": ([5000 * 3] * 3, [1000] * 3, 8, (1, -1, 1, -1, 1), 40),
     "wide-fused": ([200 * 7000] * 4, [7000] * 4, 64, None, 80),
+    # as many long waveforms as the block decoder keeps resident: the inverse filter inside it (DRX_PATH_IIR_FUSED)
+    "iir-fused": ([800 * 9001 - 9001 // 3] * 2, [9001] * 2, 8, (1, -1, 1, -1), 10),
 }
 
 # every flag alone, and the combinations the other tests use
@@ -83,6 +85,11 @@ EXPECTED = {
         0: "1/4 1/2 1/2 1/4 1/4 1/4 1/4 1/4 1/4 1/4 1/4 1/4 1/4 1/4 1/2 1/2 1/2 1/2 1/2",
         1: "3/4 3/2 3/2 3/4 3/4 2/4 4/4 4/4 3/4 3/4 3/4 3/4 3/4 3/4 3/2 3/2 3/2 3/2 3/2",
         2: "3/4 3/2 3/2 3/4 3/4 2/4 4/4 4/4 3/4 5/4 3/4 6/4 3/4 3/4 5/2 6/2 5/2 3/2 3/2",
+    },
+    "iir-fused": {
+        0: "1/68 1/2 1/2 1/68 1/68 1/68 1/68 1/68 1/68 1/68 1/36 1/68 1/68 1/68 1/2 1/2 1/2 1/2 1/2",
+        1: "3/68 3/2 3/2 3/68 3/68 3/68 4/68 3/68 3/68 3/68 3/36 3/68 3/68 3/68 3/2 3/2 3/2 3/2 3/2",
+        2: "3/68 3/2 3/2 3/68 3/68 3/68 4/68 3/68 3/68 5/68 3/36 6/68 3/68 3/68 5/2 6/2 5/2 3/2 3/2",
     },
 }
 
