@@ -21,6 +21,40 @@
 
 using namespace drx;
 
+// Device and pinned host memory of a context or a plan: every buffer of either is allocated here and freed by the destructor,
+// which runs with the owner's device current (drx_ctx_destroy() and plan_free() hold a DeviceGuard).
+class Buffers {
+    struct Buf { void *ptr; bool pinned; };
+    std::vector<Buf> bufs_;
+    static void free_buf(const Buf &b) {
+        if (b.pinned) (void)hipHostFree(b.ptr);
+        else (void)hipFree(b.ptr);
+    }
+
+  public:
+    Buffers() = default;
+    Buffers(const Buffers &) = delete;
+    Buffers &operator=(const Buffers &) = delete;
+    ~Buffers() { for (const Buf &b : bufs_) free_buf(b); }
+    template <typename T> hipError_t alloc(T **out, size_t bytes, bool pinned = false) {
+        void *ptr = nullptr;
+        const hipError_t e = pinned ? hipHostMalloc(&ptr, bytes, hipHostMallocDefault) : hipMalloc(&ptr, bytes);
+        if (e != hipSuccess) return e;
+        bufs_.push_back(Buf{ptr, pinned});
+        *out = static_cast<T *>(ptr);
+        return hipSuccess;
+    }
+    void release(const void *ptr) {  // frees one buffer now (nullptr: none)
+        if (!ptr) return;
+        for (size_t i = 0; i < bufs_.size(); ++i)
+            if (bufs_[i].ptr == ptr) {
+                free_buf(bufs_[i]);
+                bufs_.erase(bufs_.begin() + i);
+                return;
+            }
+    }
+};
+
 struct drx_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -33,6 +67,7 @@ struct drx_ctx {
     int profile = 0;      // bracket kernels with HIP events (drx_plan_last_timings)
     uint32_t debug_flags = 0;  // Geom::dbg
     std::string last_error;
+    Buffers mem;  // owns the buffers below
     // scratch of the one-chunk host path (drx_filter_chunk_host), grown on demand
     void *d_raw = nullptr;   size_t raw_cap = 0;
     void *d_enc = nullptr;   size_t enc_cap = 0;
@@ -40,7 +75,7 @@ struct drx_ctx {
     void *h_pin = nullptr;   size_t pin_cap = 0;
     void *h_stage = nullptr; size_t stage_cap = 0;  // drx_ctx_host_staging(): the direct-chunk HDF5 path's staging buffer
     // the host path's plan is kept between calls: HDF5 calls the filter once per chunk with the same
-    // geometry, and creating a plan costs eight hipMalloc/hipFree pairs (about a millisecond)
+    // geometry, and creating a plan costs its allocations and frees (about a millisecond)
     drx_plan *host_plan = nullptr;
     uint32_t hp_samples = 0, hp_L = 0, hp_k = 0, hp_ntaps = 0;
     int32_t hp_taps[DRX_MAX_TAPS] = {0};
@@ -69,10 +104,9 @@ struct DeviceGuard {
 
 struct drx_plan {
     drx_ctx *ctx = nullptr;
-    Geom G{};
-    uint64_t total_samples = 0;
+    Geom G{};      // its device tables (chunks, walk lists, taps, ...) and pinned host_words are buffers of mem, held nowhere else
+    Buffers mem;   // owns every buffer of the plan
     uint64_t max_words = 0;
-    ChunkDesc *d_chunks = nullptr;
     uint32_t *d_wave_words = nullptr;  // n_i
     uint32_t *d_wave_rel = nullptr;    // encode: header position relative to chunk start
     uint64_t *d_wave_off = nullptr;    // decode: absolute header position
@@ -81,25 +115,14 @@ struct drx_plan {
     size_t scan_bytes = 0;             // ... its size
     uint32_t last_enc_path = 0;         // DRX_ENC_* of the last drx_encode
     uint64_t enc_words_per_wave = 0;   // of the plan's last encode (0: none yet)
-    int32_t *d_taps = nullptr;         // general prediction filter (nullptr: delta)
-    uint32_t *d_seg_bits = nullptr;    // few long waveforms: bits and bit position of every 8192-sample segment,
-    uint64_t *d_seg_pos = nullptr;     // allocated by the first encode that needs them
-    uint64_t *d_seg_unit_base = nullptr;  // ragged plans the segment encoder takes
-    uint32_t *d_pc_wg_base = nullptr;     // ragged plans the pieces encoder takes: first workgroup of every chunk
+    uint32_t *d_seg_bits = nullptr;    // segment encoder: bits and bit position of every segment (both or neither:
+    uint64_t *d_seg_pos = nullptr;     // seg_scratch())
     uint64_t *d_pc_scan = nullptr;        // pieces encoder: look-back entry per workgroup + ticket
     uint64_t pc_wgs = 0;                  // its workgroups (0: the plan's geometry never takes it)
     void *d_pw = nullptr;              // a handful of chunks: candidate lists of the parallel header walk
     void *d_blk = nullptr;             // few waveforms: unit table, look-back state and flags of the block-parallel decoder
-    uint32_t *d_walk_lists = nullptr;  // ragged plans: chunk indices, short-waveform chunks first
-    uint2 *d_rag_order = nullptr;      // ragged plans: decode wavefronts, longest WaveformLength first
-    uint32_t *d_iir_tab = nullptr;     // general filter behind the block decoder (drx_iir.hip): matrix tables of the plan's filter,
-    uint64_t *d_iir_state = nullptr;   // look-back state of its tiles (+ ticket), and (ragged plans) the first tile of every chunk
-    uint64_t *d_iir_chunk_base = nullptr;
-    uint32_t *d_blk_list = nullptr;    // ragged plans the block decoder takes: waveform indices, class by class
-    uint32_t n_short = 0, n_long = 0;
     DevStatus *d_status = nullptr;
     DevStatus *h_status = nullptr;  // pinned
-    uint64_t *h_enc_words = nullptr;  // pinned, written by the encoders themselves (Geom::host_words): the last encode's word count, 0 = none yet
     bool last_was_encode = false;
     uint32_t last_path = 0;  // DRX_PATH_* of the last decode
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -125,6 +148,22 @@ static drx_status fail(drx_ctx *ctx, drx_status st, const char *fmt, ...) {
         if (e_ != hipSuccess)                                                                   \
             return fail((ctx), DRX_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// n entries of a host table into the plan's device copy *view, allocated by the first upload (the same n every time);
+// n = 0 leaves *view as it is (a planner's empty table: nullptr, the path is not taken)
+template <typename T> static hipError_t upload(drx_plan *p, const T *host, size_t n, const T **view) {
+    if (!n) return hipSuccess;
+    T *d = const_cast<T *>(*view);
+    if (!d) {
+        const hipError_t e = p->mem.alloc(&d, n * sizeof(T));
+        if (e != hipSuccess) return e;
+        *view = d;
+    }
+    return hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice);
+}
+template <typename T> static hipError_t upload(drx_plan *p, const std::vector<T> &tab, const T **view) {
+    return upload(p, tab.data(), tab.size(), view);
+}
 
 extern "C" {
 
@@ -212,16 +251,11 @@ void drx_ctx_destroy(drx_ctx *c) {
     if (!c) return;
     DeviceGuard guard(c->device);
     if (c->host_plan) plan_free(c->host_plan);
-    if (c->d_raw) (void)hipFree(c->d_raw);
-    if (c->d_enc) (void)hipFree(c->d_enc);
-    if (c->d_off) (void)hipFree(c->d_off);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     if (c->side.s) (void)hipStreamDestroy(c->side.s);
     if (c->side.fork) (void)hipEventDestroy(c->side.fork);
     if (c->side.join) (void)hipEventDestroy(c->side.join);
-    delete c;
+    delete c;  // (and its buffers)
 }
 
 drx_status drx_ctx_synchronize(drx_ctx *c) {
@@ -237,9 +271,9 @@ drx_status drx_ctx_host_staging(drx_ctx *ctx, size_t bytes, void **host_out) {
     if (!ctx || !host_out) return DRX_ERR_ARG;
     DRX_ON_DEVICE(ctx);
     if (ctx->stage_cap < bytes) {
-        if (ctx->h_stage) { (void)hipStreamSynchronize(ctx->stream); (void)hipHostFree(ctx->h_stage); ctx->h_stage = nullptr; ctx->stage_cap = 0; }
+        if (ctx->h_stage) { (void)hipStreamSynchronize(ctx->stream); ctx->mem.release(ctx->h_stage); ctx->h_stage = nullptr; ctx->stage_cap = 0; }
         const size_t want = bytes + bytes / 8 + 4096;
-        const hipError_t e = hipHostMalloc(&ctx->h_stage, want, hipHostMallocDefault);
+        const hipError_t e = ctx->mem.alloc(&ctx->h_stage, want, true);
         if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "pinned staging buffer of %zu bytes: %s", want, hipGetErrorString(e));
         ctx->stage_cap = want;
     }
@@ -271,11 +305,15 @@ drx_status drx_ctx_set_option(drx_ctx *c, const char *key, int64_t value) {
     return DRX_ERR_ARG;
 }
 
+// the context's host-path buffers: a call that needs more replaces the buffer (freeing the old one first: every call grows
+// them again before use)
 static drx_status grow(drx_ctx *ctx, void **ptr, size_t *cap, size_t need, bool pinned) {
     if (*cap >= need) return DRX_OK;
     size_t want = need + need / 4 + 4096;
-    if (*ptr) { if (pinned) (void)hipHostFree(*ptr); else (void)hipFree(*ptr); *ptr = nullptr; *cap = 0; }
-    hipError_t e = pinned ? hipHostMalloc(ptr, want, hipHostMallocDefault) : hipMalloc(ptr, want);
+    ctx->mem.release(*ptr);
+    *ptr = nullptr;
+    *cap = 0;
+    hipError_t e = ctx->mem.alloc(ptr, want, pinned);
     if (e != hipSuccess) return fail(ctx, DRX_ERR_DEVICE, "allocation of %zu bytes failed: %s", want, hipGetErrorString(e));
     *cap = want;
     return DRX_OK;
@@ -284,271 +322,165 @@ static drx_status grow(drx_ctx *ctx, void **ptr, size_t *cap, size_t need, bool 
 static void plan_free(drx_plan *p) {
     if (!p) return;
     DeviceGuard guard(p->ctx->device);
-    if (p->d_chunks) (void)hipFree(p->d_chunks);
-    if (p->d_wave_words) (void)hipFree(p->d_wave_words);
-    if (p->d_wave_rel) (void)hipFree(p->d_wave_rel);
-    if (p->d_wave_off) (void)hipFree(p->d_wave_off);
-    if (p->d_chunk_words) (void)hipFree(p->d_chunk_words);
-    if (p->d_scan) (void)hipFree(p->d_scan);
-    if (p->d_taps) (void)hipFree(p->d_taps);
-    if (p->d_walk_lists) (void)hipFree(p->d_walk_lists);
-    if (p->d_rag_order) (void)hipFree(p->d_rag_order);
-    if (p->d_iir_tab) (void)hipFree(p->d_iir_tab);
-    if (p->d_iir_state) (void)hipFree(p->d_iir_state);
-    if (p->d_iir_chunk_base) (void)hipFree(p->d_iir_chunk_base);
-    if (p->d_blk_list) (void)hipFree(p->d_blk_list);
-    if (p->d_seg_bits) (void)hipFree(p->d_seg_bits);
-    if (p->d_seg_pos) (void)hipFree(p->d_seg_pos);
-    if (p->d_seg_unit_base) (void)hipFree(p->d_seg_unit_base);
-    if (p->d_pc_wg_base) (void)hipFree(p->d_pc_wg_base);
-    if (p->d_pc_scan) (void)hipFree(p->d_pc_scan);
-    if (p->d_pw) (void)hipFree(p->d_pw);
-    if (p->d_blk) (void)hipFree(p->d_blk);
-    if (p->d_status) (void)hipFree(p->d_status);
-    if (p->h_status) (void)hipHostFree(p->h_status);
-    if (p->h_enc_words) (void)hipHostFree(p->h_enc_words);
     for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
-    delete p;
+    delete p;  // (and its buffers)
 }
 
-static drx_status plan_alloc(drx_ctx *ctx, drx_plan *p) {  // (callers hold the device guard)
-    const uint64_t W = p->G.total_waves ? p->G.total_waves : 1;
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_wave_words, W * sizeof(uint32_t)));
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_wave_rel, W * sizeof(uint32_t)));
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_wave_off, W * sizeof(uint64_t)));
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_chunk_words, (p->G.n_chunks + 1) * sizeof(uint64_t)));
+// the segment encoder's bits and bit positions per unit: both or neither
+static hipError_t seg_scratch(drx_plan *p) {
+    const uint64_t units = long_batch_units(p->G);
+    uint32_t *bits = nullptr;
+    uint64_t *pos = nullptr;
+    hipError_t e = p->mem.alloc(&bits, units * sizeof(uint32_t));
+    if (e == hipSuccess && (e = p->mem.alloc(&pos, units * sizeof(uint64_t))) != hipSuccess) p->mem.release(bits);
+    if (e != hipSuccess) return e;
+    p->d_seg_bits = bits;
+    p->d_seg_pos = pos;
+    return hipSuccess;
+}
+
+// Buffers of every plan
+static drx_status plan_alloc(drx_plan *p) {
+    drx_ctx *ctx = p->ctx;
+    Geom &G = p->G;
+    const uint64_t W = G.total_waves ? G.total_waves : 1;
+    DRX_HIP(ctx, p->mem.alloc(&p->d_wave_words, W * sizeof(uint32_t)));
+    DRX_HIP(ctx, p->mem.alloc(&p->d_wave_rel, W * sizeof(uint32_t)));
+    DRX_HIP(ctx, p->mem.alloc(&p->d_wave_off, W * sizeof(uint64_t)));
+    DRX_HIP(ctx, p->mem.alloc(&p->d_chunk_words, (G.n_chunks + 1) * sizeof(uint64_t)));
     // (every user clears what it reads on the stream before its launch.  k_encode_stream: size[W] | place[W] | control; its
     // segment form, where it is the default choice: size[T] | place[2 T] | control with T tickets at the shortest segments)
     uint64_t words = 2 * W + 192;
-    if (stream_segs_admits(p->G) && p->G.u_wave_len >= kEsSegsFromLen) words = std::max(words, segs_scan_words(p->G, kEsSegMinLen));
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_scan, p->scan_bytes = words * sizeof(uint64_t)));
-    DRX_HIP(ctx, hipMalloc((void **)&p->d_status, sizeof(DevStatus)));
-    DRX_HIP(ctx, hipHostMalloc((void **)&p->h_status, sizeof(DevStatus), hipHostMallocDefault));
+    if (stream_segs_admits(G) && G.u_wave_len >= kEsSegsFromLen) words = std::max(words, segs_scan_words(G, kEsSegMinLen));
+    DRX_HIP(ctx, p->mem.alloc(&p->d_scan, p->scan_bytes = words * sizeof(uint64_t)));
+    DRX_HIP(ctx, p->mem.alloc(&p->d_status, sizeof(DevStatus)));
+    DRX_HIP(ctx, p->mem.alloc(&p->h_status, sizeof(DevStatus), true));
     memset(p->h_status, 0, sizeof(DevStatus));
-    DRX_HIP(ctx, hipHostMalloc((void **)&p->h_enc_words, sizeof(uint64_t), hipHostMallocDefault));
-    *p->h_enc_words = 0;
-    p->G.host_words = p->h_enc_words;  // (pinned host memory is device-visible at the same address)
+    DRX_HIP(ctx, p->mem.alloc(&G.host_words, sizeof(uint64_t), true));  // (pinned host memory is device-visible at the same address)
+    *G.host_words = 0;
     for (hipEvent_t &e : p->ev) DRX_HIP(ctx, hipEventCreate(&e));
     return DRX_OK;
 }
 
-// Scratch that only some geometries need (segment encoder, long-waveform decoder, parallel header walks): allocated
-// with the plan, so that drx_encode / drx_decode never allocate.
-static drx_status plan_alloc_scratch(drx_ctx *ctx, drx_plan *p) {
-    if (long_batch(p->G)) {
-        const uint64_t units = long_batch_units(p->G);
-        DRX_HIP(ctx, hipMalloc((void **)&p->d_seg_bits, units * sizeof(uint32_t)));
-        DRX_HIP(ctx, hipMalloc((void **)&p->d_seg_pos, units * sizeof(uint64_t)));
+// Ragged plans: the chunk table, and each path's tables as its planner decided them from the host's copy
+static drx_status plan_ragged(drx_plan *p, const std::vector<ChunkDesc> &desc) {
+    Geom &G = p->G;
+    const ChunkDesc *d = desc.data();
+    std::vector<uint32_t> walk_lists;
+    std::vector<uint2> order;
+    decode_plan_ragged(G, d, &walk_lists, &order);
+    const std::vector<uint64_t> unit_base = segments_plan_ragged(G, d);
+    const std::vector<uint32_t> wg_base = pieces_plan_ragged(G, d);
+    p->pc_wgs = wg_base.empty() ? 0 : wg_base.back();
+    // few long waveforms: the block-parallel decoder and, behind it, the in-place inverse of a general filter
+    const std::vector<uint32_t> blk_list = blocks_plan_ragged(G, d);
+    std::vector<uint64_t> tile_base;
+    if (!blk_list.empty()) {
+        tile_base.resize(G.n_chunks + 1);
+        G.iir_n_tiles = iir_tiles(G, d, tile_base.data());
     }
-    if (const uint64_t nb = par_walk_scratch_bytes(p->G)) DRX_HIP(ctx, hipMalloc(&p->d_pw, nb));
-    if (const uint64_t nb = blocks_scratch_bytes(p->G)) {
-        DRX_HIP(ctx, hipMalloc(&p->d_blk, nb));
+    hipError_t e = upload(p, desc, &G.chunks);
+    if (e == hipSuccess) e = upload(p, walk_lists, &G.walk_short);
+    if (e == hipSuccess) e = upload(p, order, &G.rag_order);
+    if (e == hipSuccess) e = upload(p, unit_base, &G.seg_unit_base);
+    if (e == hipSuccess) e = upload(p, wg_base, &G.pc_wg_base);
+    if (e == hipSuccess) e = upload(p, blk_list, &G.rag_blk_list);
+    if (e == hipSuccess) e = upload(p, tile_base, &G.iir_chunk_tile_base);
+    if (e != hipSuccess) return fail(p->ctx, DRX_ERR_DEVICE, "chunk table upload failed: %s", hipGetErrorString(e));
+    G.walk_long = G.walk_short + G.n_short;
+    return DRX_OK;
+}
+
+// Scratch of the paths the plan's geometry takes by default (segment and pieces encoders, parallel header walks, block decoder
+// and the inverse filter behind it).  A route that a debug flag forces gets what it lacks from drx_encode (route_scratch()).
+static drx_status plan_alloc_scratch(drx_plan *p) {
+    drx_ctx *ctx = p->ctx;
+    Geom &G = p->G;
+    if (long_batch(G)) DRX_HIP(ctx, seg_scratch(p));
+    if (const uint64_t nb = par_walk_scratch_bytes(G)) DRX_HIP(ctx, p->mem.alloc(&p->d_pw, nb));
+    if (const uint64_t nb = blocks_scratch_bytes(G)) {
+        DRX_HIP(ctx, p->mem.alloc(&p->d_blk, nb));
         // ... and, should the plan get a general prediction filter, the look-back state of the in-place inverse filter
-        if (p->G.uniform) p->G.iir_n_tiles = iir_tiles(p->G, nullptr, nullptr);
-        DRX_HIP(ctx, hipMalloc((void **)&p->d_iir_state, (p->G.iir_n_tiles + 1) * sizeof(uint64_t)));
-        p->G.iir_state = p->d_iir_state;
+        if (G.uniform) G.iir_n_tiles = iir_tiles(G, nullptr, nullptr);
+        DRX_HIP(ctx, p->mem.alloc(&G.iir_state, (G.iir_n_tiles + 1) * sizeof(uint64_t)));
     }
-    if (p->G.uniform && pieces_admits(p->G)) p->pc_wgs = pieces_workgroups(p->G, nullptr);  // (ragged: drx_plan_create)
-    if (p->pc_wgs) DRX_HIP(ctx, hipMalloc((void **)&p->d_pc_scan, pieces_scan_words(p->G, p->pc_wgs) * sizeof(uint64_t)));
+    if (G.uniform && pieces_admits(G)) p->pc_wgs = pieces_workgroups(G);  // (ragged: pieces_plan_ragged())
+    if (p->pc_wgs) DRX_HIP(ctx, p->mem.alloc(&p->d_pc_scan, pieces_scan_words(G, p->pc_wgs) * sizeof(uint64_t)));
+    return DRX_OK;
+}
+
+// One chunk of a plan: N samples (< 2^31: int totalNumber, src/deltaRice.c:389) in waveforms of wave_len (0: the whole chunk)
+static drx_status chunk_desc(drx_ctx *ctx, uint64_t c, uint32_t N, uint32_t wave_len, ChunkDesc *out) {
+    if (N == 0 || N > 0x7fffffffu) return fail(ctx, DRX_ERR_ARG, "chunk %llu: bad sample count %u", (unsigned long long)c, N);
+    const uint32_t L = wave_len ? wave_len : N;
+    if (L > 0x7fffffffu) return fail(ctx, DRX_ERR_ARG, "chunk %llu: bad waveform length", (unsigned long long)c);
+    *out = ChunkDesc{0, 0, N, L, (uint32_t)(((uint64_t)N + L - 1) / L), 0};
+    return DRX_OK;
+}
+
+// The one plan builder behind drx_plan_create (per_chunk: an entry of each array per chunk) and drx_plan_create_uniform (the
+// first entries hold every chunk's).  A batch whose chunks are all equal is uniform; a ragged one has the host's chunk table.
+static drx_status plan_create(drx_ctx *ctx, uint64_t n_chunks, const uint32_t *chunk_samples, const uint32_t *chunk_wave_len,
+                              bool per_chunk, uint32_t rice_k, drx_plan **out) {
+    if (!ctx || !out || !n_chunks || !chunk_samples || !chunk_wave_len) return DRX_ERR_ARG;
+    *out = nullptr;
+    if (rice_k > 15) return fail(ctx, DRX_ERR_ARG, "rice_k %u out of range 0..15", rice_k);
+    if (n_chunks > 0xffffffffull) return fail(ctx, DRX_ERR_ARG, "too many chunks");
+    ChunkDesc first;
+    if (const drx_status st = chunk_desc(ctx, 0, chunk_samples[0], chunk_wave_len[0], &first)) return st;
+    std::vector<ChunkDesc> desc;
+    bool uniform = true;
+    if (per_chunk) {
+        desc.resize(n_chunks);
+        uint64_t soff = 0, wbase = 0;
+        for (uint64_t c = 0; c < n_chunks; ++c) {
+            if (const drx_status st = chunk_desc(ctx, c, chunk_samples[c], chunk_wave_len[c], &desc[c])) return st;
+            desc[c].sample_off = soff;
+            desc[c].wave_base = wbase;
+            uniform = uniform && desc[c].n_samples == first.n_samples && desc[c].wave_len == first.wave_len;
+            soff += desc[c].n_samples;
+            wbase += desc[c].n_waves;
+        }
+        if (uniform) desc.clear();
+    }
+    DRX_ON_DEVICE(ctx);  // every allocation and table upload below lands on the context's device
+    drx_plan *p = new (std::nothrow) drx_plan;
+    if (!p) return DRX_ERR_NOMEM;
+    p->ctx = ctx;
+    Geom &G = p->G;
+    G.n_chunks = n_chunks;
+    G.uniform = uniform ? 1u : 0u;
+    G.u_n_samples = first.n_samples;
+    G.u_wave_len = first.wave_len;
+    G.u_n_waves = first.n_waves;
+    G.k = rice_k;
+    // 25 bits per sample worst case, rounded up per waveform, + headers
+    auto max_words = [](const ChunkDesc &d) { return 1 + 2ull * d.n_waves + (((uint64_t)d.n_samples * 25u + 31u) >> 5); };
+    if (uniform) {
+        G.total_samples = n_chunks * first.n_samples;
+        G.total_waves = n_chunks * first.n_waves;
+        p->max_words = n_chunks * max_words(first);
+    } else {
+        G.total_samples = desc.back().sample_off + desc.back().n_samples;
+        G.total_waves = desc.back().wave_base + desc.back().n_waves;
+        for (const ChunkDesc &d : desc) p->max_words += max_words(d);
+    }
+    drx_status st = plan_alloc(p);
+    if (st == DRX_OK && !uniform) st = plan_ragged(p, desc);
+    if (st == DRX_OK) st = plan_alloc_scratch(p);
+    if (st != DRX_OK) { plan_free(p); return st; }
+    *out = p;
     return DRX_OK;
 }
 
 drx_status drx_plan_create(drx_ctx *ctx, uint64_t n_chunks, const uint32_t *chunk_samples,
                            const uint32_t *chunk_wave_len, uint32_t rice_k, drx_plan **out) {
-    if (!ctx || !out || !n_chunks || !chunk_samples || !chunk_wave_len) return DRX_ERR_ARG;
-    *out = nullptr;
-    if (rice_k > 15) return fail(ctx, DRX_ERR_ARG, "rice_k %u out of range 0..15", rice_k);
-    if (n_chunks > 0xffffffffull) return fail(ctx, DRX_ERR_ARG, "too many chunks");
-    DRX_ON_DEVICE(ctx);  // every allocation and table upload below, plan_alloc_scratch() included, lands on the context's device
-    std::vector<ChunkDesc> desc(n_chunks);
-    uint64_t soff = 0, wbase = 0, maxw = 0;
-    bool uniform = true;
-    for (uint64_t c = 0; c < n_chunks; ++c) {
-        const uint32_t N = chunk_samples[c];
-        // one chunk holds < 2^31 samples (int totalNumber, src/deltaRice.c:389)
-        if (N == 0 || N > 0x7fffffffu) return fail(ctx, DRX_ERR_ARG, "chunk %llu: bad sample count %u", (unsigned long long)c, N);
-        uint32_t L = chunk_wave_len[c] ? chunk_wave_len[c] : N;
-        if (L > 0x7fffffffu) return fail(ctx, DRX_ERR_ARG, "chunk %llu: bad waveform length", (unsigned long long)c);
-        const uint32_t W = (uint32_t)(((uint64_t)N + L - 1) / L);
-        desc[c] = ChunkDesc{soff, wbase, N, L, W, 0};
-        if (N != chunk_samples[0] || L != (chunk_wave_len[0] ? chunk_wave_len[0] : chunk_samples[0])) uniform = false;
-        soff += N;
-        wbase += W;
-        // 25 bits per sample worst case, rounded up per waveform, + headers
-        maxw += 1 + W + (((uint64_t)N * 25u + 31u) >> 5) + W;
-    }
-    drx_plan *p = new (std::nothrow) drx_plan;
-    if (!p) return DRX_ERR_NOMEM;
-    p->ctx = ctx;
-    p->total_samples = soff;
-    p->max_words = maxw;
-    p->G.n_chunks = n_chunks;
-    p->G.total_waves = wbase;
-    p->G.uniform = uniform ? 1u : 0u;
-    p->G.u_n_samples = desc[0].n_samples;
-    p->G.u_wave_len = desc[0].wave_len;
-    p->G.u_n_waves = desc[0].n_waves;
-    p->G.k = rice_k;
-    p->G.total_samples = soff;
-    drx_status st = plan_alloc(ctx, p);
-    if (st == DRX_OK && !uniform) {
-        hipError_t e = hipMalloc((void **)&p->d_chunks, n_chunks * sizeof(ChunkDesc));
-        if (e == hipSuccess) e = hipMemcpy(p->d_chunks, desc.data(), n_chunks * sizeof(ChunkDesc), hipMemcpyHostToDevice);
-        // walk lists: chunks of short waveforms are walked through LDS, the others hop by hop
-        std::vector<uint32_t> lists;
-        for (uint64_t c = 0; c < n_chunks; ++c) if (desc[c].wave_len <= kWalkShortLenHost) lists.push_back((uint32_t)c);
-        p->n_short = (uint32_t)lists.size();
-        for (uint64_t c = 0; c < n_chunks; ++c) if (desc[c].wave_len > kWalkShortLenHost) lists.push_back((uint32_t)c);
-        p->n_long = (uint32_t)lists.size() - p->n_short;
-        if (e == hipSuccess) e = hipMalloc((void **)&p->d_walk_lists, lists.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpy(p->d_walk_lists, lists.data(), lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        uint32_t max_groups = 0;
-        for (uint64_t c = 0; c < n_chunks; ++c) max_groups = std::max(max_groups, (desc[c].n_waves + 63u) / 64u);
-        p->G.walk_short = p->d_walk_lists;
-        p->G.walk_long = p->d_walk_lists ? p->d_walk_lists + p->n_short : nullptr;
-        p->G.n_short = p->n_short;
-        p->G.n_long = p->n_long;
-        p->G.max_groups = max_groups;
-        {
-            uint32_t max_len = 0;
-            for (uint64_t c = 0; c < n_chunks; ++c) max_len = std::max(max_len, desc[c].wave_len);
-            p->G.max_wave_len64 = 64ull * max_len;
-        }
-        // decode order: wavefronts (groups of 64 waveforms of one chunk) by decreasing WaveformLength
-        {
-            std::vector<uint32_t> by_len(n_chunks);
-            for (uint64_t c = 0; c < n_chunks; ++c) by_len[c] = (uint32_t)c;
-            std::stable_sort(by_len.begin(), by_len.end(), [&](uint32_t a, uint32_t b) { return desc[a].wave_len > desc[b].wave_len; });
-            std::vector<uint2> order;
-            uint64_t n_long_groups = 0;
-            for (uint32_t c : by_len)
-                for (uint32_t j = 0; j < (desc[c].n_waves + 63u) / 64u; ++j) {
-                    order.push_back(make_uint2(c, j));
-                    if (desc[c].wave_len > kWalkShortLenHost) ++n_long_groups;
-                }
-            if (order.size() <= 0x7fffffffull) {
-                if (e == hipSuccess) e = hipMalloc((void **)&p->d_rag_order, order.size() * sizeof(uint2));
-                if (e == hipSuccess) e = hipMemcpy(p->d_rag_order, order.data(), order.size() * sizeof(uint2), hipMemcpyHostToDevice);
-                p->G.rag_order = p->d_rag_order;
-                p->G.rag_groups = (uint32_t)order.size();
-                p->G.rag_groups_long = (uint32_t)n_long_groups;
-            }
-        }
-        // parallel header walks for small ragged batches: every long-waveform chunk within the chunk-wide walk's
-        // capacity, every short-waveform chunk worth the two block passes (same limits as for uniform batches)
-        {
-            bool ok = p->n_long <= kPwMaxChunks && p->n_short <= kPwMaxChunks;
-            uint64_t bmax = 0;
-            uint32_t min_len = 0xffffffffu, min_long_waves = 0xffffffffu;
-            for (uint64_t c = 0; c < n_chunks && ok; ++c) {
-                const ChunkDesc &d = desc[c];
-                if (d.wave_len > kWalkShortLenHost) {
-                    ok = d.n_waves <= kPwMaxWaves;
-                    min_long_waves = std::min(min_long_waves, d.n_waves);
-                } else {
-                    ok = d.wave_len >= 16u && p->n_short <= d.n_waves / 35u;
-                    const uint64_t mw = 1u + 2ull * d.n_waves + (((uint64_t)d.n_samples * 25u + 31u) >> 5);
-                    bmax = std::max<uint64_t>(bmax, (mw + 4095u) / 4096u);
-                    min_len = std::min(min_len, d.wave_len);
-                }
-            }
-            p->G.rag_par = ok && bmax <= 0xfffffu;
-            p->G.rag_bw_blocks_max = (uint32_t)bmax;
-            p->G.rag_bw_min_len = min_len;
-            p->G.rag_pw_min_waves = min_long_waves;
-        }
-        // the segment encoder for ragged batches with short (<= 2048) or long (>= 16384) waveforms somewhere: unit
-        // (waveform x 8192-sample segment slot) numbering per chunk
-        bool seg = false;
-        std::vector<uint64_t> ub(n_chunks + 1, 0);
-        for (uint64_t c = 0; c < n_chunks; ++c) {
-            seg = seg || desc[c].wave_len <= kSegShortLenHost || desc[c].wave_len >= kSegLongLenHost;
-            ub[c + 1] = ub[c] + (uint64_t)desc[c].n_waves * ((desc[c].wave_len + 8191u) / 8192u);
-        }
-        if (seg) {
-            if (e == hipSuccess) e = hipMalloc((void **)&p->d_seg_unit_base, ub.size() * sizeof(uint64_t));
-            if (e == hipSuccess) e = hipMemcpy(p->d_seg_unit_base, ub.data(), ub.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
-            p->G.seg_unit_base = p->d_seg_unit_base;
-            p->G.seg_units = ub[n_chunks];
-        }
-        // the pieces encoder (drx_pieces.hip): every WaveformLength within its range and some chunk of short or of long
-        // waveforms -- or every WaveformLength above its range (waveforms over several workgroups); workgroup numbering per chunk
-        {
-            bool ok = soff >= 512u, some = false, all_super = true, none_super = true, all_packed = true;
-            for (uint64_t c = 0; c < n_chunks; ++c) all_packed = all_packed && piece_packable(desc[c].wave_len);
-            std::vector<uint32_t> wb(n_chunks + 1, 0);
-            uint64_t wgs = 0;
-            for (uint64_t c = 0; c < n_chunks && ok; ++c) {
-                const PieceShape sh = piece_shape(desc[c].wave_len, desc[c].n_waves, p->G.k, all_packed);
-                ok = (all_packed || desc[c].wave_len >= kPcMinLen) && (uint64_t)desc[c].n_waves * sh.parts <= 0x7fffffffull;
-                all_super = all_super && sh.parts > 1u;
-                none_super = none_super && sh.parts == 1u;
-                some = some || all_packed || sh.run > 1u || sh.segs > 1u;
-                wgs += sh.wgs;
-                ok = ok && wgs <= 0x7fffffffull;
-                wb[c + 1] = (uint32_t)wgs;
-            }
-            if (ok && some && (all_super || none_super)) {
-                if (e == hipSuccess) e = hipMalloc((void **)&p->d_pc_wg_base, wb.size() * sizeof(uint32_t));
-                if (e == hipSuccess) e = hipMemcpy(p->d_pc_wg_base, wb.data(), wb.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-                p->G.pc_wg_base = p->d_pc_wg_base;
-                p->G.pc_super = all_super ? 1u : 0u;
-                p->G.pc_packed = all_packed ? 1u : 0u;
-                p->pc_wgs = wgs;
-            }
-        }
-        // few long waveforms: the block-parallel decoder (and, behind it, the in-place inverse of a general filter)
-        std::vector<uint32_t> blk_list(wbase ? wbase : 1);
-        blocks_plan_ragged(p->G, desc.data(), blk_list.data());
-        if (p->G.rag_blocks) {
-            if (e == hipSuccess) e = hipMalloc((void **)&p->d_blk_list, blk_list.size() * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemcpy(p->d_blk_list, blk_list.data(), blk_list.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-            p->G.rag_blk_list = p->d_blk_list;
-            std::vector<uint64_t> tb(n_chunks + 1, 0);
-            p->G.iir_n_tiles = iir_tiles(p->G, desc.data(), tb.data());
-            if (e == hipSuccess) e = hipMalloc((void **)&p->d_iir_chunk_base, tb.size() * sizeof(uint64_t));
-            if (e == hipSuccess) e = hipMemcpy(p->d_iir_chunk_base, tb.data(), tb.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
-            p->G.iir_chunk_tile_base = p->d_iir_chunk_base;
-        }
-        if (e != hipSuccess) st = fail(ctx, DRX_ERR_DEVICE, "chunk table upload failed: %s", hipGetErrorString(e));
-    }
-    if (st != DRX_OK) { plan_free(p); return st; }
-    p->G.chunks = p->d_chunks;
-    if ((st = plan_alloc_scratch(ctx, p)) != DRX_OK) { plan_free(p); return st; }
-    *out = p;
-    return DRX_OK;
+    return plan_create(ctx, n_chunks, chunk_samples, chunk_wave_len, true, rice_k, out);
 }
 
 drx_status drx_plan_create_uniform(drx_ctx *ctx, uint64_t n_chunks, uint32_t chunk_samples,
                                    uint32_t wave_len, uint32_t rice_k, drx_plan **out) {
-    if (!ctx || !out || !n_chunks) return DRX_ERR_ARG;
-    *out = nullptr;
-    if (rice_k > 15) return fail(ctx, DRX_ERR_ARG, "rice_k %u out of range 0..15", rice_k);
-    if (chunk_samples == 0 || chunk_samples > 0x7fffffffu) return fail(ctx, DRX_ERR_ARG, "bad chunk sample count");
-    if (n_chunks > 0xffffffffull) return fail(ctx, DRX_ERR_ARG, "too many chunks");
-    const uint32_t L = wave_len ? wave_len : chunk_samples;
-    if (L > 0x7fffffffu) return fail(ctx, DRX_ERR_ARG, "bad waveform length");
-    DRX_ON_DEVICE(ctx);  // (as in drx_plan_create)
-    const uint32_t W = (uint32_t)(((uint64_t)chunk_samples + L - 1) / L);
-    drx_plan *p = new (std::nothrow) drx_plan;
-    if (!p) return DRX_ERR_NOMEM;
-    p->ctx = ctx;
-    p->total_samples = n_chunks * chunk_samples;
-    p->max_words = n_chunks * (1 + 2ull * W + (((uint64_t)chunk_samples * 25u + 31u) >> 5));
-    p->G.chunks = nullptr;
-    p->G.n_chunks = n_chunks;
-    p->G.total_waves = n_chunks * W;
-    p->G.uniform = 1;
-    p->G.u_n_samples = chunk_samples;
-    p->G.u_wave_len = L;
-    p->G.u_n_waves = W;
-    p->G.k = rice_k;
-    p->G.total_samples = p->total_samples;
-    drx_status st = plan_alloc(ctx, p);
-    if (st == DRX_OK) st = plan_alloc_scratch(ctx, p);
-    if (st != DRX_OK) { plan_free(p); return st; }
-    *out = p;
-    return DRX_OK;
+    return plan_create(ctx, n_chunks, &chunk_samples, &wave_len, false, rice_k, out);
 }
 
 drx_status drx_plan_set_filter(drx_plan *p, uint32_t n_taps, const int32_t *taps) {
@@ -557,48 +489,49 @@ drx_status drx_plan_set_filter(drx_plan *p, uint32_t n_taps, const int32_t *taps
     if (taps[0] == 0) return fail(ctx, DRX_ERR_ARG, "taps[0] must not be 0 (the inverse filter divides by it)");
     DRX_ON_DEVICE(ctx);
     DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    Geom &G = p->G;
     p->enc_words_per_wave = 0;  // (another filter, another code length: what the last encode measured no longer applies)
-    if (p->h_enc_words) *p->h_enc_words = 0;
-    p->G.fast_taps = 0;
-    p->G.enc_fast = 0;
-    if (n_taps == 2 && taps[0] == 1 && taps[1] == -1) {  // checkIfDeltaFilter, src/deltaRice.c:38-46
-        p->G.n_taps = 0;
-        p->G.taps = nullptr;
-        p->G.iir_tab = nullptr;
-        p->G.blk_iir_tab = nullptr;
-        return DRX_OK;
+    *G.host_words = 0;
+    G.fast_taps = 0;
+    G.enc_fast = 0;
+    const bool delta = n_taps == 2 && taps[0] == 1 && taps[1] == -1;  // checkIfDeltaFilter, src/deltaRice.c:38-46
+    if (!delta && n_taps <= 4) {
+        G.enc_fast = 1;
+        for (uint32_t j = 0; j < 4; ++j) G.enc_t[j] = (j < n_taps) ? (uint32_t)taps[j] & 0xffffu : 0u;
     }
-    if (n_taps <= 4) {
-        p->G.enc_fast = 1;
-        for (uint32_t j = 0; j < 4; ++j) p->G.enc_t[j] = (j < n_taps) ? (uint32_t)taps[j] & 0xffffu : 0u;
+    if (!delta && n_taps <= 4 && (taps[0] == 1 || taps[0] == -1)) {
+        G.fast_taps = 1;
+        G.fast_t0neg = taps[0] == -1;
+        for (uint32_t j = 1; j < 4; ++j) G.fast_nt[j - 1] = (j < n_taps) ? 0u - (uint32_t)taps[j] : 0u;
     }
-    if (n_taps <= 4 && (taps[0] == 1 || taps[0] == -1)) {
-        p->G.fast_taps = 1;
-        p->G.fast_t0neg = taps[0] == -1;
-        for (uint32_t j = 1; j < 4; ++j) p->G.fast_nt[j - 1] = (j < n_taps) ? 0u - (uint32_t)taps[j] : 0u;
-    }
-    p->G.iir_tab = nullptr;
-    p->G.blk_iir_tab = nullptr;
-    if (p->G.fast_taps && p->d_iir_state) {  // the block decoder's geometry: the inverse filter's matrix tables
+    // the device copies of the filter: kept for the plan's next filter, freed when this one has no use for them
+    if (G.fast_taps && G.iir_state) {  // the block decoder's geometry: the inverse filter's matrix tables
         const uint32_t words = kIirTabWords + blocks_iir_tab_words();  // k_iir_tiles' tables, then the block decoder's own
         std::vector<uint32_t> tab(words);
-        iir_tables(p->G.fast_nt, p->G.fast_t0neg, tab.data());
-        blocks_iir_tables(p->G.fast_nt, p->G.fast_t0neg, tab.data() + kIirTabWords);
-        if (!p->d_iir_tab) DRX_HIP(ctx, hipMalloc((void **)&p->d_iir_tab, words * sizeof(uint32_t)));
-        DRX_HIP(ctx, hipMemcpy(p->d_iir_tab, tab.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice));
-        p->G.iir_tab = p->d_iir_tab;
-        p->G.blk_iir_tab = p->d_iir_tab + kIirTabWords;
+        iir_tables(G.fast_nt, G.fast_t0neg, tab.data());
+        blocks_iir_tables(G.fast_nt, G.fast_t0neg, tab.data() + kIirTabWords);
+        DRX_HIP(ctx, upload(p, tab, &G.iir_tab));
+        G.blk_iir_tab = G.iir_tab + kIirTabWords;
+    } else {
+        p->mem.release(G.iir_tab);
+        G.iir_tab = G.blk_iir_tab = nullptr;
     }
-    if (!p->d_taps) DRX_HIP(ctx, hipMalloc((void **)&p->d_taps, DRX_MAX_TAPS * sizeof(int32_t)));
-    DRX_HIP(ctx, hipMemcpy(p->d_taps, taps, n_taps * sizeof(int32_t), hipMemcpyHostToDevice));
-    p->G.n_taps = n_taps;
-    p->G.taps = p->d_taps;
+    if (delta) {
+        p->mem.release(G.taps);
+        G.n_taps = 0;
+        G.taps = nullptr;
+        return DRX_OK;
+    }
+    int32_t t[DRX_MAX_TAPS] = {0};
+    memcpy(t, taps, n_taps * sizeof(int32_t));
+    DRX_HIP(ctx, upload(p, t, DRX_MAX_TAPS, &G.taps));
+    G.n_taps = n_taps;
     return DRX_OK;
 }
 
 void drx_plan_destroy(drx_plan *p) { plan_free(p); }
 uint64_t drx_plan_n_chunks(const drx_plan *p) { return p ? p->G.n_chunks : 0; }
-uint64_t drx_plan_total_samples(const drx_plan *p) { return p ? p->total_samples : 0; }
+uint64_t drx_plan_total_samples(const drx_plan *p) { return p ? p->G.total_samples : 0; }
 uint64_t drx_plan_total_waves(const drx_plan *p) { return p ? p->G.total_waves : 0; }
 uint64_t drx_plan_max_encoded_words(const drx_plan *p) { return p ? p->max_words : 0; }
 const uint32_t *drx_plan_wave_words(const drx_plan *p) { return p ? p->d_wave_words : nullptr; }
@@ -625,7 +558,7 @@ drx_status drx_plan_read_wave_words(drx_plan *p, uint32_t *host_out) {
 // encode says (the same data shape comes again), and before that k + 3.5 bits per sample (the RiceParameter that suits).
 static bool stream_encoder_suits(const drx_plan *p, int wide) {
     const Geom &G = p->G;
-    if (wide != 0 || G.total_waves < 8192u) return false;
+    if (wide != 0 || G.total_waves < kEsMinUnits) return false;
     const uint64_t L = G.uniform ? G.u_wave_len : G.max_wave_len64 / 64u;
     const uint64_t words = p->enc_words_per_wave ? p->enc_words_per_wave : (L * (2u * G.k + 7u)) / 64u;
     return words <= (uint64_t)kEsRingWords * 67u / 100u;
@@ -647,7 +580,7 @@ static uint32_t stream_segs_target(const drx_plan *p) {
     uint64_t t = ((uint64_t)kEsRingWords * 32u * 57u / 100u) * 16u / (bps16 ? bps16 : 1u);
     t = t > kEsSegMaxLen ? kEsSegMaxLen : (t < kEsSegMinLen ? kEsSegMinLen : t);
     const EsSegShape sh = es_seg_shape((uint32_t)L, (uint32_t)t);
-    if (G.total_waves * sh.nseg < 8192u) return 0u;
+    if (G.total_waves * sh.nseg < kEsMinUnits) return 0u;
     return (uint32_t)t;
 }
 
@@ -656,10 +589,10 @@ static uint32_t stream_segs_target(const drx_plan *p) {
 // (geometry, filter, encode_impl); its default row takes those it is the best choice for.
 //   encoder     | admits                                               | default choice
 //   ------------+------------------------------------------------------+-------------------------------------------------------
-//   STREAM_SEGS | impl 2, stream_segs_admits()                         | L >= kEsSegsFromLen, 8192 segments (stream_segs_target())
+//   STREAM_SEGS | impl 2, stream_segs_admits()                         | L >= kEsSegsFromLen, kEsMinUnits segments (stream_segs_target())
 //   PIECES      | impl >= 1, pieces_admits()                           | pieces_batch(): runs of short / segments of long waveforms
 //   SEGMENTS    | impl >= 1, long_batch_admits()                       | long_batch(): short, long or few long waveforms
-//   STREAM      | impl 2, delta or fast filter                         | stream_encoder_suits(): >= 8192 waveforms, code fits a ring
+//   STREAM      | impl 2, delta or fast filter                         | stream_encoder_suits(): >= kEsMinUnits waveforms, code fits a ring
 //   FUSED       | impl >= 1, delta or fast filter                      | always (fused_wide(): larger buffers for m above 8)
 //   TWO_PASS    | always                                               | always
 // Forced rows come first, in this order: DRX_DBG_FORCE_STREAM_SEGS (segments of kEsSegMinLen samples), FORCE_SEGMENTS,
@@ -686,6 +619,26 @@ static EncodeRoute route_encode(const drx_plan *p, int impl, uint32_t dbg) {
     return {single && fast ? DRX_ENC_FUSED : DRX_ENC_TWO_PASS, 0, wide};
 }
 
+// Scratch of a route beyond what the plan was sized for, which only a route that a debug flag forces needs: the segment
+// form's look-back state for shorter segments, the segment encoder's where its default row would not take the batch
+static drx_status route_scratch(drx_plan *p, const EncodeRoute &R) {
+    drx_ctx *ctx = p->ctx;
+    if (R.enc == DRX_ENC_STREAM_SEGS) {
+        const size_t need = segs_scan_words(p->G, R.seg_target) * sizeof(uint64_t);
+        if (p->scan_bytes < need) {
+            // the larger buffer first: should that fail, the plan keeps the one its default routes were sized for
+            const size_t want = need + need / 4 + 4096;
+            uint64_t *scan = nullptr;
+            DRX_HIP(ctx, p->mem.alloc(&scan, want));
+            p->mem.release(p->d_scan);  // (waits for the device)
+            p->d_scan = scan;
+            p->scan_bytes = want;
+        }
+    }
+    if (R.enc == DRX_ENC_SEGMENTS && !p->d_seg_bits) DRX_HIP(ctx, seg_scratch(p));
+    return DRX_OK;
+}
+
 drx_status drx_encode(drx_plan *p, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap_words,
                       uint64_t *d_chunk_word_off) {
     if (!p || !d_in || !d_out || !d_chunk_word_off) return DRX_ERR_ARG;
@@ -695,23 +648,18 @@ drx_status drx_encode(drx_plan *p, const int16_t *d_in, uint32_t *d_out, uint64_
     p->G.dbg = ctx->debug_flags;
     // what the plan's last encode measured decides this one's kernel -- read from the word the encoders write to pinned host
     // memory, so that callers that never wait for an encode (bench.py's steps) are covered without a copy or an event
-    if (const uint64_t w = *(volatile uint64_t *)p->h_enc_words) p->enc_words_per_wave = p->G.total_waves ? w / p->G.total_waves : 0;
+    if (const uint64_t w = *(volatile uint64_t *)p->G.host_words) p->enc_words_per_wave = p->G.total_waves ? w / p->G.total_waves : 0;
     const EncodeRoute R = route_encode(p, ctx->encode_impl, ctx->debug_flags);
+    if (const drx_status st = route_scratch(p, R)) return st;
     hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
     switch (R.enc) {
-    case DRX_ENC_STREAM_SEGS:  // (shorter segments than the plan was sized for: a forced route; hipFree waits for the device)
-        if (const drx_status st = grow(ctx, (void **)&p->d_scan, &p->scan_bytes, segs_scan_words(p->G, R.seg_target) * sizeof(uint64_t), false)) return st;
+    case DRX_ENC_STREAM_SEGS:
         DRX_HIP(ctx, launch_encode_stream_segs(p->G, R.seg_target, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
                                                p->d_scan, p->d_status, ev, ctx->stream)); break;
     case DRX_ENC_PIECES:
-        DRX_HIP(ctx, launch_encode_pieces(p->G, d_in, p->total_samples, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
+        DRX_HIP(ctx, launch_encode_pieces(p->G, d_in, p->G.total_samples, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
                                           p->d_pc_scan, p->pc_wgs, p->d_status, ev, ctx->stream)); break;
     case DRX_ENC_SEGMENTS:
-        if (!p->d_seg_bits) {  // (a route the plan was not sized for)
-            const uint64_t units = long_batch_units(p->G);
-            DRX_HIP(ctx, hipMalloc((void **)&p->d_seg_bits, units * sizeof(uint32_t)));
-            DRX_HIP(ctx, hipMalloc((void **)&p->d_seg_pos, units * sizeof(uint64_t)));
-        }
         DRX_HIP(ctx, launch_encode_long(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words, p->d_wave_rel,
                                         p->d_chunk_words, p->d_seg_bits, p->d_seg_pos, p->d_status, ev, ctx->stream)); break;
     case DRX_ENC_STREAM:
@@ -838,7 +786,7 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts, co
         return fail(ctx, DRX_ERR_ARG, "invalid compression_opts");
     std::lock_guard<std::mutex> lock(ctx->mu);
     DRX_ON_DEVICE(ctx);
-    if (!ctx->d_off) DRX_HIP(ctx, hipMalloc((void **)&ctx->d_off, 2 * sizeof(uint64_t)));
+    if (!ctx->d_off) DRX_HIP(ctx, ctx->mem.alloc(&ctx->d_off, 2 * sizeof(uint64_t)));
 
     uint32_t n_samples;
     if (!reverse) {

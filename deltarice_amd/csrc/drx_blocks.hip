@@ -987,7 +987,7 @@ bool blocks_batch(const Geom &G) {
     return blocks_us < lanes_us;
 }
 
-void blocks_plan_ragged(Geom &G, const ChunkDesc *d, uint32_t *list_out) {
+std::vector<uint32_t> blocks_plan_ragged(Geom &G, const ChunkDesc *d) {
     G.rag_blocks = 0;
     G.rag_blk_classes = 0;
     uint32_t max_len = 0, min_len = 0xffffffffu;
@@ -995,26 +995,27 @@ void blocks_plan_ragged(Geom &G, const ChunkDesc *d, uint32_t *list_out) {
         max_len = d[c].wave_len > max_len ? d[c].wave_len : max_len;
         min_len = d[c].wave_len < min_len ? d[c].wave_len : min_len;
     }
-    if (G.total_waves > 98304u || min_len < 2048u) return;
+    if (G.total_waves > 98304u || min_len < 2048u) return {};
     const int nt = nt_for_len(max_len, G.k);
     double wb = 0;
     for (uint64_t c = 0; c < G.n_chunks; ++c) wb += blocks_weighted(d[c].n_waves, d[c].wave_len, G.k, nt);
     // a lane takes 60 ns per sample: a lane-per-waveform launch lasts as long as its longest waveform, per 98 304 of them
     const double lanes_us = 0.06 * (double)max_len * (double)((G.total_waves + 98303u) / 98304u);
-    if (!(blocks_us_of(wb, nt, G.k) < lanes_us)) return;
+    if (!(blocks_us_of(wb, nt, G.k) < lanes_us)) return {};
     // look-back slots per waveform: enough for the longest one at 25 bits per sample, in blocks of the SMALLEST class's size
     const uint64_t per = (max_payload_words(max_len) + blk_words_min(64u) - 1u) / blk_words_min(64u);
-    if (G.total_waves * per * 12u > (1ull << 30)) return;  // (one very long waveform among very many: the table would not pay)
+    if (G.total_waves * per * 12u > (1ull << 30)) return {};  // (one very long waveform among very many: the table would not pay)
     G.rag_blocks = 1u;
     G.rag_blk_nt = (uint32_t)nt;
     G.rag_blk_slots = (uint32_t)(per ? per : 1u);
     // classes by floor(log2 WaveformLength), longest first (the long classes start while the grid is empty)
+    std::vector<uint32_t> list(G.total_waves);
     uint32_t n_cls = 0, at = 0;
     for (int b = 31; b >= 11; --b) {
         uint32_t cnt = 0, cls_max = 0;
         for (uint64_t c = 0; c < G.n_chunks; ++c) {
             if ((31 - __builtin_clz(d[c].wave_len)) != b) continue;
-            for (uint32_t i = 0; i < d[c].n_waves; ++i) list_out[at + cnt++] = (uint32_t)(d[c].wave_base + i);
+            for (uint32_t i = 0; i < d[c].n_waves; ++i) list[at + cnt++] = (uint32_t)(d[c].wave_base + i);
             cls_max = d[c].wave_len > cls_max ? d[c].wave_len : cls_max;
         }
         if (!cnt) continue;
@@ -1025,6 +1026,7 @@ void blocks_plan_ragged(Geom &G, const ChunkDesc *d, uint32_t *list_out) {
     }
     G.rag_blk_class_off[n_cls] = at;
     G.rag_blk_classes = n_cls;
+    return list;
 }
 
 // the fused inverse filter's tables: one set per lane share (76, 68, 60 samples), kRunTabWords each

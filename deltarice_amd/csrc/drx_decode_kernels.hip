@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "drx_internal.h"
@@ -845,21 +846,30 @@ hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t 
     return hipGetLastError();
 }
 
+// The block-parallel walk of a batch's chunks, each of n_waves waveforms of wave_len samples (from 16), pays against the walk
+// inside the decode launch (serial chase through LDS, 0.13 us per waveform of a chunk, all chunks at once, so that large
+// batches hide most of it) while it walks no more chunks than one per 35 waveforms of a chunk.  Measured (chunks of 14 M
+// samples, decode GB/s of the two paths at 150 / 220 chunks): L = 512 1602 / 1627 against 875 / 1265; L = 1024 1869 / 1927
+// against 1521 / 1954; L = 2048 1906 / 2012 against 1673 / 2169.  Above WaveformLength 2048 the alternative is the scalar
+// chain at 0.85 us per hop (L = 3072, 100 / 220 chunks: 1731 / 1459+ against 596 / 1123): one per 18.
+static bool bw_walk_pays(uint64_t walked_chunks, uint32_t n_waves, uint32_t wave_len) {
+    return walked_chunks <= n_waves / (wave_len <= kWalkShortLen ? 35u : 18u) && wave_len >= 16u;
+}
+// ... the 4096-word blocks of such a chunk: its code at 25 bits per sample with its headers, at most kBwMaxBlocks
+constexpr uint64_t kBwMaxBlocks = 0xfffffu;
+static uint64_t bw_chunk_blocks(uint32_t n_samples, uint32_t n_waves) {
+    const uint64_t max_words = 1u + 2ull * n_waves + (((uint64_t)n_samples * 25u + 31u) >> 5);
+    return (max_words + kWalkBlockWords - 1u) / kWalkBlockWords;
+}
+
 uint32_t bw_walk_blocks_max(const Geom &G) {
-    // against the walk inside the decode launch (serial chase through LDS, 0.13 us per waveform of a chunk, all chunks at
-    // once, so that large batches hide most of it).  Measured (chunks of 14 M samples, decode GB/s of the two paths at
-    // 150 / 220 chunks): L = 512 1602 / 1627 against 875 / 1265; L = 1024 1869 / 1927 against 1521 / 1954; L = 2048
-    // 1906 / 2012 against 1673 / 2169: about one chunk per 35 waveforms of a chunk.  Above WaveformLength 2048 the
-    // alternative is the scalar chain at 0.85 us per hop (L = 3072, 100 / 220 chunks: 1731 / 1459+ against 596 / 1123): W / 18
-    const uint64_t per = G.u_wave_len <= kWalkShortLen ? 35u : 18u, cap = kPwMaxChunks;
-    const uint64_t limit = G.u_n_waves / per < cap ? G.u_n_waves / per : cap;
     // every 4096-word block must hold a header: n_i <= 25 L / 32 < 4096, i.e. L <= 5000; chunks of longer
     // waveforms within the chunk-wide walk's capacity take that one
     const bool chunk_wide = G.u_wave_len > kWalkShortLen && G.u_n_waves <= kSwMaxWaves && G.u_n_waves >= kSwMinWaves;
-    if (!(G.uniform && G.n_chunks <= limit && G.u_wave_len <= 5000u && G.u_wave_len >= 16u && !chunk_wide)) return 0;
-    const uint64_t max_words = 1u + G.u_n_waves + (((uint64_t)G.u_n_samples * 25u + 31u) >> 5) + G.u_n_waves;
-    const uint64_t nb = (max_words + kWalkBlockWords - 1u) / kWalkBlockWords;
-    return nb > 0xfffffu ? 0u : (uint32_t)nb;
+    if (!(G.uniform && bw_walk_pays(G.n_chunks, G.u_n_waves, G.u_wave_len) && G.n_chunks <= kPwMaxChunks && G.u_wave_len <= 5000u &&
+          !chunk_wide)) return 0;
+    const uint64_t nb = bw_chunk_blocks(G.u_n_samples, G.u_n_waves);
+    return nb > kBwMaxBlocks ? 0u : (uint32_t)nb;
 }
 
 // bytes of header list per 4096 words of stream for the block size the launch will choose (0: none kept)
@@ -890,6 +900,60 @@ uint64_t par_walk_scratch_bytes(const Geom &G) {
     return (pw && G.n_chunks <= kPwMaxChunks ? G.n_chunks * kPwStride * sizeof(uint2) : 0) + (3u * G.n_chunks + 2u) * sizeof(uint32_t) +
            bw_units * (kWalkBlockWords / 1024u) * sizeof(BwBlock) +  // (blocks of 1024 words at the smallest)
            bw_units * bw_hop_bytes_per_block4096(G);                 // header lists of the first block pass
+}
+
+void decode_plan_ragged(Geom &G, const ChunkDesc *d, std::vector<uint32_t> *walk_lists, std::vector<uint2> *order) {
+    const uint64_t n = G.n_chunks;
+    // walk lists: chunks of short waveforms are walked through LDS, the others hop by hop
+    std::vector<uint32_t> &lists = *walk_lists;
+    lists.clear();
+    for (uint64_t c = 0; c < n; ++c) if (d[c].wave_len <= kWalkShortLen) lists.push_back((uint32_t)c);
+    G.n_short = (uint32_t)lists.size();
+    for (uint64_t c = 0; c < n; ++c) if (d[c].wave_len > kWalkShortLen) lists.push_back((uint32_t)c);
+    G.n_long = (uint32_t)lists.size() - G.n_short;
+    uint32_t max_groups = 0, max_len = 0;
+    for (uint64_t c = 0; c < n; ++c) {
+        max_groups = std::max(max_groups, (d[c].n_waves + 63u) / 64u);
+        max_len = std::max(max_len, d[c].wave_len);
+    }
+    G.max_groups = max_groups;
+    G.max_wave_len64 = 64ull * max_len;
+    // decode order: wavefronts (groups of 64 waveforms of one chunk) by decreasing WaveformLength
+    std::vector<uint32_t> by_len(n);
+    for (uint64_t c = 0; c < n; ++c) by_len[c] = (uint32_t)c;
+    std::stable_sort(by_len.begin(), by_len.end(), [&](uint32_t a, uint32_t b) { return d[a].wave_len > d[b].wave_len; });
+    order->clear();
+    uint64_t n_long_groups = 0;
+    for (uint32_t c : by_len)
+        for (uint32_t j = 0; j < (d[c].n_waves + 63u) / 64u; ++j) {
+            order->push_back(make_uint2(c, j));
+            if (d[c].wave_len > kWalkShortLen) ++n_long_groups;
+        }
+    if (order->size() <= 0x7fffffffull) {
+        G.rag_groups = (uint32_t)order->size();
+        G.rag_groups_long = (uint32_t)n_long_groups;
+    } else {
+        order->clear();
+    }
+    // parallel header walks for small ragged batches: every long-waveform chunk within the chunk-wide walk's capacity, every
+    // short-waveform chunk worth the block-parallel walk (bw_walk_pays(), bw_chunk_blocks(): the rules of uniform batches)
+    bool ok = G.n_long <= kPwMaxChunks && G.n_short <= kPwMaxChunks;
+    uint64_t bmax = 0;
+    uint32_t min_len = 0xffffffffu, min_long_waves = 0xffffffffu;
+    for (uint64_t c = 0; c < n && ok; ++c) {
+        if (d[c].wave_len > kWalkShortLen) {
+            ok = d[c].n_waves <= kPwMaxWaves;
+            min_long_waves = std::min(min_long_waves, d[c].n_waves);
+        } else {
+            ok = bw_walk_pays(G.n_short, d[c].n_waves, d[c].wave_len);
+            bmax = std::max(bmax, bw_chunk_blocks(d[c].n_samples, d[c].n_waves));
+            min_len = std::min(min_len, d[c].wave_len);
+        }
+    }
+    G.rag_par = ok && bmax <= kBwMaxBlocks;
+    G.rag_bw_blocks_max = (uint32_t)bmax;
+    G.rag_bw_min_len = min_len;
+    G.rag_pw_min_waves = min_long_waves;
 }
 
 // Ablation builds only: DRX_DEC_LDS_PAD = bytes of dynamic LDS added to every k_decode_lanes launch (occupancy A/B at an

@@ -938,18 +938,32 @@ hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, ui
 // single-pass encoder pays a workgroup barrier, a look-back and an 8 KB LDS clear per 512-2048 samples
 // (200 chunks of 14 M samples: L = 512 0.57 -> 0.95 TB/s, 1024 0.97 -> 1.33, 2048 1.51 -> 1.68), and waveforms
 // long enough to outgrow the single pass's LDS buffer; in between the single pass is better
-// block-parallel walk of short waveforms: blocks per chunk at 25 bits per sample (0: the batch does not take it)
-// (delta; ragged: decided when the plan was made, some chunk is short or long)
+// (delta; ragged: decided when the plan was made, segments_plan_ragged())
 bool long_batch_admits(const Geom &G) { return !G.n_taps && (G.uniform || G.seg_unit_base != nullptr); }
+// WaveformLengths the segment encoder takes in any batch: up to kSegShortLen, and from kSegLongLen.  Measured at 100 chunks of
+// 14 M samples (single pass / segments, TB/s): L = 2049 0.95 / 1.06, 3000 1.57 / 1.64, 4096 1.93 / 1.85, 7000 2.16 / 1.87,
+// 12000 1.33 / 1.63 (the single pass outgrows its 8 KB LDS buffer at ~6.5 bits per sample and encodes such waveforms twice)
+constexpr uint32_t kSegShortLen = 3072, kSegLongLen = 10240;
+static bool seg_len_suits(uint32_t wave_len) { return wave_len <= kSegShortLen || wave_len >= kSegLongLen; }
 bool long_batch(const Geom &G) {
-    // measured at 100 chunks of 14 M samples (single pass / segments, TB/s): L = 2049 0.95 / 1.06, 3000 1.57 / 1.64,
-    // 4096 1.93 / 1.85, 7000 2.16 / 1.87, 12000 1.33 / 1.63 (the single pass outgrows its 8 KB LDS buffer at
-    // ~6.5 bits per sample and encodes such waveforms twice)
-    return long_batch_admits(G) && (!G.uniform || long_waveform_batch(G.total_waves, G.u_wave_len) ||
-                                    G.u_wave_len <= kSegShortLenHost || G.u_wave_len >= kSegLongLenHost);
+    return long_batch_admits(G) && (!G.uniform || long_waveform_batch(G.total_waves, G.u_wave_len) || seg_len_suits(G.u_wave_len));
 }
-static uint32_t uniform_segments(const Geom &G) { return (G.u_wave_len + kSegSamples - 1u) / kSegSamples; }
-uint64_t long_batch_units(const Geom &G) { return G.uniform ? G.total_waves * uniform_segments(G) : G.seg_units; }
+static uint32_t segments_of(uint32_t wave_len) { return (wave_len + kSegSamples - 1u) / kSegSamples; }
+uint64_t long_batch_units(const Geom &G) { return G.uniform ? G.total_waves * segments_of(G.u_wave_len) : G.seg_units; }
+
+// ragged batches: the encoder takes those with short or long waveforms somewhere; units (waveform x segment slot) are
+// numbered chunk by chunk, each chunk's waveforms with as many slots as its WaveformLength has segments (locate_seg())
+std::vector<uint64_t> segments_plan_ragged(Geom &G, const ChunkDesc *d) {
+    bool seg = false;
+    std::vector<uint64_t> unit_base(G.n_chunks + 1, 0);
+    for (uint64_t c = 0; c < G.n_chunks; ++c) {
+        seg = seg || seg_len_suits(d[c].wave_len);
+        unit_base[c + 1] = unit_base[c] + (uint64_t)d[c].n_waves * segments_of(d[c].wave_len);
+    }
+    if (!seg) return {};
+    G.seg_units = unit_base[G.n_chunks];
+    return unit_base;
+}
 
 // Encoder for few long waveforms.  d_seg_bits: uint32[total_waves * segments], d_seg_pos: uint64[same].
 hipError_t launch_encode_long(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
@@ -957,7 +971,7 @@ hipError_t launch_encode_long(const Geom &G, const int16_t *d_in, uint32_t *d_ou
                               uint64_t *d_chunk_words, uint32_t *d_seg_bits, uint64_t *d_seg_pos, DevStatus *d_status,
                               hipEvent_t *ev, hipStream_t s) {
     if (G.total_waves == 0) return hipSuccess;
-    const uint32_t S = G.uniform ? uniform_segments(G) : 0u;
+    const uint32_t S = G.uniform ? segments_of(G.u_wave_len) : 0u;
     const uint64_t units = long_batch_units(G);
     mark(ev, 0, s);
     const uint32_t upw = (G.uniform && S == 1u && G.u_wave_len <= 1024u) ? 8u : 1u;  // short waveforms: eight per wavefront

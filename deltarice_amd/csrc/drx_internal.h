@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/deltarice_hip.h"
 
 namespace drx {
@@ -19,7 +21,8 @@ struct ChunkDesc {
     uint32_t pad_;
 };
 
-// Passed to kernels by value.
+// Passed to kernels by value.  Its device tables are buffers of the plan (drx_api.hip), which keeps no other pointer to them;
+// a ragged plan's tables are what each path's planner (*_plan_ragged() below) computed from the host's chunk table.
 struct Geom {
     const ChunkDesc *chunks;  // device pointer, n_chunks entries (unused when uniform)
     uint64_t n_chunks;
@@ -45,7 +48,7 @@ struct Geom {
     uint64_t *host_words;
     uint32_t dbg;  // "debug_flags" context option (DRX_DBG_* of include/deltarice_hip.h; -DDRX_ABLATION builds: drx_device.h); 0 in normal use
     // ragged batches, walk inside the decode launch: chunk indices, short-waveform chunks first
-    // (walk_short[n_short], then walk_long[n_long]), and the largest ceil(n_waves / 64) of any chunk
+    // (walk_short[n_short], then walk_long[n_long]), and the largest ceil(n_waves / 64) of any chunk (decode_plan_ragged())
     const uint32_t *walk_short, *walk_long;
     uint32_t n_short, n_long, max_groups;
     uint64_t max_wave_len64;  // ragged batches: 64 x the longest WaveformLength (how far apart a wavefront's 64 lines can lie)
@@ -65,10 +68,10 @@ struct Geom {
     uint64_t iir_n_tiles;
     uint64_t *iir_state;                  // uint64[iir_n_tiles + 1]
     // ragged batches that the segment encoder takes (some chunk has short or long waveforms): first unit (waveform x
-    // segment slot) of every chunk, n_chunks + 1 entries, and their total
+    // segment slot) of every chunk, n_chunks + 1 entries, and their total (segments_plan_ragged())
     const uint64_t *seg_unit_base;
     uint64_t seg_units;
-    // ragged batches small enough for the parallel header walks (drx_walk.h): set when the plan is made;
+    // ragged batches small enough for the parallel header walks (drx_walk.h): set when the plan is made (decode_plan_ragged());
     // rag_bw_blocks_max = 4096-word blocks of the largest short-waveform chunk at 25 bits per sample
     uint32_t rag_par, rag_bw_blocks_max;
     uint32_t rag_bw_min_len;  // ... and the smallest WaveformLength among those chunks (bounds the headers of a block)
@@ -78,7 +81,7 @@ struct Geom {
     const uint2 *rag_order;
     uint32_t rag_groups;
     uint32_t rag_groups_long;  // ... of which the first ones belong to chunks of WaveformLength > 2048 (the chunk-wide walk's)
-    // ragged batches the pieces encoder takes (drx_pieces.hip): first workgroup of every chunk, n_chunks + 1 entries
+    // ragged batches the pieces encoder takes (pieces_plan_ragged()): first workgroup of every chunk, n_chunks + 1 entries
     const uint32_t *pc_wg_base;
     uint32_t pc_super;  // ... and every chunk's WaveformLength is above kPcMaxLen (waveforms over several workgroups)
     uint32_t pc_packed;  // ... or every chunk's WaveformLength is piece_packable()
@@ -125,6 +128,7 @@ hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uin
 #define DRX_ES_RING 2496
 #endif
 constexpr uint32_t kEsRingWords = DRX_ES_RING;
+constexpr uint64_t kEsMinUnits = 8192;  // waveforms (segments) from which the persistent forms suit a batch: its 4096 wavefronts a few each
 hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                 uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
                                 DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
@@ -172,6 +176,8 @@ hipError_t launch_encode_stream_segs(const Geom &G, uint32_t seg_target, const i
 bool long_batch_admits(const Geom &G);
 bool long_batch(const Geom &G);
 uint64_t long_batch_units(const Geom &G);
+// ragged plans: sets seg_units and returns seg_unit_base's host copy (empty: the encoder does not take the batch)
+std::vector<uint64_t> segments_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 hipError_t launch_encode_long(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                               uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint32_t *d_wave_rel,
                               uint64_t *d_chunk_words, uint32_t *d_seg_bits, uint64_t *d_seg_pos, DevStatus *d_status,
@@ -192,9 +198,9 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
                          void *d_pw, void *d_blk, const SideStream *side, hipEvent_t *ev, hipStream_t s, uint32_t *path_out = nullptr);
 // block-parallel decoder for batches of few waveforms (drx_blocks.hip): a workgroup per block of a waveform's stream
 bool blocks_batch(const Geom &G);
-// ragged plans: decides rag_blocks / rag_blk_nt / rag_blk_slots from the host's chunk table (call once, when the plan is made)
-// (list_out: the host copy of rag_blk_list, for the caller to upload)
-void blocks_plan_ragged(Geom &G, const ChunkDesc *host_chunks, uint32_t *list_out);
+// ragged plans: decides rag_blocks / rag_blk_nt / rag_blk_slots and the classes from the host's chunk table (call once, when
+// the plan is made); returns rag_blk_list's host copy (empty: the decoder does not take the batch)
+std::vector<uint32_t> blocks_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 uint64_t blocks_scratch_bytes(const Geom &G);
 // resid: leave the residuals (not their running sums) in d_out: a general prediction filter's inverse follows (launch_iir)
 // fused_out: a general filter's inverse ran inside the kernel (no k_iir_tiles pass is needed behind it)
@@ -294,7 +300,10 @@ inline int fused_wide(const Geom &G) {
 }
 bool pieces_admits(const Geom &G);            // the encoder can run the batch (delta or a forward filter of up to four taps)
 bool pieces_batch(const Geom &G, int wide);   // ... and is its default choice
-uint64_t pieces_workgroups(const Geom &G, const ChunkDesc *host_chunks);
+uint64_t pieces_workgroups(const Geom &G);     // uniform batches it admits
+// ragged plans: sets pc_super / pc_packed and returns pc_wg_base's host copy, whose last entry is the workgroup total (empty:
+// the encoder does not take the batch)
+std::vector<uint32_t> pieces_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 uint64_t pieces_scan_words(const Geom &G, uint64_t total_wgs);  // uint64 words of its look-back state
 hipError_t launch_encode_pieces(const Geom &G, const int16_t *d_in, uint64_t in_samples, uint32_t *d_out, uint64_t out_cap,
                                 uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan, uint64_t total_wgs,
@@ -315,9 +324,10 @@ hipError_t launch_iir(const Geom &G, const uint64_t *d_chunk_tile_base, uint64_t
                       const uint32_t *d_skip, DevStatus *d_status, int16_t *d_out, hipStream_t s);
 uint64_t par_walk_scratch_bytes(const Geom &G);
 uint32_t bw_walk_blocks_max(const Geom &G);
-constexpr uint32_t kWalkShortLenHost = 2048;  // keep equal to kWalkShortLen in drx_walk.h
-// WaveformLengths the segment encoder takes in any batch: up to kSegShortLenHost, and from kSegLongLenHost
-constexpr uint32_t kSegShortLenHost = 3072, kSegLongLenHost = 10240;
+// ragged plans: sets n_short / n_long, max_groups, max_wave_len64, rag_groups / rag_groups_long and the parallel walks' rag_*
+// fields; returns the host copies of the walk lists (walk_short = the first n_short entries, walk_long the rest) and of
+// rag_order (empty: more wavefronts than 31 bits count)
+void decode_plan_ragged(Geom &G, const ChunkDesc *host_chunks, std::vector<uint32_t> *walk_lists, std::vector<uint2> *order);
 // limits of the parallel header walks (see k_walk_parallel / k_bw_blocks)
 constexpr uint32_t kPwMaxWaves = 3584;   // waveforms per chunk the chunk-wide walk takes (leaves room for impostors)
 #ifndef DRX_PW_MAX_CHUNKS

@@ -704,12 +704,29 @@ bool pieces_batch(const Geom &G, int wide) {
     return piece_packable(G.u_wave_len) || sh.run > 1u || sh.segs > 1u;
 }
 
-uint64_t pieces_workgroups(const Geom &G, const ChunkDesc *host_chunks) {
-    const bool packed = pieces_packed(G);
-    if (G.uniform) return (uint64_t)piece_shape(G.u_wave_len, G.u_n_waves, G.k, packed).wgs * G.n_chunks;
-    uint64_t t = 0;
-    for (uint64_t c = 0; c < G.n_chunks; ++c) t += piece_shape(host_chunks[c].wave_len, host_chunks[c].n_waves, G.k, packed).wgs;
-    return t;
+uint64_t pieces_workgroups(const Geom &G) { return (uint64_t)piece_shape(G.u_wave_len, G.u_n_waves, G.k, pieces_packed(G)).wgs * G.n_chunks; }
+
+// ragged batches: every WaveformLength within the encoder's range and some chunk of short or of long waveforms -- or every
+// WaveformLength above its range (waveforms over several workgroups); workgroups are numbered chunk by chunk
+std::vector<uint32_t> pieces_plan_ragged(Geom &G, const ChunkDesc *d) {
+    bool ok = G.total_samples >= 512u, some = false, all_super = true, none_super = true, all_packed = true;
+    for (uint64_t c = 0; c < G.n_chunks; ++c) all_packed = all_packed && piece_packable(d[c].wave_len);
+    std::vector<uint32_t> wg_base(G.n_chunks + 1, 0);
+    uint64_t wgs = 0;
+    for (uint64_t c = 0; c < G.n_chunks && ok; ++c) {
+        const PieceShape sh = piece_shape(d[c].wave_len, d[c].n_waves, G.k, all_packed);
+        ok = (all_packed || d[c].wave_len >= kPcMinLen) && (uint64_t)d[c].n_waves * sh.parts <= 0x7fffffffull;
+        all_super = all_super && sh.parts > 1u;
+        none_super = none_super && sh.parts == 1u;
+        some = some || all_packed || sh.run > 1u || sh.segs > 1u;
+        wgs += sh.wgs;
+        ok = ok && wgs <= 0x7fffffffull;
+        wg_base[c + 1] = (uint32_t)wgs;
+    }
+    if (!(ok && some && (all_super || none_super))) return {};
+    G.pc_super = all_super ? 1u : 0u;
+    G.pc_packed = all_packed ? 1u : 0u;
+    return wg_base;
 }
 
 // look-back state: one entry per workgroup (SUPER: per waveform) | SUPER: one per workgroup for the parts | ticket

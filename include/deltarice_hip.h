@@ -94,8 +94,8 @@ int drx_ctx_device(const drx_ctx *ctx); /* the HIP device the context was create
 drx_status drx_ctx_host_staging(drx_ctx *ctx, size_t bytes, void **host_out);
 
 /* Plans.  chunk_wave_len[c] == 0 means "whole chunk" (WaveformLength = -1).
- * Allocates the per-waveform tables and every scratch buffer the batch's geometry can need on the device;
- * drx_encode / drx_decode allocate nothing.
+ * Allocates the per-waveform tables and the scratch of every path the batch's geometry takes by default on the device;
+ * drx_decode allocates nothing, drx_encode only for a route that DRX_DBG_FORCE_STREAM_SEGS or DRX_DBG_FORCE_SEGMENTS forces.
  *
  * Threading: a context and its plans are for one thread at a time (calls are ordered on the context's stream);
  * drx_filter_chunk_host alone takes the context's lock and may be called from any thread (HDF5 does).
