@@ -10,7 +10,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
-#include <chrono>
 #include <mutex>
 #include <new>
 #include <string>
@@ -571,11 +570,7 @@ static bool stream_encoder_suits(const drx_plan *p, int wide) {
 static uint32_t stream_segs_target(const drx_plan *p) {
     const Geom &G = p->G;
     const uint64_t L = G.u_wave_len;
-    uint64_t min_len = kEsSegsFromLen;
-#ifdef DRX_ABLATION
-    if (const char *e = getenv("DRX_SEGS_MIN_LEN")) min_len = (uint64_t)atoll(e);  // (A/B builds: where the two encoders cross)
-#endif
-    if (L < min_len) return 0u;
+    if (L < kEsSegsFromLen) return 0u;
     const uint64_t bps16 = p->enc_words_per_wave ? (p->enc_words_per_wave * 512u) / L : 16u * G.k + 56u;  // bits per sample x 16
     uint64_t t = ((uint64_t)kEsRingWords * 32u * 57u / 100u) * 16u / (bps16 ? bps16 : 1u);
     t = t > kEsSegMaxLen ? kEsSegMaxLen : (t < kEsSegMinLen ? kEsSegMinLen : t);
@@ -815,16 +810,6 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts, co
         memcpy(ctx->hp_taps, o.taps, sizeof ctx->hp_taps);
     }
     drx_plan *plan = ctx->host_plan;
-    // DRX_TRACE=1: wall time of each phase of the call on stderr
-    static const bool trace = getenv("DRX_TRACE") != nullptr;
-    auto now = []() { return std::chrono::steady_clock::now(); };
-    auto t_prev = now();
-    auto lap = [&](const char *what) {
-        if (!trace) return;
-        const auto t = now();
-        fprintf(stderr, "[drx] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
-        t_prev = t;
-    };
     const size_t raw_bytes = (size_t)n_samples * 2;
     const size_t enc_cap_bytes = (size_t)plan->max_words * 4;
     void *result = nullptr;
@@ -835,27 +820,22 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts, co
         if (!reverse) {
             e = hipMemcpyAsync(ctx->d_raw, in, raw_bytes, hipMemcpyHostToDevice, ctx->stream);
             if (e != hipSuccess) { st = fail(ctx, DRX_ERR_DEVICE, "H2D failed: %s", hipGetErrorString(e)); break; }
-            lap("encode: H2D issue");
             if ((st = drx_encode(plan, (const int16_t *)ctx->d_raw, (uint32_t *)ctx->d_enc, plan->max_words, ctx->d_off)) != DRX_OK) break;
             uint64_t words = 0;
             if ((st = drx_plan_finish(plan, &words)) != DRX_OK) break;
-            lap("encode: kernels + finish");
             const size_t nb = (size_t)words * 4;
             result = malloc(nb);
             if (!result) { st = DRX_ERR_NOMEM; break; }
             e = hipMemcpyAsync(result, ctx->d_enc, nb, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            lap("encode: D2H");
             if (e != hipSuccess) { st = fail(ctx, DRX_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e)); break; }
             *out_bytes = nb;
         } else {
-            // The device finds the headers of a large chunk (parallel walk: 0.14 ms for 2000 waveforms; the CPU takes 0.28 ms,
-            // DRX_HOST_WALK=1 forces that, =0 forbids it).
+            // The device finds the headers of a large chunk (parallel walk: 0.14 ms for 2000 waveforms; the CPU takes 0.28 ms).
             const uint64_t W = plan->G.total_waves;
             // A chunk of a few hundred waveforms is walked on the CPU as well: ~0.14 us per hop out of host memory against
             // ~1 us per dependent load on the device (20 waveforms: 19 us) or the 60 us of the parallel walk's three launches.
-            static const char *walk_env = getenv("DRX_HOST_WALK");
-            const bool device_walk = walk_env ? atoi(walk_env) == 0 : W > 512u;
+            const bool device_walk = W > 512u;
             const size_t tab_bytes = 16 + (device_walk ? 0 : (size_t)W * (sizeof(uint64_t) + sizeof(uint32_t)));
             if ((st = grow(ctx, &ctx->h_pin, &ctx->pin_cap, tab_bytes, true)) != DRX_OK) break;
             uint64_t *h_off = (uint64_t *)ctx->h_pin;              // [2] chunk table, then [W] wave_off
@@ -863,7 +843,6 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts, co
             h_off[0] = 0;
             h_off[1] = (uint64_t)(nbytes / 4);
             e = hipMemcpyAsync(ctx->d_enc, in, nbytes, hipMemcpyHostToDevice, ctx->stream);
-            lap("decode: H2D chunk");
             if (e == hipSuccess) e = hipMemcpyAsync(ctx->d_off, h_off, 2 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
             if (!device_walk) {
                 if (!walk_chunk_host((const uint32_t *)in, nbytes / 4, n_samples, L, o.rice_k, h_off + 2, h_words)) {
@@ -871,21 +850,17 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts, co
                     st = fail(ctx, DRX_ERR_CORRUPT, "encoded chunk failed header-chain validation");
                     break;
                 }
-                lap("decode: host walk");
                 if (e == hipSuccess) e = hipMemcpyAsync(plan->d_wave_off, h_off + 2, W * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream);
                 if (e == hipSuccess) e = hipMemcpyAsync(plan->d_wave_words, h_words, W * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
-                lap("decode: H2D tables");
             }
             // (no wait here: the pinned table is not touched again before this call's final synchronisation)
             if (e != hipSuccess) { st = fail(ctx, DRX_ERR_DEVICE, "H2D failed: %s", hipGetErrorString(e)); break; }
             if ((st = decode_launch(plan, (const uint32_t *)ctx->d_enc, nbytes / 4, ctx->d_off, (int16_t *)ctx->d_raw, !device_walk)) != DRX_OK) break;
             if ((st = drx_plan_finish(plan, nullptr)) != DRX_OK) break;
-            lap("decode: kernels + finish");
             result = malloc(raw_bytes);
             if (!result) { st = DRX_ERR_NOMEM; break; }
             e = hipMemcpyAsync(result, ctx->d_raw, raw_bytes, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            lap("decode: D2H");
             if (e != hipSuccess) { st = fail(ctx, DRX_ERR_DEVICE, "D2H failed: %s", hipGetErrorString(e)); break; }
             *out_bytes = raw_bytes;
         }

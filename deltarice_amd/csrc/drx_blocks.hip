@@ -36,7 +36,6 @@
 // Delta filter only: the prefix sum over residual sums is what makes blocks independent.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <type_traits>
 
 #include "drx_device.h"
@@ -63,15 +62,9 @@ __host__ __device__ constexpr int blk_segw_plan(uint32_t k) { return k <= 4u ? 1
 __host__ __device__ constexpr int blk_segw_bits10(uint64_t b10) { return b10 >= 117u ? 19 : (b10 >= 82u ? 15 : (b10 >= 54u ? 11 : 9)); }
 __host__ __device__ constexpr uint32_t blk_lane_cap(int segw) { return segw <= 11 ? 76u : (segw == 15 ? 68u : 60u); }
 constexpr uint32_t kBlkPre = 8;          // words kept in front of a block: lane 0's run-up
-#ifndef DRX_BLK_GUESS_BITS
-#define DRX_BLK_GUESS_BITS 128
-#endif
-constexpr uint32_t kBlkGuessBits = DRX_BLK_GUESS_BITS;  // run-up in front of a segment (a parse is in step after a few codes; 96, 128,
+constexpr uint32_t kBlkGuessBits = 128;  // run-up in front of a segment (a parse is in step after a few codes; 96, 128,
                                          // 160 and 224 bits measured: within 4 % of one another, profiles/r02_notes.md)
-#ifndef DRX_BLK_ROUNDS
-#define DRX_BLK_ROUNDS 8
-#endif
-constexpr uint32_t kBlkRounds = DRX_BLK_ROUNDS;  // tickets per resident workgroup a launch should at least have (see run_len)
+constexpr uint32_t kBlkRounds = 8;       // tickets per resident workgroup a launch should at least have (see run_len)
 constexpr uint32_t kBlkTail = 4;         // words behind a block: a code that starts inside may end 24 bits behind it,
                                          // and a window reads three words
 
@@ -123,21 +116,6 @@ __device__ __forceinline__ void blk_barrier() {
 }
 
 enum { kBlkSkip = 0, kBlkCount = 1, kBlkValue = 2 };
-
-// Diagnostic build (-DDRX_BLK_STAMPS, never shipped): thread 0 of every workgroup adds the cycles between phase
-// boundaries into prof[]; launch_decode_blocks prints the shares.
-#ifdef DRX_BLK_STAMPS
-#define BLK_STAMP(i)                                                                                         \
-    do {                                                                                                     \
-        if (tid == 0) {                                                                                      \
-            const unsigned long long t_now = __builtin_amdgcn_s_memtime();                                   \
-            s_prof[(i)] += t_now - t_prev;                                                                   \
-            t_prev = t_now;                                                                                  \
-        }                                                                                                    \
-    } while (0)
-#else
-#define BLK_STAMP(i) do { } while (0)
-#endif
 
 // count-leading-zeros that is defined for 0: v_ffbh_u32 returns -1 there, which with the escape's 16 payload bits moves the
 // parse on by 15 + 1 bits -- any progress will do (an all-zero window is the padding behind a waveform or a corrupt stream)
@@ -301,6 +279,8 @@ __device__ __forceinline__ void blk_skip_pairs(const uint32_t *W, uint32_t k, bo
 // to the next run's first through `xstate` (one 8-byte word per block slot, its own flag).  That hand-over is a serial chain
 // along a waveform, so the host fuses only where runs of ONE waveform are rarely in flight together (as many waveforms as
 // resident workgroups); elsewhere the two-pass form stays.
+// (The order of the last arguments is part of the code: `out`, `wave_list` and the filter's tables are loaded on entry, the
+// compiler merges adjacent ones into one wider scalar load, and another merge moves this kernel's SGPR spills.)
 template <int NT, bool RESID, int SW, bool FUSE = false>
 __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
                                                       const uint64_t *__restrict__ wave_off,
@@ -309,9 +289,9 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                                                       uint32_t run_len, uint64_t *__restrict__ state,
                                                       uint32_t *__restrict__ ends, uint32_t *__restrict__ ticket,
                                                       uint32_t *__restrict__ fail, uint32_t *__restrict__ suspect,
-                                                      DevStatus *st, int16_t *__restrict__ out, unsigned long long *prof,
-                                                      const uint32_t *__restrict__ wave_list, uint32_t n_list,
-                                                      const uint32_t *__restrict__ itab, uint64_t *__restrict__ xstate) {
+                                                      DevStatus *st, int16_t *__restrict__ out, uint32_t n_list,
+                                                      const uint32_t *__restrict__ itab, uint64_t *__restrict__ xstate,
+                                                      const uint32_t *__restrict__ wave_list) {
     static_assert(!FUSE || RESID, "the fused inverse filter works on residuals");
     using BG = BlkGeom<NT, SW>;
     constexpr int kBlkSegW = SW;
@@ -356,16 +336,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
     typedef u32x4v __attribute__((address_space(1))) g_uint4;
     constexpr int NQ = (int)((BG::kLdsWords / 4u + NT - 1u) / NT);  // 16-byte pieces of an image per thread
 
-#ifdef DRX_BLK_STAMPS
-    // (per workgroup in LDS, added to the launch's counters once at the end: an atomic per stamp on sixteen shared addresses was
-    // itself what the stamped build waited for)
-    __shared__ unsigned long long s_prof[16];
-    if (tid < 16u) s_prof[tid] = 0ull;
-    unsigned long long t_prev = __builtin_amdgcn_s_memtime();
-    auto flush_prof = [&]() { if (tid == 0) for (int i = 0; i < 10; ++i) atomicAdd(prof + i, s_prof[i]); };
-#else
-    auto flush_prof = [] {};
-#endif
     // tickets: every lower ticket is held by a running (or finished) workgroup, so waiting for a predecessor cannot
     // deadlock whatever the dispatch order; the grid is sized to be resident
     uint32_t &s_next = s_e[NT + 2 * NW + 6];
@@ -559,7 +529,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
         uint32_t next_ticket = 0;
         if (tid == 0)
             asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(next_ticket) : "v"((uint64_t)(uintptr_t)ticket), "v"(1u) : "memory");
-        BLK_STAMP(0);  // ticket
         const uint64_t g = cur.g, pay_lo = cur.pay_lo;
         const uint32_t n = cur.n, blk_lo = cur.blk_lo, blk_hi = cur.blk_hi;
         const WaveRef r = locate(G, g);
@@ -590,7 +559,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
             store_image(cur, blk, img);
             if (tid == 0) s_defer = 0u;
             blk_barrier();
-            BLK_STAMP(1);  // image
 
             // ---- phase 1: where the codes of my segment start, how many there are, what they sum to ----
             const uint32_t B0 = 32u * s_i0, bend = B0 + 32u * avail;
@@ -612,7 +580,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
             else blk_count_pairs<RESID>(W, k, active, Qp, C - lim, cnt, sum, my_stage, kCap2);
             if (!active) { cnt = 0; sum = 0; }
             uint32_t e = C - Qp;  // first code that starts behind it (or where the padding starts)
-            BLK_STAMP(2);  // run-up + count (thread 0's wave)
 
             // Every lane must start where its predecessor ended; lanes that do not, start again from there.
             // CREEP: in a stream of equal-length codes whose pattern reads as the same codes from another phase (a slope-1 ramp
@@ -678,7 +645,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
             }
             settle();
             const bool defer = s_defer != 0u;  // (read behind settle()'s barriers)
-            BLK_STAMP(3);  // settle (includes waiting for the slowest wave)
             const uint32_t last_active = (avail + (uint32_t)kBlkSegW - 1u) / (uint32_t)kBlkSegW - 1u;
             const uint32_t e_last0 = s_e[last_active];
             const bool last_of_run = blk + 1u == blk_hi;
@@ -721,7 +687,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                     __hip_atomic_store(ends + sidx, 0x80000000u | (s_e[last_active] - bend), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             const uint32_t e_end = s_e[last_active];  // (after a correction: the corrected end)
-            BLK_STAMP(4);  // predecessor's end
 
             // ---- samples and residual sum in front of my segment (workgroup scan) and in front of the block ----
             const uint32_t incl_c = wave_incl_scan_dpp(cnt), incl_s = wave_incl_scan_dpp(sum);
@@ -793,7 +758,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                 if (lane == 0) { s_b[0] = ex_c; s_b[1] = ex_s; }
             }
             blk_barrier();
-            BLK_STAMP(5);  // scan + look-back
             const uint64_t base_c = s_b[0];
             const uint32_t acc_base = (uint32_t)s_b[1];
             run_base_c = base_c + tot_c;
@@ -904,10 +868,8 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                     if (cnt != 0u) op[cnt - 1u] = (uint16_t)(base16 + sum);  // (my last sample = the running sum behind my codes; residual mode: my last residual)
                 }
                 blk_barrier();
-                BLK_STAMP(6);  // reorder
                 if (FUSE) iir_lds(a0, blk_count);
                 copy_out(0u);
-                BLK_STAMP(7);  // copy-out
             } else {
                 // some lane holds more codes than its share (long runs of tiny residuals), or codes past the waveform's
                 // last sample (a corrupt stream): decode again from f, in as many staging passes as the block needs
@@ -929,12 +891,8 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                 __hip_atomic_store(xstate + sidx, (1ull << 63) | (uint64_t)(xs.x & 0xffffu) | ((uint64_t)(xs.y & 0xffffu) << 16) | ((uint64_t)(xs.z & 0xffffu) << 32),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             blk_barrier();  // W, the staging buffer and the s_* words are rewritten by the next block
-            BLK_STAMP(8);
-#ifdef DRX_BLK_STAMPS
-            if (tid == 0) s_prof[9] += 1ull;
-#endif
         }
-        if (next_unit >= total_units) { flush_prof(); return; }
+        if (next_unit >= total_units) return;
         unit = next_unit;
         cur = nxt;
     }
@@ -945,9 +903,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
 // ---------------------------------------------------------------------------
 static int nt_for_len(uint32_t wave_len, uint32_t k) {
     // lanes per block: a waveform of about (k + 3.5) bits per sample should fill most of its last block
-#ifdef DRX_BLK_FORCE_NT
-    return DRX_BLK_FORCE_NT;
-#endif
     const uint64_t typ_words = ((uint64_t)wave_len * (2u * k + 7u)) >> 6;
     return typ_words <= blk_words(64, k) ? 64 : (typ_words <= blk_words(128, k) ? 128 : 256);
 }
@@ -1044,11 +999,10 @@ static uint32_t blocks_slots_per_wave(const Geom &G) {  // blocks of a waveform 
 }
 
 constexpr uint32_t kBlkMaxClasses = 32;  // ragged batches: one launch per class of WaveformLengths floor(log2 L)
-// scratch: u32 info[32][4] | u32 fail[W] | u32 suspect[W] | u32 ticket[1] (+ pad to 16 bytes) | u32 ends[slots] | u64 state[slots] | u64 xstate[slots] | prof
+// scratch: u32 info[32][4] | u32 fail[W] | u32 suspect[W] | u32 ticket[1] (+ pad to 16 bytes) | u32 ends[slots] | u64 state[slots] | u64 xstate[slots]
 struct BlkScratch {
     uint32_t *info, *fail, *suspect, *ticket, *ends;
     uint64_t *state, *xstate;  // xstate: the inverse filter's state behind every block slot (FUSE)
-    unsigned long long *prof;  // 16 counters of the diagnostic build
     uint64_t bytes;
 };
 static BlkScratch blocks_layout(const Geom &G, void *base) {
@@ -1065,8 +1019,7 @@ static BlkScratch blocks_layout(const Geom &G, void *base) {
     const uint64_t ends32 = (U + 1u) & ~1ull;
     L.state = reinterpret_cast<uint64_t *>(L.ends + ends32);
     L.xstate = L.state + U;
-    L.prof = reinterpret_cast<unsigned long long *>(L.xstate + U);
-    L.bytes = (n32 + ends32) * 4u + 2u * U * 8u + 16u * 8u;
+    L.bytes = (n32 + ends32) * 4u + 2u * U * 8u;
     return L;
 }
 
@@ -1082,11 +1035,7 @@ hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in
     const uint32_t spw = blocks_slots_per_wave(G);
     // the block geometry of this decode: by the stream's bits per sample as the caller states them (a wrong in_words costs speed, nothing else)
     const uint64_t b10 = G.total_samples ? 320ull * in_words / G.total_samples : 65ull;
-#ifdef DRX_BLK_FORCE_SW
-    const int sw = DRX_BLK_FORCE_SW;
-#else
     const int sw = blk_segw_bits10(b10);
-#endif
     // General filters: the inverse filter inside this kernel (FUSE) where its state can pass from a run's last block to the next
     // run's first without a chain of waits, i.e. where every launch has at least as many waveforms as resident workgroups (the
     // condition under which runs are longer than one block); else residuals now and k_iir_tiles behind (DRX_DBG_IIR_SEPARATE: always).
@@ -1126,7 +1075,7 @@ hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in
             // the filter's tables for runs of this geometry's lane share (76 / 68 / 60 samples)
             const uint32_t *itab = G.blk_iir_tab ? G.blk_iir_tab + kRunTabWords * (blk_lane_cap(SW) == 76u ? 0u : (blk_lane_cap(SW) == 68u ? 1u : 2u)) : nullptr;
             k_decode_blocks<NT, MODE != 0, SW, MODE == 2><<<grid, NT, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, info, spw, run_len, L.state, L.ends,
-                                                                             info + 2, L.fail, L.suspect, d_status, d_out, L.prof, list, n_waves, itab, L.xstate);
+                                                                             info + 2, L.fail, L.suspect, d_status, d_out, n_waves, itab, L.xstate, list);
         };
         auto by_sw = [&](auto nt_tag, auto resid_tag, unsigned per_cu) {
             switch (sw) {
@@ -1154,19 +1103,6 @@ hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in
             launch_class(c, G.rag_blk_list + G.rag_blk_class_off[c], G.rag_blk_class_off[c + 1] - G.rag_blk_class_off[c],
                          nt_for_len(G.rag_blk_class_len[c], G.k), G.rag_blk_class_len[c]);
     }
-#ifdef DRX_BLK_STAMPS
-    {
-        unsigned long long h[16];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, L.prof, sizeof h, hipMemcpyDeviceToHost);
-        static const char *names[9] = {"ticket", "image load", "run-up + count", "settle", "pred end", "scan + look-back", "reorder", "copy-out", "tail"};
-        unsigned long long tot = 0;
-        for (int i = 0; i < 9; ++i) tot += h[i];
-        fprintf(stderr, "[blk stamps]");
-        for (int i = 0; i < 9; ++i) fprintf(stderr, " %s %.1f%%", names[i], 100.0 * (double)h[i] / (double)(tot ? tot : 1));
-        fprintf(stderr, "  | %llu blocks, %.0f ticks of s_memtime each\n", h[9], (double)tot / (double)(h[9] ? h[9] : 1));
-    }
-#endif
     *fail_out = L.fail;
     *suspect_out = L.suspect;
     return hipGetLastError();

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(kLongThreads) void k_decode_long(Geom G, const uint
                 const uint32_t d = (z >> 1) ^ (0u - (z & 1u));
                 const uint32_t s2 = sacc + d;
                 if (EMIT) {
-                    if (act && idx + c < len && !(kAblate && (G.dbg & kAbLongNoStores))) {
+                    if (act && idx + c < len) {
                         const uint32_t i = idx + c;
                         if (((i + par4) & 1u) == 0u) {  // low half of an aligned dword: wait for the next sample
                             held = s2 & 0xffffu;
@@ -365,14 +365,7 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
     // three consecutive words: rows r + 1, r, r - 1)
     __shared__ uint32_t ring_all[(RW + 2) * 64];
     uint32_t *const ring = ring_all + 64;
-#ifdef DRX_DEC_NOOBUF  // (ablation builds: no transposition buffer, a lane's sample stores go to four words, no write-out)
-    constexpr int OBW = 256;
-    constexpr bool kNoObuf = true;
-#else
-    constexpr int OBW = 64 * OSW;
-    constexpr bool kNoObuf = false;
-#endif
-    __shared__ __attribute__((aligned(16))) uint32_t obuf[OBW];  // doubles as the start-up tables
+    __shared__ __attribute__((aligned(16))) uint32_t obuf[64 * OSW];  // doubles as the start-up tables
     uint64_t *tab_off = reinterpret_cast<uint64_t *>(obuf);  // [64] sample offset of step 0 of round 0
     uint32_t *tab_lo = obuf + 128, *tab_hi = obuf + 192;      // [64] each
     static_assert(64 * OSW >= 256, "tables fit in obuf");
@@ -530,13 +523,7 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
     const bool in_vec_ok = ((uintptr_t)in & 15u) == 0;
     uint32_t *myring = ring + lane;
     typedef uint16_t __attribute__((may_alias)) u16a;
-#ifdef DRX_DEC_NOOBUF
-    u16a *myout = reinterpret_cast<u16a *>(obuf + lane * 4);
-#define DRX_OIDX(x) ((x) & 6)
-#else
     u16a *myout = reinterpret_cast<u16a *>(obuf + lane * OSW);
-#define DRX_OIDX(x) (x)
-#endif
     // the round's whole-line stores
     auto store16 = [&](g_i16 *dst, const uint4 &v) __attribute__((always_inline)) {
         *(g_uint4 *)dst = (u32x4v){v.x, v.y, v.z, v.w};
@@ -591,12 +578,10 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
             const uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
             const bool more = flw < endw;
             if (!__any(more && avail < NEED_AT)) break;
-            if (more && avail <= (uint32_t)(RW - LW) && !(kAblate && (G.dbg & kAbNoLoads))) {
+            if (more && avail <= (uint32_t)(RW - LW)) {
                 uint4 v[NV];
                 load_piece(v);
                 store_piece(v);
-            } else if (more && avail <= (uint32_t)(RW - LW)) {
-                flw += (uint32_t)LW;
             }
             wave_sync();
         }
@@ -607,7 +592,8 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
         for (int i = 0; i < RW / LW; ++i) {
             if (__ballot(flw < endw && flw + (uint32_t)LW <= s0 + (uint32_t)RW) == 0) break;
             if (flw < endw && flw + (uint32_t)LW <= s0 + (uint32_t)RW) {
-                if (!(kAblate && (G.dbg & kAbNoLoads))) { load_piece(v); store_piece(v); } else flw += (uint32_t)LW;
+                load_piece(v);
+                store_piece(v);
             }
         }
         wave_sync();
@@ -672,7 +658,7 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
                 const uint32_t a1 = (uint32_t)acc;
                 advance((int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u));
                 // low halves of the two running sums in one v_perm_b32
-                *reinterpret_cast<uint32_t *>(myout + DRX_OIDX(tg + u)) = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u);
+                *reinterpret_cast<uint32_t *>(myout + tg + u) = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u);
             }
             return;
         }
@@ -697,7 +683,7 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
             y3 = act ? y3 : o3;
             Q = act ? Q - used : Q;
             if constexpr (EDGE) Q_end = (tcur + (uint32_t)u + 1u == hi_step) ? Q : Q_end;
-            myout[DRX_OIDX(tg + u)] = (uint16_t)acc;
+            myout[tg + u] = (uint16_t)acc;
         }
     };
 
@@ -718,7 +704,6 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
         }
     };
     auto write_out = [&](uint32_t t0) __attribute__((always_inline)) {
-        if (kNoObuf || (kAblate && (G.dbg & kAbNoStores))) return;
         if (t0 >= lo_max && t0 + T <= hi_min) {  // interior round: whole aligned lines only
 #pragma unroll
             for (int i = 0; i < PPS; ++i) {
@@ -770,7 +755,7 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
     uint32_t t0 = T;
     for (; t0 < steps && !(t0 >= lo_max && t0 + T <= hi_min); t0 += T) edge_round(t0);
 
-    const uint32_t min_words = (kAblate && (G.dbg & kAbNoMinConsume)) ? 0u : ((uint32_t)T * (k + 1u)) >> 5;
+    const uint32_t min_words = ((uint32_t)T * (k + 1u)) >> 5;
     uint4 pv0[NV], pv1[NV];               // pieces in flight
     bool pneed0 = false, pneed1 = false;  // this lane has them in flight
     set_limits();
@@ -813,18 +798,16 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
             // samples of at least k + 1 bits each, i.e. consumed min_words more words
             const uint32_t mc = (t0 + 2u * T <= hi_min && t0 + T < steps) ? min_words : 0u;
             const uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
-            pneed0 = (flw < endw) && avail + (uint32_t)LW <= (uint32_t)RW + mc && !(kAblate && (G.dbg & kAbNoLoads));
+            pneed0 = (flw < endw) && avail + (uint32_t)LW <= (uint32_t)RW + mc;
             pneed1 = pneed0 && (flw + (uint32_t)LW < endw) && avail + 2u * (uint32_t)LW <= (uint32_t)RW + mc;
             if (pneed0) load_piece(pv0);
             if (pneed1) load_piece(pv1, (uint32_t)LW);
         }
-        if (!(kNoObuf || (kAblate && (G.dbg & kAbNoStores)))) {
 #pragma unroll
-            for (int i = 0; i < PPS; ++i) {  // whole aligned lines only
-                const int st = i * SPI + lane / PPS, p = lane % PPS;
-                const uint4 v = orow16(st, p);
-                store16(outg + wo_off[i] + t0, v);
-            }
+        for (int i = 0; i < PPS; ++i) {  // whole aligned lines only
+            const int st = i * SPI + lane / PPS, p = lane % PPS;
+            const uint4 v = orow16(st, p);
+            store16(outg + wo_off[i] + t0, v);
         }
         wave_sync();
     }
@@ -956,17 +939,6 @@ void decode_plan_ragged(Geom &G, const ChunkDesc *d, std::vector<uint32_t> *walk
     G.rag_pw_min_waves = min_long_waves;
 }
 
-// Ablation builds only: DRX_DEC_LDS_PAD = bytes of dynamic LDS added to every k_decode_lanes launch (occupancy A/B at an
-// unchanged instruction stream: 26 KB + pad per wavefront decides how many of them a CU holds).
-static unsigned dec_lds_pad() {
-#ifdef DRX_ABLATION
-    static const unsigned pad = [] { const char *e = getenv("DRX_DEC_LDS_PAD"); return e ? (unsigned)atoi(e) : 0u; }();
-    return pad;
-#else
-    return 0u;
-#endif
-}
-
 // ---------------------------------------------------------------------------
 // How a decode call is routed: ONE table, first matching row wins (route_decode()).
 //
@@ -1041,7 +1013,6 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
     uint32_t &path = path_out ? *path_out : path_dummy;
     path = 0;
     if (G.total_waves == 0) return hipSuccess;
-    const unsigned lpad = dec_lds_pad();
     mark(ev, 0, s);
     // impl >= 100: wave_off / wave_words are already filled in (the one-chunk host path walks the header chain on the CPU while
     // the chunk is in flight to the device; the side-band decode derives them from the caller's table): no walk
@@ -1055,9 +1026,9 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
     auto launch_lanes = [&](const Geom &Gv, unsigned nb, hipStream_t st_) {
         path |= 2u;  // DRX_PATH_LANES
         if (gen)
-            k_decode_lanes<false, true><<<nb, 64, lpad, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
+            k_decode_lanes<false, true><<<nb, 64, 0, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
         else
-            k_decode_lanes<false><<<nb, 64, lpad, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
+            k_decode_lanes<false><<<nb, 64, 0, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
     };
 
     // ---- the walk ----
@@ -1190,9 +1161,9 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         }
         path |= 1u;  // DRX_PATH_LANES_FUSED
         if (gen)
-            k_decode_lanes<true, true><<<nb, 64, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
+            k_decode_lanes<true, true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
         else
-            k_decode_lanes<true><<<nb, 64, lpad, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
+            k_decode_lanes<true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
         break;
     }
     case Dec::Blocks: {

@@ -9,17 +9,6 @@
 
 namespace drx {
 
-// Ablation switches inside the hot loops (Geom::dbg bits beside DRX_DBG_*; results invalid), only in -DDRX_ABLATION builds (A/B
-// timing through DRX_LIB_PATH).  decode: no output / long-waveform stores, no stream loads, pieces requested without counting on a
-// round's minimum consumption; encode: per-code LDS emission, no emission, no copy-out, no look-back.
-#ifdef DRX_ABLATION
-constexpr bool kAblate = true;
-#else
-constexpr bool kAblate = false;
-#endif
-constexpr uint32_t kAbNoStores = 1, kAbLongNoStores = 16384, kAbNoLoads = 2, kAbNoMinConsume = 4;
-constexpr uint32_t kAbLdsEmit = 16, kAbNoEmit = 32, kAbNoCopyOut = 64, kAbNoLookback = 128, kAbSparsePlace = 1024;
-
 // ---------------------------------------------------------------------------
 // small device helpers
 // ---------------------------------------------------------------------------

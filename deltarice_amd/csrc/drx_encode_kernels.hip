@@ -15,8 +15,6 @@
 // (The packed tile code: drx_encode.h; short and very long waveforms: drx_pieces.hip.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -306,47 +304,17 @@ __global__ __launch_bounds__(256) void k_encode_pack(Geom G, const int16_t *__re
 // re-encoded tile by tile straight to its final position (second read of its samples).
 // (the packed tile code: drx_encode.h)
 
-#ifndef DRX_ENC_WAVES
-#define DRX_ENC_WAVES 8
-#endif
-constexpr int kEncWaves = DRX_ENC_WAVES;  // waveforms (wavefronts) per workgroup = per ticket
-#ifndef DRX_ENC_LB_WIN
-#define DRX_ENC_LB_WIN 2
-#endif
-#ifndef DRX_ENC_GATE_SLEEP
-#define DRX_ENC_GATE_SLEEP 8
-#endif
-constexpr int kLbWin = DRX_ENC_LB_WIN;  // look-back window of k_encode_fused in units of 64 entries
+constexpr int kEncWaves = 8;      // waveforms (wavefronts) per workgroup = per ticket
+constexpr int kLbWin = 2;         // look-back window of k_encode_fused in units of 64 entries
+constexpr int kEncGateSleep = 8;  // s_sleep between two polls of the nearest predecessor's entry
 
-#ifndef DRX_ENC_WAVES_PER_EU
-#define DRX_ENC_WAVES_PER_EU 1
-#endif
 // WV x CAPW: waveforms per workgroup x LDS words per waveform.  8 x 2048 (9.3 bits per sample at WaveformLength 7000) is the
 // measured geometry of the headline workload; noisier data with the RiceParameter that suits it needs k + 3.5 bits per
 // sample, and a waveform whose code outgrows its buffer is coded twice -- 8 x 2496 (two workgroups per CU), 4 x 3072 (three)
 // and 4 x 4096 words (two) keep the single pass for it (fused_wide(), drx_internal.h).  Six waveforms per workgroup were
 // measured a third slower whatever the buffer (three of them on two SIMDs, one each on the others).
-// Diagnostic build (-DDRX_ENC_STAMPS, never shipped): lane 0 of every workgroup's wave 0 adds the 100 MHz ticks between the
-// phases of k_encode_fused into eight counters behind the look-back state; launch_encode_fused prints the shares.
-//   0 encode (start -> all eight waveforms coded)   1 gate (nearest predecessor has published ANYTHING)
-//   2 window (a prefix found behind it)   3 copy-out of wave 0
-#ifdef DRX_ENC_STAMPS
-// (a slot per workgroup in the upper half of the look-back state, which k_encode_fused does not use: atomics on eight shared
-// counters ran at the rate of one counter -- ~88 per microsecond -- and turned a 5.5 ms kernel into an 8 ms one)
-#define ENC_STAMP(i)                                                                        \
-    do {                                                                                    \
-        if (threadIdx.x == 0) {                                                             \
-            const uint64_t t_now = __builtin_amdgcn_s_memrealtime();                        \
-            scan_state[G.total_waves + 16 + (uint64_t)s_ticket * 4u + (i)] = t_now - t_prev; \
-            t_prev = t_now;                                                                 \
-        }                                                                                   \
-    } while (0)
-#else
-#define ENC_STAMP(i) do { } while (0)
-#endif
-
-template <bool GEN, int WV = DRX_ENC_WAVES, uint32_t CAPW = kEncCapWords>
-__global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(Geom G, const int16_t *__restrict__ in,
+template <bool GEN, int WV = kEncWaves, uint32_t CAPW = kEncCapWords>
+__global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16_t *__restrict__ in,
                                                       uint32_t *__restrict__ out, uint64_t out_cap,
                                                       uint64_t *__restrict__ chunk_word_off,
                                                       uint32_t *__restrict__ wave_words,
@@ -368,9 +336,6 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
     // wave.  One ticket per workgroup of kEncWaves waveforms: a single global counter serves
     // about 88 atomics per microsecond (a ticket per waveform made the whole kernel run at
     // exactly that rate: 1M waveforms in 11.9 ms).
-#ifdef DRX_ENC_STAMPS
-    uint64_t t_prev = __builtin_amdgcn_s_memrealtime();
-#endif
     if (threadIdx.x == 0) s_ticket = atomicAdd(ticket, 1u);
     __syncthreads();
     const uint64_t g = (uint64_t)s_ticket * kEncWaves + (threadIdx.x >> 6);
@@ -417,9 +382,8 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
         if (FULLT) concat_codes(c, cw);  // independent of the scan: fills its DPP wait states
         const uint32_t incl = wave_incl_scan_dpp(lane_bits);
         const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        if (kAblate && (G.dbg & kAbNoEmit)) {  // ablation: no emission
-        } else if (fits && ((P + tile_bits + 31u) >> 5) < (uint64_t)kEncCapWords) {
-            if (FULLT && !(kAblate && (G.dbg & kAbLdsEmit)) && !__any(lane_bits > 128u))
+        if (fits && ((P + tile_bits + 31u) >> 5) < (uint64_t)kEncCapWords) {
+            if (FULLT && !__any(lane_bits > 128u))
                 place_words(cw, buf_bits + (uint32_t)P + incl);
             else
                 emit_tile<FULLT>(c, buf_bits + (uint32_t)P + incl - lane_bits);
@@ -492,16 +456,14 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
     const int wv = threadIdx.x >> 6;
     if (lane == 0) s_mine[wv] = mine;
     __syncthreads();
-    ENC_STAMP(0);
     if (wv == 0) {
         uint64_t block_sum = 0;
 #pragma unroll
         for (int i = 0; i < kEncWaves; ++i) block_sum += s_mine[i];
         const uint64_t T = s_ticket;
         uint64_t excl_blk = 0;
-        if (T == 0 || (kAblate && (G.dbg & kAbNoLookback))) {  // (ablation: positions are wrong)
+        if (T == 0) {
             if (lane == 0) __hip_atomic_store(scan_state + T, kScanPrefix | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (T) excl_blk = T * 2048ull * kEncWaves;
         } else {
             if (lane == 0) __hip_atomic_store(scan_state + T, kScanAgg | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             int64_t base = (int64_t)T - 1;
@@ -514,10 +476,9 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
                 uint64_t v = 0;
                 if (lane == 0) v = __hip_atomic_load(scan_state + base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 62)) != 0) break;
-                __builtin_amdgcn_s_sleep(DRX_ENC_GATE_SLEEP);
+                __builtin_amdgcn_s_sleep(kEncGateSleep);
                 if (++spins > (1u << 22)) break;  // (the window loop below reports it)
             }
-            ENC_STAMP(1);
             // kLbWin x 64 entries per poll.  The frontier of known prefixes advances one window per hop (a hop = an
             // agent-scope store becoming visible + an agent-scope load, 3-5 us under the encoder's own streaming loads), so
             // the window bounds the rate of the whole kernel: 128 entries carried ~25 workgroups per microsecond, just what
@@ -562,9 +523,7 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
             if (lane == 0)
                 __hip_atomic_store(scan_state + T, kScanPrefix | (excl_blk + block_sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (kAblate && (G.dbg & kAbSparsePlace)) excl_blk = T * 2048ull * kEncWaves;  // ablation: look-back done, sparse placement all the same
         if (lane == 0) s_excl = excl_blk;
-        ENC_STAMP(2);
     }
     __syncthreads();
     uint64_t excl = s_excl;
@@ -589,23 +548,17 @@ __global__ __launch_bounds__(64 * WV, DRX_ENC_WAVES_PER_EU) void k_encode_fused(
     }
     uint32_t *__restrict__ outp = out + pos + 1;
     if (fits) {
-        if (!(kAblate && (G.dbg & kAbNoCopyOut))) {
-            // 16 bytes per lane: 1 KB per store instruction instead of 256 bytes.  The waveform's place in the stream is
-            // only word aligned; unaligned vector stores are on for HSA queues, and a wavefront's 64 pieces are contiguous
-            // whatever their alignment (round 3: 22 store instructions per waveform became 6)
-            typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
-            typedef u32x4s __attribute__((address_space(1), aligned(4))) g_u32x4_a4;
-            const uint32_t n4 = n & ~3u;
-            for (uint32_t i = 4u * (uint32_t)lane; i < n4; i += 256u) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(buf + i);
-                *(g_u32x4_a4 *)(outp + i) = (u32x4s){v.x, v.y, v.z, v.w};
-            }
-            if ((uint32_t)lane < n - n4) outp[n4 + (uint32_t)lane] = buf[n4 + (uint32_t)lane];
+        // 16 bytes per lane: 1 KB per store instruction instead of 256 bytes.  The waveform's place in the stream is only word
+        // aligned; unaligned vector stores are on for HSA queues, and a wavefront's 64 pieces are contiguous whatever their
+        // alignment (round 3: 22 store instructions per waveform became 6)
+        typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));
+        typedef u32x4s __attribute__((address_space(1), aligned(4))) g_u32x4_a4;
+        const uint32_t n4 = n & ~3u;
+        for (uint32_t i = 4u * (uint32_t)lane; i < n4; i += 256u) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(buf + i);
+            *(g_u32x4_a4 *)(outp + i) = (u32x4s){v.x, v.y, v.z, v.w};
         }
-#ifdef DRX_ENC_STAMPS
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ENC_STAMP(3);
-#endif
+        if ((uint32_t)lane < n - n4) outp[n4 + (uint32_t)lane] = buf[n4 + (uint32_t)lane];
         return;
     }
 
@@ -859,17 +812,6 @@ hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned lo
     return hipGetLastError();
 }
 
-// Ablation builds only: DRX_ENC_LDS_PAD = bytes of dynamic LDS added to every k_encode_fused launch (occupancy A/B at an
-// unchanged instruction stream).
-static unsigned enc_lds_pad() {
-#ifdef DRX_ABLATION
-    static const unsigned pad = [] { const char *e = getenv("DRX_ENC_LDS_PAD"); return e ? (unsigned)atoi(e) : 0u; }();
-    return pad;
-#else
-    return 0u;
-#endif
-}
-
 // Single-pass encode (k_encode_fused).  d_scan: uint64[total_waves] + one uint32 ticket
 // word after it, zeroed here on the stream before every launch.
 hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
@@ -886,8 +828,8 @@ hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uin
         constexpr bool GEN = decltype(gen_tag)::value;
         constexpr int WV = decltype(wv_tag)::value;
         constexpr uint32_t CAPW = decltype(cap_tag)::value;
-        k_encode_fused<GEN, WV, CAPW><<<blocks_for(G.total_waves, WV), 64 * WV, enc_lds_pad(), s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words,
-                                                                                    d_scan, ticket, d_status);
+        k_encode_fused<GEN, WV, CAPW><<<blocks_for(G.total_waves, WV), 64 * WV, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words,
+                                                                                      d_scan, ticket, d_status);
     };
     using std::integral_constant;
     const std::true_type T;
@@ -900,20 +842,6 @@ hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uin
         default: pick(integral_constant<int, kEncWaves>{}, integral_constant<uint32_t, kEncCapWords>{}); break;
     }
     mark(ev, 3, s);
-#ifdef DRX_ENC_STAMPS
-    if (G.total_waves >= 64) {
-        const uint64_t wgs = blocks_for(G.total_waves, kEncWaves);
-        unsigned long long *h = (unsigned long long *)malloc(wgs * 4 * sizeof(unsigned long long));
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, d_scan + G.total_waves + 16, wgs * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        double sum[4] = {0, 0, 0, 0};
-        for (uint64_t i = 0; i < wgs; ++i)
-            for (int j = 0; j < 4; ++j) sum[j] += (double)h[i * 4 + j];
-        free(h);
-        fprintf(stderr, "enc stamps (us per workgroup, 100 MHz ticks): encode %.2f  gate %.2f  window %.2f  copy-out %.2f  | %llu workgroups\n",
-                sum[0] / wgs / 100.0, sum[1] / wgs / 100.0, sum[2] / wgs / 100.0, sum[3] / wgs / 100.0, (unsigned long long)wgs);
-    }
-#endif
     return hipGetLastError();
 }
 

@@ -27,8 +27,6 @@
 // look-back of this library.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -40,10 +38,7 @@ namespace drx {
 
 // wavefronts per workgroup = waveforms per ticket; 16 wavefronts per CU either way (4: 4.95 ms on the headline, 8: 5.1 -- the
 // rendezvous of four costs less than that of eight; with the priority feedback below 4.80 / 4.84)
-#ifndef DRX_ES_WAVES
-#define DRX_ES_WAVES 4
-#endif
-constexpr int kEsWaves = DRX_ES_WAVES;
+constexpr int kEsWaves = 4;
 constexpr uint32_t kEsFront = 4;   // pad words in front of a ring (place_words writes up to four words below a lane's last)
 constexpr uint32_t kEsBack = 12;   // ... and behind it (emit_tile runs up to eight codes past a lane's first word)
 constexpr uint64_t kEsFlag = 1ull << 63;
@@ -51,26 +46,7 @@ constexpr uint32_t kEsCtrlWords = 32;  // uint64 words of control state: 128 byt
 // ring words per wavefront: 16 x (2496 + 16) x 4 bytes = 157 KB, 16 wavefronts per CU (the geometry fused_wide() = 1 already
 // runs); a 1414-word waveform (the headline's) leaves the next one 1072 words = nine tiles before it has to know its place
 constexpr uint32_t kEsRing = kEsRingWords;  // (drx_internal.h: the dispatch needs it too)
-#ifndef DRX_ES_POLL_SLEEP
-#define DRX_ES_POLL_SLEEP 4
-#endif
-
-// Diagnostic build (-DDRX_ENC_STAMPS, never shipped): every workgroup counts in LDS and adds its counts to eight shared
-// counters when its wavefronts leave (a global atomic per event ran the kernel at the rate of one counter; counters in
-// per-lane registers spilled).
-//   0 ticks (100 MHz) spent in wait_place   1 waits   2 waveforms placed by a look-up between tile groups   3 waveforms
-//   4 waveforms streamed   5 ticks from kernel start to the wavefront's exit   6 ticks at the rendezvous   7 failed polls
-// ... and, with DRX_ES_TRACE=file in the environment, five 100 MHz stamps per waveform, written to the file after the launch
-// (tools/r04_es_trace.py reads it): 1 begun, 2 size known, 3 place seen by its coder; in the slot of a ticket's first
-// waveform also 0 the ticket's total published and 4 its place stored by the scanner
-#ifdef DRX_ENC_STAMPS
-__device__ uint64_t *g_es_trace = nullptr;
-#define ES_COUNT(i, v) do { if (lane == 0) __hip_atomic_fetch_add((lds_u64 *)&s_prof[i], (uint64_t)(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } while (0)
-#define ES_TRACE(g, i) do { if (trace && lane == 0) trace[5ull * (g) + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define ES_COUNT(i, v) do { } while (0)
-#define ES_TRACE(g, i) do { } while (0)
-#endif
+constexpr int kEsPollSleep = 4;  // s_sleep between two polls of a ticket's place
 
 __device__ __forceinline__ uint64_t es_load(const uint64_t *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -87,22 +63,15 @@ __device__ __forceinline__ void es_store(uint64_t *p, uint64_t v) {
 // over one entry per WAVEFORM: a 512-lane window with three workgroup barriers per round, eight wavefronts on a block of 512
 // entries each chained through LDS, one wavefront with 1024- and 2048-entry windows -- a round took 5 / 7 / 5 / 16 us and
 // the sweep, 100-200 entries per microsecond, was the kernel's rate every time.)
-#ifndef DRX_ES_SCAN_PER
-#define DRX_ES_SCAN_PER 8
-#endif
-constexpr uint32_t kScPer = DRX_ES_SCAN_PER;
+constexpr uint32_t kScPer = 8;
 
-__device__ __forceinline__ void es_scanner(uint64_t total, uint32_t wv_per_ticket, const uint64_t *__restrict__ size,
-                                           uint64_t *__restrict__ place, DevStatus *st, unsigned long long *prof, uint64_t *trace) {
+__device__ __forceinline__ void es_scanner(uint64_t total, const uint64_t *__restrict__ size, uint64_t *__restrict__ place,
+                                           DevStatus *st) {
     const int lane = lane_id();
     if (threadIdx.x >= 64) return;
     __builtin_amdgcn_s_setprio(3);
     uint64_t pos = 0, base = 0;  // the frontier: every entry below pos has its place; base = words in front of entry pos
     uint32_t idle = 0;
-#ifdef DRX_ENC_STAMPS
-    unsigned long long sc_rounds = 0, sc_idle = 0, sc_full = 0;
-    const uint64_t sc_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
     auto sample = [&](uint64_t (&v)[kScPer], uint64_t at) {
 #pragma unroll
         for (int j = 0; j < (int)kScPer; ++j) {
@@ -111,9 +80,6 @@ __device__ __forceinline__ void es_scanner(uint64_t total, uint32_t wv_per_ticke
         }
     };
     while (pos < total) {
-#ifdef DRX_ENC_STAMPS
-        ++sc_rounds;
-#endif
         uint64_t v[kScPer];
         const uint64_t bs = pos;
         sample(v, pos);
@@ -131,9 +97,6 @@ __device__ __forceinline__ void es_scanner(uint64_t total, uint32_t wv_per_ticke
         uint64_t end = bs + run;  // the new frontier
         end = end < total ? end : total;
         if (end <= pos) {
-#ifdef DRX_ENC_STAMPS
-            ++sc_idle;
-#endif
             if (++idle > (1u << 22)) {  // (bounded like every wait of this library: seconds)
                 if (lane == 0) atomicOr(&st->err, kErrInternal);
                 return;
@@ -142,9 +105,6 @@ __device__ __forceinline__ void es_scanner(uint64_t total, uint32_t wv_per_ticke
             continue;
         }
         idle = 0;
-#ifdef DRX_ENC_STAMPS
-        if (end - bs == 64u * kScPer) ++sc_full;
-#endif
         uint64_t running = 0;
 #pragma unroll
         for (int j = 0; j < (int)kScPer; ++j) {
@@ -164,21 +124,12 @@ __device__ __forceinline__ void es_scanner(uint64_t total, uint32_t wv_per_ticke
                     }
                 }
                 if (in) es_store(place + e, kEsFlag | (base + running + inc - val));
-#ifdef DRX_ENC_STAMPS
-                if (in && trace) trace[5ull * e * wv_per_ticket + 4] = __builtin_amdgcn_s_memrealtime();
-#endif
                 running += big ? __shfl(inc, 63) : (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)inc, 63);
             }
         }
         base += running;
         pos = end;
     }
-#ifdef DRX_ENC_STAMPS
-    if (lane == 0) {
-        prof[8] = sc_rounds; prof[9] = sc_idle; prof[10] = sc_full;
-        prof[11] = __builtin_amdgcn_s_memrealtime() - sc_t0;
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -189,7 +140,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                                                               uint64_t out_cap, uint64_t *__restrict__ chunk_word_off,
                                                               uint32_t *__restrict__ wave_words, uint64_t *__restrict__ size,
                                                               uint64_t *__restrict__ place, uint32_t *__restrict__ ctrl,
-                                                              DevStatus *st, unsigned long long *prof) {
+                                                              DevStatus *st) {
     __shared__ __attribute__((aligned(16))) uint32_t ring_all[WV][kEsFront + RING + kEsBack];
     __shared__ uint32_t s_role, s_arrive, s_ticket[4];
     __shared__ uint64_t s_mine[2][WV];              // sizes of the waveforms of the last two tickets
@@ -197,13 +148,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     __shared__ uint32_t s_place_t[2];               // ... and which ticket (+ 1) that was
     typedef uint32_t __attribute__((address_space(3))) lds_u32;
     typedef uint64_t __attribute__((address_space(3))) lds_u64;
-#ifdef DRX_ENC_STAMPS
-    __shared__ uint64_t s_prof[8];
-    if (threadIdx.x < 8) s_prof[threadIdx.x] = 0;
-    uint64_t *trace = g_es_trace;
-#else
-    uint64_t *trace = nullptr;
-#endif
     static_assert((kEsFront + RING + kEsBack) % 4 == 0 && RING % 4 == 0, "16-byte LDS accesses");
     constexpr uint32_t kRingBits = RING * 32u;
     const int lane = lane_id(), wv = threadIdx.x >> 6;
@@ -220,16 +164,13 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     __syncthreads();
     const uint64_t n_tickets = (G.total_waves + WV - 1) / WV;
     if (s_role == 0) {  // the first workgroup to start sweeps the totals; everybody else codes
-        es_scanner(n_tickets, (uint32_t)WV, size, place, st, prof, trace);
+        es_scanner(n_tickets, size, place, st);
         return;
     }
 
     const uint32_t k = G.k;
     const u16x2 tp[4] = {splat(GEN ? G.enc_t[0] : 1u), splat(GEN ? G.enc_t[1] : 0xffffu), splat(GEN ? G.enc_t[2] : 0u),
                          splat(GEN ? G.enc_t[3] : 0u)};
-#ifdef DRX_ENC_STAMPS
-    const uint64_t es_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
     // ---- waveform A: coded, waiting in the ring (or, if it did not fit, not at all) for its place.  Wave uniform. ----
     bool pend = false, fitsA = true;
@@ -258,7 +199,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     };
     // copies waveform A out (its ticket begins `ex` words into the stream) and clears its part of the ring
     auto copy_out = [&](uint64_t ex) {
-        ES_TRACE(gA, 3);
         const WaveRef rA = locate(G, gA);
         uint64_t pos;
         const bool room = place_header(rA, gA, nA, ex + offA, pos);
@@ -297,11 +237,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     };
     // the same, waiting for it (bounded; a wait that expires reports kErrInternal and returns a place nothing is written to)
     auto wait_place = [&]() -> uint64_t {
-        if (kAblate && (G.dbg & kAbNoLookback)) return (uint64_t)TA * WV * 2048ull;  // ablation: no waiting at all (positions are wrong)
         uint32_t spins = 0;
-#ifdef DRX_ENC_STAMPS
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-#endif
         for (;;) {
             uint64_t ex;
             bool have = place_in_lds(ex);
@@ -315,15 +251,8 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                     have = true;
                 }
             }
-            if (have) {
-#ifdef DRX_ENC_STAMPS
-                ES_COUNT(0, __builtin_amdgcn_s_memrealtime() - t0);
-                ES_COUNT(1, 1);
-#endif
-                return ex;
-            }
-            __builtin_amdgcn_s_sleep(DRX_ES_POLL_SLEEP);
-            ES_COUNT(7, 1);
+            if (have) return ex;
+            __builtin_amdgcn_s_sleep(kEsPollSleep);
             if (++spins > (1u << 22)) {
                 if (lane == 0) atomicOr(&st->err, kErrInternal);
                 return out_cap;  // (no room for any waveform there: nothing is stored)
@@ -334,8 +263,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     // A waveform that outgrew the ring (incompressible data, long waveforms) is coded a second time, tile by tile through the
     // (empty) ring's first words, straight to its place: a second read of its samples.
     auto stream_out = [&](uint64_t ex) {
-        ES_COUNT(4, 1);
-        ES_TRACE(gA, 3);
         const WaveRef r = locate(G, gA);
         const int16_t *x = in + r.sample_off;
         const uint32_t wlen = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.len);
@@ -399,9 +326,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     uint32_t start = 0;  // first ring word of the waveform being coded (a multiple of four)
     uint32_t Tprev = 0;
     for (uint32_t cyc = 0;; ++cyc) {
-#ifdef DRX_ENC_STAMPS
-        const uint64_t es_tr = __builtin_amdgcn_s_memrealtime();
-#endif
         uint32_t arr = 0;
         if (lane == 0) arr = __hip_atomic_fetch_add((lds_u32 *)&s_arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         arr = (uint32_t)__builtin_amdgcn_readfirstlane((int)arr);
@@ -409,7 +333,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             if (lane == 0) s_ticket[cyc & 3u] = atomicAdd(ctrl + 32, 1u);
         }
         __syncthreads();
-        ES_COUNT(6, __builtin_amdgcn_s_memrealtime() - es_tr);
         const uint32_t T = s_ticket[cyc & 3u];
         // the ticket before: its total to the scanner, and where in it this wavefront's waveform lies
         if (cyc) {
@@ -421,10 +344,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                 before += i < wv ? m : 0ull;
             }
             offA = before;
-            if (threadIdx.x == 0) {
-                es_store(size + Tprev, kEsFlag | sum);
-                ES_TRACE((uint64_t)Tprev * WV, 0);
-            }
+            if (threadIdx.x == 0) es_store(size + Tprev, kEsFlag | sum);
         }
         // a waveform that did not fit is streamed before the next one takes the ring
         if (pend && !fitsA) stream_out(wait_place());
@@ -436,7 +356,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             if (pend) copy_out(wait_place());  // (offA is this waveform's only until the next rendezvous)
             continue;
         }
-        ES_TRACE(g, 1);
 
         WaveRef r = locate(G, g);
         const int16_t *x = in + r.sample_off;
@@ -482,7 +401,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                 const bool seen = place_in_lds(ex);
                 const bool must = fits && ((P + tile_bits + 31u) >> 5) >= (uint64_t)limit;
                 if (seen || must) {
-                    if (seen) ES_COUNT(2, 1);
                     // A wavefront that has to wait for its place is AHEAD of the stream's frontier; one that finds the place of
                     // its last waveform almost as soon as it looks is what the others are waiting for.  Issue priority on
                     // the SIMD follows (4.96-5.02 -> 4.79-4.83 ms on the headline; more levels or other thresholds: the same).
@@ -523,7 +441,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         bool polling = false;
         auto between = [&]() {
             if (!pend) return;
-            if (kAblate && (G.dbg & kAbNoLookback)) { place_to_lds(wait_place()); return; }
             if (polling) {
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pollv >> 32));
                 polling = false;
@@ -581,8 +498,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             wave_words[g] = n;
             s_mine[cyc & 1u][wv] = 1ull + n + (r.idx == 0 ? 1ull : 0ull);
         }
-        ES_COUNT(3, 1);
-        ES_TRACE(g, 2);
         if (pend) copy_out(wait_place());  // (waveforms too short for the look-ups between tile groups)
         pend = true;
         fitsA = fits;
@@ -596,11 +511,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         }
     }
     if (pend) copy_out(wait_place());
-#ifdef DRX_ENC_STAMPS
-    ES_COUNT(5, __builtin_amdgcn_s_memrealtime() - es_t0);
-    __syncthreads();
-    if (threadIdx.x < 8) atomicAdd(prof + threadIdx.x, (unsigned long long)s_prof[threadIdx.x]);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -854,7 +764,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         return true;
     };
     auto wait_place = [&]() -> EsPlace2 {
-        if (kAblate && (G.dbg & kAbNoLookback)) return EsPlace2{(uint64_t)TA * WV * 2048ull, 0ull};  // ablation: no waiting at all (positions are wrong)
         uint32_t spins = 0;
         for (;;) {
             EsPlace2 pl;
@@ -865,7 +774,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
                 place_to_lds(pl);
                 return pl;
             }
-            __builtin_amdgcn_s_sleep(DRX_ES_POLL_SLEEP);
+            __builtin_amdgcn_s_sleep(kEsPollSleep);
             if (++spins > (1u << 22)) {
                 if (lane == 0) atomicOr(&st->err, kErrInternal);
                 pl.whdr = out_cap;  // (no room there: nothing is stored)
@@ -1079,7 +988,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         bool polling = false;
         auto between = [&]() {
             if (!pend) return;
-            if (kAblate && (G.dbg & kAbNoLookback)) { place_to_lds(wait_place()); return; }
             if (polling) {
                 polling = false;
                 EsPlace2 pl;
@@ -1160,8 +1068,8 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
 // ---------------------------------------------------------------------------
 // launcher
 // ---------------------------------------------------------------------------
-// d_scan: uint64[2 * tickets + kEsCtrlWords + 16] (tickets <= total_waves): total[tickets] | place[tickets] | control, zeroed
-// here on the stream before every launch | the diagnostic build's counters.
+// d_scan: uint64[2 * tickets + kEsCtrlWords] (tickets <= total_waves): total[tickets] | place[tickets] | control, zeroed here
+// on the stream before every launch.
 hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                 uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
                                 DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
@@ -1175,17 +1083,6 @@ hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_
     mark(ev, 2, s);
     uint64_t *size = d_scan, *place = d_scan + tickets;
     uint32_t *ctrl = reinterpret_cast<uint32_t *>(d_scan + 2 * tickets);
-    unsigned long long *prof = reinterpret_cast<unsigned long long *>(d_scan + 2 * tickets + kEsCtrlWords);
-#ifdef DRX_ENC_STAMPS
-    static uint64_t *d_trace = nullptr;
-    const char *trace_path = getenv("DRX_ES_TRACE");
-    if (trace_path && !d_trace) {
-        (void)hipMalloc((void **)&d_trace, 5 * W * sizeof(uint64_t));
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_es_trace), &d_trace, sizeof d_trace);
-    }
-    if (d_trace) (void)hipMemsetAsync(d_trace, 0, 5 * W * sizeof(uint64_t), s);
-    (void)hipMemsetAsync(prof, 0, 12 * sizeof(unsigned long long), s);
-#endif
     // persistent: 16 wavefronts per CU, one workgroup of them the scanner's; never more than the batch can feed
     // (DRX_DBG_STREAM_THREE_WGS: three workgroups -- a scanner and two coders -- so that a small test batch takes every wavefront
     // through many waveforms, i.e. around its ring)
@@ -1193,32 +1090,11 @@ hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_
     const unsigned grid = (G.dbg & DRX_DBG_STREAM_THREE_WGS) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
     if (G.n_taps)
         k_encode_stream<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words, size,
-                                                                              place, ctrl, d_status, prof);
+                                                                              place, ctrl, d_status);
     else
         k_encode_stream<false, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words, size,
-                                                                               place, ctrl, d_status, prof);
+                                                                               place, ctrl, d_status);
     mark(ev, 3, s);
-#ifdef DRX_ENC_STAMPS
-    {
-        unsigned long long h[12];
-        (void)hipStreamSynchronize(s);
-        if (d_trace && trace_path) {
-            uint64_t *ht = (uint64_t *)malloc(5 * W * sizeof(uint64_t));
-            (void)hipMemcpy(ht, d_trace, 5 * W * sizeof(uint64_t), hipMemcpyDeviceToHost);
-            FILE *f = fopen(trace_path, "wb");
-            if (f) { fwrite(ht, sizeof(uint64_t), 5 * W, f); fclose(f); }
-            free(ht);
-        }
-        (void)hipMemcpy(h, prof, sizeof h, hipMemcpyDeviceToHost);
-        const double wf = h[3] ? (double)h[3] : 1.0;
-        fprintf(stderr, "enc stream stamps: %llu waveforms: %llu placed between tile groups without waiting, %llu waits (%.2f us each), %llu streamed; "
-                "per waveform: %.2f us in all, %.2f us waiting for the place, %.2f us at the rendezvous\n",
-                h[3], h[2], h[1], h[1] ? h[0] / (double)h[1] / 100.0 : 0.0, h[4], h[5] / wf / 100.0, h[0] / wf / 100.0, h[6] / wf / 100.0);
-        fprintf(stderr, "enc stream scanner: %llu rounds in %.1f us (%.2f us each), %llu found nothing new, %llu a full window; "
-                "%.1f failed polls per wait of a coder\n",
-                h[8], h[11] / 100.0, h[8] ? h[11] / 100.0 / h[8] : 0.0, h[9], h[10], h[1] ? h[7] / (double)h[1] : 0.0);
-    }
-#endif
     return hipGetLastError();
 }
 

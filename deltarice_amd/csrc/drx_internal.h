@@ -46,7 +46,7 @@ struct Geom {
     // pinned host word (device-visible) that every encoder writes the batch's encoded word count to beside DevStatus: the host
     // reads it -- without waiting for anything -- when it chooses the NEXT encode's kernel (drx_api.hip, stream_encoder_suits())
     uint64_t *host_words;
-    uint32_t dbg;  // "debug_flags" context option (DRX_DBG_* of include/deltarice_hip.h; -DDRX_ABLATION builds: drx_device.h); 0 in normal use
+    uint32_t dbg;  // "debug_flags" context option (DRX_DBG_* of include/deltarice_hip.h); 0 in normal use
     // ragged batches, walk inside the decode launch: chunk indices, short-waveform chunks first
     // (walk_short[n_short], then walk_long[n_long]), and the largest ceil(n_waves / 64) of any chunk (decode_plan_ragged())
     const uint32_t *walk_short, *walk_long;
@@ -123,11 +123,8 @@ hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uin
                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 
 // the persistent form of the single pass (drx_encode_stream.hip): a ring of kEsRingWords LDS words per wavefront, a scanner
-// wavefront.  d_scan: uint64[2 * tickets + 48], tickets <= total_waves (32 words of control, 16 of the stamp build's counters)
-#ifndef DRX_ES_RING
-#define DRX_ES_RING 2496
-#endif
-constexpr uint32_t kEsRingWords = DRX_ES_RING;
+// wavefront.  d_scan: uint64[2 * tickets + 32], tickets <= total_waves (32 words of control)
+constexpr uint32_t kEsRingWords = 2496;
 constexpr uint64_t kEsMinUnits = 8192;  // waveforms (segments) from which the persistent forms suit a batch: its 4096 wavefronts a few each
 hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                                 uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
@@ -310,13 +307,7 @@ hipError_t launch_encode_pieces(const Geom &G, const int16_t *d_in, uint64_t in_
                                 DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 // in-place inverse of a general prediction filter over decoded residuals (drx_iir.hip): tiles of kIirThreads lanes x kIirRun
 // samples, decoupled look-back over kIirWin tiles per poll, tables of kIirTabWords uint32 per filter
-#ifndef DRX_IIR_THREADS
-#define DRX_IIR_THREADS 512
-#endif
-#ifndef DRX_IIR_RUN
-#define DRX_IIR_RUN 64
-#endif
-constexpr uint32_t kIirRun = DRX_IIR_RUN, kIirThreads = DRX_IIR_THREADS, kIirTile = kIirRun * kIirThreads, kIirWin = 128;
+constexpr uint32_t kIirRun = 64, kIirThreads = 512, kIirTile = kIirRun * kIirThreads, kIirWin = 128;
 constexpr uint32_t kIirTabWords = (7 + 64 + (kIirWin + 1)) * 9 + 4;
 void iir_tables(const uint32_t fast_nt[3], uint32_t t0neg, uint32_t *tab);
 uint64_t iir_tiles(const Geom &G, const ChunkDesc *host_chunks, uint64_t *chunk_tile_base);  // (chunk_tile_base: n_chunks + 1, ragged only)
@@ -330,11 +321,8 @@ uint32_t bw_walk_blocks_max(const Geom &G);
 void decode_plan_ragged(Geom &G, const ChunkDesc *host_chunks, std::vector<uint32_t> *walk_lists, std::vector<uint2> *order);
 // limits of the parallel header walks (see k_walk_parallel / k_bw_blocks)
 constexpr uint32_t kPwMaxWaves = 3584;   // waveforms per chunk the chunk-wide walk takes (leaves room for impostors)
-#ifndef DRX_PW_MAX_CHUNKS
-#define DRX_PW_MAX_CHUNKS 224
-#endif
-constexpr uint64_t kPwMaxChunks = DRX_PW_MAX_CHUNKS;  // the walks that READ the chunks (block-parallel; the chunk-wide walk's scan form,
-                                                      // DRX_DBG_WALK_BY_SCAN): more chunks hide the serial walk behind the decoding
+constexpr uint64_t kPwMaxChunks = 224;  // the walks that READ the chunks (block-parallel; the chunk-wide walk's scan form,
+                                        // DRX_DBG_WALK_BY_SCAN): more chunks hide the serial walk behind the decoding
 // the chunk-wide walk by chains (k_walk_sparse) costs ~60 us per 512 chunks whatever their size: every uniform batch of
 // long waveforms takes it, the headline's 500 chunks included (4.74 + 0.08 ms against 5.33 with the walk inside the launch)
 constexpr uint64_t kSwMaxChunks = 1u << 20;

@@ -343,8 +343,6 @@ drx_status drx_h5_write_filtered(drx_ctx *ctx, const char *file, const char *nam
     if (enter_device(ctx, &prev_dev) != 0) return DRX_ERR_DEVICE;
 
     double t0 = now();
-    const int timing = getenv("DRX_H5_TIMING") != NULL;
-#define STAMP(what) do { if (timing) fprintf(stderr, "  h5 write %-28s %8.3f ms\n", what, (now() - t0) * 1e3); } while (0)
     uint64_t words = 0, words_e = 0, cap = 0, cap_e = 0;
     hipEvent_t ev[kMaxSlabs];
     int n_ev = 0;
@@ -353,12 +351,9 @@ drx_status drx_h5_write_filtered(drx_ctx *ctx, const char *file, const char *nam
     if (n_full) {
         if ((rc = drx_plan_create_uniform(ctx, n_full, chunk_samples, wave_len, k, &plan)) != DRX_OK) goto out;
         if (n_taps && (rc = drx_plan_set_filter(plan, n_taps, taps)) != DRX_OK) goto out;
-        STAMP("plan created");
         cap = drx_plan_max_encoded_words(plan);
         if (hipMalloc(&d_words, cap * 4) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
-        STAMP("output buffer allocated");
         if ((rc = drx_encode(plan, d_in, (uint32_t *)d_words, cap, d_off)) != DRX_OK) goto out;
-        STAMP("encode launched");
     }
     if (edge_rows) {
         if ((rc = drx_plan_create_uniform(ctx, 1, chunk_samples, wave_len, k, &plan_edge)) != DRX_OK) goto out;
@@ -382,10 +377,8 @@ drx_status drx_h5_write_filtered(drx_ctx *ctx, const char *file, const char *nam
     if (H5Pset_chunk(pl, 2, chunk) < 0 || H5Pset_filter(pl, FILTER_ID, H5Z_FLAG_MANDATORY, n_taps ? 3 + n_taps : 2, cd) < 0) goto out;
     if ((d = H5Dcreate2(f, name, H5T_NATIVE_SHORT, sp, H5P_DEFAULT, pl, H5P_DEFAULT)) < 0) goto out;
     s.t_file = now() - t1;
-    STAMP("file and dataset created");
     t1 = now();
     if (n_full && (rc = drx_plan_finish(plan, &words)) != DRX_OK) goto out;
-    STAMP("encode finished");
     if (edge_rows && (rc = drx_plan_finish(plan_edge, &words_e)) != DRX_OK) goto out;
     s.t_gpu = (t1 - t0 - s.t_file) + (now() - t1);  /* launches + what was left of the kernels behind the file's creation */
     s.stored_bytes = (words + words_e) * 4;
@@ -414,7 +407,6 @@ drx_status drx_h5_write_filtered(drx_ctx *ctx, const char *file, const char *nam
         ++n_ev;
         if (hipEventRecord(ev[n_ev - 1], cs) != hipSuccess) goto out;
     }
-    STAMP("copies issued");
     double t_wait = now() - t0, t_h5 = 0;
     for (int sl = 0; sl < n_slabs; ++sl) {
         t1 = now();

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the decode variants at full bench size on one box: tools/ab_impls.sh [impl ...]
-for i in "${@:-1 2 3 4 5 6}"; do
+for i in "${@:-0 7 8}"; do
   for j in $i; do
     timeout -k 5 200 python bench.py --full --cpu-seconds 0 --steps 4 --warmup 1 --decode-impl $j > /tmp/ab_$j.json || exit 1
     python - $j <<'PY'

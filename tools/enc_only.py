@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Encoder-only timing of the bench workload under kernel ablation flags (results invalid with flags):
+"""Encoder-only timing of the bench workload under each debug_flags value given (DRX_ENCODE_IMPL: the encode_impl option):
 tools/enc_only.py [flags ...]"""
 import os
 import sys

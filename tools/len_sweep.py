@@ -17,6 +17,8 @@ def main():
     ctx.set_option("profile", 1)
     if os.environ.get("DRX_DEBUG_FLAGS"):
         ctx.set_option("debug_flags", int(os.environ["DRX_DEBUG_FLAGS"]))
+    if os.environ.get("DRX_ENCODE_IMPL"):
+        ctx.set_option("encode_impl", int(os.environ["DRX_ENCODE_IMPL"]))
     lens = [int(a) for a in sys.argv[1:]] or [64, 512, 2048, 3500, 7000, 16384, 65536]
     print(f"{'L':>7s} {'chunks':>6s} {'enc ms':>8s} {'enc GB/s':>9s} {'walk ms':>8s} {'dec ms':>8s} {'dec GB/s':>9s}")
     for L in lens:
@@ -33,11 +35,8 @@ def main():
         te, tw, td, tt = [], [], [], []
         for _ in range(3):
             plan.encode_async(x, words, off)
-            if os.environ.get("DRX_SWEEP_ENCODE_ONLY"):  # (ablation builds whose streams do not decode)
-                try:
-                    plan.finish()
-                except dr.DeltaRiceError:
-                    pass
+            if os.environ.get("DRX_SWEEP_ENCODE_ONLY"):
+                plan.finish()
                 te.append(plan.last_timings()[3]); tw.append(0.0); td.append(0.0); tt.append(1.0)
                 continue
             nw = plan.finish()

@@ -86,7 +86,7 @@ def main():
     ap.add_argument("--ramp", action="store_true", help="a slope-1 sawtooth instead of noise (a DAQ's test pattern: codes of one length, "
                     "a speculative parse never falls into step)")
     ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--encode-only", action="store_true", help="time the encoder alone (ablation builds whose streams do not decode)")
+    ap.add_argument("--encode-only", action="store_true", help="time the encoder alone")
     ap.add_argument("--debug-flags", type=int, default=0)
     ap.add_argument("--sideband", action="store_true", help="decode with the encoder's n_i table as a side-band (drx_decode_with_wave_words)")
     ap.add_argument("--white", action="store_true", help="_fir4 workloads: white noise as it is (the filter then hurts)")
