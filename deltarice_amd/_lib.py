@@ -17,6 +17,7 @@ DRX_MAX_TAPS = 64
 
 # DRX_PATH_*, DRX_ENC_* and DRX_DBG_* of include/deltarice_hip.h (tests/test_abi_surface.py holds them equal)
 PATH_LANES_FUSED, PATH_LANES, PATH_BLOCKS, PATH_LONG, PATH_SIMPLE, PATH_IIR, PATH_IIR_FUSED = 1, 2, 4, 8, 16, 32, 64
+PATH_SELECT = 128
 ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
 DBG_NO_LONG_PATHS = 256
 DBG_LONG_NOT_BLOCKS = 512
@@ -76,6 +77,8 @@ SIGNATURES = {
     "drx_encode": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "drx_decode": (C.c_int, [_vp, _vp, _u64, _vp, _vp]),
     "drx_decode_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "drx_decode_select": (C.c_int, [_vp, _vp, _u64, _vp, C.POINTER(_u64), _u64, _vp, _u64]),
+    "drx_decode_select_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _vp, _u64]),
     "drx_estimate_words": (C.c_int, [_vp, _vp, C.POINTER(_u64)]),
     "drx_plan_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "drx_plan_finish": (C.c_int, [_vp, C.POINTER(_u64)]),

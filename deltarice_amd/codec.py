@@ -36,6 +36,42 @@ def _is_delta(o: DrxOpts) -> bool:
     return o.n_taps == 2 and o.taps[0] == 1 and o.taps[1] == -1
 
 
+def wave_lengths(chunk_samples: Sequence[int], wave_lens: Sequence[int], wave_idx) -> np.ndarray:
+    """Samples of each waveform of ``wave_idx`` (global waveform indices) in a batch whose chunk c holds
+    ``chunk_samples[c]`` samples in waveforms of ``wave_lens[c]`` (0 or less: the whole chunk): WaveformLength, or what is
+    left for the last waveform of a chunk (src/deltaRice.c:399-403 of the reference).  Host arithmetic; no GPU."""
+    N = np.asarray(chunk_samples, dtype=np.int64).reshape(-1)
+    L = np.asarray(wave_lens, dtype=np.int64).reshape(-1)
+    if N.size == 0 or N.size != L.size or (N <= 0).any():
+        raise DeltaRiceError(1, "chunk_samples / wave_lens mismatch")
+    L = np.where(L <= 0, N, L)
+    W = (N + L - 1) // L
+    base = np.concatenate(([0], np.cumsum(W)))
+    idx = _as_index_array(wave_idx)
+    if idx.size and int(idx.max()) >= int(base[-1]):
+        raise DeltaRiceError(1, f"waveform index {int(idx.max())} out of range (the batch has {int(base[-1])})")
+    g = idx.astype(np.int64)
+    c = np.searchsorted(base, g, side="right") - 1
+    i = g - base[c]
+    return np.where(i + 1 == W[c], N[c] - i * L[c], L[c]).astype(np.int64)
+
+
+def _as_index_array(wave_idx) -> np.ndarray:
+    """Any integer sequence, numpy array or CPU tensor -> contiguous uint64 [n]."""
+    if isinstance(wave_idx, torch.Tensor):
+        if wave_idx.device.type != "cpu":
+            raise DeltaRiceError(1, "wave_idx: a selection lives on the host (a CPU tensor, an array or a sequence)")
+        wave_idx = wave_idx.numpy()
+    a = np.asarray(wave_idx).reshape(-1)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint64)
+    if a.dtype.kind not in "iu":
+        raise DeltaRiceError(1, f"wave_idx: integers wanted, got {a.dtype}")
+    if a.dtype.kind == "i" and int(a.min()) < 0:
+        raise DeltaRiceError(1, f"wave_idx: negative index {int(a.min())}")
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
 @dataclass
 class EncodedBatch:
     """Encoded chunks back to back in HBM + the table saying where each one starts."""
@@ -89,7 +125,7 @@ class Context:
         h = C.c_void_p()
         L = 0 if o.wave_len < 0 else int(o.wave_len)
         self._check(self.lib.drx_plan_create_uniform(self._h, n_chunks, chunk_samples, L, o.rice_k, C.byref(h)))
-        plan = Plan(self, h)
+        plan = Plan(self, h, np.full(n_chunks, chunk_samples, dtype=np.int64), np.full(n_chunks, L, dtype=np.int64))
         if not _is_delta(o):  # general prediction filter: GPU FIR/IIR kernels (correct, not tuned)
             self._check(self.lib.drx_plan_set_filter(h, o.n_taps, o.taps))
         return plan
@@ -106,7 +142,7 @@ class Context:
         wl = (C.c_uint32 * n)(*[0 if int(v) <= 0 else int(v) for v in wave_lens])
         h = C.c_void_p()
         self._check(self.lib.drx_plan_create(self._h, n, cs, wl, o.rice_k, C.byref(h)))
-        plan = Plan(self, h)
+        plan = Plan(self, h, list(cs), list(wl))
         if taps is not None:
             t = (C.c_int32 * len(taps))(*[int(v) for v in taps])
             self._check(self.lib.drx_plan_set_filter(h, len(taps), t))
@@ -130,8 +166,11 @@ class Context:
 class Plan:
     """Geometry of one batch (chunks x waveforms), device resident; reusable."""
 
-    def __init__(self, ctx: Context, handle):
+    def __init__(self, ctx: Context, handle, chunk_samples: Sequence[int] = (), wave_lens: Sequence[int] = ()):
         self.ctx, self._h = ctx, handle
+        # the batch's geometry as the plan was made from it (wave_lengths(), decode_select's row stride)
+        self._chunk_samples = np.asarray(chunk_samples, dtype=np.int64)
+        self._wave_lens = np.asarray(wave_lens, dtype=np.int64)
         lib = ctx.lib
         self.n_chunks = int(lib.drx_plan_n_chunks(handle))
         self.total_samples = int(lib.drx_plan_total_samples(handle))
@@ -212,6 +251,61 @@ class Plan:
         cur = torch.cuda.current_stream(self.ctx.device)
         self.ctx.stream.wait_stream(cur)
         y = self.decode_async(enc.words, enc.chunk_word_off, out, in_words=enc.total_words)
+        self.finish()
+        return y
+
+    def wave_lengths(self, wave_idx) -> np.ndarray:
+        """len_i of the waveforms ``wave_idx`` names: WaveformLength, or less for the last waveform of a chunk."""
+        return wave_lengths(self._chunk_samples, self._wave_lens, wave_idx)
+
+    def longest_wave(self) -> int:
+        """The longest waveform of the plan (the row stride decode_select allocates)."""
+        L = np.where(self._wave_lens <= 0, self._chunk_samples, self._wave_lens)
+        return int(np.minimum(L, self._chunk_samples).max())
+
+    def decode_select_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, wave_idx,
+                            out: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
+                            wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Decodes the waveforms ``wave_idx`` names (global indices; any order, duplicates allowed; any integer sequence,
+        numpy array or CPU tensor) and no others: row i of the result holds waveform wave_idx[i].  Only the chunks those
+        waveforms lie in are read and validated.  out: int16 [n_sel, stride] with contiguous rows, of which exactly len_i
+        samples per row are written; None: a new tensor whose stride is the plan's longest waveform, zero behind a shorter
+        one.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).
+        Launch only; finish() raises on device-side errors."""
+        idx = _as_index_array(wave_idx)
+        n_sel = int(idx.size)
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        if out is None:
+            out = torch.zeros((n_sel, self.longest_wave()), dtype=torch.int16, device=self.ctx.device)
+            self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))  # (the zero fill)
+        if (out.dim() != 2 or out.device != self.ctx.device or out.dtype != torch.int16 or out.shape[0] < n_sel or
+                (out.shape[1] > 1 and out.stride(1) != 1) or (out.shape[0] > 1 and out.stride(0) < out.shape[1])):
+            raise DeltaRiceError(1, f"out: need an int16 [>= {n_sel}, stride] tensor with contiguous rows on {self.ctx.device}")
+        stride = int(out.stride(0)) if out.shape[0] > 1 else int(out.shape[1])
+        # (rows of the plan's longest waveform hold any selection; shorter ones are checked against this one)
+        if n_sel and out.shape[1] < self.longest_wave() and int(self.wave_lengths(idx).max()) > out.shape[1]:
+            raise DeltaRiceError(1, f"out: rows of {out.shape[1]} samples are shorter than the longest selected waveform")
+        n = words.numel() if in_words is None else int(in_words)
+        ip = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+        lib = self.ctx.lib
+        if wave_words is None:
+            st = lib.drx_decode_select(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), ip, n_sel, out.data_ptr(), stride)
+        else:
+            st = lib.drx_decode_select_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
+                                                       wave_words.data_ptr(), ip, n_sel, out.data_ptr(), stride)
+        self.ctx._check(st)
+        return out
+
+    def decode_select(self, enc: EncodedBatch, wave_idx, out: Optional[torch.Tensor] = None,
+                      wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """decode_select_async on an EncodedBatch; waits, and raises like decode()."""
+        cur = torch.cuda.current_stream(self.ctx.device)
+        self.ctx.stream.wait_stream(cur)
+        y = self.decode_select_async(enc.words, enc.chunk_word_off, wave_idx, out, in_words=enc.total_words,
+                                     wave_words=wave_words)
         self.finish()
         return y
 

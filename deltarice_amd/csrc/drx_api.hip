@@ -126,6 +126,13 @@ struct drx_plan {
     uint32_t last_path = 0;  // DRX_PATH_* of the last decode
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool ev_valid = false;
+    // drx_decode_select: the host's chunk table (ragged plans; host memory), and the selection's scratch -- allocated by the
+    // first select call, grown when a later one needs more (sel_scratch())
+    std::vector<ChunkDesc> host_chunks;
+    void *h_sel = nullptr, *d_sel = nullptr;  // uint64 sel[n_sel] | uint32 chunk lists[touched]: pinned staging and its device copy
+    size_t sel_cap = 0;                       // ... bytes of each
+    uint32_t *d_sel_fail = nullptr;           // uint32[n_chunks]: chunks the chunk-wide walk handed to the scalar walker
+    hipEvent_t sel_copied = nullptr;          // the staging buffer has crossed to the device (the next call may fill it again)
 };
 
 static drx_status fail(drx_ctx *ctx, drx_status st, const char *fmt, ...) {
@@ -322,6 +329,7 @@ static void plan_free(drx_plan *p) {
     if (!p) return;
     DeviceGuard guard(p->ctx->device);
     for (hipEvent_t e : p->ev) if (e) (void)hipEventDestroy(e);
+    if (p->sel_copied) (void)hipEventDestroy(p->sel_copied);
     delete p;  // (and its buffers)
 }
 
@@ -353,6 +361,7 @@ static drx_status plan_alloc(drx_plan *p) {
     if (stream_segs_admits(G) && G.u_wave_len >= kEsSegsFromLen) words = std::max(words, segs_scan_words(G, kEsSegMinLen));
     DRX_HIP(ctx, p->mem.alloc(&p->d_scan, p->scan_bytes = words * sizeof(uint64_t)));
     DRX_HIP(ctx, p->mem.alloc(&p->d_status, sizeof(DevStatus)));
+    DRX_HIP(ctx, hipMemset(p->d_status, 0, sizeof(DevStatus)));  // (drx_plan_finish before any launch, or behind an empty selection: no error)
     DRX_HIP(ctx, p->mem.alloc(&p->h_status, sizeof(DevStatus), true));
     memset(p->h_status, 0, sizeof(DevStatus));
     DRX_HIP(ctx, p->mem.alloc(&G.host_words, sizeof(uint64_t), true));  // (pinned host memory is device-visible at the same address)
@@ -466,6 +475,7 @@ static drx_status plan_create(drx_ctx *ctx, uint64_t n_chunks, const uint32_t *c
     }
     drx_status st = plan_alloc(p);
     if (st == DRX_OK && !uniform) st = plan_ragged(p, desc);
+    if (st == DRX_OK && !uniform) p->host_chunks = std::move(desc);
     if (st == DRX_OK) st = plan_alloc_scratch(p);
     if (st != DRX_OK) { plan_free(p); return st; }
     *out = p;
@@ -709,6 +719,139 @@ drx_status drx_decode_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_
     if (!d_wave_words) return DRX_ERR_ARG;
     if (p && d_wave_words == p->d_wave_words) return fail(p->ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
     return decode_launch(p, d_in, in_words, d_chunk_word_off, d_out, false, d_wave_words);
+}
+
+// ---------------------------------------------------------------------------
+// selected waveforms (drx_select.hip)
+// ---------------------------------------------------------------------------
+// The selection's scratch: pinned staging and device copy of `bytes` each, the walk's flags.  A call that needs more
+// replaces the pair (the larger ones first: should that fail, the plan keeps what it had).
+static drx_status sel_scratch(drx_plan *p, size_t bytes) {
+    drx_ctx *ctx = p->ctx;
+    if (!p->sel_copied) DRX_HIP(ctx, hipEventCreateWithFlags(&p->sel_copied, hipEventDisableTiming));
+    if (!p->d_sel_fail) DRX_HIP(ctx, p->mem.alloc(&p->d_sel_fail, p->G.n_chunks * sizeof(uint32_t)));
+    if (p->sel_cap >= bytes) return DRX_OK;
+    const size_t want = bytes + bytes / 4 + 4096;
+    void *h = nullptr, *d = nullptr;
+    DRX_HIP(ctx, p->mem.alloc(&h, want, true));
+    const hipError_t e = p->mem.alloc(&d, want);
+    if (e != hipSuccess) {
+        p->mem.release(h);
+        return fail(ctx, DRX_ERR_NOMEM, "selection scratch of %zu bytes: %s", want, hipGetErrorString(e));
+    }
+    DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier select call may still read the old pair)
+    p->mem.release(p->h_sel);
+    p->mem.release(p->d_sel);
+    p->h_sel = h;
+    p->d_sel = d;
+    p->sel_cap = want;
+    return DRX_OK;
+}
+
+static drx_status decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                const uint32_t *d_sideband, bool sideband, const uint64_t *wave_idx, uint64_t n_sel,
+                                int16_t *d_out, uint64_t stride) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (n_sel == 0) return DRX_OK;
+    if (!d_in || !d_chunk_word_off || !wave_idx || !d_out || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "decode_select: null pointer");
+    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    if (n_sel >= (1ull << 32)) return fail(ctx, DRX_ERR_ARG, "decode_select: %llu entries (at most 2^32 - 1)", (unsigned long long)n_sel);
+    const Geom &G = p->G;
+    // the chunk and the length of every selected waveform: arithmetic (uniform) or a bisection of the host's chunk table
+    auto chunk_of = [&](uint64_t g, uint32_t *len) -> uint64_t {
+        uint64_t c, idx;
+        uint32_t W, L, N;
+        if (G.uniform) {
+            c = g / G.u_n_waves; idx = g - c * G.u_n_waves;
+            W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples;
+        } else {
+            uint64_t lo = 0, hi = G.n_chunks;  // invariant: wave_base[lo] <= g < wave_base[hi]
+            while (hi - lo > 1) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (p->host_chunks[mid].wave_base <= g) lo = mid; else hi = mid;
+            }
+            const ChunkDesc &d = p->host_chunks[c = lo];
+            idx = g - d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples;
+        }
+        *len = idx + 1 == W ? N - (uint32_t)idx * L : L;
+        return c;
+    };
+    // the sorted set of chunks the selection touches: a flag per chunk for large selections, sort + unique for small ones
+    std::vector<uint32_t> touched;
+    std::vector<uint8_t> flag;
+    const bool by_flag = n_sel > G.n_chunks / 8u;
+    if (by_flag) flag.assign(G.n_chunks, 0);
+    else touched.reserve(n_sel);
+    uint32_t longest = 0;
+    for (uint64_t i = 0; i < n_sel; ++i) {
+        if (wave_idx[i] >= G.total_waves)
+            return fail(ctx, DRX_ERR_ARG, "decode_select: entry %llu is waveform %llu of %llu", (unsigned long long)i,
+                        (unsigned long long)wave_idx[i], (unsigned long long)G.total_waves);
+        uint32_t len;
+        const uint64_t c = chunk_of(wave_idx[i], &len);
+        longest = std::max(longest, len);
+        if (by_flag) flag[c] = 1;
+        else touched.push_back((uint32_t)c);
+    }
+    if (stride < longest) return fail(ctx, DRX_ERR_ARG, "decode_select: row stride %llu below the longest selected waveform (%u)", (unsigned long long)stride, longest);
+    if (by_flag) {
+        for (uint64_t c = 0; c < G.n_chunks; ++c) if (flag[c]) touched.push_back((uint32_t)c);
+    } else {
+        std::sort(touched.begin(), touched.end());
+        touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
+    }
+    // ... as the walk takes them: three lists, each sorted (select_walk_class()); the side-band takes them as one
+    uint32_t n_class[3] = {0, 0, 0};
+    std::vector<uint32_t> lists(touched.size());
+    if (sideband) {
+        lists = touched;
+    } else {
+        auto cls = [&](uint32_t c) { return G.uniform ? select_walk_class(G.u_n_waves, G.u_wave_len)
+                                                      : select_walk_class(p->host_chunks[c].n_waves, p->host_chunks[c].wave_len); };
+        for (uint32_t c : touched) ++n_class[cls(c)];
+        uint32_t at[3] = {0, n_class[0], n_class[0] + n_class[1]};
+        for (uint32_t c : touched) lists[at[cls(c)]++] = c;
+    }
+    DRX_ON_DEVICE(ctx);
+    const size_t sel_bytes = n_sel * sizeof(uint64_t), bytes = sel_bytes + lists.size() * sizeof(uint32_t);
+    if (const drx_status st = sel_scratch(p, bytes)) return st;
+    DRX_HIP(ctx, hipEventSynchronize(p->sel_copied));  // (the last call's copy out of the staging buffer)
+    memcpy(p->h_sel, wave_idx, sel_bytes);
+    memcpy((char *)p->h_sel + sel_bytes, lists.data(), lists.size() * sizeof(uint32_t));
+    DRX_HIP(ctx, hipMemcpyAsync(p->d_sel, p->h_sel, bytes, hipMemcpyHostToDevice, ctx->stream));
+    DRX_HIP(ctx, hipEventRecord(p->sel_copied, ctx->stream));
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
+    const uint64_t *d_sel = (const uint64_t *)p->d_sel;
+    const uint32_t *d_lists = (const uint32_t *)((const char *)p->d_sel + sel_bytes);
+    mark(ev, 0, ctx->stream);
+    if (sideband)
+        DRX_HIP(ctx, launch_sideband_tables(G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words, p->d_status,
+                                            ctx->stream, d_lists, (uint32_t)lists.size()));
+    else
+        DRX_HIP(ctx, launch_select_walk(G, d_in, in_words, d_chunk_word_off, d_lists, n_class[0], n_class[1], n_class[2], p->d_sel_fail,
+                                        p->d_wave_off, p->d_wave_words, p->d_status, ctx->stream));
+    mark(ev, 1, ctx->stream);
+    DRX_HIP(ctx, launch_decode_select(G, d_in, p->d_wave_off, p->d_wave_words, d_sel, n_sel, p->d_status, d_out, stride, ctx->stream));
+    mark(ev, 2, ctx->stream);
+    mark(ev, 3, ctx->stream);
+    p->last_path = DRX_PATH_SELECT;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+drx_status drx_decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             const uint64_t *wave_idx, uint64_t n_sel, int16_t *d_out, uint64_t out_stride_samples) {
+    return decode_select(p, d_in, in_words, d_chunk_word_off, nullptr, false, wave_idx, n_sel, d_out, out_stride_samples);
+}
+
+drx_status drx_decode_select_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                             const uint32_t *d_wave_words, const uint64_t *wave_idx, uint64_t n_sel,
+                                             int16_t *d_out, uint64_t out_stride_samples) {
+    return decode_select(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, wave_idx, n_sel, d_out, out_stride_samples);
 }
 
 // Header chain of ONE encoded chunk in host memory (src/deltaRice.c:320-325), with the validation the device

@@ -29,13 +29,15 @@ namespace drx {
 // "reuse its offset table as a side-band"), so no header chain is walked.  Per chunk: header positions by a prefix sum over
 // 1 + n_i, each checked against the stream itself (the word at that position must BE n_i, n_i within the bounds of its
 // waveform, the chain must end exactly at the chunk's end, the chunk header must be the sample count) -- a table that does
-// not belong to the stream is DRX_ERR_CORRUPT, never a wild read.
+// not belong to the stream is DRX_ERR_CORRUPT, never a wild read.  list (optional): the chunks to do, one per workgroup
+// (drx_decode_select_with_wave_words: the chunks its selection touches; the others are not looked at).
 __global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
                                                          const uint64_t *__restrict__ chunk_word_off,
                                                          const uint32_t *__restrict__ n_in, uint64_t *__restrict__ wave_off,
-                                                         uint32_t *__restrict__ wave_words, DevStatus *st) {
+                                                         uint32_t *__restrict__ wave_words, DevStatus *st,
+                                                         const uint32_t *__restrict__ list) {
     __shared__ uint64_t wsum[4];
-    const uint64_t c = blockIdx.x;
+    const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
     const int lane = lane_id(), wv = threadIdx.x >> 6;
     uint64_t base;
     uint32_t W, L, N;
@@ -823,9 +825,39 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
 // launchers (host side, same translation unit so that <<<>>> stays in HIP code)
 // ---------------------------------------------------------------------------
 hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
-    if (G.total_waves == 0) return hipSuccess;
-    k_sideband_tables<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_n, d_wave_off, d_wave_words, d_status);
+                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,
+                                  const uint32_t *d_list, uint32_t n_list) {
+    if (G.total_waves == 0 || (d_list && !n_list)) return hipSuccess;
+    k_sideband_tables<<<d_list ? n_list : (unsigned)G.n_chunks, 256, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_n, d_wave_off,
+                                                                          d_wave_words, d_status, d_list);
+    return hipGetLastError();
+}
+
+// The header walk in front of drx_decode_select: the chunks its selection touches and no others, by the walk kernels' chunk
+// lists.  d_lists = the three lists back to back, as select_walk_class() sorted the touched chunks:
+//   n_sparse  long waveforms, 8 ... 8192 of them: k_walk_sparse (64 chains per chunk; the chunk is not read), then the
+//             scalar walker for the chunks it flagged in d_fail (uint32[n_chunks], cleared here), which also judges them
+//   n_block   WaveformLength <= kWalkShortLen: the LDS block walker, a wavefront per chunk
+//   n_chain   the rest (a few very long waveforms, or more than 8192 long ones): one lane per chunk, hop by hop
+int select_walk_class(uint32_t n_waves, uint32_t wave_len) {
+    if (wave_len <= kWalkShortLen) return 1;
+    return n_waves >= kSwMinWaves && n_waves <= kSwMaxWaves ? 0 : 2;
+}
+hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain, uint32_t *d_fail,
+                              uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
+    if (n_sparse) {
+        const hipError_t e = hipMemsetAsync(d_fail, 0, G.n_chunks * sizeof(uint32_t), s);
+        if (e != hipSuccess) return e;
+        k_walk_sparse<<<n_sparse, kSwThreads, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_fail, d_lists);
+        k_walk_scalar_only<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off,
+                                                                              d_wave_words, d_status, d_fail);
+    }
+    if (n_block)
+        k_walk_block<<<n_block, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_lists + n_sparse, n_block, d_wave_off, d_wave_words, d_status);
+    if (n_chain)
+        k_walk_list<<<blocks_for(n_chain, 64), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_lists + n_sparse + n_block, n_chain,
+                                                           d_wave_off, d_wave_words, d_status);
     return hipGetLastError();
 }
 

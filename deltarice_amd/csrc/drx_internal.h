@@ -114,7 +114,17 @@ static inline void mark(hipEvent_t *ev, int i, hipStream_t s) {  // (optional pr
 }
 
 hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
+                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,
+                                  const uint32_t *d_list = nullptr, uint32_t n_list = 0);  // d_list: these chunks only
+// drx_decode_select (drx_select.hip): the walk over the chunks a selection touches (drx_decode_kernels.hip, where the walk
+// kernels live; select_walk_class(): which of its three lists a chunk belongs to), then a wavefront per selected waveform
+int select_walk_class(uint32_t n_waves, uint32_t wave_len);
+hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain, uint32_t *d_fail,
+                              uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
+hipError_t launch_decode_select(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
+                                const uint64_t *d_sel, uint64_t n_sel, DevStatus *d_status, int16_t *d_out, uint64_t stride,
+                                hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 
 // wide: fused_wide() as the route decided it

@@ -131,6 +131,46 @@ static int log2_m(unsigned m, unsigned *k) {
     return 0;
 }
 
+/* A dataset this path takes (include/deltarice_h5io.h), opened read-only: its extent, chunk shape and parsed cd_values.
+ * Returns DRX_OK with all four handles open, or the status to report with whatever was opened left for close_dataset(). */
+typedef struct {
+    hid_t f, d, sp, pl;
+    hsize_t dims[2], chunk[2];
+    drx_opts o;
+} dataset_t;
+static void close_dataset(dataset_t *ds) {
+    if (ds->pl >= 0) H5Pclose(ds->pl);
+    if (ds->sp >= 0) H5Sclose(ds->sp);
+    if (ds->d >= 0) H5Dclose(ds->d);
+    if (ds->f >= 0) H5Fclose(ds->f);
+    ds->f = ds->d = ds->sp = ds->pl = -1;
+}
+static drx_status open_dataset(const char *file, const char *name, dataset_t *ds) {
+    ds->f = ds->d = ds->sp = ds->pl = -1;
+    if ((ds->f = H5Fopen(file, H5F_ACC_RDONLY, H5P_DEFAULT)) < 0) return DRX_ERR_ARG;
+    if ((ds->d = H5Dopen2(ds->f, name, H5P_DEFAULT)) < 0) return DRX_ERR_ARG;
+    ds->sp = H5Dget_space(ds->d);
+    ds->pl = H5Dget_create_plist(ds->d);
+    if (H5Sget_simple_extent_ndims(ds->sp) != 2 || H5Sget_simple_extent_dims(ds->sp, ds->dims, NULL) < 0) return DRX_ERR_ARG;
+    if (H5Pget_chunk(ds->pl, 2, ds->chunk) != 2 || ds->chunk[1] != ds->dims[1]) return DRX_ERR_UNSUPPORTED;
+    {
+        hid_t ty = H5Dget_type(ds->d);
+        /* 16-bit integers in the byte order the codec computes in; signed or unsigned alike (the reference reinterprets the
+         * bytes as int16 whatever the type, tests/test.py:72-83) */
+        const int ok = H5Tget_class(ty) == H5T_INTEGER && H5Tget_size(ty) == 2 && H5Tget_order(ty) == H5T_ORDER_LE;
+        H5Tclose(ty);
+        if (!ok) return DRX_ERR_UNSUPPORTED;
+    }
+    unsigned cd[3 + DRX_MAX_TAPS], flags = 0, fcfg = 0;
+    size_t ncd = 3 + DRX_MAX_TAPS;
+    char fname[8];
+    if (H5Pget_nfilters(ds->pl) != 1 ||
+        H5Pget_filter_by_id2(ds->pl, FILTER_ID, &flags, &ncd, cd, sizeof fname, fname, &fcfg) < 0)
+        return DRX_ERR_UNSUPPORTED;  /* other filters in the pipeline */
+    if (drx_parse_cd_values(ncd, cd, &ds->o) != DRX_OK) return DRX_ERR_ARG;
+    return DRX_OK;
+}
+
 drx_status drx_h5_read(drx_ctx *ctx, const char *file, const char *name, int16_t *d_out,
                        uint64_t out_cap_samples, drx_h5_stats *st) {
     if (!ctx || !file || !name || !d_out) return DRX_ERR_ARG;
@@ -146,31 +186,13 @@ drx_status drx_h5_read(drx_ctx *ctx, const char *file, const char *name, int16_t
     int prev_dev = -1;
     if (enter_device(ctx, &prev_dev) != 0) return DRX_ERR_DEVICE;
 
-    if ((f = H5Fopen(file, H5F_ACC_RDONLY, H5P_DEFAULT)) < 0) goto out;
-    if ((d = H5Dopen2(f, name, H5P_DEFAULT)) < 0) goto out;
-    sp = H5Dget_space(d);
-    pl = H5Dget_create_plist(d);
-    hsize_t dims[2], chunk[2];
-    if (H5Sget_simple_extent_ndims(sp) != 2 || H5Sget_simple_extent_dims(sp, dims, NULL) < 0) goto out;
-    if (H5Pget_chunk(pl, 2, chunk) != 2 || chunk[1] != dims[1]) { rc = DRX_ERR_UNSUPPORTED; goto out; }
-    {
-        hid_t ty = H5Dget_type(d);
-        /* 16-bit integers in the byte order the codec computes in; signed or unsigned alike (the reference reinterprets the
-         * bytes as int16 whatever the type, tests/test.py:72-83) */
-        const int ok = H5Tget_class(ty) == H5T_INTEGER && H5Tget_size(ty) == 2 && H5Tget_order(ty) == H5T_ORDER_LE;
-        H5Tclose(ty);
-        if (!ok) { rc = DRX_ERR_UNSUPPORTED; goto out; }
-    }
-    unsigned cd[3 + DRX_MAX_TAPS], flags = 0, fcfg = 0;
-    size_t ncd = 3 + DRX_MAX_TAPS;
-    char fname[8];
-    if (H5Pget_nfilters(pl) != 1 ||
-        H5Pget_filter_by_id2(pl, FILTER_ID, &flags, &ncd, cd, sizeof fname, fname, &fcfg) < 0) {
-        rc = DRX_ERR_UNSUPPORTED;  /* other filters in the pipeline */
-        goto out;
-    }
-    drx_opts o;
-    if (drx_parse_cd_values(ncd, cd, &o) != DRX_OK) goto out;
+    dataset_t ds;
+    rc = open_dataset(file, name, &ds);
+    f = ds.f; d = ds.d; sp = ds.sp; pl = ds.pl;
+    if (rc != DRX_OK) goto out;
+    rc = DRX_ERR_ARG;
+    const hsize_t *dims = ds.dims, *chunk = ds.chunk;
+    const drx_opts o = ds.o;
     const unsigned k = o.rice_k, L = o.wave_len < 0 ? 0u : (unsigned)o.wave_len;
     /* HDF5 stores the last chunk full size when the rows do not divide: it is decoded into scratch and the
      * rows that exist are copied out */
@@ -308,6 +330,107 @@ out:
     if (sp >= 0) H5Sclose(sp);
     if (d >= 0) H5Dclose(d);
     if (f >= 0) H5Fclose(f);
+    leave_device(prev_dev);
+    if (st) *st = s;
+    return rc;
+}
+
+static int cmp_u64(const void *a, const void *b) {
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? -1 : (x > y ? 1 : 0);
+}
+
+drx_status drx_h5_read_rows(drx_ctx *ctx, const char *file, const char *name, const uint64_t *rows, uint64_t n_rows,
+                            int16_t *d_out, uint64_t out_cap_samples, drx_h5_stats *st) {
+    if (!ctx || !file || !name || (n_rows && (!rows || !d_out))) return DRX_ERR_ARG;
+    drx_h5_stats s;
+    memset(&s, 0, sizeof s);
+    dataset_t ds;
+    void *h_words = NULL, *d_words = NULL;  /* (h_words: the context's staging buffer, not freed here) */
+    uint64_t *touched = NULL, *h_off = NULL, *d_off = NULL, *wave_idx = NULL;
+    drx_plan *plan = NULL;
+    int prev_dev = -1;
+    if (enter_device(ctx, &prev_dev) != 0) return DRX_ERR_DEVICE;
+    double t0 = now();
+    drx_status rc = open_dataset(file, name, &ds);
+    if (rc != DRX_OK) goto out;
+    rc = DRX_ERR_ARG;
+    const uint64_t n_data_rows = ds.dims[0], cols = ds.dims[1], chunk_rows = ds.chunk[0];
+    if (chunk_rows * cols > 0x7fffffffull) goto out;
+    const uint32_t chunk_samples = (uint32_t)(chunk_rows * cols);
+    s.rows = n_data_rows; s.cols = cols; s.chunk_rows = chunk_rows;
+    s.raw_bytes = n_rows * cols * 2;
+    /* a row must be a whole number of waveforms: its samples are then rows of drx_decode_select's output */
+    const uint64_t L = ds.o.wave_len < 0 ? (uint64_t)chunk_samples : (uint64_t)ds.o.wave_len;
+    if (cols % L != 0) { rc = DRX_ERR_UNSUPPORTED; goto out; }
+    const uint64_t wpr = cols / L;  /* waveforms per row */
+    for (uint64_t i = 0; i < n_rows; ++i) if (rows[i] >= n_data_rows) goto out;
+    if (n_rows * wpr >= (1ull << 32)) goto out;
+    if (n_rows * cols > out_cap_samples) { rc = DRX_ERR_CAPACITY; goto out; }
+    if (!n_rows) { rc = DRX_OK; goto out; }
+
+    /* the sorted set of chunks the rows lie in (HDF5 stores a padded last chunk full size: the same geometry as the others) */
+    touched = (uint64_t *)malloc(n_rows * sizeof(uint64_t));
+    wave_idx = (uint64_t *)malloc(n_rows * wpr * sizeof(uint64_t));
+    if (!touched || !wave_idx) { rc = DRX_ERR_NOMEM; goto out; }
+    for (uint64_t i = 0; i < n_rows; ++i) touched[i] = rows[i] / chunk_rows;
+    qsort(touched, n_rows, sizeof(uint64_t), cmp_u64);
+    uint64_t n_touched = 0;
+    for (uint64_t i = 0; i < n_rows; ++i) if (!n_touched || touched[n_touched - 1] != touched[i]) touched[n_touched++] = touched[i];
+    s.n_chunks = n_touched;
+    /* their stored sizes -> offsets -> the context's staging buffer <- their stored bytes */
+    h_off = (uint64_t *)malloc((n_touched + 1) * sizeof(uint64_t));
+    if (!h_off) { rc = DRX_ERR_NOMEM; goto out; }
+    uint64_t words = 0;
+    for (uint64_t t = 0; t < n_touched; ++t) {
+        hsize_t off[2] = {touched[t] * chunk_rows, 0}, nb = 0;
+        if (H5Dget_chunk_storage_size(ds.d, off, &nb) < 0 || (nb & 3)) { rc = DRX_ERR_CORRUPT; goto out; }
+        if (nb == 0) { rc = DRX_ERR_UNSUPPORTED; goto out; }  /* a chunk that was never written (fill value): not a stored stream */
+        h_off[t] = words;
+        words += nb / 4;
+    }
+    h_off[n_touched] = words;
+    s.stored_bytes = words * 4;
+    if (drx_ctx_host_staging(ctx, words * 4, &h_words) != DRX_OK) { rc = DRX_ERR_NOMEM; goto out; }
+    for (uint64_t t = 0; t < n_touched; ++t) {
+        hsize_t off[2] = {touched[t] * chunk_rows, 0};
+        uint32_t mask = 0;
+        if (H5Dread_chunk(ds.d, H5P_DEFAULT, off, &mask, (uint32_t *)h_words + h_off[t]) < 0 || mask) { rc = DRX_ERR_CORRUPT; goto out; }
+    }
+    s.t_file = now() - t0;
+
+    t0 = now();
+    hipStream_t stream = (hipStream_t)drx_ctx_stream(ctx);
+    if (hipMalloc(&d_words, words * 4) != hipSuccess || hipMalloc((void **)&d_off, (n_touched + 1) * 8) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
+    if (hipMemcpyAsync(d_words, h_words, words * 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(d_off, h_off, (n_touched + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) { rc = DRX_ERR_DEVICE; goto out; }
+    s.t_pcie = now() - t0;
+
+    /* a plan over the fetched chunks; row r = waveforms (local row) * wpr ... of chunk number (its place among the fetched) */
+    t0 = now();
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        const uint64_t c = rows[i] / chunk_rows, lr = rows[i] % chunk_rows;
+        uint64_t lo = 0, hi = n_touched;  /* invariant: touched[lo] <= c < touched[hi] */
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (touched[mid] <= c) lo = mid; else hi = mid;
+        }
+        for (uint64_t j = 0; j < wpr; ++j) wave_idx[i * wpr + j] = (lo * chunk_rows + lr) * wpr + j;
+    }
+    if ((rc = drx_plan_create_uniform(ctx, n_touched, chunk_samples, (uint32_t)L, ds.o.rice_k, &plan)) != DRX_OK) goto out;
+    if ((rc = drx_plan_set_filter(plan, ds.o.n_taps, ds.o.taps)) != DRX_OK) goto out;
+    if ((rc = drx_decode_select(plan, (const uint32_t *)d_words, words, d_off, wave_idx, n_rows * wpr, d_out, L)) != DRX_OK) goto out;
+    if ((rc = drx_plan_finish(plan, NULL)) != DRX_OK) goto out;
+    s.t_gpu = now() - t0;
+out:
+    if (plan) drx_plan_destroy(plan);
+    if (d_words) (void)hipFree(d_words);
+    if (d_off) (void)hipFree(d_off);
+    free(touched);
+    free(wave_idx);
+    free(h_off);
+    close_dataset(&ds);
     leave_device(prev_dev);
     if (st) *st = s;
     return rc;

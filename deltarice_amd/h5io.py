@@ -35,6 +35,9 @@ def _load():
         L = C.CDLL(H5IO_PATH)
         L.drx_h5_read.restype = C.c_int
         L.drx_h5_read.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(Stats)]
+        L.drx_h5_read_rows.restype = C.c_int
+        L.drx_h5_read_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p,
+                                       C.c_uint64, C.POINTER(Stats)]
         L.drx_h5_write.restype = C.c_int
         L.drx_h5_write.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.c_uint64, C.c_uint, C.c_uint, C.POINTER(Stats)]
@@ -53,6 +56,31 @@ def read(ctx: Context, path: str, name: str, out: torch.Tensor) -> dict:
     if rc != _lib.DRX_OK:
         raise _lib.DeltaRiceError(rc, f"drx_h5_read({path!r}, {name!r})")
     return st.as_dict()
+
+
+def read_rows(ctx: Context, path: str, name: str, rows, out: torch.Tensor | None = None):
+    """File -> VRAM, the dataset rows ``rows`` names (any integer sequence, array or CPU tensor; any order, duplicates
+    allowed): only the chunks those rows lie in are fetched and decoded.  Returns (int16 tensor [n_rows, cols] on
+    ctx.device, stats); out: a contiguous int16 tensor on ctx.device with room for n_rows * cols samples."""
+    from .codec import _as_index_array
+    idx = _as_index_array(rows)
+    L = _load()
+    st = Stats()
+    ctx.stream.wait_stream(torch.cuda.current_stream(ctx.device))
+    ip = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+    if out is None:
+        # the dataset's width is in the file: ask with an empty selection (opens the dataset, fetches nothing)
+        rc = L.drx_h5_read_rows(ctx._h, os.fsencode(path), name.encode(), ip, 0, None, 0, C.byref(st))
+        if rc != _lib.DRX_OK:
+            raise _lib.DeltaRiceError(rc, f"drx_h5_read_rows({path!r}, {name!r})")
+        out = torch.empty((idx.size, int(st.cols)), dtype=torch.int16, device=ctx.device)
+    if out.device != ctx.device or out.dtype != torch.int16 or not out.is_contiguous():
+        raise _lib.DeltaRiceError(1, f"out: need a contiguous int16 tensor on {ctx.device}")
+    rc = L.drx_h5_read_rows(ctx._h, os.fsencode(path), name.encode(), ip, idx.size, out.data_ptr(), out.numel(), C.byref(st))
+    if rc != _lib.DRX_OK:
+        raise _lib.DeltaRiceError(rc, f"drx_h5_read_rows({path!r}, {name!r})")
+    cols = int(st.cols)
+    return out.view(-1)[:idx.size * cols].view(idx.size, cols), st.as_dict()
 
 
 def write(ctx: Context, path: str, name: str, x: torch.Tensor, rows: int, cols: int, chunk_rows: int,

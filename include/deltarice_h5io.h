@@ -35,6 +35,16 @@ typedef struct {
 drx_status drx_h5_read(drx_ctx *ctx, const char *file, const char *name, int16_t *d_out,
                        uint64_t out_cap_samples, drx_h5_stats *stats);
 
+/* File -> VRAM, selected rows: row i of d_out (device int16[out_cap_samples], rows of `cols` samples back to back) receives
+ * dataset row rows[i] (host array; any order, duplicates allowed).  Same datasets as drx_h5_read, with the further condition
+ * that a row is a whole number of waveforms (cols % WaveformLength == 0; otherwise DRX_ERR_UNSUPPORTED).  Only the stored
+ * bytes of the chunks the rows lie in are fetched (H5Dread_chunk into the context's staging buffer), copied to the device
+ * once and decoded by one drx_decode_select over a plan of those chunks: stats->n_chunks and stats->stored_bytes count
+ * what was fetched, stats->raw_bytes what was delivered; the other chunks are neither read nor validated.
+ * A row >= the dataset's rows: DRX_ERR_ARG. */
+drx_status drx_h5_read_rows(drx_ctx *ctx, const char *file, const char *name, const uint64_t *rows, uint64_t n_rows,
+                            int16_t *d_out, uint64_t out_cap_samples, drx_h5_stats *stats);
+
 /* VRAM -> file: encodes d_in (device int16[rows*cols]) and writes it as dataset `name` (file is
  * created/truncated).  rice_m, wave_len: compression_opts (RiceParameter, WaveformLength). */
 drx_status drx_h5_write(drx_ctx *ctx, const char *file, const char *name, const int16_t *d_in,

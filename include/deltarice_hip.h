@@ -141,6 +141,28 @@ drx_status drx_decode(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
 drx_status drx_decode_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
                                       const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, int16_t *d_out);
 
+/* Decode SELECTED waveforms.  wave_idx: HOST array of n_sel global waveform indices (0 ... total_waves - 1, any order,
+ * duplicates allowed), consumed before the call returns; row i of d_out -- int16 at d_out + i * out_stride_samples -- receives
+ * the len_i samples of waveform wave_idx[i] (WaveformLength, or less for the last waveform of a chunk) and nothing else is
+ * written: the samples between rows keep what they held.  Otherwise asynchronous on the context's stream like drx_decode;
+ * errors found on the device arrive at drx_plan_finish.
+ *   Only the chunks that hold a selected waveform are walked (whole, with drx_decode's validation of the header chain: a
+ * corrupt touched chunk is reported as drx_decode reports it).  The other chunks are NEITHER READ NOR VALIDATED, and
+ * drx_plan_wave_words / drx_plan_wave_word_off after the call are valid for the touched chunks only.
+ *   DRX_ERR_ARG, with nothing launched: an index >= total_waves, out_stride_samples below the longest selected waveform,
+ * n_sel >= 2^32, a NULL pointer with n_sel > 0.  n_sel == 0: DRX_OK, nothing launched.
+ *   Every prediction filter the plan accepts: the delta filter a wavefront per selected waveform (parallel inside the
+ * waveform), any other a lane per selected waveform.  The selection's scratch belongs to the plan: allocated by the first
+ * such call, grown when a later one needs more. */
+drx_status drx_decode_select(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             const uint64_t *wave_idx, uint64_t n_sel, int16_t *d_out, uint64_t out_stride_samples);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device): no
+ * walk; the table is checked against the stream for the touched chunks, its entries for the others are not looked at. */
+drx_status drx_decode_select_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                             const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words,
+                                             const uint64_t *wave_idx, uint64_t n_sel, int16_t *d_out,
+                                             uint64_t out_stride_samples);
+
 /* RiceParameter optimiser (docs/Optimization.md:5-19 of the reference describes one, the tree does not
  * contain it): exact number of uint32 words drx_encode would emit for this batch with RiceParameter
  * 2^k, for every k = 0..15 (host array of 16), in one pass over the samples.  Synchronous. */
@@ -162,6 +184,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_SIMPLE 16u     /* the simple kernel (filters the fast kernels do not take) */
 #define DRX_PATH_IIR 32u        /* residuals first, then the general filter's inverse in place, parallel inside a waveform */
 #define DRX_PATH_IIR_FUSED 64u  /* the general filter's inverse inside the block decoder: one kernel, samples straight to the output */
+#define DRX_PATH_SELECT 128u    /* drx_decode_select: a wavefront (general filters: a lane) per selected waveform; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
