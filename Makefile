@@ -12,7 +12,7 @@ HIPFLAGS  ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-funct
 CSRC      := deltarice_amd/csrc
 HIP_LIB   := deltarice_amd/libdeltarice_hip.so
 PLUGIN    := deltarice_amd/plugin/libh5deltarice.so
-HIP_SRCS  := $(CSRC)/drx_encode_kernels.hip $(CSRC)/drx_encode_stream.hip $(CSRC)/drx_decode_kernels.hip $(CSRC)/drx_blocks.hip $(CSRC)/drx_pieces.hip $(CSRC)/drx_iir.hip $(CSRC)/drx_select.hip $(CSRC)/drx_api.hip
+HIP_SRCS  := $(CSRC)/drx_encode_kernels.hip $(CSRC)/drx_encode_stream.hip $(CSRC)/drx_walk.hip $(CSRC)/drx_decode_kernels.hip $(CSRC)/drx_blocks.hip $(CSRC)/drx_pieces.hip $(CSRC)/drx_iir.hip $(CSRC)/drx_select.hip $(CSRC)/drx_api.hip
 HIP_OBJS  := $(HIP_SRCS:.hip=.o)
 HIP_HDRS  := $(CSRC)/drx_internal.h $(CSRC)/drx_device.h $(CSRC)/drx_encode.h $(CSRC)/drx_walk.h $(CSRC)/drx_iir_math.h include/deltarice_hip.h
 
@@ -27,7 +27,7 @@ PY_INC    := $(shell $(PYTHON) -c "import sysconfig; print(sysconfig.get_paths()
 PYEXT     := deltaRice/h5$(PY_SUFFIX)
 PLUGIN_DIR ?= /usr/local/hdf5/lib/plugin
 
-.PHONY: all hip plugin h5io pyext install-plugin oracle asan check-asm clean
+.PHONY: all hip plugin h5io pyext install-plugin oracle asan check-asm print-hip-srcs clean
 all: hip plugin h5io pyext
 
 hip: $(HIP_LIB)
@@ -41,6 +41,10 @@ $(HIP_LIB): $(HIP_OBJS)
 # vector-memory instruction; a returning atomic's destination touched before its s_waitcnt), on the gfx950 disassembly
 check-asm: $(HIP_OBJS)
 	$(PYTHON) tools/check_asm_hazards.py $(HIP_OBJS)
+
+# the library's translation units, for tools that compile them their own way (tools/build_variant.sh)
+print-hip-srcs:
+	@echo $(HIP_SRCS)
 
 plugin: $(PLUGIN)
 $(PLUGIN): $(CSRC)/h5z_deltarice.c include/deltarice_h5filter.h include/deltarice_hip.h $(HIP_LIB)

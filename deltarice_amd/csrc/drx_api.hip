@@ -374,9 +374,8 @@ static drx_status plan_alloc(drx_plan *p) {
 static drx_status plan_ragged(drx_plan *p, const std::vector<ChunkDesc> &desc) {
     Geom &G = p->G;
     const ChunkDesc *d = desc.data();
-    std::vector<uint32_t> walk_lists;
-    std::vector<uint2> order;
-    decode_plan_ragged(G, d, &walk_lists, &order);
+    const std::vector<uint32_t> walk_lists = walk_plan_ragged(G, d);
+    const std::vector<uint2> order = decode_plan_ragged(G, d);
     const std::vector<uint64_t> unit_base = segments_plan_ragged(G, d);
     const std::vector<uint32_t> wg_base = pieces_plan_ragged(G, d);
     p->pc_wgs = wg_base.empty() ? 0 : wg_base.back();
@@ -405,7 +404,7 @@ static drx_status plan_alloc_scratch(drx_plan *p) {
     drx_ctx *ctx = p->ctx;
     Geom &G = p->G;
     if (long_batch(G)) DRX_HIP(ctx, seg_scratch(p));
-    if (const uint64_t nb = par_walk_scratch_bytes(G)) DRX_HIP(ctx, p->mem.alloc(&p->d_pw, nb));
+    if (const uint64_t nb = walk_scratch_bytes(G)) DRX_HIP(ctx, p->mem.alloc(&p->d_pw, nb));
     if (const uint64_t nb = blocks_scratch_bytes(G)) {
         DRX_HIP(ctx, p->mem.alloc(&p->d_blk, nb));
         // ... and, should the plan get a general prediction filter, the look-back state of the in-place inverse filter
@@ -462,16 +461,14 @@ static drx_status plan_create(drx_ctx *ctx, uint64_t n_chunks, const uint32_t *c
     G.u_wave_len = first.wave_len;
     G.u_n_waves = first.n_waves;
     G.k = rice_k;
-    // 25 bits per sample worst case, rounded up per waveform, + headers
-    auto max_words = [](const ChunkDesc &d) { return 1 + 2ull * d.n_waves + (((uint64_t)d.n_samples * 25u + 31u) >> 5); };
     if (uniform) {
         G.total_samples = n_chunks * first.n_samples;
         G.total_waves = n_chunks * first.n_waves;
-        p->max_words = n_chunks * max_words(first);
+        p->max_words = n_chunks * chunk_max_words(first.n_samples, first.n_waves);
     } else {
         G.total_samples = desc.back().sample_off + desc.back().n_samples;
         G.total_waves = desc.back().wave_base + desc.back().n_waves;
-        for (const ChunkDesc &d : desc) p->max_words += max_words(d);
+        for (const ChunkDesc &d : desc) p->max_words += chunk_max_words(d.n_samples, d.n_waves);
     }
     drx_status st = plan_alloc(p);
     if (st == DRX_OK && !uniform) st = plan_ragged(p, desc);
@@ -702,7 +699,7 @@ static drx_status decode_launch(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     // not take those paths)
     DRX_HIP(ctx, launch_decode(p->G, d_in, in_words, d_chunk_word_off, d_out, p->d_wave_off,
                                p->d_wave_words, p->d_scan, p->d_status,
-                               (tables_ready ? 100 : 0) + ctx->decode_impl, p->d_pw, p->d_blk, ctx->side.s ? &ctx->side : nullptr,
+                               ctx->decode_impl, tables_ready, p->d_pw, p->d_blk, ctx->side.s ? &ctx->side : nullptr,
                                ctx->profile ? p->ev : nullptr, ctx->stream, &p->last_path));
     p->ev_valid = ctx->profile != 0;
     p->last_was_encode = false;

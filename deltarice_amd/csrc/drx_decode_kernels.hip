@@ -1,6 +1,6 @@
 // drx_decode_kernels.hip -- gfx950 (MI355X, CDNA4) DECODE kernels of the Delta-Rice codec, the decode launch and its dispatch
-// (round 3 split drx_kernels.hip by role: drx_encode_kernels.hip, drx_walk.h, this file; few long waveforms: drx_blocks.hip,
-// general filters behind it: drx_iir.hip).
+// (the header walk in front of them: drx_walk.hip, its in-launch walkers: drx_walk.h; few long waveforms: drx_blocks.hip,
+// general filters behind it: drx_iir.hip; selected waveforms: drx_select.hip).
 //
 // Format contract (bit-exact with /root/reference/src/deltaRice.c):
 //   chunk   := u32 N | { u32 n_i | u32 payload_i[n_i] }            (:415,379,427-433)
@@ -24,64 +24,6 @@
 #include "drx_walk.h"
 
 namespace drx {
-
-// Side-band decode (drx_decode_with_wave_words): the caller hands over the n_i table an encode left behind (SURVEY section 7:
-// "reuse its offset table as a side-band"), so no header chain is walked.  Per chunk: header positions by a prefix sum over
-// 1 + n_i, each checked against the stream itself (the word at that position must BE n_i, n_i within the bounds of its
-// waveform, the chain must end exactly at the chunk's end, the chunk header must be the sample count) -- a table that does
-// not belong to the stream is DRX_ERR_CORRUPT, never a wild read.  list (optional): the chunks to do, one per workgroup
-// (drx_decode_select_with_wave_words: the chunks its selection touches; the others are not looked at).
-__global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                         const uint64_t *__restrict__ chunk_word_off,
-                                                         const uint32_t *__restrict__ n_in, uint64_t *__restrict__ wave_off,
-                                                         uint32_t *__restrict__ wave_words, DevStatus *st,
-                                                         const uint32_t *__restrict__ list) {
-    __shared__ uint64_t wsum[4];
-    const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
-    uint64_t base;
-    uint32_t W, L, N;
-    if (G.uniform) { base = c * G.u_n_waves; W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; }
-    else { const ChunkDesc d = G.chunks[c]; base = d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples; }
-    const uint64_t off0 = chunk_word_off[c], off1 = chunk_word_off[c + 1];
-    bool bad = off1 > in_words || off0 >= off1;  // (the same in every lane here; block-wide after every round below)
-    uint64_t run = 1;  // the chunk header word
-    for (uint32_t i0 = 0; i0 < W; i0 += 256) {
-        const uint32_t i = i0 + threadIdx.x;
-        const uint32_t n = (i < W) ? n_in[base + i] : 0u;
-        const uint32_t len = (i < W) ? ((i + 1u == W) ? N - i * L : L) : 0u;
-        // An entry outside the bounds of its waveform never enters the prefix sum (64-bit: 256 entries of up to 25 bits per
-        // sample of a 2^31-sample waveform do not fit 32), so no later position can wrap below off0 or past 2^64; and the
-        // whole chunk is rejected before any lane looks at the stream.
-        const bool n_ok = i >= W || (n <= max_payload_words(len) && n >= min_payload_words(len, G.k));
-        const uint64_t v = (i < W && n_ok) ? (uint64_t)n + 1u : 0u;
-        uint64_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wv] = inc;
-        bad = __syncthreads_or(bad || !n_ok) != 0;
-        uint64_t before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { before += (w < wv) ? wsum[w] : 0u; all += wsum[w]; }
-        bool mine_bad = bad;
-        if (i < W) {
-            const uint64_t at = off0 + run + before + inc - v;
-            if (!mine_bad && (at <= off0 || at >= off1 || at + 1u + n > off1)) mine_bad = true;
-            if (!mine_bad && in[at] != n) mine_bad = true;
-            // a rejected entry is left pointing at the chunk's own header with no payload words: the decode launch behind
-            // this one runs whatever the status says, and reads nothing through such an entry
-            wave_off[base + i] = mine_bad ? off0 : at;
-            wave_words[base + i] = mine_bad ? 0u : n;
-        }
-        run += all;
-        bad = __syncthreads_or(mine_bad) != 0;  // (also keeps wsum until every lane has read it)
-    }
-    if (threadIdx.x == 0 && !bad && (off0 + run != off1 || in[off0] != N)) bad = true;
-    if (bad && threadIdx.x == 0) atomicOr(&st->err, kErrCorrupt);
-}
 
 // Straightforward lane-per-waveform decoder: global loads and 2-byte stores.
 // Kept as the simple cross-check of the staged kernel below (decode_impl = 0).
@@ -822,110 +764,10 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
 }
 
 // ---------------------------------------------------------------------------
-// launchers (host side, same translation unit so that <<<>>> stays in HIP code)
+// the lane decoder's ragged plan, the decode route and launch (host side, same translation unit so that <<<>>> stays in HIP code)
 // ---------------------------------------------------------------------------
-hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,
-                                  const uint32_t *d_list, uint32_t n_list) {
-    if (G.total_waves == 0 || (d_list && !n_list)) return hipSuccess;
-    k_sideband_tables<<<d_list ? n_list : (unsigned)G.n_chunks, 256, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_n, d_wave_off,
-                                                                          d_wave_words, d_status, d_list);
-    return hipGetLastError();
-}
-
-// The header walk in front of drx_decode_select: the chunks its selection touches and no others, by the walk kernels' chunk
-// lists.  d_lists = the three lists back to back, as select_walk_class() sorted the touched chunks:
-//   n_sparse  long waveforms, 8 ... 8192 of them: k_walk_sparse (64 chains per chunk; the chunk is not read), then the
-//             scalar walker for the chunks it flagged in d_fail (uint32[n_chunks], cleared here), which also judges them
-//   n_block   WaveformLength <= kWalkShortLen: the LDS block walker, a wavefront per chunk
-//   n_chain   the rest (a few very long waveforms, or more than 8192 long ones): one lane per chunk, hop by hop
-int select_walk_class(uint32_t n_waves, uint32_t wave_len) {
-    if (wave_len <= kWalkShortLen) return 1;
-    return n_waves >= kSwMinWaves && n_waves <= kSwMaxWaves ? 0 : 2;
-}
-hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                              const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain, uint32_t *d_fail,
-                              uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
-    if (n_sparse) {
-        const hipError_t e = hipMemsetAsync(d_fail, 0, G.n_chunks * sizeof(uint32_t), s);
-        if (e != hipSuccess) return e;
-        k_walk_sparse<<<n_sparse, kSwThreads, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_fail, d_lists);
-        k_walk_scalar_only<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off,
-                                                                              d_wave_words, d_status, d_fail);
-    }
-    if (n_block)
-        k_walk_block<<<n_block, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_lists + n_sparse, n_block, d_wave_off, d_wave_words, d_status);
-    if (n_chain)
-        k_walk_list<<<blocks_for(n_chain, 64), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_lists + n_sparse + n_block, n_chain,
-                                                           d_wave_off, d_wave_words, d_status);
-    return hipGetLastError();
-}
-
-// The block-parallel walk of a batch's chunks, each of n_waves waveforms of wave_len samples (from 16), pays against the walk
-// inside the decode launch (serial chase through LDS, 0.13 us per waveform of a chunk, all chunks at once, so that large
-// batches hide most of it) while it walks no more chunks than one per 35 waveforms of a chunk.  Measured (chunks of 14 M
-// samples, decode GB/s of the two paths at 150 / 220 chunks): L = 512 1602 / 1627 against 875 / 1265; L = 1024 1869 / 1927
-// against 1521 / 1954; L = 2048 1906 / 2012 against 1673 / 2169.  Above WaveformLength 2048 the alternative is the scalar
-// chain at 0.85 us per hop (L = 3072, 100 / 220 chunks: 1731 / 1459+ against 596 / 1123): one per 18.
-static bool bw_walk_pays(uint64_t walked_chunks, uint32_t n_waves, uint32_t wave_len) {
-    return walked_chunks <= n_waves / (wave_len <= kWalkShortLen ? 35u : 18u) && wave_len >= 16u;
-}
-// ... the 4096-word blocks of such a chunk: its code at 25 bits per sample with its headers, at most kBwMaxBlocks
-constexpr uint64_t kBwMaxBlocks = 0xfffffu;
-static uint64_t bw_chunk_blocks(uint32_t n_samples, uint32_t n_waves) {
-    const uint64_t max_words = 1u + 2ull * n_waves + (((uint64_t)n_samples * 25u + 31u) >> 5);
-    return (max_words + kWalkBlockWords - 1u) / kWalkBlockWords;
-}
-
-uint32_t bw_walk_blocks_max(const Geom &G) {
-    // every 4096-word block must hold a header: n_i <= 25 L / 32 < 4096, i.e. L <= 5000; chunks of longer
-    // waveforms within the chunk-wide walk's capacity take that one
-    const bool chunk_wide = G.u_wave_len > kWalkShortLen && G.u_n_waves <= kSwMaxWaves && G.u_n_waves >= kSwMinWaves;
-    if (!(G.uniform && bw_walk_pays(G.n_chunks, G.u_n_waves, G.u_wave_len) && G.n_chunks <= kPwMaxChunks && G.u_wave_len <= 5000u &&
-          !chunk_wide)) return 0;
-    const uint64_t nb = bw_chunk_blocks(G.u_n_samples, G.u_n_waves);
-    return nb > kBwMaxBlocks ? 0u : (uint32_t)nb;
-}
-
-// bytes of header list per 4096 words of stream for the block size the launch will choose (0: none kept)
-static uint64_t bw_hop_bytes_per_block4096(const Geom &G) {
-    const uint32_t max_len = G.uniform ? G.u_wave_len : kWalkShortLen, min_len = G.uniform ? G.u_wave_len : G.rag_bw_min_len;
-    const uint32_t max_full = (uint32_t)(((uint64_t)max_len * 25u + 31u) >> 5);
-    const uint32_t B = max_full + 2u <= 1024u ? 1024u : (max_full + 2u <= 2048u ? 2048u : 4096u);
-    return (uint64_t)bw_hop_cap(B, min_len, G.k) * sizeof(uint32_t) * (kWalkBlockWords / B);
-}
-
-// scratch of the parallel header walks (0: the batch takes neither); layout in launch_decode()
-uint64_t par_walk_scratch_bytes(const Geom &G) {
-    bool pw, bw;
-    uint64_t bw_units;
-    if (G.uniform) {
-        const uint32_t nb = bw_walk_blocks_max(G);
-        bw = nb != 0;
-        bw_units = G.n_chunks * nb;
-        pw = !bw && G.n_chunks <= kSwMaxChunks && G.u_n_waves <= kSwMaxWaves && G.u_n_waves >= kSwMinWaves && G.u_wave_len > kWalkShortLen;
-    } else {
-        if (!G.rag_par) return 0;
-        pw = G.n_long != 0;
-        bw = G.n_short != 0;
-        bw_units = (uint64_t)G.n_short * G.rag_bw_blocks_max;
-    }
-    if (!pw && !bw) return 0;
-    // (the candidate lists of the scan form only where that form may run)
-    return (pw && G.n_chunks <= kPwMaxChunks ? G.n_chunks * kPwStride * sizeof(uint2) : 0) + (3u * G.n_chunks + 2u) * sizeof(uint32_t) +
-           bw_units * (kWalkBlockWords / 1024u) * sizeof(BwBlock) +  // (blocks of 1024 words at the smallest)
-           bw_units * bw_hop_bytes_per_block4096(G);                 // header lists of the first block pass
-}
-
-void decode_plan_ragged(Geom &G, const ChunkDesc *d, std::vector<uint32_t> *walk_lists, std::vector<uint2> *order) {
+std::vector<uint2> decode_plan_ragged(Geom &G, const ChunkDesc *d) {
     const uint64_t n = G.n_chunks;
-    // walk lists: chunks of short waveforms are walked through LDS, the others hop by hop
-    std::vector<uint32_t> &lists = *walk_lists;
-    lists.clear();
-    for (uint64_t c = 0; c < n; ++c) if (d[c].wave_len <= kWalkShortLen) lists.push_back((uint32_t)c);
-    G.n_short = (uint32_t)lists.size();
-    for (uint64_t c = 0; c < n; ++c) if (d[c].wave_len > kWalkShortLen) lists.push_back((uint32_t)c);
-    G.n_long = (uint32_t)lists.size() - G.n_short;
     uint32_t max_groups = 0, max_len = 0;
     for (uint64_t c = 0; c < n; ++c) {
         max_groups = std::max(max_groups, (d[c].n_waves + 63u) / 64u);
@@ -937,38 +779,20 @@ void decode_plan_ragged(Geom &G, const ChunkDesc *d, std::vector<uint32_t> *walk
     std::vector<uint32_t> by_len(n);
     for (uint64_t c = 0; c < n; ++c) by_len[c] = (uint32_t)c;
     std::stable_sort(by_len.begin(), by_len.end(), [&](uint32_t a, uint32_t b) { return d[a].wave_len > d[b].wave_len; });
-    order->clear();
+    std::vector<uint2> order;
     uint64_t n_long_groups = 0;
     for (uint32_t c : by_len)
         for (uint32_t j = 0; j < (d[c].n_waves + 63u) / 64u; ++j) {
-            order->push_back(make_uint2(c, j));
+            order.push_back(make_uint2(c, j));
             if (d[c].wave_len > kWalkShortLen) ++n_long_groups;
         }
-    if (order->size() <= 0x7fffffffull) {
-        G.rag_groups = (uint32_t)order->size();
+    if (order.size() <= 0x7fffffffull) {
+        G.rag_groups = (uint32_t)order.size();
         G.rag_groups_long = (uint32_t)n_long_groups;
     } else {
-        order->clear();
+        order.clear();
     }
-    // parallel header walks for small ragged batches: every long-waveform chunk within the chunk-wide walk's capacity, every
-    // short-waveform chunk worth the block-parallel walk (bw_walk_pays(), bw_chunk_blocks(): the rules of uniform batches)
-    bool ok = G.n_long <= kPwMaxChunks && G.n_short <= kPwMaxChunks;
-    uint64_t bmax = 0;
-    uint32_t min_len = 0xffffffffu, min_long_waves = 0xffffffffu;
-    for (uint64_t c = 0; c < n && ok; ++c) {
-        if (d[c].wave_len > kWalkShortLen) {
-            ok = d[c].n_waves <= kPwMaxWaves;
-            min_long_waves = std::min(min_long_waves, d[c].n_waves);
-        } else {
-            ok = bw_walk_pays(G.n_short, d[c].n_waves, d[c].wave_len);
-            bmax = std::max(bmax, bw_chunk_blocks(d[c].n_samples, d[c].n_waves));
-            min_len = std::min(min_len, d[c].wave_len);
-        }
-    }
-    G.rag_par = ok && bmax <= kBwMaxBlocks;
-    G.rag_bw_blocks_max = (uint32_t)bmax;
-    G.rag_bw_min_len = min_len;
-    G.rag_pw_min_waves = min_long_waves;
+    return order;
 }
 
 // ---------------------------------------------------------------------------
@@ -981,82 +805,57 @@ void decode_plan_ragged(Geom &G, const ChunkDesc *d, std::vector<uint32_t> *walk
 //   LONG          | uniform, delta, long_waveform_batch() and not BLOCKS; LONG_NOT_BLOCKS             | parallel walks / serial
 //   LANES fused   | decode_impl 8, not a batch the parallel walks take (short waveforms in many    | inside the launch
 //                 | chunks, chunks of more than 8192 or fewer than 8 waveforms), grid not mostly idle |
-//   LANES         | everything else; ragged batches behind both parallel walks: two launches          | parallel walks / serial
+//   LANES         | everything else                                                                   | parallel walks / serial
+//   LANES split   | ... ragged batches behind both parallel walks: a lanes launch behind each         | both parallel walks
 //
-//   walk          | when (never with tables_ready: the caller filled wave_off / wave_words)
-//   --------------+-----------------------------------------------------------------------------------
-//   chunk-wide    | chunks of 8 ... 8192 waveforms longer than 2048 samples (uniform, any number of chunks: k_walk_sparse chases 64 chains per
-//                 | chunk without reading it -- the headline batch too), the long-waveform chunks of a small ragged batch
-//   block-parallel| bw_walk_blocks_max(): few chunks of many short waveforms (uniform), the short-waveform chunks of a small ragged batch
-//   serial        | otherwise: LDS block walkers (WaveformLength <= 2048) / scalar chains, one launch in front of the decoder
-//   chunk-wide by chains (k_walk_sparse), or by reading the chunks (k_pw_scan + k_walk_parallel) for one to four chunks of 64 ...
-//   kPwMaxWaves waveforms.  Ragged batches behind both walks: a lanes launch behind each (split).
-// Flags (DRX_DBG_*): NO_LONG_PATHS never BLOCKS / LONG, LONG_NOT_BLOCKS LONG instead of BLOCKS, NO_PARALLEL_WALKS, WALK_BY_SCAN
-// and WALK_BY_CHAINS (where the other form is the default), RAGGED_ONE_LANES_LAUNCH.
+// Which walk "parallel walks / serial" is: route_walk() and its table, drx_walk.hip.
+// Flags (DRX_DBG_*): NO_LONG_PATHS never BLOCKS / LONG, LONG_NOT_BLOCKS LONG instead of BLOCKS, RAGGED_ONE_LANES_LAUNCH; the
+// walk's own with route_walk().
 // ---------------------------------------------------------------------------
-enum class Dec { Simple, Blocks, Long, LanesFused, Lanes };
+enum class Dec { Simple, Blocks, Long, LanesFused, Lanes, LanesSplit };
 enum class Walk { None, InLaunch, Parallel, Serial };
 struct DecodeRoute {
     Dec dec;
     Walk walk;
-    bool gen;             // a general prediction filter
-    bool use_pw, use_bw;  // Walk::Parallel: the chunk-wide walk, the block-parallel walk
-    bool pw_chains;       // ... the chunk-wide walk by chains, not by reading the chunks
-    bool split;           // ... ragged, behind both walks: two lanes launches
-    uint32_t bw_blocks_max;
+    WalkRoute par;  // Walk::Parallel: which of the two
+    bool gen;       // a general prediction filter
 };
 
 static DecodeRoute route_decode(const Geom &G, int impl, bool tables_ready, bool have_pw, bool have_blk, bool have_side) {
     DecodeRoute R{};
     R.gen = G.n_taps != 0;
+    R.par = route_walk(G, tables_ready, have_pw);
     const bool simple = impl == 0 || (R.gen && !G.fast_taps);
     const bool want_fused = !tables_ready && impl == 8;
-    const bool no_par = tables_ready || !have_pw || (G.dbg & DRX_DBG_NO_PARALLEL_WALKS);
-    const bool par_walk = !no_par && G.uniform && G.n_chunks <= kSwMaxChunks && G.u_n_waves <= kSwMaxWaves && G.u_n_waves >= kSwMinWaves &&
-                          G.u_wave_len > kWalkShortLen;
-    R.bw_blocks_max = bw_walk_blocks_max(G);
-    const bool bw_walk = !no_par && R.bw_blocks_max != 0;
-    const bool rag_par = !no_par && !G.uniform && G.rag_par;
-    R.use_pw = par_walk || (rag_par && G.n_long);
-    R.use_bw = bw_walk || (rag_par && G.n_short);
     const bool blocks = !simple && !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS)) && have_blk && blocks_batch(G) && (!R.gen || (G.iir_tab && G.iir_state));
     const bool longp = !simple && !blocks && !R.gen && !(G.dbg & DRX_DBG_NO_LONG_PATHS) && G.uniform && long_waveform_batch(G.total_waves, G.u_wave_len);
     // ragged: the group-major grid of the fused launch has max_groups tickets per chunk; not when most of them would be idle
     const bool sparse = !G.uniform && (uint64_t)G.n_chunks * G.max_groups > 8ull * ((G.total_waves + 63u) / 64u) + 4096ull;
     R.dec = simple ? Dec::Simple : (blocks ? Dec::Blocks : (longp ? Dec::Long : Dec::Lanes));
-    const bool parallel = par_walk || bw_walk || rag_par;
+    const bool parallel = R.par.chunk_wide || R.par.blocks;
     if (R.dec == Dec::Lanes && want_fused && !sparse && !parallel) R.dec = Dec::LanesFused;
     R.walk = tables_ready ? Walk::None : (R.dec == Dec::LanesFused ? Walk::InLaunch : (parallel ? Walk::Parallel : Walk::Serial));
-    // (up to four chunks the scan form is quicker: 128 workgroups read one chunk in 11 us, where a chain is 31 dependent loads;
-    // so for ragged chunks of a few very long waveforms: a start costs half a waveform's code in reads)
-    const bool few_waves = G.uniform && (G.u_n_waves < 64u || G.u_n_waves > kPwMaxWaves);  // (outside the scan form's range)
-    const bool chains_suit = (G.dbg & DRX_DBG_WALK_BY_CHAINS) || few_waves || ((G.uniform ? G.n_chunks : G.n_long) > 4u && (G.uniform || G.rag_pw_min_waves >= 64u));
-    R.pw_chains = (!(G.dbg & DRX_DBG_WALK_BY_SCAN) && chains_suit) || G.n_chunks > kPwMaxChunks || few_waves;
-    R.split = R.walk == Walk::Parallel && R.use_pw && R.use_bw && have_side && R.dec == Dec::Lanes && G.rag_order && G.rag_groups_long &&
-              G.rag_groups_long < G.rag_groups && !(G.dbg & DRX_DBG_RAGGED_ONE_LANES_LAUNCH);
+    if (R.dec == Dec::Lanes && R.par.chunk_wide && R.par.blocks && have_side && G.rag_order && G.rag_groups_long &&
+        G.rag_groups_long < G.rag_groups && !(G.dbg & DRX_DBG_RAGGED_ONE_LANES_LAUNCH)) R.dec = Dec::LanesSplit;
     return R;
 }
 
 hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
                          const uint64_t *d_chunk_word_off, int16_t *d_out, uint64_t *d_wave_off,
-                         uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl,
+                         uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl, bool tables_ready,
                          void *d_pw, void *d_blk, const SideStream *side, hipEvent_t *ev, hipStream_t s, uint32_t *path_out) {
     uint32_t path_dummy = 0;
     uint32_t &path = path_out ? *path_out : path_dummy;
     path = 0;
     if (G.total_waves == 0) return hipSuccess;
     mark(ev, 0, s);
-    // impl >= 100: wave_off / wave_words are already filled in (the one-chunk host path walks the header chain on the CPU while
-    // the chunk is in flight to the device; the side-band decode derives them from the caller's table): no walk
-    const bool tables_ready = impl >= 100;
-    if (tables_ready) impl -= 100;
     const DecodeRoute R = route_decode(G, impl, tables_ready, d_pw != nullptr, d_blk != nullptr, side && side->s);
     const bool gen = R.gen;
     const unsigned nb_plain = blocks_for(G.total_waves, 64);
 
     // the lane-per-waveform launch behind a walk (tables in wave_off / wave_words): `nb` wavefronts of view Gv
     auto launch_lanes = [&](const Geom &Gv, unsigned nb, hipStream_t st_) {
-        path |= 2u;  // DRX_PATH_LANES
+        path |= DRX_PATH_LANES;
         if (gen)
             k_decode_lanes<false, true><<<nb, 64, 0, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
         else
@@ -1064,50 +863,28 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
     };
 
     // ---- the walk ----
-    bool lanes_done = false;
     if (R.walk == Walk::InLaunch) {
         // granules + ticket word, zeroed before every launch (a granule is its own ready flag)
         hipError_t e = hipMemsetAsync(d_granules, 0, (G.total_waves + 2) * sizeof(uint64_t), s);
         if (e != hipSuccess) return e;
     } else if (R.walk == Walk::Parallel) {
-        // scratch: uint2 cand[n_chunks * kPwCap] | uint32 count[n_chunks] | pw_fail[n_chunks] | bw_fail[n_chunks] |
-        //          BwBlock info[n_bw * bw_blocks]   (cand .. pw_fail only where the chunk-wide walk is used)
-        const uint32_t *pw_list = G.uniform ? nullptr : G.walk_long, *bw_list = G.uniform ? nullptr : G.walk_short;
-        const uint32_t n_pw = G.uniform ? (uint32_t)G.n_chunks : G.n_long, n_bw = G.uniform ? (uint32_t)G.n_chunks : G.n_short;
-        const uint32_t bwb = G.uniform ? R.bw_blocks_max : G.rag_bw_blocks_max;
-        uint2 *cand = reinterpret_cast<uint2 *>(d_pw);
-        const bool have_cand = R.use_pw && G.n_chunks <= kPwMaxChunks;  // (par_walk_scratch_bytes())
-        uint32_t *cnt = reinterpret_cast<uint32_t *>(cand + (have_cand ? G.n_chunks * kPwStride : 0));
-        uint32_t *pw_fail = cnt + G.n_chunks, *bw_fail = pw_fail + G.n_chunks;
-        BwBlock *info = reinterpret_cast<BwBlock *>(bw_fail + G.n_chunks + (G.n_chunks & 1u));
-        hipError_t e = hipMemsetAsync(cnt, 0, 3u * G.n_chunks * sizeof(uint32_t), s);
+        const bool split = R.dec == Dec::LanesSplit;
+        hipError_t e = walk_scratch_reset(G, d_pw, s);
         if (e != hipSuccess) return e;
         // a ragged batch has both kinds of chunk and the two walks touch different chunks: the chunk-wide walk goes to the
         // context's side stream while the block walk runs here (config 5: 0.18 ms of 0.6 off the critical path)
-        const bool forked = R.use_pw && R.use_bw && side && side->s;
+        const bool forked = R.par.chunk_wide && R.par.blocks && side && side->s;
         hipStream_t spw = forked ? side->s : s;
         if (forked) {
             if ((e = hipEventRecord(side->fork, s)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(side->s, side->fork, 0)) != hipSuccess) return e;
         }
-        if (R.use_pw) {
-            if (R.pw_chains) {
-                // 64 chains per chunk chased in parallel from starts found by looking forward from 64 cuts (drx_walk.h): the chunk is
-                // not read
-                const unsigned sw_threads = (G.uniform && G.u_n_waves < 256u) ? 256u : (unsigned)kSwThreads;  // (few chains: few wavefronts)
-                k_walk_sparse<<<n_pw, sw_threads, 0, spw>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, pw_fail, pw_list);
-            } else {
-                k_pw_scan<<<(unsigned)(n_pw * pw_parts(n_pw)), 256, 0, spw>>>(G, d_in, in_words, d_chunk_word_off, pw_list, cand, cnt, pw_parts(n_pw));
-                k_walk_parallel<<<n_pw, kPwThreads, 0, spw>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words,
-                                                              pw_fail, pw_list, cand, cnt, pw_parts(n_pw));
-            }
-            k_walk_scalar_only<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, spw>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off,
-                                                                                    d_wave_words, d_status, pw_fail);
-        }
+        if (R.par.chunk_wide)
+            launch_walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, R.par.by_chains, spw);
         // ... and so does the decoding of the long-waveform chunks, whose tables are complete long before the block walk is
         // through: their wavefronts (the first rag_groups_long of the longest-first order) are launched behind the
         // chunk-wide walk on the side stream, the rest here behind the block walk
-        if (R.split) {
+        if (split) {
             Geom Gl = G;
             Gl.rag_groups = G.rag_groups_long;
             launch_lanes(Gl, Gl.rag_groups, spw);
@@ -1117,65 +894,25 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
             (void)hipStreamSynchronize(side->s);
             return e;
         }
-        if (R.use_bw) {
-            // block size: the smallest that exceeds every listed chunk's max_words; wavefronts: what the LDS lets the chip hold
-            const uint32_t max_len = G.uniform ? G.u_wave_len : kWalkShortLen;
-            const uint32_t max_full = (uint32_t)(((uint64_t)max_len * 25u + 31u) >> 5);
-            const uint32_t min_len = G.uniform ? G.u_wave_len : G.rag_bw_min_len;
-            auto run_bw = [&](auto btag, unsigned waves_per_cu) {
-                constexpr uint32_t B = decltype(btag)::value;
-                const uint32_t bmax = bwb * (kWalkBlockWords / B);
-                const unsigned grid = 256u * waves_per_cu;
-                // header lists behind info[] (sized for the smallest block: par_walk_scratch_bytes())
-                const uint32_t hop_cap = bw_hop_cap(B, min_len, G.k);
-                uint32_t *hops = hop_cap ? reinterpret_cast<uint32_t *>(info + (uint64_t)n_bw * bwb * (kWalkBlockWords / 1024u)) : nullptr;
-                if (hops)
-                    k_bw_blocks<B, false, true><<<grid, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, bw_list, n_bw, bmax, info, nullptr, nullptr, nullptr, d_status, hops, hop_cap);
-                else
-                    k_bw_blocks<B, false><<<grid, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, bw_list, n_bw, bmax, info, nullptr, nullptr, nullptr, d_status, nullptr, 0u);
-                k_bw_scan<B><<<n_bw, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, bw_list, n_bw, bmax, info, bw_fail);
-                if (hops)
-                    k_bw_emit<B><<<256u * 8u, 256, 0, s>>>(G, in_words, d_chunk_word_off, bw_list, n_bw, bmax, info, bw_fail, hops, hop_cap, d_wave_off, d_wave_words, d_status);
-                else
-                    k_bw_blocks<B, true><<<grid, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, bw_list, n_bw, bmax, info, bw_fail, d_wave_off, d_wave_words, d_status, nullptr, 0u);
-            };
-            if (max_full + 2u <= 1024u) run_bw(std::integral_constant<uint32_t, 1024>{}, 24u);
-            else if (max_full + 2u <= 2048u) run_bw(std::integral_constant<uint32_t, 2048>{}, 13u);
-            else run_bw(std::integral_constant<uint32_t, 4096>{}, 7u);
-            k_walk_block_only<<<(unsigned)G.n_chunks, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, bw_fail);
-        }
-        if (R.split) {
+        if (R.par.blocks) launch_walk_blocks(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
+        if (split) {
             mark(ev, 1, s);  // (the block walk's end; the other stream is decoding already)
             Geom Gs = G;
             Gs.rag_order = G.rag_order + G.rag_groups_long;
             Gs.rag_groups = G.rag_groups - G.rag_groups_long;
             launch_lanes(Gs, Gs.rag_groups, s);
-            lanes_done = true;
         }
         if (forked && (e = hipStreamWaitEvent(s, side->join, 0)) != hipSuccess) {
             (void)hipStreamSynchronize(side->s);
             return e;
         }
     } else if (R.walk == Walk::Serial) {
-        // chunks of short waveforms: stream the chunk through LDS; long waveforms: one dependent load per hop
-        if (G.uniform) {
-            if (G.u_wave_len <= kWalkShortLen)
-                k_walk_block<<<(unsigned)G.n_chunks, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, nullptr,
-                                                                 (uint32_t)G.n_chunks, d_wave_off, d_wave_words, d_status);
-            else
-                k_walk_scalar<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off,
-                                                                                 d_wave_off, d_wave_words, d_status);
-        } else {
-            if (G.n_short) k_walk_block<<<G.n_short, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, G.walk_short, G.n_short,
-                                                                 d_wave_off, d_wave_words, d_status);
-            if (G.n_long) k_walk_list<<<blocks_for(G.n_long, 64), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, G.walk_long,
-                                                                             G.n_long, d_wave_off, d_wave_words, d_status);
-        }
+        launch_walk_serial(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, s);
     }
-    if (!lanes_done) mark(ev, 1, s);
+    if (R.dec != Dec::LanesSplit) mark(ev, 1, s);
 
     // ---- the decoder ----
-    switch (lanes_done ? Dec::Simple /* nothing left to launch */ : R.dec) {
+    switch (R.dec) {
     case Dec::LanesFused: {
         uint32_t *ticket = reinterpret_cast<uint32_t *>(d_granules + G.total_waves);
         unsigned n_walk, groups;
@@ -1191,7 +928,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
             groups = G.max_groups;
             nb = n_walk + (unsigned)(G.n_chunks * groups);
         }
-        path |= 1u;  // DRX_PATH_LANES_FUSED
+        path |= DRX_PATH_LANES_FUSED;
         if (gen)
             k_decode_lanes<true, true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
         else
@@ -1205,7 +942,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         bool fused = false;
         hipError_t e = launch_decode_blocks(G, d_in, in_words, d_wave_off, d_wave_words, d_blk, d_status, d_out, &fail, &suspect, gen, s, &fused);
         if (e != hipSuccess) return e;
-        path |= 4u | (gen ? (fused ? 64u : 32u) : 0u);  // DRX_PATH_BLOCKS (| DRX_PATH_IIR_FUSED / DRX_PATH_IIR)
+        path |= DRX_PATH_BLOCKS | (gen ? (fused ? DRX_PATH_IIR_FUSED : DRX_PATH_IIR) : 0u);
         k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, fail, suspect, gen ? 1u : 0u);
         if (gen) {
             // (not fused: residuals -> samples, in place;) then the waveforms the block decoder flagged, serially (a slope-1 ramp)
@@ -1215,17 +952,17 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         break;
     }
     case Dec::Long:  // (LONG_NOT_BLOCKS, or a long-waveform batch the block decoder does not take: one workgroup per waveform)
-        path |= 8u;  // DRX_PATH_LONG
+        path |= DRX_PATH_LONG;
         k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, nullptr, nullptr, 0u);
         break;
     case Dec::Lanes:
         launch_lanes(G, (!G.uniform && G.rag_order) ? G.rag_groups : nb_plain, s);  // (ragged: groups per chunk round up)
         break;
+    case Dec::LanesSplit:  // (both launches went out behind their walks)
+        break;
     case Dec::Simple:
-        if (!lanes_done) {
-            path |= 16u;  // DRX_PATH_SIMPLE
-            k_decode_simple<<<nb_plain, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, nullptr);
-        }
+        path |= DRX_PATH_SIMPLE;
+        k_decode_simple<<<nb_plain, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, nullptr);
         break;
     }
     mark(ev, 2, s);

@@ -1,5 +1,5 @@
 // drx_encode_kernels.hip -- gfx950 (MI355X, CDNA4) ENCODE kernels of the Delta-Rice codec and their launchers
-// (round 3 split drx_kernels.hip by role: this file, drx_walk.h, drx_decode_kernels.hip).
+// (the decoders: drx_decode_kernels.hip, the header walk in front of them: drx_walk.hip).
 //
 // Format contract (bit-exact with /root/reference/src/deltaRice.c):
 //   chunk   := u32 N | { u32 n_i | u32 payload_i[n_i] }            (:415,379,427-433)

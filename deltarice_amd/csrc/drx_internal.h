@@ -48,7 +48,8 @@ struct Geom {
     uint64_t *host_words;
     uint32_t dbg;  // "debug_flags" context option (DRX_DBG_* of include/deltarice_hip.h); 0 in normal use
     // ragged batches, walk inside the decode launch: chunk indices, short-waveform chunks first
-    // (walk_short[n_short], then walk_long[n_long]), and the largest ceil(n_waves / 64) of any chunk (decode_plan_ragged())
+    // (walk_short[n_short], then walk_long[n_long]: walk_plan_ragged()), and the largest ceil(n_waves / 64) of any chunk
+    // (decode_plan_ragged())
     const uint32_t *walk_short, *walk_long;
     uint32_t n_short, n_long, max_groups;
     uint64_t max_wave_len64;  // ragged batches: 64 x the longest WaveformLength (how far apart a wavefront's 64 lines can lie)
@@ -71,7 +72,7 @@ struct Geom {
     // segment slot) of every chunk, n_chunks + 1 entries, and their total (segments_plan_ragged())
     const uint64_t *seg_unit_base;
     uint64_t seg_units;
-    // ragged batches small enough for the parallel header walks (drx_walk.h): set when the plan is made (decode_plan_ragged());
+    // ragged batches small enough for the parallel header walks (drx_walk.hip): set when the plan is made (walk_plan_ragged());
     // rag_bw_blocks_max = 4096-word blocks of the largest short-waveform chunk at 25 bits per sample
     uint32_t rag_par, rag_bw_blocks_max;
     uint32_t rag_bw_min_len;  // ... and the smallest WaveformLength among those chunks (bounds the headers of a block)
@@ -113,11 +114,33 @@ static inline void mark(hipEvent_t *ev, int i, hipStream_t s) {  // (optional pr
     if (ev) (void)hipEventRecord(ev[i], s);
 }
 
+// a chunk's worst-case word count: its header, 25 bits per sample rounded up per waveform, the waveforms' headers
+inline uint64_t chunk_max_words(uint32_t n_samples, uint32_t n_waves) { return 1u + 2ull * n_waves + (((uint64_t)n_samples * 25u + 31u) >> 5); }
+
+// The header walk in front of the decoders (drx_walk.hip): fills wave_off / wave_words and judges the chain.
+// Which parallel walks take the batch (neither: the serial walk, or the walk inside the lanes launch -- route_decode())
+struct WalkRoute {
+    bool chunk_wide, blocks;  // the chunk-wide walk, the block-parallel walk (ragged batches: both)
+    bool by_chains;           // ... the chunk-wide walk by chains, not by reading the chunks
+};
+WalkRoute route_walk(const Geom &G, bool tables_ready, bool have_scratch);
+// ragged plans: sets n_short / n_long and the parallel walks' rag_par / rag_bw_* / rag_pw_* fields; returns the host copy of
+// the walk lists (walk_short = the first n_short entries, walk_long the rest)
+std::vector<uint32_t> walk_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
+uint64_t walk_scratch_bytes(const Geom &G);  // d_pw of the launchers below (0: the batch takes neither parallel walk)
+hipError_t walk_scratch_reset(const Geom &G, void *d_pw, hipStream_t s);  // in front of the parallel walks of a call
+void launch_walk_chunk_wide(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                            uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, bool by_chains, hipStream_t s);
+void launch_walk_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s);
+void launch_walk_serial(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
+// ... no walk: the tables from the n_i table an encode left behind, checked against the stream
 hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                   const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,
                                   const uint32_t *d_list = nullptr, uint32_t n_list = 0);  // d_list: these chunks only
-// drx_decode_select (drx_select.hip): the walk over the chunks a selection touches (drx_decode_kernels.hip, where the walk
-// kernels live; select_walk_class(): which of its three lists a chunk belongs to), then a wavefront per selected waveform
+// drx_decode_select (drx_select.hip): the walk over the chunks a selection touches (select_walk_class(): which of its three
+// lists a chunk belongs to), then a wavefront per selected waveform
 int select_walk_class(uint32_t n_waves, uint32_t wave_len);
 hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                               const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain, uint32_t *d_fail,
@@ -198,10 +221,12 @@ struct SideStream {
     hipStream_t s;
     hipEvent_t fork, join;
 };
+// tables_ready: wave_off / wave_words are already filled in (the one-chunk host path walks the header chain on the CPU while the
+// chunk is in flight to the device; the side-band decode derives them from the caller's table): no walk
 // path_out (optional): which decoders the call used, DRX_PATH_* bits of include/deltarice_hip.h
 hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
                          const uint64_t *d_chunk_word_off, int16_t *d_out, uint64_t *d_wave_off,
-                         uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl,
+                         uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl, bool tables_ready,
                          void *d_pw, void *d_blk, const SideStream *side, hipEvent_t *ev, hipStream_t s, uint32_t *path_out = nullptr);
 // block-parallel decoder for batches of few waveforms (drx_blocks.hip): a workgroup per block of a waveform's stream
 bool blocks_batch(const Geom &G);
@@ -323,20 +348,9 @@ void iir_tables(const uint32_t fast_nt[3], uint32_t t0neg, uint32_t *tab);
 uint64_t iir_tiles(const Geom &G, const ChunkDesc *host_chunks, uint64_t *chunk_tile_base);  // (chunk_tile_base: n_chunks + 1, ragged only)
 hipError_t launch_iir(const Geom &G, const uint64_t *d_chunk_tile_base, uint64_t n_tiles, const uint32_t *d_tab, uint64_t *d_state,
                       const uint32_t *d_skip, DevStatus *d_status, int16_t *d_out, hipStream_t s);
-uint64_t par_walk_scratch_bytes(const Geom &G);
-uint32_t bw_walk_blocks_max(const Geom &G);
-// ragged plans: sets n_short / n_long, max_groups, max_wave_len64, rag_groups / rag_groups_long and the parallel walks' rag_*
-// fields; returns the host copies of the walk lists (walk_short = the first n_short entries, walk_long the rest) and of
-// rag_order (empty: more wavefronts than 31 bits count)
-void decode_plan_ragged(Geom &G, const ChunkDesc *host_chunks, std::vector<uint32_t> *walk_lists, std::vector<uint2> *order);
-// limits of the parallel header walks (see k_walk_parallel / k_bw_blocks)
-constexpr uint32_t kPwMaxWaves = 3584;   // waveforms per chunk the chunk-wide walk takes (leaves room for impostors)
-constexpr uint64_t kPwMaxChunks = 224;  // the walks that READ the chunks (block-parallel; the chunk-wide walk's scan form,
-                                        // DRX_DBG_WALK_BY_SCAN): more chunks hide the serial walk behind the decoding
-// the chunk-wide walk by chains (k_walk_sparse) costs ~60 us per 512 chunks whatever their size: every uniform batch of
-// long waveforms takes it, the headline's 500 chunks included (4.74 + 0.08 ms against 5.33 with the walk inside the launch)
-constexpr uint64_t kSwMaxChunks = 1u << 20;
-constexpr uint32_t kSwMinWaves = 8, kSwMaxWaves = 8192;  // ... chunks of 8 ... 8192 waveforms (its scan form: 64 ... kPwMaxWaves)
+// ragged plans: sets max_groups, max_wave_len64, rag_groups / rag_groups_long; returns rag_order's host copy (empty: more
+// wavefronts than 31 bits count)
+std::vector<uint2> decode_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 
 }  // namespace drx
 #endif

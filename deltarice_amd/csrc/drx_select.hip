@@ -2,7 +2,7 @@
 // caller's list, not 64 consecutive waveforms (k_decode_lanes) or every block of every waveform (drx_blocks.hip).
 //
 // The header tables (wave_off / wave_words) are valid for the chunks the selection touches: the host walks those chunks
-// alone (launch_select_walk(), drx_decode_kernels.hip) before this launch.
+// alone (launch_select_walk(), drx_walk.hip) before this launch.
 //
 //   k_decode_select   delta filter: one WAVEFRONT per selected waveform, the parse parallel inside the waveform by the
 //                     method of k_decode_long (a lane per 16-word segment of a 1024-word block: guess, re-synchronise from

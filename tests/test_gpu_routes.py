@@ -1,6 +1,6 @@
 """Where each encode_impl and debug flag sends a batch: drx_plan_last_encode_path / drx_plan_last_decode_path over a table
-of small batches (route_encode() in drx_api.hip, route_decode() in drx_decode_kernels.hip), with the round trip of every
-case."""
+of small batches (route_encode() in drx_api.hip, route_decode() in drx_decode_kernels.hip and, for the walk in front of the
+decoder, route_walk() in drx_walk.hip), with the round trip of every case."""
 import numpy as np
 import pytest
 
