@@ -13,7 +13,7 @@ H5FILTER = 32025
 
 def __getattr__(name):
     # torch is only needed for the device-resident API; keep `import deltarice_amd` light
-    if name in ("Context", "Plan", "EncodedBatch", "parse_opts"):
+    if name in ("Context", "Plan", "EncodedBatch", "Gathered", "parse_opts"):
         from . import codec
         return getattr(codec, name)
     raise AttributeError(name)

@@ -18,6 +18,7 @@ DRX_MAX_TAPS = 64
 # DRX_PATH_*, DRX_ENC_* and DRX_DBG_* of include/deltarice_hip.h (tests/test_abi_surface.py holds them equal)
 PATH_LANES_FUSED, PATH_LANES, PATH_BLOCKS, PATH_LONG, PATH_SIMPLE, PATH_IIR, PATH_IIR_FUSED = 1, 2, 4, 8, 16, 32, 64
 PATH_SELECT = 128
+PATH_GATHER = 256
 ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
 DBG_NO_LONG_PATHS = 256
 DBG_LONG_NOT_BLOCKS = 512
@@ -33,6 +34,7 @@ DBG_IIR_SEPARATE = 2097152
 DBG_FORCE_STREAM_SEGS = 4194304
 DBG_WALK_BY_SCAN = 8388608
 DBG_WALK_BY_CHAINS = 16777216
+DBG_GATHER_OTHER_COPY = 33554432
 
 
 class DrxOpts(C.Structure):
@@ -79,6 +81,8 @@ SIGNATURES = {
     "drx_decode_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "drx_decode_select": (C.c_int, [_vp, _vp, _u64, _vp, C.POINTER(_u64), _u64, _vp, _u64]),
     "drx_decode_select_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _vp, _u64]),
+    "drx_gather_encoded": (C.c_int, [_vp, _vp, _u64, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
+    "drx_gather_encoded_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
     "drx_estimate_words": (C.c_int, [_vp, _vp, C.POINTER(_u64)]),
     "drx_plan_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "drx_plan_finish": (C.c_int, [_vp, C.POINTER(_u64)]),

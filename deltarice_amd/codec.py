@@ -51,9 +51,56 @@ def wave_lengths(chunk_samples: Sequence[int], wave_lens: Sequence[int], wave_id
     if idx.size and int(idx.max()) >= int(base[-1]):
         raise DeltaRiceError(1, f"waveform index {int(idx.max())} out of range (the batch has {int(base[-1])})")
     g = idx.astype(np.int64)
-    c = np.searchsorted(base, g, side="right") - 1
+    if (W == W[0]).all():  # (every chunk the same number of waveforms: no search)
+        c = g // W[0]
+    else:
+        c = np.searchsorted(base, g, side="right") - 1
     i = g - base[c]
     return np.where(i + 1 == W[c], N[c] - i * L[c], L[c]).astype(np.int64)
+
+
+def gather_geometry(chunk_samples: Sequence[int], wave_lens: Sequence[int], wave_idx, chunk_waves: int):
+    """Geometry of the batch Plan.gather_encoded makes of the waveforms ``wave_idx`` names, ``chunk_waves`` to an output chunk:
+    -> (chunk_samples, wave_lens) of the result, int64 each, as Context.plan() takes them.  Output chunk c holds entries
+    [c * chunk_waves, (c + 1) * chunk_waves) of the list; its WaveformLength is its first entry's length, which every entry but
+    its last must share (the last may be shorter): a list that breaks this raises DRX_ERR_ARG.  Host arithmetic; no GPU."""
+    cw = int(chunk_waves)
+    if cw < 1:
+        raise DeltaRiceError(1, "chunk_waves must be at least 1")
+    Ns = np.asarray(chunk_samples, dtype=np.int64).reshape(-1)
+    Ls = np.asarray(wave_lens, dtype=np.int64).reshape(-1)
+    if Ns.size and Ns.size == Ls.size and Ls[0] > 0 and Ns[0] % Ls[0] == 0 and (Ns == Ns[0]).all() and (Ls == Ls[0]).all():
+        # every waveform of the batch has one length: any list at any chunking is valid, and its geometry is counting
+        idx = _as_index_array(wave_idx)
+        W = int(Ns.size * (Ns[0] // Ls[0]))
+        if idx.size and int(idx.max()) >= W:
+            raise DeltaRiceError(1, f"waveform index {int(idx.max())} out of range (the batch has {W})")
+        n_out = -(-idx.size // cw)
+        N = np.full(n_out, cw * int(Ls[0]), dtype=np.int64)
+        if n_out:
+            N[-1] = (idx.size - (n_out - 1) * cw) * int(Ls[0])
+            if int(N.max()) >= 1 << 31:
+                raise DeltaRiceError(1, f"output chunk 0 has {int(N.max())} samples (2^31 - 1 at most)")
+        return N, np.full(n_out, int(Ls[0]), dtype=np.int64)
+    lens = wave_lengths(chunk_samples, wave_lens, wave_idx)
+    n = lens.size
+    if n == 0:
+        return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    first = np.arange(0, n, cw)
+    last = np.minimum(first + cw, n) - 1
+    L = lens[first]
+    want = np.repeat(L, last - first + 1)
+    is_last = np.zeros(n, dtype=bool)
+    is_last[last] = True
+    bad = np.nonzero((lens > want) | ((lens < want) & ~is_last))[0]
+    if bad.size:
+        e = int(bad[0])
+        raise DeltaRiceError(1, f"entry {e} has {int(lens[e])} samples, output chunk {e // cw}'s first has {int(want[e])}"
+                                + ("" if lens[e] > want[e] else " and it is not the chunk's last"))
+    N = np.add.reduceat(lens, first)
+    if int(N.max()) >= 1 << 31:
+        raise DeltaRiceError(1, f"output chunk {int(N.argmax())} has {int(N.max())} samples (2^31 - 1 at most)")
+    return N.astype(np.int64), L.astype(np.int64)
 
 
 def _as_index_array(wave_idx) -> np.ndarray:
@@ -86,6 +133,27 @@ class EncodedBatch:
     def to_numpy(self):
         w = self.words[:self.total_words].cpu().numpy().view(np.uint32)
         return w, self.chunk_word_off.cpu().numpy().astype(np.uint64)
+
+
+@dataclass
+class Gathered:
+    """What Plan.gather_encoded returns: a new encoded batch made of selected waveforms, and all that is needed to use it."""
+    enc: EncodedBatch             # the chunks, back to back, with their offset table
+    chunk_samples: np.ndarray     # int64 [n_out_chunks]: N_c of every output chunk ...
+    wave_lens: np.ndarray         # ... and its WaveformLength (what Context.plan() takes)
+    wave_words: torch.Tensor      # int32 [n_sel] on the device: n_i of every entry, the result's side-band
+    rice_m: int                   # the source plan's RiceParameter ...
+    taps: Optional[tuple]         # ... and prediction filter (None: delta)
+
+    def plan(self, ctx: "Context") -> "Plan":
+        """The plan of the result: its own geometry, the source's RiceParameter and filter."""
+        N, L = self.chunk_samples, self.wave_lens
+        if N.size == 0:
+            raise DeltaRiceError(1, "an empty selection has no plan")
+        if (N == N[0]).all() and (L == L[0]).all():
+            ftaps = (len(self.taps),) + tuple(int(t) & 0xFFFFFFFF for t in self.taps) if self.taps else ()
+            return ctx.plan_uniform(int(N.size), int(N[0]), (self.rice_m, int(L[0])) + ftaps)
+        return ctx.plan(N.tolist(), L.tolist(), self.rice_m, self.taps)
 
 
 class Context:
@@ -126,8 +194,10 @@ class Context:
         L = 0 if o.wave_len < 0 else int(o.wave_len)
         self._check(self.lib.drx_plan_create_uniform(self._h, n_chunks, chunk_samples, L, o.rice_k, C.byref(h)))
         plan = Plan(self, h, np.full(n_chunks, chunk_samples, dtype=np.int64), np.full(n_chunks, L, dtype=np.int64))
+        plan._rice_m = 1 << o.rice_k
         if not _is_delta(o):  # general prediction filter: GPU FIR/IIR kernels (correct, not tuned)
             self._check(self.lib.drx_plan_set_filter(h, o.n_taps, o.taps))
+            plan._taps = tuple(int(o.taps[i]) for i in range(o.n_taps))
         return plan
 
     def plan(self, chunk_samples: Sequence[int], wave_lens: Sequence[int], rice_m: int = 8,
@@ -143,9 +213,11 @@ class Context:
         h = C.c_void_p()
         self._check(self.lib.drx_plan_create(self._h, n, cs, wl, o.rice_k, C.byref(h)))
         plan = Plan(self, h, list(cs), list(wl))
+        plan._rice_m = 1 << o.rice_k
         if taps is not None:
             t = (C.c_int32 * len(taps))(*[int(v) for v in taps])
             self._check(self.lib.drx_plan_set_filter(h, len(taps), t))
+            plan._taps = tuple(int(v) for v in t)
         return plan
 
     def filter_chunk(self, data: bytes | np.ndarray, opts: Sequence[int] = (), reverse: bool = False) -> bytes:
@@ -171,6 +243,7 @@ class Plan:
         # the batch's geometry as the plan was made from it (wave_lengths(), decode_select's row stride)
         self._chunk_samples = np.asarray(chunk_samples, dtype=np.int64)
         self._wave_lens = np.asarray(wave_lens, dtype=np.int64)
+        self._rice_m, self._taps = 8, None  # (Context.plan / plan_uniform set them: what Gathered.plan() carries over)
         lib = ctx.lib
         self.n_chunks = int(lib.drx_plan_n_chunks(handle))
         self.total_samples = int(lib.drx_plan_total_samples(handle))
@@ -308,6 +381,67 @@ class Plan:
                                      wave_words=wave_words)
         self.finish()
         return y
+
+    def gather_encoded_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, wave_idx, chunk_waves: int,
+                             out_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
+                             wave_words: Optional[torch.Tensor] = None, out_chunk_word_off: Optional[torch.Tensor] = None,
+                             out_wave_words: Optional[torch.Tensor] = None):
+        """Launches drx_gather_encoded on the context's stream: the waveforms ``wave_idx`` names (as decode_select takes
+        them), ``chunk_waves`` to an output chunk, copied -- not decoded -- into ``out_words`` (int32, its numel the capacity).
+        out_words None: the SIZING call, which writes the two tables only; finish() then returns the words needed.
+        -> (out_words, out_chunk_word_off int64 [n_out_chunks + 1], out_wave_words int32 [n_sel]).  finish() raises on
+        device-side errors (DRX_ERR_CAPACITY: nothing was written; DRX_ERR_CORRUPT: a touched chunk failed validation)."""
+        idx = _as_index_array(wave_idx)
+        n_sel, cw = int(idx.size), int(chunk_waves)
+        n_out = -(-n_sel // cw) if cw > 0 else 0
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        if out_words is not None:
+            self._dev_check(out_words, torch.int32, 0, "out_words")
+        if out_chunk_word_off is None:
+            out_chunk_word_off = torch.empty(n_out + 1, dtype=torch.int64, device=self.ctx.device)
+        self._dev_check(out_chunk_word_off, torch.int64, n_out + 1, "out_chunk_word_off")
+        if out_wave_words is None:
+            out_wave_words = torch.empty(n_sel, dtype=torch.int32, device=self.ctx.device)
+        self._dev_check(out_wave_words, torch.int32, n_sel, "out_wave_words")
+        n = words.numel() if in_words is None else int(in_words)
+        ip = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
+        lib = self.ctx.lib
+        if wave_words is None:
+            st = lib.drx_gather_encoded(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), ip, n_sel, cw, op, cap,
+                                        out_chunk_word_off.data_ptr(), out_wave_words.data_ptr() if n_sel else None)
+        else:
+            st = lib.drx_gather_encoded_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
+                                                        wave_words.data_ptr(), ip, n_sel, cw, op, cap,
+                                                        out_chunk_word_off.data_ptr(), out_wave_words.data_ptr() if n_sel else None)
+        self.ctx._check(st)
+        return out_words, out_chunk_word_off, out_wave_words
+
+    def gather_encoded(self, enc: EncodedBatch, wave_idx, chunk_waves: int, wave_words: Optional[torch.Tensor] = None,
+                       out_words: Optional[torch.Tensor] = None) -> Gathered:
+        """A new encoded batch of the waveforms ``wave_idx`` names (any order, duplicates allowed), ``chunk_waves`` to a chunk,
+        without decoding them: byte for byte what encode() gives for the gathered samples under this plan's RiceParameter and
+        filter.  Every output chunk needs one WaveformLength (gather_geometry()).  out_words None: sized by a first call and
+        allocated exactly (the second call resumes from the first one's tables: one walk, one scan); otherwise
+        DRX_ERR_CAPACITY if the result does not fit it.  Waits, and raises like decode()."""
+        idx = _as_index_array(wave_idx)
+        N, L = gather_geometry(self._chunk_samples, self._wave_lens, idx, chunk_waves)
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        if idx.size == 0:
+            off = torch.zeros(1, dtype=torch.int64, device=self.ctx.device)
+            tab = torch.empty(0, dtype=torch.int32, device=self.ctx.device)
+            out_words = torch.empty(0, dtype=torch.int32, device=self.ctx.device) if out_words is None else out_words
+            return Gathered(EncodedBatch(out_words, off, 0), N, L, tab, self._rice_m, self._taps)
+        off = tab = None
+        if out_words is None:
+            _, off, tab = self.gather_encoded_async(enc.words, enc.chunk_word_off, idx, chunk_waves, None, enc.total_words, wave_words)
+            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
+        _, off, tab = self.gather_encoded_async(enc.words, enc.chunk_word_off, idx, chunk_waves, out_words, enc.total_words,
+                                                wave_words, off, tab)
+        return Gathered(EncodedBatch(out_words, off, self.finish()), N, L, tab, self._rice_m, self._taps)
 
     def estimate_words(self, x: torch.Tensor) -> np.ndarray:
         """Exact encoded size (uint32 words) of this batch for RiceParameter 2^k, k = 0..15 -- the

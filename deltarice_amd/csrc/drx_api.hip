@@ -133,6 +133,19 @@ struct drx_plan {
     size_t sel_cap = 0;                       // ... bytes of each
     uint32_t *d_sel_fail = nullptr;           // uint32[n_chunks]: chunks the chunk-wide walk handed to the scalar walker
     hipEvent_t sel_copied = nullptr;          // the staging buffer has crossed to the device (the next call may fill it again)
+    void *d_gat = nullptr;                    // drx_gather_encoded: positions, sizes and scan state (gather_scratch())
+    size_t gat_cap = 0;
+    // ... and what the plan's last call was asked IF that call was a gather's SIZING call (d_out == NULL: it wrote no output): its
+    // list is still in h_sel / d_sel, its tables (the walk's, sizes, scanned block sums, total and verdict) in d_wave_* / d_gat.
+    // The gather with the same arguments right behind it resumes from them, once.  `valid` is cleared by every other call on the
+    // plan that launches or writes one of those buffers, by a gather that regrows h_sel / d_gat (so a valid key always fits the
+    // buffers it describes), and by the resumed call itself: no call that copied anything is ever resumed from
+    struct GatherKey {
+        bool valid = false;
+        const uint32_t *d_in = nullptr, *d_sideband = nullptr;
+        const uint64_t *d_off = nullptr;
+        uint64_t in_words = 0, n_sel = 0, cw = 0;
+    } gat_last;
 };
 
 static drx_status fail(drx_ctx *ctx, drx_status st, const char *fmt, ...) {
@@ -169,6 +182,70 @@ template <typename T> static hipError_t upload(drx_plan *p, const T *host, size_
 }
 template <typename T> static hipError_t upload(drx_plan *p, const std::vector<T> &tab, const T **view) {
     return upload(p, tab.data(), tab.size(), view);
+}
+
+// What a selection asks of the plan: every entry's chunk and length (arithmetic for a uniform plan, a bisection of the host's
+// chunk table for a ragged one) handed to per_entry(i, chunk, len), which may refuse the list; and the sorted set of chunks the
+// selection touches as the walk takes them -- three lists, each sorted (select_walk_class()); the side-band takes them as one.
+template <typename F>
+static drx_status sel_survey(drx_plan *p, const char *who, const uint64_t *wave_idx, uint64_t n_sel, bool sideband,
+                             std::vector<uint32_t> &lists, uint32_t n_class[3], F &&per_entry) {
+    drx_ctx *ctx = p->ctx;
+    const Geom &G = p->G;
+    const bool small = G.total_waves <= 0xffffffffull;
+    auto chunk_of = [&](uint64_t g, uint32_t *len) -> uint64_t {
+        uint64_t c, idx;
+        uint32_t W, L, N;
+        if (G.uniform) {
+            c = small ? (uint32_t)g / G.u_n_waves : g / G.u_n_waves;  // (a million entries: the 32-bit division is a third of the loop)
+            idx = g - c * G.u_n_waves;
+            W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples;
+        } else {
+            uint64_t lo = 0, hi = G.n_chunks;  // invariant: wave_base[lo] <= g < wave_base[hi]
+            while (hi - lo > 1) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (p->host_chunks[mid].wave_base <= g) lo = mid; else hi = mid;
+            }
+            const ChunkDesc &d = p->host_chunks[c = lo];
+            idx = g - d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples;
+        }
+        *len = idx + 1 == W ? N - (uint32_t)idx * L : L;
+        return c;
+    };
+    // a flag per chunk for large selections, sort + unique for small ones
+    std::vector<uint32_t> touched;
+    std::vector<uint8_t> flag;
+    const bool by_flag = n_sel > G.n_chunks / 8u;
+    if (by_flag) flag.assign(G.n_chunks, 0);
+    else touched.reserve(n_sel);
+    for (uint64_t i = 0; i < n_sel; ++i) {
+        if (wave_idx[i] >= G.total_waves)
+            return fail(ctx, DRX_ERR_ARG, "%s: entry %llu is waveform %llu of %llu", who, (unsigned long long)i,
+                        (unsigned long long)wave_idx[i], (unsigned long long)G.total_waves);
+        uint32_t len;
+        const uint64_t c = chunk_of(wave_idx[i], &len);
+        if (const drx_status st = per_entry(i, c, len)) return st;
+        if (by_flag) flag[c] = 1;
+        else touched.push_back((uint32_t)c);
+    }
+    if (by_flag) {
+        for (uint64_t c = 0; c < G.n_chunks; ++c) if (flag[c]) touched.push_back((uint32_t)c);
+    } else {
+        std::sort(touched.begin(), touched.end());
+        touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
+    }
+    n_class[0] = n_class[1] = n_class[2] = 0;
+    lists.assign(touched.size(), 0);
+    if (sideband) {
+        lists = touched;
+    } else {
+        auto cls = [&](uint32_t c) { return G.uniform ? select_walk_class(G.u_n_waves, G.u_wave_len)
+                                                      : select_walk_class(p->host_chunks[c].n_waves, p->host_chunks[c].wave_len); };
+        for (uint32_t c : touched) ++n_class[cls(c)];
+        uint32_t at[3] = {0, n_class[0], n_class[0] + n_class[1]};
+        for (uint32_t c : touched) lists[at[cls(c)]++] = c;
+    }
+    return DRX_OK;
 }
 
 extern "C" {
@@ -497,6 +574,7 @@ drx_status drx_plan_set_filter(drx_plan *p, uint32_t n_taps, const int32_t *taps
     DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     Geom &G = p->G;
     p->enc_words_per_wave = 0;  // (another filter, another code length: what the last encode measured no longer applies)
+    p->gat_last.valid = false;
     *G.host_words = 0;
     G.fast_taps = 0;
     G.enc_fast = 0;
@@ -646,6 +724,7 @@ drx_status drx_encode(drx_plan *p, const int16_t *d_in, uint32_t *d_out, uint64_
     if (!p || !d_in || !d_out || !d_chunk_word_off) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
     DRX_ON_DEVICE(ctx);
+    p->gat_last.valid = false;
     DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
     p->G.dbg = ctx->debug_flags;
     // what the plan's last encode measured decides this one's kernel -- read from the word the encoders write to pinned host
@@ -686,6 +765,7 @@ static drx_status decode_launch(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     if (!p || !d_in || !d_chunk_word_off || !d_out) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
     DRX_ON_DEVICE(ctx);
+    p->gat_last.valid = false;
     DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
     p->G.dbg = ctx->debug_flags;
     // (in_words says nothing about how long a waveform's code is -- it may be, and in bench.py IS, the buffer's capacity; round 4
@@ -755,61 +835,16 @@ static drx_status decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
     if (n_sel >= (1ull << 32)) return fail(ctx, DRX_ERR_ARG, "decode_select: %llu entries (at most 2^32 - 1)", (unsigned long long)n_sel);
     const Geom &G = p->G;
-    // the chunk and the length of every selected waveform: arithmetic (uniform) or a bisection of the host's chunk table
-    auto chunk_of = [&](uint64_t g, uint32_t *len) -> uint64_t {
-        uint64_t c, idx;
-        uint32_t W, L, N;
-        if (G.uniform) {
-            c = g / G.u_n_waves; idx = g - c * G.u_n_waves;
-            W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples;
-        } else {
-            uint64_t lo = 0, hi = G.n_chunks;  // invariant: wave_base[lo] <= g < wave_base[hi]
-            while (hi - lo > 1) {
-                const uint64_t mid = (lo + hi) >> 1;
-                if (p->host_chunks[mid].wave_base <= g) lo = mid; else hi = mid;
-            }
-            const ChunkDesc &d = p->host_chunks[c = lo];
-            idx = g - d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples;
-        }
-        *len = idx + 1 == W ? N - (uint32_t)idx * L : L;
-        return c;
-    };
-    // the sorted set of chunks the selection touches: a flag per chunk for large selections, sort + unique for small ones
-    std::vector<uint32_t> touched;
-    std::vector<uint8_t> flag;
-    const bool by_flag = n_sel > G.n_chunks / 8u;
-    if (by_flag) flag.assign(G.n_chunks, 0);
-    else touched.reserve(n_sel);
     uint32_t longest = 0;
-    for (uint64_t i = 0; i < n_sel; ++i) {
-        if (wave_idx[i] >= G.total_waves)
-            return fail(ctx, DRX_ERR_ARG, "decode_select: entry %llu is waveform %llu of %llu", (unsigned long long)i,
-                        (unsigned long long)wave_idx[i], (unsigned long long)G.total_waves);
-        uint32_t len;
-        const uint64_t c = chunk_of(wave_idx[i], &len);
-        longest = std::max(longest, len);
-        if (by_flag) flag[c] = 1;
-        else touched.push_back((uint32_t)c);
-    }
+    uint32_t n_class[3];
+    std::vector<uint32_t> lists;
+    if (const drx_status st = sel_survey(p, "decode_select", wave_idx, n_sel, sideband, lists, n_class, [&](uint64_t, uint64_t, uint32_t len) {
+            longest = std::max(longest, len);
+            return DRX_OK;
+        }))
+        return st;
+    p->gat_last.valid = false;
     if (stride < longest) return fail(ctx, DRX_ERR_ARG, "decode_select: row stride %llu below the longest selected waveform (%u)", (unsigned long long)stride, longest);
-    if (by_flag) {
-        for (uint64_t c = 0; c < G.n_chunks; ++c) if (flag[c]) touched.push_back((uint32_t)c);
-    } else {
-        std::sort(touched.begin(), touched.end());
-        touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
-    }
-    // ... as the walk takes them: three lists, each sorted (select_walk_class()); the side-band takes them as one
-    uint32_t n_class[3] = {0, 0, 0};
-    std::vector<uint32_t> lists(touched.size());
-    if (sideband) {
-        lists = touched;
-    } else {
-        auto cls = [&](uint32_t c) { return G.uniform ? select_walk_class(G.u_n_waves, G.u_wave_len)
-                                                      : select_walk_class(p->host_chunks[c].n_waves, p->host_chunks[c].wave_len); };
-        for (uint32_t c : touched) ++n_class[cls(c)];
-        uint32_t at[3] = {0, n_class[0], n_class[0] + n_class[1]};
-        for (uint32_t c : touched) lists[at[cls(c)]++] = c;
-    }
     DRX_ON_DEVICE(ctx);
     const size_t sel_bytes = n_sel * sizeof(uint64_t), bytes = sel_bytes + lists.size() * sizeof(uint32_t);
     if (const drx_status st = sel_scratch(p, bytes)) return st;
@@ -842,13 +877,165 @@ static drx_status decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_w
 
 drx_status drx_decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                              const uint64_t *wave_idx, uint64_t n_sel, int16_t *d_out, uint64_t out_stride_samples) {
-    return decode_select(p, d_in, in_words, d_chunk_word_off, nullptr, false, wave_idx, n_sel, d_out, out_stride_samples);
+    try {
+        return decode_select(p, d_in, in_words, d_chunk_word_off, nullptr, false, wave_idx, n_sel, d_out, out_stride_samples);
+    } catch (const std::bad_alloc &) { return fail(p->ctx, DRX_ERR_NOMEM, "decode_select: host memory for a list of %llu entries", (unsigned long long)n_sel); }
 }
 
 drx_status drx_decode_select_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                              const uint32_t *d_wave_words, const uint64_t *wave_idx, uint64_t n_sel,
                                              int16_t *d_out, uint64_t out_stride_samples) {
-    return decode_select(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, wave_idx, n_sel, d_out, out_stride_samples);
+    try {
+        return decode_select(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, wave_idx, n_sel, d_out, out_stride_samples);
+    } catch (const std::bad_alloc &) { return fail(p->ctx, DRX_ERR_NOMEM, "decode_select: host memory for a list of %llu entries", (unsigned long long)n_sel); }
+}
+
+// ---------------------------------------------------------------------------
+// selected waveforms into a new encoded batch (drx_gather.hip)
+// ---------------------------------------------------------------------------
+// The gather's device-only scratch beside the selection's: uint64 ent_pos[n_sel] | uint64 block_sum[blocks + 2] | uint32
+// ent_words[n_sel] | uint32 ctrl[1]; grown like the selection's.
+static drx_status gather_scratch(drx_plan *p, size_t bytes) {
+    drx_ctx *ctx = p->ctx;
+    if (p->gat_cap >= bytes) return DRX_OK;
+    const size_t want = bytes + bytes / 4 + 4096;
+    void *d = nullptr;
+    const hipError_t e = p->mem.alloc(&d, want);
+    if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "gather scratch of %zu bytes: %s", want, hipGetErrorString(e));
+    DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier gather may still use the old one)
+    p->mem.release(p->d_gat);
+    p->d_gat = d;
+    p->gat_cap = want;
+    return DRX_OK;
+}
+
+// mean words per entry from which the copy is a wavefront per entry; below, a workgroup per run of entries
+constexpr uint64_t kGatherWavesFromWords = 192;
+
+static drx_status gather_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                 const uint32_t *d_sideband, bool sideband, const uint64_t *wave_idx, uint64_t n_sel,
+                                 uint64_t cw, uint32_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint32_t *d_out_wave_words) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (cw == 0) return fail(ctx, DRX_ERR_ARG, "gather_encoded: out_chunk_waves is 0");
+    if (n_sel == 0) return DRX_OK;
+    if (!d_in || !d_chunk_word_off || !wave_idx || !d_out_off || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "gather_encoded: null pointer");
+    if (!d_out && out_cap) return fail(ctx, DRX_ERR_ARG, "gather_encoded: no output buffer but a capacity of %llu words", (unsigned long long)out_cap);
+    if (sideband && (d_sideband == p->d_wave_words || d_out_wave_words == d_sideband))
+        return fail(ctx, DRX_ERR_ARG, "the side-band table must be neither the plan's own nor the output's (copy it first)");
+    if (n_sel >= (1ull << 32)) return fail(ctx, DRX_ERR_ARG, "gather_encoded: %llu entries (at most 2^32 - 1)", (unsigned long long)n_sel);
+    const Geom &G = p->G;
+    const uint64_t n_out = (n_sel + cw - 1) / cw, blocks = gather_scan_blocks(n_sel);
+    const size_t sel_bytes = n_sel * sizeof(uint64_t), cn_bytes = n_out * sizeof(uint32_t);
+    // the copy's form by the batch's mean code length (in_words may be a capacity: a speed matter only, like the grid's shape)
+    const uint64_t mean_words = in_words / G.total_waves;
+    const bool tiles = (mean_words < kGatherWavesFromWords) != ((ctx->debug_flags & DRX_DBG_GATHER_OTHER_COPY) != 0);
+    // The call behind a SIZING call: the same stream, tables and list as the plan's last call, which wrote no output.  The scalar
+    // key first, then the list word for word against the staged one (only then: 8 MB at 10^6 entries); the walk and the sizes are
+    // not repeated.  One resume per sizing call: a call that has copied is never a source of tables.
+    const drx_plan::GatherKey K = p->gat_last;
+    p->gat_last.valid = false;
+    if (K.valid && d_out && K.d_in == d_in && K.in_words == in_words && K.d_off == d_chunk_word_off && K.d_sideband == (sideband ? d_sideband : nullptr) &&
+        K.n_sel == n_sel && K.cw == cw && memcmp(p->h_sel, wave_idx, sel_bytes) == 0) {
+        DRX_ON_DEVICE(ctx);
+        DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+        hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
+        uint64_t *d_ent_pos = (uint64_t *)p->d_gat, *d_block_sum = d_ent_pos + n_sel;
+        uint32_t *d_ent_words = (uint32_t *)(d_block_sum + blocks + 2), *d_ctrl = d_ent_words + n_sel;
+        mark(ev, 0, ctx->stream);
+        mark(ev, 1, ctx->stream);
+        DRX_HIP(ctx, launch_gather(G, d_in, p->d_wave_off, p->d_wave_words, (const uint64_t *)p->d_sel, n_sel, cw,
+                                   (const uint32_t *)((const char *)p->d_sel + sel_bytes), d_out, out_cap, d_out_off, d_out_wave_words, d_ent_words,
+                                   d_ent_pos, d_block_sum, d_ctrl, tiles, mean_words, /*resume*/ true, p->d_status, ev, ctx->stream));
+        mark(ev, 3, ctx->stream);
+        p->last_path = DRX_PATH_GATHER;
+        p->ev_valid = ctx->profile != 0;
+        p->last_was_encode = false;
+        return DRX_OK;
+    }
+    // every output chunk is a chunk under ONE WaveformLength (its first entry's; only its last entry may be shorter) of fewer
+    // than 2^31 samples (src/deltaRice.c:389); chunk_n[c] = its sample count N_c
+    std::vector<uint32_t> chunk_n(n_out);
+    uint32_t first = 0, n_class[3];
+    uint64_t left = 0, sum = 0, oc = ~0ull;  // entries left in the current output chunk, its samples so far, its number
+    bool closed = false;         // a shorter entry has been seen: it must be the chunk's last
+    std::vector<uint32_t> lists;
+    if (const drx_status st = sel_survey(p, "gather_encoded", wave_idx, n_sel, sideband, lists, n_class, [&](uint64_t i, uint64_t, uint32_t len) {
+            if (left == 0) { left = cw; first = len; sum = 0; closed = false; ++oc; }
+            if (closed)
+                return fail(ctx, DRX_ERR_ARG, "gather_encoded: entry %llu is shorter than output chunk %llu's first (%u samples) and not its last",
+                            (unsigned long long)(i - 1), (unsigned long long)oc, first);
+            if (len > first)
+                return fail(ctx, DRX_ERR_ARG, "gather_encoded: entry %llu has %u samples, output chunk %llu's first has %u",
+                            (unsigned long long)i, len, (unsigned long long)oc, first);
+            closed = len < first;
+            sum += len;
+            if (sum >= (1ull << 31))
+                return fail(ctx, DRX_ERR_ARG, "gather_encoded: output chunk %llu reaches 2^31 samples at entry %llu", (unsigned long long)oc,
+                            (unsigned long long)i);
+            chunk_n[oc] = (uint32_t)sum;
+            --left;
+            return DRX_OK;
+        }))
+        return st;
+    DRX_ON_DEVICE(ctx);
+    // staging: uint64 sel[n_sel] | uint32 chunk_n[n_out] | uint32 chunk lists[touched]
+    const size_t bytes = sel_bytes + cn_bytes + lists.size() * sizeof(uint32_t);
+    if (const drx_status st = sel_scratch(p, bytes)) return st;
+    const size_t pos_bytes = n_sel * sizeof(uint64_t), bs_bytes = blocks * sizeof(uint64_t), ew_bytes = n_sel * sizeof(uint32_t);
+    if (const drx_status st = gather_scratch(p, pos_bytes + bs_bytes + 2 * sizeof(uint64_t) + ew_bytes + sizeof(uint32_t))) return st;
+    DRX_HIP(ctx, hipEventSynchronize(p->sel_copied));  // (the last call's copy out of the staging buffer)
+    memcpy(p->h_sel, wave_idx, sel_bytes);
+    memcpy((char *)p->h_sel + sel_bytes, chunk_n.data(), cn_bytes);
+    memcpy((char *)p->h_sel + sel_bytes + cn_bytes, lists.data(), lists.size() * sizeof(uint32_t));
+    DRX_HIP(ctx, hipMemcpyAsync(p->d_sel, p->h_sel, bytes, hipMemcpyHostToDevice, ctx->stream));
+    DRX_HIP(ctx, hipEventRecord(p->sel_copied, ctx->stream));
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
+    const uint64_t *d_sel = (const uint64_t *)p->d_sel;
+    const uint32_t *d_chunk_n = (const uint32_t *)((const char *)p->d_sel + sel_bytes);
+    const uint32_t *d_lists = d_chunk_n + n_out;
+    uint64_t *d_ent_pos = (uint64_t *)p->d_gat, *d_block_sum = d_ent_pos + n_sel;
+    uint32_t *d_ent_words = (uint32_t *)(d_block_sum + blocks + 2), *d_ctrl = d_ent_words + n_sel;  // (block_sum[blocks .. +2): total, status)
+    mark(ev, 0, ctx->stream);
+    if (sideband)
+        DRX_HIP(ctx, launch_sideband_tables(G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words, p->d_status,
+                                            ctx->stream, d_lists, (uint32_t)lists.size()));
+    else
+        DRX_HIP(ctx, launch_select_walk(G, d_in, in_words, d_chunk_word_off, d_lists, n_class[0], n_class[1], n_class[2], p->d_sel_fail,
+                                        p->d_wave_off, p->d_wave_words, p->d_status, ctx->stream));
+    mark(ev, 1, ctx->stream);
+    DRX_HIP(ctx, launch_gather(G, d_in, p->d_wave_off, p->d_wave_words, d_sel, n_sel, cw, d_chunk_n, d_out, out_cap, d_out_off,
+                               d_out_wave_words, d_ent_words, d_ent_pos, d_block_sum, d_ctrl, tiles, mean_words, /*resume*/ false, p->d_status, ev,
+                               ctx->stream));
+    mark(ev, 3, ctx->stream);
+    p->gat_last.valid = d_out == nullptr;
+    p->gat_last.d_in = d_in; p->gat_last.in_words = in_words; p->gat_last.d_off = d_chunk_word_off;
+    p->gat_last.d_sideband = sideband ? d_sideband : nullptr; p->gat_last.n_sel = n_sel; p->gat_last.cw = cw;
+    p->last_path = DRX_PATH_GATHER;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+drx_status drx_gather_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const uint64_t *wave_idx, uint64_t n_sel, uint64_t out_chunk_waves, uint32_t *d_out,
+                              uint64_t out_cap_words, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words) {
+    try {
+        return gather_encoded(p, d_in, in_words, d_chunk_word_off, nullptr, false, wave_idx, n_sel, out_chunk_waves, d_out, out_cap_words,
+                              d_out_chunk_word_off, d_out_wave_words);
+    } catch (const std::bad_alloc &) { return fail(p->ctx, DRX_ERR_NOMEM, "gather_encoded: host memory for a list of %llu entries", (unsigned long long)n_sel); }
+}
+
+drx_status drx_gather_encoded_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                              const uint32_t *d_wave_words, const uint64_t *wave_idx, uint64_t n_sel,
+                                              uint64_t out_chunk_waves, uint32_t *d_out, uint64_t out_cap_words,
+                                              uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words) {
+    try {
+        return gather_encoded(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, wave_idx, n_sel, out_chunk_waves, d_out, out_cap_words,
+                              d_out_chunk_word_off, d_out_wave_words);
+    } catch (const std::bad_alloc &) { return fail(p->ctx, DRX_ERR_NOMEM, "gather_encoded: host memory for a list of %llu entries", (unsigned long long)n_sel); }
 }
 
 // Header chain of ONE encoded chunk in host memory (src/deltaRice.c:320-325), with the validation the device

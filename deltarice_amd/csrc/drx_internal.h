@@ -148,6 +148,15 @@ hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_w
 hipError_t launch_decode_select(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
                                 const uint64_t *d_sel, uint64_t n_sel, DevStatus *d_status, int16_t *d_out, uint64_t stride,
                                 hipStream_t s);
+// drx_gather_encoded (drx_gather.hip): behind the same walk, sizes + scan + offsets, then the copy of the entries' word ranges
+// (tiles: a workgroup per run of short entries; otherwise a wavefront per entry, or per piece of a long one; resume: the walk's
+// tables, the sizes and the scanned block sums of the last call with this list are still in place -- the call behind a sizing call)
+uint64_t gather_scan_blocks(uint64_t n_sel);
+hipError_t launch_gather(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
+                         const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves, const uint32_t *d_chunk_samples,
+                         uint32_t *d_out, uint64_t out_cap, uint64_t *d_out_chunk_off, uint32_t *d_out_wave_words,
+                         uint32_t *d_ent_words, uint64_t *d_ent_pos, uint64_t *d_block_sum, uint32_t *d_ctrl, bool tiles,
+                         uint64_t mean_words, bool resume, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 
 // wide: fused_wide() as the route decided it

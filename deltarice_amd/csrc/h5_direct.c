@@ -12,6 +12,7 @@
 #include <stdio.h>
 #include <unistd.h>
 #include <stdlib.h>
+#include <sys/stat.h>
 #include <string.h>
 #include <time.h>
 
@@ -340,18 +341,91 @@ static int cmp_u64(const void *a, const void *b) {
     return x < y ? -1 : (x > y ? 1 : 0);
 }
 
+/* What drx_h5_read_rows and drx_h5_copy_rows fetch: the stored bytes of the chunks the rows lie in, on the device, and the rows
+ * as waveform indices of a uniform plan over those chunks. */
+typedef struct {
+    uint64_t *touched, *h_off, *d_off, *wave_idx;  /* sorted chunk numbers; word offsets (host, device); n_rows * wpr indices */
+    void *d_words;
+    uint64_t n_touched, words, wpr;  /* chunks fetched, their words; waveforms per row (set by the caller) */
+    double t_file, t_pcie;
+} fetched_t;
+static void free_fetched(fetched_t *fx) {
+    if (fx->d_words) (void)hipFree(fx->d_words);
+    if (fx->d_off) (void)hipFree(fx->d_off);
+    free(fx->touched);
+    free(fx->wave_idx);
+    free(fx->h_off);
+    memset(fx, 0, sizeof *fx);
+}
+/* ds: an open dataset whose rows are whole waveforms (fx->wpr of them, set by the caller); n_rows >= 1, every
+ * row below the dataset's.  On failure the caller frees whatever was allocated. */
+static drx_status fetch_rows_chunks(drx_ctx *ctx, dataset_t *ds, const uint64_t *rows, uint64_t n_rows, fetched_t *fx) {
+    const uint64_t chunk_rows = ds->chunk[0], wpr = fx->wpr;
+    void *h_words = NULL;  /* (the context's staging buffer, not freed here) */
+    double t0 = now();
+    /* the sorted set of chunks the rows lie in (HDF5 stores a padded last chunk full size: the same geometry as the others) */
+    fx->touched = (uint64_t *)malloc(n_rows * sizeof(uint64_t));
+    fx->wave_idx = (uint64_t *)malloc(n_rows * wpr * sizeof(uint64_t));
+    if (!fx->touched || !fx->wave_idx) return DRX_ERR_NOMEM;
+    uint64_t *touched = fx->touched;
+    for (uint64_t i = 0; i < n_rows; ++i) touched[i] = rows[i] / chunk_rows;
+    qsort(touched, n_rows, sizeof(uint64_t), cmp_u64);
+    uint64_t n_touched = 0;
+    for (uint64_t i = 0; i < n_rows; ++i) if (!n_touched || touched[n_touched - 1] != touched[i]) touched[n_touched++] = touched[i];
+    fx->n_touched = n_touched;
+    /* their stored sizes -> offsets -> the context's staging buffer <- their stored bytes */
+    uint64_t *h_off = fx->h_off = (uint64_t *)malloc((n_touched + 1) * sizeof(uint64_t));
+    if (!h_off) return DRX_ERR_NOMEM;
+    uint64_t words = 0;
+    for (uint64_t t = 0; t < n_touched; ++t) {
+        hsize_t off[2] = {touched[t] * chunk_rows, 0}, nb = 0;
+        if (H5Dget_chunk_storage_size(ds->d, off, &nb) < 0 || (nb & 3)) return DRX_ERR_CORRUPT;
+        if (nb == 0) return DRX_ERR_UNSUPPORTED;  /* a chunk that was never written (fill value): not a stored stream */
+        h_off[t] = words;
+        words += nb / 4;
+    }
+    h_off[n_touched] = words;
+    fx->words = words;
+    if (drx_ctx_host_staging(ctx, words * 4, &h_words) != DRX_OK) return DRX_ERR_NOMEM;
+    for (uint64_t t = 0; t < n_touched; ++t) {
+        hsize_t off[2] = {touched[t] * chunk_rows, 0};
+        uint32_t mask = 0;
+        if (H5Dread_chunk(ds->d, H5P_DEFAULT, off, &mask, (uint32_t *)h_words + h_off[t]) < 0 || mask) return DRX_ERR_CORRUPT;
+    }
+    fx->t_file = now() - t0;
+
+    t0 = now();
+    hipStream_t stream = (hipStream_t)drx_ctx_stream(ctx);
+    if (hipMalloc(&fx->d_words, words * 4) != hipSuccess || hipMalloc((void **)&fx->d_off, (n_touched + 1) * 8) != hipSuccess) return DRX_ERR_NOMEM;
+    if (hipMemcpyAsync(fx->d_words, h_words, words * 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipMemcpyAsync(fx->d_off, h_off, (n_touched + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) return DRX_ERR_DEVICE;
+    fx->t_pcie = now() - t0;
+
+    /* a plan over the fetched chunks; row r = waveforms (local row) * wpr ... of chunk number (its place among the fetched) */
+    for (uint64_t i = 0; i < n_rows; ++i) {
+        const uint64_t c = rows[i] / chunk_rows, lr = rows[i] % chunk_rows;
+        uint64_t lo = 0, hi = n_touched;  /* invariant: touched[lo] <= c < touched[hi] */
+        while (hi - lo > 1) {
+            const uint64_t mid = (lo + hi) >> 1;
+            if (touched[mid] <= c) lo = mid; else hi = mid;
+        }
+        for (uint64_t j = 0; j < wpr; ++j) fx->wave_idx[i * wpr + j] = (lo * chunk_rows + lr) * wpr + j;
+    }
+    return DRX_OK;
+}
+
 drx_status drx_h5_read_rows(drx_ctx *ctx, const char *file, const char *name, const uint64_t *rows, uint64_t n_rows,
                             int16_t *d_out, uint64_t out_cap_samples, drx_h5_stats *st) {
     if (!ctx || !file || !name || (n_rows && (!rows || !d_out))) return DRX_ERR_ARG;
     drx_h5_stats s;
     memset(&s, 0, sizeof s);
     dataset_t ds;
-    void *h_words = NULL, *d_words = NULL;  /* (h_words: the context's staging buffer, not freed here) */
-    uint64_t *touched = NULL, *h_off = NULL, *d_off = NULL, *wave_idx = NULL;
+    fetched_t fx;
+    memset(&fx, 0, sizeof fx);
     drx_plan *plan = NULL;
     int prev_dev = -1;
     if (enter_device(ctx, &prev_dev) != 0) return DRX_ERR_DEVICE;
-    double t0 = now();
     drx_status rc = open_dataset(file, name, &ds);
     if (rc != DRX_OK) goto out;
     rc = DRX_ERR_ARG;
@@ -369,67 +443,165 @@ drx_status drx_h5_read_rows(drx_ctx *ctx, const char *file, const char *name, co
     if (n_rows * cols > out_cap_samples) { rc = DRX_ERR_CAPACITY; goto out; }
     if (!n_rows) { rc = DRX_OK; goto out; }
 
-    /* the sorted set of chunks the rows lie in (HDF5 stores a padded last chunk full size: the same geometry as the others) */
-    touched = (uint64_t *)malloc(n_rows * sizeof(uint64_t));
-    wave_idx = (uint64_t *)malloc(n_rows * wpr * sizeof(uint64_t));
-    if (!touched || !wave_idx) { rc = DRX_ERR_NOMEM; goto out; }
-    for (uint64_t i = 0; i < n_rows; ++i) touched[i] = rows[i] / chunk_rows;
-    qsort(touched, n_rows, sizeof(uint64_t), cmp_u64);
-    uint64_t n_touched = 0;
-    for (uint64_t i = 0; i < n_rows; ++i) if (!n_touched || touched[n_touched - 1] != touched[i]) touched[n_touched++] = touched[i];
-    s.n_chunks = n_touched;
-    /* their stored sizes -> offsets -> the context's staging buffer <- their stored bytes */
-    h_off = (uint64_t *)malloc((n_touched + 1) * sizeof(uint64_t));
-    if (!h_off) { rc = DRX_ERR_NOMEM; goto out; }
-    uint64_t words = 0;
-    for (uint64_t t = 0; t < n_touched; ++t) {
-        hsize_t off[2] = {touched[t] * chunk_rows, 0}, nb = 0;
-        if (H5Dget_chunk_storage_size(ds.d, off, &nb) < 0 || (nb & 3)) { rc = DRX_ERR_CORRUPT; goto out; }
-        if (nb == 0) { rc = DRX_ERR_UNSUPPORTED; goto out; }  /* a chunk that was never written (fill value): not a stored stream */
-        h_off[t] = words;
-        words += nb / 4;
-    }
-    h_off[n_touched] = words;
-    s.stored_bytes = words * 4;
-    if (drx_ctx_host_staging(ctx, words * 4, &h_words) != DRX_OK) { rc = DRX_ERR_NOMEM; goto out; }
-    for (uint64_t t = 0; t < n_touched; ++t) {
-        hsize_t off[2] = {touched[t] * chunk_rows, 0};
-        uint32_t mask = 0;
-        if (H5Dread_chunk(ds.d, H5P_DEFAULT, off, &mask, (uint32_t *)h_words + h_off[t]) < 0 || mask) { rc = DRX_ERR_CORRUPT; goto out; }
-    }
-    s.t_file = now() - t0;
+    fx.wpr = wpr;
+    rc = fetch_rows_chunks(ctx, &ds, rows, n_rows, &fx);
+    s.n_chunks = fx.n_touched;
+    s.stored_bytes = fx.words * 4;
+    s.t_file = fx.t_file;
+    s.t_pcie = fx.t_pcie;
+    if (rc != DRX_OK) goto out;
 
-    t0 = now();
-    hipStream_t stream = (hipStream_t)drx_ctx_stream(ctx);
-    if (hipMalloc(&d_words, words * 4) != hipSuccess || hipMalloc((void **)&d_off, (n_touched + 1) * 8) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
-    if (hipMemcpyAsync(d_words, h_words, words * 4, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipMemcpyAsync(d_off, h_off, (n_touched + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess) { rc = DRX_ERR_DEVICE; goto out; }
-    s.t_pcie = now() - t0;
-
-    /* a plan over the fetched chunks; row r = waveforms (local row) * wpr ... of chunk number (its place among the fetched) */
-    t0 = now();
-    for (uint64_t i = 0; i < n_rows; ++i) {
-        const uint64_t c = rows[i] / chunk_rows, lr = rows[i] % chunk_rows;
-        uint64_t lo = 0, hi = n_touched;  /* invariant: touched[lo] <= c < touched[hi] */
-        while (hi - lo > 1) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (touched[mid] <= c) lo = mid; else hi = mid;
-        }
-        for (uint64_t j = 0; j < wpr; ++j) wave_idx[i * wpr + j] = (lo * chunk_rows + lr) * wpr + j;
-    }
-    if ((rc = drx_plan_create_uniform(ctx, n_touched, chunk_samples, (uint32_t)L, ds.o.rice_k, &plan)) != DRX_OK) goto out;
+    double t0 = now();
+    if ((rc = drx_plan_create_uniform(ctx, fx.n_touched, chunk_samples, (uint32_t)L, ds.o.rice_k, &plan)) != DRX_OK) goto out;
     if ((rc = drx_plan_set_filter(plan, ds.o.n_taps, ds.o.taps)) != DRX_OK) goto out;
-    if ((rc = drx_decode_select(plan, (const uint32_t *)d_words, words, d_off, wave_idx, n_rows * wpr, d_out, L)) != DRX_OK) goto out;
+    if ((rc = drx_decode_select(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, fx.wave_idx, n_rows * wpr, d_out, L)) != DRX_OK) goto out;
     if ((rc = drx_plan_finish(plan, NULL)) != DRX_OK) goto out;
     s.t_gpu = now() - t0;
 out:
     if (plan) drx_plan_destroy(plan);
-    if (d_words) (void)hipFree(d_words);
-    if (d_off) (void)hipFree(d_off);
-    free(touched);
-    free(wave_idx);
+    free_fetched(&fx);
+    close_dataset(&ds);
+    leave_device(prev_dev);
+    if (st) *st = s;
+    return rc;
+}
+
+/* File -> file: rows of one dataset into a new dataset of another file, the gathered chunks never decoded. */
+drx_status drx_h5_copy_rows(drx_ctx *ctx, const char *src_file, const char *src_name, const uint64_t *rows, uint64_t n_rows,
+                            const char *dst_file, const char *dst_name, uint64_t dst_chunk_rows, drx_h5_stats *st) {
+    if (!ctx || !src_file || !src_name || !dst_file || !dst_name || !rows || !n_rows || dst_chunk_rows > n_rows)
+        return DRX_ERR_ARG;  /* (HDF5: chunk <= dataset) */
+    {
+        struct stat a, b;  /* (the same file under another name, a hard link included; dst may not exist yet) */
+        if (!strcmp(src_file, dst_file) || (stat(src_file, &a) == 0 && stat(dst_file, &b) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino))
+            return DRX_ERR_ARG;
+    }
+    drx_h5_stats s;
+    memset(&s, 0, sizeof s);
+    dataset_t ds;
+    fetched_t fx;
+    memset(&fx, 0, sizeof fx);
+    drx_plan *plan = NULL, *plan_edge = NULL;
+    void *d_out = NULL, *d_edge = NULL, *d_words_e = NULL, *h_words = NULL;
+    uint64_t *d_out_off = NULL, *h_off = NULL;
+    hid_t f = -1, d = -1, sp = -1, pl = -1, ty = -1;
+    int prev_dev = -1;
+    if (enter_device(ctx, &prev_dev) != 0) return DRX_ERR_DEVICE;
+    hipStream_t stream = (hipStream_t)drx_ctx_stream(ctx);
+    drx_status rc = open_dataset(src_file, src_name, &ds);
+    if (rc != DRX_OK) goto out;
+    rc = DRX_ERR_ARG;
+    const uint64_t n_data_rows = ds.dims[0], cols = ds.dims[1], chunk_rows = ds.chunk[0];
+    if (!dst_chunk_rows) dst_chunk_rows = chunk_rows < n_rows ? chunk_rows : n_rows;  /* the source's chunking */
+    if (chunk_rows * cols > 0x7fffffffull || dst_chunk_rows * cols > 0x7fffffffull) goto out;
+    const uint32_t chunk_samples = (uint32_t)(chunk_rows * cols), dst_samples = (uint32_t)(dst_chunk_rows * cols);
+    s.rows = n_rows; s.cols = cols; s.chunk_rows = dst_chunk_rows;
+    s.raw_bytes = n_rows * cols * 2;
+    /* a row must be a whole number of waveforms; with WaveformLength -1 (the whole chunk one waveform) that is a chunk of one
+     * row, on both sides: the cd_values travel verbatim */
+    const uint64_t L = ds.o.wave_len < 0 ? (uint64_t)chunk_samples : (uint64_t)ds.o.wave_len;
+    if (cols % L != 0 || (ds.o.wave_len < 0 && dst_chunk_rows != 1)) { rc = DRX_ERR_UNSUPPORTED; goto out; }
+    const uint64_t wpr = cols / L;
+    for (uint64_t i = 0; i < n_rows; ++i) if (rows[i] >= n_data_rows) goto out;
+    if (n_rows * wpr >= (1ull << 32)) goto out;
+
+    fx.wpr = wpr;
+    rc = fetch_rows_chunks(ctx, &ds, rows, n_rows, &fx);
+    s.n_chunks = fx.n_touched;
+    s.stored_bytes = fx.words * 4;
+    s.t_file = fx.t_file;
+    s.t_pcie = fx.t_pcie;
+    if (rc != DRX_OK) goto out;
+
+    /* whole output chunks: one gather, sized first.  Rows left over: HDF5 stores the last chunk full size, so those are decoded,
+     * padded with the fill value (0) and encoded, as drx_h5_write pads its last chunk */
+    double t0 = now();
+    const uint64_t n_full = n_rows / dst_chunk_rows, edge_rows = n_rows % dst_chunk_rows, n_out = n_full + (edge_rows ? 1 : 0);
+    const uint64_t n_sel = n_full * dst_chunk_rows * wpr;
+    uint64_t words = 0, words_e = 0;
+    if ((rc = drx_plan_create_uniform(ctx, fx.n_touched, chunk_samples, (uint32_t)L, ds.o.rice_k, &plan)) != DRX_OK) goto out;
+    if ((rc = drx_plan_set_filter(plan, ds.o.n_taps, ds.o.taps)) != DRX_OK) goto out;
+    if (hipMalloc((void **)&d_out_off, (n_out + 3) * 8) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
+    if (n_full) {
+        if ((rc = drx_gather_encoded(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, fx.wave_idx, n_sel, dst_chunk_rows * wpr,
+                                     NULL, 0, d_out_off, NULL)) != DRX_OK) goto out;
+        if ((rc = drx_plan_finish(plan, &words)) != DRX_OK) goto out;
+        if (hipMalloc(&d_out, words * 4) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
+        if ((rc = drx_gather_encoded(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, fx.wave_idx, n_sel, dst_chunk_rows * wpr,
+                                     (uint32_t *)d_out, words, d_out_off, NULL)) != DRX_OK) goto out;
+        if ((rc = drx_plan_finish(plan, &words)) != DRX_OK) goto out;
+    }
+    if (edge_rows) {
+        if ((rc = drx_plan_create_uniform(ctx, 1, dst_samples, (uint32_t)L, ds.o.rice_k, &plan_edge)) != DRX_OK) goto out;
+        if ((rc = drx_plan_set_filter(plan_edge, ds.o.n_taps, ds.o.taps)) != DRX_OK) goto out;
+        const uint64_t cap_e = drx_plan_max_encoded_words(plan_edge);
+        if (hipMalloc(&d_edge, (size_t)dst_samples * 2) != hipSuccess || hipMalloc(&d_words_e, cap_e * 4) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
+        if (hipMemsetAsync(d_edge, 0, (size_t)dst_samples * 2, stream) != hipSuccess) { rc = DRX_ERR_DEVICE; goto out; }
+        if ((rc = drx_decode_select(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, fx.wave_idx + n_sel, edge_rows * wpr,
+                                    (int16_t *)d_edge, L)) != DRX_OK) goto out;
+        if ((rc = drx_plan_finish(plan, NULL)) != DRX_OK) goto out;
+        if ((rc = drx_encode(plan_edge, (const int16_t *)d_edge, (uint32_t *)d_words_e, cap_e, d_out_off + n_full + 1)) != DRX_OK) goto out;
+        if ((rc = drx_plan_finish(plan_edge, &words_e)) != DRX_OK) goto out;
+    }
+    s.t_gpu = now() - t0;
+
+    /* the result to the context's staging buffer (the fetched bytes have left it) */
+    t0 = now();
+    rc = DRX_ERR_NOMEM;
+    h_off = (uint64_t *)malloc((n_out + 3) * 8);
+    if (!h_off || drx_ctx_host_staging(ctx, (words + words_e + 1) * 4, &h_words) != DRX_OK) goto out;
+    rc = DRX_ERR_DEVICE;
+    h_off[0] = 0;
+    if (n_full && hipMemcpyAsync(h_off, d_out_off, (n_full + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess) goto out;
+    if (n_full && hipMemcpyAsync(h_words, d_out, words * 4, hipMemcpyDeviceToHost, stream) != hipSuccess) goto out;
+    if (edge_rows && hipMemcpyAsync((uint32_t *)h_words + words, d_words_e, words_e * 4, hipMemcpyDeviceToHost, stream) != hipSuccess) goto out;
+    if (hipStreamSynchronize(stream) != hipSuccess) goto out;
+    if (edge_rows) h_off[n_full + 1] = words + words_e;  /* h_off[n_full] == words (or 0 without full chunks) */
+    s.t_pcie += now() - t0;
+
+    /* the new dataset: the source's element type and cd_values verbatim, chunks of dst_chunk_rows x cols */
+    t0 = now();
+    rc = DRX_ERR_ARG;
+    ensure_filter_registered();
+    unsigned cd[3 + DRX_MAX_TAPS], flags = 0, fcfg = 0;
+    size_t ncd = 3 + DRX_MAX_TAPS;
+    char fname[8];
+    if (H5Pget_filter_by_id2(ds.pl, FILTER_ID, &flags, &ncd, cd, sizeof fname, fname, &fcfg) < 0) goto out;
+    {
+        hid_t sty = H5Dget_type(ds.d);
+        ty = H5Tcopy(sty);
+        H5Tclose(sty);
+        if (ty < 0) goto out;
+    }
+    if ((f = H5Fcreate(dst_file, H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT)) < 0) goto out;
+    hsize_t dims[2] = {n_rows, cols}, chunk[2] = {dst_chunk_rows, cols};
+    sp = H5Screate_simple(2, dims, NULL);
+    pl = H5Pcreate(H5P_DATASET_CREATE);
+    if (H5Pset_chunk(pl, 2, chunk) < 0 || H5Pset_filter(pl, FILTER_ID, flags, ncd, cd) < 0) goto out;
+    if ((d = H5Dcreate2(f, dst_name, ty, sp, H5P_DEFAULT, pl, H5P_DEFAULT)) < 0) goto out;
+    for (uint64_t c = 0; c < n_out; ++c) {
+        hsize_t off[2] = {c * dst_chunk_rows, 0};
+        if (H5Dwrite_chunk(d, H5P_DEFAULT, 0, off, (size_t)(h_off[c + 1] - h_off[c]) * 4, (const uint32_t *)h_words + h_off[c]) < 0) goto out;
+    }
+    rc = DRX_OK;
+out:
+    if (d >= 0) H5Dclose(d);
+    if (pl >= 0) H5Pclose(pl);
+    if (sp >= 0) H5Sclose(sp);
+    if (ty >= 0) H5Tclose(ty);
+    if (f >= 0) {
+        if (H5Fclose(f) < 0 && rc == DRX_OK) rc = DRX_ERR_ARG;
+        s.t_file += now() - t0;
+        if (rc != DRX_OK) (void)unlink(dst_file);  /* (no half-written file is left behind) */
+    }
+    if (plan) drx_plan_destroy(plan);
+    if (plan_edge) drx_plan_destroy(plan_edge);
+    if (d_out) (void)hipFree(d_out);
+    if (d_edge) (void)hipFree(d_edge);
+    if (d_words_e) (void)hipFree(d_words_e);
+    if (d_out_off) (void)hipFree(d_out_off);
     free(h_off);
+    free_fetched(&fx);
     close_dataset(&ds);
     leave_device(prev_dev);
     if (st) *st = s;

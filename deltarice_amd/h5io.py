@@ -38,6 +38,9 @@ def _load():
         L.drx_h5_read_rows.restype = C.c_int
         L.drx_h5_read_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_void_p,
                                        C.c_uint64, C.POINTER(Stats)]
+        L.drx_h5_copy_rows.restype = C.c_int
+        L.drx_h5_copy_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p,
+                                       C.c_char_p, C.c_uint64, C.POINTER(Stats)]
         L.drx_h5_write.restype = C.c_int
         L.drx_h5_write.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.c_uint64, C.c_uint, C.c_uint, C.POINTER(Stats)]
@@ -81,6 +84,25 @@ def read_rows(ctx: Context, path: str, name: str, rows, out: torch.Tensor | None
         raise _lib.DeltaRiceError(rc, f"drx_h5_read_rows({path!r}, {name!r})")
     cols = int(st.cols)
     return out.view(-1)[:idx.size * cols].view(idx.size, cols), st.as_dict()
+
+
+def copy_rows(ctx: Context, src: str, name: str, rows, dst: str, dst_name: str | None = None,
+              chunk_rows: int | None = None) -> dict:
+    """File -> file: the dataset rows ``rows`` names (as read_rows takes them) become dataset ``dst_name`` (None: ``name``) of
+    the new file ``dst`` in chunks of ``chunk_rows`` rows (None: the source's, or all rows where there are fewer), with the
+    source's element type and compression_opts.  Only the chunks those rows lie in are fetched; their waveforms are regrouped
+    on the GPU as encoded words (drx_gather_encoded), not decoded.  Returns the stats: n_chunks / stored_bytes = fetched."""
+    from .codec import _as_index_array
+    idx = _as_index_array(rows)
+    L = _load()
+    st = Stats()
+    ctx.stream.wait_stream(torch.cuda.current_stream(ctx.device))
+    ip = idx.ctypes.data_as(C.POINTER(C.c_uint64))
+    rc = L.drx_h5_copy_rows(ctx._h, os.fsencode(src), name.encode(), ip, idx.size, os.fsencode(dst),
+                            (name if dst_name is None else dst_name).encode(), 0 if chunk_rows is None else int(chunk_rows), C.byref(st))
+    if rc != _lib.DRX_OK:
+        raise _lib.DeltaRiceError(rc, f"drx_h5_copy_rows({src!r}, {name!r} -> {dst!r})")
+    return st.as_dict()
 
 
 def write(ctx: Context, path: str, name: str, x: torch.Tensor, rows: int, cols: int, chunk_rows: int,

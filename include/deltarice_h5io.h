@@ -45,6 +45,20 @@ drx_status drx_h5_read(drx_ctx *ctx, const char *file, const char *name, int16_t
 drx_status drx_h5_read_rows(drx_ctx *ctx, const char *file, const char *name, const uint64_t *rows, uint64_t n_rows,
                             int16_t *d_out, uint64_t out_cap_samples, drx_h5_stats *stats);
 
+/* File -> file, selected rows: dataset `dst_name` of `dst_file` (created / truncated as drx_h5_write does; dst_file equal to
+ * src_file: DRX_ERR_ARG) receives the n_rows x cols rows `rows` names (host array; any order, duplicates allowed; n_rows >= 1),
+ * in chunks of dst_chunk_rows x cols (1 <= dst_chunk_rows <= n_rows; 0: the source's chunk rows, or n_rows where that is less), with the SOURCE's element type and cd_values verbatim
+ * (general prediction filters included).  Source datasets as drx_h5_read_rows takes them.  The stored bytes of the chunks the
+ * rows lie in are fetched, and ONE drx_gather_encoded with dst_chunk_rows * (cols / WaveformLength) waveforms per output chunk
+ * makes the new chunks out of them without decoding a sample: they are the bytes the filter would write for those rows.
+ * Where n_rows does not divide by dst_chunk_rows HDF5 stores the last chunk full size: that one chunk is decoded
+ * (drx_decode_select), padded with the fill value 0 and encoded, as drx_h5_write pads its last chunk.  WaveformLength -1 (the
+ * whole chunk is one waveform) needs chunks of one row on both sides, else DRX_ERR_UNSUPPORTED.
+ * stats: n_chunks / stored_bytes count what was FETCHED, raw_bytes the int16 bytes the new dataset represents, rows /
+ * chunk_rows describe the new dataset. */
+drx_status drx_h5_copy_rows(drx_ctx *ctx, const char *src_file, const char *src_name, const uint64_t *rows, uint64_t n_rows,
+                            const char *dst_file, const char *dst_name, uint64_t dst_chunk_rows, drx_h5_stats *stats);
+
 /* VRAM -> file: encodes d_in (device int16[rows*cols]) and writes it as dataset `name` (file is
  * created/truncated).  rice_m, wave_len: compression_opts (RiceParameter, WaveformLength). */
 drx_status drx_h5_write(drx_ctx *ctx, const char *file, const char *name, const int16_t *d_in,

@@ -163,6 +163,50 @@ drx_status drx_decode_select_with_wave_words(drx_plan *plan, const uint32_t *d_i
                                              const uint64_t *wave_idx, uint64_t n_sel, int16_t *d_out,
                                              uint64_t out_stride_samples);
 
+/* Gather SELECTED waveforms into a new ENCODED batch, without decoding them.  wave_idx: HOST array of n_sel global waveform
+ * indices as drx_decode_select takes it (any order, duplicates allowed), consumed before the call returns.  Output chunk c holds
+ * entries [c * out_chunk_waves, min(n_sel, (c + 1) * out_chunk_waves)) of the list, in list order; n_out_chunks =
+ * ceil(n_sel / out_chunk_waves).  Its words are N_c | { n_i | payload_i } per entry, N_c the sum of the entries' sample counts;
+ * the chunks lie back to back from d_out[0], and d_out_chunk_word_off (uint64[n_out_chunks + 1]) is written as drx_encode
+ * writes it (last entry = total words).  A waveform is coded on its own and is a whole number of words (src/deltaRice.c:365-381,
+ * 427-432), so these are the bytes drx_encode -- hence the reference's filter -- gives for the gathered samples under the source
+ * plan's RiceParameter and prediction filter, whichever filter that is.  d_out_wave_words (uint32[n_sel], or NULL) receives the
+ * n_i of every entry: the side-band of the result.
+ *   One WaveformLength per output chunk: all its entries have the length of its first, except the last, which may be shorter.
+ * That admits ragged source plans (group by length) and the short last waveform of a source chunk (at the end of an output
+ * chunk only).
+ *   DRX_ERR_ARG, with nothing launched: a list that breaks that rule (the message names the entry), an index >= total_waves,
+ * out_chunk_waves == 0, n_sel >= 2^32, an output chunk of 2^31 samples or more (src/deltaRice.c:389), a NULL pointer among d_in,
+ * d_chunk_word_off, wave_idx, d_out_chunk_word_off with n_sel > 0.  n_sel == 0: DRX_OK, nothing launched.
+ *   Sizing.  The size of the result is known on the device before a word is copied.  d_out == NULL (with out_cap_words == 0)
+ * runs exactly that far: the offset table and d_out_wave_words are written, drx_plan_finish reports the total, nothing else is
+ * touched.  With d_out != NULL and a total above out_cap_words: DRX_ERR_CAPACITY at drx_plan_finish, which still reports the
+ * total NEEDED, and not one word of d_out is written.
+ *   The call behind a sizing call costs no second walk: the drx_gather_encoded call that follows a SIZING call on the same plan
+ * with the same pointers, sizes and list (compared entry by entry), no other call on the plan in between, resumes from the
+ * sizing call's tables -- once.  Every other call, also one that repeats the arguments of a call that copied, walks and
+ * validates the stream anew.
+ *   Asynchronous on the context's stream like drx_decode_select; errors found on the device arrive at drx_plan_finish.  Only
+ * the chunks that hold a selected waveform are walked -- whole, with drx_decode's validation of the header chain: a corrupt
+ * touched chunk is DRX_ERR_CORRUPT and nothing is copied.  The other chunks are NEITHER READ NOR VALIDATED.  Payload words are
+ * COPIED, NOT PARSED: damage inside a payload that leaves the header chain intact travels to the output unnoticed (the
+ * reference's own level of trust in a stored chunk).  drx_plan_wave_words / drx_plan_wave_word_off after the call are valid for
+ * the touched chunks only.
+ *   The buffers rule at the top of this file holds: any element alignment for d_in, d_out and both tables; nothing is written
+ * outside [d_out, d_out + total), the n_out_chunks + 1 offsets and the n_sel table entries; the result depends neither on what
+ * those held before nor on words outside [0, in_words).  d_out must not overlap d_in (not checked).  The gather's scratch
+ * belongs to the plan beside the selection's: allocated by the first such call, grown when a later one needs more. */
+drx_status drx_gather_encoded(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const uint64_t *wave_idx, uint64_t n_sel, uint64_t out_chunk_waves, uint32_t *d_out,
+                              uint64_t out_cap_words, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
+/* ... with the encoder's side-band (d_wave_words: uint32[total_waves] on the device, neither the plan's own table nor
+ * d_out_wave_words): no walk; the table is checked against the stream for the touched chunks as
+ * drx_decode_select_with_wave_words checks it (a table that does not belong to the stream: DRX_ERR_CORRUPT). */
+drx_status drx_gather_encoded_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                              const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words,
+                                              const uint64_t *wave_idx, uint64_t n_sel, uint64_t out_chunk_waves, uint32_t *d_out,
+                                              uint64_t out_cap_words, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
+
 /* RiceParameter optimiser (docs/Optimization.md:5-19 of the reference describes one, the tree does not
  * contain it): exact number of uint32 words drx_encode would emit for this batch with RiceParameter
  * 2^k, for every k = 0..15 (host array of 16), in one pass over the samples.  Synchronous. */
@@ -185,6 +229,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_IIR 32u        /* residuals first, then the general filter's inverse in place, parallel inside a waveform */
 #define DRX_PATH_IIR_FUSED 64u  /* the general filter's inverse inside the block decoder: one kernel, samples straight to the output */
 #define DRX_PATH_SELECT 128u    /* drx_decode_select: a wavefront (general filters: a lane) per selected waveform; reported alone */
+#define DRX_PATH_GATHER 256u    /* drx_gather_encoded: word ranges copied, nothing decoded; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -210,7 +255,8 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
 /* Kernel times of the plan's last call, measured with HIP events on the context's
  * stream (needs the context option "profile" = 1 before the call; waits for it).
  *   after drx_encode: ms = { size pass, offset scan, pack pass, whole call }
- *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call } */
+ *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call }
+ *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call } */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 
 /* Tuning / diagnostics.  Returns DRX_ERR_ARG for unknown keys or values.
@@ -240,6 +286,7 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 #define DRX_DBG_FORCE_STREAM_SEGS 4194304u      /* the persistent encoder's segment form (encode_impl 2, uniform), segments of ~1024 samples */
 #define DRX_DBG_WALK_BY_SCAN 8388608u           /* the chunk-wide header walk by reading the whole chunk instead of chasing 64 chains */
 #define DRX_DBG_WALK_BY_CHAINS 16777216u        /* the chunk-wide header walk by chains also where the scan form is the default */
+#define DRX_DBG_GATHER_OTHER_COPY 33554432u      /* drx_gather_encoded: the copy form the batch's code length does NOT choose (a workgroup per run of entries <-> a wavefront per entry) */
 drx_status drx_ctx_set_option(drx_ctx *ctx, const char *key, int64_t value);
 
 #ifdef __cplusplus
