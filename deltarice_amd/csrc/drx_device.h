@@ -14,6 +14,19 @@ namespace drx {
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
+// Wave-uniform values the compiler does not keep in scalar registers: it cannot prove threadIdx.x >> 6 uniform, so
+// everything addressed or computed through the wave index is divergent to it; and the result of an LDS or vector-memory
+// load arrives in a VGPR even where the address is provably uniform.  Read such a value from lane 0 into scalar registers
+// at its SOURCE (the wave index, the word published through LDS), so that what is computed from it -- indices, bit counts,
+// limits, loop and branch conditions -- is scalar code and the branches are s_cbranch, not exec-mask regions; a load whose
+// address the compiler already knows to be uniform needs nothing.  ONLY for values that are
+// uniform by construction: kernel arguments, blockIdx, threadIdx.x >> 6, readlane results, and a word that every lane of
+// the wavefront loads from the same address behind the barrier or wave_sync() that orders its write.  Never for anything
+// per lane: the other 63 values are dropped without a trace.
+__device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v); }
+__device__ __forceinline__ int wave_id() { return (int)rfl(threadIdx.x >> 6); }  // wavefront of the workgroup (1-D blocks)
+
 __device__ __forceinline__ void wave_sync() {
     // All lanes of a wave run in lock step and its LDS operations complete in order;
     // this only stops the compiler from moving LDS accesses across a phase boundary.
@@ -101,6 +114,16 @@ __device__ __forceinline__ WaveRef locate(const Geom &G, uint64_t g) {
     r.len = (r.idx + 1 == W) ? (r.n_samples - r.idx * L) : L;  // trailing partial waveform (:420-425)
     return r;
 }
+// the same for a wave-uniform g: the result in scalar registers (the ragged form reads the chunk table)
+__device__ __forceinline__ WaveRef locate_uniform(const Geom &G, uint64_t g) {
+    WaveRef r = locate(G, rfl64(g));
+    r.chunk = rfl64(r.chunk);
+    r.sample_off = rfl64(r.sample_off);
+    r.idx = rfl(r.idx);
+    r.len = rfl(r.len);
+    r.n_samples = rfl(r.n_samples);
+    return r;
+}
 
 // inclusive prefix sum over the 64 lanes (DPP: row shifts, then row broadcasts)
 __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
@@ -111,6 +134,14 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
     return v;
+}
+
+// v of the lane below; lane 0 receives the wave-uniform `first` (one v_writelane from a scalar register, where a select
+// on lane == 0 costs a move and a v_cndmask)
+__device__ __forceinline__ uint32_t wave_shr1_carry(uint32_t v, uint32_t first) {
+    uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true);  // wave_shr:1
+    asm("v_writelane_b32 %0, %1, 0" : "+v"(r) : "s"(rfl(first)));
+    return r;
 }
 
 // decoupled look-back entries: 2 status bits on top of the value (the word is its own flag; zero = not yet)

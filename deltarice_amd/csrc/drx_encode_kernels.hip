@@ -69,9 +69,9 @@ __device__ __forceinline__ int32_t fir_residual(const int16_t *__restrict__ x, u
 __global__ __launch_bounds__(256) void k_encode_sizes(Geom G, const int16_t *__restrict__ in,
                                                       uint32_t *__restrict__ wave_words) {
     const int lane = lane_id();
-    const uint64_t g = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint64_t g = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_id();
     if (g >= G.total_waves) return;
-    const WaveRef r = locate(G, g);
+    const WaveRef r = locate_uniform(G, g);
     const int16_t *x = in + r.sample_off;
     const bool vec_ok = ((uintptr_t)x & 15u) == 0;
     const uint32_t k = G.k;
@@ -103,9 +103,9 @@ __global__ __launch_bounds__(256) void k_encode_sizes(Geom G, const int16_t *__r
 __global__ __launch_bounds__(256) void k_estimate_words(Geom G, const int16_t *__restrict__ in,
                                                         unsigned long long *__restrict__ words) {
     const int lane = lane_id();
-    const uint64_t g = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint64_t g = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_id();
     if (g >= G.total_waves) return;
-    const WaveRef r = locate(G, g);
+    const WaveRef r = locate_uniform(G, g);
     const int16_t *x = in + r.sample_off;
     const bool vec_ok = ((uintptr_t)x & 15u) == 0;
     uint32_t bits[16];
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_chunk_scan(Geom G, const uint32_t *__re
                                                     uint64_t *__restrict__ chunk_words) {
     __shared__ uint32_t wsum[4];
     const uint64_t c = blockIdx.x;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int lane = lane_id(), wv = wave_id();
     uint64_t base;
     uint32_t W;
     if (G.uniform) { base = c * G.u_n_waves; W = G.u_n_waves; }
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void k_chunk_scan(Geom G, const uint32_t *__re
         __syncthreads();
         uint32_t before = 0, all = 0;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) { before += (w < wv) ? wsum[w] : 0u; all += wsum[w]; }
+        for (int w = 0; w < 4; ++w) { const uint32_t s = rfl(wsum[w]); before += (w < wv) ? s : 0u; all += s; }
         if (i < W) wave_rel[base + i] = (uint32_t)(run + before + inc - v);
         run += all;
         __syncthreads();
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(1024) void k_chunk_offsets(uint64_t n_chunks, const
                                                         uint64_t *__restrict__ chunk_word_off,
                                                         uint64_t out_cap, DevStatus *st, uint64_t *host_words) {
     __shared__ uint64_t wsum[16];
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int lane = lane_id(), wv = wave_id();
     uint64_t run = 0;
     for (uint64_t i0 = 0; i0 < n_chunks; i0 += 1024) {
         const uint64_t i = i0 + threadIdx.x;
@@ -210,11 +210,12 @@ __global__ __launch_bounds__(256) void k_encode_pack(Geom G, const int16_t *__re
                                                      uint32_t *__restrict__ out, uint64_t out_cap) {
     __shared__ uint32_t stage_all[4][kStageWords];
     const int lane = lane_id();
-    uint32_t *stage = stage_all[threadIdx.x >> 6];
-    const uint64_t g = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    const int wv = wave_id();
+    uint32_t *stage = stage_all[wv];
+    const uint64_t g = (uint64_t)blockIdx.x * 4u + (uint32_t)wv;
     if (g >= G.total_waves) return;
     for (int i = lane; i < kStageWords; i += 64) stage[i] = 0;
-    const WaveRef r = locate(G, g);
+    const WaveRef r = locate_uniform(G, g);
     const uint64_t pos = chunk_word_off[r.chunk] + wave_rel[g];  // this waveform's header word
     const uint32_t n = wave_words[g];
     if (pos + 1u + n > out_cap) return;  // k_chunk_offsets has raised kErrCapacity
@@ -327,8 +328,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
     __shared__ uint32_t s_ticket;
     __shared__ uint64_t s_mine[kEncWaves];
     __shared__ uint64_t s_excl;
-    const int lane = lane_id();
-    uint32_t *row = buf_all[threadIdx.x >> 6];
+    const int lane = lane_id(), wv = wave_id();
+    uint32_t *row = buf_all[wv];
     uint32_t *buf = row + 4;
     const uint32_t buf_bits = lds_addr(buf) * 8u;  // LDS is 160 KB: bit addresses fit easily
 
@@ -338,11 +339,11 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
     // exactly that rate: 1M waveforms in 11.9 ms).
     if (threadIdx.x == 0) s_ticket = atomicAdd(ticket, 1u);
     __syncthreads();
-    const uint64_t g = (uint64_t)s_ticket * kEncWaves + (threadIdx.x >> 6);
+    const uint64_t g = (uint64_t)rfl(s_ticket) * kEncWaves + (uint32_t)wv;  // (one address, written before the barrier)
     const bool live = g < G.total_waves;  // the last workgroup may be partial; its idle waves still join the barriers
 
     for (int i = lane; i < (int)(kEncCapWords + 8) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
-    WaveRef r = locate(G, live ? g : 0);
+    WaveRef r = locate_uniform(G, live ? g : 0);
     if (!live) { r.len = 0; r.idx = 1; }  // an idle wave of the last workgroup: nothing to encode, nothing to add
     const int16_t *x = in + r.sample_off;
     // 16-byte loads at any int16 alignment (unaligned access is on for HSA queues): a WaveformLength like 3500 puts
@@ -365,13 +366,11 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
     // while the current one is packed; the trailing partial tile (if any) takes the masked path once.
     auto process_tile = [&](const uint32_t (&w)[4], int nv, auto full_tag) {
         constexpr bool FULLT = decltype(full_tag)::value;
-        uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
-        if (lane == 0) xprev = carry;
+        const uint32_t xprev = wave_shr1_carry(w[3], carry);
         carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
         uint32_t xprev2 = 0;
         if (GEN) {
-            xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);  // wave_shr:1
-            if (lane == 0) xprev2 = carry2;
+            xprev2 = wave_shr1_carry(w[2], carry2);
             carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
         }
         PackedCodes c;
@@ -382,7 +381,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
         if (FULLT) concat_codes(c, cw);  // independent of the scan: fills its DPP wait states
         const uint32_t incl = wave_incl_scan_dpp(lane_bits);
         const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        if (fits && ((P + tile_bits + 31u) >> 5) < (uint64_t)kEncCapWords) {
+        // (32 bits: while `fits` holds P is below the buffer's 2^17 bits, and a scalar 64-bit `<` does not exist)
+        if (fits && (((uint32_t)P + tile_bits + 31u) >> 5) < kEncCapWords) {
             if (FULLT && !__any(lane_bits > 128u))
                 place_words(cw, buf_bits + (uint32_t)P + incl);
             else
@@ -392,9 +392,9 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
         }
         P += tile_bits;
     };
-    // r.len is the same in every lane (one waveform per wave): say so, or the tile loop is compiled with
-    // per-lane predicates, register copies and a full vmcnt(0) in front of every tile
-    const uint32_t wlen = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.len);
+    // (r.len is wave uniform, locate_uniform(): otherwise the tile loop is compiled with per-lane predicates, register
+    // copies and a full vmcnt(0) in front of every tile)
+    const uint32_t wlen = r.len;
     const uint32_t n_full = wlen / kTile;
     {
         // kDepth tiles of loads in flight, in kDepth fixed register sets (the loop is unrolled by
@@ -453,14 +453,13 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
     // prefix is published one round trip after its aggregate, so the frontier of known prefixes
     // advances by at most one window per round trip.)
     const uint64_t mine = live ? 1ull + n + (r.idx == 0 ? 1ull : 0ull) : 0ull;
-    const int wv = threadIdx.x >> 6;
     if (lane == 0) s_mine[wv] = mine;
     __syncthreads();
     if (wv == 0) {
         uint64_t block_sum = 0;
 #pragma unroll
-        for (int i = 0; i < kEncWaves; ++i) block_sum += s_mine[i];
-        const uint64_t T = s_ticket;
+        for (int i = 0; i < kEncWaves; ++i) block_sum += rfl64(s_mine[i]);
+        const uint64_t T = rfl(s_ticket);
         uint64_t excl_blk = 0;
         if (T == 0) {
             if (lane == 0) __hip_atomic_store(scan_state + T, kScanPrefix | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -526,9 +525,9 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
         if (lane == 0) s_excl = excl_blk;
     }
     __syncthreads();
-    uint64_t excl = s_excl;
+    uint64_t excl = rfl64(s_excl);
 #pragma unroll
-    for (int i = 0; i < kEncWaves; ++i) excl += (i < wv) ? s_mine[i] : 0ull;
+    for (int i = 0; i < kEncWaves; ++i) excl += (i < wv) ? rfl64(s_mine[i]) : 0ull;
     if (!live) return;
     const uint64_t pos = excl + (r.idx == 0 ? 1ull : 0ull);  // this waveform's header word
     if (lane == 0) {
@@ -653,6 +652,21 @@ __device__ __forceinline__ SegRef locate_seg(const Geom &G, uint64_t u, uint32_t
     q.last = q.start + q.count == q.r.len;
     return q;
 }
+// the same for a wave-uniform u: the result in scalar registers
+__device__ __forceinline__ SegRef locate_seg_uniform(const Geom &G, uint64_t u, uint32_t segs_per_wave) {
+    SegRef q = locate_seg(G, rfl64(u), segs_per_wave);
+    q.r.chunk = rfl64(q.r.chunk);
+    q.r.sample_off = rfl64(q.r.sample_off);
+    q.r.idx = rfl(q.r.idx);
+    q.r.len = rfl(q.r.len);
+    q.r.n_samples = rfl(q.r.n_samples);
+    q.g = rfl64(q.g);
+    q.s = rfl(q.s);
+    q.start = rfl(q.start);
+    q.count = rfl(q.count);
+    q.last = rfl(q.last ? 1u : 0u) != 0u;
+    return q;
+}
 
 // the tiles of one segment: calls tile(c, lane_bits, incl, tile_bits, full) for each
 template <typename F>
@@ -661,13 +675,12 @@ __device__ __forceinline__ void for_segment_tiles(const int16_t *__restrict__ xw
     const bool vec_ok = true;  // any int16 alignment (see k_encode_fused)
     // dword whose high half is the sample before the segment (x[-1] := 0 at the start of the waveform, :53-54)
     // (a unit past the end of a shorter last waveform has count == 0: nothing of it may be touched)
-    uint32_t carry = (q.start && q.count) ? ((uint32_t)(uint16_t)xw[q.start - 1u] << 16) : 0u;
+    uint32_t carry = (q.start && q.count) ? rfl((uint32_t)(uint16_t)xw[q.start - 1u] << 16) : 0u;
     const u16x2 tp[4] = {splat(1u), splat(0xffffu), splat(0u), splat(0u)};
     for (uint32_t t0 = 0; t0 < q.count; t0 += kTile) {
         uint32_t w[4];
         const int nv = load8_dwords(x, q.count, t0, lane, vec_ok, w);
-        uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
-        if (lane == 0) xprev = carry;
+        const uint32_t xprev = wave_shr1_carry(w[3], carry);
         carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
         PackedCodes c;
         packed_codes<false>(w, xprev, 0u, tp, k, c);
@@ -684,11 +697,11 @@ __global__ __launch_bounds__(256) void k_seg_sizes(Geom G, const int16_t *__rest
                                                    uint64_t n_units, uint32_t upw, uint32_t *__restrict__ seg_bits) {
     const int lane = lane_id();
     // upw consecutive units per wavefront: with one-tile waveforms the launch of a wavefront costs as much as its work
-    const uint64_t u0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * upw;
+    const uint64_t u0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave_id()) * upw;
     for (uint32_t rep = 0; rep < upw; ++rep) {
         const uint64_t u = u0 + rep;
         if (u >= n_units) return;
-        const SegRef q = locate_seg(G, u, segs_per_wave);
+        const SegRef q = locate_seg_uniform(G, u, segs_per_wave);
         uint32_t bits = 0;  // <= 8192 * 25
         for_segment_tiles(in + q.r.sample_off, q, G.k, lane,
                           [&](const PackedCodes &, uint32_t, uint32_t, uint32_t tile_bits, bool) { bits += tile_bits; });
@@ -743,13 +756,14 @@ __global__ __launch_bounds__(256) void k_seg_pack(Geom G, const int16_t *__restr
     // per wave: 4 pad words (place_words ORs zeros below a lane's first word), the stage, slack
     __shared__ __attribute__((aligned(16))) uint32_t stage_all[4][4 + kStageWords + 12];
     const int lane = lane_id();
-    uint32_t *row = stage_all[threadIdx.x >> 6];
+    const int wv = wave_id();
+    uint32_t *row = stage_all[wv];
     uint32_t *stage = row + 4;
-    const uint64_t u0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * upw;
+    const uint64_t u0 = ((uint64_t)blockIdx.x * 4u + (uint32_t)wv) * upw;
     for (uint32_t rep = 0; rep < upw; ++rep) {
         const uint64_t u = u0 + rep;
         if (u >= n_units) return;
-        const SegRef q = locate_seg(G, u, segs_per_wave);
+        const SegRef q = locate_seg_uniform(G, u, segs_per_wave);
         if (q.count == 0) continue;
         for (int i = lane; i < 4 + (int)kStageWords + 12; i += 64) row[i] = 0;
         const uint64_t pos = chunk_word_off[q.r.chunk] + wave_rel[q.g];  // the waveform's header word

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     typedef uint64_t __attribute__((address_space(3))) lds_u64;
     static_assert((kEsFront + RING + kEsBack) % 4 == 0 && RING % 4 == 0, "16-byte LDS accesses");
     constexpr uint32_t kRingBits = RING * 32u;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int lane = lane_id(), wv = wave_id();
     uint32_t *row = ring_all[wv];
     uint32_t *ring = row + kEsFront;
     const uint32_t ring_bits0 = lds_addr(ring) * 8u;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     const uint64_t n_tickets = (G.total_waves + WV - 1) / WV;
-    if (s_role == 0) {  // the first workgroup to start sweeps the totals; everybody else codes
+    if (rfl(s_role) == 0) {  // the first workgroup to start sweeps the totals; everybody else codes
         es_scanner(n_tickets, size, place, st);
         return;
     }
@@ -176,6 +176,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     bool pend = false, fitsA = true;
     uint64_t gA = 0, offA = 0;   // its index; words of its ticket in front of it (known behind the next rendezvous)
     uint32_t TA = 0, startA = 0, nA = 0;
+    WaveRef rA = {};             // where it lies in the batch, from the moment it was located
 
     // header words and bookkeeping of a waveform whose place is known; returns whether its words may be stored
     auto place_header = [&](const WaveRef &r, uint64_t g, uint32_t n, uint64_t ex, uint64_t &pos) -> bool {
@@ -199,7 +200,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     };
     // copies waveform A out (its ticket begins `ex` words into the stream) and clears its part of the ring
     auto copy_out = [&](uint64_t ex) {
-        const WaveRef rA = locate(G, gA);
         uint64_t pos;
         const bool room = place_header(rA, gA, nA, ex + offA, pos);
         uint32_t *__restrict__ outp = out + pos + 1;
@@ -225,8 +225,8 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     // Ticket TA's place, if a wavefront of this workgroup has seen it already (they all need the same word).
     auto place_in_lds = [&](uint64_t &ex) -> bool {
         const uint32_t t = __hip_atomic_load((lds_u32 *)&s_place_t[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)t) != TA + 1u) return false;
-        ex = __hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (rfl(t) != TA + 1u) return false;
+        ex = rfl64(__hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         return true;
     };
     auto place_to_lds = [&](uint64_t ex) {
@@ -263,9 +263,9 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     // A waveform that outgrew the ring (incompressible data, long waveforms) is coded a second time, tile by tile through the
     // (empty) ring's first words, straight to its place: a second read of its samples.
     auto stream_out = [&](uint64_t ex) {
-        const WaveRef r = locate(G, gA);
+        const WaveRef &r = rA;
         const int16_t *x = in + r.sample_off;
-        const uint32_t wlen = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.len);
+        const uint32_t wlen = r.len;
         uint64_t pos;
         const bool room = place_header(r, gA, nA, ex + offA, pos);
         for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
@@ -333,18 +333,18 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             if (lane == 0) s_ticket[cyc & 3u] = atomicAdd(ctrl + 32, 1u);
         }
         __syncthreads();
-        const uint32_t T = s_ticket[cyc & 3u];
+        const uint32_t T = rfl(s_ticket[cyc & 3u]);  // (one address, written before the barrier)
         // the ticket before: its total to the scanner, and where in it this wavefront's waveform lies
         if (cyc) {
             uint64_t sum = 0, before = 0;
 #pragma unroll
             for (int i = 0; i < WV; ++i) {
-                const uint64_t m = s_mine[(cyc - 1u) & 1u][i];
+                const uint64_t m = rfl64(s_mine[(cyc - 1u) & 1u][i]);
                 sum += m;
                 before += i < wv ? m : 0ull;
             }
             offA = before;
-            if (threadIdx.x == 0) es_store(size + Tprev, kEsFlag | sum);
+            if (wv == 0 && lane == 0) es_store(size + Tprev, kEsFlag | sum);
         }
         // a waveform that did not fit is streamed before the next one takes the ring
         if (pend && !fitsA) stream_out(wait_place());
@@ -357,9 +357,9 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             continue;
         }
 
-        WaveRef r = locate(G, g);
+        const WaveRef r = locate_uniform(G, g);
         const int16_t *x = in + r.sample_off;
-        const uint32_t wlen = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.len);
+        const uint32_t wlen = r.len;
 
         // words this waveform may take: up to the waveform in front of it in the ring, or the whole ring
         auto gap = [&]() -> uint32_t {
@@ -377,13 +377,11 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         auto wrap = [&](uint32_t bits) -> uint32_t { return bits >= kRingBits ? bits - kRingBits : bits; };
         auto process_tile = [&](const uint32_t (&w)[4], int nv, auto full_tag) {
             constexpr bool FULLT = decltype(full_tag)::value;
-            uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
-            if (lane == 0) xprev = carry;
+            const uint32_t xprev = wave_shr1_carry(w[3], carry);
             carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
             uint32_t xprev2 = 0;
             if (GEN) {
-                xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-                if (lane == 0) xprev2 = carry2;
+                xprev2 = wave_shr1_carry(w[2], carry2);
                 carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
             }
             PackedCodes cc;
@@ -396,10 +394,14 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             // Waveform A leaves the ring here if a sibling has seen the ticket's place meanwhile (a word in LDS) -- or if this
             // tile would run into it: the one point at which a wavefront may have to WAIT for a place.
+            // The tile's last word against the words the ring has left: once per tile, and again only behind a copy_out.
+            // (32 bits: while `fits` holds P is below the ring's 2^17 bits, and a scalar 64-bit `<` does not exist)
+            const uint32_t need = ((uint32_t)P + tile_bits + 31u) >> 5;
+            bool ok = fits && need < limit;
             if (pend) {
                 uint64_t ex;
                 const bool seen = place_in_lds(ex);
-                const bool must = fits && ((P + tile_bits + 31u) >> 5) >= (uint64_t)limit;
+                const bool must = fits && !ok;
                 if (seen || must) {
                     // A wavefront that has to wait for its place is AHEAD of the stream's frontier; one that finds the place of
                     // its last waveform almost as soon as it looks is what the others are waiting for.  Issue priority on
@@ -409,9 +411,10 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                     else __builtin_amdgcn_s_setprio(1);
                     copy_out(seen ? ex : wait_place());
                     limit = gap();
+                    ok = fits && need < limit;
                 }
             }
-            if (fits && ((P + tile_bits + 31u) >> 5) < (uint64_t)limit) {
+            if (ok) {
                 const uint32_t s0 = start * 32u + (uint32_t)P;  // the tile's first bit, from the ring's word 0, not wrapped
                 if (FULLT && !__any(lane_bits > 128u))
                     place_words(cw, ring_bits0 + wrap(s0 + incl));
@@ -502,6 +505,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         pend = true;
         fitsA = fits;
         gA = g;
+        rA = r;
         TA = T;
         startA = start;
         nA = n;
@@ -640,7 +644,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
     static_assert((kEsFront + RING + kEsBack) % 4 == 0 && RING % 4 == 0, "16-byte LDS accesses");
     static_assert(WV == (int)kEsSegWaves, "es_seg_shape() counts tickets of kEsSegWaves segments");
     constexpr uint32_t kRingBits = RING * 32u;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int lane = lane_id(), wv = wave_id();
     uint32_t *row = ring_all[wv];
     uint32_t *ring = row + kEsFront;
     const uint32_t ring_bits0 = lds_addr(ring) * 8u;
@@ -653,7 +657,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
     for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
     __syncthreads();
     const uint64_t n_tickets = G.total_waves * tpw;
-    if (s_role == 0) {
+    if (rfl(s_role) == 0) {
         es_scanner_segs(n_tickets, tpw, G.u_n_waves, size, place, st);
         return;
     }
@@ -665,6 +669,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
     bool pend = false, fitsA = true, lastA = false, sibA = false;  // sibA: the next segment is the next wavefront's, same ticket
     uint64_t gA = 0, offA = 0;  // its waveform; bits of its ticket in front of it (known behind the next rendezvous)
     uint32_t TA = 0, startA = 0, nA = 0, bitsA = 0, sbeginA = 0, sendA = 0, parA = 0;  // nA: ring words, bitsA: bits of the segment proper, parA: its cycle's parity
+    WaveRef rA = {};            // where its waveform lies in the batch, from the moment it was located
 
     // header words and bookkeeping of segment A at its place; B = the waveform-relative bit it begins at
     auto headers = [&](const WaveRef &r, const EsPlace2 &pl, uint64_t B) {
@@ -688,7 +693,6 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
     };
     // copies segment A out, shifted to its bit position, and clears its part of the ring
     auto copy_out = [&](const EsPlace2 &pl) {
-        const WaveRef rA = locate(G, gA);
         const uint64_t B = pl.bits + offA;               // bits of the waveform in front of the segment
         headers(rA, pl, B);
         const uint64_t w0 = pl.whdr + 1ull + (B >> 5);   // output word that holds the segment's first bit
@@ -742,9 +746,9 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
     };
     auto place_in_lds = [&](EsPlace2 &pl) -> bool {
         const uint32_t t = __hip_atomic_load((lds_u32 *)&s_place_t[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if ((uint32_t)__builtin_amdgcn_readfirstlane((int)t) != TA + 1u) return false;
-        pl.whdr = __hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        pl.bits = __hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (rfl(t) != TA + 1u) return false;
+        pl.whdr = rfl64(__hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        pl.bits = rfl64(__hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         return true;
     };
     auto place_to_lds = [&](const EsPlace2 &pl) {
@@ -787,7 +791,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
     // A segment that outgrew the ring is coded a second time, tile by tile through the (empty) ring's first words, straight to
     // its place: from the bit it starts at inside its first output word, so that staged words ARE output words.
     auto stream_out = [&](const EsPlace2 &pl) {
-        const WaveRef r = locate(G, gA);
+        const WaveRef &r = rA;
         const uint64_t B = pl.bits + offA;
         headers(r, pl, B);
         for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
@@ -862,26 +866,26 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
             if (lane == 0) s_ticket[cyc & 3u] = atomicAdd(ctrl + 32, 1u);
         }
         __syncthreads();
-        const uint32_t T = s_ticket[cyc & 3u];
+        const uint32_t T = rfl(s_ticket[cyc & 3u]);  // (one address, written before the barrier)
         // the ticket before: its total to the scanner, and the bits of it in front of this wavefront's segment
         if (cyc) {
             uint64_t sum = 0, before = 0;
 #pragma unroll
             for (int i = 0; i < WV; ++i) {
-                const uint64_t m = s_mine[(cyc - 1u) & 1u][i];
+                const uint64_t m = rfl64(s_mine[(cyc - 1u) & 1u][i]);
                 sum += m;
                 before += i < wv ? m : 0ull;
             }
             offA = before;
-            if (threadIdx.x == 0) es_store(size + Tprev, kEsFlag | sum);
+            if (wv == 0 && lane == 0) es_store(size + Tprev, kEsFlag | sum);
         }
         if (pend && !fitsA) stream_out(wait_place());
         if ((uint64_t)T >= n_tickets) break;
         Tprev = T;
         const uint32_t gw = T / tpw, tj = T - gw * tpw;
         const uint64_t g = gw;
-        WaveRef r = locate(G, g);
-        const uint32_t wlen = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.len);
+        const WaveRef r = locate_uniform(G, g);
+        const uint32_t wlen = r.len;
         const uint32_t sgi = tj * (uint32_t)WV + (uint32_t)wv;
         const uint64_t sb64 = (uint64_t)sgi * seg_len;
         if (sb64 >= wlen) {  // (a waveform's last ticket: no segment for this wavefront, it only keeps the rendezvous)
@@ -925,13 +929,11 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         // mark: the lane (wave uniform, -1: none) whose first sample is the first one BEHIND the segment proper
         auto process_tile = [&](const uint32_t (&w)[4], int nv, int mark, auto full_tag) {
             constexpr bool FULLT = decltype(full_tag)::value;
-            uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);  // wave_shr:1
-            if (lane == 0) xprev = carry;
+            const uint32_t xprev = wave_shr1_carry(w[3], carry);
             carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
             uint32_t xprev2 = 0;
             if (GEN) {
-                xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-                if (lane == 0) xprev2 = carry2;
+                xprev2 = wave_shr1_carry(w[2], carry2);
                 carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
             }
             PackedCodes cc;
@@ -943,19 +945,22 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
             const uint32_t incl = wave_incl_scan_dpp(lane_bits);
             const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             if (!FULLT && mark >= 0) seg_bits = (uint32_t)P + (mark ? (uint32_t)__builtin_amdgcn_readlane((int)incl, mark - 1) : 0u);
+            const uint32_t need = ((uint32_t)P + tile_bits + 31u) >> 5;  // (32 bits: P < 2^17 while `fits` holds)
+            bool ok = fits && need < limit;
             if (pend) {
                 EsPlace2 pl;
                 const bool seen = place_in_lds(pl);
-                const bool must = fits && ((P + tile_bits + 31u) >> 5) >= (uint64_t)limit;
+                const bool must = fits && !ok;
                 if (seen || must) {
                     if (!seen) __builtin_amdgcn_s_setprio(0);
                     else if (P < (uint64_t)(4u * kTile * 7u)) __builtin_amdgcn_s_setprio(2);
                     else __builtin_amdgcn_s_setprio(1);
                     copy_out(seen ? pl : wait_place());
                     limit = gap();
+                    ok = fits && need < limit;
                 }
             }
-            if (fits && ((P + tile_bits + 31u) >> 5) < (uint64_t)limit) {
+            if (ok) {
                 const uint32_t s0 = start * 32u + (uint32_t)P;
                 if (FULLT && !__any(lane_bits > 128u))
                     place_words(cw, ring_bits0 + wrap(s0 + incl));
@@ -1048,6 +1053,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         pend = true;
         fitsA = fits;
         gA = g;
+        rA = r;
         TA = T;
         startA = start;
         nA = fits ? n : 0u;

@@ -32,7 +32,7 @@ constexpr uint32_t kGtEntries = 256, kGtThreads = 256;
 
 // exclusive prefix sum of v over a workgroup of NT threads (a multiple of 64); *total: the workgroup's sum.  ws: NT / 64 words of LDS
 template <uint32_t NT> __device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *ws, uint64_t *total) {
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int lane = lane_id(), wv = wave_id();
     uint64_t inc = v;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
@@ -44,7 +44,7 @@ template <uint32_t NT> __device__ __forceinline__ uint64_t block_excl_scan(uint6
     __syncthreads();
     uint64_t before = 0, all = 0;
 #pragma unroll
-    for (uint32_t w = 0; w < NT / 64; ++w) { before += ((int)w < wv) ? ws[w] : 0u; all += ws[w]; }
+    for (uint32_t w = 0; w < NT / 64; ++w) { const uint64_t s = rfl64(ws[w]); before += ((int)w < wv) ? s : 0u; all += s; }
     *total = all;
     return before + inc - v;
 }
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void k_gather_waves(uint64_t total_waves, cons
     if (ctrl[0]) return;
     const uint32_t lane = (uint32_t)lane_id();
     const uint64_t n_items = n_sel * slots, stride = (uint64_t)gridDim.x * 4u;
-    for (uint64_t it = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); it < n_items; it += stride) {
+    for (uint64_t it = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_id(); it < n_items; it += stride) {
         const uint64_t e = it / slots;
         const uint32_t slot = (uint32_t)(it - e * slots);
         const uint64_t g = sel[e];

@@ -50,9 +50,6 @@ struct PcChunk {
     uint32_t j;  // workgroup inside the chunk
 };
 
-__device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t rfl64(uint64_t v) { return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v); }
-
 // workgroup (ticket) T -> chunk
 __device__ __forceinline__ PcChunk pc_locate(const Geom &G, uint32_t T, bool packed) {
     PcChunk q;

@@ -272,7 +272,7 @@ __global__ __launch_bounds__(kSwThreads) void k_walk_sparse(Geom G, const uint32
     __shared__ uint32_t s_bad;
     const uint32_t tid = threadIdx.x;
     const int lane = lane_id();
-    const uint32_t wv = tid >> 6;
+    const uint32_t wv = (uint32_t)wave_id();
     const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
     uint32_t W, L, N;
     uint64_t base;
@@ -328,8 +328,8 @@ __global__ __launch_bounds__(kSwThreads) void k_walk_sparse(Geom G, const uint32
             }
             // a payload word is plausible once in a million, and this kernel looks at millions: a start counts only if the
             // word it points to is plausible too (or the chunk's end): one dependent load per cut
-            const uint32_t nxt = found + 1u + cw[found];  // (<= len_w: plausible())
-            if (nxt == len_w || plausible(cw[nxt], nxt)) break;
+            const uint32_t nxt = found + 1u + rfl(cw[found]);  // (<= len_w: plausible())
+            if (nxt == len_w || plausible(rfl(cw[nxt]), nxt)) break;
             from = found + 1u;
             found = len_w;
         }
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(kSwThreads) void k_walk_sparse(Geom G, const uint32
     if (s_bad || s_base[64] != W) { if (tid == 0) fail[c] = 1u; return; }
     bool bad = false;
     for (uint32_t sg = wv; sg < S; sg += blockDim.x >> 6) {
-        const uint32_t cnt = s_cnt[sg], b0 = s_base[sg];
+        const uint32_t cnt = rfl(s_cnt[sg]), b0 = rfl(s_base[sg]);
         for (uint32_t i = (uint32_t)lane; i < cnt; i += 64u) {
             const uint32_t at = s_list[sg][i];
             const uint32_t n = (i + 1u < cnt ? s_list[sg][i + 1u] : s_a[sg + 1u]) - at - 1u;  // (the chain arrived at the next one's start)
@@ -834,7 +834,7 @@ __global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t 
                                                          const uint32_t *__restrict__ list) {
     __shared__ uint64_t wsum[4];
     const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
-    const int lane = lane_id(), wv = threadIdx.x >> 6;
+    const int lane = lane_id(), wv = wave_id();
     uint64_t base;
     uint32_t W, L, N;
     if (G.uniform) { base = c * G.u_n_waves; W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; }
@@ -861,7 +861,7 @@ __global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t 
         bad = __syncthreads_or(bad || !n_ok) != 0;
         uint64_t before = 0, all = 0;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) { before += (w < wv) ? wsum[w] : 0u; all += wsum[w]; }
+        for (int w = 0; w < 4; ++w) { const uint64_t s = rfl64(wsum[w]); before += (w < wv) ? s : 0u; all += s; }
         bool mine_bad = bad;
         if (i < W) {
             const uint64_t at = off0 + run + before + inc - v;
