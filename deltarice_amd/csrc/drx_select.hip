@@ -43,6 +43,8 @@ __global__ __launch_bounds__(64) void k_decode_select(Geom G, const uint32_t *__
     __shared__ uint32_t col[kSelRows * NT];
     const uint32_t tid = threadIdx.x;
     const uint32_t k = G.k;
+    // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream (k_gather_scan's rule)
+    if (st->err) return;
 
     for (uint64_t e = blockIdx.x; e < n_sel; e += gridDim.x) {
         const uint64_t g = sel[e];
@@ -188,6 +190,7 @@ __global__ __launch_bounds__(64) void k_select_serial(Geom G, const uint32_t *__
     __shared__ int16_t hist[64][64];  // [sample mod 64][lane]
     const uint32_t lane = threadIdx.x;
     const uint64_t e = (uint64_t)blockIdx.x * 64u + lane;
+    if (st->err) return;  // (as k_decode_select)
     if (e >= n_sel) return;
     const uint64_t g = sel[e];
     if (g >= G.total_waves) return;

@@ -147,8 +147,10 @@ drx_status drx_decode_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint
  * written: the samples between rows keep what they held.  Otherwise asynchronous on the context's stream like drx_decode;
  * errors found on the device arrive at drx_plan_finish.
  *   Only the chunks that hold a selected waveform are walked (whole, with drx_decode's validation of the header chain: a
- * corrupt touched chunk is reported as drx_decode reports it).  The other chunks are NEITHER READ NOR VALIDATED, and
- * drx_plan_wave_words / drx_plan_wave_word_off after the call are valid for the touched chunks only.
+ * corrupt touched chunk is reported as drx_decode reports it, and then no waveform is decoded: d_out keeps what it held; a
+ * payload found damaged while it is parsed is reported too, and which other rows were written by then is undefined).  The other
+ * chunks are NEITHER READ NOR VALIDATED, and drx_plan_wave_words / drx_plan_wave_word_off after the call are valid for the
+ * touched chunks only.
  *   DRX_ERR_ARG, with nothing launched: an index >= total_waves, out_stride_samples below the longest selected waveform,
  * n_sel >= 2^32, a NULL pointer with n_sel > 0.  n_sel == 0: DRX_OK, nothing launched.
  *   Every prediction filter the plan accepts: the delta filter a wavefront per selected waveform (parallel inside the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on the GPU: random batch shapes (uniform and ragged), waveform lengths from 1 to
 hundreds of thousands, every k, several signal kinds, general filters; GPU encode must equal the oracle's
-bytes and GPU decode (default path and the variants a shape can take) must return the input.
+bytes and GPU decode (default path and the variants a shape can take) must return the input; a random selection of each
+batch's waveforms goes through drx_decode_select and drx_gather_encoded, against the same input and the oracle's bytes.
 usage: python tests/fuzz_parity.py [cases] [seed]   (test infrastructure: it uses the oracle)"""
 import os
 import sys
@@ -35,6 +36,22 @@ def data(rng, kind, n, k):
 
 def dev(ctx, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
+
+
+def waves(Ns, Ls):
+    """-> (first sample, length) of every waveform of the batch."""
+    start, length, at = [], [], 0
+    for N, L in zip(Ns, Ls):
+        s = np.arange(0, N, L, dtype=np.int64)
+        start.append(at + s)
+        length.append(np.minimum(L, N - s))
+        at += N
+    return np.concatenate(start), np.concatenate(length)
+
+
+def pick(srng, n_waves, longest):
+    """How many waveforms a case selects: up to 64, fewer of very long ones (2 M samples a list: the sweep stays a sweep)."""
+    return int(srng.integers(1, max(1, min(64, n_waves, 2_000_000 // longest)) + 1))
 
 
 def main():
@@ -141,6 +158,41 @@ def main():
             assert eb == words[0].tobytes(), "host path encode"
             db = np.frombuffer(ctx.filter_chunk(eb, opts0, reverse=True), np.int16)
             assert np.array_equal(db, expect[:Ns[0]]), "host path decode"
+            # selected waveforms: decoded alone, and regrouped without decoding (drawn from a generator of their own: the case
+            # sequence of a seed does not depend on them)
+            srng = np.random.default_rng((seed, it))
+            start, length = waves(Ns, Ls)
+            ftaps = (len(taps),) + tuple(t & 0xFFFFFFFF for t in taps) if taps else ()
+            ed = xd if lossless else dev(ctx, expect)
+            sel = srng.integers(0, start.size, pick(srng, start.size, int(length.max())))
+            for tab in (None, table):
+                log(f"  select {sel.size} side-band {tab is not None}")
+                y = plan.decode_select(enc, sel, wave_words=tab)
+                assert plan.last_decode_path() == D.PATH_SELECT
+                for i, g in enumerate(sel):
+                    s, n = int(start[g]), int(length[g])
+                    assert torch.equal(y[i, :n], ed[s:s + n]) and not bool(y[i, n:].any()), f"select row {i} (side-band {tab is not None})"
+            same = np.nonzero(length == length[srng.integers(0, start.size)])[0]  # one length: any chunking of them is a batch
+            gsel = srng.choice(same, pick(srng, same.size, int(length[same[0]])))
+            cw = int(srng.integers(1, gsel.size + 1))
+            Lg = int(length[gsel[0]])
+            want = [O.encode_chunk(np.concatenate([x[start[g]:start[g] + Lg] for g in gsel[c0:c0 + cw]]), (1 << k, Lg) + ftaps)
+                    for c0 in range(0, gsel.size, cw)]
+            want_off = np.cumsum([0] + [w.size for w in want])
+            gflags = D.DBG_GATHER_OTHER_COPY if it & 1 else 0
+            ctx.set_option("debug_flags", gflags)
+            for tab in (None, table):
+                log(f"  gather {gsel.size} by {cw} flags {gflags} side-band {tab is not None}")
+                got = plan.gather_encoded(enc, gsel, cw, wave_words=tab)
+                assert plan.last_decode_path() == D.PATH_GATHER
+                assert np.array_equal(got.enc.chunk_word_off.cpu().numpy(), want_off), f"gather offsets (side-band {tab is not None})"
+                assert np.array_equal(got.enc.words.cpu().numpy().view(np.uint32), np.concatenate(want)), f"gather (side-band {tab is not None})"
+                if not lossless:  # ... and what those bytes decode to: the oracle's decode of the source
+                    gp = got.plan(ctx)
+                    rows = torch.cat([ed[start[g]:start[g] + Lg] for g in gsel])
+                    assert torch.equal(gp.decode(got.enc), rows), "gather, decoded"
+                    gp.close()
+            ctx.set_option("debug_flags", 0)
             if os.environ.get("DRX_FUZZ_CORRUPT"):
                 # payload bits flipped (headers intact): any result or DRX_ERR_CORRUPT is fine, a fault is not
                 bad = ref_w.copy()
@@ -160,6 +212,19 @@ def main():
                         pass
                 ctx.set_option("debug_flags", 0)
                 ctx.set_option("decode_impl", 8)
+                # ... and through the selections (the select kernels follow no table once a walk has failed; the gather copies
+                # nothing then): any rows or DRX_ERR_CORRUPT; behind an error the gather has written nothing
+                for tab in (None, table):
+                    log(f"  corrupt select / gather side-band {tab is not None}")
+                    try:
+                        plan.decode_select(encb, sel, wave_words=tab)
+                    except dr.DeltaRiceError:
+                        pass
+                    out = torch.full((int(want_off[-1]) + 64,), 0x5A5A5A5A, dtype=torch.int32, device=ctx.device)
+                    try:
+                        plan.gather_encoded(encb, gsel, cw, wave_words=tab, out_words=out)
+                    except dr.DeltaRiceError:
+                        assert bool((out == 0x5A5A5A5A).all()), "gather wrote behind an error"
         except Exception as e:  # noqa: BLE001
             print("FAIL", label, "->", repr(e), flush=True)
             return 1

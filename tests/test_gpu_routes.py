@@ -98,8 +98,7 @@ def make_plan(ctx, Ns, Ls, m, taps):
     if len(set(Ns)) == 1 and len(set(Ls)) == 1:
         opts = ((m, Ls[0]) if Ls[0] else (m,)) + ((len(taps),) + tuple(t & 0xFFFFFFFF for t in taps) if taps else ())
         return ctx.plan_uniform(len(Ns), Ns[0], opts)
-    assert taps is None
-    return ctx.plan(Ns, Ls, m)
+    return ctx.plan(Ns, Ls, m, taps)
 
 
 def observe(ctx, name):
