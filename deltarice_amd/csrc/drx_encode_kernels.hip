@@ -61,7 +61,7 @@ __device__ __forceinline__ void rice_code(int32_t d, uint32_t k, uint32_t &code,
 // samples that exist, every partial sum truncated to int16 -- i.e. the sum mod 2^16.
 __device__ __forceinline__ int32_t fir_residual(const int16_t *__restrict__ x, uint32_t i, const Geom &G) {
     uint32_t acc = 0;
-    for (uint32_t t = 0; t < G.n_taps && t <= i; ++t) acc += (uint32_t)((int32_t)x[i - t] * G.taps[t]);
+    for (uint32_t t = 0; t < G.n_taps && t <= i; ++t) acc += (uint32_t)(int32_t)x[i - t] * (uint32_t)G.taps[t];
     return (int32_t)(int16_t)(uint16_t)acc;
 }
 

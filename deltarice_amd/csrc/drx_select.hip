@@ -221,7 +221,7 @@ __global__ __launch_bounds__(64) void k_select_serial(Geom G, const uint32_t *__
         } else {
             // general inverse (:92-101): y[i] = (int16)((int16)(d[i] - sum_{j>=1} taps[j] y[i-j]) / taps[0])
             uint32_t a = (uint32_t)(int32_t)(int16_t)d;
-            for (uint32_t j = 1; j < G.n_taps && j <= i; ++j) a -= (uint32_t)((int32_t)hist[(i - j) & 63u][lane] * G.taps[j]);
+            for (uint32_t j = 1; j < G.n_taps && j <= i; ++j) a -= (uint32_t)(int32_t)hist[(i - j) & 63u][lane] * (uint32_t)G.taps[j];
             acc = (int32_t)(int16_t)(uint16_t)a / G.taps[0];
             hist[i & 63u][lane] = (int16_t)acc;
         }

@@ -110,7 +110,9 @@ drx_status drx_plan_create_uniform(drx_ctx *ctx, uint64_t n_chunks, uint32_t chu
  *   ... and taps[0] = +-1      the fast decoders: a lane per waveform with the recurrence in the lane, or -- few long waveforms --
  *                              the block decoder with the inverse filter inside it (DRX_PATH_IIR_FUSED) or as a parallel pass of
  *                              its own behind it (DRX_PATH_IIR);
- *   anything else              the two-pass encoder and the simple decode kernel (DRX_PATH_SIMPLE): a lane per waveform, serial. */
+ *   anything else              the two-pass encoder and the simple decode kernel (DRX_PATH_SIMPLE): a lane per waveform, serial.
+ * The arithmetic is the reference's modulo 2^16, the division by the whole int32 taps[0] towards zero; tests/test_gpu_filter_domain.py
+ * holds every route to it over this domain (1 to 64 taps, coefficients up to the int32 extremes, any lead but 0). */
 drx_status drx_plan_set_filter(drx_plan *plan, uint32_t n_taps, const int32_t *taps);
 void drx_plan_destroy(drx_plan *plan);
 uint64_t drx_plan_n_chunks(const drx_plan *plan);

@@ -92,7 +92,7 @@ void dro_filter_forward(const int16_t *x, int16_t *d, long n, const dro_opts *o)
     for (long i = 0; i < n; ++i) {
         uint32_t acc = 0;
         for (int j = 0; j < o->n_taps && j <= i; ++j)
-            acc += (uint32_t)((int32_t)x[i - j] * o->taps[j]);
+            acc += (uint32_t)(int32_t)x[i - j] * (uint32_t)o->taps[j];
         d[i] = (int16_t)(uint16_t)acc;
     }
 }
@@ -103,7 +103,7 @@ void dro_filter_inverse(const int16_t *d, int16_t *y, long n, const dro_opts *o)
     for (long i = 0; i < n; ++i) {
         uint32_t acc = (uint32_t)(int32_t)d[i];
         for (int j = 1; j < o->n_taps && j <= i; ++j)
-            acc -= (uint32_t)((int32_t)y[i - j] * o->taps[j]);
+            acc -= (uint32_t)(int32_t)y[i - j] * (uint32_t)o->taps[j];
         int32_t t = (int16_t)(uint16_t)acc;
         y[i] = (int16_t)(t / o->taps[0]);
     }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on the GPU: random batch shapes (uniform and ragged), waveform lengths from 1 to
-hundreds of thousands, every k, several signal kinds, general filters; GPU encode must equal the oracle's
+hundreds of thousands, every k, several signal kinds, general filters of 1 to 64 taps; GPU encode must equal the oracle's
 bytes and GPU decode (default path and the variants a shape can take) must return the input; a random selection of each
 batch's waveforms goes through drx_decode_select and drx_gather_encoded, against the same input and the oracle's bytes.
 usage: python tests/fuzz_parity.py [cases] [seed]   (test infrastructure: it uses the oracle)"""
@@ -83,6 +83,17 @@ def main():
         if rng.random() < 0.2:  # (ragged batches too: drx_plan_set_filter applies to every chunk)
             nt = int(rng.integers(1, 6))
             taps = [int(rng.choice([1, -1])) if rng.random() < 0.8 else int(rng.integers(2, 5))] + [int(v) for v in rng.integers(-3, 4, nt - 1)]
+        if taps is not None and k != 0:
+            # a third of the filtered cases: the rest of what drx_plan_set_filter accepts -- 6 to 64 taps, coefficients of the
+            # whole int16 range, now and then an int32 extreme, leads that are no unit or one only modulo 2^16.  Drawn from a
+            # generator of their own (as srng below): the case sequence of a seed stays what it was.  Not at k = 0: such
+            # residuals are full range, and M = 1 is defined only while z < 32768.
+            frng = np.random.default_rng((seed, it, 64))
+            if frng.random() < 1 / 3:
+                nt = int(frng.integers(6, 65))
+                taps = [int(frng.choice([1, -1, 2, -2, 3, -3, 65537, -32767]))] + [int(v) for v in frng.integers(-32767, 32768, nt - 1)]
+                if frng.random() < 0.25:
+                    taps[int(frng.integers(1, nt))] = int(frng.choice([2 ** 31 - 1, -2 ** 31, 65536, -65537]))
         if ragged:
             Ls = [int(rng.choice(Lc)) for _ in range(n_chunks)]
             Ns = [int(min(400000 * scale, max(1, L * int(rng.integers(1, 40 * scale)) + int(rng.integers(0, L))))) for L in Ls]

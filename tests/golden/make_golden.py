@@ -4,7 +4,8 @@
 Run where the reference tree is present (it needs oracle/_ref, built by
 `make -C oracle ref` from the reference's src/deltaRice.c, unmodified):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py                # everything
+    python tests/golden/make_golden.py ref_filters    # tests/golden/ref_filters.json alone
 
 Every case is an (opts, words) pair: `words` are the uint32 words the reference's
 H5Z_filter_deltarice (src/deltaRice.c:468-490, OpenMP build) emitted for one chunk.
@@ -17,6 +18,7 @@ from __future__ import annotations
 import hashlib
 import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -141,7 +143,28 @@ def write_random_trials():
     print(f"{len(trials)} random trials")
 
 
+def write_ref_filters():
+    """ref_filters.json: the reference's bytes and decoded samples for the filter table of tests/filter_reference.py, one entry
+    of digests per filter over its cases inside the reference's domain (the inputs are regenerated from the table's seeds).
+    The reference runs in a child process under a time limit, as in tests/test_filter_reference.py."""
+    tests = os.path.dirname(HERE)
+    r = subprocess.run([sys.executable, os.path.join(tests, "ref_filters_child.py"), "omp"], capture_output=True, text=True,
+                       timeout=120, check=True)
+    filters = [json.loads(line) for line in r.stdout.splitlines()]
+    head = json.dumps({"generator": "tests/golden/make_golden.py (write_ref_filters)",
+                       "source": "reference src/deltaRice.c compiled unmodified (oracle/Makefile, -fopenmp build)",
+                       "domain": "tests/filter_reference.py in_reference_domain(): |tap| <= 32767, L >= 4 W, staging buffer not overrun"},
+                      indent=1)
+    with open(os.path.join(HERE, "ref_filters.json"), "w") as f:  # (a line per filter)
+        f.write(head[:-2] + ',\n "filters": [\n' + ",\n".join("  " + json.dumps(d, separators=(",", ":")) for d in filters) + "\n ]\n}\n")
+    print(f"{len(filters)} filters, {sum(d['n_cases'] for d in filters)} cases")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "ref_filters":  # (this file alone; golden.npz stays as it is)
+        if not O.have_ref("omp"):
+            sys.exit("oracle/_ref missing: run `make -C oracle ref` where /root/reference exists")
+        return write_ref_filters()
     if not O.have_ref("omp"):
         sys.exit("oracle/_ref missing: run `make -C oracle ref` where /root/reference exists")
     arrays, manifest = {}, []
@@ -168,6 +191,7 @@ def main():
                    "cases": manifest}, f, indent=1)
     print(f"{len(manifest)} cases, {os.path.getsize(os.path.join(HERE, 'golden.npz'))} bytes")
     write_random_trials()
+    write_ref_filters()
 
 
 if __name__ == "__main__":

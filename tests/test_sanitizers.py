@@ -45,6 +45,21 @@ def test_oracle_golden_suite_under_asan_ubsan(san):
     assert "AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]
 
 
+def test_oracle_filter_extremes_under_ubsan(san):
+    """The named filters of tests/filter_reference.py (taps up to the int32 extremes, where a signed product overflows) through
+    the instrumented restatement: its arithmetic modulo 2^16 is defined C."""
+    env = dict(os.environ, DRO_ORACLE_SO=os.path.join(san, "libdeltarice_oracle_asan.so"), LD_PRELOAD=_libasan(),
+               ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
+               OMP_NUM_THREADS="4")
+    # (-s: a halting sanitizer's report must not die with pytest's capture; the seeded filters' names all hold "mag")
+    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-s", "-p", "no:cacheprovider", "-k", "statement and not mag",
+                        os.path.join(ROOT, "tests", "test_filter_reference.py")],
+                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=900)
+    out = r.stdout + r.stderr
+    assert r.returncode == 0 and "12 passed" in r.stdout, out[-4000:]
+    assert "AddressSanitizer" not in out and "runtime error:" not in out, out[-4000:]
+
+
 def test_filter_callback_failure_paths_under_asan_lsan(san):
     # leaks are checked too: whatever the HIP runtime itself keeps after a failed initialisation is not ours
     supp = os.path.join(san, "lsan.supp")
