@@ -1,6 +1,14 @@
-// Packed 16-bit Rice coding of a 512-sample tile (64 lanes x 8 samples) and its emission into an LDS bit buffer: shared by
-// the single-pass encoders (k_encode_fused in drx_encode_kernels.hip, k_encode_pieces in drx_pieces.hip) and the segment
-// encoder.  Device code only; included by the .hip translation units.
+// Packed 16-bit Rice coding of a 512-sample tile (64 lanes x 8 samples), its emission into an LDS bit buffer, and the loops
+// the single-pass encoders build from them.  Device code only; included by the .hip translation units.  Who uses what:
+//   packed_codes .. place_words   the tile arithmetic: every user below, and k_encode_pieces' own tile (drx_pieces.hip), which
+//                                 rewrites a lane's history per waveform and so keeps its own front half
+//   code_tile, put_tile           four dwords -> codes, lengths, scan, and into LDS: k_encode_fused, for_segment_tiles
+//                                 (drx_encode_kernels.hip), k_encode_stream, k_encode_stream_segs (drx_encode_stream.hip),
+//                                 recode_tiles
+//   for_full_tiles                the three-deep load pipeline: k_encode_fused and both stream kernels
+//   recode_waveform, recode_range, history_before
+//                                 a waveform or a sample range whose code outgrew its LDS buffer, coded again straight to its
+//                                 place: k_encode_fused, both stream kernels, k_encode_pieces
 #ifndef DRX_ENCODE_H
 #define DRX_ENCODE_H
 #include <hip/hip_runtime.h>
@@ -171,6 +179,179 @@ __device__ __forceinline__ void place_words(const uint32_t (&wd)[4], uint32_t pe
         __hip_atomic_fetch_or(w + 1, x3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (x4) __hip_atomic_fetch_or(w, x4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
+}
+
+// ---------------------------------------------------------------------------
+// one tile, from its samples to LDS
+// ---------------------------------------------------------------------------
+constexpr uint32_t kBufFront = 4;  // pad words in front of an LDS bit buffer (place_words writes up to four words below a lane's last)
+
+__device__ __forceinline__ void zero_row(uint32_t *row, uint32_t words, int lane) {  // (16-byte aligned, a multiple of four words)
+    for (int i = lane; i < (int)(words / 4u); i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
+}
+
+// A tile's codes: cw = the lane's 8 codes as one string (FULLT only), incl = inclusive scan of lane_bits over the lanes.
+struct TileCodes {
+    PackedCodes c;
+    uint32_t cw[4], lane_bits, incl, tile_bits;
+};
+
+// w: the lane's 8 samples; carry / carry2: the dwords whose high halves are samples -1 and -3 of the tile (wave uniform;
+// x[-1] := 0 in front of a waveform, src/deltaRice.c:53-54), moved on to the next tile.  FULLT: all 512 samples exist;
+// otherwise nv of the lane's 8.
+template <bool GEN, bool FULLT>
+__device__ __forceinline__ TileCodes code_tile(const uint32_t (&w)[4], int nv, uint32_t &carry, uint32_t &carry2, const u16x2 (&tp)[4],
+                                               uint32_t k) {
+    TileCodes t;
+    const uint32_t xprev = wave_shr1_carry(w[3], carry);
+    carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
+    uint32_t xprev2 = 0;
+    if (GEN) {
+        xprev2 = wave_shr1_carry(w[2], carry2);
+        carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
+    }
+    packed_codes<GEN>(w, xprev, xprev2, tp, k, t.c);
+    if (!FULLT) mask_tail(t.c, nv);
+    t.lane_bits = lane_tile_bits(t.c);
+    if (FULLT) concat_codes(t.c, t.cw);  // independent of the scan: fills its DPP wait states
+    t.incl = wave_incl_scan_dpp(t.lane_bits);
+    t.tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)t.incl, 63);
+    return t;
+}
+
+// The tile into LDS: at(bit) = 8 * (LDS byte address of the buffer's word 0) + the buffer bit of the tile's bit `bit`.
+template <bool FULLT, typename At>
+__device__ __forceinline__ void put_tile(const TileCodes &t, At &&at) {
+    if (FULLT && !__any(t.lane_bits > 128u))
+        place_words(t.cw, at(t.incl));
+    else
+        emit_tile<FULLT>(t.c, at(t.incl - t.lane_bits));
+}
+
+// The full tiles of x[0, 512 n_full): full(w) for each, between() in front of every group of kDepth.
+// kDepth tiles of loads in flight, in kDepth fixed register sets (the loop is unrolled by kDepth so that no
+// loaded-but-not-yet-arrived register is ever copied): with 4 waves per SIMD a tile takes ~2.6 K cycles of wall time, less
+// than one HBM round trip under load (PMC: 76 % of the wave cycles were s_waitcnt with one tile in flight).  16-byte loads at
+// any int16 alignment (unaligned access is on for HSA queues): a WaveformLength like 3500 puts every other waveform 8 bytes
+// off a 16-byte boundary, an odd one 2 bytes off a dword, and the per-sample fallback is 2x slower.
+template <typename B, typename F>
+__device__ __forceinline__ void for_full_tiles(const int16_t *__restrict__ x, uint32_t n_full, int lane, B &&between, F &&full) {
+    constexpr int kDepth = 3;
+    const uint4 *xv = reinterpret_cast<const uint4 *>(x) + lane;  // tile t: xv[64 * t]
+    uint4 q[kDepth];
+    uint32_t t = 0;
+#pragma unroll
+    for (int u = 0; u < kDepth; ++u) {
+        q[u] = make_uint4(0, 0, 0, 0);
+        if ((uint32_t)u < n_full) q[u] = xv[64 * (size_t)u];
+    }
+    // while every register set has a successor tile: consume a set, then refill it -- no predicate on the load, so no copy
+    // of a set and a plain vmcnt(kDepth - 1) in front of each tile
+#pragma unroll 1
+    for (; t + 2u * kDepth <= n_full; t += kDepth) {
+        between();
+#pragma unroll
+        for (int u = 0; u < kDepth; ++u) {
+            const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+            full(w);
+            q[u] = xv[64 * (size_t)(t + u + kDepth)];
+        }
+    }
+    // drain: the last kDepth..2 kDepth - 1 full tiles
+#pragma unroll 1
+    for (; t < n_full; t += kDepth) {
+        between();
+#pragma unroll
+        for (int u = 0; u < kDepth; ++u) {
+            if (t + (uint32_t)u < n_full) {
+                const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+                full(w);
+                if (t + (uint32_t)u + kDepth < n_full) q[u] = xv[64 * (size_t)(t + u + kDepth)];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// coded once more, tile by tile, straight to its place
+// ---------------------------------------------------------------------------
+// What a waveform, segment or part whose code outgrew its LDS buffer gets: a second read of its samples, each tile coded
+// through the first words of the (cleared) row -- from bit P0 of outp[0] on, so that staged words ARE output words -- and
+// its full words stored at once; the partly filled word becomes word 0 of the next tile.  The next tile's samples travel
+// while this one is coded.  WINDOW: only the words [skip, limit) below `cap` are stored.  Returns the bit behind the last
+// code; the row is left zeroed.
+template <bool GEN, bool WINDOW>
+__device__ __forceinline__ uint64_t recode_tiles(const int16_t *__restrict__ x, uint32_t len, uint32_t carry, uint32_t carry2,
+                                                 const u16x2 (&tp)[4], uint32_t k, int lane, uint32_t *row, uint32_t row_words,
+                                                 uint32_t *__restrict__ outp, uint32_t P0, uint32_t skip, uint32_t limit, uint64_t cap) {
+    zero_row(row, row_words, lane);
+    wave_sync();
+    uint32_t *buf = row + kBufFront;
+    const uint32_t buf_bits = lds_addr(buf) * 8u;
+    auto mine = [&](uint64_t idx) -> bool { return !WINDOW || (idx >= skip && idx < limit && idx < cap); };
+    uint64_t P = P0;
+    uint32_t wn[4];
+    int nvn = load8_dwords(x, len, 0u, lane, true, wn);
+    for (uint32_t t0 = 0; t0 < len; t0 += kTile) {
+        const uint32_t w[4] = {wn[0], wn[1], wn[2], wn[3]};
+        const int nv = nvn;
+        if (t0 + kTile < len) nvn = load8_dwords(x, len, t0 + kTile, lane, true, wn);
+        const TileCodes t = code_tile<GEN, false>(w, nv, carry, carry2, tp, k);
+        const uint64_t wfirst = P >> 5;  // first staged word
+        const uint32_t at0 = buf_bits + (uint32_t)(P & 31u);
+        put_tile<false>(t, [&](uint32_t bit) -> uint32_t { return at0 + bit; });
+        P += t.tile_bits;
+        wave_sync();
+        const uint32_t nfull = (uint32_t)((P >> 5) - wfirst);
+        for (uint32_t i = lane; i < nfull; i += 64) {
+            if (mine(wfirst + i)) outp[wfirst + i] = buf[i];
+            buf[i] = 0;
+        }
+        wave_sync();
+        if (nfull && lane == 0) { const uint32_t cwd = buf[nfull]; buf[nfull] = 0; buf[0] = cwd; }
+        wave_sync();
+    }
+    if (lane == 0) {
+        if ((P & 31u) && mine(P >> 5)) outp[P >> 5] = buf[0];  // last word left aligned, zero padded (:237-241)
+        buf[0] = 0;
+    }
+    wave_sync();
+    return P;
+}
+
+// a whole waveform x[0, len), from bit 0 of outp[0]; returns its bits
+template <bool GEN>
+__device__ __forceinline__ uint64_t recode_waveform(const int16_t *__restrict__ x, uint32_t len, const u16x2 (&tp)[4], uint32_t k, int lane,
+                                                    uint32_t *row, uint32_t row_words, uint32_t *__restrict__ outp) {
+    return recode_tiles<GEN, false>(x, len, 0u, 0u, tp, k, lane, row, row_words, outp, 0u, 0u, 0u, 0ull);
+}
+
+// The filter's history in front of x[0], a sample that does not begin its waveform: the dwords a tile's first lane takes
+// for the lane below (carry: samples -2, -1; GEN only: carry2: samples -4, -3).
+template <bool GEN>
+__device__ __forceinline__ void history_before(const int16_t *__restrict__ x, uint32_t &carry, uint32_t &carry2) {
+    carry = (uint32_t)(uint16_t)x[-1] << 16;
+    if (GEN) {
+        carry |= (uint32_t)(uint16_t)x[-2];
+        carry2 = (uint32_t)(uint16_t)x[-4] | ((uint32_t)(uint16_t)x[-3] << 16);
+    }
+}
+
+// Samples [s_begin, s_end) of the waveform xw[0, wf_len), whose code is bits [Bp, Bp + bits_mine) of the waveform's stream
+// payload[0, cap_words).  The word in which they start belongs to whoever codes the samples in front; the word in which they
+// end is completed from the (up to) 32 samples that follow (at least a bit each), coded here too: wavefronts exchange nothing
+// and no word is written twice.
+template <bool GEN>
+__device__ __forceinline__ void recode_range(const int16_t *__restrict__ xw, uint32_t wf_len, uint32_t s_begin, uint32_t s_end, uint64_t Bp,
+                                             uint32_t bits_mine, const u16x2 (&tp)[4], uint32_t k, int lane, uint32_t *row,
+                                             uint32_t row_words, uint32_t *__restrict__ payload, uint64_t cap_words) {
+    const uint32_t P0 = (uint32_t)(Bp & 31u);
+    const uint64_t wbase = Bp >> 5;
+    const uint32_t more = wf_len - s_end < 32u ? wf_len - s_end : 32u;
+    uint32_t carry = 0, carry2 = 0;
+    if (s_begin) history_before<GEN>(xw + s_begin, carry, carry2);
+    recode_tiles<GEN, true>(xw + s_begin, s_end - s_begin + more, carry, carry2, tp, k, lane, row, row_words, payload + wbase, P0,
+                            P0 ? 1u : 0u, (P0 + bits_mine + 31u) >> 5, cap_words > wbase ? cap_words - wbase : 0ull);
 }
 
 }  // namespace drx

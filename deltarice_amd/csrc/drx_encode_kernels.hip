@@ -342,105 +342,41 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
     const uint64_t g = (uint64_t)rfl(s_ticket) * kEncWaves + (uint32_t)wv;  // (one address, written before the barrier)
     const bool live = g < G.total_waves;  // the last workgroup may be partial; its idle waves still join the barriers
 
-    for (int i = lane; i < (int)(kEncCapWords + 8) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
+    zero_row(row, kEncCapWords + 8u, lane);
     WaveRef r = locate_uniform(G, live ? g : 0);
     if (!live) { r.len = 0; r.idx = 1; }  // an idle wave of the last workgroup: nothing to encode, nothing to add
     const int16_t *x = in + r.sample_off;
-    // 16-byte loads at any int16 alignment (unaligned access is on for HSA queues): a WaveformLength like 3500 puts
-    // every other waveform 8 bytes off a 16-byte boundary, an odd one 2 bytes off a dword, and the per-sample
-    // fallback is 2x slower
-    const bool vec_ok = true;
     const uint32_t k = G.k;
     wave_sync();
 
     // ---- pass over the samples: emit into LDS while it fits, count bits always ----
-    // The next tile's load is issued before the current tile is processed, so that the HBM
-    // round trip (PMC: 76 % of the wave cycles were s_waitcnt without this) overlaps the packing.
     uint64_t P = 0;        // bits so far (wave uniform)
     bool fits = true;      // everything so far is in buf (wave uniform)
     uint32_t carry = 0;    // dword whose high half is the sample before the tile (x[-1] := 0, :53-54)
     uint32_t carry2 = 0;   // GEN: the dword before that one (samples -4, -3)
     const u16x2 tp[4] = {splat(GEN ? G.enc_t[0] : 1u), splat(GEN ? G.enc_t[1] : 0xffffu), splat(GEN ? G.enc_t[2] : 0u),
                          splat(GEN ? G.enc_t[3] : 0u)};
-    // Full tiles run in a loop without any masking, with the next tile's 16-byte load in flight
-    // while the current one is packed; the trailing partial tile (if any) takes the masked path once.
+    // Full tiles run without any masking, with the next tiles' 16-byte loads in flight while the current one is packed
+    // (for_full_tiles); the trailing partial tile (if any) takes the masked path once.
     auto process_tile = [&](const uint32_t (&w)[4], int nv, auto full_tag) {
         constexpr bool FULLT = decltype(full_tag)::value;
-        const uint32_t xprev = wave_shr1_carry(w[3], carry);
-        carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
-        uint32_t xprev2 = 0;
-        if (GEN) {
-            xprev2 = wave_shr1_carry(w[2], carry2);
-            carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
-        }
-        PackedCodes c;
-        packed_codes<GEN>(w, xprev, xprev2, tp, k, c);
-        if (!FULLT) mask_tail(c, nv);
-        const uint32_t lane_bits = lane_tile_bits(c);
-        uint32_t cw[4];
-        if (FULLT) concat_codes(c, cw);  // independent of the scan: fills its DPP wait states
-        const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-        const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const TileCodes t = code_tile<GEN, FULLT>(w, nv, carry, carry2, tp, k);
         // (32 bits: while `fits` holds P is below the buffer's 2^17 bits, and a scalar 64-bit `<` does not exist)
-        if (fits && (((uint32_t)P + tile_bits + 31u) >> 5) < kEncCapWords) {
-            if (FULLT && !__any(lane_bits > 128u))
-                place_words(cw, buf_bits + (uint32_t)P + incl);
-            else
-                emit_tile<FULLT>(c, buf_bits + (uint32_t)P + incl - lane_bits);
-        } else {
+        if (fits && (((uint32_t)P + t.tile_bits + 31u) >> 5) < kEncCapWords)
+            put_tile<FULLT>(t, [&](uint32_t bit) -> uint32_t { return buf_bits + (uint32_t)P + bit; });
+        else
             fits = false;
-        }
-        P += tile_bits;
+        P += t.tile_bits;
     };
     // (r.len is wave uniform, locate_uniform(): otherwise the tile loop is compiled with per-lane predicates, register
     // copies and a full vmcnt(0) in front of every tile)
     const uint32_t wlen = r.len;
     const uint32_t n_full = wlen / kTile;
-    {
-        // kDepth tiles of loads in flight, in kDepth fixed register sets (the loop is unrolled by
-        // kDepth so that no loaded-but-not-yet-arrived register is ever copied): with 4 waves per
-        // SIMD a tile takes ~2.6 K cycles of wall time, less than one HBM round trip under load.
-        constexpr int kDepth = 3;
-        const uint4 *xv = reinterpret_cast<const uint4 *>(x) + lane;  // tile t: xv[64 * t]
-        uint4 q[kDepth];
-        uint32_t t = 0;
-        if (vec_ok) {
-#pragma unroll
-            for (int u = 0; u < kDepth; ++u) {
-                q[u] = make_uint4(0, 0, 0, 0);
-                if ((uint32_t)u < n_full) q[u] = xv[64 * (size_t)u];
-            }
-            // while every register set has a successor tile: consume a set, then refill it -- no predicate
-            // on the load, so no copy of a set and a plain vmcnt(kDepth - 1) in front of each tile
-#pragma unroll 1
-            for (; t + 2u * kDepth <= n_full; t += kDepth) {
-#pragma unroll
-                for (int u = 0; u < kDepth; ++u) {
-                    const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                    process_tile(w, 8, std::true_type{});
-                    q[u] = xv[64 * (size_t)(t + u + kDepth)];
-                }
-            }
-            // drain: the last kDepth..2 kDepth - 1 full tiles
-#pragma unroll 1
-            for (; t < n_full; t += kDepth) {
-#pragma unroll
-                for (int u = 0; u < kDepth; ++u) {
-                    if (t + (uint32_t)u < n_full) {
-                        const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                        process_tile(w, 8, std::true_type{});
-                        if (t + (uint32_t)u + kDepth < n_full) q[u] = xv[64 * (size_t)(t + u + kDepth)];
-                    }
-                }
-            }
-            t = n_full;
-        }
-        // unaligned waveforms, and the trailing partial tile
-        for (uint32_t t0 = t * kTile; t0 < wlen; t0 += kTile) {
-            uint32_t w[4];
-            const int nv = load8_dwords(x, wlen, t0, lane, vec_ok, w);
-            process_tile(w, nv, std::false_type{});
-        }
+    for_full_tiles(x, n_full, lane, [] {}, [&](const uint32_t (&w)[4]) { process_tile(w, 8, std::true_type{}); });
+    for (uint32_t t0 = n_full * kTile; t0 < wlen; t0 += kTile) {
+        uint32_t w[4];
+        const int nv = load8_dwords(x, wlen, t0, lane, true, w);
+        process_tile(w, nv, std::false_type{});
     }
     const uint32_t n = (uint32_t)((P + 31u) >> 5);  // payload words n_i
     wave_sync();
@@ -561,44 +497,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
         return;
     }
 
-    // ---- the code did not fit the LDS buffer: stream it tile by tile to its final position ----
-    for (int i = lane; i < (int)(kEncCapWords + 8) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
-    wave_sync();
-    P = 0;
-    carry = 0;
-    carry2 = 0;
-    uint32_t wn[4];
-    int nvn = r.len ? load8_dwords(x, r.len, 0u, lane, vec_ok, wn) : 0;
-    for (uint32_t t0 = 0; t0 < r.len; t0 += kTile) {
-        uint32_t w[4] = {wn[0], wn[1], wn[2], wn[3]};
-        const int nv = nvn;
-        if (t0 + kTile < r.len) nvn = load8_dwords(x, r.len, t0 + kTile, lane, vec_ok, wn);  // (travels while this tile is coded)
-        uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);
-        if (lane == 0) xprev = carry;
-        carry = (uint32_t)__shfl((int)w[3], 63);
-        uint32_t xprev2 = 0;
-        if (GEN) {
-            xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-            if (lane == 0) xprev2 = carry2;
-            carry2 = (uint32_t)__shfl((int)w[2], 63);
-        }
-        PackedCodes c;
-        packed_codes<GEN>(w, xprev, xprev2, tp, k, c);
-        mask_tail(c, nv);
-        const uint32_t lane_bits = lane_tile_bits(c);
-        const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-        const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        const uint64_t w0 = P >> 5;  // first staged word
-        emit_tile<false>(c, buf_bits + (uint32_t)(P & 31u) + incl - lane_bits);
-        P += tile_bits;
-        wave_sync();
-        const uint32_t nfull = (uint32_t)((P >> 5) - w0);
-        for (uint32_t i = lane; i < nfull; i += 64) { outp[w0 + i] = buf[i]; buf[i] = 0; }
-        wave_sync();
-        if (nfull && lane == 0) { const uint32_t cw = buf[nfull]; buf[nfull] = 0; buf[0] = cw; }
-        wave_sync();
-    }
-    if ((P & 31u) && lane == 0) outp[P >> 5] = buf[0];
+    // ---- the code did not fit the LDS buffer: coded again, tile by tile, to its final position ----
+    recode_waveform<GEN>(x, wlen, tp, k, lane, row, kEncCapWords + 8u, outp);
 }
 
 // ---------------------------------------------------------------------------
@@ -672,7 +572,7 @@ __device__ __forceinline__ SegRef locate_seg_uniform(const Geom &G, uint64_t u, 
 template <typename F>
 __device__ __forceinline__ void for_segment_tiles(const int16_t *__restrict__ xw, const SegRef &q, uint32_t k, int lane, F &&tile) {
     const int16_t *x = xw + q.start;
-    const bool vec_ok = true;  // any int16 alignment (see k_encode_fused)
+    const bool vec_ok = true;  // any int16 alignment (see for_full_tiles, drx_encode.h)
     // dword whose high half is the sample before the segment (x[-1] := 0 at the start of the waveform, :53-54)
     // (a unit past the end of a shorter last waveform has count == 0: nothing of it may be touched)
     uint32_t carry = (q.start && q.count) ? rfl((uint32_t)(uint16_t)xw[q.start - 1u] << 16) : 0u;

@@ -22,6 +22,14 @@
 //     waveform was the whole kernel's rate (profiles/r04_notes.md section 1).
 // Output bytes are those of k_encode_fused (and of src/deltaRice.c): a waveform's place is the same prefix sum.
 //
+// Two kernels run this machine: k_encode_stream over waveforms and k_encode_stream_segs over segments of long waveforms.
+// Shared, below ("the machine both coders share"): the rendezvous (es_rendezvous), the ring's free words (es_gap), the
+// decision to copy unit A out in front of a tile (es_release), the emission into the ring with its fold-back (ring_put), the
+// grid (es_grid); from drx_encode.h: a tile's codes (code_tile), the load pipeline (for_full_tiles), the coding-again of a unit
+// that outgrew the ring (recode_waveform, recode_range).  Each kernel's own: its place type (one word / EsPlace2) with
+// place_in_lds, place_to_lds, wait_place and between; copy_out; place_header / headers; its scanner; and the segment form's
+// `mark` and s_first.
+//
 // Look-back state (d_scan, zeroed before the launch): total[tickets] | place[tickets] | role counter, ticket counter (a
 // 128-byte line each).  An entry is its own flag (bit 63), written and polled with relaxed agent-scope atomics, as in every
 // look-back of this library.
@@ -39,7 +47,7 @@ namespace drx {
 // wavefronts per workgroup = waveforms per ticket; 16 wavefronts per CU either way (4: 4.95 ms on the headline, 8: 5.1 -- the
 // rendezvous of four costs less than that of eight; with the priority feedback below 4.80 / 4.84)
 constexpr int kEsWaves = 4;
-constexpr uint32_t kEsFront = 4;   // pad words in front of a ring (place_words writes up to four words below a lane's last)
+constexpr uint32_t kEsFront = kBufFront;  // pad words in front of a ring
 constexpr uint32_t kEsBack = 12;   // ... and behind it (emit_tile runs up to eight codes past a lane's first word)
 constexpr uint64_t kEsFlag = 1ull << 63;
 constexpr uint32_t kEsCtrlWords = 32;  // uint64 words of control state: 128 bytes each for the role and the ticket counter
@@ -133,6 +141,113 @@ __device__ __forceinline__ void es_scanner(uint64_t total, const uint64_t *__res
 }
 
 // ---------------------------------------------------------------------------
+// the machine both coders share
+// ---------------------------------------------------------------------------
+// What the wavefronts of a workgroup share besides their rings and the place of a ticket (one word or two: per kernel).
+template <int WV>
+struct EsShared {
+    uint32_t role, arrive, ticket[4];
+    uint64_t mine[2][WV];  // sizes of the units (waveforms: words, segments: bits) of the last two tickets
+    uint32_t place_t[2];   // which ticket (+ 1) the kernel's s_place_v holds, once one wavefront has seen its place
+};
+
+// ---- which units: a ticket per workgroup and WV units, taken by its wavefronts TOGETHER ----
+// A unit's place needs every EARLIER unit's size, so the order of the indices has to be the order in which the work
+// is started, to within the slack a ring gives (~10 us).  Two forms that broke this were measured (profiles/r04_notes.md
+// section 1): wavefronts taking the next index of their workgroup's ticket whenever they were free drift apart, a
+// ticket's last waveform is then begun a whole waveform's time after its first, and every place arrives that much later;
+// an index per wavefront from eight global counters keeps the order but puts a 3 us returning atomic in front of every
+// waveform's first load (data returns in order) and arrives in bursts.  So: a rendezvous of the workgroup's wavefronts per
+// unit.  Whoever arrives first draws the ticket -- its round trip runs while the others finish -- and the barrier
+// costs what the slowest of WV costs.
+// Returns the ticket of cycle `cyc`.  Behind the barrier the ticket before (Tprev) is complete: its total goes to the
+// scanner, and `off` becomes the part of it in front of this wavefront's unit.
+template <int WV>
+__device__ __forceinline__ uint32_t es_rendezvous(EsShared<WV> &shm, uint32_t cyc, int lane, int wv, uint32_t *__restrict__ ctrl,
+                                                  uint64_t *__restrict__ size, uint32_t Tprev, uint64_t &off) {
+    typedef uint32_t __attribute__((address_space(3))) lds_u32;
+    uint32_t arr = 0;
+    if (lane == 0) arr = __hip_atomic_fetch_add((lds_u32 *)&shm.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    arr = (uint32_t)__builtin_amdgcn_readfirstlane((int)arr);
+    if (arr == (uint32_t)WV * cyc) {
+        if (lane == 0) shm.ticket[cyc & 3u] = atomicAdd(ctrl + 32, 1u);
+    }
+    __syncthreads();
+    const uint32_t T = rfl(shm.ticket[cyc & 3u]);  // (one address, written before the barrier)
+    if (cyc) {
+        uint64_t sum = 0, before = 0;
+#pragma unroll
+        for (int i = 0; i < WV; ++i) {
+            const uint64_t m = rfl64(shm.mine[(cyc - 1u) & 1u][i]);
+            sum += m;
+            before += i < wv ? m : 0ull;
+        }
+        off = before;
+        if (wv == 0 && lane == 0) es_store(size + Tprev, kEsFlag | sum);
+    }
+    return T;
+}
+
+// words the unit being coded from ring word `start` on may take: up to unit A in front of it in the ring (less `behind`
+// words), or the whole ring
+template <uint32_t RING>
+__device__ __forceinline__ uint32_t es_gap(bool pend, uint32_t startA, uint32_t start, uint32_t behind) {
+    if (!pend) return RING - 8u;
+    const uint32_t d = startA >= start ? startA - start : startA + RING - start;
+    return d > behind ? d - behind : 0u;
+}
+
+// Unit A leaves the ring in front of a tile if a sibling has seen its ticket's place meanwhile (a word in LDS) -- or if the
+// tile would run into it (`must`): the one point at which a wavefront may have to WAIT for a place.  P: bits of the unit
+// being coded so far.  Returns whether A was copied out.
+template <typename InLds, typename Wait, typename Copy>
+__device__ __forceinline__ bool es_release(bool must, uint64_t P, InLds &&place_in_lds, Wait &&wait_place, Copy &&copy_out) {
+    decltype(wait_place()) pl;
+    const bool seen = place_in_lds(pl);
+    if (!(seen || must)) return false;
+    // A wavefront that has to wait for its place is AHEAD of the stream's frontier; one that finds the place of
+    // its last waveform almost as soon as it looks is what the others are waiting for.  Issue priority on
+    // the SIMD follows (4.96-5.02 -> 4.79-4.83 ms on the headline; more levels or other thresholds: the same).
+    if (!seen) __builtin_amdgcn_s_setprio(0);
+    else if (P < (uint64_t)(4u * kTile * 7u)) __builtin_amdgcn_s_setprio(2);
+    else __builtin_amdgcn_s_setprio(1);
+    copy_out(seen ? pl : wait_place());
+    return true;
+}
+
+// The tile into the ring at ring bit s0 (from the ring's word 0, not wrapped; row = the ring with its pads).
+template <bool FULLT, uint32_t RING>
+__device__ __forceinline__ void ring_put(const TileCodes &t, uint32_t *row, uint32_t s0, int lane) {
+    constexpr uint32_t kRingBits = RING * 32u;
+    uint32_t *ring = row + kEsFront;
+    const uint32_t ring_bits0 = lds_addr(ring) * 8u;
+    put_tile<FULLT>(t, [&](uint32_t bit) -> uint32_t {
+        const uint32_t b = s0 + bit;
+        return ring_bits0 + (b >= kRingBits ? b - kRingBits : b);
+    });
+    if (s0 < kRingBits && s0 + t.tile_bits >= kRingBits) {
+        // the tile ran across the end of the ring: what its lanes wrote into the pads belongs to the other end
+        wave_sync();
+        if (lane < (int)kEsFront) {
+            const uint32_t v = row[lane];
+            if (v) { ring[RING - kEsFront + lane] |= v; row[lane] = 0; }
+        } else if (lane < (int)(kEsFront + kEsBack)) {
+            const uint32_t i = (uint32_t)lane - kEsFront, v = ring[RING + i];
+            if (v) { ring[i] |= v; ring[RING + i] = 0; }
+        }
+        wave_sync();
+    }
+}
+
+// persistent: 16 wavefronts per CU, one workgroup of them the scanner's; never more than the batch can feed
+// (DRX_DBG_STREAM_THREE_WGS: three workgroups -- a scanner and two coders -- so that a small test batch takes every wavefront
+// through many units, i.e. around its ring)
+static unsigned es_grid(const Geom &G, uint64_t tickets) {
+    const unsigned full = 256u * (16u / kEsWaves);
+    return (G.dbg & DRX_DBG_STREAM_THREE_WGS) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
+}
+
+// ---------------------------------------------------------------------------
 // the coders
 // ---------------------------------------------------------------------------
 template <bool GEN, int WV, uint32_t RING>
@@ -142,28 +257,25 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                                                               uint64_t *__restrict__ place, uint32_t *__restrict__ ctrl,
                                                               DevStatus *st) {
     __shared__ __attribute__((aligned(16))) uint32_t ring_all[WV][kEsFront + RING + kEsBack];
-    __shared__ uint32_t s_role, s_arrive, s_ticket[4];
-    __shared__ uint64_t s_mine[2][WV];              // sizes of the waveforms of the last two tickets
-    __shared__ uint64_t s_place_v[2];               // place of a ticket, once one wavefront has seen it ...
-    __shared__ uint32_t s_place_t[2];               // ... and which ticket (+ 1) that was
+    __shared__ EsShared<WV> shm;
+    __shared__ uint64_t s_place_v[2];  // place of a ticket, once one wavefront has seen it (shm.place_t: which ticket)
     typedef uint32_t __attribute__((address_space(3))) lds_u32;
     typedef uint64_t __attribute__((address_space(3))) lds_u64;
     static_assert((kEsFront + RING + kEsBack) % 4 == 0 && RING % 4 == 0, "16-byte LDS accesses");
-    constexpr uint32_t kRingBits = RING * 32u;
+    constexpr uint32_t kRowWords = kEsFront + RING + kEsBack;
     const int lane = lane_id(), wv = wave_id();
     uint32_t *row = ring_all[wv];
     uint32_t *ring = row + kEsFront;
-    const uint32_t ring_bits0 = lds_addr(ring) * 8u;
 
     if (threadIdx.x == 0) {
-        s_role = atomicAdd(ctrl, 1u);
-        s_arrive = 0;
-        s_place_t[0] = s_place_t[1] = 0;
+        shm.role = atomicAdd(ctrl, 1u);
+        shm.arrive = 0;
+        shm.place_t[0] = shm.place_t[1] = 0;
     }
-    for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
+    zero_row(row, kRowWords, lane);
     __syncthreads();
     const uint64_t n_tickets = (G.total_waves + WV - 1) / WV;
-    if (rfl(s_role) == 0) {  // the first workgroup to start sweeps the totals; everybody else codes
+    if (rfl(shm.role) == 0) {  // the first workgroup to start sweeps the totals; everybody else codes
         es_scanner(n_tickets, size, place, st);
         return;
     }
@@ -224,7 +336,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     };
     // Ticket TA's place, if a wavefront of this workgroup has seen it already (they all need the same word).
     auto place_in_lds = [&](uint64_t &ex) -> bool {
-        const uint32_t t = __hip_atomic_load((lds_u32 *)&s_place_t[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t t = __hip_atomic_load((lds_u32 *)&shm.place_t[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (rfl(t) != TA + 1u) return false;
         ex = rfl64(__hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         return true;
@@ -232,7 +344,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
     auto place_to_lds = [&](uint64_t ex) {
         if (lane == 0) {  // (value, then tag: LDS operations of one wavefront are performed in order)
             __hip_atomic_store((lds_u64 *)&s_place_v[TA & 1u], ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store((lds_u32 *)&s_place_t[TA & 1u], TA + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store((lds_u32 *)&shm.place_t[TA & 1u], TA + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     };
     // the same, waiting for it (bounded; a wait that expires reports kErrInternal and returns a place nothing is written to)
@@ -260,99 +372,26 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         }
     };
 
-    // A waveform that outgrew the ring (incompressible data, long waveforms) is coded a second time, tile by tile through the
-    // (empty) ring's first words, straight to its place: a second read of its samples.
+    // A waveform that outgrew the ring (incompressible data, long waveforms) is coded again to its place, through the ring,
+    // which is cleared for that (no room for the waveform: cleared only)
     auto stream_out = [&](uint64_t ex) {
-        const WaveRef &r = rA;
-        const int16_t *x = in + r.sample_off;
-        const uint32_t wlen = r.len;
         uint64_t pos;
-        const bool room = place_header(r, gA, nA, ex + offA, pos);
-        for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
-        wave_sync();
+        const bool room = place_header(rA, gA, nA, ex + offA, pos);
+        recode_waveform<GEN>(in + rA.sample_off, room ? rA.len : 0u, tp, k, lane, row, kRowWords, out + pos + 1);
         pend = false;
-        if (!room) return;
-        uint32_t *__restrict__ outp = out + pos + 1;
-        uint32_t *buf = ring;
-        uint64_t P = 0;
-        uint32_t carry = 0, carry2 = 0;
-        uint32_t wn[4];
-        int nvn = wlen ? load8_dwords(x, wlen, 0u, lane, true, wn) : 0;
-        for (uint32_t t0 = 0; t0 < wlen; t0 += kTile) {
-            uint32_t w[4] = {wn[0], wn[1], wn[2], wn[3]};
-            const int nv = nvn;
-            if (t0 + kTile < wlen) nvn = load8_dwords(x, wlen, t0 + kTile, lane, true, wn);  // (travels while this tile is coded)
-            uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);
-            if (lane == 0) xprev = carry;
-            carry = (uint32_t)__shfl((int)w[3], 63);
-            uint32_t xprev2 = 0;
-            if (GEN) {
-                xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-                if (lane == 0) xprev2 = carry2;
-                carry2 = (uint32_t)__shfl((int)w[2], 63);
-            }
-            PackedCodes cc;
-            packed_codes<GEN>(w, xprev, xprev2, tp, k, cc);
-            mask_tail(cc, nv);
-            const uint32_t lane_bits = lane_tile_bits(cc);
-            const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-            const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint64_t w0 = P >> 5;  // first staged word
-            emit_tile<false>(cc, ring_bits0 + (uint32_t)(P & 31u) + incl - lane_bits);
-            P += tile_bits;
-            wave_sync();
-            const uint32_t nfull = (uint32_t)((P >> 5) - w0);
-            for (uint32_t i = lane; i < nfull; i += 64) { outp[w0 + i] = buf[i]; buf[i] = 0; }
-            wave_sync();
-            if (nfull && lane == 0) { const uint32_t cwd = buf[nfull]; buf[nfull] = 0; buf[0] = cwd; }
-            wave_sync();
-        }
-        if (lane == 0) {
-            if (P & 31u) outp[P >> 5] = buf[0];
-            buf[0] = 0;
-        }
-        wave_sync();
     };
 
-    // ---- which waveforms: a ticket per workgroup and WV waveforms, taken by its wavefronts TOGETHER ----
-    // A waveform's place needs every EARLIER waveform's size, so the order of the indices has to be the order in which the work
-    // is started, to within the slack a ring gives (~10 us).  Two forms that broke this were measured (profiles/r04_notes.md
-    // section 1): wavefronts taking the next index of their workgroup's ticket whenever they were free drift apart, a
-    // ticket's last waveform is then begun a whole waveform's time after its first, and every place arrives that much later;
-    // an index per wavefront from eight global counters keeps the order but puts a 3 us returning atomic in front of every
-    // waveform's first load (data returns in order) and arrives in bursts.  So: a rendezvous of the workgroup's wavefronts per
-    // waveform.  Whoever arrives first draws the ticket -- its round trip runs while the others finish -- and the barrier
-    // costs what the slowest of WV costs.
     uint32_t start = 0;  // first ring word of the waveform being coded (a multiple of four)
     uint32_t Tprev = 0;
     for (uint32_t cyc = 0;; ++cyc) {
-        uint32_t arr = 0;
-        if (lane == 0) arr = __hip_atomic_fetch_add((lds_u32 *)&s_arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        arr = (uint32_t)__builtin_amdgcn_readfirstlane((int)arr);
-        if (arr == (uint32_t)WV * cyc) {
-            if (lane == 0) s_ticket[cyc & 3u] = atomicAdd(ctrl + 32, 1u);
-        }
-        __syncthreads();
-        const uint32_t T = rfl(s_ticket[cyc & 3u]);  // (one address, written before the barrier)
-        // the ticket before: its total to the scanner, and where in it this wavefront's waveform lies
-        if (cyc) {
-            uint64_t sum = 0, before = 0;
-#pragma unroll
-            for (int i = 0; i < WV; ++i) {
-                const uint64_t m = rfl64(s_mine[(cyc - 1u) & 1u][i]);
-                sum += m;
-                before += i < wv ? m : 0ull;
-            }
-            offA = before;
-            if (wv == 0 && lane == 0) es_store(size + Tprev, kEsFlag | sum);
-        }
+        const uint32_t T = es_rendezvous(shm, cyc, lane, wv, ctrl, size, Tprev, offA);
         // a waveform that did not fit is streamed before the next one takes the ring
         if (pend && !fitsA) stream_out(wait_place());
         if ((uint64_t)T * WV >= G.total_waves) break;
         Tprev = T;
         const uint64_t g = (uint64_t)T * WV + (uint32_t)wv;
         if (g >= G.total_waves) {  // (the batch's last ticket: this wavefront only keeps the rendezvous)
-            if (lane == 0) s_mine[cyc & 1u][wv] = 0;
+            if (lane == 0) shm.mine[cyc & 1u][wv] = 0;
             if (pend) copy_out(wait_place());  // (offA is this waveform's only until the next rendezvous)
             continue;
         }
@@ -361,12 +400,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         const int16_t *x = in + r.sample_off;
         const uint32_t wlen = r.len;
 
-        // words this waveform may take: up to the waveform in front of it in the ring, or the whole ring
-        auto gap = [&]() -> uint32_t {
-            if (!pend) return RING - 8u;
-            const uint32_t d = startA >= start ? startA - start : startA + RING - start;
-            return d > 8u ? d - 8u : 0u;
-        };
+        auto gap = [&]() -> uint32_t { return es_gap<RING>(pend, startA, start, 8u); };
         if (pend && gap() < 512u) copy_out(wait_place());  // (short waveforms behind a long one: no room to start)
         uint32_t limit = gap();
 
@@ -374,68 +408,22 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         bool fits = true;      // everything so far is in the ring (wave uniform)
         uint32_t carry = 0;    // dword whose high half is the sample before the tile (x[-1] := 0, :53-54)
         uint32_t carry2 = 0;   // GEN: the dword before that one
-        auto wrap = [&](uint32_t bits) -> uint32_t { return bits >= kRingBits ? bits - kRingBits : bits; };
         auto process_tile = [&](const uint32_t (&w)[4], int nv, auto full_tag) {
             constexpr bool FULLT = decltype(full_tag)::value;
-            const uint32_t xprev = wave_shr1_carry(w[3], carry);
-            carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
-            uint32_t xprev2 = 0;
-            if (GEN) {
-                xprev2 = wave_shr1_carry(w[2], carry2);
-                carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
-            }
-            PackedCodes cc;
-            packed_codes<GEN>(w, xprev, xprev2, tp, k, cc);
-            if (!FULLT) mask_tail(cc, nv);
-            const uint32_t lane_bits = lane_tile_bits(cc);
-            uint32_t cw[4];
-            if (FULLT) concat_codes(cc, cw);  // independent of the scan: fills its DPP wait states
-            const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-            const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            // Waveform A leaves the ring here if a sibling has seen the ticket's place meanwhile (a word in LDS) -- or if this
-            // tile would run into it: the one point at which a wavefront may have to WAIT for a place.
+            const TileCodes t = code_tile<GEN, FULLT>(w, nv, carry, carry2, tp, k);
             // The tile's last word against the words the ring has left: once per tile, and again only behind a copy_out.
             // (32 bits: while `fits` holds P is below the ring's 2^17 bits, and a scalar 64-bit `<` does not exist)
-            const uint32_t need = ((uint32_t)P + tile_bits + 31u) >> 5;
+            const uint32_t need = ((uint32_t)P + t.tile_bits + 31u) >> 5;
             bool ok = fits && need < limit;
-            if (pend) {
-                uint64_t ex;
-                const bool seen = place_in_lds(ex);
-                const bool must = fits && !ok;
-                if (seen || must) {
-                    // A wavefront that has to wait for its place is AHEAD of the stream's frontier; one that finds the place of
-                    // its last waveform almost as soon as it looks is what the others are waiting for.  Issue priority on
-                    // the SIMD follows (4.96-5.02 -> 4.79-4.83 ms on the headline; more levels or other thresholds: the same).
-                    if (!seen) __builtin_amdgcn_s_setprio(0);
-                    else if (P < (uint64_t)(4u * kTile * 7u)) __builtin_amdgcn_s_setprio(2);
-                    else __builtin_amdgcn_s_setprio(1);
-                    copy_out(seen ? ex : wait_place());
-                    limit = gap();
-                    ok = fits && need < limit;
-                }
+            if (pend && es_release(fits && !ok, P, place_in_lds, wait_place, copy_out)) {
+                limit = gap();
+                ok = fits && need < limit;
             }
-            if (ok) {
-                const uint32_t s0 = start * 32u + (uint32_t)P;  // the tile's first bit, from the ring's word 0, not wrapped
-                if (FULLT && !__any(lane_bits > 128u))
-                    place_words(cw, ring_bits0 + wrap(s0 + incl));
-                else
-                    emit_tile<FULLT>(cc, ring_bits0 + wrap(s0 + incl - lane_bits));
-                if (s0 < kRingBits && s0 + tile_bits >= kRingBits) {
-                    // the tile ran across the end of the ring: what its lanes wrote into the pads belongs to the other end
-                    wave_sync();
-                    if (lane < (int)kEsFront) {
-                        const uint32_t v = row[lane];
-                        if (v) { ring[RING - kEsFront + lane] |= v; row[lane] = 0; }
-                    } else if (lane < (int)(kEsFront + kEsBack)) {
-                        const uint32_t i = (uint32_t)lane - kEsFront, v = ring[RING + i];
-                        if (v) { ring[i] |= v; ring[RING + i] = 0; }
-                    }
-                    wave_sync();
-                }
-            } else {
+            if (ok)
+                ring_put<FULLT, RING>(t, row, start * 32u + (uint32_t)P, lane);
+            else
                 fits = false;
-            }
-            P += tile_bits;
+            P += t.tile_bits;
         };
         const uint32_t n_full = wlen / kTile;
         // between tile groups: is waveform A's place known by now?  The load travels while a group is coded; whoever of the
@@ -456,50 +444,17 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
             polling = true;
         };
 
-        {
-            constexpr int kDepth = 3;
-            const uint4 *xv = reinterpret_cast<const uint4 *>(x) + lane;  // tile t: xv[64 * t]
-            uint4 q[kDepth];
-            uint32_t t = 0;
-#pragma unroll
-            for (int u = 0; u < kDepth; ++u) {
-                q[u] = make_uint4(0, 0, 0, 0);
-                if ((uint32_t)u < n_full) q[u] = xv[64 * (size_t)u];
-            }
-#pragma unroll 1
-            for (; t + 2u * kDepth <= n_full; t += kDepth) {
-                between();
-#pragma unroll
-                for (int u = 0; u < kDepth; ++u) {
-                    const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                    process_tile(w, 8, std::true_type{});
-                    q[u] = xv[64 * (size_t)(t + u + kDepth)];
-                }
-            }
-#pragma unroll 1
-            for (; t < n_full; t += kDepth) {
-                between();
-#pragma unroll
-                for (int u = 0; u < kDepth; ++u) {
-                    if (t + (uint32_t)u < n_full) {
-                        const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                        process_tile(w, 8, std::true_type{});
-                        if (t + (uint32_t)u + kDepth < n_full) q[u] = xv[64 * (size_t)(t + u + kDepth)];
-                    }
-                }
-            }
-            // the trailing partial tile
-            for (uint32_t t0 = n_full * kTile; t0 < wlen; t0 += kTile) {
-                uint32_t w[4];
-                const int nv = load8_dwords(x, wlen, t0, lane, true, w);
-                process_tile(w, nv, std::false_type{});
-            }
+        for_full_tiles(x, n_full, lane, between, [&](const uint32_t (&w)[4]) { process_tile(w, 8, std::true_type{}); });
+        for (uint32_t t0 = n_full * kTile; t0 < wlen; t0 += kTile) {  // the trailing partial tile
+            uint32_t w[4];
+            const int nv = load8_dwords(x, wlen, t0, lane, true, w);
+            process_tile(w, nv, std::false_type{});
         }
         const uint32_t n = (uint32_t)((P + 31u) >> 5);  // payload words n_i
         wave_sync();
         if (lane == 0) {
             wave_words[g] = n;
-            s_mine[cyc & 1u][wv] = 1ull + n + (r.idx == 0 ? 1ull : 0ull);
+            shm.mine[cyc & 1u][wv] = 1ull + n + (r.idx == 0 ? 1ull : 0ull);
         }
         if (pend) copy_out(wait_place());  // (waveforms too short for the look-ups between tile groups)
         pend = true;
@@ -634,30 +589,27 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
                                                                    uint64_t *__restrict__ size, uint64_t *__restrict__ place,
                                                                    uint32_t *__restrict__ ctrl, DevStatus *st) {
     __shared__ __attribute__((aligned(16))) uint32_t ring_all[WV][kEsFront + RING + kEsBack];
-    __shared__ uint32_t s_role, s_arrive, s_ticket[4];
-    __shared__ uint64_t s_mine[2][WV];   // bits of the segments of the last two tickets
-    __shared__ uint64_t s_place_v[2][2];  // place of a ticket (header word, bits in front), once one wavefront has seen it ...
-    __shared__ uint32_t s_place_t[2];     // ... and which ticket (+ 1) that was
+    __shared__ EsShared<WV> shm;
+    __shared__ uint64_t s_place_v[2][2];  // place of a ticket (header word, bits in front), once one wavefront has seen it
     __shared__ uint32_t s_first[2][WV];   // first 32 bits of the segments of the last two tickets (what completes the word the segment in front ends in)
     typedef uint32_t __attribute__((address_space(3))) lds_u32;
     typedef uint64_t __attribute__((address_space(3))) lds_u64;
     static_assert((kEsFront + RING + kEsBack) % 4 == 0 && RING % 4 == 0, "16-byte LDS accesses");
     static_assert(WV == (int)kEsSegWaves, "es_seg_shape() counts tickets of kEsSegWaves segments");
-    constexpr uint32_t kRingBits = RING * 32u;
+    constexpr uint32_t kRowWords = kEsFront + RING + kEsBack;
     const int lane = lane_id(), wv = wave_id();
     uint32_t *row = ring_all[wv];
     uint32_t *ring = row + kEsFront;
-    const uint32_t ring_bits0 = lds_addr(ring) * 8u;
 
     if (threadIdx.x == 0) {
-        s_role = atomicAdd(ctrl, 1u);
-        s_arrive = 0;
-        s_place_t[0] = s_place_t[1] = 0;
+        shm.role = atomicAdd(ctrl, 1u);
+        shm.arrive = 0;
+        shm.place_t[0] = shm.place_t[1] = 0;
     }
-    for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
+    zero_row(row, kRowWords, lane);
     __syncthreads();
     const uint64_t n_tickets = G.total_waves * tpw;
-    if (rfl(s_role) == 0) {
+    if (rfl(shm.role) == 0) {
         es_scanner_segs(n_tickets, tpw, G.u_n_waves, size, place, st);
         return;
     }
@@ -745,7 +697,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         pend = false;
     };
     auto place_in_lds = [&](EsPlace2 &pl) -> bool {
-        const uint32_t t = __hip_atomic_load((lds_u32 *)&s_place_t[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t t = __hip_atomic_load((lds_u32 *)&shm.place_t[TA & 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (rfl(t) != TA + 1u) return false;
         pl.whdr = rfl64(__hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
         pl.bits = rfl64(__hip_atomic_load((lds_u64 *)&s_place_v[TA & 1u][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -755,7 +707,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         if (lane == 0) {  // (values, then tag: LDS operations of one wavefront are performed in order)
             __hip_atomic_store((lds_u64 *)&s_place_v[TA & 1u][0], pl.whdr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_store((lds_u64 *)&s_place_v[TA & 1u][1], pl.bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_store((lds_u32 *)&s_place_t[TA & 1u], TA + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_store((lds_u32 *)&shm.place_t[TA & 1u], TA + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     };
     // lanes 0 and 1 hold the two words of a place (one load instruction): both flagged -> the place
@@ -788,97 +740,19 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         }
     };
 
-    // A segment that outgrew the ring is coded a second time, tile by tile through the (empty) ring's first words, straight to
-    // its place: from the bit it starts at inside its first output word, so that staged words ARE output words.
+    // A segment that outgrew the ring is coded again to its place, through the ring, which is cleared for that
     auto stream_out = [&](const EsPlace2 &pl) {
-        const WaveRef &r = rA;
         const uint64_t B = pl.bits + offA;
-        headers(r, pl, B);
-        for (int i = lane; i < (int)(kEsFront + RING + kEsBack) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
-        wave_sync();
+        headers(rA, pl, B);
+        recode_range<GEN>(in + rA.sample_off, rA.len, sbeginA, sendA, B, bitsA, tp, k, lane, row, kRowWords, out + pl.whdr + 1ull,
+                          out_cap > pl.whdr + 1ull ? out_cap - pl.whdr - 1ull : 0ull);
         pend = false;
-        const uint64_t wbase = pl.whdr + 1ull + (B >> 5);
-        const uint32_t P0 = (uint32_t)B & 31u;
-        const uint32_t limit = (P0 + bitsA + 31u) >> 5, skip = P0 ? 1u : 0u;  // words [skip, limit) from wbase are mine
-        const uint32_t more = r.len - sendA < 32u ? r.len - sendA : 32u;
-        const uint32_t len = sendA - sbeginA + more;
-        const int16_t *x = in + r.sample_off + sbeginA;
-        uint32_t *buf = ring;
-        uint64_t P = P0;
-        uint32_t carry = 0, carry2 = 0;
-        if (sbeginA) {
-            carry = (uint32_t)(uint16_t)x[-1] << 16;
-            if (GEN) {
-                carry |= (uint32_t)(uint16_t)x[-2];
-                carry2 = (uint32_t)(uint16_t)x[-4] | ((uint32_t)(uint16_t)x[-3] << 16);
-            }
-        }
-        uint32_t wn[4];
-        int nvn = load8_dwords(x, len, 0u, lane, true, wn);
-        for (uint32_t t0 = 0; t0 < len; t0 += kTile) {
-            uint32_t w[4] = {wn[0], wn[1], wn[2], wn[3]};
-            const int nv = nvn;
-            if (t0 + kTile < len) nvn = load8_dwords(x, len, t0 + kTile, lane, true, wn);  // (travels while this tile is coded)
-            uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);
-            if (lane == 0) xprev = carry;
-            carry = (uint32_t)__shfl((int)w[3], 63);
-            uint32_t xprev2 = 0;
-            if (GEN) {
-                xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-                if (lane == 0) xprev2 = carry2;
-                carry2 = (uint32_t)__shfl((int)w[2], 63);
-            }
-            PackedCodes cc;
-            packed_codes<GEN>(w, xprev, xprev2, tp, k, cc);
-            mask_tail(cc, nv);
-            const uint32_t lane_bits = lane_tile_bits(cc);
-            const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-            const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint64_t wfirst = P >> 5;  // first staged word
-            emit_tile<false>(cc, ring_bits0 + (uint32_t)(P & 31u) + incl - lane_bits);
-            P += tile_bits;
-            wave_sync();
-            const uint32_t nfull = (uint32_t)((P >> 5) - wfirst);
-            for (uint32_t i = lane; i < nfull; i += 64) {
-                const uint64_t idx = wfirst + i;
-                if (idx >= skip && idx < limit && wbase + idx < out_cap) out[wbase + idx] = buf[i];
-                buf[i] = 0;
-            }
-            wave_sync();
-            if (nfull && lane == 0) { const uint32_t cwd = buf[nfull]; buf[nfull] = 0; buf[0] = cwd; }
-            wave_sync();
-        }
-        if (lane == 0) {
-            const uint64_t idx = P >> 5;
-            if ((P & 31u) && idx >= skip && idx < limit && wbase + idx < out_cap) out[wbase + idx] = buf[0];
-            buf[0] = 0;
-        }
-        wave_sync();
     };
 
     uint32_t start = 0;  // first ring word of the segment being coded (a multiple of four)
     uint32_t Tprev = 0;
     for (uint32_t cyc = 0;; ++cyc) {
-        uint32_t arr = 0;
-        if (lane == 0) arr = __hip_atomic_fetch_add((lds_u32 *)&s_arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        arr = (uint32_t)__builtin_amdgcn_readfirstlane((int)arr);
-        if (arr == (uint32_t)WV * cyc) {
-            if (lane == 0) s_ticket[cyc & 3u] = atomicAdd(ctrl + 32, 1u);
-        }
-        __syncthreads();
-        const uint32_t T = rfl(s_ticket[cyc & 3u]);  // (one address, written before the barrier)
-        // the ticket before: its total to the scanner, and the bits of it in front of this wavefront's segment
-        if (cyc) {
-            uint64_t sum = 0, before = 0;
-#pragma unroll
-            for (int i = 0; i < WV; ++i) {
-                const uint64_t m = rfl64(s_mine[(cyc - 1u) & 1u][i]);
-                sum += m;
-                before += i < wv ? m : 0ull;
-            }
-            offA = before;
-            if (wv == 0 && lane == 0) es_store(size + Tprev, kEsFlag | sum);
-        }
+        const uint32_t T = es_rendezvous(shm, cyc, lane, wv, ctrl, size, Tprev, offA);
         if (pend && !fitsA) stream_out(wait_place());
         if ((uint64_t)T >= n_tickets) break;
         Tprev = T;
@@ -889,7 +763,7 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         const uint32_t sgi = tj * (uint32_t)WV + (uint32_t)wv;
         const uint64_t sb64 = (uint64_t)sgi * seg_len;
         if (sb64 >= wlen) {  // (a waveform's last ticket: no segment for this wavefront, it only keeps the rendezvous)
-            if (lane == 0) s_mine[cyc & 1u][wv] = 0;
+            if (lane == 0) shm.mine[cyc & 1u][wv] = 0;
             if (pend) copy_out(wait_place());  // (offA is segment A's only until the next rendezvous)
             continue;
         }
@@ -905,11 +779,8 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         const uint32_t clen = slen + more;           // samples coded
         const int16_t *x = in + r.sample_off + s_begin;
 
-        auto gap = [&]() -> uint32_t {
-            if (!pend) return RING - 8u;
-            const uint32_t d = startA >= start ? startA - start : startA + RING - start;
-            return d > 12u ? d - 12u : 0u;  // (a segment may be given two words behind its code: copy_out's completion)
-        };
+        // (a segment may be given two words behind its code: copy_out's completion)
+        auto gap = [&]() -> uint32_t { return es_gap<RING>(pend, startA, start, 12u); };
         if (pend && gap() < 512u) copy_out(wait_place());
         uint32_t limit = gap();
 
@@ -918,69 +789,23 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
         bool first = true;     // no tile coded yet
         bool fits = true;
         uint32_t carry = 0, carry2 = 0;
-        if (s_begin) {  // the samples in front of the segment (a waveform's first sample has none: x[-1] := 0, :53-54)
-            carry = (uint32_t)(uint16_t)x[-1] << 16;
-            if (GEN) {
-                carry |= (uint32_t)(uint16_t)x[-2];
-                carry2 = (uint32_t)(uint16_t)x[-4] | ((uint32_t)(uint16_t)x[-3] << 16);
-            }
-        }
-        auto wrap = [&](uint32_t bits) -> uint32_t { return bits >= kRingBits ? bits - kRingBits : bits; };
+        if (s_begin) history_before<GEN>(x, carry, carry2);
         // mark: the lane (wave uniform, -1: none) whose first sample is the first one BEHIND the segment proper
         auto process_tile = [&](const uint32_t (&w)[4], int nv, int mark, auto full_tag) {
             constexpr bool FULLT = decltype(full_tag)::value;
-            const uint32_t xprev = wave_shr1_carry(w[3], carry);
-            carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
-            uint32_t xprev2 = 0;
-            if (GEN) {
-                xprev2 = wave_shr1_carry(w[2], carry2);
-                carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
-            }
-            PackedCodes cc;
-            packed_codes<GEN>(w, xprev, xprev2, tp, k, cc);
-            if (!FULLT) mask_tail(cc, nv);
-            const uint32_t lane_bits = lane_tile_bits(cc);
-            uint32_t cw[4];
-            if (FULLT) concat_codes(cc, cw);
-            const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-            const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            if (!FULLT && mark >= 0) seg_bits = (uint32_t)P + (mark ? (uint32_t)__builtin_amdgcn_readlane((int)incl, mark - 1) : 0u);
-            const uint32_t need = ((uint32_t)P + tile_bits + 31u) >> 5;  // (32 bits: P < 2^17 while `fits` holds)
+            const TileCodes t = code_tile<GEN, FULLT>(w, nv, carry, carry2, tp, k);
+            if (!FULLT && mark >= 0) seg_bits = (uint32_t)P + (mark ? (uint32_t)__builtin_amdgcn_readlane((int)t.incl, mark - 1) : 0u);
+            const uint32_t need = ((uint32_t)P + t.tile_bits + 31u) >> 5;  // (32 bits: P < 2^17 while `fits` holds)
             bool ok = fits && need < limit;
-            if (pend) {
-                EsPlace2 pl;
-                const bool seen = place_in_lds(pl);
-                const bool must = fits && !ok;
-                if (seen || must) {
-                    if (!seen) __builtin_amdgcn_s_setprio(0);
-                    else if (P < (uint64_t)(4u * kTile * 7u)) __builtin_amdgcn_s_setprio(2);
-                    else __builtin_amdgcn_s_setprio(1);
-                    copy_out(seen ? pl : wait_place());
-                    limit = gap();
-                    ok = fits && need < limit;
-                }
+            if (pend && es_release(fits && !ok, P, place_in_lds, wait_place, copy_out)) {
+                limit = gap();
+                ok = fits && need < limit;
             }
-            if (ok) {
-                const uint32_t s0 = start * 32u + (uint32_t)P;
-                if (FULLT && !__any(lane_bits > 128u))
-                    place_words(cw, ring_bits0 + wrap(s0 + incl));
-                else
-                    emit_tile<FULLT>(cc, ring_bits0 + wrap(s0 + incl - lane_bits));
-                if (s0 < kRingBits && s0 + tile_bits >= kRingBits) {
-                    wave_sync();
-                    if (lane < (int)kEsFront) {
-                        const uint32_t v = row[lane];
-                        if (v) { ring[RING - kEsFront + lane] |= v; row[lane] = 0; }
-                    } else if (lane < (int)(kEsFront + kEsBack)) {
-                        const uint32_t i = (uint32_t)lane - kEsFront, v = ring[RING + i];
-                        if (v) { ring[i] |= v; ring[RING + i] = 0; }
-                    }
-                    wave_sync();
-                }
-            } else {
+            if (ok)
+                ring_put<FULLT, RING>(t, row, start * 32u + (uint32_t)P, lane);
+            else
                 fits = false;
-            }
-            P += tile_bits;
+            P += t.tile_bits;
             if (first) {  // (the first tile always fits: at least 500 words are free, a tile is at most 400)
                 first = false;
                 wave_sync();
@@ -1005,50 +830,18 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
             if (lane < 2) pollv = es_load(place + 2ull * TA + (uint32_t)lane);
             polling = true;
         };
-        {
-            constexpr int kDepth = 3;
-            const uint4 *xv = reinterpret_cast<const uint4 *>(x) + lane;  // tile t: xv[64 * t]
-            uint4 q[kDepth];
-            uint32_t t = 0;
-#pragma unroll
-            for (int u = 0; u < kDepth; ++u) {
-                q[u] = make_uint4(0, 0, 0, 0);
-                if ((uint32_t)u < n_fast) q[u] = xv[64 * (size_t)u];
-            }
-#pragma unroll 1
-            for (; t + 2u * kDepth <= n_fast; t += kDepth) {
-                between();
-#pragma unroll
-                for (int u = 0; u < kDepth; ++u) {
-                    const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                    process_tile(w, 8, -1, std::true_type{});
-                    q[u] = xv[64 * (size_t)(t + u + kDepth)];
-                }
-            }
-#pragma unroll 1
-            for (; t < n_fast; t += kDepth) {
-                between();
-#pragma unroll
-                for (int u = 0; u < kDepth; ++u) {
-                    if (t + (uint32_t)u < n_fast) {
-                        const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
-                        process_tile(w, 8, -1, std::true_type{});
-                        if (t + (uint32_t)u + kDepth < n_fast) q[u] = xv[64 * (size_t)(t + u + kDepth)];
-                    }
-                }
-            }
-            // the tile(s) with the segment's end and the samples coded behind it
-            for (uint32_t t0 = n_fast * kTile; t0 < clen; t0 += kTile) {
-                uint32_t w[4];
-                const int nv = load8_dwords(x, clen, t0, lane, true, w);
-                const int mark = (more && slen >= t0 && slen < t0 + (uint32_t)kTile) ? (int)((slen - t0) >> 3) : -1;
-                process_tile(w, nv, mark, std::false_type{});
-            }
+        for_full_tiles(x, n_fast, lane, between, [&](const uint32_t (&w)[4]) { process_tile(w, 8, -1, std::true_type{}); });
+        // the tile(s) with the segment's end and the samples coded behind it
+        for (uint32_t t0 = n_fast * kTile; t0 < clen; t0 += kTile) {
+            uint32_t w[4];
+            const int nv = load8_dwords(x, clen, t0, lane, true, w);
+            const int mark = (more && slen >= t0 && slen < t0 + (uint32_t)kTile) ? (int)((slen - t0) >> 3) : -1;
+            process_tile(w, nv, mark, std::false_type{});
         }
         if (!more) seg_bits = (uint32_t)P;  // (nothing coded behind the segment)
         const uint32_t n = (uint32_t)((P + (sib ? 63u : 31u)) >> 5);  // ring words (sib: + the 32 bits copy_out puts behind the code)
         wave_sync();
-        if (lane == 0) s_mine[cyc & 1u][wv] = seg_bits;
+        if (lane == 0) shm.mine[cyc & 1u][wv] = seg_bits;
         if (pend) copy_out(wait_place());
         pend = true;
         fitsA = fits;
@@ -1089,11 +882,7 @@ hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_
     mark(ev, 2, s);
     uint64_t *size = d_scan, *place = d_scan + tickets;
     uint32_t *ctrl = reinterpret_cast<uint32_t *>(d_scan + 2 * tickets);
-    // persistent: 16 wavefronts per CU, one workgroup of them the scanner's; never more than the batch can feed
-    // (DRX_DBG_STREAM_THREE_WGS: three workgroups -- a scanner and two coders -- so that a small test batch takes every wavefront
-    // through many waveforms, i.e. around its ring)
-    const unsigned full = 256u * (16u / kEsWaves);
-    const unsigned grid = (G.dbg & DRX_DBG_STREAM_THREE_WGS) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
+    const unsigned grid = es_grid(G, tickets);
     if (G.n_taps)
         k_encode_stream<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words, size,
                                                                               place, ctrl, d_status);
@@ -1119,8 +908,7 @@ hipError_t launch_encode_stream_segs(const Geom &G, uint32_t seg_target, const i
     mark(ev, 2, s);
     uint64_t *size = d_scan, *place = d_scan + tickets;
     uint32_t *ctrl = reinterpret_cast<uint32_t *>(d_scan + 3 * tickets);
-    const unsigned full = 256u * (16u / kEsWaves);
-    const unsigned grid = (G.dbg & DRX_DBG_STREAM_THREE_WGS) ? 3u : (unsigned)(tickets + 1 < full ? tickets + 1 : full);
+    const unsigned grid = es_grid(G, tickets);
     if (G.n_taps)
         k_encode_stream_segs<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, sh.seg_len, sh.tpw, d_in, d_out, out_cap, d_chunk_word_off,
                                                                                    d_wave_words, size, place, ctrl, d_status);

@@ -27,8 +27,8 @@
 // per workgroup as in k_encode_fused.  A piece whose code outgrows the 8 KB buffer (incompressible data) is coded again
 // after the look-back, tile by tile to its final position, by one wavefront per waveform.
 //
-// The arithmetic of a tile (packed 16-bit code lengths, DPP scan, lane-local concatenation, ds_or) is drx_encode.h, the
-// same code k_encode_fused runs; reference: src/deltaRice.c:49-63 (delta), :191-244 (Rice code), :383-441 (framing).
+// The arithmetic of a tile (packed 16-bit code lengths, DPP scan, lane-local concatenation, ds_or) and the coding-again of a
+// piece that outgrew its buffer (recode_waveform, recode_range) are drx_encode.h, the same code k_encode_fused runs; reference: src/deltaRice.c:49-63 (delta), :191-244 (Rice code), :383-441 (framing).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
     const uint32_t buf_bits = lds_addr(buf) * 8u;
 
     if (threadIdx.x == 0) s_ticket = atomicAdd(ticket, 1u);
-    for (int i = lane; i < (int)(kEncCapWords + 8) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
+    zero_row(row, kEncCapWords + 8u, lane);
     __syncthreads();
     const uint32_t T = s_ticket;
     if (T >= total_wgs) return;  // (the grid is exactly total_wgs workgroups)
@@ -206,13 +206,7 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
     // the sample in front of a segment (a waveform's first sample has none: x[-1] := 0, src/deltaRice.c:53-54)
     // (GEN, a forward filter of up to four taps, src/deltaRice.c:64-74: the three samples in front, as two dwords)
     uint32_t carry0 = 0, carry2_0 = 0;
-    if (!runs && sg && nspans) {
-        carry0 = (uint32_t)(uint16_t)in[xoff - 1u] << 16;
-        if (GEN) {  // (a segment starts at least 512 samples into its waveform)
-            carry0 |= (uint32_t)(uint16_t)in[xoff - 2u];
-            carry2_0 = (uint32_t)(uint16_t)in[xoff - 4u] | ((uint32_t)(uint16_t)in[xoff - 3u] << 16);
-        }
-    }
+    if (!runs && sg && nspans) history_before<GEN>(in + xoff, carry0, carry2_0);  // (a segment starts at least 512 samples into its waveform)
     const u16x2 tp[4] = {splat(GEN ? G.enc_t[0] : 1u), splat(GEN ? G.enc_t[1] : 0xffffu), splat(GEN ? G.enc_t[2] : 0u),
                          splat(GEN ? G.enc_t[3] : 0u)};
 
@@ -481,110 +475,6 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
     // runs: first header of the run; segments: the waveform's header
     const uint64_t pos = s_excl + ((SUPER ? w0 == 0u : first_wg) ? 1ull : 0ull) + words_before;
 
-    // a waveform coded once more, tile by tile, straight to its place (its code did not fit the buffer)
-    auto stream_waveform = [&](uint64_t soff, uint32_t len, uint32_t *__restrict__ outp) -> uint64_t {
-        for (int i = lane; i < (int)(kEncCapWords + 8) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
-        wave_sync();
-        const int16_t *x = in + soff;
-        uint64_t P = 0;
-        uint32_t cr = 0, cr2 = 0;
-        uint32_t wn[4];
-        int nvn = load8_dwords(x, len, 0u, lane, true, wn);
-        for (uint32_t t0 = 0; t0 < len; t0 += kTile) {
-            uint32_t w[4] = {wn[0], wn[1], wn[2], wn[3]};
-            const int nv = nvn;
-            if (t0 + kTile < len) nvn = load8_dwords(x, len, t0 + kTile, lane, true, wn);  // (travels while this tile is coded)
-            uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);
-            if (lane == 0) xprev = cr;
-            cr = (uint32_t)__shfl((int)w[3], 63);
-            uint32_t xprev2 = 0;
-            if (GEN) {
-                xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-                if (lane == 0) xprev2 = cr2;
-                cr2 = (uint32_t)__shfl((int)w[2], 63);
-            }
-            PackedCodes pc;
-            packed_codes<GEN>(w, xprev, xprev2, tp, k, pc);
-            mask_tail(pc, nv);
-            const uint32_t lane_bits = lane_tile_bits(pc);
-            const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-            const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint64_t wfirst = P >> 5;  // first staged word
-            emit_tile<false>(pc, buf_bits + (uint32_t)(P & 31u) + incl - lane_bits);
-            P += tile_bits;
-            wave_sync();
-            const uint32_t nfull = (uint32_t)((P >> 5) - wfirst);
-            for (uint32_t i = lane; i < nfull; i += 64) { outp[wfirst + i] = buf[i]; buf[i] = 0; }
-            wave_sync();
-            if (nfull && lane == 0) { const uint32_t cwd = buf[nfull]; buf[nfull] = 0; buf[0] = cwd; }
-            wave_sync();
-        }
-        if ((P & 31u) && lane == 0) outp[P >> 5] = buf[0];
-        return P;
-    };
-
-    // Samples [s_begin, s_end) of the waveform once more, tile by tile, from bit Bp of the waveform's stream on (their code did
-    // not fit the buffer).  The word in which they start belongs to whoever codes the samples in front; the word in which they
-    // end is completed from the (up to) 32 samples that follow (at least a bit each): wavefronts exchange nothing.  The next
-    // tile's samples travel while this one is coded.
-    auto stream_samples = [&](uint32_t s_begin, uint32_t s_end, uint64_t Bp, uint32_t bits_mine, uint32_t *__restrict__ outp,
-                              uint64_t cap_words) {
-        const uint32_t P0 = (uint32_t)(Bp & 31u);
-        const uint64_t wbase = Bp >> 5;
-        const uint32_t limit = (P0 + bits_mine + 31u) >> 5, skip = P0 ? 1u : 0u;  // words [skip, limit) from wbase are mine
-        const uint32_t more = wf_len - s_end < 32u ? wf_len - s_end : 32u;
-        const uint32_t len = s_end - s_begin + more;
-        for (int i = lane; i < (int)(kEncCapWords + 8) / 4; i += 64) reinterpret_cast<uint4 *>(row)[i] = make_uint4(0, 0, 0, 0);
-        wave_sync();
-        const int16_t *x = in + wf_off + s_begin;
-        uint64_t P = P0;
-        uint32_t cr = 0, cr2 = 0;
-        if (s_begin) {
-            cr = (uint32_t)(uint16_t)x[-1] << 16;
-            if (GEN) {
-                cr |= (uint32_t)(uint16_t)x[-2];
-                cr2 = (uint32_t)(uint16_t)x[-4] | ((uint32_t)(uint16_t)x[-3] << 16);
-            }
-        }
-        uint32_t wn[4];
-        int nvn = load8_dwords(x, len, 0u, lane, true, wn);
-        for (uint32_t t0 = 0; t0 < len; t0 += kTile) {
-            uint32_t w[4] = {wn[0], wn[1], wn[2], wn[3]};
-            const int nv = nvn;
-            if (t0 + kTile < len) nvn = load8_dwords(x, len, t0 + kTile, lane, true, wn);
-            uint32_t xprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[3], 0x138, 0xf, 0xf, false);
-            if (lane == 0) xprev = cr;
-            cr = (uint32_t)__shfl((int)w[3], 63);
-            uint32_t xprev2 = 0;
-            if (GEN) {
-                xprev2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w[2], 0x138, 0xf, 0xf, false);
-                if (lane == 0) xprev2 = cr2;
-                cr2 = (uint32_t)__shfl((int)w[2], 63);
-            }
-            PackedCodes pc;
-            packed_codes<GEN>(w, xprev, xprev2, tp, k, pc);
-            mask_tail(pc, nv);
-            const uint32_t lane_bits = lane_tile_bits(pc);
-            const uint32_t incl = wave_incl_scan_dpp(lane_bits);
-            const uint32_t tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-            const uint64_t wfirst = P >> 5;  // first staged word
-            emit_tile<false>(pc, buf_bits + (uint32_t)(P & 31u) + incl - lane_bits);
-            P += tile_bits;
-            wave_sync();
-            const uint32_t nfull = (uint32_t)((P >> 5) - wfirst);
-            for (uint32_t i = lane; i < nfull; i += 64) {
-                const uint64_t idx = wfirst + i;
-                if (idx >= skip && idx < limit && wbase + idx < cap_words) outp[wbase + idx] = buf[i];
-                buf[i] = 0;
-            }
-            wave_sync();
-            if (nfull && lane == 0) { const uint32_t cwd = buf[nfull]; buf[nfull] = 0; buf[0] = cwd; }
-            wave_sync();
-        }
-        const uint64_t idx = P >> 5;
-        if ((P & 31u) && lane == 0 && idx >= skip && idx < limit && wbase + idx < cap_words) outp[wbase + idx] = buf[0];
-    };
-
     if (runs) {
         const uint32_t words = s_size[wv];
         if (!PACKED && (uint32_t)lane < nspans) wave_words[q.wave_base + w0 + (uint32_t)lane] = s_n[wv][lane];
@@ -597,7 +487,7 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
         const uint32_t n_wf = PACKED ? run_wfs : nspans;
         for (uint32_t i = 0; i < n_wf; ++i) {
             const uint32_t len_i = (w0 + i + 1u == q.W) ? q.n_samples - (w0 + i) * q.L : q.L;
-            const uint64_t bits = stream_waveform(wf_off + (uint64_t)i * q.L, len_i, out + at + 1u);
+            const uint64_t bits = recode_waveform<GEN>(in + wf_off + (uint64_t)i * q.L, len_i, tp, k, lane, row, kEncCapWords + 8u, out + at + 1u);
             const uint32_t n = (uint32_t)((bits + 31u) >> 5);
             if (lane == 0) out[at] = n;  // src/deltaRice.c:379
             wave_sync();
@@ -621,7 +511,7 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
             const uint32_t s_begin = (part * kPcWaves + wv) * sh.seg_len;
             if (s_begin < wf_len) {
                 const uint32_t s_end = wf_len - s_begin < sh.seg_len ? wf_len : s_begin + sh.seg_len;
-                stream_samples(s_begin, s_end, s_excl_bits + before, s_size[wv], outp, cap_words);
+                recode_range<GEN>(in + wf_off, wf_len, s_begin, s_end, s_excl_bits + before, s_size[wv], tp, k, lane, row, kEncCapWords + 8u, outp, cap_words);
             }
             return;
         }
@@ -651,7 +541,7 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
         const uint32_t s_begin = sg * sh.seg_len;
         if (s_begin < wf_len) {
             const uint32_t s_end = wf_len - s_begin < sh.seg_len ? wf_len : s_begin + sh.seg_len;
-            stream_samples(s_begin, s_end, bits_before, s_size[wv], outp, out_cap - pos - 1u);
+            recode_range<GEN>(in + wf_off, wf_len, s_begin, s_end, bits_before, s_size[wv], tp, k, lane, row, kEncCapWords + 8u, outp, out_cap - pos - 1u);
         }
         return;
     }

@@ -620,6 +620,10 @@ def test_persistent_encoder_rings_and_streaming(ctx, O):
     cases.append(("near-ring-size", [9000 * 120], [9000], 4, None, noisy(9000 * 120, 30)))   # ~8.5 bits per sample: ~2400 words
     cases.append(("long", [30000 * 20, 30000 * 7 + 5], [30000, 30000], 3, None, noisy(30000 * 27 + 5, 10)))
     cases.append(("fir4", [5000 * 100], [5000], 3, (1, -1, 1, -1), noisy(5000 * 100, 20)))
+    x = noisy(5000 * 100, 20)
+    for w in (3, 17, 18, 99):  # an escape is 25 bits: 3907 words against the ring's 2496, coded again with the general filter
+        x[w * 5000:(w + 1) * 5000] = rough(5000)
+    cases.append(("fir4-streamed-among-ringed", [5000 * 100], [5000], 3, (1, -1, 1, -1), x))
     lens = [512, 2048, 7000, 16384, 0, 3333]
     Ns = [512 * 40, 2048 * 9 + 17, 7000 * 30, 16384 * 4, 4321, 3333 * 21 + 1]
     cases.append(("ragged", Ns, lens, 3, None, noisy(sum(Ns), 10)))
@@ -723,6 +727,22 @@ def test_encoder_dispatch_follows_the_measured_code_length(ctx, O):
         for c in (0, 17, 39):
             assert enc.chunk_bytes(c) == O.encode_chunk(x[c * N:(c + 1) * N], (8, 50000)).tobytes(), (i, sigma, c)
         assert np.array_equal(plan.decode(enc).cpu().numpy(), x), (i, sigma)
+    # a general filter on the default segment route, loud waveforms among quiet ones: at k + 3.5 bits the plan's first encode aims
+    # at 7004 samples, i.e. four segments of 5120 per waveform, 8192 in the batch; a loud segment (every code an escape: 4000
+    # words) outgrows its ring and is coded again to its place, with the filter's history from the three samples in front of
+    # it; the second encode runs in the shorter segments the measured length gives
+    n_chunks, N, L = 64, 32 * 20480, 20480
+    opts = (8, L, 4) + tuple(t & 0xFFFFFFFF for t in (1, -1, 1, -1))
+    x = rng.normal(0, 10, n_chunks * N).astype(np.int16).reshape(-1, L)
+    x[1::2] = rng.integers(-32768, 32768, x[1::2].shape, dtype=np.int16)
+    x = x.reshape(-1)
+    plan = ctx.plan_uniform(n_chunks, N, opts)
+    xd = dev(ctx, x)
+    for i in range(2):
+        enc = plan.encode(xd)
+        assert plan.last_encode_path() == ENC_SEGS, i
+        for c in (0, 31, 63):
+            assert enc.chunk_bytes(c) == O.encode_chunk(x[c * N:(c + 1) * N], opts).tobytes(), (i, c)
 
 
 def test_rice_parameter_optimiser_is_exact(ctx, O):
