@@ -257,8 +257,8 @@ __global__ __launch_bounds__(kLongThreads) void k_decode_long(Geom G, const uint
 // Decomposition.  The Rice parse is serial inside a waveform, so the unit of parallelism is the
 // waveform: one lane per waveform, 64 waveforms per wavefront.
 //   stream in   each lane owns an LDS ring of RW words of its compressed stream, refilled in
-//               pieces of LW words by 16-byte loads (every byte of the stream is requested once;
-//               rocprofv3: TCC_EA0_RDREQ x 128 B = the stream size).  A piece is loaded ahead of
+//               pieces of LW words = one 128-byte line by 16-byte loads (every line of the stream is
+//               requested once, by one lane, in one round).  A piece is loaded ahead of
 //               need and written to the ring just before the round's stores are issued (vmcnt is
 //               in order: a load issued after a store cannot be waited for without that store).
 //   ring layout word-major and reversed, ring[RW - (w mod RW)][lane], plus a mirror row: a lane's
@@ -268,8 +268,9 @@ __global__ __launch_bounds__(kLongThreads) void k_decode_long(Geom G, const uint
 //               (lo, hi) = ds_read2st64_b32, win = v_alignbit(hi, lo, Q): 3 VALU + 1 LDS
 //               instruction form the 32-bit window, no refill state.  Escape and ordinary codes
 //               share one extraction (payload width kk = esc ? 16 : k; the 8 << 16 an escape leaves
-//               above bit 15 never reaches the int16 running sum).  14.5 VALU instructions per
-//               sample; the kernel is bound by VALU issue (4 cycles per wave64 instruction).
+//               above bit 15 never reaches the int16 running sum).  217 VALU instructions per group of
+//               16 samples in the interior rounds (13.6 per sample; tests/test_lanes_decoder_build.py), 13
+//               dependent VALU levels and one LDS round trip per pair: what bounds the parse is that chain.
 //   samples out transposed through LDS; a lane-private start delay phi makes step u of every round
 //               land u*2 bytes past a T*2-byte boundary, so each round stores whole aligned
 //               128-byte lines (T = 64).  tools/ubench_store.hip: 16-byte stores reach 5.5 TB/s only
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
                                                      uint64_t *__restrict__ granules, uint32_t *__restrict__ ticket,
                                                      DevStatus *st, int16_t *__restrict__ out) {
     constexpr int RW = 64;          // ring words per lane
-    constexpr int LW = 16;          // words per stream piece
+    constexpr int LW = 32;          // words per stream piece: one 128-byte line
     constexpr int T = 64;           // samples per round
     constexpr int GS = 16;          // samples per group (a refill test per group)
     constexpr int LOG_RW = 6;
@@ -477,8 +478,8 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
         return *reinterpret_cast<const uint4 *>(obuf + st * OSW + 4 * p);
     };
 
-    auto load_piece = [&](uint4 (&v)[NV], uint32_t ahead = 0) {
-        const uint64_t a = A + flw + ahead;
+    auto load_piece = [&](uint4 (&v)[NV]) {
+        const uint64_t a = A + flw;
         if (in_vec_ok && a + (uint32_t)LW <= in_words) {
 #pragma unroll
             for (int j = 0; j < NV; ++j) v[j] = *reinterpret_cast<const uint4 *>(in + a + 4 * j);
@@ -678,14 +679,23 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
     }
 
     // steady state.  Stream pieces are requested at the END of a round, just BEFORE the round's stores
-    // are issued, and written to the ring at the end of the next round.  vmcnt retires in issue order
+    // are issued, and written to the ring at the end of a later round.  vmcnt retires in issue order
     // and counts loads and stores together, so a wait for loads that are OLDER than the PPS stores of
     // their own round is `s_waitcnt vmcnt(PPS)` and never waits for those stores (ablation: loads alone
     // +0.04 ms, stores alone +0.11 ms, both +1.0 ms when the commit had to drain the stores too).
     // The interior rounds (every stream fully inside its waveform: whole-line stores only) run in a
     // loop of their own whose only vector-memory operations are those loads and those PPS stores, so
-    // that the compiler's waitcnt insertion can prove the count.  Up to two pieces per lane and round
-    // (2 LW words = 16 bits per sample at LW = 16); hungrier streams fall back to sync_refill().
+    // that the compiler's waitcnt insertion can prove the count.  ONE piece per lane is in flight: a piece is
+    // a whole 128-byte line, so every line of a stream is requested once, by one lane, by the NV loads of one
+    // round (two 64-byte halves a round apart found a quarter of the lines gone from L2 again: 1.24 x the
+    // stream in HBM reads).  A lane requests its next piece as soon as it holds none and commits it at the
+    // first round end (or refill test) at which it fits, avail <= RW - LW; until then it stays in its
+    // registers.  A piece that does not fit at a round's end leaves more than RW - LW words, so at a STEADY
+    // rate of up to (RW - LW - NEED_AT) / 0.75 = 18 words per round (9 bits per sample; the headline's mean
+    // is 13) a stream does not reach a refill test short of words, and at up to LW words per round (16 bits
+    // per sample) it commits at a refill test at the earliest without waiting for a load; hungrier streams
+    // take the rest through sync_refill().  That is arithmetic: rates vary from waveform to waveform and from
+    // round to round, and how often the interior loop enters sync_refill() on a real batch is not counted.
     auto edge_round = [&](uint32_t t0) __attribute__((always_inline)) {  // first / last rounds: masked stores, synchronous refills
 #pragma unroll 1
         for (int tg = 0; tg < T; tg += GS) {
@@ -699,29 +709,21 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
     uint32_t t0 = T;
     for (; t0 < steps && !(t0 >= lo_max && t0 + T <= hi_min); t0 += T) edge_round(t0);
 
-    const uint32_t min_words = ((uint32_t)T * (k + 1u)) >> 5;
-    uint4 pv0[NV], pv1[NV];               // pieces in flight
-    bool pneed0 = false, pneed1 = false;  // this lane has them in flight
+    uint4 pv[NV];        // the piece in flight
+    bool pneed = false;  // this lane has one in flight
     set_limits();
+    auto commit_if_fits = [&]() __attribute__((always_inline)) {  // the rows a piece overwrites must have been consumed
+        const uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
+        if (pneed && avail <= (uint32_t)(RW - LW)) {
+            store_piece(pv);
+            pneed = false;
+        }
+    };
     auto group_refill = [&]() __attribute__((always_inline)) {
         if (__any((int32_t)(Q - Q_need) <= 0)) {  // one signed compare per test (positions are mod 2^32)
-            // a piece in flight was requested counting on the words this round consumes at least
-            // (min_words): before the round is over it may only be committed where it already fits
-            uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
-            if (pneed0 && avail <= (uint32_t)(RW - LW)) {
-                store_piece(pv0);
-                pneed0 = false;
-                avail += (uint32_t)LW;
-                if (pneed1 && avail <= (uint32_t)(RW - LW)) { store_piece(pv1); pneed1 = false; }
-            }
-            if (!pneed0 && pneed1) {
-#pragma unroll
-                for (int j = 0; j < NV; ++j) pv0[j] = pv1[j];
-                pneed0 = true;
-                pneed1 = false;
-            }
+            commit_if_fits();  // (a lane short of words has room for its piece: NEED_AT <= RW - LW)
             wave_sync();
-            sync_refill();
+            sync_refill();  // loads only where a lane is still short: it held no piece, or eats more than one per round
             set_limits();
         }
     };
@@ -733,19 +735,16 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
         }
         Q_end = (t0 + (uint32_t)T == hi_step) ? Q : Q_end;  // a lane whose last step closes an interior round
         wave_sync();
-        if (pneed0) store_piece(pv0);  // loads of the previous round end: older than that round's PPS stores
-        if (pneed1) store_piece(pv1);
+        commit_if_fits();  // loads of an earlier round's end: older than that round's PPS stores
         wave_sync();
         set_limits();
-        {
-            // a piece is committed one interior round after its request: by then every lane has decoded T more
-            // samples of at least k + 1 bits each, i.e. consumed min_words more words
-            const uint32_t mc = (t0 + 2u * T <= hi_min && t0 + T < steps) ? min_words : 0u;
+        if (!pneed) {
+            // behind the last interior round a piece is committed once more and then dropped: there, request only what
+            // fits already (a dropped piece would be fetched again by the edge rounds' sync_refill())
+            const bool last = !(t0 + 2u * T <= hi_min && t0 + T < steps);
             const uint32_t avail = (flw - ((~Q) >> 5)) & WMASK;
-            pneed0 = (flw < endw) && avail + (uint32_t)LW <= (uint32_t)RW + mc;
-            pneed1 = pneed0 && (flw + (uint32_t)LW < endw) && avail + 2u * (uint32_t)LW <= (uint32_t)RW + mc;
-            if (pneed0) load_piece(pv0);
-            if (pneed1) load_piece(pv1, (uint32_t)LW);
+            pneed = (flw < endw) && (!last || avail <= (uint32_t)(RW - LW));
+            if (pneed) load_piece(pv);
         }
 #pragma unroll
         for (int i = 0; i < PPS; ++i) {  // whole aligned lines only
@@ -755,8 +754,8 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
         }
         wave_sync();
     }
-    if (pneed0) store_piece(pv0);
-    if (pneed1) store_piece(pv1);
+    commit_if_fits();
+    pneed = false;  // a piece that still does not fit is dropped (flw has not advanced: sync_refill() fetches it again)
     wave_sync();
     for (; t0 < steps; t0 += T) edge_round(t0);
     // bits of the waveform = -Q_end - 32 s0 (Q counts from A); n_i words hold them exactly
