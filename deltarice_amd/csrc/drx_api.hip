@@ -672,9 +672,11 @@ static uint32_t stream_segs_target(const drx_plan *p) {
 //   STREAM_SEGS | impl 2, stream_segs_admits()                         | L >= kEsSegsFromLen, kEsMinUnits segments (stream_segs_target())
 //   PIECES      | impl >= 1, pieces_admits()                           | pieces_batch(): runs of short / segments of long waveforms
 //   SEGMENTS    | impl >= 1, long_batch_admits()                       | long_batch(): short, long or few long waveforms
-//   STREAM      | impl 2, delta or fast filter                         | stream_encoder_suits(): >= kEsMinUnits waveforms, code fits a ring
-//   FUSED       | impl >= 1, delta or fast filter                      | always (fused_wide(): larger buffers for m above 8)
-//   TWO_PASS    | always                                               | always
+//   STREAM      | impl 2, delta or fast filter, tickets fit 32 bits    | stream_encoder_suits(): >= kEsMinUnits waveforms, code fits a ring
+//   FUSED       | impl >= 1, delta or fast filter, <= kMaxWavefrontWaves | always (fused_wide(): larger buffers for m above 8)
+//   TWO_PASS    | always (launched in slices)                          | always
+// A launch carries fewer than 2^32 threads: the encoders that give every waveform (segment slot) a wavefront of ONE launch admit
+// batches of at most kMaxWavefrontWaves of them, k_encode_pieces fewer than 2^23 workgroups (include/deltarice_hip.h).
 // Forced rows come first, in this order: DRX_DBG_FORCE_STREAM_SEGS (segments of kEsSegMinLen samples), FORCE_SEGMENTS,
 // FORCE_PIECES, FORCE_STREAM take their encoder wherever it admits the batch.  Exclusions: NO_PIECES drops the default
 // PIECES and STREAM_SEGS rows, NO_LONG_PATHS the default SEGMENTS and STREAM_SEGS rows; NO_WIDE_FUSED sets fused_wide to 0.
@@ -686,7 +688,8 @@ static EncodeRoute route_encode(const drx_plan *p, int impl, uint32_t dbg) {
     const int wide = (dbg & DRX_DBG_NO_WIDE_FUSED) ? 0 : fused_wide(G);
     const bool fast = G.n_taps == 0 || G.enc_fast, single = impl >= 1;
     const bool segs_in = impl == 2 && stream_segs_admits(G), pieces_in = single && pieces_admits(G);
-    const bool long_in = single && long_batch_admits(G), stream_in = impl == 2 && fast;
+    const bool long_in = single && long_batch_admits(G), stream_in = impl == 2 && fast && G.total_waves < 0xffff0000ull;
+    const bool fused_in = single && fast && G.total_waves <= kMaxWavefrontWaves;
     if ((dbg & DRX_DBG_FORCE_STREAM_SEGS) && segs_in) return {DRX_ENC_STREAM_SEGS, kEsSegMinLen, wide};
     if ((dbg & DRX_DBG_FORCE_SEGMENTS) && long_in) return {DRX_ENC_SEGMENTS, 0, wide};
     if ((dbg & DRX_DBG_FORCE_PIECES) && pieces_in) return {DRX_ENC_PIECES, 0, wide};
@@ -696,7 +699,7 @@ static EncodeRoute route_encode(const drx_plan *p, int impl, uint32_t dbg) {
     if (pieces_in && !(dbg & DRX_DBG_NO_PIECES) && pieces_batch(G, wide)) return {DRX_ENC_PIECES, 0, wide};
     if (long_in && !(dbg & DRX_DBG_NO_LONG_PATHS) && long_batch(G)) return {DRX_ENC_SEGMENTS, 0, wide};
     if (stream_in && stream_encoder_suits(p, wide)) return {DRX_ENC_STREAM, 0, wide};
-    return {single && fast ? DRX_ENC_FUSED : DRX_ENC_TWO_PASS, 0, wide};
+    return {fused_in ? DRX_ENC_FUSED : DRX_ENC_TWO_PASS, 0, wide};
 }
 
 // Scratch of a route beyond what the plan was sized for, which only a route that a debug flag forces needs: the segment

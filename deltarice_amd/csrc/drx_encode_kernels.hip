@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "drx_internal.h"
@@ -66,10 +67,10 @@ __device__ __forceinline__ int32_t fir_residual(const int16_t *__restrict__ x, u
 }
 
 // Pass A: payload word count n_i of every waveform.
-__global__ __launch_bounds__(256) void k_encode_sizes(Geom G, const int16_t *__restrict__ in,
+__global__ __launch_bounds__(256) void k_encode_sizes(Geom G, uint64_t g0, const int16_t *__restrict__ in,
                                                       uint32_t *__restrict__ wave_words) {
     const int lane = lane_id();
-    const uint64_t g = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_id();
+    const uint64_t g = g0 + (uint64_t)blockIdx.x * 4u + (uint32_t)wave_id();  // (g0: the launch's first waveform, for_wave_slices())
     if (g >= G.total_waves) return;
     const WaveRef r = locate_uniform(G, g);
     const int16_t *x = in + r.sample_off;
@@ -99,44 +100,50 @@ __global__ __launch_bounds__(256) void k_encode_sizes(Geom G, const int16_t *__r
 
 // RiceParameter optimiser (the routine docs/Optimization.md:5-19 describes but the reference does not
 // ship): exact size of the encoded batch for every k = 0..15 in one pass over the samples.
-// words[k] += 1 + ceil(bits_k / 32) per waveform (+1 per chunk); one wavefront per waveform.
-__global__ __launch_bounds__(256) void k_estimate_words(Geom G, const int16_t *__restrict__ in,
+// words[k] += 1 + ceil(bits_k / 32) per waveform (+1 per chunk); a wavefront takes `per` consecutive waveforms and adds their
+// sum once (an atomic per waveform and k made 6.7 s of 6.8e7 waveforms of 64 samples: sixteen addresses for the whole chip).
+__global__ __launch_bounds__(256) void k_estimate_words(Geom G, uint32_t per, const int16_t *__restrict__ in,
                                                         unsigned long long *__restrict__ words) {
     const int lane = lane_id();
-    const uint64_t g = (uint64_t)blockIdx.x * 4u + (uint32_t)wave_id();
-    if (g >= G.total_waves) return;
-    const WaveRef r = locate_uniform(G, g);
-    const int16_t *x = in + r.sample_off;
-    const bool vec_ok = ((uintptr_t)x & 15u) == 0;
-    uint32_t bits[16];
+    const uint64_t first = ((uint64_t)blockIdx.x * 4u + (uint32_t)wave_id()) * per;
+    uint64_t acc[16];  // (wave uniform)
 #pragma unroll
-    for (int k = 0; k < 16; ++k) bits[k] = 0;
-    int32_t carry = 0;
-    for (uint32_t t0 = 0; t0 < r.len; t0 += kTile) {
-        int32_t v[8];
-        const int nv = load8(x, r.len, t0, lane, vec_ok, v);
-        int32_t prev = __shfl_up(v[7], 1);
-        if (lane == 0) prev = carry;
-        carry = __shfl(v[7], 63);
+    for (int k = 0; k < 16; ++k) acc[k] = 0;
+    for (uint32_t i = 0; i < per && first + i < G.total_waves; ++i) {
+        const WaveRef r = locate_uniform(G, first + i);
+        const int16_t *x = in + r.sample_off;
+        const bool vec_ok = ((uintptr_t)x & 15u) == 0;
+        uint32_t bits[16];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            int32_t d = (int32_t)(int16_t)(v[j] - prev);
-            prev = v[j];
-            if (G.n_taps) d = (j < nv) ? fir_residual(x, t0 + 8u * (uint32_t)lane + (uint32_t)j, G) : 0;
-            const uint32_t z = (uint32_t)((d << 1) ^ (d >> 31));
-            if (j < nv) {
+        for (int k = 0; k < 16; ++k) bits[k] = 0;
+        int32_t carry = 0;
+        for (uint32_t t0 = 0; t0 < r.len; t0 += kTile) {
+            int32_t v[8];
+            const int nv = load8(x, r.len, t0, lane, vec_ok, v);
+            int32_t prev = __shfl_up(v[7], 1);
+            if (lane == 0) prev = carry;
+            carry = __shfl(v[7], 63);
 #pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const uint32_t q = z >> k;
-                    bits[k] += q < 8u ? q + 1u + (uint32_t)k : 25u;
+            for (int j = 0; j < 8; ++j) {
+                int32_t d = (int32_t)(int16_t)(v[j] - prev);
+                prev = v[j];
+                if (G.n_taps) d = (j < nv) ? fir_residual(x, t0 + 8u * (uint32_t)lane + (uint32_t)j, G) : 0;
+                const uint32_t z = (uint32_t)((d << 1) ^ (d >> 31));
+                if (j < nv) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const uint32_t q = z >> k;
+                        bits[k] += q < 8u ? q + 1u + (uint32_t)k : 25u;
+                    }
                 }
             }
         }
-    }
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const uint64_t total = wave_sum_u64(bits[k]);
-        if (lane == 0) atomicAdd(words + k, (unsigned long long)(1u + ((total + 31u) >> 5) + (r.idx == 0 ? 1u : 0u)));
+        for (int k = 0; k < 16; ++k) acc[k] += 1u + ((wave_sum_u64(bits[k]) + 31u) >> 5) + (r.idx == 0 ? 1u : 0u);
+    }
+    if (lane == 0 && first < G.total_waves) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) atomicAdd(words + k, (unsigned long long)acc[k]);
     }
 }
 
@@ -203,7 +210,7 @@ __global__ __launch_bounds__(1024) void k_chunk_offsets(uint64_t n_chunks, const
 }
 
 // Pass B: encode and write every waveform at its final position.
-__global__ __launch_bounds__(256) void k_encode_pack(Geom G, const int16_t *__restrict__ in,
+__global__ __launch_bounds__(256) void k_encode_pack(Geom G, uint64_t g0, const int16_t *__restrict__ in,
                                                      const uint32_t *__restrict__ wave_words,
                                                      const uint32_t *__restrict__ wave_rel,
                                                      const uint64_t *__restrict__ chunk_word_off,
@@ -212,7 +219,7 @@ __global__ __launch_bounds__(256) void k_encode_pack(Geom G, const int16_t *__re
     const int lane = lane_id();
     const int wv = wave_id();
     uint32_t *stage = stage_all[wv];
-    const uint64_t g = (uint64_t)blockIdx.x * 4u + (uint32_t)wv;
+    const uint64_t g = g0 + (uint64_t)blockIdx.x * 4u + (uint32_t)wv;
     if (g >= G.total_waves) return;
     for (int i = lane; i < kStageWords; i += 64) stage[i] = 0;
     const WaveRef r = locate_uniform(G, g);
@@ -719,10 +726,22 @@ __global__ __launch_bounds__(256) void k_seg_pack(Geom G, const int16_t *__restr
 // ---------------------------------------------------------------------------
 // launchers (host side, same translation unit so that <<<>>> stays in HIP code)
 // ---------------------------------------------------------------------------
+// A launch carries fewer than 2^32 threads -- the runtime takes a larger grid modulo 2^32 and the rest of the batch is never
+// coded -- and the kernels that give every waveform a wavefront of a 256-thread workgroup reach that at 2^26 waveforms (2^32
+// samples of WaveformLength 64): the two-pass encoder's are launched in slices of kWaveSliceBlocks workgroups (2^30 threads),
+// each told its first waveform.  go(first waveform, workgroups)
+constexpr uint64_t kWaveSliceBlocks = 1u << 22;
+template <class F> static void for_wave_slices(uint64_t total_waves, F go) {
+    const uint64_t blocks = (total_waves + 3u) / 4u;
+    for (uint64_t b0 = 0; b0 < blocks; b0 += kWaveSliceBlocks) go(4u * b0, (unsigned)std::min(kWaveSliceBlocks, blocks - b0));
+}
+
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s) {
     hipError_t e = hipMemsetAsync(d_words16, 0, 16 * sizeof(unsigned long long), s);
     if (e != hipSuccess || G.total_waves == 0) return e;
-    k_estimate_words<<<blocks_for(G.total_waves, 4), 256, 0, s>>>(G, d_in, d_words16);
+    // as many waveforms to a wavefront as leave the launch 2^18 wavefronts (one each up to there)
+    const uint32_t per = (uint32_t)((G.total_waves + (1u << 18) - 1u) >> 18);
+    k_estimate_words<<<blocks_for(G.total_waves, 4u * per), 256, 0, s>>>(G, per, d_in, d_words16);
     return hipGetLastError();
 }
 
@@ -765,13 +784,14 @@ hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, ui
                          uint64_t *d_chunk_words, DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
     if (G.total_waves == 0) return hipSuccess;
     mark(ev, 0, s);
-    k_encode_sizes<<<blocks_for(G.total_waves, 4), 256, 0, s>>>(G, d_in, d_wave_words);
+    for_wave_slices(G.total_waves, [&](uint64_t g0, unsigned nb) { k_encode_sizes<<<nb, 256, 0, s>>>(G, g0, d_in, d_wave_words); });
     mark(ev, 1, s);
     k_chunk_scan<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, d_wave_words, d_wave_rel, d_chunk_words);
     k_chunk_offsets<<<1, 1024, 0, s>>>(G.n_chunks, d_chunk_words, d_chunk_word_off, out_cap, d_status, G.host_words);
     mark(ev, 2, s);
-    k_encode_pack<<<blocks_for(G.total_waves, 4), 256, 0, s>>>(G, d_in, d_wave_words, d_wave_rel,
-                                                               d_chunk_word_off, d_out, out_cap);
+    for_wave_slices(G.total_waves, [&](uint64_t g0, unsigned nb) {
+        k_encode_pack<<<nb, 256, 0, s>>>(G, g0, d_in, d_wave_words, d_wave_rel, d_chunk_word_off, d_out, out_cap);
+    });
     mark(ev, 3, s);
     return hipGetLastError();
 }
@@ -781,7 +801,10 @@ hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, ui
 // (200 chunks of 14 M samples: L = 512 0.57 -> 0.95 TB/s, 1024 0.97 -> 1.33, 2048 1.51 -> 1.68), and waveforms
 // long enough to outgrow the single pass's LDS buffer; in between the single pass is better
 // (delta; ragged: decided when the plan was made, segments_plan_ragged())
-bool long_batch_admits(const Geom &G) { return !G.n_taps && (G.uniform || G.seg_unit_base != nullptr); }
+// ... and a wavefront per unit, per waveform (k_seg_scan), of one launch: at most kMaxWavefrontWaves of either
+bool long_batch_admits(const Geom &G) {
+    return !G.n_taps && (G.uniform || G.seg_unit_base != nullptr) && G.total_waves <= kMaxWavefrontWaves && long_batch_units(G) <= kMaxWavefrontWaves;
+}
 // WaveformLengths the segment encoder takes in any batch: up to kSegShortLen, and from kSegLongLen.  Measured at 100 chunks of
 // 14 M samples (single pass / segments, TB/s): L = 2049 0.95 / 1.06, 3000 1.57 / 1.64, 4096 1.93 / 1.85, 7000 2.16 / 1.87,
 // 12000 1.33 / 1.63 (the single pass outgrows its 8 KB LDS buffer at ~6.5 bits per sample and encodes such waveforms twice)

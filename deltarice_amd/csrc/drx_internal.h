@@ -109,6 +109,9 @@ hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, ui
 __host__ __device__ inline bool long_waveform_batch(uint64_t total_waves, uint32_t wave_len) {
     return (wave_len >= 65536u && total_waves <= 16384u) || (wave_len >= 16384u && total_waves <= 4096u);
 }
+// A launch carries fewer than 2^32 threads (the HIP runtime refuses more): a kernel that gives every waveform a wavefront in
+// workgroups of up to eight takes at most this many waveforms in one launch
+constexpr uint64_t kMaxWavefrontWaves = (1ull << 26) - 8u;
 static inline unsigned blocks_for(uint64_t items, unsigned per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 static inline void mark(hipEvent_t *ev, int i, hipStream_t s) {  // (optional profiling events of a launch)
     if (ev) (void)hipEventRecord(ev[i], s);

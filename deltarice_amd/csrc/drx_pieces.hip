@@ -570,6 +570,8 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
 static bool pieces_packed(const Geom &G) { return G.uniform ? piece_packable(G.u_wave_len) : G.pc_packed != 0; }
 static bool pieces_super(const Geom &G) { return G.uniform ? G.u_wave_len > pc_max_len(G.k) : G.pc_super != 0; }
 
+// one launch of workgroups of 64 x kPcWaves threads, fewer than 2^32 threads in all
+constexpr uint64_t kPcMaxWgs = (1ull << 32) / (64u * kPcWaves);
 bool pieces_admits(const Geom &G) {  // (the plan allocates the encoder's look-back state where this holds)
     if (G.n_taps && !G.enc_fast) return false;       // delta, or a forward filter of up to four taps
     if (!G.uniform) return G.pc_wg_base != nullptr;  // decided when the plan was made
@@ -577,7 +579,7 @@ bool pieces_admits(const Geom &G) {  // (the plan allocates the encoder's look-b
     const bool packed = piece_packable(L);
     if ((L < kPcMinLen && !packed) || (uint64_t)G.n_chunks * G.u_n_samples < (uint64_t)kTile) return false;
     const PieceShape sh = piece_shape(L, G.u_n_waves, G.k, packed);
-    return (uint64_t)G.u_n_waves * sh.parts <= 0x7fffffffull && (uint64_t)sh.wgs * G.n_chunks <= 0x7fffffffull;
+    return (uint64_t)G.u_n_waves * sh.parts <= 0x7fffffffull && (uint64_t)sh.wgs * G.n_chunks < kPcMaxWgs;
 }
 
 bool pieces_batch(const Geom &G, int wide) {
@@ -603,7 +605,7 @@ std::vector<uint32_t> pieces_plan_ragged(Geom &G, const ChunkDesc *d) {
         none_super = none_super && sh.parts == 1u;
         some = some || all_packed || sh.run > 1u || sh.segs > 1u;
         wgs += sh.wgs;
-        ok = ok && wgs <= 0x7fffffffull;
+        ok = ok && wgs < kPcMaxWgs;
         wg_base[c + 1] = (uint32_t)wgs;
     }
     if (!(ok && some && (all_super || none_super))) return {};

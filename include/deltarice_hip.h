@@ -244,6 +244,13 @@ uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 #define DRX_ENC_STREAM 5u      /* k_encode_stream: persistent, a ring per wavefront, a scanner */
 #define DRX_ENC_STREAM_SEGS 6u /* k_encode_stream_segs: the same over segments of long waveforms */
 uint32_t drx_plan_last_encode_path(const drx_plan *plan);
+/* Limits of the encoders (a launch carries fewer than 2^32 threads).  DRX_ENC_FUSED and DRX_ENC_SEGMENTS give every waveform
+ * (the segment encoder: every 8192-sample segment slot too) a wavefront of one launch and take batches of at most 2^26 - 8
+ * of them; DRX_ENC_PIECES takes fewer than 2^23 workgroups, DRX_ENC_STREAM fewer than 2^32 - 2^16 waveforms and
+ * DRX_ENC_STREAM_SEGS as many tickets.  A batch beyond an encoder's limit is not admitted to it, by default or by a
+ * DRX_DBG_FORCE_* flag, and takes the next encoder that admits it; DRX_ENC_TWO_PASS (launched in slices of 2^24
+ * waveforms) and drx_estimate_words (several waveforms to a wavefront) have no such limit.  drx_plan_last_encode_path says
+ * which encoder ran. */
 /* Copies n_i of every waveform to host memory (waits for the stream). */
 drx_status drx_plan_read_wave_words(drx_plan *plan, uint32_t *host_out);
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from test_gpu_routes import BATCHES
-from test_select_abi import brute_force_lengths
+from test_select_abi import boundary_indices, brute_force_lengths, large_geometries, length_of
 
 
 def test_libraries_export_the_gather_entry_points():
@@ -88,3 +88,26 @@ def test_gather_geometry_arguments():
         gather_geometry([2 ** 30] * 4, [0] * 4, [0, 1], 2)  # an output chunk of 2^31 samples
     N, L = gather_geometry([2 ** 30] * 4, [0] * 4, [0, 1], 1)
     assert N.tolist() == [2 ** 30] * 2 and L.tolist() == [2 ** 30] * 2
+
+
+@pytest.mark.parametrize("name", ["fused-7000", "packed-64"])
+@pytest.mark.parametrize("cw", [1, 3, 2000])
+def test_gather_geometry_past_2_31_and_2_32_samples(name, cw):
+    """gather_geometry of entries whose first sample needs bit 31 or bit 32, against the loop: indices as Python ints, int64
+    and uint32."""
+    pytest.importorskip("torch")
+    from deltarice_amd import DeltaRiceError
+    from deltarice_amd.codec import gather_geometry
+    Ns, Ls = large_geometries()[name]
+    idx, W = boundary_indices(Ns, Ls)
+    lens = {g: length_of(Ns, Ls, g) for g in idx}
+    want, bad = brute_force_gather(lens, idx, cw)
+    assert bad is None
+    assert int(want[0].sum()) == len(idx) * Ls[0]
+    for given in (idx, np.array(idx, dtype=np.int64), np.array(idx, dtype=np.uint32)):
+        N, L = gather_geometry(Ns, Ls, given, cw)
+        assert N.dtype == np.int64 and L.dtype == np.int64
+        assert np.array_equal(N, want[0]) and np.array_equal(L, want[1]), type(given)
+    for out_of_range in ([0, W], np.array([W], dtype=np.uint32)):
+        with pytest.raises(DeltaRiceError):
+            gather_geometry(Ns, Ls, out_of_range, cw)
