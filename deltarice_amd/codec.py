@@ -257,6 +257,15 @@ class Plan:
 
     __del__ = close
 
+    def set_filter(self, taps: Optional[Sequence[int]] = None):
+        """Another prediction filter for this plan, which may have been used (waits for the context's stream); None or
+        (1, -1): the delta filter again.  Gathered.plan() carries over the filter set here."""
+        t = (1, -1) if taps is None else tuple(int(v) for v in taps)
+        arr = (C.c_int32 * max(len(t), 1))(*t)
+        self.ctx._check(self.ctx.lib.drx_plan_set_filter(self._h, len(t), arr))
+        t = tuple(int(v) for v in arr[:len(t)])
+        self._taps = None if t == (1, -1) else t
+
     def _dev_check(self, t: torch.Tensor, dtype, n: int, name: str):
         if t.device != self.ctx.device or t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
             raise DeltaRiceError(1, f"{name}: need contiguous {dtype} tensor of >= {n} elements on {self.ctx.device}")

@@ -12,7 +12,6 @@ Nothing here runs on the CPU but the loop over candidate filters; the samples st
 """
 from __future__ import annotations
 
-import ctypes as C
 import itertools
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -52,8 +51,7 @@ def optimise(ctx: Context, x: torch.Tensor, chunk_samples: int, wave_len: int, t
 
     def size_of(f: Tuple[int, ...]) -> np.ndarray:
         if f not in seen:
-            t = (C.c_int32 * len(f))(*f)
-            ctx._check(ctx.lib.drx_plan_set_filter(plan._h, len(f), t))  # ([1, -1] selects the delta kernels again)
+            plan.set_filter(f)  # ([1, -1] selects the delta kernels again)
             seen[f] = plan.estimate_words(x)
         return seen[f]
 

@@ -112,7 +112,11 @@ drx_status drx_plan_create_uniform(drx_ctx *ctx, uint64_t n_chunks, uint32_t chu
  *                              its own behind it (DRX_PATH_IIR);
  *   anything else              the two-pass encoder and the simple decode kernel (DRX_PATH_SIMPLE): a lane per waveform, serial.
  * The arithmetic is the reference's modulo 2^16, the division by the whole int32 taps[0] towards zero; tests/test_gpu_filter_domain.py
- * holds every route to it over this domain (1 to 64 taps, coefficients up to the int32 extremes, any lead but 0). */
+ * holds every route to it over this domain (1 to 64 taps, coefficients up to the int32 extremes, any lead but 0).
+ *   May be called on a plan that has been used, any number of times: it WAITS for the context's stream (calls in flight still
+ * read the old filter's device tables, which it frees or replaces), forgets the code length the plan's last encode measured
+ * (the next encode chooses its kernel as a new plan's would) and ends a pending drx_gather_encoded sizing call's resume.
+ * The plan's geometry, scratch, RiceParameter and status word stay as they are. */
 drx_status drx_plan_set_filter(drx_plan *plan, uint32_t n_taps, const int32_t *taps);
 void drx_plan_destroy(drx_plan *plan);
 uint64_t drx_plan_n_chunks(const drx_plan *plan);
@@ -217,7 +221,14 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *plan, const uint32_t *d_
 drx_status drx_estimate_words(drx_plan *plan, const int16_t *d_in, uint64_t words_out[16]);
 
 /* Waits for the plan's last encode/decode, reports device-side errors and (for
- * encode) the number of words produced.  total_words may be NULL. */
+ * encode) the number of words produced.  total_words may be NULL.
+ *   It reports the plan's LAST encode, decode, select or gather call only: every such call (a select or gather of no entries
+ * excepted, which launches nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
+ * (and the word count) of an earlier call that was never finished is not kept.  drx_estimate_words,
+ * drx_plan_read_wave_words and drx_plan_set_filter leave the status word as it is: a finish behind them still reports the
+ * encode or decode before them.  A caller
+ * that needs the verdict of every call finishes each one before the plan's next.  Calls on OTHER plans of the context do not
+ * touch this plan's status.  An error reported here leaves the plan usable: the next call starts clean. */
 drx_status drx_plan_finish(drx_plan *plan, uint64_t *total_words);
 
 /* Device-side tables of the last call (valid until the next call on the plan):
