@@ -19,6 +19,10 @@ DRX_MAX_TAPS = 64
 PATH_LANES_FUSED, PATH_LANES, PATH_BLOCKS, PATH_LONG, PATH_SIMPLE, PATH_IIR, PATH_IIR_FUSED = 1, 2, 4, 8, 16, 32, 64
 PATH_SELECT = 128
 PATH_GATHER = 256
+PATH_STATS = 512
+# DRX_STAT_*: the columns of a drx_wave_stats row (tests/test_wave_stats_abi.py holds them equal)
+STAT_MIN, STAT_ARGMIN, STAT_MAX, STAT_ARGMAX, STAT_SUM, STAT_SUMSQ, STAT_HEAD_SUM, STAT_HEAD_SUMSQ = range(8)
+STAT_COLS = 8
 ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
 DBG_NO_LONG_PATHS = 256
 DBG_LONG_NOT_BLOCKS = 512
@@ -83,6 +87,8 @@ SIGNATURES = {
     "drx_decode_select_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _vp, _u64]),
     "drx_gather_encoded": (C.c_int, [_vp, _vp, _u64, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
     "drx_gather_encoded_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
+    "drx_wave_stats": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp]),
+    "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "drx_estimate_words": (C.c_int, [_vp, _vp, C.POINTER(_u64)]),
     "drx_plan_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "drx_plan_finish": (C.c_int, [_vp, C.POINTER(_u64)]),

@@ -452,6 +452,48 @@ class Plan:
                                                 wave_words, off, tab)
         return Gathered(EncodedBatch(out_words, off, self.finish()), N, L, tab, self._rice_m, self._taps)
 
+    def wave_stats_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, head: int = 0,
+                         out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None,
+                         in_words: Optional[int] = None) -> torch.Tensor:
+        """Launches drx_wave_stats on the context's stream: int64 [total_waves, STAT_COLS], row g = (min, argmin, max, argmax,
+        sum, sum of squares, head sum, head sum of squares) of waveform g over the int16 samples decode() would give, exact;
+        first occurrences; ``head``: the window of the last two columns, the first min(head, len) samples.  Nothing is decoded
+        to memory.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).
+        Launch only; finish() raises on device-side errors."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "wave_stats: the plan is closed")
+        head = int(head)
+        if not 0 <= head < 1 << 32:
+            raise DeltaRiceError(1, f"head: {head} is not a uint32")
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        if out is None:
+            out = torch.empty((self.total_waves, _lib.STAT_COLS), dtype=torch.int64, device=self.ctx.device)
+        self._dev_check(out, torch.int64, self.total_waves * _lib.STAT_COLS, "out")
+        n = words.numel() if in_words is None else int(in_words)
+        lib = self.ctx.lib
+        if wave_words is None:
+            st = lib.drx_wave_stats(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), head, out.data_ptr())
+        else:
+            st = lib.drx_wave_stats_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
+                                                    wave_words.data_ptr(), head, out.data_ptr())
+        self.ctx._check(st)
+        return out
+
+    def wave_stats(self, enc: EncodedBatch, head: int = 0, out: Optional[torch.Tensor] = None,
+                   wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """wave_stats_async on an EncodedBatch; waits, and raises like decode().  The cuts of an analysis come from its
+        columns: ``plan.gather_encoded(enc, torch.nonzero(cut(stats)).flatten().cpu(), 2000)``."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "wave_stats: the plan is closed")
+        cur = torch.cuda.current_stream(self.ctx.device)
+        self.ctx.stream.wait_stream(cur)
+        s = self.wave_stats_async(enc.words, enc.chunk_word_off, head, out, wave_words, in_words=enc.total_words)
+        self.finish()
+        return s
+
     def estimate_words(self, x: torch.Tensor) -> np.ndarray:
         """Exact encoded size (uint32 words) of this batch for RiceParameter 2^k, k = 0..15 -- the
         optimisation the reference's docs/Optimization.md describes; argmin gives the best m."""
@@ -464,7 +506,7 @@ class Plan:
 
     def last_timings(self):
         """Kernel times (ms) of the last call, HIP events on the context's stream; needs
-        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode: (walk, decode, 0, total)."""
+        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode and wave_stats: (walk, kernel, 0, total)."""
         ms = (C.c_float * 4)()
         self.ctx._check(self.ctx.lib.drx_plan_last_timings(self._h, ms))
         return tuple(float(v) for v in ms)

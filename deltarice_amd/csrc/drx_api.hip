@@ -1041,6 +1041,40 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *p, const uint32_t *d_in,
     } catch (const std::bad_alloc &) { return fail(p->ctx, DRX_ERR_NOMEM, "gather_encoded: host memory for a list of %llu entries", (unsigned long long)n_sel); }
 }
 
+// ---------------------------------------------------------------------------
+// per-waveform statistics from the encoded stream (drx_stats.hip)
+// ---------------------------------------------------------------------------
+static drx_status wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             const uint32_t *d_sideband, bool sideband, uint32_t head_len, int64_t *d_out) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (!d_in || !d_chunk_word_off || !d_out || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "wave_stats: null pointer");
+    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    DRX_ON_DEVICE(ctx);
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
+        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
+                                            p->d_status, ctx->stream));
+    DRX_HIP(ctx, launch_wave_stats(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, head_len,
+                                   p->d_status, d_out, ctx->profile ? p->ev : nullptr, ctx->stream));
+    p->last_path = DRX_PATH_STATS;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+drx_status drx_wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t head_len,
+                          int64_t *d_out) {
+    return wave_stats(p, d_in, in_words, d_chunk_word_off, nullptr, false, head_len, d_out);
+}
+
+drx_status drx_wave_stats_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                          const uint32_t *d_wave_words, uint32_t head_len, int64_t *d_out) {
+    return wave_stats(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, head_len, d_out);
+}
+
 // Header chain of ONE encoded chunk in host memory (src/deltaRice.c:320-325), with the validation the device
 // walk does: sample count, every n_i between 1 + k and 25 bits per sample, the chain ends exactly at the chunk end.
 static bool walk_chunk_host(const uint32_t *w, uint64_t n_words, uint32_t n_samples, uint32_t wave_len, uint32_t k,

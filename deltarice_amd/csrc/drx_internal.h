@@ -160,6 +160,11 @@ hipError_t launch_gather(const Geom &G, const uint32_t *d_in, const uint64_t *d_
                          uint32_t *d_out, uint64_t out_cap, uint64_t *d_out_chunk_off, uint32_t *d_out_wave_words,
                          uint32_t *d_ent_words, uint64_t *d_ent_pos, uint64_t *d_block_sum, uint32_t *d_ctrl, bool tiles,
                          uint64_t mean_words, bool resume, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+// drx_wave_stats (drx_stats.hip): behind the whole batch's walk (tables_ready: the side-band's tables are in place), a lane per
+// waveform that parses and reduces: int64 d_out[total_waves][DRX_STAT_COLS].  ev: {start, walk's end, kernel's end, end}
+hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t head_len,
+                             DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 
 // wide: fused_wide() as the route decided it

@@ -215,6 +215,41 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *plan, const uint32_t *d_
                                               const uint64_t *wave_idx, uint64_t n_sel, uint64_t out_chunk_waves, uint32_t *d_out,
                                               uint64_t out_cap_words, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
 
+/* Per-waveform STATISTICS straight from the encoded stream: what a cut needs of a waveform -- a baseline, an extreme and where
+ * it sits, an integral, a noise figure -- without decoding the batch to memory.  d_out: int64[total_waves][DRX_STAT_COLS] on the
+ * device; row g holds the eight values of global waveform g (the order of drx_plan_wave_words), computed over the int16 samples
+ * y[0 .. len) that drx_decode would write for it (len = WaveformLength, or less for the last waveform of a chunk, which is a row
+ * like any other; the samples of an unsigned dataset are read as int16, as they are coded).  Everything is exact: a waveform has
+ * fewer than 2^31 samples, so every sum fits an int64.  head_len: the window of the two HEAD columns, e.g. a baseline in front
+ * of the pulse; 0 gives 0 in both, a value beyond len the whole waveform.
+ *   Asynchronous on the context's stream like drx_decode; the call clears the plan's status word first, errors found on the
+ * device arrive at drx_plan_finish.  Validation is drx_decode's: the header chain of every chunk is walked and judged, and a
+ * payload that ends before its samples do, or whose codes do not end in its last payload word, is DRX_ERR_CORRUPT; the rows
+ * are then undefined and the plan stays usable.  DRX_ERR_ARG, with nothing launched and the status word as it was: a NULL pointer.
+ *   The buffers rule at the top of this file holds: any 4-byte alignment of d_in and any 8-byte alignment of d_out; exactly
+ * 8 * total_waves int64 are written; the result depends neither on what they held before nor on words outside [0, in_words),
+ * and no load leaves [0, in_words).
+ *   Every prediction filter the plan accepts: the delta filter a lane per waveform that parses as the lane decoder does and
+ * reduces in registers; any other filter a lane per waveform in a serial kernel, correct but not fast.  Few long waveforms go
+ * through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow: a wavefront or workgroup per long
+ * waveform is not built).  drx_plan_last_decode_path reports DRX_PATH_STATS alone. */
+#define DRX_STAT_MIN 0        /* smallest sample                                   */
+#define DRX_STAT_ARGMIN 1     /* smallest i with y[i] == MIN                        */
+#define DRX_STAT_MAX 2
+#define DRX_STAT_ARGMAX 3     /* smallest i with y[i] == MAX                        */
+#define DRX_STAT_SUM 4        /* sum of y[i], all i                                 */
+#define DRX_STAT_SUMSQ 5      /* sum of y[i]^2                                      */
+#define DRX_STAT_HEAD_SUM 6   /* sum of y[i], i < min(head_len, len)                */
+#define DRX_STAT_HEAD_SUMSQ 7 /* sum of y[i]^2 over the same window                 */
+#define DRX_STAT_COLS 8
+drx_status drx_wave_stats(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                          uint32_t head_len, int64_t *d_out);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
+ * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_wave_stats_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                          const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, uint32_t head_len,
+                                          int64_t *d_out);
+
 /* RiceParameter optimiser (docs/Optimization.md:5-19 of the reference describes one, the tree does not
  * contain it): exact number of uint32 words drx_encode would emit for this batch with RiceParameter
  * 2^k, for every k = 0..15 (host array of 16), in one pass over the samples.  Synchronous. */
@@ -222,7 +257,7 @@ drx_status drx_estimate_words(drx_plan *plan, const int16_t *d_in, uint64_t word
 
 /* Waits for the plan's last encode/decode, reports device-side errors and (for
  * encode) the number of words produced.  total_words may be NULL.
- *   It reports the plan's LAST encode, decode, select or gather call only: every such call (a select or gather of no entries
+ *   It reports the plan's LAST encode, decode, select, gather or statistics call only: every such call (a select or gather of no entries
  * excepted, which launches nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
  * (and the word count) of an earlier call that was never finished is not kept.  drx_estimate_words,
  * drx_plan_read_wave_words and drx_plan_set_filter leave the status word as it is: a finish behind them still reports the
@@ -245,6 +280,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_IIR_FUSED 64u  /* the general filter's inverse inside the block decoder: one kernel, samples straight to the output */
 #define DRX_PATH_SELECT 128u    /* drx_decode_select: a wavefront (general filters: a lane) per selected waveform; reported alone */
 #define DRX_PATH_GATHER 256u    /* drx_gather_encoded: word ranges copied, nothing decoded; reported alone */
+#define DRX_PATH_STATS 512u     /* drx_wave_stats: a lane per waveform that parses and reduces; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -278,7 +314,8 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  * stream (needs the context option "profile" = 1 before the call; waits for it).
  *   after drx_encode: ms = { size pass, offset scan, pack pass, whole call }
  *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call }
- *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call } */
+ *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
+ *   after drx_wave_stats: ms = { header-chain walk, statistics kernel, 0, whole call } */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 
 /* Tuning / diagnostics.  Returns DRX_ERR_ARG for unknown keys or values.
