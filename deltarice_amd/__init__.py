@@ -7,7 +7,7 @@ chunks over the GPUs of a node; ``optimise`` searches RiceParameter and encoding
 (docs/Optimization.md of the reference).  There is no CPU implementation in this package.
 """
 from ._lib import DeltaRiceError, LIB_PATH, PLUGIN_PATH  # noqa: F401
-from ._lib import (PATH_STATS, STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD_SUMSQ, STAT_MAX,  # noqa: F401
+from ._lib import (PATH_STATS, PATH_TRANSCODE, STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD_SUMSQ, STAT_MAX,  # noqa: F401
                    STAT_MIN, STAT_SUM, STAT_SUMSQ)
 
 H5FILTER = 32025
@@ -15,7 +15,7 @@ H5FILTER = 32025
 
 def __getattr__(name):
     # torch is only needed for the device-resident API; keep `import deltarice_amd` light
-    if name in ("Context", "Plan", "EncodedBatch", "Gathered", "parse_opts"):
+    if name in ("Context", "Plan", "EncodedBatch", "Gathered", "Transcoded", "parse_opts"):
         from . import codec
         return getattr(codec, name)
     raise AttributeError(name)

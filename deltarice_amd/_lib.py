@@ -20,6 +20,7 @@ PATH_LANES_FUSED, PATH_LANES, PATH_BLOCKS, PATH_LONG, PATH_SIMPLE, PATH_IIR, PAT
 PATH_SELECT = 128
 PATH_GATHER = 256
 PATH_STATS = 512
+PATH_TRANSCODE = 1024
 # DRX_STAT_*: the columns of a drx_wave_stats row (tests/test_wave_stats_abi.py holds them equal)
 STAT_MIN, STAT_ARGMIN, STAT_MAX, STAT_ARGMAX, STAT_SUM, STAT_SUMSQ, STAT_HEAD_SUM, STAT_HEAD_SUMSQ = range(8)
 STAT_COLS = 8
@@ -89,6 +90,9 @@ SIGNATURES = {
     "drx_gather_encoded_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
     "drx_wave_stats": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp]),
     "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
+    "drx_transcode": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),
+    "drx_transcode_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
+    "drx_estimate_words_encoded": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
     "drx_estimate_words": (C.c_int, [_vp, _vp, C.POINTER(_u64)]),
     "drx_plan_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "drx_plan_finish": (C.c_int, [_vp, C.POINTER(_u64)]),

@@ -156,6 +156,27 @@ class Gathered:
         return ctx.plan(N.tolist(), L.tolist(), self.rice_m, self.taps)
 
 
+@dataclass
+class Transcoded:
+    """What Plan.transcode returns: the source batch re-coded at another RiceParameter, and all that is needed to use it."""
+    enc: EncodedBatch             # the chunks, back to back, with their offset table
+    wave_words: torch.Tensor      # int32 [total_waves] on the device: n_i of every waveform, the result's side-band
+    rice_m: int                   # the RiceParameter of the result ...
+    taps: Optional[tuple]         # ... and the source plan's prediction filter (None: delta)
+    chunk_samples: np.ndarray     # int64 [n_chunks]: the source plan's geometry (what Context.plan() takes)
+    wave_lens: np.ndarray
+
+    def plan(self, ctx: "Context") -> "Plan":
+        """The plan of the result: the source's geometry and filter, the new RiceParameter."""
+        N, L = np.asarray(self.chunk_samples, dtype=np.int64), np.asarray(self.wave_lens, dtype=np.int64)
+        if N.size == 0:
+            raise DeltaRiceError(1, "an empty batch has no plan")
+        if (N == N[0]).all() and (L == L[0]).all():
+            ftaps = (len(self.taps),) + tuple(int(t) & 0xFFFFFFFF for t in self.taps) if self.taps else ()
+            return ctx.plan_uniform(int(N.size), int(N[0]), (self.rice_m, int(L[0]) if L[0] > 0 else 0xFFFFFFFF) + ftaps)
+        return ctx.plan(N.tolist(), L.tolist(), self.rice_m, self.taps)
+
+
 class Context:
     """One GPU, one HIP stream (a torch stream, so torch events/ordering apply to it)."""
 
@@ -494,6 +515,79 @@ class Plan:
         self.finish()
         return s
 
+    def estimate_words_encoded(self, enc: EncodedBatch, wave_words: Optional[torch.Tensor] = None) -> np.ndarray:
+        """estimate_words from the encoded stream: entry k is the total words transcode() gives at RiceParameter 2^k, k = 0..15;
+        nothing is decoded to memory.  wave_words: the source's n_i table (no header walk).  Waits; raises DRX_ERR_CORRUPT for a
+        stream that fails validation."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "estimate_words_encoded: the plan is closed")
+        self._dev_check(enc.words, torch.int32, 1, "words")
+        self._dev_check(enc.chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        out = (C.c_uint64 * 16)()
+        self.ctx._check(self.ctx.lib.drx_estimate_words_encoded(self._h, enc.words.data_ptr(), int(enc.total_words),
+                                                                enc.chunk_word_off.data_ptr(),
+                                                                wave_words.data_ptr() if wave_words is not None else None, out))
+        return np.array(list(out), dtype=np.uint64)
+
+    def transcode_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, rice_m: int,
+                        out_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
+                        wave_words: Optional[torch.Tensor] = None, out_chunk_word_off: Optional[torch.Tensor] = None,
+                        out_wave_words: Optional[torch.Tensor] = None):
+        """Launches drx_transcode on the context's stream: the batch re-coded -- not decoded -- at RiceParameter ``rice_m`` into
+        ``out_words`` (int32, its numel the capacity).  out_words None: the SIZING call, which writes the two tables only;
+        finish() then returns the words needed.  -> (out_words, out_chunk_word_off int64 [n_chunks + 1], out_wave_words int32
+        [total_waves]).  finish() raises on device-side errors (DRX_ERR_CAPACITY, DRX_ERR_CORRUPT: nothing was written)."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "transcode: the plan is closed")
+        k = parse_opts((int(rice_m),)).rice_k
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        if out_words is not None:
+            self._dev_check(out_words, torch.int32, 0, "out_words")
+        if out_chunk_word_off is None:
+            out_chunk_word_off = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=self.ctx.device)
+        self._dev_check(out_chunk_word_off, torch.int64, self.n_chunks + 1, "out_chunk_word_off")
+        if out_wave_words is None:
+            out_wave_words = torch.empty(self.total_waves, dtype=torch.int32, device=self.ctx.device)
+        self._dev_check(out_wave_words, torch.int32, self.total_waves, "out_wave_words")
+        n = words.numel() if in_words is None else int(in_words)
+        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
+        lib = self.ctx.lib
+        if wave_words is None:
+            st = lib.drx_transcode(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), k, op, cap,
+                                   out_chunk_word_off.data_ptr(), out_wave_words.data_ptr())
+        else:
+            st = lib.drx_transcode_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), wave_words.data_ptr(),
+                                                   k, op, cap, out_chunk_word_off.data_ptr(), out_wave_words.data_ptr())
+        self.ctx._check(st)
+        return out_words, out_chunk_word_off, out_wave_words
+
+    def transcode(self, enc: EncodedBatch, rice_m: Optional[int] = None, wave_words: Optional[torch.Tensor] = None,
+                  out_words: Optional[torch.Tensor] = None) -> "Transcoded":
+        """The batch re-coded at RiceParameter ``rice_m`` without decoding it: for a filter with lead +-1 byte for byte what
+        encode() gives for the decoded samples at that parameter, for every filter a stream that decodes to the same samples.
+        rice_m None: the parameter of the smallest total of estimate_words_encoded() (on a tie the smaller).  out_words None:
+        sized by a first call and allocated exactly -- that costs a second sizes pass, so a caller that has a bound (the
+        plan's max_encoded_words bounds any result) should pass out_words; otherwise DRX_ERR_CAPACITY if the result does not
+        fit it.  Waits, and raises like decode()."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "transcode: the plan is closed")
+        if rice_m is None:
+            rice_m = 1 << int(np.argmin(self.estimate_words_encoded(enc, wave_words)))  # (argmin: the first of equals)
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        off = tab = None
+        if out_words is None:
+            _, off, tab = self.transcode_async(enc.words, enc.chunk_word_off, rice_m, None, enc.total_words, wave_words)
+            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
+        _, off, tab = self.transcode_async(enc.words, enc.chunk_word_off, rice_m, out_words, enc.total_words, wave_words, off, tab)
+        return Transcoded(EncodedBatch(out_words, off, self.finish()), tab, int(rice_m), self._taps,
+                          self._chunk_samples.copy(), self._wave_lens.copy())
+
     def estimate_words(self, x: torch.Tensor) -> np.ndarray:
         """Exact encoded size (uint32 words) of this batch for RiceParameter 2^k, k = 0..15 -- the
         optimisation the reference's docs/Optimization.md describes; argmin gives the best m."""
@@ -506,7 +600,8 @@ class Plan:
 
     def last_timings(self):
         """Kernel times (ms) of the last call, HIP events on the context's stream; needs
-        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode and wave_stats: (walk, kernel, 0, total)."""
+        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode and wave_stats: (walk, kernel, 0, total);
+        transcode: (walk, sizes + scan + offsets, pack, total)."""
         ms = (C.c_float * 4)()
         self.ctx._check(self.ctx.lib.drx_plan_last_timings(self._h, ms))
         return tuple(float(v) for v in ms)

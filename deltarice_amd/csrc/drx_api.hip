@@ -133,6 +133,9 @@ struct drx_plan {
     size_t sel_cap = 0;                       // ... bytes of each
     uint32_t *d_sel_fail = nullptr;           // uint32[n_chunks]: chunks the chunk-wide walk handed to the scalar walker
     hipEvent_t sel_copied = nullptr;          // the staging buffer has crossed to the device (the next call may fill it again)
+    // drx_transcode / drx_estimate_words_encoded: uint64 chunk_words[n_chunks + 1] | uint64 est[16] | uint32 n_i'[W] | uint32
+    // header positions[W] of the RESULT (the plan's own tables describe the source); allocated by the first such call
+    void *d_trc = nullptr;
     void *d_gat = nullptr;                    // drx_gather_encoded: positions, sizes and scan state (gather_scratch())
     size_t gat_cap = 0;
     // ... and what the plan's last call was asked IF that call was a gather's SIZING call (d_out == NULL: it wrote no output): its
@@ -1073,6 +1076,94 @@ drx_status drx_wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, 
 drx_status drx_wave_stats_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                           const uint32_t *d_wave_words, uint32_t head_len, int64_t *d_out) {
     return wave_stats(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, head_len, d_out);
+}
+
+// ---------------------------------------------------------------------------
+// re-coding to another RiceParameter, and the sizes at every one, from the encoded stream (drx_transcode.hip)
+// ---------------------------------------------------------------------------
+struct TrcScratch {
+    uint64_t *chunk_words;
+    unsigned long long *est;
+    uint32_t *words, *rel;
+};
+static drx_status trc_scratch(drx_plan *p, TrcScratch *t) {
+    drx_ctx *ctx = p->ctx;
+    const uint64_t W = p->G.total_waves ? p->G.total_waves : 1, C = p->G.n_chunks + 1;
+    if (!p->d_trc) {
+        const hipError_t e = p->mem.alloc(&p->d_trc, (C + 16) * sizeof(uint64_t) + 2 * W * sizeof(uint32_t));
+        if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "transcode scratch: %s", hipGetErrorString(e));
+    }
+    t->chunk_words = (uint64_t *)p->d_trc;
+    t->est = (unsigned long long *)(t->chunk_words + C);
+    t->words = (uint32_t *)(t->est + 16);
+    t->rel = t->words + W;
+    return DRX_OK;
+}
+
+static drx_status transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                            const uint32_t *d_sideband, bool sideband, uint32_t new_k, uint32_t *d_out, uint64_t out_cap,
+                            uint64_t *d_out_off, uint32_t *d_out_wave_words) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (new_k > 15u) return fail(ctx, DRX_ERR_ARG, "transcode: new_rice_k %u (0..15)", new_k);
+    if (!d_in || !d_chunk_word_off || !d_out_off || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "transcode: null pointer");
+    if (!d_out && out_cap) return fail(ctx, DRX_ERR_ARG, "transcode: no output buffer but a capacity of %llu words", (unsigned long long)out_cap);
+    if (sideband && (d_sideband == p->d_wave_words || d_out_wave_words == d_sideband))
+        return fail(ctx, DRX_ERR_ARG, "the side-band table must be neither the plan's own nor the output's (copy it first)");
+    DRX_ON_DEVICE(ctx);
+    TrcScratch t;
+    if (const drx_status st = trc_scratch(p, &t)) return st;
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
+        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
+                                            p->d_status, ctx->stream));
+    DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, new_k,
+                                  t.words, t.rel, t.chunk_words, d_out, out_cap, d_out_off, d_out_wave_words, nullptr, p->d_status,
+                                  ctx->profile ? p->ev : nullptr, ctx->stream));
+    p->last_path = DRX_PATH_TRANSCODE;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+drx_status drx_transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t new_rice_k,
+                         uint32_t *d_out, uint64_t out_cap_words, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words) {
+    return transcode(p, d_in, in_words, d_chunk_word_off, nullptr, false, new_rice_k, d_out, out_cap_words, d_out_chunk_word_off,
+                     d_out_wave_words);
+}
+
+drx_status drx_transcode_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                         const uint32_t *d_wave_words, uint32_t new_rice_k, uint32_t *d_out, uint64_t out_cap_words,
+                                         uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words) {
+    return transcode(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, new_rice_k, d_out, out_cap_words, d_out_chunk_word_off,
+                     d_out_wave_words);
+}
+
+drx_status drx_estimate_words_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                      const uint32_t *d_wave_words, uint64_t words_out[16]) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (!d_in || !d_chunk_word_off || !words_out) return fail(ctx, DRX_ERR_ARG, "estimate_words_encoded: null pointer");
+    if (d_wave_words && d_wave_words == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    DRX_ON_DEVICE(ctx);
+    TrcScratch t;
+    if (const drx_status st = trc_scratch(p, &t)) return st;
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    if (d_wave_words)
+        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_wave_words, p->d_wave_off, p->d_wave_words,
+                                            p->d_status, ctx->stream));
+    DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, d_wave_words != nullptr, p->d_pw,
+                                  0u, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, t.est, p->d_status,
+                                  ctx->profile ? p->ev : nullptr, ctx->stream));
+    p->last_path = DRX_PATH_TRANSCODE;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    DRX_HIP(ctx, hipMemcpyAsync(words_out, t.est, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    return drx_plan_finish(p, nullptr);  // (waits; a stream that failed validation: DRX_ERR_CORRUPT, words_out undefined)
 }
 
 // Header chain of ONE encoded chunk in host memory (src/deltaRice.c:320-325), with the validation the device

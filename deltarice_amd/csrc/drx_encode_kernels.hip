@@ -779,6 +779,15 @@ hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uin
 }
 
 // ev: optional 4 events recorded before / between / after the kernels (profiling).
+// header positions, chunk offsets, the total and kErrCapacity from a table of n_i that another pass made (drx_transcode.hip);
+// the encoders' pinned word count (Geom::host_words) is left alone: the result is no encode of this plan's
+hipError_t launch_chunk_offsets(const Geom &G, const uint32_t *d_wave_words, uint32_t *d_wave_rel, uint64_t *d_chunk_words,
+                                uint64_t *d_chunk_word_off, uint64_t out_cap, DevStatus *d_status, hipStream_t s) {
+    k_chunk_scan<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, d_wave_words, d_wave_rel, d_chunk_words);
+    k_chunk_offsets<<<1, 1024, 0, s>>>(G.n_chunks, d_chunk_words, d_chunk_word_off, out_cap, d_status, nullptr);
+    return hipGetLastError();
+}
+
 hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
                          uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint32_t *d_wave_rel,
                          uint64_t *d_chunk_words, DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {

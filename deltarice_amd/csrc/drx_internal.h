@@ -166,6 +166,19 @@ hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_wo
                              uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t head_len,
                              DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
+// k_chunk_scan + k_chunk_offsets (drx_encode_kernels.hip) over a table of n_i that is not an encode's: header positions relative
+// to the chunk, chunk offsets, DevStatus::total_words and kErrCapacity against out_cap
+hipError_t launch_chunk_offsets(const Geom &G, const uint32_t *d_wave_words, uint32_t *d_wave_rel, uint64_t *d_chunk_words,
+                                uint64_t *d_chunk_word_off, uint64_t out_cap, DevStatus *d_status, hipStream_t s);
+// drx_transcode / drx_estimate_words_encoded (drx_transcode.hip): behind the whole batch's walk, a lane per waveform that parses
+// and sizes at RiceParameter 2^k2, the scan above over the new table (d_new_*: scratch of the call), then a lane per waveform
+// that parses and packs.  d_out == nullptr: as far as the offsets.  d_est != nullptr: the words at every k alone (uint64[16]).
+// ev: {start, walk's end, offsets' end, end}
+hipError_t launch_transcode(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                            uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t k2,
+                            uint32_t *d_new_words, uint32_t *d_new_rel, uint64_t *d_new_chunk_words, uint32_t *d_out,
+                            uint64_t out_cap, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words,
+                            unsigned long long *d_est, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 
 // wide: fused_wide() as the route decided it
 hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,

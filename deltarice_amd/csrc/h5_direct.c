@@ -608,6 +608,130 @@ out:
     return rc;
 }
 
+/* File -> file: every stored chunk of one dataset re-coded at another RiceParameter, never decoded. */
+drx_status drx_h5_recompress(drx_ctx *ctx, const char *src_file, const char *src_name, const char *dst_file, const char *dst_name,
+                             unsigned rice_m, drx_h5_stats *st) {
+    if (!ctx || !src_file || !src_name || !dst_file || !dst_name) return DRX_ERR_ARG;
+    unsigned k2 = 0;
+    if (rice_m && log2_m(rice_m, &k2)) return DRX_ERR_ARG;
+    {
+        struct stat a, b;  /* (the same file under another name, a hard link included; dst may not exist yet) */
+        if (!strcmp(src_file, dst_file) || (stat(src_file, &a) == 0 && stat(dst_file, &b) == 0 && a.st_dev == b.st_dev && a.st_ino == b.st_ino))
+            return DRX_ERR_ARG;
+    }
+    drx_h5_stats s;
+    memset(&s, 0, sizeof s);
+    dataset_t ds;
+    fetched_t fx;
+    memset(&fx, 0, sizeof fx);
+    drx_plan *plan = NULL;
+    void *d_out = NULL, *h_words = NULL;
+    uint64_t *d_out_off = NULL, *h_off = NULL, *rows = NULL;
+    hid_t f = -1, d = -1, sp = -1, pl = -1, ty = -1;
+    int prev_dev = -1;
+    if (enter_device(ctx, &prev_dev) != 0) return DRX_ERR_DEVICE;
+    hipStream_t stream = (hipStream_t)drx_ctx_stream(ctx);
+    drx_status rc = open_dataset(src_file, src_name, &ds);
+    if (rc != DRX_OK) goto out;
+    rc = DRX_ERR_ARG;
+    const uint64_t n_data_rows = ds.dims[0], cols = ds.dims[1], chunk_rows = ds.chunk[0];
+    if (!n_data_rows || chunk_rows * cols > 0x7fffffffull) goto out;
+    const uint32_t chunk_samples = (uint32_t)(chunk_rows * cols);
+    /* HDF5 stores a last chunk that the rows do not fill at full size: every stored chunk has one geometry */
+    const uint64_t n_chunks = (n_data_rows + chunk_rows - 1) / chunk_rows;
+    s.rows = n_data_rows; s.cols = cols; s.chunk_rows = chunk_rows;
+    s.raw_bytes = n_data_rows * cols * 2;
+
+    /* every stored chunk to the staging buffer and to the device: the first row of each names it */
+    rc = DRX_ERR_NOMEM;
+    if (!(rows = (uint64_t *)malloc(n_chunks * sizeof(uint64_t)))) goto out;
+    for (uint64_t c = 0; c < n_chunks; ++c) rows[c] = c * chunk_rows;
+    fx.wpr = 1;
+    rc = fetch_rows_chunks(ctx, &ds, rows, n_chunks, &fx);
+    s.n_chunks = fx.n_touched;
+    s.stored_bytes = fx.words * 4;
+    s.t_file = fx.t_file;
+    s.t_pcie = fx.t_pcie;
+    if (rc != DRX_OK) goto out;
+
+    /* one estimate where the best parameter is asked for (it gives the result's size too), one transcode */
+    double t0 = now();
+    uint64_t words = 0, cap = 0;
+    if ((rc = drx_plan_create_uniform(ctx, n_chunks, chunk_samples, ds.o.wave_len < 0 ? 0u : (uint32_t)ds.o.wave_len, ds.o.rice_k, &plan)) != DRX_OK) goto out;
+    if ((rc = drx_plan_set_filter(plan, ds.o.n_taps, ds.o.taps)) != DRX_OK) goto out;
+    if (!rice_m) {
+        uint64_t est[16];
+        if ((rc = drx_estimate_words_encoded(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, NULL, est)) != DRX_OK) goto out;
+        for (unsigned k = 1; k < 16; ++k) if (est[k] < est[k2]) k2 = k;  /* (on a tie the smaller) */
+        cap = est[k2];
+    } else {
+        cap = drx_plan_max_encoded_words(plan);
+    }
+    if (hipMalloc(&d_out, cap * 4) != hipSuccess || hipMalloc((void **)&d_out_off, (n_chunks + 1) * 8) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
+    if ((rc = drx_transcode(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, k2, (uint32_t *)d_out, cap, d_out_off, NULL)) != DRX_OK) goto out;
+    if ((rc = drx_plan_finish(plan, &words)) != DRX_OK) goto out;
+    s.t_gpu = now() - t0;
+
+    /* the result to the context's staging buffer (the fetched bytes have left it) */
+    t0 = now();
+    rc = DRX_ERR_NOMEM;
+    h_off = (uint64_t *)malloc((n_chunks + 1) * 8);
+    if (!h_off || drx_ctx_host_staging(ctx, (words + 1) * 4, &h_words) != DRX_OK) goto out;
+    rc = DRX_ERR_DEVICE;
+    if (hipMemcpyAsync(h_off, d_out_off, (n_chunks + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(h_words, d_out, words * 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) goto out;
+    s.t_pcie += now() - t0;
+
+    /* the new dataset: the source's shape, element type and chunking, its cd_values verbatim except the RiceParameter */
+    t0 = now();
+    rc = DRX_ERR_ARG;
+    ensure_filter_registered();
+    unsigned cd[3 + DRX_MAX_TAPS], flags = 0, fcfg = 0;
+    size_t ncd = 3 + DRX_MAX_TAPS;
+    char fname[8];
+    if (H5Pget_filter_by_id2(ds.pl, FILTER_ID, &flags, &ncd, cd, sizeof fname, fname, &fcfg) < 0) goto out;
+    if (ncd == 0) ncd = 1;  /* (a dataset stored under the default RiceParameter names none) */
+    cd[0] = 1u << k2;
+    {
+        hid_t sty = H5Dget_type(ds.d);
+        ty = H5Tcopy(sty);
+        H5Tclose(sty);
+        if (ty < 0) goto out;
+    }
+    if ((f = H5Fcreate(dst_file, H5F_ACC_TRUNC, H5P_DEFAULT, H5P_DEFAULT)) < 0) goto out;
+    hsize_t dims[2] = {n_data_rows, cols}, chunk[2] = {chunk_rows, cols};
+    sp = H5Screate_simple(2, dims, NULL);
+    pl = H5Pcreate(H5P_DATASET_CREATE);
+    if (H5Pset_chunk(pl, 2, chunk) < 0 || H5Pset_filter(pl, FILTER_ID, flags, ncd, cd) < 0) goto out;
+    if ((d = H5Dcreate2(f, dst_name, ty, sp, H5P_DEFAULT, pl, H5P_DEFAULT)) < 0) goto out;
+    for (uint64_t c = 0; c < n_chunks; ++c) {
+        hsize_t off[2] = {c * chunk_rows, 0};
+        if (H5Dwrite_chunk(d, H5P_DEFAULT, 0, off, (size_t)(h_off[c + 1] - h_off[c]) * 4, (const uint32_t *)h_words + h_off[c]) < 0) goto out;
+    }
+    rc = DRX_OK;
+out:
+    if (d >= 0) H5Dclose(d);
+    if (pl >= 0) H5Pclose(pl);
+    if (sp >= 0) H5Sclose(sp);
+    if (ty >= 0) H5Tclose(ty);
+    if (f >= 0) {
+        if (H5Fclose(f) < 0 && rc == DRX_OK) rc = DRX_ERR_ARG;
+        s.t_file += now() - t0;
+        if (rc != DRX_OK) (void)unlink(dst_file);  /* (no half-written file is left behind) */
+    }
+    if (plan) drx_plan_destroy(plan);
+    if (d_out) (void)hipFree(d_out);
+    if (d_out_off) (void)hipFree(d_out_off);
+    free(h_off);
+    free(rows);
+    free_fetched(&fx);
+    close_dataset(&ds);
+    leave_device(prev_dev);
+    if (st) *st = s;
+    return rc;
+}
+
 drx_status drx_h5_write(drx_ctx *ctx, const char *file, const char *name, const int16_t *d_in,
                         uint64_t rows, uint64_t cols, uint64_t chunk_rows, unsigned rice_m,
                         unsigned wave_len, drx_h5_stats *st) {

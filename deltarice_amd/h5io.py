@@ -41,6 +41,8 @@ def _load():
         L.drx_h5_copy_rows.restype = C.c_int
         L.drx_h5_copy_rows.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_char_p,
                                        C.c_char_p, C.c_uint64, C.POINTER(Stats)]
+        L.drx_h5_recompress.restype = C.c_int
+        L.drx_h5_recompress.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint, C.POINTER(Stats)]
         L.drx_h5_write.restype = C.c_int
         L.drx_h5_write.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.c_uint64, C.c_uint, C.c_uint, C.POINTER(Stats)]
@@ -102,6 +104,20 @@ def copy_rows(ctx: Context, src: str, name: str, rows, dst: str, dst_name: str |
                             (name if dst_name is None else dst_name).encode(), 0 if chunk_rows is None else int(chunk_rows), C.byref(st))
     if rc != _lib.DRX_OK:
         raise _lib.DeltaRiceError(rc, f"drx_h5_copy_rows({src!r}, {name!r} -> {dst!r})")
+    return st.as_dict()
+
+
+def recompress(ctx: Context, src: str, name: str, dst: str, dst_name: str | None = None, rice_m: int | None = None) -> dict:
+    """File -> file: dataset ``name`` of ``src`` becomes dataset ``dst_name`` (None: ``name``) of the new file ``dst`` with
+    every stored chunk re-coded at RiceParameter ``rice_m`` (None: the one that makes the dataset smallest) on the GPU as
+    encoded words (drx_transcode), not decoded; shape, element type, chunking and the rest of the compression_opts are the
+    source's.  Returns the stats: n_chunks / stored_bytes = fetched."""
+    st = Stats()
+    ctx.stream.wait_stream(torch.cuda.current_stream(ctx.device))
+    rc = _load().drx_h5_recompress(ctx._h, os.fsencode(src), name.encode(), os.fsencode(dst),
+                                   (name if dst_name is None else dst_name).encode(), 0 if rice_m is None else int(rice_m), C.byref(st))
+    if rc != _lib.DRX_OK:
+        raise _lib.DeltaRiceError(rc, f"drx_h5_recompress({src!r}, {name!r} -> {dst!r})")
     return st.as_dict()
 
 

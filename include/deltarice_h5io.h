@@ -59,6 +59,18 @@ drx_status drx_h5_read_rows(drx_ctx *ctx, const char *file, const char *name, co
 drx_status drx_h5_copy_rows(drx_ctx *ctx, const char *src_file, const char *src_name, const uint64_t *rows, uint64_t n_rows,
                             const char *dst_file, const char *dst_name, uint64_t dst_chunk_rows, drx_h5_stats *stats);
 
+/* File -> file, another RiceParameter: dataset `dst_name` of `dst_file` (created / truncated as drx_h5_write does; dst_file equal
+ * to src_file: DRX_ERR_ARG) receives dataset `src_name` of `src_file` with every stored chunk re-coded at RiceParameter rice_m
+ * (a power of two up to 32768; 0: the one that makes the dataset smallest, on a tie the smaller) and never decoded.  Source
+ * datasets as drx_h5_read takes them.  The stored chunks go to the context's staging buffer and to the device as
+ * drx_h5_copy_rows fetches them; then one drx_estimate_words_encoded (if rice_m is 0), one drx_transcode and H5Dwrite_chunk.
+ * The new dataset has the source's shape, element type and chunking; its cd_values are the source's verbatim except
+ * cd_values[0] (general prediction filters included: the chunks are the bytes the filter would write for the source's data
+ * under the new cd_values).  stats: n_chunks / stored_bytes count what was FETCHED, raw_bytes the int16 bytes the dataset
+ * represents. */
+drx_status drx_h5_recompress(drx_ctx *ctx, const char *src_file, const char *src_name, const char *dst_file, const char *dst_name,
+                             unsigned rice_m, drx_h5_stats *stats);
+
 /* VRAM -> file: encodes d_in (device int16[rows*cols]) and writes it as dataset `name` (file is
  * created/truncated).  rice_m, wave_len: compression_opts (RiceParameter, WaveformLength). */
 drx_status drx_h5_write(drx_ctx *ctx, const char *file, const char *name, const int16_t *d_in,

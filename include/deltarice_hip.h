@@ -250,6 +250,55 @@ drx_status drx_wave_stats_with_wave_words(drx_plan *plan, const uint32_t *d_in, 
                                           const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, uint32_t head_len,
                                           int64_t *d_out);
 
+/* RE-CODE an encoded batch to another RiceParameter, without decoding it.  Under a fixed prediction filter the codes of one
+ * sample at any two RiceParameters carry the same zig-zag value (src/deltaRice.c:207-228), so the stream is parsed, sized, scanned
+ * and packed on residuals: no filter arithmetic, no sample in memory, and every prediction filter the plan accepts -- more than
+ * four taps and leads other than +-1 included -- takes the same kernels.  The plan describes the SOURCE (geometry, filter, its
+ * RiceParameter 2^k); the result is a batch of the same geometry and filter coded at 2^new_rice_k, framed as drx_encode frames it:
+ * N_c | { n_i' | payload_i' }, chunks back to back from d_out[0]; d_out_chunk_word_off (uint64[n_chunks + 1]) is written as
+ * drx_encode writes it (last entry = total words); d_out_wave_words (uint32[total_waves], or NULL) receives every n_i': the
+ * side-band of the result.
+ *   Every residual is the int16 the decoders take from its code, in canonical form: an ordinary code whose value exceeds 65535
+ * (possible from k = 13 on in a foreign stream) folds as drx_decode folds it, an escape that holds a small value comes out as an
+ * ordinary code.  Hence, for a filter with lead +-1, the output is byte for byte drx_encode of the decoded samples at the new
+ * parameter -- what the reference's filter gives; for every filter it decodes, under the new parameter, to exactly what the input
+ * decodes to under the old.  new_rice_k equal to the plan's own is allowed: a canonical stream comes back word for word.
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: new_rice_k > 15, a NULL pointer among d_in,
+ * d_chunk_word_off, d_out_chunk_word_off, d_out == NULL with a capacity.
+ *   Sizing, as in drx_gather_encoded: d_out == NULL (with out_cap_words == 0) runs as far as the offsets: both tables are written,
+ * drx_plan_finish reports the total, nothing else is touched.  With d_out != NULL and a total above out_cap_words:
+ * DRX_ERR_CAPACITY at drx_plan_finish, which still reports the total NEEDED, and not one word of d_out is written.
+ * drx_plan_max_encoded_words bounds any result.  The call behind a sizing call starts anew (no resume), so a caller that has a
+ * bound does better to pass a buffer of that size.
+ *   Asynchronous on the context's stream like drx_decode; the call clears the plan's status word first, errors found on the
+ * device arrive at drx_plan_finish.  Validation is drx_wave_stats's: the header chain of every chunk is walked and judged, and a
+ * payload that ends before its samples do, or whose codes do not end in its last payload word, is DRX_ERR_CORRUPT; then no word
+ * of d_out is written, the tables are undefined and the plan stays usable.  drx_plan_wave_words / drx_plan_wave_word_off
+ * describe the SOURCE after the call, as after a decode; the result's n_i' and header positions live in scratch of their own that
+ * belongs to the plan (allocated by the first such call).  The plan's RiceParameter does not change.  A pending
+ * drx_gather_encoded sizing call's resume is ended.  drx_plan_last_decode_path reports DRX_PATH_TRANSCODE alone.
+ *   The buffers rule at the top of this file holds: any 4-byte alignment of d_in and d_out, any alignment of their element type
+ * for both tables; nothing is written outside [d_out, d_out + total), the n_chunks + 1 offsets and the total_waves table entries;
+ * no load leaves [0, in_words); the result does not depend on what the outputs held before.  d_out must not overlap d_in (not
+ * checked).
+ *   A lane per waveform for every geometry: few long waveforms go through the same kernels, correct and slow as in
+ * drx_wave_stats (a wavefront or workgroup per long waveform is not built). */
+drx_status drx_transcode(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                         uint32_t new_rice_k, uint32_t *d_out, uint64_t out_cap_words, uint64_t *d_out_chunk_word_off,
+                         uint32_t *d_out_wave_words);
+/* ... with the SOURCE's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, neither
+ * the plan's own table nor d_out_wave_words): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_transcode_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                         const uint32_t *d_wave_words, uint32_t new_rice_k, uint32_t *d_out, uint64_t out_cap_words,
+                                         uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
+/* drx_estimate_words' sixteen numbers from the STREAM: words_out[k] (host array of 16) is the total words drx_transcode would
+ * produce at new_rice_k = k; the plan's filter enters only through the stream.  For a canonical stream the entry at the plan's
+ * own k is the stream's total words.  d_wave_words: the source's side-band, or NULL to walk.  SYNCHRONOUS: it clears the status
+ * word as a decode does, waits, and returns the verdict itself (a stream that fails drx_transcode's validation:
+ * DRX_ERR_CORRUPT, words_out undefined). */
+drx_status drx_estimate_words_encoded(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                      const uint32_t *d_wave_words, uint64_t words_out[16]);
+
 /* RiceParameter optimiser (docs/Optimization.md:5-19 of the reference describes one, the tree does not
  * contain it): exact number of uint32 words drx_encode would emit for this batch with RiceParameter
  * 2^k, for every k = 0..15 (host array of 16), in one pass over the samples.  Synchronous. */
@@ -257,7 +306,7 @@ drx_status drx_estimate_words(drx_plan *plan, const int16_t *d_in, uint64_t word
 
 /* Waits for the plan's last encode/decode, reports device-side errors and (for
  * encode) the number of words produced.  total_words may be NULL.
- *   It reports the plan's LAST encode, decode, select, gather or statistics call only: every such call (a select or gather of no entries
+ *   It reports the plan's LAST encode, decode, select, gather, statistics or transcode call only: every such call (a select or gather of no entries
  * excepted, which launches nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
  * (and the word count) of an earlier call that was never finished is not kept.  drx_estimate_words,
  * drx_plan_read_wave_words and drx_plan_set_filter leave the status word as it is: a finish behind them still reports the
@@ -281,6 +330,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_SELECT 128u    /* drx_decode_select: a wavefront (general filters: a lane) per selected waveform; reported alone */
 #define DRX_PATH_GATHER 256u    /* drx_gather_encoded: word ranges copied, nothing decoded; reported alone */
 #define DRX_PATH_STATS 512u     /* drx_wave_stats: a lane per waveform that parses and reduces; reported alone */
+#define DRX_PATH_TRANSCODE 1024u /* drx_transcode / drx_estimate_words_encoded: a lane per waveform that parses and re-codes; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -315,7 +365,8 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_encode: ms = { size pass, offset scan, pack pass, whole call }
  *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call }
  *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
- *   after drx_wave_stats: ms = { header-chain walk, statistics kernel, 0, whole call } */
+ *   after drx_wave_stats: ms = { header-chain walk, statistics kernel, 0, whole call }
+ *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call } */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 
 /* Tuning / diagnostics.  Returns DRX_ERR_ARG for unknown keys or values.
