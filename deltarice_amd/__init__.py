@@ -7,8 +7,8 @@ chunks over the GPUs of a node; ``optimise`` searches RiceParameter and encoding
 (docs/Optimization.md of the reference).  There is no CPU implementation in this package.
 """
 from ._lib import DeltaRiceError, LIB_PATH, PLUGIN_PATH  # noqa: F401
-from ._lib import (PATH_STATS, PATH_TRANSCODE, STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD_SUMSQ, STAT_MAX,  # noqa: F401
-                   STAT_MIN, STAT_SUM, STAT_SUMSQ)
+from ._lib import (PATH_STATS, PATH_TRANSCODE, PATH_WINDOW, STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD_SUMSQ,  # noqa: F401
+                   STAT_MAX, STAT_MIN, STAT_SUM, STAT_SUMSQ)
 
 H5FILTER = 32025
 

@@ -21,6 +21,7 @@ PATH_SELECT = 128
 PATH_GATHER = 256
 PATH_STATS = 512
 PATH_TRANSCODE = 1024
+PATH_WINDOW = 2048
 # DRX_STAT_*: the columns of a drx_wave_stats row (tests/test_wave_stats_abi.py holds them equal)
 STAT_MIN, STAT_ARGMIN, STAT_MAX, STAT_ARGMAX, STAT_SUM, STAT_SUMSQ, STAT_HEAD_SUM, STAT_HEAD_SUMSQ = range(8)
 STAT_COLS = 8
@@ -90,6 +91,8 @@ SIGNATURES = {
     "drx_gather_encoded_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
     "drx_wave_stats": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp]),
     "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
+    "drx_decode_window": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
+    "drx_decode_window_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_transcode": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),
     "drx_transcode_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
     "drx_estimate_words_encoded": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),

@@ -515,6 +515,70 @@ class Plan:
         self.finish()
         return s
 
+    def decode_window_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start, width: int, offset: int = 0,
+                            pad: int = 0, out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None,
+                            wave_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None) -> torch.Tensor:
+        """Launches drx_decode_window on the context's stream: int16 [total_waves, width], row g = the ``width`` samples of
+        waveform g from sample ``start[g] + offset`` on, ``pad`` where that leaves the waveform.  A payload is read no further
+        than its window's end and the batch is not decoded to memory.  start: None, an int (folded into offset), or a 1-D
+        int64 tensor of total_waves entries on the plan's device with any element stride -- ``stats[:, STAT_ARGMAX]`` is
+        passed as it is.  out: an int16 tensor that holds (total_waves - 1) * out_stride + width samples (out_stride: samples
+        between rows, default width); the samples between rows keep what they held.  wave_words: the encoder's n_i table as
+        decode_with_wave_words takes it (no header walk).  Launch only; finish() raises on device-side errors."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "decode_window: the plan is closed")
+        width, offset, pad = int(width), int(offset), int(pad)
+        if not 0 <= width < 1 << 32:
+            raise DeltaRiceError(1, f"width: {width} is not a uint32")
+        if not -32768 <= pad <= 32767:
+            raise DeltaRiceError(1, f"pad: {pad} is not an int16")
+        sp, ss = None, 0
+        if start is not None and not isinstance(start, torch.Tensor):
+            offset += int(start)
+        elif start is not None:
+            if (start.dim() != 1 or start.device != self.ctx.device or start.dtype != torch.int64 or
+                    start.shape[0] != self.total_waves or (self.total_waves > 1 and start.stride(0) < 1)):
+                raise DeltaRiceError(1, f"start: need a 1-D int64 tensor of {self.total_waves} entries on {self.ctx.device}")
+            sp, ss = start.data_ptr(), (int(start.stride(0)) if self.total_waves > 1 else 1)
+        if not -(1 << 63) <= offset < 1 << 63:
+            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        stride = width if out_stride is None else int(out_stride)
+        if stride < width:
+            raise DeltaRiceError(1, f"out_stride: rows {stride} samples apart do not hold {width}")
+        need = (self.total_waves - 1) * stride + width if self.total_waves else 0
+        if out is None:
+            out = torch.empty((self.total_waves, width) if stride == width else (need,), dtype=torch.int16, device=self.ctx.device)
+        self._dev_check(out, torch.int16, need, "out")
+        n = words.numel() if in_words is None else int(in_words)
+        lib = self.ctx.lib
+        if width == 0 or self.total_waves == 0:
+            return out
+        if wave_words is None:
+            st = lib.drx_decode_window(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), sp, ss, offset, width, pad,
+                                       out.data_ptr(), stride)
+        else:
+            st = lib.drx_decode_window_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), wave_words.data_ptr(),
+                                                       sp, ss, offset, width, pad, out.data_ptr(), stride)
+        self.ctx._check(st)
+        return out
+
+    def decode_window(self, enc: EncodedBatch, start, width: int, offset: int = 0, pad: int = 0,
+                      out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """decode_window_async on an EncodedBatch -> int16 [total_waves, width]; waits, and raises like decode().  The samples
+        around every pulse: ``plan.decode_window(enc, stats[:, STAT_ARGMAX], 256, offset=-64)``."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "decode_window: the plan is closed")
+        cur = torch.cuda.current_stream(self.ctx.device)
+        self.ctx.stream.wait_stream(cur)
+        y = self.decode_window_async(enc.words, enc.chunk_word_off, start, width, offset, pad, out, None, wave_words,
+                                     in_words=enc.total_words)
+        self.finish()
+        return y
+
     def estimate_words_encoded(self, enc: EncodedBatch, wave_words: Optional[torch.Tensor] = None) -> np.ndarray:
         """estimate_words from the encoded stream: entry k is the total words transcode() gives at RiceParameter 2^k, k = 0..15;
         nothing is decoded to memory.  wave_words: the source's n_i table (no header walk).  Waits; raises DRX_ERR_CORRUPT for a
@@ -600,7 +664,7 @@ class Plan:
 
     def last_timings(self):
         """Kernel times (ms) of the last call, HIP events on the context's stream; needs
-        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode and wave_stats: (walk, kernel, 0, total);
+        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode, wave_stats and decode_window: (walk, kernel, 0, total);
         transcode: (walk, sizes + scan + offsets, pack, total)."""
         ms = (C.c_float * 4)()
         self.ctx._check(self.ctx.lib.drx_plan_last_timings(self._h, ms))

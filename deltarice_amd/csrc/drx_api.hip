@@ -1079,6 +1079,51 @@ drx_status drx_wave_stats_with_wave_words(drx_plan *p, const uint32_t *d_in, uin
 }
 
 // ---------------------------------------------------------------------------
+// a window of every waveform, at per-waveform offsets (drx_window.hip)
+// ---------------------------------------------------------------------------
+static drx_status decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                const uint32_t *d_sideband, bool sideband, const int64_t *d_start, uint64_t start_stride,
+                                int64_t offset, uint32_t width, int16_t pad, int16_t *d_out, uint64_t out_stride) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (!d_in || !d_chunk_word_off || !d_out || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "decode_window: null pointer");
+    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    if (out_stride < width)
+        return fail(ctx, DRX_ERR_ARG, "decode_window: rows %llu samples apart do not hold %u", (unsigned long long)out_stride, width);
+    if (d_start && start_stride == 0) return fail(ctx, DRX_ERR_ARG, "decode_window: start_stride 0");
+    if (width == 0) return DRX_OK;  // (no row receives a sample: nothing to launch)
+    DRX_ON_DEVICE(ctx);
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
+        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
+                                            p->d_status, ctx->stream));
+    DRX_HIP(ctx, launch_decode_window(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, d_start,
+                                      start_stride, offset, width, pad, p->d_status, d_out, out_stride, ctx->profile ? p->ev : nullptr,
+                                      ctx->stream));
+    p->last_path = DRX_PATH_WINDOW;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+drx_status drx_decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
+                             int16_t *d_out, uint64_t out_stride_samples) {
+    return decode_window(p, d_in, in_words, d_chunk_word_off, nullptr, false, d_start, start_stride, offset, width, pad, d_out,
+                         out_stride_samples);
+}
+
+drx_status drx_decode_window_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                             const uint32_t *d_wave_words, const int64_t *d_start, uint64_t start_stride,
+                                             int64_t offset, uint32_t width, int16_t pad, int16_t *d_out,
+                                             uint64_t out_stride_samples) {
+    return decode_window(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_start, start_stride, offset, width, pad, d_out,
+                         out_stride_samples);
+}
+
+// ---------------------------------------------------------------------------
 // re-coding to another RiceParameter, and the sizes at every one, from the encoded stream (drx_transcode.hip)
 // ---------------------------------------------------------------------------
 struct TrcScratch {

@@ -165,6 +165,13 @@ hipError_t launch_gather(const Geom &G, const uint32_t *d_in, const uint64_t *d_
 hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                              uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t head_len,
                              DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s);
+// drx_decode_window (drx_window.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
+// far as its window's end and writes `width` samples from start[g * start_stride] + offset on (pad outside the waveform) to row
+// g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}
+hipError_t launch_decode_window(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw,
+                                const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
+                                DevStatus *d_status, int16_t *d_out, uint64_t out_stride, hipEvent_t *ev, hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 // k_chunk_scan + k_chunk_offsets (drx_encode_kernels.hip) over a table of n_i that is not an encode's: header positions relative
 // to the chunk, chunk offsets, DevStatus::total_words and kErrCapacity against out_cap

@@ -250,6 +250,44 @@ drx_status drx_wave_stats_with_wave_words(drx_plan *plan, const uint32_t *d_in, 
                                           const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, uint32_t head_len,
                                           int64_t *d_out);
 
+/* A WINDOW of every waveform, at per-waveform offsets, straight from the encoded stream: the samples around a pulse that
+ * drx_wave_stats found, or the first few hundred samples of each waveform, without decoding the batch to memory and -- unlike
+ * every other stream call -- without reading a payload beyond its window.
+ *   The window.  Waveform g (a global waveform index in the order of drx_plan_wave_words) has a window that starts at sample
+ * a_g = (d_start ? d_start[g * start_stride] : 0) + offset; the sum saturates.  d_start: int64 on the device, any 8-byte
+ * alignment; start_stride counts int64 elements, so a column of drx_wave_stats' [total_waves][8] output is passed as it is,
+ * with stride 8: no host round trip lies between the statistics and the windows.
+ *   The output row.  Row g is d_out + g * out_stride_samples and receives exactly `width` samples: y[a_g + j] where
+ * 0 <= a_g + j < len_g (the int16 drx_decode would write there), and `pad` elsewhere.  A window entirely outside the waveform is
+ * a row of pad; the short last waveform of a chunk is a row like any other; the samples between rows keep what they held.
+ *   Asynchronous on the context's stream like drx_decode; the call clears the plan's status word first and ends a pending
+ * drx_gather_encoded sizing call's resume; errors found on the device arrive at drx_plan_finish.  drx_plan_last_decode_path
+ * reports DRX_PATH_WINDOW alone, drx_plan_last_timings { header-chain walk, window kernel, 0, whole call }.
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: a NULL pointer among d_in, d_chunk_word_off, d_out; a NULL
+ * side-band in the second form, or the plan's own table passed as the side-band; out_stride_samples < width; start_stride == 0
+ * with d_start != NULL.  width == 0 returns DRX_OK with nothing launched.
+ *   Validation and trust.  The header chain of every chunk is walked and judged as drx_decode does (the second form checks the
+ * table against the stream instead).  A lane parses no further than the last code of its window: neither the result nor the
+ * verdict depends on payload bits behind it.  A lane whose window reaches its waveform's last sample makes drx_wave_stats'
+ * end-of-payload check; a payload that runs out of words before the window's codes do is DRX_ERR_CORRUPT.  After a corrupt
+ * verdict the rows are undefined and the plan stays usable.
+ *   The buffers rule at the top of this file holds: any 4-byte alignment of d_in, any 2-byte alignment of d_out and any stride
+ * >= width; no load leaves [0, in_words); nothing is written outside the total_waves rows of width samples; row addressing is
+ * 64-bit (g * out_stride_samples may exceed 2^32 bytes).
+ *   Every prediction filter the plan accepts: the delta filter a lane per waveform that parses as the lane decoder does and
+ * writes its own row; any other filter a lane per waveform in a serial kernel that stops at the window's end, correct but not
+ * fast.  Few long waveforms go through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow: a
+ * wavefront or workgroup per long waveform is not built). */
+drx_status drx_decode_window(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
+                             int16_t *d_out, uint64_t out_stride_samples);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
+ * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_decode_window_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                             const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, const int64_t *d_start,
+                                             uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad, int16_t *d_out,
+                                             uint64_t out_stride_samples);
+
 /* RE-CODE an encoded batch to another RiceParameter, without decoding it.  Under a fixed prediction filter the codes of one
  * sample at any two RiceParameters carry the same zig-zag value (src/deltaRice.c:207-228), so the stream is parsed, sized, scanned
  * and packed on residuals: no filter arithmetic, no sample in memory, and every prediction filter the plan accepts -- more than
@@ -306,8 +344,8 @@ drx_status drx_estimate_words(drx_plan *plan, const int16_t *d_in, uint64_t word
 
 /* Waits for the plan's last encode/decode, reports device-side errors and (for
  * encode) the number of words produced.  total_words may be NULL.
- *   It reports the plan's LAST encode, decode, select, gather, statistics or transcode call only: every such call (a select or gather of no entries
- * excepted, which launches nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
+ *   It reports the plan's LAST encode, decode, select, gather, statistics, transcode or window call only: every such call (a select or gather of no entries
+ * and a window of no width excepted, which launch nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
  * (and the word count) of an earlier call that was never finished is not kept.  drx_estimate_words,
  * drx_plan_read_wave_words and drx_plan_set_filter leave the status word as it is: a finish behind them still reports the
  * encode or decode before them.  A caller
@@ -331,6 +369,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_GATHER 256u    /* drx_gather_encoded: word ranges copied, nothing decoded; reported alone */
 #define DRX_PATH_STATS 512u     /* drx_wave_stats: a lane per waveform that parses and reduces; reported alone */
 #define DRX_PATH_TRANSCODE 1024u /* drx_transcode / drx_estimate_words_encoded: a lane per waveform that parses and re-codes; reported alone */
+#define DRX_PATH_WINDOW 2048u   /* drx_decode_window: a lane per waveform that parses to its window's end; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -366,7 +405,8 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call }
  *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
  *   after drx_wave_stats: ms = { header-chain walk, statistics kernel, 0, whole call }
- *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call } */
+ *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
+ *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call } */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 
 /* Tuning / diagnostics.  Returns DRX_ERR_ARG for unknown keys or values.
