@@ -41,6 +41,10 @@ DBG_FORCE_STREAM_SEGS = 4194304
 DBG_WALK_BY_SCAN = 8388608
 DBG_WALK_BY_CHAINS = 16777216
 DBG_GATHER_OTHER_COPY = 33554432
+DBG_STATS_LANES = 67108864
+DBG_STATS_ALL_FALLBACK = 134217728
+# DRX_STATS_FORM_*: drx_plan_last_stats_form (tests/test_wave_stats_blocks_abi.py holds them equal)
+STATS_FORM_LANES, STATS_FORM_BLOCKS, STATS_FORM_FALLBACK_ALL = 1, 2, 4
 
 
 class DrxOpts(C.Structure):
@@ -81,6 +85,7 @@ SIGNATURES = {
     "drx_plan_wave_word_off": (_vp, [_vp]),
     "drx_plan_last_decode_path": (C.c_uint32, [_vp]),
     "drx_plan_last_encode_path": (C.c_uint32, [_vp]),
+    "drx_plan_last_stats_form": (C.c_uint32, [_vp]),
     "drx_plan_read_wave_words": (C.c_int, [_vp, C.POINTER(_u32)]),
     "drx_encode": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "drx_decode": (C.c_int, [_vp, _vp, _u64, _vp, _vp]),

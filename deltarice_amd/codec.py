@@ -674,6 +674,11 @@ class Plan:
         """DRX_PATH_* bits (include/deltarice_hip.h) of the decoders the last decode used."""
         return int(self.ctx.lib.drx_plan_last_decode_path(self._h))
 
+    def last_stats_form(self) -> int:
+        """DRX_STATS_FORM_* (include/deltarice_hip.h): which form the last wave_stats took -- a lane per waveform, or a workgroup
+        per block of a waveform's stream (few long waveforms); 0 before the plan's first statistics call."""
+        return int(self.ctx.lib.drx_plan_last_stats_form(self._h))
+
     def last_encode_path(self) -> int:
         """DRX_ENC_* (include/deltarice_hip.h): the encoder the last encode used."""
         return int(self.ctx.lib.drx_plan_last_encode_path(self._h))

@@ -120,6 +120,8 @@ struct drx_plan {
     uint64_t pc_wgs = 0;                  // its workgroups (0: the plan's geometry never takes it)
     void *d_pw = nullptr;              // a handful of chunks: candidate lists of the parallel header walk
     void *d_blk = nullptr;             // few waveforms: unit table, look-back state and flags of the block-parallel decoder
+    void *d_sacc = nullptr;            // ... and drx_wave_stats' block form: accumulators and list, allocated by its first call
+    uint32_t last_stats_form = 0;      // DRX_STATS_FORM_* of the last drx_wave_stats (0: none yet)
     DevStatus *d_status = nullptr;
     DevStatus *h_status = nullptr;  // pinned
     bool last_was_encode = false;
@@ -625,6 +627,7 @@ const uint32_t *drx_plan_wave_words(const drx_plan *p) { return p ? p->d_wave_wo
 const uint64_t *drx_plan_wave_word_off(const drx_plan *p) { return p ? p->d_wave_off : nullptr; }
 uint32_t drx_plan_last_decode_path(const drx_plan *p) { return p ? p->last_path : 0u; }
 uint32_t drx_plan_last_encode_path(const drx_plan *p) { return p ? p->last_enc_path : 0u; }
+uint32_t drx_plan_last_stats_form(const drx_plan *p) { return p ? p->last_stats_form : 0u; }
 
 drx_status drx_plan_read_wave_words(drx_plan *p, uint32_t *host_out) {
     if (!p || !host_out) return DRX_ERR_ARG;
@@ -1057,11 +1060,13 @@ static drx_status wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_word
     p->gat_last.valid = false;
     DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
     p->G.dbg = ctx->debug_flags;
+    // the block form's accumulators and list belong to the plan: allocated by its first call that takes that form
+    if (!p->d_sacc && stats_blocks_batch(p->G, p->d_blk)) DRX_HIP(ctx, p->mem.alloc(&p->d_sacc, stats_blocks_scratch_bytes(p->G)));
     if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
         DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
                                             p->d_status, ctx->stream));
-    DRX_HIP(ctx, launch_wave_stats(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, head_len,
-                                   p->d_status, d_out, ctx->profile ? p->ev : nullptr, ctx->stream));
+    DRX_HIP(ctx, launch_wave_stats(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, p->d_blk,
+                                   p->d_sacc, head_len, p->d_status, d_out, ctx->profile ? p->ev : nullptr, ctx->stream, &p->last_stats_form));
     p->last_path = DRX_PATH_STATS;
     p->ev_valid = ctx->profile != 0;
     p->last_was_encode = false;

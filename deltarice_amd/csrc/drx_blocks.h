@@ -1,0 +1,240 @@
+// drx_blocks.h -- the block-parallel parse shared by the kernels that give a WORKGROUP a block of a waveform's stream
+// (not installed): the block geometry, the parse, and (drx_blocks_body.inc) the body of k_decode_blocks (drx_blocks.hip: the samples,
+// in output order, to HBM) and of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics).
+// drx_blocks.hip's head comment describes the scheme.  A kernel that takes this route for another purpose adds its own
+// phase 2 behind the same phase 1, look-back and flags, as the STATS form does.
+#ifndef DRX_BLOCKS_H
+#define DRX_BLOCKS_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+#include "drx_device.h"
+#include "drx_internal.h"
+#include "drx_iir_math.h"
+
+namespace drx {
+
+// Words per lane (odd: the lanes' windows fall on different banks) and the samples a lane can leave in its share of the
+// staging buffer.  A block is a fixed number of BITS and costs about the same whatever it holds, so one geometry for all
+// data loses both ways: with 352 bits per lane noisy data (12.75 bits per sample: 27 samples per lane) decoded at 0.18
+// instead of 0.25 of the roofline, and quiet data under the reference's default RiceParameter (4 bits per sample: 88
+// samples per lane, more than the 76 its share holds, so EVERY block took the second parse) at 0.16.  The class is chosen
+// per decode from what the caller states about the stream -- 32 in_words / total_samples bits per sample, so a
+// RiceParameter that does not suit the data is covered too -- for ~50 samples per lane with 15 % to spare, and every class
+// takes 48-50 dwords of LDS per lane:
+//   words per lane        9      11      15      19
+//   samples staged       76      76      68      60
+//   bits per sample   < 5.4   < 8.2  < 11.7    above
+// Plan-time estimates (which decoder a batch takes, lanes per block) assume the class that suits the RiceParameter;
+// scratch is sized for the smallest blocks.
+constexpr int kBlkSegWMin = 9;
+__host__ __device__ constexpr int blk_segw_plan(uint32_t k) { return k <= 4u ? 11 : (k <= 7u ? 15 : 19); }
+__host__ __device__ constexpr int blk_segw_bits10(uint64_t b10) { return b10 >= 117u ? 19 : (b10 >= 82u ? 15 : (b10 >= 54u ? 11 : 9)); }
+__host__ __device__ constexpr uint32_t blk_lane_cap(int segw) { return segw <= 11 ? 76u : (segw == 15 ? 68u : 60u); }
+constexpr uint32_t kBlkPre = 8;          // words kept in front of a block: lane 0's run-up
+constexpr uint32_t kBlkGuessBits = 128;  // run-up in front of a segment (a parse is in step after a few codes; 96, 128,
+                                         // 160 and 224 bits measured: within 4 % of one another, profiles/r02_notes.md)
+constexpr uint32_t kBlkRounds = 8;       // tickets per resident workgroup a launch should at least have (see run_len)
+constexpr uint32_t kBlkTail = 4;         // words behind a block: a code that starts inside may end 24 bits behind it,
+                                         // and a window reads three words
+
+template <int NT, int SW>
+struct BlkGeom {
+    static constexpr int kSegW = SW;
+    static constexpr uint32_t kLaneCap = blk_lane_cap(SW);                  // samples a lane can stage
+    static constexpr uint32_t kLaneStride = kLaneCap / 2u + 1u;             // dwords per lane: the samples + a dump slot (odd: no bank conflicts)
+    static constexpr uint32_t kWords = NT * SW;                             // payload words per block
+    static constexpr uint32_t kLdsWords = kBlkPre + kWords + kBlkTail + 4;  // + up to 3 words of 16-byte alignment
+    static constexpr uint32_t kOutCap = NT * kLaneCap;                      // samples staged per copy-out
+    static constexpr uint32_t kStageWords = NT * kLaneStride;               // the staging buffer, lane-major or output order
+    static_assert(kLdsWords % 4 == 0, "the image is filled by 16-byte pieces");
+};
+
+__host__ __device__ inline uint32_t blk_words(uint32_t nt, uint32_t k) { return nt * (uint32_t)blk_segw_plan(k); }  // plan-time estimates
+__host__ __device__ inline uint32_t blk_words_min(uint32_t nt) { return nt * (uint32_t)kBlkSegWMin; }               // scratch sizing
+
+// Workgroup barrier for data exchanged through LDS only.  __syncthreads() also fences global memory, i.e. waits for
+// every global load and store the wave has in flight (s_waitcnt vmcnt(0)): the image and the ticket fetched ahead and
+// the output lines being written would all be waited for at the next barrier, which is exactly what fetching ahead is
+// meant to avoid.  Nothing this kernel exchanges between the waves of a workgroup goes through global memory.
+__device__ __forceinline__ void blk_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+enum { kBlkSkip = 0, kBlkCount = 1, kBlkValue = 2 };
+
+// count-leading-zeros that is defined for 0: v_ffbh_u32 returns -1 there, which with the escape's 16 payload bits moves the
+// parse on by 15 + 1 bits -- any progress will do (an all-zero window is the padding behind a waveform or a corrupt stream)
+__device__ __forceinline__ uint32_t clz_nz(uint32_t x) { return ffbh(x); }
+// the 32 bits at Qp of a block's image (see blk_pair)
+__device__ __forceinline__ uint32_t blk_window(const uint32_t *W, uint32_t Qp) {
+    const uint32_t idx = Qp >> 5;
+    return __builtin_amdgcn_alignbit(W[idx + 2u], W[idx + 1u], Qp);
+}
+
+// Two codes from the 64-bit window at Qp (three words: a 64-bit window always holds two codes of at most 25 bits).
+// W: the block's LDS image; word w of the image sits at W[K + 1 - w] and Qp = 32 K - (bit position), so that
+// W[Qp >> 5 .. + 2] are the window's words, last one first, and v_alignbit(hi, lo, Qp) is its first half -- also on a
+// word boundary (as in k_decode_lanes).  nu = minus the code length; v_bfe_u32 / v_alignbit_b32 read 5 bits of their
+// offset / shift, ~t == 31 - t (mod 32) serves both.
+struct BlkPair { uint32_t nu1, nu2, z1, z2; bool pad1, pad2; };
+template <bool VALUES>
+__device__ __forceinline__ BlkPair blk_pair(const uint32_t *W, uint32_t k, uint32_t Qp) {
+    const uint32_t idx = Qp >> 5;
+    const uint32_t lo2 = W[idx], lo = W[idx + 1u], hi = W[idx + 2u];
+    const uint32_t winA = __builtin_amdgcn_alignbit(hi, lo, Qp);
+    const uint32_t winB = __builtin_amdgcn_alignbit(lo, lo2, Qp);
+    const uint32_t q1 = clz_nz(winA);
+    const uint32_t kk1 = (winA < (1u << 24)) ? 16u : k;  // escape: eight zeros (:223-228)
+    BlkPair r;
+    r.nu1 = ~(q1 + kk1);
+    const uint32_t win2 = __builtin_amdgcn_alignbit(winA, winB, r.nu1);
+    const uint32_t q2 = clz_nz(win2);
+    const uint32_t kk2 = (win2 < (1u << 24)) ? 16u : k;
+    r.nu2 = ~(q2 + kk2);
+    r.pad1 = winA < (1u << 23);  // nine zero bits: not a code
+    r.pad2 = win2 < (1u << 23);
+    r.z1 = r.z2 = 0;
+    if (VALUES) {
+        r.z1 = (q1 << kk1) + __builtin_amdgcn_ubfe(winA, r.nu1, kk1);
+        r.z2 = (q2 << kk2) + __builtin_amdgcn_ubfe(win2, r.nu2, kk2);
+    }
+    return r;
+}
+__device__ __forceinline__ uint32_t unzigzag(uint32_t z) { return (z >> 1) ^ (0u - (z & 1u)); }  // :172-177
+
+// The parse.
+//   kBlkSkip / kBlkCount: codes are taken while they START before the limit (Qp > qlim);
+//     kBlkCount also leaves the running sums (:80-89, from 0 at the lane's first code) in `stage`, two per dword,
+//     pair c / 2 at stage[min(c / 2, kBlkLaneCap / 2)] (the last dword is a dump slot), and stops at a window that
+//     opens with nine zero bits: no code does (q < 8: '1' within nine bits, escape: eight zeros then '1',
+//     :215-228), so that is the zero padding behind the waveform's last code, not a sample;
+//   kBlkValue: exactly `cmax` codes (c counts them), each running sum stored as int16 at outp[c].
+// A lane that is not enabled keeps its state.  (A variant that ran a wave without per-code masks while every lane had
+// room for two more codes, and only the last few codes masked, was measured 4-8 % SLOWER: the vote per pair and the
+// second loop cost what the masks had: profiles/r02_notes.md.)
+// RESID: the RESIDUALS themselves are staged / stored instead of their running sums (general prediction filters: the inverse
+// filter runs afterwards, in place, k_iir_tiles).
+// qpad (kBlkCount): a window of nine zero bits is the waveform's padding only where padding can be -- inside its LAST payload
+// word (Qp <= qpad; 0 = that word is not in this block).  Anywhere else it is what a parse that is not yet in step sees inside
+// an escape's payload (z < 128 has nine leading zeros in its sixteen bits); a lane that stopped there reported a wrong END, its
+// successor restarted from that end and stopped there too, and the correction crept through the block one lane per settle
+// round: 256 rounds per block at m = 4 (25 % escapes), NOPTREX 26 ms instead of 2, 25 x 14 M samples 106 ms (round 3).
+// PAD = false: the caller knows that qpad = 0 (every block but a waveform's last), and the padding test is compiled away.
+template <int MODE, bool RESID = false, bool PAD = true>
+__device__ __forceinline__ void blk_parse(const uint32_t *W, uint32_t k, bool enable, uint32_t &Qp, uint32_t qlim,
+                                          uint32_t &c, uint32_t &sum, uint32_t cmax, uint16_t *outp, uint32_t *stage = nullptr,
+                                          uint32_t qpad = 0u, uint32_t cap2 = 0u) {  // cap2: the dump slot = half the lane's share
+    auto more = [&](uint32_t q, uint32_t cc) __attribute__((always_inline)) {
+        return enable && (MODE == kBlkValue ? cc < cmax : (int32_t)(q - qlim) > 0);
+    };
+    // staging slot of the next pair (kBlkCount; c is even whenever a pair is staged): a dword index that saturates at the dump slot
+    uint32_t slot = (c >> 1) < cap2 ? (c >> 1) : cap2;
+    while (__builtin_amdgcn_ballot_w64(more(Qp, c)) != 0ull) {  // (__any() costs a v_cndmask and a v_cmp more)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {  // one vote per four codes
+            const BlkPair p = blk_pair<MODE != kBlkSkip>(W, k, Qp);
+            bool act1 = more(Qp, c);
+            const uint32_t Qa = Qp + p.nu1;
+            bool act2 = act1 && more(Qa, c + 1u);
+            if (MODE == kBlkCount && PAD) {
+                if (act1 && p.pad1 && (int32_t)(Qp - qpad) <= 0) { act1 = act2 = false; qlim = Qp; }  // (Qp stays: where the padding starts)
+                if (act2 && p.pad2 && (int32_t)(Qa - qpad) <= 0) { act2 = false; qlim = Qa; }
+            }
+            if (MODE != kBlkSkip) {
+                const uint32_t s1 = RESID ? unzigzag(p.z1) : sum + unzigzag(p.z1);
+                const uint32_t s2 = RESID ? unzigzag(p.z2) : s1 + unzigzag(p.z2);
+                if (MODE == kBlkValue) {
+                    if (act1) outp[c] = (uint16_t)s1;
+                    if (act2) outp[c + 1u] = (uint16_t)s2;
+                }
+                if (MODE == kBlkCount) {  // c is even here: only a lane's last pair can end after its first code
+                    if (act1) stage[slot] = __builtin_amdgcn_perm(s2, s1, 0x05040100u);
+                    slot = slot + 1u < cap2 ? slot + 1u : cap2;
+                }
+                sum = act2 ? s2 : (act1 ? s1 : sum);
+            }
+            c += (act1 ? 1u : 0u) + (act2 ? 1u : 0u);
+            Qp = act2 ? Qa + p.nu2 : (act1 ? Qa : Qp);
+        }
+    }
+}
+
+// The count parse of a block that does not hold its waveform's last payload word (no padding to recognise): the limit is
+// tested once per PAIR of codes and the pair's work runs under the lane's exec mask; a lane whose last pair's second code
+// started at or behind the limit takes that code back after the loop.  (The general form above tests every code: a
+// quarter more VALU instructions per sample.)  Qp stays far above zero in a block's image (C - bend >= 224 bits), so the
+// limit test is an unsigned compare.
+template <bool RESID>
+__device__ __forceinline__ void blk_count_pairs(const uint32_t *W, uint32_t k, bool enable, uint32_t &Qp, uint32_t qlim,
+                                                uint32_t &c, uint32_t &sum, uint32_t *stage, uint32_t cap2) {
+    uint32_t slot = 0, Qa_l = Qp, s1_l = sum;  // (c = 0 on entry)
+    // A lane that is not enabled gets a limit no position exceeds: the loop's condition is then ONE compare that is the exec
+    // mask.  The loop is ROTATED (test at the bottom): with the test at the top the compiler kept the values used behind the
+    // loop apart from the loop-carried ones and copied five registers there and back per trip (ten v_mov per four codes, a
+    // seventh of the parse's VALU instructions).
+    const uint32_t ql = enable ? qlim : 0xffffffffu;
+    if (__builtin_amdgcn_ballot_w64(Qp > ql) != 0ull) {
+        do {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {  // one vote per four codes
+                if (Qp > ql) {
+                    const BlkPair p = blk_pair<true>(W, k, Qp);
+                    const uint32_t s1 = RESID ? unzigzag(p.z1) : sum + unzigzag(p.z1);
+                    const uint32_t s2 = RESID ? unzigzag(p.z2) : s1 + unzigzag(p.z2);
+                    stage[slot] = __builtin_amdgcn_perm(s2, s1, 0x05040100u);
+                    Qa_l = Qp + p.nu1;
+                    s1_l = s1;
+                    sum = s2;
+                    c += 2u;
+                    Qp = Qa_l + p.nu2;
+                }
+                slot = slot + 1u < cap2 ? slot + 1u : cap2;
+            }
+        } while (__builtin_amdgcn_ballot_w64(Qp > ql) != 0ull);
+    }
+    if (enable && c != 0u && !(Qa_l > qlim)) { c -= 1u; Qp = Qa_l; sum = s1_l; }
+}
+
+// The run-up in the same form: codes are skipped, a pair at a time, while they start in front of the limit.
+__device__ __forceinline__ void blk_skip_pairs(const uint32_t *W, uint32_t k, bool enable, uint32_t &Qp, uint32_t qlim) {
+    uint32_t Qa_l = Qp;
+    const uint32_t ql = enable ? qlim : 0xffffffffu;  // (as in blk_count_pairs: one compare, a rotated loop)
+    if (__builtin_amdgcn_ballot_w64(Qp > ql) != 0ull) {
+        do {
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                if (Qp > ql) {
+                    const BlkPair p = blk_pair<false>(W, k, Qp);
+                    Qa_l = Qp + p.nu1;
+                    Qp = Qa_l + p.nu2;
+                }
+            }
+        } while (__builtin_amdgcn_ballot_w64(Qp > ql) != 0ull);
+    }
+    if (enable && !(Qa_l > qlim)) Qp = Qa_l;  // (no pair taken: Qa_l is Qp)
+}
+
+// The modes of the kernel body (drx_blocks_body.inc), behind RESID (residuals, not their running sums):
+// FUSE (with RESID): the inverse of a general prediction filter (at most four taps, taps[0] = +-1; src/deltaRice.c:91-102) runs
+// INSIDE this kernel, over a block's residuals while they sit in LDS in output order: samples, not residuals, are what reaches
+// HBM, and no second pass (k_iir_tiles: 2 + 2 more bytes of traffic per sample) follows.  The recurrence is linear over
+// Z / 2^16 (drx_iir.hip has the algebra): lane t owns samples [t M, (t + 1) M) of the staging buffer (M = its lane share, so
+// equal run lengths and matrices from a table), pass 1 = zero-state response of every run (lane 0 starts from the state in
+// front of the block instead), a scan over the lanes with A^(M 2^d), pass 2 = the runs again from their true states.  The state
+// behind a block is its last three samples: it stays with thread 0 through a run of blocks, and goes from a run's last block
+// to the next run's first through `xstate` (one 8-byte word per block slot, its own flag).  That hand-over is a serial chain
+// along a waveform, so the host fuses only where runs of ONE waveform are rarely in flight together (as many waveforms as
+// resident workgroups); elsewhere the two-pass form stays.
+// STATS (delta filter only): phase 2 reduces the block's samples instead of writing them out (drx_stats_blocks.hip); `out`,
+// `itab` and `xstate` are not used.
+struct BlkStatsArgs {
+    uint32_t head_len;        // DRX_STAT_HEAD_* cover the samples in front of min(head_len, len)
+    unsigned long long *acc;  // [waveform][6]: min key, max key, sum, sum of squares, head sum, head sum of squares
+};
+
+
+}  // namespace drx
+#endif

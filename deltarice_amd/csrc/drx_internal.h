@@ -162,9 +162,17 @@ hipError_t launch_gather(const Geom &G, const uint32_t *d_in, const uint64_t *d_
                          uint64_t mean_words, bool resume, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
 // drx_wave_stats (drx_stats.hip): behind the whole batch's walk (tables_ready: the side-band's tables are in place), a lane per
 // waveform that parses and reduces: int64 d_out[total_waves][DRX_STAT_COLS].  ev: {start, walk's end, kernel's end, end}
+// Few long waveforms under the delta filter (stats_blocks_batch(): d_blk = the block decoder's scratch, d_sacc = the plan's
+// stats_blocks_scratch_bytes() of accumulators and list) take the block form of drx_stats_blocks.hip instead, with the lane kernel
+// behind it for the waveforms it lists.  form_out: DRX_STATS_FORM_* of include/deltarice_hip.h
 hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t head_len,
-                             DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s);
+                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, void *d_blk, void *d_sacc,
+                             uint32_t head_len, DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s, uint32_t *form_out);
+bool stats_blocks_batch(const Geom &G, const void *d_blk);
+uint64_t stats_blocks_scratch_bytes(const Geom &G);
+hipError_t launch_stats_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
+                               const uint32_t *d_wave_words, void *d_blk, void *d_sacc, uint32_t head_len, DevStatus *d_status,
+                               int64_t *d_out, const uint32_t **listed_out, const uint32_t **n_listed_out, hipStream_t s);
 // drx_decode_window (drx_window.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
 // far as its window's end and writes `width` samples from start[g * start_stride] + offset on (pad outside the waveform) to row
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}
@@ -266,7 +274,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
                          uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl, bool tables_ready,
                          void *d_pw, void *d_blk, const SideStream *side, hipEvent_t *ev, hipStream_t s, uint32_t *path_out = nullptr);
 // block-parallel decoder for batches of few waveforms (drx_blocks.hip): a workgroup per block of a waveform's stream
-bool blocks_batch(const Geom &G);
+bool blocks_batch(const Geom &G, double lane_us = 0.06);
 // ragged plans: decides rag_blocks / rag_blk_nt / rag_blk_slots and the classes from the host's chunk table (call once, when
 // the plan is made); returns rag_blk_list's host copy (empty: the decoder does not take the batch)
 std::vector<uint32_t> blocks_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
@@ -276,6 +284,24 @@ uint64_t blocks_scratch_bytes(const Geom &G);
 hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
                                 const uint32_t *d_wave_words, void *d_blk, DevStatus *d_status, int16_t *d_out,
                                 const uint32_t **fail_out, const uint32_t **suspect_out, bool resid, hipStream_t s, bool *fused_out);
+// ... and for the other kernels of its scheme (drx_blocks.h; k_stats_blocks): the scratch's tables, and what one launch -- a
+// uniform batch, or one length class of a ragged one -- is given.  blocks_prepare() resets the scratch on the stream, chooses
+// the delta filter's geometry as launch_decode_blocks() does and has launched k_blk_max for every entry's info words.
+constexpr uint32_t kBlkMaxClasses = 32;  // ragged batches: one launch per class of WaveformLengths floor(log2 L)
+struct BlkTables {
+    uint32_t *fail, *suspect, *ends;
+    uint64_t *state;
+};
+struct BlkClassLaunch {
+    uint32_t *info;        // {most blocks of a waveform, tickets, the launch's ticket word, -}
+    const uint32_t *list;  // the launch's waveforms (nullptr: all of the batch)
+    uint32_t n_waves;
+    int nt, sw;            // lanes per block, words per lane
+    uint32_t spw, run_len; // look-back slots per waveform, blocks per ticket
+    unsigned grid;         // resident workgroups
+};
+hipError_t blocks_prepare(const Geom &G, uint64_t in_words, const uint32_t *d_wave_words, void *d_blk, hipStream_t s, BlkTables *T,
+                          BlkClassLaunch *launches, uint32_t *n_launches);
 uint32_t blocks_iir_tab_words();
 void blocks_iir_tables(const uint32_t fast_nt[3], uint32_t t0neg, uint32_t *tab);
 // single-pass encoder for short and long waveforms (drx_pieces.hip): a wavefront takes a PIECE, either a run of whole

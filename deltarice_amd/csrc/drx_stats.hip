@@ -14,10 +14,12 @@
 //   k_wave_stats_serial  every other prediction filter: one lane per waveform, the serial loop of k_select_serial
 //                        (drx_select.hip) with the filter's history in an LDS column.  Correct, not tuned.
 //
-// Few long waveforms (the nEDM / NOPTREX shapes: a few thousand waveforms of 10^5 - 10^6 samples) go through the same
-// lane-per-waveform kernels.  That is correct and slow, 50-60 ns per sample and lane whatever else runs, with most of the
-// chip idle (2048 waveforms of 500 000 samples: 26 ms): the open step drx_decode_select documents.  A wavefront or workgroup per long waveform is not built here
-// (DESIGN.md section 4.2f has the measured row).
+// Few long waveforms (the nEDM / NOPTREX shapes, the reference's default one waveform per chunk) under the delta filter do NOT
+// run here: a lane per waveform is 50-60 ns per sample and lane whatever else runs, with most of the chip idle (2048 waveforms of
+// 500 000 samples: 26 ms).  The batches that drx_decode gives to the block decoder take the block form of drx_stats_blocks.hip --
+// a workgroup per block of a waveform's stream -- and this file's launcher runs k_wave_stats_serial behind it over the waveforms
+// that form lists (flagged or suspect ones: computed again and judged here, a lane each).  General filters, and batches under
+// DRX_DBG_STATS_LANES, stay a lane per waveform whatever their shape (DESIGN.md section 4.2f has the measured rows).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -362,14 +364,21 @@ __global__ __launch_bounds__(64) void k_wave_stats(Geom G, const uint32_t *__res
 
 // General prediction filters: a lane per waveform, the loop of k_select_serial (global loads); the last 64 outputs of every
 // lane in an LDS column (taps <= DRX_MAX_TAPS = 64).
+// list != nullptr: the waveforms list[0 .. *n_list) instead of all of them (behind the block form, drx_stats_blocks.hip: the
+// list and its length are written on the device by the kernel in front; the launch is sized for the whole batch).
 __global__ __launch_bounds__(64) void k_wave_stats_serial(Geom G, const uint32_t *__restrict__ in,
                                                           const uint64_t *__restrict__ wave_off,
                                                           const uint32_t *__restrict__ wave_words, uint64_t wf_base,
-                                                          uint32_t head_len, DevStatus *st, int64_t *__restrict__ out) {
+                                                          uint32_t head_len, DevStatus *st, int64_t *__restrict__ out,
+                                                          const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list) {
     __shared__ int16_t hist[64][64];  // [sample mod 64][lane]
     const uint32_t lane = threadIdx.x;
-    const uint64_t g = (wf_base + blockIdx.x) * 64u + lane;
+    uint64_t g = (wf_base + blockIdx.x) * 64u + lane;
     if (st->err) return;  // (as k_wave_stats)
+    if (list) {
+        if (g >= (uint64_t)*n_list) return;
+        g = list[g];
+    }
     if (g >= G.total_waves) return;
     const WaveRef r = locate(G, g);
     const uint32_t *s = in + wave_off[g] + 1;
@@ -427,8 +436,10 @@ __global__ __launch_bounds__(64) void k_wave_stats_serial(Geom G, const uint32_t
 constexpr uint64_t kStatsMaxGrid = 1ull << 25;
 
 hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t head_len,
-                             DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s) {
+                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, void *d_blk, void *d_sacc,
+                             uint32_t head_len, DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s, uint32_t *form_out) {
+    const bool blocks = d_sacc != nullptr && stats_blocks_batch(G, d_blk);
+    if (form_out) *form_out = blocks ? (DRX_STATS_FORM_BLOCKS | ((G.dbg & DRX_DBG_STATS_ALL_FALLBACK) ? DRX_STATS_FORM_FALLBACK_ALL : 0u)) : DRX_STATS_FORM_LANES;
     if (G.total_waves == 0) return hipSuccess;
     mark(ev, 0, s);
     // ---- the walk (drx_walk.hip), all of it on this stream: nothing here is worth a fork
@@ -446,13 +457,24 @@ hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_wo
         if (e != hipSuccess) return e;
     }
     mark(ev, 1, s);
+    // ---- few long waveforms: a workgroup per block of a waveform's stream, then a lane per waveform that form lists (the
+    // launch is sized from here, at most a lane per waveform of the batch; the list's length is read on the device)
+    if (blocks) {
+        const uint32_t *listed = nullptr, *n_listed = nullptr;
+        const hipError_t e = launch_stats_blocks(G, d_in, in_words, d_wave_off, d_wave_words, d_blk, d_sacc, head_len, d_status, d_out, &listed, &n_listed, s);
+        if (e != hipSuccess) return e;
+        k_wave_stats_serial<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, 0, head_len, d_status, d_out, listed, n_listed);
+        mark(ev, 2, s);
+        mark(ev, 3, s);
+        return hipGetLastError();
+    }
     // ---- the kernel: a wavefront per 64 waveforms
     const bool serial = G.n_taps != 0;
     const uint64_t n_wf = (!serial && !G.uniform && G.rag_order) ? (uint64_t)G.rag_groups : (G.total_waves + 63u) / 64u;
     for (uint64_t base = 0; base < n_wf; base += kStatsMaxGrid) {
         const unsigned nb = (unsigned)std::min<uint64_t>(n_wf - base, kStatsMaxGrid);
         if (serial)
-            k_wave_stats_serial<<<nb, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, base, head_len, d_status, d_out);
+            k_wave_stats_serial<<<nb, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, base, head_len, d_status, d_out, nullptr, nullptr);
         else
             k_wave_stats<<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, head_len, d_status, d_out);
     }

@@ -1,0 +1,164 @@
+// drx_stats_blocks.hip -- drx_wave_stats for few long waveforms: a WORKGROUP per block of a waveform's stream.
+//
+// A lane per waveform (k_wave_stats, drx_stats.hip) parses 17 samples per microsecond whatever else runs; 2048 waveforms of
+// 500 000 samples keep 2048 of the chip's 98 304 lane slots busy, and the reference's default options (one waveform per chunk)
+// a few dozen.  The batches that drx_decode gives to the block decoder (blocks_batch(), drx_blocks.hip) take this form instead:
+//
+//   k_stats_blocks         the block decoder's phase 1, look-back and flags, word for word (drx_blocks_body.inc): the block image
+//                          in LDS, the run-up and the count parse, settle() with its creep detection, tickets dealt run-major,
+//                          the predecessor's end one hop back, {status | count | sum} entries for what lies in front of a
+//                          block, fail[] / suspect[], bounded spins that raise kErrInternal.  Phase 2 is replaced: once a lane
+//                          knows the index of its first sample, how many of its codes are samples and the running sum in front
+//                          of them, it reduces its samples -- from the running sums phase 1 staged, or, where some lane holds
+//                          more codes than its share of the staging buffer, from a second parse -- and the block folds the
+//                          result into the waveform's 48-byte accumulator with six 64-bit integer atomics (keys that order by
+//                          value, then by the earliest index; integer atomics give the same answer in any order).  No sample
+//                          is put in output order or stored.
+//   k_stats_blocks_finish  a thread per waveform: the accumulator unpacked into the caller's row, or -- the waveform is flagged
+//                          or suspect -- its index appended to a list on the device.
+// Listed waveforms are computed again, and JUDGED, by k_wave_stats_serial (drx_stats.hip) given that list: a lane per waveform,
+// correct and slow -- a flagged 14 M-sample waveform costs there what it cost before this form existed.  Noise and quiet data
+// are never flagged; a stream whose block had to correct its start after it published its end is.
+// Delta filter only, as the block decoder's phase 1.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "drx_blocks.h"
+
+namespace drx {
+
+template <int NT, int SW>
+__global__ __launch_bounds__(NT) void k_stats_blocks(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                     const uint64_t *__restrict__ wave_off,
+                                                     const uint32_t *__restrict__ wave_words,
+                                                     const uint32_t *__restrict__ info, uint32_t slots_per_wave,
+                                                     uint32_t run_len, uint64_t *__restrict__ state,
+                                                     uint32_t *__restrict__ ends, uint32_t *__restrict__ ticket,
+                                                     uint32_t *__restrict__ fail, uint32_t *__restrict__ suspect,
+                                                     DevStatus *st, uint32_t head_len, unsigned long long *__restrict__ acc,
+                                                     uint32_t n_list, const uint32_t *__restrict__ wave_list) {
+    constexpr bool RESID = false, FUSE = false, STATS = true;
+    // what the decoder's phase 2 and its fused inverse filter take: not used here
+    int16_t *const out = nullptr;
+    const uint32_t *const itab = nullptr;
+    uint64_t *const xstate = nullptr;
+    const BlkStatsArgs sa{head_len, acc};
+    // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
+    if (st->err) return;
+#include "drx_blocks_body.inc"
+}
+
+// the accumulators of a call: nothing seen yet
+__global__ __launch_bounds__(256) void k_stats_blocks_reset(uint64_t total_waves, unsigned long long *__restrict__ acc,
+                                                            uint32_t *__restrict__ n_listed) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (g == 0) *n_listed = 0u;
+    if (g >= total_waves) return;
+    unsigned long long *a = acc + 6u * g;
+    a[0] = (unsigned long long)INT64_MAX;
+    a[1] = (unsigned long long)INT64_MIN;
+    a[2] = a[3] = a[4] = a[5] = 0ull;
+}
+
+// A thread per waveform: its row from its accumulator (the stores of drx_stats.hip's store_row), or its place on the list of
+// the waveforms that the lane kernel behind this one computes and judges.  all_listed: DRX_DBG_STATS_ALL_FALLBACK.
+__global__ __launch_bounds__(256) void k_stats_blocks_finish(uint64_t total_waves, const unsigned long long *__restrict__ acc,
+                                                             const uint32_t *__restrict__ fail, const uint32_t *__restrict__ suspect,
+                                                             uint32_t all_listed, uint32_t *__restrict__ n_listed,
+                                                             uint32_t *__restrict__ listed, const DevStatus *st,
+                                                             int64_t *__restrict__ out) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (st->err) return;  // (as k_stats_blocks)
+    if (g >= total_waves) return;
+    if (all_listed || fail[g] || suspect[g]) {
+        listed[atomicAdd(n_listed, 1u)] = (uint32_t)g;
+        return;
+    }
+    const unsigned long long *a = acc + 6u * g;
+    const uint64_t kmin = a[0], kmax = a[1];
+    const int64_t v[DRX_STAT_COLS] = {(int64_t)(int32_t)(uint32_t)(kmin >> 32), (int64_t)(uint32_t)kmin,
+                                      (int64_t)(int32_t)(uint32_t)(kmax >> 32), (int64_t)(0x7fffffffu - (uint32_t)kmax),
+                                      (int64_t)a[2], (int64_t)a[3], (int64_t)a[4], (int64_t)a[5]};
+    int64_t *row = out + g * (uint64_t)DRX_STAT_COLS;
+    if (((uintptr_t)out & 15u) == 0) {  // a row is 64 bytes: every row of a 16-byte aligned buffer is aligned
+        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+        typedef u32x4v __attribute__((address_space(1))) g_uint4;
+        g_uint4 *dst = (g_uint4 *)row;
+#pragma unroll
+        for (int j = 0; j < DRX_STAT_COLS / 2; ++j)
+            dst[j] = (u32x4v){(uint32_t)v[2 * j], (uint32_t)((uint64_t)v[2 * j] >> 32), (uint32_t)v[2 * j + 1], (uint32_t)((uint64_t)v[2 * j + 1] >> 32)};
+    } else {
+#pragma unroll
+        for (int j = 0; j < DRX_STAT_COLS; ++j) row[j] = v[j];
+    }
+}
+
+// the plan's scratch of this form: u64 acc[W][6] | u32 n_listed (+ pad to 8 bytes) | u32 listed[W]
+struct StatsBlkScratch {
+    unsigned long long *acc;
+    uint32_t *n_listed, *listed;
+    uint64_t bytes;
+};
+static StatsBlkScratch stats_blocks_layout(const Geom &G, void *base) {
+    StatsBlkScratch L;
+    L.acc = reinterpret_cast<unsigned long long *>(base);
+    L.n_listed = reinterpret_cast<uint32_t *>(L.acc + 6u * G.total_waves);
+    L.listed = L.n_listed + 2;
+    L.bytes = 48u * G.total_waves + 8u + 4u * G.total_waves;
+    return L;
+}
+uint64_t stats_blocks_scratch_bytes(const Geom &G) { return stats_blocks_layout(G, nullptr).bytes; }
+
+// The batches of this form: those drx_decode gives to the block decoder, under the delta filter, on a plan that has the block
+// decoder's scratch (d_blk), unless a debug flag keeps the batch on the lane kernels.  The decoder's own test, blocks against
+// lanes by their cost, with the rate of THIS call's lane kernel: k_wave_stats takes 52 ns per sample and lane where
+// k_decode_lanes takes 60, so a uniform batch at the decoder's break-even -- 4 chunks of 2100 x 7000: one
+// block per waveform, 393 us of blocks against 420 us of decoding lanes, but 364 us of reducing lanes -- stays a lane per
+// waveform here.  (A ragged plan's choice was made from the host's chunk table when the plan was created: the decoder's.)
+constexpr double kStatsLaneUs = 0.052;
+bool stats_blocks_batch(const Geom &G, const void *d_blk) {
+    if (G.n_taps != 0 || !d_blk || !blocks_batch(G, kStatsLaneUs)) return false;
+    return !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS | DRX_DBG_STATS_LANES));
+}
+
+// k_stats_blocks per launch of the block scheme, then k_stats_blocks_finish.  The block decoder's scratch is used as the decoder
+// uses it (calls on a plan are ordered on one stream) and reset on the stream first; d_sacc is the plan's scratch of this form.
+// listed_out / n_listed_out: the device list of the waveforms left to the lane kernel, and its length.
+hipError_t launch_stats_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
+                               const uint32_t *d_wave_words, void *d_blk, void *d_sacc, uint32_t head_len, DevStatus *d_status,
+                               int64_t *d_out, const uint32_t **listed_out, const uint32_t **n_listed_out, hipStream_t s) {
+    const StatsBlkScratch A = stats_blocks_layout(G, d_sacc);
+    const unsigned nb = blocks_for(G.total_waves, 256);
+    k_stats_blocks_reset<<<nb, 256, 0, s>>>(G.total_waves, A.acc, A.n_listed);
+    BlkTables T;
+    BlkClassLaunch cls[kBlkMaxClasses];
+    uint32_t n_cls = 0;
+    const hipError_t e = blocks_prepare(G, in_words, d_wave_words, d_blk, s, &T, cls, &n_cls);
+    if (e != hipSuccess) return e;
+    for (uint32_t i = 0; i < n_cls; ++i) {
+        const BlkClassLaunch &c = cls[i];
+        auto go = [&](auto nt_tag, auto sw_tag) {
+            constexpr int NT = decltype(nt_tag)::value, SW = decltype(sw_tag)::value;
+            k_stats_blocks<NT, SW><<<c.grid, NT, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, c.info, c.spw, c.run_len, T.state, T.ends,
+                                                         c.info + 2, T.fail, T.suspect, d_status, head_len, A.acc, c.n_waves, c.list);
+        };
+        auto by_sw = [&](auto nt_tag) {
+            switch (c.sw) {
+                case 9: go(nt_tag, std::integral_constant<int, 9>{}); break;
+                case 11: go(nt_tag, std::integral_constant<int, 11>{}); break;
+                case 15: go(nt_tag, std::integral_constant<int, 15>{}); break;
+                default: go(nt_tag, std::integral_constant<int, 19>{}); break;
+            }
+        };
+        if (c.nt == 64) by_sw(std::integral_constant<int, 64>{});
+        else if (c.nt == 128) by_sw(std::integral_constant<int, 128>{});
+        else by_sw(std::integral_constant<int, 256>{});
+    }
+    k_stats_blocks_finish<<<nb, 256, 0, s>>>(G.total_waves, A.acc, T.fail, T.suspect, (G.dbg & DRX_DBG_STATS_ALL_FALLBACK) ? 1u : 0u, A.n_listed,
+                                             A.listed, d_status, d_out);
+    *listed_out = A.listed;
+    *n_listed_out = A.n_listed;
+    return hipGetLastError();
+}
+
+}  // namespace drx

@@ -230,9 +230,16 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *plan, const uint32_t *d_
  * 8 * total_waves int64 are written; the result depends neither on what they held before nor on words outside [0, in_words),
  * and no load leaves [0, in_words).
  *   Every prediction filter the plan accepts: the delta filter a lane per waveform that parses as the lane decoder does and
- * reduces in registers; any other filter a lane per waveform in a serial kernel, correct but not fast.  Few long waveforms go
- * through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow: a wavefront or workgroup per long
- * waveform is not built).  drx_plan_last_decode_path reports DRX_PATH_STATS alone. */
+ * reduces in registers; any other filter a lane per waveform in a serial kernel, correct but not fast.  Few long waveforms
+ * under the delta filter -- the batches drx_decode gives to its block decoder (DRX_PATH_BLOCKS), on a plan created with that
+ * geometry -- take a WORKGROUP per block of a waveform's stream instead: the block decoder's parse, the samples reduced where
+ * the decoder would put them in order and write them out, a block's result folded into its waveform's by integer atomics.  A
+ * waveform whose block had to correct its start after publishing its end, or whose count or last code does not fit its
+ * payload, is computed again and judged by the serial lane kernel: correct and slow, a flagged waveform of 14 M samples costs
+ * there what the whole call cost before (50-60 ns per sample); noise and quiet data are never flagged.  Under a general filter
+ * few long waveforms stay a lane per waveform.  DRX_DBG_STATS_LANES: never the block form; DRX_DBG_STATS_ALL_FALLBACK: the
+ * block form lists every waveform for the lane kernel behind it (tests).  drx_plan_last_decode_path reports DRX_PATH_STATS
+ * alone whichever form ran; drx_plan_last_stats_form says which. */
 #define DRX_STAT_MIN 0        /* smallest sample                                   */
 #define DRX_STAT_ARGMIN 1     /* smallest i with y[i] == MIN                        */
 #define DRX_STAT_MAX 2
@@ -249,6 +256,12 @@ drx_status drx_wave_stats(drx_plan *plan, const uint32_t *d_in, uint64_t in_word
 drx_status drx_wave_stats_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
                                           const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, uint32_t head_len,
                                           int64_t *d_out);
+
+/* Which form the plan's last drx_wave_stats took (0 before its first statistics call) */
+#define DRX_STATS_FORM_LANES 1u        /* a lane per waveform */
+#define DRX_STATS_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream, the lane kernel behind it for listed waveforms */
+#define DRX_STATS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_STATS_ALL_FALLBACK was in force */
+uint32_t drx_plan_last_stats_form(const drx_plan *plan);
 
 /* A WINDOW of every waveform, at per-waveform offsets, straight from the encoded stream: the samples around a pulse that
  * drx_wave_stats found, or the first few hundred samples of each waveform, without decoding the batch to memory and -- unlike
@@ -404,7 +417,7 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_encode: ms = { size pass, offset scan, pack pass, whole call }
  *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call }
  *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
- *   after drx_wave_stats: ms = { header-chain walk, statistics kernel, 0, whole call }
+ *   after drx_wave_stats: ms = { header-chain walk, statistics kernels (block form: blocks + finish + fallback), 0, whole call }
  *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
  *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call } */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
@@ -437,6 +450,8 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 #define DRX_DBG_WALK_BY_SCAN 8388608u           /* the chunk-wide header walk by reading the whole chunk instead of chasing 64 chains */
 #define DRX_DBG_WALK_BY_CHAINS 16777216u        /* the chunk-wide header walk by chains also where the scan form is the default */
 #define DRX_DBG_GATHER_OTHER_COPY 33554432u      /* drx_gather_encoded: the copy form the batch's code length does NOT choose (a workgroup per run of entries <-> a wavefront per entry) */
+#define DRX_DBG_STATS_LANES 67108864u           /* drx_wave_stats: never the block form (a lane per waveform whatever the batch) */
+#define DRX_DBG_STATS_ALL_FALLBACK 134217728u   /* drx_wave_stats, block form: every waveform is listed for the lane kernel behind the blocks */
 drx_status drx_ctx_set_option(drx_ctx *ctx, const char *key, int64_t value);
 
 #ifdef __cplusplus

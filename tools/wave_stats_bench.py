@@ -9,13 +9,21 @@ samples), and `plan.decode` + the reductions (in slabs of chunks, so that the sq
   headline-loud   the same with sigma = 400
   short           300 chunks of 8192 x 512
   config5         BASELINE's mixed-length config 5 (ragged: 512 / 2048 / 7000 / 16384)
-  noptrex         2048 waveforms of 500 000 samples (few long waveforms: a lane each, reported, not gated)
+  noptrex         2048 waveforms of 500 000 samples (few long waveforms: a workgroup per block of a waveform's stream)
   headline-sb     the headline with the encoder's side-band (no header walk)
+  nedm            256 chunks of 32 x 81 920 (the block form)
+  long25          25 chunks of ONE 14 M-sample waveform, the reference's default options (the block form; --decode-yardstick only:
+                  the torch reductions take chunks of whole waveforms of one length)
+  stream-quiet    4 chunks of 2100 x 7000: the batch at the decoder's break-even between blocks and lanes, a lane per waveform here
 
 Peak bytes: torch's peak allocation during one call that allocates its own results (the decoded batch and the reductions'
 temporaries, or the [W, 8] rows), above what the encoded batch occupies.
 
 usage: wave_stats_bench.py [--chunks 500] [--calls 20] [--warmup 5] [--head 500] [--only NAME[,NAME]] [--no-yardstick]
+                           [--decode-yardstick]
+--decode-yardstick: `plan.decode` alone, alternating with the stats call, and the stats call's ratio to it (the long shapes:
+profiles/wave_stats_blocks_bench.txt compares two builds of the library this way, in fresh processes that alternate).
+Every line names the form the call took (drx_plan_last_stats_form) where the library reports it.
 A line is "ok" when the stats call takes less time than `plan.decode` alone by more than that decode's min-to-max spread over
 the alternating runs.  Behind `rocprofv3 --kernel-trace --stats --` (no counters), `--only headline --no-yardstick` gives
 k_wave_stats' own time; behind `rocprofv3 --pmc ... --` (a run of its own) its memory traffic."""
@@ -44,11 +52,11 @@ def samples(ctx, total, sigma, seed=5):
 
 
 class Case:
-    def __init__(self, ctx, Ns, Ls, sigma, head, m=8):
+    def __init__(self, ctx, Ns, Ls, sigma, head, m=8, reduces=True):
         self.ctx, self.Ns, self.Ls, self.head = ctx, Ns, Ls, head
         x = samples(ctx, sum(Ns), sigma)
         uniform = len(set(Ns)) == 1 and len(set(Ls)) == 1
-        self.plan = ctx.plan_uniform(len(Ns), Ns[0], (m, Ls[0])) if uniform else ctx.plan(Ns, Ls, m)
+        self.plan = ctx.plan_uniform(len(Ns), Ns[0], (m, Ls[0]) if Ls[0] else (m,)) if uniform else ctx.plan(Ns, Ls, m)
         torch.cuda.synchronize()
         self.enc = self.plan.encode(x)
         self.table = self.plan.wave_words_device()
@@ -59,10 +67,12 @@ class Case:
         self.slabs, at, c = [], 0, 0
         while c < len(Ns):
             c1, n = c, 0
-            while c1 < len(Ns) and Ls[c1] == Ls[c] and Ns[c1] % Ls[c] == 0 and (n == 0 or n + Ns[c1] <= 1 << 28):
+            while c1 < len(Ns) and Ls[c] > 0 and Ls[c1] == Ls[c] and Ns[c1] % Ls[c] == 0 and (n == 0 or n + Ns[c1] <= 1 << 28):
                 n += Ns[c1]
                 c1 += 1
             if c1 == c:
+                if not reduces:
+                    break
                 raise SystemExit("the yardstick takes chunks of whole waveforms only")
             self.slabs.append((at, n, Ls[c]))
             at, c = at + n, c1
@@ -108,9 +118,23 @@ class Case:
         del r
         return torch.cuda.max_memory_allocated() - base
 
-    def line(self, label, calls, warmup, sideband=False, yardstick=True):
+    def line(self, label, calls, warmup, sideband=False, yardstick=True, decode_only=False):
         td, tr, ts = [], [], []
         match = True
+        if decode_only:  # plan.decode and plan.wave_stats alternating, nothing else
+            for i in range(warmup + calls):
+                td.append(self.timed(self.decode)[0])
+                ts.append(self.timed(lambda: self.stats(sideband))[0])
+            td, ts = np.array(td[warmup:]), np.array(ts[warmup:])
+            form = {0: "?", 1: "lanes", 2: "blocks"}.get(getattr(self.plan, "last_stats_form", lambda: 0)() & 3, "?")
+            self.ctx.set_option("profile", 1)
+            self.timed(lambda: self.stats(sideband))
+            walk, kern = self.plan.last_timings()[:2]
+            self.ctx.set_option("profile", 0)
+            print(f"{label:14s} {self.plan.total_waves:8d} waveforms {self.plan.total_samples / 1e9:6.2f} GS stream {self.enc.total_words * 4 / 1e9:5.2f} GB  "
+                  f"decode {np.median(td):8.3f} [{td.min():.3f} .. {td.max():.3f}]  stats({form}) {np.median(ts):8.3f} [{ts.min():.3f} .. {ts.max():.3f}] "
+                  f"(walk {walk:.3f} kernels {kern:.3f})  x{np.median(ts) / np.median(td):.2f} of decode", flush=True)
+            return
         for i in range(warmup + calls):
             if yardstick:
                 td.append(self.timed(self.decode)[0])
@@ -152,6 +176,7 @@ def main():
     ap.add_argument("--head", type=int, default=500)
     ap.add_argument("--only", default="")
     ap.add_argument("--no-yardstick", action="store_true")
+    ap.add_argument("--decode-yardstick", action="store_true")
     a = ap.parse_args()
     ctx = dr.Context(0)
     only = [s for s in a.only.split(",") if s]
@@ -163,13 +188,19 @@ def main():
         ("config5", lambda: geometry("config5"), 10.0, False),
         ("noptrex", lambda: geometry("noptrex"), 10.0, False),
         ("headline-sb", lambda: ([2000 * 7000] * a.chunks, [7000] * a.chunks), 10.0, True),
+        ("nedm", lambda: geometry("nedm"), 10.0, False),
+        ("long25", lambda: geometry("long25"), 10.0, False),
+        ("stream-quiet", lambda: ([2100 * 7000] * 4, [7000] * 4), 10.0, False),
     ]
     for name, geom, sigma, sideband in cases:
         if only and name not in only:
             continue
         Ns, Ls = geom()
-        c = Case(ctx, list(Ns), list(Ls), sigma, a.head)
-        c.line(name, a.calls, a.warmup, sideband, not a.no_yardstick)
+        if name == "long25" and not (a.decode_yardstick or a.no_yardstick):
+            print("long25         skipped: --decode-yardstick or --no-yardstick only", flush=True)
+            continue
+        c = Case(ctx, list(Ns), list(Ls), sigma, a.head, reduces=not (a.decode_yardstick or a.no_yardstick))
+        c.line(name, a.calls, a.warmup, sideband, not a.no_yardstick, a.decode_yardstick)
         c.plan.close()
         del c
         torch.cuda.empty_cache()
