@@ -22,9 +22,13 @@ PATH_GATHER = 256
 PATH_STATS = 512
 PATH_TRANSCODE = 1024
 PATH_WINDOW = 2048
+PATH_PULSES = 4096
 # DRX_STAT_*: the columns of a drx_wave_stats row (tests/test_wave_stats_abi.py holds them equal)
 STAT_MIN, STAT_ARGMIN, STAT_MAX, STAT_ARGMAX, STAT_SUM, STAT_SUMSQ, STAT_HEAD_SUM, STAT_HEAD_SUMSQ = range(8)
 STAT_COLS = 8
+# DRX_PULSE_*: the columns of a drx_find_pulses record (tests/test_find_pulses_abi.py holds them equal)
+PULSE_START, PULSE_WIDTH, PULSE_PEAK, PULSE_ARGPEAK, PULSE_SUM = range(5)
+PULSE_COLS = 5
 ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
 DBG_NO_LONG_PATHS = 256
 DBG_LONG_NOT_BLOCKS = 512
@@ -98,6 +102,8 @@ SIGNATURES = {
     "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "drx_decode_window": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_decode_window_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
+    "drx_find_pulses": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, C.c_int32, _u32, _u32, _vp, _vp]),
+    "drx_find_pulses_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, C.c_int32, _u32, _u32, _vp, _vp]),
     "drx_transcode": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),
     "drx_transcode_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
     "drx_estimate_words_encoded": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),

@@ -579,6 +579,77 @@ class Plan:
         self.finish()
         return y
 
+    def find_pulses_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, threshold, polarity: int = 1,
+                          min_width: int = 1, max_pulses: int = 4, offset: int = 0, count: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None,
+                          in_words: Optional[int] = None):
+        """Launches drx_find_pulses on the context's stream -> (count, pulses): int32 [total_waves], the number of pulses of
+        every waveform (all of them, those beyond max_pulses included), and int64 [total_waves, max_pulses, PULSE_COLS], row g
+        slot p = (start, width, peak, argpeak, sum) of pulse p of waveform g, zero beyond its last pulse.  A pulse is a maximal
+        run of at least ``min_width`` consecutive samples above (polarity > 0) or below (polarity < 0) ``threshold[g] + offset``,
+        strictly, over the int16 samples decode() would give; exact; nothing is decoded to memory.  threshold: an int (folded
+        into offset), or a 1-D int64 tensor of total_waves entries on the plan's device with any positive element stride -- a
+        column of wave_stats() or an expression over it is passed as it is.  max_pulses 0: the counting form, pulses is empty.
+        count / out: an int32 tensor of total_waves and an int64 tensor of total_waves * max_pulses * PULSE_COLS elements to
+        write to.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).  Launch only;
+        finish() raises on device-side errors."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "find_pulses: the plan is closed")
+        polarity, min_width, max_pulses, offset = int(polarity), int(min_width), int(max_pulses), int(offset)
+        if polarity == 0:
+            raise DeltaRiceError(1, "polarity: 0 is neither above nor below")
+        if not 1 <= min_width < 1 << 32:
+            raise DeltaRiceError(1, f"min_width: {min_width} is not in 1 .. 2^32 - 1")
+        if not 0 <= max_pulses < 1 << 32:
+            raise DeltaRiceError(1, f"max_pulses: {max_pulses} is not a uint32")
+        tp, ts = None, 0
+        if not isinstance(threshold, torch.Tensor):
+            offset += int(threshold)
+        else:
+            if (threshold.dim() != 1 or threshold.device != self.ctx.device or threshold.dtype != torch.int64 or
+                    threshold.shape[0] != self.total_waves or (self.total_waves > 1 and threshold.stride(0) < 1)):
+                raise DeltaRiceError(1, f"threshold: need a 1-D int64 tensor of {self.total_waves} entries on {self.ctx.device}")
+            tp, ts = threshold.data_ptr(), (int(threshold.stride(0)) if self.total_waves > 1 else 1)
+        if not -(1 << 63) <= offset < 1 << 63:
+            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        W, need = self.total_waves, self.total_waves * max_pulses * _lib.PULSE_COLS
+        if count is None:
+            count = torch.empty(W, dtype=torch.int32, device=self.ctx.device)
+        self._dev_check(count, torch.int32, W, "count")
+        if out is None:
+            out = torch.empty(need, dtype=torch.int64, device=self.ctx.device)
+        self._dev_check(out, torch.int64, need, "out")
+        n = words.numel() if in_words is None else int(in_words)
+        lib = self.ctx.lib
+        op = out.data_ptr() if need else None
+        pol = 1 if polarity > 0 else -1
+        if wave_words is None:
+            st = lib.drx_find_pulses(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), tp, ts, offset, pol, min_width,
+                                     max_pulses, count.data_ptr(), op)
+        else:
+            st = lib.drx_find_pulses_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), wave_words.data_ptr(),
+                                                     tp, ts, offset, pol, min_width, max_pulses, count.data_ptr(), op)
+        self.ctx._check(st)
+        return count.view(-1)[:W], out.view(-1)[:need].view(W, max_pulses, _lib.PULSE_COLS)
+
+    def find_pulses(self, enc: EncodedBatch, threshold, polarity: int = 1, min_width: int = 1, max_pulses: int = 4,
+                    offset: int = 0, count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    wave_words: Optional[torch.Tensor] = None):
+        """find_pulses_async on an EncodedBatch -> (count, pulses); waits, and raises like decode().  Forty counts above every
+        waveform's own baseline: ``plan.find_pulses(enc, stats[:, STAT_HEAD_SUM] // 500, offset=40)``."""
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, "find_pulses: the plan is closed")
+        cur = torch.cuda.current_stream(self.ctx.device)
+        self.ctx.stream.wait_stream(cur)
+        r = self.find_pulses_async(enc.words, enc.chunk_word_off, threshold, polarity, min_width, max_pulses, offset, count, out,
+                                   wave_words, in_words=enc.total_words)
+        self.finish()
+        return r
+
     def estimate_words_encoded(self, enc: EncodedBatch, wave_words: Optional[torch.Tensor] = None) -> np.ndarray:
         """estimate_words from the encoded stream: entry k is the total words transcode() gives at RiceParameter 2^k, k = 0..15;
         nothing is decoded to memory.  wave_words: the source's n_i table (no header walk).  Waits; raises DRX_ERR_CORRUPT for a
@@ -664,7 +735,7 @@ class Plan:
 
     def last_timings(self):
         """Kernel times (ms) of the last call, HIP events on the context's stream; needs
-        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode, wave_stats and decode_window: (walk, kernel, 0, total);
+        ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode, wave_stats, decode_window and find_pulses: (walk, kernel, 0, total);
         transcode: (walk, sizes + scan + offsets, pack, total)."""
         ms = (C.c_float * 4)()
         self.ctx._check(self.ctx.lib.drx_plan_last_timings(self._h, ms))

@@ -1129,6 +1129,51 @@ drx_status drx_decode_window_with_wave_words(drx_plan *p, const uint32_t *d_in, 
 }
 
 // ---------------------------------------------------------------------------
+// every pulse of every waveform: threshold discrimination (drx_pulses.hip)
+// ---------------------------------------------------------------------------
+static drx_status find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const uint32_t *d_sideband, bool sideband, const int64_t *d_thr, uint64_t thr_stride, int64_t thr,
+                              int32_t polarity, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (!d_in || !d_chunk_word_off || !d_count || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "find_pulses: null pointer");
+    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    if (max_pulses && !d_out) return fail(ctx, DRX_ERR_ARG, "find_pulses: no output for %u pulses per waveform", max_pulses);
+    if (polarity == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: polarity 0");
+    if (min_width == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: min_width 0");
+    if (d_thr && thr_stride == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: thr_stride 0");
+    DRX_ON_DEVICE(ctx);
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
+        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
+                                            p->d_status, ctx->stream));
+    DRX_HIP(ctx, launch_find_pulses(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, d_thr,
+                                    thr_stride, thr, polarity < 0, min_width, max_pulses, p->d_status, d_count, d_out,
+                                    ctx->profile ? p->ev : nullptr, ctx->stream));
+    p->last_path = DRX_PATH_PULSES;
+    p->ev_valid = ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+drx_status drx_find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                           const int64_t *d_thr, uint64_t thr_stride, int64_t thr, int32_t polarity, uint32_t min_width,
+                           uint32_t max_pulses, uint32_t *d_count, int64_t *d_out) {
+    return find_pulses(p, d_in, in_words, d_chunk_word_off, nullptr, false, d_thr, thr_stride, thr, polarity, min_width, max_pulses,
+                       d_count, d_out);
+}
+
+drx_status drx_find_pulses_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                           const uint32_t *d_wave_words, const int64_t *d_thr, uint64_t thr_stride, int64_t thr,
+                                           int32_t polarity, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count,
+                                           int64_t *d_out) {
+    return find_pulses(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_thr, thr_stride, thr, polarity, min_width,
+                       max_pulses, d_count, d_out);
+}
+
+// ---------------------------------------------------------------------------
 // re-coding to another RiceParameter, and the sizes at every one, from the encoded stream (drx_transcode.hip)
 // ---------------------------------------------------------------------------
 struct TrcScratch {

@@ -180,6 +180,15 @@ hipError_t launch_decode_window(const Geom &G, const uint32_t *d_in, uint64_t in
                                 uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw,
                                 const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
                                 DevStatus *d_status, int16_t *d_out, uint64_t out_stride, hipEvent_t *ev, hipStream_t s);
+// drx_find_pulses (drx_pulses.hip): behind the whole batch's walk (tables_ready as above), the output zeroed by one memset, a lane
+// per waveform that parses, compares every sample with thr[g * thr_stride] + thr (d_thr == nullptr: 0; neg: below it, otherwise
+// above it) and writes the records of the first max_pulses runs of at least min_width samples to int64
+// d_out[total_waves][max_pulses][DRX_PULSE_COLS] and the number of all such runs to d_count[total_waves].
+// ev: {start, walk's end, kernel's end, end}
+hipError_t launch_find_pulses(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, const int64_t *d_thr,
+                              uint64_t thr_stride, int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses,
+                              DevStatus *d_status, uint32_t *d_count, int64_t *d_out, hipEvent_t *ev, hipStream_t s);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 // k_chunk_scan + k_chunk_offsets (drx_encode_kernels.hip) over a table of n_i that is not an encode's: header positions relative
 // to the chunk, chunk offsets, DevStatus::total_words and kErrCapacity against out_cap

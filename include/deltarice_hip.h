@@ -301,6 +301,55 @@ drx_status drx_decode_window_with_wave_words(drx_plan *plan, const uint32_t *d_i
                                              uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad, int16_t *d_out,
                                              uint64_t out_stride_samples);
 
+/* EVERY PULSE of every waveform, straight from the encoded stream: threshold discrimination -- time over threshold, the number
+ * of pulses, and the start, width, peak and integral of each -- without decoding the batch to memory.  What drx_wave_stats (one
+ * maximum per waveform) and drx_decode_window (one start per waveform) cannot say of a waveform with two pulses, of a noise
+ * spike beside a wide lower pulse, or of a long trace that holds many events.
+ *   The threshold.  Waveform g (a global waveform index in the order of drx_plan_wave_words) has the samples y[0 .. len_g), the
+ * int16 drx_decode would write, and the threshold t_g = (d_thr ? d_thr[g * thr_stride] : 0) + thr; the sum saturates at the
+ * int64 ends.  d_thr: int64 on the device, any 8-byte alignment; thr_stride counts int64 elements, so a column of
+ * drx_wave_stats' output, or any expression over it, goes in with no host round trip, as drx_decode_window takes its starts.
+ *   A pulse.  Sample i is OVER when polarity > 0 and y[i] > t_g, or polarity < 0 and y[i] < t_g (strictly, both).  A run is a
+ * maximal range [s, e) of consecutive over samples; it may begin at sample 0, and one still open at the waveform's last sample
+ * ends there, e = len_g.  A pulse is a run with e - s >= min_width; pulses are numbered by s.
+ *   The output.  d_count[g] (uint32[total_waves]) receives the number of pulses of waveform g -- all of them, those beyond
+ * max_pulses included, so a row that overflowed shows.  d_out is int64[total_waves][max_pulses][DRX_PULSE_COLS]: slot
+ * p < min(count_g, max_pulses) holds pulse p, every other slot is all zero.  PEAK is the run's maximum for positive polarity and
+ * its minimum for negative, ARGPEAK its first occurrence.  Everything is exact: a waveform has fewer than 2^31 samples, so SUM
+ * fits an int64.  max_pulses == 0 is the counting form: only d_count is written and d_out may be NULL.
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: a NULL pointer among d_in, d_chunk_word_off, d_count;
+ * d_out == NULL with max_pulses > 0; polarity == 0; min_width == 0; thr_stride == 0 with d_thr != NULL; in the second form a NULL
+ * side-band, or the plan's own table passed as the side-band.
+ *   Asynchronous on the context's stream like drx_decode; the call clears the plan's status word first and ends a pending
+ * drx_gather_encoded sizing call's resume; errors found on the device arrive at drx_plan_finish.  drx_plan_last_decode_path
+ * reports DRX_PATH_PULSES alone, drx_plan_last_timings { header-chain walk, pulse kernel, 0, whole call }.
+ *   Validation is drx_wave_stats': the header chain of every chunk is walked and judged (the second form checks the table
+ * against the stream instead), and a payload that ends before its samples do, or whose codes do not end in its last payload
+ * word, is DRX_ERR_CORRUPT; the outputs are then undefined and the plan stays usable.
+ *   The buffers rule at the top of this file holds: any 4-byte alignment of d_in and d_count, any 8-byte alignment of d_thr and
+ * d_out; no load leaves [0, in_words); exactly total_waves counts and total_waves * max_pulses * DRX_PULSE_COLS int64 are
+ * written, and the result does not depend on what they held before; slot addressing is 64-bit.
+ *   Every prediction filter the plan accepts: the delta filter a lane per waveform that parses as drx_wave_stats' lane kernel
+ * does and keeps a small state machine (a group of 16 samples that holds nothing over the threshold costs one packed maximum
+ * and one compare); any other filter a lane per waveform in a serial kernel, correct but not fast.  Few long waveforms go
+ * through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow): a block form like drx_wave_stats'
+ * is not built, since a run spans block borders and the blocks' open runs would have to be stitched. */
+#define DRX_PULSE_START 0   /* first sample of the run, waveform-relative               */
+#define DRX_PULSE_WIDTH 1   /* samples in the run (time over threshold)                  */
+#define DRX_PULSE_PEAK 2    /* the extreme sample of the run in the polarity's direction */
+#define DRX_PULSE_ARGPEAK 3 /* smallest waveform-relative i with y[i] == PEAK            */
+#define DRX_PULSE_SUM 4     /* sum of y[i] over the run                                  */
+#define DRX_PULSE_COLS 5
+drx_status drx_find_pulses(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                           const int64_t *d_thr, uint64_t thr_stride, int64_t thr, int32_t polarity, uint32_t min_width,
+                           uint32_t max_pulses, uint32_t *d_count, int64_t *d_out);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
+ * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_find_pulses_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                           const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, const int64_t *d_thr,
+                                           uint64_t thr_stride, int64_t thr, int32_t polarity, uint32_t min_width,
+                                           uint32_t max_pulses, uint32_t *d_count, int64_t *d_out);
+
 /* RE-CODE an encoded batch to another RiceParameter, without decoding it.  Under a fixed prediction filter the codes of one
  * sample at any two RiceParameters carry the same zig-zag value (src/deltaRice.c:207-228), so the stream is parsed, sized, scanned
  * and packed on residuals: no filter arithmetic, no sample in memory, and every prediction filter the plan accepts -- more than
@@ -357,7 +406,7 @@ drx_status drx_estimate_words(drx_plan *plan, const int16_t *d_in, uint64_t word
 
 /* Waits for the plan's last encode/decode, reports device-side errors and (for
  * encode) the number of words produced.  total_words may be NULL.
- *   It reports the plan's LAST encode, decode, select, gather, statistics, transcode or window call only: every such call (a select or gather of no entries
+ *   It reports the plan's LAST encode, decode, select, gather, statistics, transcode, window or pulse call only: every such call (a select or gather of no entries
  * and a window of no width excepted, which launch nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
  * (and the word count) of an earlier call that was never finished is not kept.  drx_estimate_words,
  * drx_plan_read_wave_words and drx_plan_set_filter leave the status word as it is: a finish behind them still reports the
@@ -383,6 +432,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_STATS 512u     /* drx_wave_stats: a lane per waveform that parses and reduces; reported alone */
 #define DRX_PATH_TRANSCODE 1024u /* drx_transcode / drx_estimate_words_encoded: a lane per waveform that parses and re-codes; reported alone */
 #define DRX_PATH_WINDOW 2048u   /* drx_decode_window: a lane per waveform that parses to its window's end; reported alone */
+#define DRX_PATH_PULSES 4096u   /* drx_find_pulses: a lane per waveform that parses and discriminates; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -419,7 +469,8 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
  *   after drx_wave_stats: ms = { header-chain walk, statistics kernels (block form: blocks + finish + fallback), 0, whole call }
  *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
- *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call } */
+ *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call }
+ *   after drx_find_pulses: ms = { header-chain walk, pulse kernel, 0, whole call } */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 
 /* Tuning / diagnostics.  Returns DRX_ERR_ARG for unknown keys or values.
