@@ -1048,29 +1048,50 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *p, const uint32_t *d_in,
 }
 
 // ---------------------------------------------------------------------------
+// The calls that read the whole batch from the encoded stream without decoding it -- wave_stats, decode_window, find_pulses,
+// transcode, estimate_words_encoded -- share their first and last steps.  stream_call_args(): the pointers every one of them
+// takes (have_pointers: the caller's own included; who: its name in the message).  stream_call_begin(), on the context's device:
+// the plan's status word, debug flags and, for the side-band form, the header tables.  stream_call_end(): what the plan
+// remembers of its last call.
+// ---------------------------------------------------------------------------
+static drx_status stream_call_args(drx_plan *p, const char *who, bool have_pointers, const uint32_t *d_sideband, bool sideband) {
+    if (!have_pointers || (sideband && !d_sideband)) return fail(p->ctx, DRX_ERR_ARG, "%s: null pointer", who);
+    if (sideband && d_sideband == p->d_wave_words) return fail(p->ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    return DRX_OK;
+}
+static drx_status stream_call_begin(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                    const uint32_t *d_sideband, bool sideband) {
+    drx_ctx *ctx = p->ctx;
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
+        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
+                                            p->d_status, ctx->stream));
+    return DRX_OK;
+}
+static drx_status stream_call_end(drx_plan *p, uint32_t path) {
+    p->last_path = path;
+    p->ev_valid = p->ctx->profile != 0;
+    p->last_was_encode = false;
+    return DRX_OK;
+}
+
+// ---------------------------------------------------------------------------
 // per-waveform statistics from the encoded stream (drx_stats.hip)
 // ---------------------------------------------------------------------------
 static drx_status wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                              const uint32_t *d_sideband, bool sideband, uint32_t head_len, int64_t *d_out) {
     if (!p) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
-    if (!d_in || !d_chunk_word_off || !d_out || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "wave_stats: null pointer");
-    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    if (const drx_status st = stream_call_args(p, "wave_stats", d_in && d_chunk_word_off && d_out, d_sideband, sideband)) return st;
     DRX_ON_DEVICE(ctx);
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
     // the block form's accumulators and list belong to the plan: allocated by its first call that takes that form
     if (!p->d_sacc && stats_blocks_batch(p->G, p->d_blk)) DRX_HIP(ctx, p->mem.alloc(&p->d_sacc, stats_blocks_scratch_bytes(p->G)));
-    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
     DRX_HIP(ctx, launch_wave_stats(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, p->d_blk,
                                    p->d_sacc, head_len, p->d_status, d_out, ctx->profile ? p->ev : nullptr, ctx->stream, &p->last_stats_form));
-    p->last_path = DRX_PATH_STATS;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    return stream_call_end(p, DRX_PATH_STATS);
 }
 
 drx_status drx_wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t head_len,
@@ -1091,26 +1112,17 @@ static drx_status decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_w
                                 int64_t offset, uint32_t width, int16_t pad, int16_t *d_out, uint64_t out_stride) {
     if (!p) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
-    if (!d_in || !d_chunk_word_off || !d_out || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "decode_window: null pointer");
-    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    if (const drx_status st = stream_call_args(p, "decode_window", d_in && d_chunk_word_off && d_out, d_sideband, sideband)) return st;
     if (out_stride < width)
         return fail(ctx, DRX_ERR_ARG, "decode_window: rows %llu samples apart do not hold %u", (unsigned long long)out_stride, width);
     if (d_start && start_stride == 0) return fail(ctx, DRX_ERR_ARG, "decode_window: start_stride 0");
     if (width == 0) return DRX_OK;  // (no row receives a sample: nothing to launch)
     DRX_ON_DEVICE(ctx);
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
     DRX_HIP(ctx, launch_decode_window(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, d_start,
                                       start_stride, offset, width, pad, p->d_status, d_out, out_stride, ctx->profile ? p->ev : nullptr,
                                       ctx->stream));
-    p->last_path = DRX_PATH_WINDOW;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    return stream_call_end(p, DRX_PATH_WINDOW);
 }
 
 drx_status drx_decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -1136,26 +1148,17 @@ static drx_status find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_wor
                               int32_t polarity, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out) {
     if (!p) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
-    if (!d_in || !d_chunk_word_off || !d_count || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "find_pulses: null pointer");
-    if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    if (const drx_status st = stream_call_args(p, "find_pulses", d_in && d_chunk_word_off && d_count, d_sideband, sideband)) return st;
     if (max_pulses && !d_out) return fail(ctx, DRX_ERR_ARG, "find_pulses: no output for %u pulses per waveform", max_pulses);
     if (polarity == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: polarity 0");
     if (min_width == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: min_width 0");
     if (d_thr && thr_stride == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: thr_stride 0");
     DRX_ON_DEVICE(ctx);
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
     DRX_HIP(ctx, launch_find_pulses(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, d_thr,
                                     thr_stride, thr, polarity < 0, min_width, max_pulses, p->d_status, d_count, d_out,
                                     ctx->profile ? p->ev : nullptr, ctx->stream));
-    p->last_path = DRX_PATH_PULSES;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    return stream_call_end(p, DRX_PATH_PULSES);
 }
 
 drx_status drx_find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -1208,19 +1211,11 @@ static drx_status transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words
     DRX_ON_DEVICE(ctx);
     TrcScratch t;
     if (const drx_status st = trc_scratch(p, &t)) return st;
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
     DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, new_k,
                                   t.words, t.rel, t.chunk_words, d_out, out_cap, d_out_off, d_out_wave_words, nullptr, p->d_status,
                                   ctx->profile ? p->ev : nullptr, ctx->stream));
-    p->last_path = DRX_PATH_TRANSCODE;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    return stream_call_end(p, DRX_PATH_TRANSCODE);
 }
 
 drx_status drx_transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t new_rice_k,
@@ -1240,23 +1235,16 @@ drx_status drx_estimate_words_encoded(drx_plan *p, const uint32_t *d_in, uint64_
                                       const uint32_t *d_wave_words, uint64_t words_out[16]) {
     if (!p) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
-    if (!d_in || !d_chunk_word_off || !words_out) return fail(ctx, DRX_ERR_ARG, "estimate_words_encoded: null pointer");
-    if (d_wave_words && d_wave_words == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
+    const bool sideband = d_wave_words != nullptr;
+    if (const drx_status st = stream_call_args(p, "estimate_words_encoded", d_in && d_chunk_word_off && words_out, d_wave_words, sideband)) return st;
     DRX_ON_DEVICE(ctx);
     TrcScratch t;
     if (const drx_status st = trc_scratch(p, &t)) return st;
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    if (d_wave_words)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_wave_words, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
-    DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, d_wave_words != nullptr, p->d_pw,
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_wave_words, sideband)) return st;
+    DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw,
                                   0u, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, t.est, p->d_status,
                                   ctx->profile ? p->ev : nullptr, ctx->stream));
-    p->last_path = DRX_PATH_TRANSCODE;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
+    (void)stream_call_end(p, DRX_PATH_TRANSCODE);
     DRX_HIP(ctx, hipMemcpyAsync(words_out, t.est, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     return drx_plan_finish(p, nullptr);  // (waits; a stream that failed validation: DRX_ERR_CORRUPT, words_out undefined)
 }

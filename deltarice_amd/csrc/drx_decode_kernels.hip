@@ -21,6 +21,7 @@
 
 #include "drx_internal.h"
 #include "drx_device.h"
+#include "drx_lane_stream.h"
 #include "drx_walk.h"
 
 namespace drx {
@@ -38,43 +39,10 @@ __global__ __launch_bounds__(64) void k_decode_simple(Geom G, const uint32_t *__
     const uint32_t *s = in + wave_off[g] + 1;
     const uint32_t n = wave_words[g];
     int16_t *y = out + r.sample_off;
-    const uint32_t k = G.k;
-    uint64_t win = 0;
-    uint32_t have = 0, wi = 0;
-    int32_t acc = 0;
     int16_t hist[64];  // general prediction filters only (lives in scratch; the delta path never touches it)
-    for (uint32_t i = 0; i < r.len; ++i) {
-        if (have <= 32u) {
-            const uint32_t w = wi < n ? s[wi] : 0u;
-            ++wi;
-            win |= (uint64_t)w << (32u - have);
-            have += 32u;
-        }
-        uint32_t q = (uint32_t)__clzll((long long)win);
-        q = q > 8u ? 8u : q;
-        const uint32_t pl = (q == 8u) ? 16u : k;
-        const uint64_t t = win << (q + 1u);
-        const uint32_t rem = pl ? (uint32_t)(t >> (64u - pl)) : 0u;
-        const uint32_t z = (q == 8u) ? rem : ((q << k) + rem);
-        const int32_t d = (int32_t)(z >> 1) ^ -(int32_t)(z & 1u);  // un-zig-zag (:172-177)
-        if (G.n_taps == 0) {
-            acc += d;  // running sum (:80-89)
-        } else {
-            // general inverse (:92-101): y[i] = (int16)((int16)(d[i] - sum_{j>=1} taps[j] y[i-j]) / taps[0]);
-            // the last 64 outputs live in a lane-private circular history (taps <= DRX_MAX_TAPS = 64)
-            uint32_t a = (uint32_t)(int32_t)(int16_t)d;
-            for (uint32_t j = 1; j < G.n_taps && j <= i; ++j) a -= (uint32_t)(int32_t)hist[(i - j) & 63u] * (uint32_t)G.taps[j];
-            acc = (int32_t)(int16_t)(uint16_t)a / G.taps[0];
-            hist[i & 63u] = (int16_t)acc;
-        }
-        y[i] = (int16_t)acc;
-        const uint32_t used = q + 1u + pl;
-        win <<= used;
-        have -= used;
-    }
+    const uint64_t words = serial_wave(G, s, n, r.len, hist, 1u, [&](uint32_t i, int16_t v) __attribute__((always_inline)) { y[i] = v; });
     // a valid waveform's codes end in its last payload word: n_i = ceil(bits / 32) (src/deltaRice.c:237-241)
-    const uint64_t bits = 32ull * wi - have;
-    if (r.len && ((bits + 31u) >> 5) != n) atomicOr(&st->err, kErrCorrupt);
+    if (r.len && words != n) atomicOr(&st->err, kErrCorrupt);
 }
 
 // Decoder for FEW, LONG waveforms (WaveformLength = -1, the reference's default, makes every chunk one

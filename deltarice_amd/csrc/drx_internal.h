@@ -138,6 +138,19 @@ void launch_walk_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, 
                         uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s);
 void launch_walk_serial(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                         uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
+// The walk in front of a call that reads the WHOLE batch behind it (drx_wave_stats, drx_decode_window, drx_find_pulses,
+// drx_transcode): route_walk()'s choice, all of it on the stream s
+hipError_t launch_batch_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s);
+// ... and the launches of those calls' kernels, a lane per waveform: the wavefronts of the batch -- rag_order's groups for a
+// ragged plan that has them under the kernels that follow it (by_rag_order: lane_wave(), drx_lane_stream.h), 64 consecutive
+// waveforms each otherwise -- in slices of at most 2^25 per launch (a launch carries fewer than 2^32 threads).
+// go(first wavefront, wavefronts)
+template <class F> inline void for_wavefront_slices(const Geom &G, bool by_rag_order, F go) {
+    constexpr uint64_t max_grid = 1ull << 25;
+    const uint64_t n_wf = (by_rag_order && !G.uniform && G.rag_order) ? (uint64_t)G.rag_groups : (G.total_waves + 63u) / 64u;
+    for (uint64_t base = 0; base < n_wf; base += max_grid) go(base, (unsigned)(n_wf - base < max_grid ? n_wf - base : max_grid));
+}
 // ... no walk: the tables from the n_i table an encode left behind, checked against the stream
 hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                   const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,

@@ -6,10 +6,9 @@
 // The header tables (wave_off / wave_words) are valid for the whole batch: the host runs the walk in front of these launches
 // (launch_transcode(): the walks of drx_walk.hip, or the side-band's tables), as launch_wave_stats() does.
 //
-//   k_recode_sizes<false>  one LANE per waveform, the stream side of k_wave_stats (drx_stats.hip): a per-lane word-major reversed
-//                          LDS ring refilled in whole 128-byte lines, each requested once; a 64-bit window gives two codes per
-//                          ring access; escape and ordinary codes share one extraction; the end-of-payload check.  Adds the
-//                          length of every z at the new parameter and stores n_i' = ceil(bits / 32).
+//   k_recode_sizes<false>  one LANE per waveform, the stream side the shared reader's (drx_lane_reader.inc) with its
+//                          end-of-payload check.  Adds the length of every z at the new parameter and stores
+//                          n_i' = ceil(bits / 32).
 //   k_recode_sizes<true>   the same parse with sixteen bit counts per lane: the batch's words at every k = 0..15, added as
 //                          k_estimate_words adds them (a header word per waveform and per chunk), one atomic per wavefront and k.
 //   (k_chunk_scan / k_chunk_offsets of drx_encode_kernels.hip turn the table of n_i' into header positions, chunk offsets, the
@@ -32,154 +31,29 @@
 
 #include "drx_internal.h"
 #include "drx_device.h"
+#include "drx_lane_stream.h"
 
 namespace drx {
 
 namespace {
 
-constexpr int kRW = 64;      // input ring words per lane
-constexpr int kLW = 32;      // words per stream piece / output line: 128 bytes
-constexpr int kGS = 16;      // samples per group (a refill test and an output test per group)
-constexpr int kT = 64;       // samples per round (a piece is committed and the next requested per round)
-constexpr int kLogRW = 6;
-constexpr int kNV = kLW / 4;  // 16-byte loads per piece
 constexpr int kOW = 32;      // output ring words per lane
 constexpr int kOL = 16;      // words per output segment: half a line, 64 bytes
-constexpr uint32_t kWMask = (1u << 27) - 1u;
-constexpr uint32_t kNeedAt = kGS + 2;  // must refill below this many words (16 codes of 25 bits: 12.5 words; a pair reads three)
 // the output ring is looked at once per group: a lane holds at most kFlushAt - 1 words then, a group adds at most 13.  (A ring of
 // 64 words written out in whole 128-byte lines leaves the LDS room for four wavefronts per CU instead of six and was measured
 // 40 % slower, 15.7 against 11.2 ms on the headline batch: DESIGN.md section 4.2g)
 constexpr uint32_t kFlushAt = 20;
-static_assert(kT % kGS == 0 && kRW - kLW >= kGS + 2, "round length / ring slack");
 static_assert(kFlushAt - 1 + (kGS * 25 + 31) / 32 <= kOW && kFlushAt >= kOL, "output ring slack");
-constexpr int kInRingWords = (kRW + 2) * 64;
 constexpr int kOutRingWords = kOW * 64;
 
-// which waveform a lane takes (as k_wave_stats: g = 64 * wavefront + lane, or rag_order's {chunk, group} entries)
-struct LaneWave {
-    uint64_t g, chunk;
-    uint32_t idx, len, n_samples;
-    bool active;
-};
-__device__ __forceinline__ bool lane_wave(const Geom &G, uint64_t wf, int lane, LaneWave &w) {
-    w.g = 0; w.chunk = 0; w.idx = 0; w.len = 0; w.n_samples = 0;
-    if (!G.uniform && G.rag_order) {
-        if (wf >= G.rag_groups) return false;
-        const uint2 e = G.rag_order[wf];  // {chunk, group of 64 waveforms inside it}
-        const ChunkDesc d = G.chunks[e.x];
-        w.idx = e.y * 64u + (uint32_t)lane;
-        w.active = w.idx < d.n_waves;
-        w.g = d.wave_base + w.idx;
-        w.chunk = e.x;
-        w.n_samples = d.n_samples;
-        if (w.active) w.len = (w.idx + 1 == d.n_waves) ? (d.n_samples - w.idx * d.wave_len) : d.wave_len;
-    } else {
-        w.g = wf * 64u + (uint32_t)lane;
-        w.active = w.g < G.total_waves;
-        if (w.active) {
-            const WaveRef r = locate(G, w.g);
-            w.chunk = r.chunk; w.idx = r.idx; w.len = r.len; w.n_samples = r.n_samples;
-        }
-    }
-    return true;
-}
-
-// The parse of one waveform per lane: sink(z) receives the canonical zig-zag value of every sample in order, group_end() runs
-// once per group of kGS samples with the whole wavefront converged.  Returns whether the lane's codes ended in its last payload
-// word (k_wave_stats' check).  S: the payload's first word, n: its words, k: the stream's parameter.
+// The parse of one waveform per lane over the shared reader (drx_lane_reader.inc): sink(z) receives the canonical zig-zag value
+// of every sample in order, group_end() runs once per group of kGS samples with the whole wavefront converged.  Returns whether
+// the lane's codes ended in its last payload word.  ring: the wavefront's ring_all + 64, S: the payload's first word, n: its
+// words, k: the stream's parameter.
 template <typename Sink, typename GroupEnd>
 __device__ __forceinline__ bool parse_lane(uint32_t *__restrict__ ring, const uint32_t *__restrict__ in, uint64_t in_words, uint64_t S,
                                            uint32_t n, uint32_t len, uint32_t k, int lane, Sink &&sink, GroupEnd &&group_end) {
-    constexpr int RW = kRW, LW = kLW, GS = kGS, T = kT, NV = kNV;
-    const uint64_t A = (S & ~(uint64_t)(RW - 1)) - (uint64_t)RW;  // s0 in [RW, 2 RW)
-    const uint32_t s0 = (uint32_t)(S - A);
-    const uint32_t endw = s0 + n;
-    uint32_t flw = s0 & ~(uint32_t)(LW - 1);
-    const bool in_vec_ok = ((uintptr_t)in & 15u) == 0;
-    uint32_t *myring = ring + lane;
-
-    // a piece lies inside [0, in_words) or is read word by word, zero beyond: no load leaves the caller's stream
-    auto load_piece = [&](uint4 (&v)[NV]) {
-        const uint64_t a = A + flw;
-        if (in_vec_ok && a + (uint32_t)LW <= in_words) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) v[j] = *reinterpret_cast<const uint4 *>(in + a + 4 * j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) {
-                v[j].x = (a + 4 * j + 0 < in_words) ? in[a + 4 * j + 0] : 0u;
-                v[j].y = (a + 4 * j + 1 < in_words) ? in[a + 4 * j + 1] : 0u;
-                v[j].z = (a + 4 * j + 2 < in_words) ? in[a + 4 * j + 2] : 0u;
-                v[j].w = (a + 4 * j + 3 < in_words) ? in[a + 4 * j + 3] : 0u;
-            }
-        }
-    };
-    auto store_piece = [&](const uint4 (&v)[NV]) {
-        const uint32_t r0 = (uint32_t)RW - (flw & (uint32_t)(RW - 1));
-        uint32_t *dst = myring + r0 * 64u;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            dst[-(4 * j + 0) * 64] = v[j].x; dst[-(4 * j + 1) * 64] = v[j].y;
-            dst[-(4 * j + 2) * 64] = v[j].z; dst[-(4 * j + 3) * 64] = v[j].w;
-        }
-        if (r0 == (uint32_t)RW) {
-            myring[0] = v[0].x;
-            myring[-64] = v[0].y;
-        }
-        flw += (uint32_t)LW;
-    };
-
-    uint32_t Q = 0u - 32u * s0;  // minus the bit position (relative to A)
-    uint32_t Q_need;
-    auto set_limits = [&]() __attribute__((always_inline)) {
-        const bool more = flw < endw;
-        Q_need = more ? ~(32u * (flw - kNeedAt + 1u)) : Q - 0x7fffffffu;
-    };
-    auto sync_refill = [&]() __attribute__((always_inline)) {  // serve every lane that is (nearly) dry, waiting for the data
-        for (;;) {
-            const uint32_t avail = (flw - ((~Q) >> 5)) & kWMask;
-            const bool more = flw < endw;
-            if (!__any(more && avail < kNeedAt)) break;
-            if (more && avail <= (uint32_t)(RW - LW)) {
-                uint4 v[NV];
-                load_piece(v);
-                store_piece(v);
-            }
-            wave_sync();
-        }
-    };
-
-    {   // start-up: the piece that holds word s0 and as many more as fit
-        uint4 v[NV];
-        for (int i = 0; i < RW / LW; ++i) {
-            if (__ballot(flw < endw && flw + (uint32_t)LW <= s0 + (uint32_t)RW) == 0) break;
-            if (flw < endw && flw + (uint32_t)LW <= s0 + (uint32_t)RW) {
-                load_piece(v);
-                store_piece(v);
-            }
-        }
-        wave_sync();
-    }
-
-    // ONE piece per lane is in flight (k_wave_stats): requested at a round's end, committed where it fits
-    uint4 pv[NV];
-    bool pneed = false;
-    auto commit_if_fits = [&]() __attribute__((always_inline)) {
-        const uint32_t avail = (flw - ((~Q) >> 5)) & kWMask;
-        if (pneed && avail <= (uint32_t)(RW - LW)) {
-            store_piece(pv);
-            pneed = false;
-        }
-    };
-    auto group_refill = [&]() __attribute__((always_inline)) {
-        if (__any((int32_t)(Q - Q_need) <= 0)) {
-            commit_if_fits();
-            wave_sync();
-            sync_refill();
-            set_limits();
-        }
-    };
+#include "drx_lane_reader.inc"
     // the int16 residual the decoders take from a code, as its zig-zag value: below k = 13 an ordinary code's value fits 15 bits
     // and an escape's sixteen payload bits ARE it (the extraction leaves 8 << 16 above them)
     const bool wide = k >= 13u;
@@ -190,66 +64,32 @@ __device__ __forceinline__ bool parse_lane(uint32_t *__restrict__ ring, const ui
         }
         return z & 0xffffu;
     };
-
     const uint32_t steps = wave_max_u32(len);
     set_limits();
-    for (uint32_t i = 0; i < steps; i += (uint32_t)GS) {
+    for (uint32_t i = 0; i < steps; i += (uint32_t)kGS) {
         group_refill();
-        if (i + (uint32_t)GS <= len) {
-            // ---- the unmasked group: eight pairs, two codes per ring access (a 64-bit window always holds two codes)
+        if (i + (uint32_t)kGS <= len) {
+            // ---- the unmasked group: eight pairs, two codes per ring access
 #pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                const uint32_t row = __builtin_amdgcn_ubfe(Q, 5u, (uint32_t)kLogRW);
-                const uint32_t *wp = myring + row * 64u;
-                const uint32_t lo = wp[0], hi = wp[64], lo2 = wp[-64];
-                const uint32_t winA = __builtin_amdgcn_alignbit(hi, lo, Q);
-                const uint32_t winB = __builtin_amdgcn_alignbit(lo, lo2, Q);
-                const uint32_t q1 = ffbh(winA);
-                const uint32_t kk1 = (winA < (1u << 24)) ? 16u : k;
-                const uint32_t nu1 = ~(q1 + kk1);  // minus the code length
-                const uint32_t win2 = __builtin_amdgcn_alignbit(winA, winB, nu1);
-                const uint32_t q2 = ffbh(win2);
-                const uint32_t kk2 = (win2 < (1u << 24)) ? 16u : k;
-                const uint32_t nu2 = ~(q2 + kk2);
-                asm("v_add3_u32 %0, %1, %2, %3" : "=v"(Q) : "v"(Q), "v"(nu1), "v"(nu2));
-                const uint32_t z1 = (q1 << kk1) + __builtin_amdgcn_ubfe(winA, nu1, kk1);
-                const uint32_t z2 = (q2 << kk2) + __builtin_amdgcn_ubfe(win2, nu2, kk2);
+            for (int u = 0; u < kGS; u += 2) {
+                LANE_PAIR(z1, z2)
                 sink(canon(z1));
                 sink(canon(z2));
             }
         } else if (i < len) {
             // ---- the masked group: the lane's waveform ends inside it.  One sample per ring access.
 #pragma unroll 1
-            for (uint32_t u = 0; u < (uint32_t)GS; ++u) {
+            for (uint32_t u = 0; u < (uint32_t)kGS; ++u) {
                 if (i + u < len) {
-                    const uint32_t row = __builtin_amdgcn_ubfe(Q, 5u, (uint32_t)kLogRW);
-                    const uint32_t *wp = myring + row * 64u;
-                    const uint32_t lo = wp[0], hi = wp[64];
-                    const uint32_t win = __builtin_amdgcn_alignbit(hi, lo, Q);
-                    const uint32_t q = ffbh(win);  // win == 0 only past the end of a corrupt stream
-                    const uint32_t kk = (win < (1u << 24)) ? 16u : k;
-                    const uint32_t used = q + kk + 1u;
-                    const uint32_t z = (q << kk) + __builtin_amdgcn_ubfe(win, 32u - used, kk);
-                    Q -= used;
+                    LANE_ONE(z)
                     sink(canon(z));
                 }
             }
         }
         group_end();
-        if ((i & (uint32_t)(T - 1)) == (uint32_t)(T - GS)) {  // a round's end
-            wave_sync();
-            commit_if_fits();
-            wave_sync();
-            set_limits();
-            if (!pneed) {
-                pneed = flw < endw;
-                if (pneed) load_piece(pv);
-            }
-        }
+        round_end(i);
     }
-    // A valid waveform's codes end inside its last payload word, n_i = ceil(bits / 32) (src/deltaRice.c:237-241), and every
-    // word of it has been through the ring by then (k_wave_stats)
-    return !(len && (((((0u - Q) - 32u * s0 + 31u) >> 5) & kWMask) != (n & kWMask) || flw < endw));
+    return !(len && LANE_MISSES_LAST_WORD());
 }
 
 // length of z's code at parameter k2
@@ -271,7 +111,6 @@ __global__ __launch_bounds__(64) void k_recode_sizes(Geom G, const uint32_t *__r
                                                      unsigned long long *__restrict__ est) {
     constexpr int NK = ALLK ? 16 : 1;
     __shared__ uint32_t ring_all[kInRingWords];
-    uint32_t *const ring = ring_all + 64;
     const int lane = lane_id();
     // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
     if (st->err) return;
@@ -287,7 +126,7 @@ __global__ __launch_bounds__(64) void k_recode_sizes(Geom G, const uint32_t *__r
     uint32_t gb[NK];  // of the current group: at most 16 x 25
 #pragma unroll
     for (int j = 0; j < NK; ++j) { bits[j] = 0; gb[j] = 0; }
-    const bool ok = parse_lane(ring, in, in_words, S, n, w.len, G.k, lane,
+    const bool ok = parse_lane(ring_all + 64, in, in_words, S, n, w.len, G.k, lane,
         [&](uint32_t z) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < NK; ++j) gb[j] += code_bits(z, ALLK ? (uint32_t)j : k2);
@@ -322,7 +161,6 @@ __global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__re
                                                     const uint64_t *__restrict__ out_chunk_off, uint32_t *__restrict__ out) {
     __shared__ uint32_t ring_all[kInRingWords];
     __shared__ __attribute__((aligned(16))) uint32_t oring_all[kOutRingWords];
-    uint32_t *const ring = ring_all + 64;
     const int lane = lane_id();
     if (st->err) return;
     LaneWave w;
@@ -368,7 +206,7 @@ __global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__re
         fl = le;
     };
 
-    (void)parse_lane(ring, in, in_words, S, n, w.len, G.k, lane,
+    (void)parse_lane(ring_all + 64, in, in_words, S, n, w.len, G.k, lane,
         [&](uint32_t z) __attribute__((always_inline)) {
             // rice_code()'s code and length (drx_encode_kernels.hip), from the zig-zag value
             const uint32_t q = z >> k2;
@@ -406,9 +244,6 @@ __global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__re
     for (uint32_t x = fl; x < ow; ++x) outB[x] = myout[(x & (uint32_t)(kOW - 1)) * 64u];
 }
 
-// A launch carries fewer than 2^32 threads: at most this many wavefronts of 64 lanes go into one, a larger batch into several
-constexpr uint64_t kRecodeMaxGrid = 1ull << 25;
-
 // ev: {start, walk's end, offsets' end, end}.  d_out == nullptr: as far as the offsets (the sizing call).  d_est != nullptr:
 // the estimate -- walk and k_recode_sizes<true> alone.
 hipError_t launch_transcode(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -418,47 +253,34 @@ hipError_t launch_transcode(const Geom &G, const uint32_t *d_in, uint64_t in_wor
                             unsigned long long *d_est, DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
     if (G.total_waves == 0) return hipSuccess;
     mark(ev, 0, s);
-    // ---- the walk (drx_walk.hip), as launch_wave_stats() runs it
+    // ---- the walk (drx_walk.hip): launch_batch_walk()
     if (!tables_ready) {
-        const WalkRoute R = route_walk(G, false, d_pw != nullptr);
-        if (R.chunk_wide || R.blocks) {
-            const hipError_t e = walk_scratch_reset(G, d_pw, s);
-            if (e != hipSuccess) return e;
-            if (R.chunk_wide) launch_walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, R.by_chains, s);
-            if (R.blocks) launch_walk_blocks(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
-        } else {
-            launch_walk_serial(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, s);
-        }
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = launch_batch_walk(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
         if (e != hipSuccess) return e;
     }
     mark(ev, 1, s);
-    const uint64_t n_wf = (!G.uniform && G.rag_order) ? (uint64_t)G.rag_groups : (G.total_waves + 63u) / 64u;
     if (d_est) {
         const hipError_t e = hipMemsetAsync(d_est, 0, 16 * sizeof(unsigned long long), s);
         if (e != hipSuccess) return e;
-        for (uint64_t base = 0; base < n_wf; base += kRecodeMaxGrid) {
-            const unsigned nb = (unsigned)std::min<uint64_t>(n_wf - base, kRecodeMaxGrid);
+        for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
             k_recode_sizes<true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, 0u, d_status, nullptr, nullptr, d_est);
-        }
+        });
         mark(ev, 2, s);
         mark(ev, 3, s);
         return hipGetLastError();
     }
     // ---- sizes, scan, offsets
-    for (uint64_t base = 0; base < n_wf; base += kRecodeMaxGrid) {
-        const unsigned nb = (unsigned)std::min<uint64_t>(n_wf - base, kRecodeMaxGrid);
+    for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
         k_recode_sizes<false><<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, k2, d_status, d_new_words, d_out_wave_words, nullptr);
-    }
+    });
     hipError_t e = launch_chunk_offsets(G, d_new_words, d_new_rel, d_new_chunk_words, d_out_chunk_word_off, d_out ? out_cap : ~0ull, d_status, s);
     if (e != hipSuccess) return e;
     mark(ev, 2, s);
     // ---- pack
     if (d_out) {
-        for (uint64_t base = 0; base < n_wf; base += kRecodeMaxGrid) {
-            const unsigned nb = (unsigned)std::min<uint64_t>(n_wf - base, kRecodeMaxGrid);
+        for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
             k_recode_pack<<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, k2, d_status, d_new_words, d_new_rel, d_out_chunk_word_off, d_out);
-        }
+        });
     }
     mark(ev, 3, s);
     return hipGetLastError();

@@ -1149,6 +1149,21 @@ void launch_walk_serial(const Geom &G, const uint32_t *d_in, uint64_t in_words, 
     walk_serial(G, d_in, in_words, d_chunk_word_off, nullptr, n_short, nullptr, n - n_short, d_wave_off, d_wave_words, d_status, s);
 }
 
+// The walk in front of a call that reads the whole batch behind it, on one stream
+hipError_t launch_batch_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s) {
+    const WalkRoute R = route_walk(G, false, d_pw != nullptr);
+    if (R.chunk_wide || R.blocks) {
+        const hipError_t e = walk_scratch_reset(G, d_pw, s);
+        if (e != hipSuccess) return e;
+        if (R.chunk_wide) launch_walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, R.by_chains, s);
+        if (R.blocks) launch_walk_blocks(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
+    } else {
+        launch_walk_serial(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, s);
+    }
+    return hipGetLastError();
+}
+
 // The walk in front of drx_decode_select: the chunks its selection touches and no others.  d_lists = the three lists of
 // select_walk_class() back to back; d_fail: uint32[n_chunks], cleared here.  Always by chains, in workgroups of kSwThreads.
 hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,

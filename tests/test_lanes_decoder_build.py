@@ -7,57 +7,25 @@ and records the pair chain of the interior rounds' group (the basic block of eig
 262 instructions, 217 of them VALU, as in the parent.  The shorter length chain (the negated code length as one v_sub behind a
 select, no v_not between a pair's windows) was built and measured and is not in the kernel: it returned nothing
 (profiles/lanes_lines_ab.txt), so nothing is asserted about v_not here."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "deltarice_amd", "csrc", "drx_decode_kernels.hip")
+from kernel_build import _field, _remark, compile_asm, find_compiler, kernel_resources
+
 PAIRS = 8  # per group of 16 samples
-
-
-def _make_var(name):
-    out = subprocess.run(["make", "-s", "--no-print-directory", "-C", ROOT, "--eval", f"print-var: ; @echo $({name})", "print-var"],
-                         check=True, capture_output=True, text=True).stdout
-    return out.strip().split()
 
 
 @pytest.fixture(scope="module")
 def lanes_kernels(tmp_path_factory):
     """mangled name -> (body text, metadata block, the compiler's resource remarks) of the four instantiations"""
-    cc = _make_var("HIPCC")
-    if not cc or not (os.path.exists(cc[0]) or shutil.which(cc[0])):
-        pytest.skip("hipcc not found")
-    out = tmp_path_factory.mktemp("asm") / "drx_decode_kernels.s"
-    r = subprocess.run([cc[0]] + _make_var("HIPFLAGS") + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", SRC,
-                                                          "-o", str(out)], check=True, capture_output=True, text=True)
-    asm = out.read_text()
-    blocks = asm[asm.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]
+    asm, stderr = compile_asm(find_compiler(), tmp_path_factory.mktemp("asm"), "drx_decode_kernels.hip")
     found = {}
     for m in re.finditer(r"^(_ZN3drx14k_decode_lanesI\w+):[^\n]*\n(.*?)^\s*\.end_amdhsa_kernel", asm, re.S | re.M):
         name, body = m.group(1), m.group(2)
-        meta = [b for b in blocks if re.search(r"\.name:\s+" + re.escape(name) + r"\n", b)]
-        assert len(meta) == 1, name
-        remarks = re.search(r"Function Name: " + re.escape(name) + r"\b(.*?)(?=Function Name:|\Z)", r.stderr, re.S)
-        assert remarks, name
-        found[name] = (body.split(".section")[0], meta[0], remarks.group(1))
+        found[name] = (body.split(".section")[0],) + kernel_resources(asm, stderr, name)
     assert len(found) == 4, sorted(found)
     return found
-
-
-def _field(meta, key):
-    m = re.search(r"\." + key + r":\s+(\d+)", meta)
-    assert m, key
-    return int(m.group(1))
-
-
-def _remark(remarks, key):
-    m = re.search(re.escape(key) + r":\s+(\d+)", remarks)
-    assert m, key
-    return int(m.group(1))
 
 
 def _instructions(block):

@@ -6,68 +6,29 @@ test_window_kernel_build.py.  Compiles drx_pulses.hip to gfx950 assembly with th
                         k_wave_stats and k_find_pulses are held to); 158 VGPRs, 16 896 bytes with this compiler now
   k_find_pulses_serial  no private segment
 and that `make`'s hazard check of hand-written asm statements passes on the object file."""
-import os
-import re
-import shutil
-import subprocess
-import sys
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "deltarice_amd", "csrc", "drx_pulses.hip")
+from kernel_build import _remark, check_object_hazards, find_compiler, kernels_of, resources
 
-
-def _make_var(name):
-    out = subprocess.run(["make", "-s", "--no-print-directory", "-C", ROOT, "--eval", f"print-var: ; @echo $({name})", "print-var"],
-                         check=True, capture_output=True, text=True).stdout
-    return out.strip().split()
+SRC = "drx_pulses.hip"
 
 
 @pytest.fixture(scope="module")
 def compiler():
-    cc = _make_var("HIPCC")
-    if not cc or not (os.path.exists(cc[0]) or shutil.which(cc[0])):
-        pytest.skip("hipcc not found")
-    return cc[0], _make_var("HIPFLAGS")
+    return find_compiler()
 
 
 @pytest.fixture(scope="module")
 def pulse_kernels(compiler, tmp_path_factory):
     """kernel (unmangled) -> (metadata block, the compiler's resource remarks)"""
-    cc, flags = compiler
-    out = tmp_path_factory.mktemp("asm") / "drx_pulses.s"
-    r = subprocess.run([cc] + flags + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", SRC, "-o", str(out)],
-                       check=True, capture_output=True, text=True)
-    asm = out.read_text()
-    blocks = asm[asm.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]
-    found = {}
-    for m in re.finditer(r"^(_ZN3drx\d+(k_find_pulses(?:_serial)?)E\w+):", asm, re.M):
-        name, short = m.group(1), m.group(2)
-        meta = [b for b in blocks if re.search(r"\.name:\s+" + re.escape(name) + r"\n", b)]
-        assert len(meta) == 1, name
-        remarks = re.search(r"Function Name: " + re.escape(name) + r"\b(.*?)(?=Function Name:|\Z)", r.stderr, re.S)
-        assert remarks, name
-        found[short] = (meta[0], remarks.group(1))
+    found = kernels_of(compiler, tmp_path_factory.mktemp("asm"), SRC, r"(k_find_pulses(?:_serial)?)E")
     assert sorted(found) == ["k_find_pulses", "k_find_pulses_serial"], sorted(found)
     return found
 
 
-def _field(meta, key):
-    m = re.search(r"\." + key + r":\s+(\d+)", meta)
-    assert m, key
-    return int(m.group(1))
-
-
-def _remark(remarks, key):
-    m = re.search(re.escape(key) + r":\s+(\d+)", remarks)
-    assert m, key
-    return int(m.group(1))
-
-
 def test_find_pulses_resources(pulse_kernels):
     meta, remarks = pulse_kernels["k_find_pulses"]
-    vgprs, lds, scratch = _field(meta, "vgpr_count"), _field(meta, "group_segment_fixed_size"), _field(meta, "private_segment_fixed_size")
+    vgprs, lds, scratch = resources(pulse_kernels["k_find_pulses"])
     print(f"k_find_pulses: vgpr_count {vgprs}, LDS {lds}, private segment {scratch}")
     assert lds * 9 <= 163840 and _remark(remarks, "LDS Size [bytes/block]") * 9 <= 163840, lds
     assert scratch == 0 and _remark(remarks, "ScratchSize [bytes/lane]") == 0, scratch
@@ -76,17 +37,10 @@ def test_find_pulses_resources(pulse_kernels):
 
 def test_find_pulses_serial_resources(pulse_kernels):
     meta, remarks = pulse_kernels["k_find_pulses_serial"]
-    scratch = _field(meta, "private_segment_fixed_size")
-    print(f"k_find_pulses_serial: vgpr_count {_field(meta, 'vgpr_count')}, LDS {_field(meta, 'group_segment_fixed_size')}, private segment {scratch}")
+    vgprs, lds, scratch = resources(pulse_kernels["k_find_pulses_serial"])
+    print(f"k_find_pulses_serial: vgpr_count {vgprs}, LDS {lds}, private segment {scratch}")
     assert scratch == 0 and _remark(remarks, "ScratchSize [bytes/lane]") == 0, scratch
 
 
 def test_pulses_object_passes_the_asm_hazard_check(compiler, tmp_path):
-    """The check `make` runs over every object before it links the library, on this translation unit's."""
-    cc, flags = compiler
-    obj = tmp_path / "drx_pulses.o"
-    subprocess.run([cc] + flags + ["-c", SRC, "-o", str(obj)], check=True, capture_output=True, text=True)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_asm_hazards.py"), str(obj)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    srcs = subprocess.run(["make", "-s", "--no-print-directory", "-C", ROOT, "print-hip-srcs"], check=True, capture_output=True, text=True).stdout.split()
-    assert "deltarice_amd/csrc/drx_pulses.hip" in srcs, "drx_pulses.hip is not among the Makefile's HIP_SRCS"
+    check_object_hazards(compiler, tmp_path, SRC)

@@ -6,44 +6,24 @@ instantiation k_stats_blocks<NT, SW>:
   four SIMDs) -- not below those of k_decode_blocks<NT, false, SW>, the delta-filter decoder of the same geometry: the kernel
   shares that decoder's phase 1 and must not be the reason fewer blocks are resident;
 and that `make`'s hazard check of hand-written asm statements passes on the object file."""
-import os
-import re
-import subprocess
-import sys
-
 import pytest
 
-from test_stats_kernel_build import _field, _make_var, _remark, compiler  # noqa: F401  (compiler: a fixture)
+from kernel_build import _field, _remark, check_object_hazards, find_compiler, kernels_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "deltarice_amd", "csrc")
 GEOMETRIES = [(nt, sw) for nt in (64, 128, 256) for sw in (9, 11, 15, 19)]
 
 
-def kernels_of(compiler, tmp, src, pattern):
-    """{(NT, SW): (metadata block, the compiler's resource remarks)} of the kernels of `src` whose mangled name matches."""
-    cc, flags = compiler
-    out = tmp / (os.path.basename(src) + ".s")
-    r = subprocess.run([cc] + flags + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", src, "-o", str(out)],
-                       check=True, capture_output=True, text=True)
-    asm = out.read_text()
-    blocks = asm[asm.index("amdhsa.kernels:"):].split("  - .agpr_count:")[1:]
-    found = {}
-    for m in re.finditer(r"^(_ZN3drx\d+" + pattern + r"\w+):", asm, re.M):
-        name = m.group(1)
-        meta = [b for b in blocks if re.search(r"\.name:\s+" + re.escape(name) + r"\n", b)]
-        assert len(meta) == 1, name
-        remarks = re.search(r"Function Name: " + re.escape(name) + r"\b(.*?)(?=Function Name:|\Z)", r.stderr, re.S)
-        assert remarks, name
-        found[(int(m.group(2)), int(m.group(3)))] = (meta[0], remarks.group(1))
-    return found
+@pytest.fixture(scope="module")
+def compiler():
+    return find_compiler()
 
 
 @pytest.fixture(scope="module")
 def built(compiler, tmp_path_factory):
     tmp = tmp_path_factory.mktemp("asm")
-    stats = kernels_of(compiler, tmp, os.path.join(CSRC, "drx_stats_blocks.hip"), r"k_stats_blocksILi(\d+)ELi(\d+)EE")
-    decode = kernels_of(compiler, tmp, os.path.join(CSRC, "drx_blocks.hip"), r"k_decode_blocksILi(\d+)ELb0ELi(\d+)ELb0EE")
+    geometry = lambda m: (int(m.group(2)), int(m.group(3)))  # noqa: E731
+    stats = kernels_of(compiler, tmp, "drx_stats_blocks.hip", r"k_stats_blocksILi(\d+)ELi(\d+)EE", key=geometry)
+    decode = kernels_of(compiler, tmp, "drx_blocks.hip", r"k_decode_blocksILi(\d+)ELb0ELi(\d+)ELb0EE", key=geometry)
     assert sorted(stats) == sorted(decode) == sorted(GEOMETRIES), (sorted(stats), sorted(decode))
     return stats, decode
 
@@ -70,11 +50,4 @@ def test_stats_blocks_resources(built, nt, sw):
 
 
 def test_stats_blocks_object_passes_the_asm_hazard_check(compiler, tmp_path):
-    """The check `make` runs over every object before it links the library, on this translation unit's."""
-    cc, flags = compiler
-    obj = tmp_path / "drx_stats_blocks.o"
-    subprocess.run([cc] + flags + ["-c", os.path.join(CSRC, "drx_stats_blocks.hip"), "-o", str(obj)], check=True, capture_output=True, text=True)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_asm_hazards.py"), str(obj)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    srcs = subprocess.run(["make", "-s", "--no-print-directory", "-C", ROOT, "print-hip-srcs"], check=True, capture_output=True, text=True).stdout.split()
-    assert "deltarice_amd/csrc/drx_stats_blocks.hip" in srcs, "drx_stats_blocks.hip is not among the Makefile's HIP_SRCS"
+    check_object_hazards(compiler, tmp_path, "drx_stats_blocks.hip")
