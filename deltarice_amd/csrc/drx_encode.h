@@ -5,7 +5,10 @@
 //   code_tile, put_tile           four dwords -> codes, lengths, scan, and into LDS: k_encode_fused, for_segment_tiles
 //                                 (drx_encode_kernels.hip), k_encode_stream, k_encode_stream_segs (drx_encode_stream.hip),
 //                                 recode_tiles
-//   for_full_tiles                the three-deep load pipeline: k_encode_fused and both stream kernels
+//   for_full_tiles                the three-deep load pipeline: k_encode_fused and k_encode_stream_segs
+//   code_tail_tile, put_tail_tile, for_tiles
+//                                 k_encode_stream: a waveform's trailing partial tile on the full tile's arithmetic, and the
+//                                 pipeline with that tile in it and nothing but unconditional loads
 //   recode_waveform, recode_range, history_before
 //                                 a waveform or a sample range whose code outgrew its LDS buffer, coded again straight to its
 //                                 place: k_encode_fused, both stream kernels, k_encode_pieces
@@ -228,6 +231,69 @@ __device__ __forceinline__ void put_tile(const TileCodes &t, At &&at) {
         emit_tile<FULLT>(t.c, at(t.incl - t.lane_bits));
 }
 
+// ---- a waveform's trailing tile on the full tile's arithmetic (k_encode_stream) ----
+// w3:w2:w1:w0 >> n, any n (128 and more: zero)
+__device__ __forceinline__ void shr128(uint32_t (&w)[4], uint32_t n) {
+    const uint32_t ws = n >> 5;
+    const uint32_t y0 = ws == 0u ? w[0] : ws == 1u ? w[1] : ws == 2u ? w[2] : ws == 3u ? w[3] : 0u;
+    const uint32_t y1 = ws == 0u ? w[1] : ws == 1u ? w[2] : ws == 2u ? w[3] : 0u;
+    const uint32_t y2 = ws == 0u ? w[2] : ws == 1u ? w[3] : 0u;
+    const uint32_t y3 = ws == 0u ? w[3] : 0u;
+    w[0] = __builtin_amdgcn_alignbit(y1, y0, n);
+    w[1] = __builtin_amdgcn_alignbit(y2, y1, n);
+    w[2] = __builtin_amdgcn_alignbit(y3, y2, n);
+    w[3] = y3 >> (n & 31u);
+}
+
+// The trailing tile's codes: nv of the lane's 8 samples exist, the missing ones are its LAST and were loaded as zeros.
+// concat_codes needs every code to be at least a bit long (32 - 0 is no funnel shift), so the lane's string is built from
+// all eight codes as they come out of packed_codes -- a missing sample has a code like any other, k + 1 bits or more -- and
+// what the missing ones put at its low end is shifted out again.  `ragged` (wave uniform: the length is no multiple of 8):
+// one lane holds 1..7 samples and the string is shifted by the bits of its missing codes; otherwise a lane holds eight
+// samples or none, and a select per word does.  t.c keeps the unmasked lengths: put_tail_tile() masks them for emit_tile.
+// `wide` (wave uniform): a lane's eight codes are more than 128 bits, the strings are not valid.
+template <bool GEN>
+__device__ __forceinline__ TileCodes code_tail_tile(const uint32_t (&w)[4], int nv, bool ragged, uint32_t &carry, uint32_t &carry2,
+                                                    const u16x2 (&tp)[4], uint32_t k, bool &wide) {
+    TileCodes t;
+    const uint32_t xprev = wave_shr1_carry(w[3], carry);
+    carry = (uint32_t)__builtin_amdgcn_readlane((int)w[3], 63);
+    uint32_t xprev2 = 0;
+    if (GEN) {
+        xprev2 = wave_shr1_carry(w[2], carry2);
+        carry2 = (uint32_t)__builtin_amdgcn_readlane((int)w[2], 63);
+    }
+    packed_codes<GEN>(w, xprev, xprev2, tp, k, t.c);
+    const uint32_t all_bits = lane_tile_bits(t.c);
+    concat_codes(t.c, t.cw);
+    if (ragged) {
+        PackedCodes cm = t.c;
+        mask_tail(cm, nv);
+        t.lane_bits = lane_tile_bits(cm);
+        shr128(t.cw, all_bits - t.lane_bits);
+    } else {
+        t.lane_bits = nv ? all_bits : 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t.cw[j] = nv ? t.cw[j] : 0u;
+    }
+    wide = __any((nv ? all_bits : 0u) > 128u);
+    t.incl = wave_incl_scan_dpp(t.lane_bits);
+    t.tile_bits = (uint32_t)__builtin_amdgcn_readlane((int)t.incl, 63);
+    return t;
+}
+
+// The trailing tile into LDS (at: as put_tile's).  A lane without samples ORs zeros into the words its neighbour ends in.
+template <typename At>
+__device__ __forceinline__ void put_tail_tile(const TileCodes &t, int nv, bool wide, At &&at) {
+    if (!wide) {
+        place_words(t.cw, at(t.incl));
+    } else {
+        PackedCodes c = t.c;
+        mask_tail(c, nv);
+        emit_tile<false>(c, at(t.incl - t.lane_bits));
+    }
+}
+
 // The full tiles of x[0, 512 n_full): full(w) for each, between() in front of every group of kDepth.
 // kDepth tiles of loads in flight, in kDepth fixed register sets (the loop is unrolled by kDepth so that no
 // loaded-but-not-yet-arrived register is ever copied): with 4 waves per SIMD a tile takes ~2.6 K cycles of wall time, less
@@ -269,6 +335,76 @@ __device__ __forceinline__ void for_full_tiles(const int16_t *__restrict__ x, ui
                 if (t + (uint32_t)u + kDepth < n_full) q[u] = xv[64 * (size_t)(t + u + kDepth)];
             }
         }
+    }
+}
+
+// The pipeline for a waveform WITH its trailing partial tile (k_encode_stream; for_full_tiles above stays as the other
+// encoders compile it): full(w) for each of the n_full full tiles, tailf(w) for the trailing one (`tail`), between(again)
+// in front of every group of kDepth -- again = false in front of the last, short one, behind which nobody would read what
+// a look-up brings (its register is the next tile's scratch, which then waits for it at once).  len >= 8.  Two things
+// differ from for_full_tiles.
+//   * The trailing tile is tile n_full of the same pipeline: its load is issued kDepth tiles ahead like any other.  Only
+//     the lanes that hold eight of its samples get them; tailf() must not look at the other lanes' registers.
+//   * EVERY load is unconditional: kDepth in the prologue, one behind every tile.  The compiler's s_waitcnt in front of a
+//     tile counts what is in flight on the WORST path into it, feasible or not.  Behind a prologue of `if (u < n_full)`
+//     loads that is a path on which the tile's own load is the youngest, and the wait was vmcnt(0) at the head of every
+//     group of kDepth tiles: the whole pipeline drained, the look-up that between() had just issued included (the assembly
+//     of for_full_tiles shows it).  Here a load beyond the waveform's last tile is that tile again (in the cache by
+//     then), and a lane whose 16 bytes would end behind x[len - 1] reads the waveform's last 16 bytes instead: no lane
+//     reads in front of x[0] or behind x[len - 1], and every tile's wait is vmcnt(kDepth - 1).
+template <typename B, typename F, typename T>
+__device__ __forceinline__ void for_tiles(const int16_t *__restrict__ x, uint32_t len, uint32_t n_full, bool tail, int lane,
+                                          B &&between, F &&full, T &&tailf) {
+    constexpr int kDepth = 3;
+    const uint32_t last = tail ? n_full : n_full - 1u;  // the waveform's last tile (n_full or tail: len >= 8)
+    const uint32_t imax = len - 8u;                     // the last sample a lane's 16 bytes may begin at
+    auto load = [&](uint32_t tile) -> uint4 {           // (tile: wave uniform)
+        tile = tile < last ? tile : last;
+        uint32_t i = tile * (uint32_t)kTile + 8u * (uint32_t)lane;
+        i = i < imax ? i : imax;
+        return *reinterpret_cast<const uint4 *>(x + i);
+    };
+    uint4 q[kDepth];
+    // (in THIS order: the scheduler issued them last tile first, which makes the first tile's load the youngest again)
+#pragma unroll
+    for (int u = 0; u < kDepth; ++u) {
+        q[u] = load((uint32_t)u);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    uint32_t t = 0;
+#pragma unroll 1
+    for (; t + kDepth <= n_full; t += kDepth) {
+        between(true);
+#pragma unroll
+        for (int u = 0; u < kDepth; ++u) {
+            const uint32_t w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
+            full(w);
+            q[u] = load(t + (uint32_t)u + kDepth);
+        }
+    }
+    // tile t + u is in set u: up to kDepth - 1 full tiles, then the trailing one
+    const uint32_t left = n_full - t;
+    static_assert(kDepth == 3, "the straight code below");
+    if (left) {
+        between(false);
+        const uint32_t w0[4] = {q[0].x, q[0].y, q[0].z, q[0].w};
+        full(w0);
+        if (left > 1u) {
+            const uint32_t w1[4] = {q[1].x, q[1].y, q[1].z, q[1].w};
+            full(w1);
+        }
+    }
+    if (tail) {
+        // (component by component: a select between the sets themselves is one between their addresses)
+        auto sel = [left](uint32_t a, uint32_t b, uint32_t c) -> uint32_t { return left == 0u ? a : (left == 1u ? b : c); };
+        const uint32_t w[4] = {sel(q[0].x, q[1].x, q[2].x), sel(q[0].y, q[1].y, q[2].y), sel(q[0].z, q[1].z, q[2].z),
+                               sel(q[0].w, q[1].w, q[2].w)};
+        tailf(w);
+    } else {
+        // Loads beyond the last tile are in flight and nobody reads them, but the next waveform's first write to one of
+        // their registers would wait for them -- with a vmcnt(0) that waits for the stores issued since as well (a
+        // ticket's total, wave_words).  Behind a trailing tile nothing is in flight: its selects have waited.
+        __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
     }
 }
 

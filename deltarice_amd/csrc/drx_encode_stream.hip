@@ -25,8 +25,9 @@
 // Two kernels run this machine: k_encode_stream over waveforms and k_encode_stream_segs over segments of long waveforms.
 // Shared, below ("the machine both coders share"): the rendezvous (es_rendezvous), the ring's free words (es_gap), the
 // decision to copy unit A out in front of a tile (es_release), the emission into the ring with its fold-back (ring_put), the
-// grid (es_grid); from drx_encode.h: a tile's codes (code_tile), the load pipeline (for_full_tiles), the coding-again of a unit
-// that outgrew the ring (recode_waveform, recode_range).  Each kernel's own: its place type (one word / EsPlace2) with
+// grid (es_grid); from drx_encode.h: a tile's codes (code_tile), the load pipeline (for_full_tiles; k_encode_stream: for_tiles,
+// with the waveform's trailing tile in it, coded by code_tail_tile), the coding-again of a unit that outgrew the ring
+// (recode_waveform, recode_range).  Each kernel's own: its place type (one word / EsPlace2) with
 // place_in_lds, place_to_lds, wait_place and between; copy_out; place_header / headers; its scanner; and the segment form's
 // `mark` and s_first.
 //
@@ -216,12 +217,13 @@ __device__ __forceinline__ bool es_release(bool must, uint64_t P, InLds &&place_
 }
 
 // The tile into the ring at ring bit s0 (from the ring's word 0, not wrapped; row = the ring with its pads).
-template <bool FULLT, uint32_t RING>
-__device__ __forceinline__ void ring_put(const TileCodes &t, uint32_t *row, uint32_t s0, int lane) {
+// put(at): put_tile or put_tail_tile.
+template <uint32_t RING, typename Put>
+__device__ __forceinline__ void ring_put_with(const TileCodes &t, uint32_t *row, uint32_t s0, int lane, Put &&put) {
     constexpr uint32_t kRingBits = RING * 32u;
     uint32_t *ring = row + kEsFront;
     const uint32_t ring_bits0 = lds_addr(ring) * 8u;
-    put_tile<FULLT>(t, [&](uint32_t bit) -> uint32_t {
+    put([&](uint32_t bit) -> uint32_t {
         const uint32_t b = s0 + bit;
         return ring_bits0 + (b >= kRingBits ? b - kRingBits : b);
     });
@@ -237,6 +239,10 @@ __device__ __forceinline__ void ring_put(const TileCodes &t, uint32_t *row, uint
         }
         wave_sync();
     }
+}
+template <bool FULLT, uint32_t RING>
+__device__ __forceinline__ void ring_put(const TileCodes &t, uint32_t *row, uint32_t s0, int lane) {
+    ring_put_with<RING>(t, row, s0, lane, [&](auto &&at) { put_tile<FULLT>(t, at); });
 }
 
 // persistent: 16 wavefronts per CU, one workgroup of them the scanner's; never more than the batch can feed
@@ -399,6 +405,11 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         const WaveRef r = locate_uniform(G, g);
         const int16_t *x = in + r.sample_off;
         const uint32_t wlen = r.len;
+        // The trailing partial tile is tile n_full of the load pipeline for the lanes that hold eight of its samples; whether
+        // one lane holds 1..7 (`ragged`) is wave uniform.
+        const uint32_t n_full = wlen / kTile, rem = wlen - n_full * (uint32_t)kTile;
+        const bool tail = rem != 0u, ragged = (rem & 7u) != 0u;
+        const bool tail_lane = 8u * (uint32_t)lane + 8u <= rem;
 
         auto gap = [&]() -> uint32_t { return es_gap<RING>(pend, startA, start, 8u); };
         if (pend && gap() < 512u) copy_out(wait_place());  // (short waveforms behind a long one: no room to start)
@@ -410,7 +421,10 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
         uint32_t carry2 = 0;   // GEN: the dword before that one
         auto process_tile = [&](const uint32_t (&w)[4], int nv, auto full_tag) {
             constexpr bool FULLT = decltype(full_tag)::value;
-            const TileCodes t = code_tile<GEN, FULLT>(w, nv, carry, carry2, tp, k);
+            bool wide = false;  // (trailing tile: a lane's codes are more than 128 bits)
+            TileCodes t;
+            if constexpr (FULLT) t = code_tile<GEN, true>(w, nv, carry, carry2, tp, k);
+            else t = code_tail_tile<GEN>(w, nv, ragged, carry, carry2, tp, k, wide);
             // The tile's last word against the words the ring has left: once per tile, and again only behind a copy_out.
             // (32 bits: while `fits` holds P is below the ring's 2^17 bits, and a scalar 64-bit `<` does not exist)
             const uint32_t need = ((uint32_t)P + t.tile_bits + 31u) >> 5;
@@ -419,18 +433,19 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                 limit = gap();
                 ok = fits && need < limit;
             }
-            if (ok)
-                ring_put<FULLT, RING>(t, row, start * 32u + (uint32_t)P, lane);
-            else
+            if (ok) {
+                if constexpr (FULLT) ring_put<true, RING>(t, row, start * 32u + (uint32_t)P, lane);
+                else ring_put_with<RING>(t, row, start * 32u + (uint32_t)P, lane, [&](auto &&at) { put_tail_tile(t, nv, wide, at); });
+            } else {
                 fits = false;
+            }
             P += t.tile_bits;
         };
-        const uint32_t n_full = wlen / kTile;
         // between tile groups: is waveform A's place known by now?  The load travels while a group is coded; whoever of the
         // workgroup sees the place first leaves it in LDS for the others (they look there at every tile).
         uint64_t pollv = 0;
         bool polling = false;
-        auto between = [&]() {
+        auto between = [&](bool again) {  // again: look once more if the place is not there yet
             if (!pend) return;
             if (polling) {
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(pollv >> 32));
@@ -440,15 +455,34 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream(Geom G, const int1
                     return;
                 }
             }
+            if (!again) return;
             if (lane == 0) pollv = es_load(place + TA);
             polling = true;
         };
 
-        for_full_tiles(x, n_full, lane, between, [&](const uint32_t (&w)[4]) { process_tile(w, 8, std::true_type{}); });
-        for (uint32_t t0 = n_full * kTile; t0 < wlen; t0 += kTile) {  // the trailing partial tile
+        auto full_tile = [&](const uint32_t (&w)[4]) { process_tile(w, 8, std::true_type{}); };
+        auto tail_tile = [&](const uint32_t (&wq)[4]) {  // wq: the samples of the lanes that hold eight
+            const uint32_t i0 = 8u * (uint32_t)lane;     // the lane's first sample in the tile
+            const int nv = tail_lane ? 8 : (i0 < rem ? (int)(rem - i0) : 0);
             uint32_t w[4];
-            const int nv = load8_dwords(x, wlen, t0, lane, true, w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = tail_lane ? wq[j] : 0u;
+            if (ragged && nv > 0 && nv < 8) {  // the one lane with 1..7 samples: sample by sample
+                const int16_t *xl = x + (size_t)n_full * kTile + i0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t a = (2 * j < nv) ? (uint32_t)(uint16_t)xl[2 * j] : 0u;
+                    const uint32_t b = (2 * j + 1 < nv) ? (uint32_t)(uint16_t)xl[2 * j + 1] : 0u;
+                    w[j] = a | (b << 16);
+                }
+            }
             process_tile(w, nv, std::false_type{});
+        };
+        if (wlen >= 8u) {
+            for_tiles(x, wlen, n_full, tail, lane, between, full_tile, tail_tile);
+        } else {  // (no 16 bytes to load: lane 0's samples are the waveform)
+            const uint32_t none[4] = {0u, 0u, 0u, 0u};
+            tail_tile(none);
         }
         const uint32_t n = (uint32_t)((P + 31u) >> 5);  // payload words n_i
         wave_sync();
