@@ -291,6 +291,33 @@ class Plan:
         if t.device != self.ctx.device or t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
             raise DeltaRiceError(1, f"{name}: need contiguous {dtype} tensor of >= {n} elements on {self.ctx.device}")
 
+    # What the calls on an encoded batch share: the closed-plan check, the checks of the batch's tensors, the choice between
+    # drx_X and drx_X_with_wave_words (the side-band table goes in front of the call's own arguments), and the blocking form.
+    def _open(self, who: str):
+        if not getattr(self, "_h", None):
+            raise DeltaRiceError(1, f"{who}: the plan is closed")
+
+    def _check_encoded(self, words: torch.Tensor, chunk_word_off: torch.Tensor, wave_words: Optional[torch.Tensor]):
+        self._dev_check(words, torch.int32, 1, "words")
+        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        if wave_words is not None:
+            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+
+    def _call_encoded(self, name: str, words, chunk_word_off, wave_words, in_words, *args):
+        n = words.numel() if in_words is None else int(in_words)
+        if wave_words is None:
+            st = getattr(self.ctx.lib, "drx_" + name)(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), *args)
+        else:
+            st = getattr(self.ctx.lib, f"drx_{name}_with_wave_words")(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
+                                                                      wave_words.data_ptr(), *args)
+        self.ctx._check(st)
+
+    def _blocking(self, launch, *args, **kw):
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        r = launch(*args, **kw)
+        self.finish()
+        return r
+
     def encode_async(self, x: torch.Tensor, out_words: Optional[torch.Tensor] = None,
                      chunk_word_off: Optional[torch.Tensor] = None, capacity_words: Optional[int] = None):
         """Launches the encode on the context's stream; no host sync."""
@@ -351,11 +378,7 @@ class Plan:
         return torch.from_numpy(self.wave_words().view(np.int32)).to(self.ctx.device)
 
     def decode(self, enc: EncodedBatch, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        cur = torch.cuda.current_stream(self.ctx.device)
-        self.ctx.stream.wait_stream(cur)
-        y = self.decode_async(enc.words, enc.chunk_word_off, out, in_words=enc.total_words)
-        self.finish()
-        return y
+        return self._blocking(self.decode_async, enc.words, enc.chunk_word_off, out, in_words=enc.total_words)
 
     def wave_lengths(self, wave_idx) -> np.ndarray:
         """len_i of the waveforms ``wave_idx`` names: WaveformLength, or less for the last waveform of a chunk."""
@@ -377,10 +400,7 @@ class Plan:
         Launch only; finish() raises on device-side errors."""
         idx = _as_index_array(wave_idx)
         n_sel = int(idx.size)
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._check_encoded(words, chunk_word_off, wave_words)
         if out is None:
             out = torch.zeros((n_sel, self.longest_wave()), dtype=torch.int16, device=self.ctx.device)
             self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))  # (the zero fill)
@@ -391,26 +411,15 @@ class Plan:
         # (rows of the plan's longest waveform hold any selection; shorter ones are checked against this one)
         if n_sel and out.shape[1] < self.longest_wave() and int(self.wave_lengths(idx).max()) > out.shape[1]:
             raise DeltaRiceError(1, f"out: rows of {out.shape[1]} samples are shorter than the longest selected waveform")
-        n = words.numel() if in_words is None else int(in_words)
-        ip = idx.ctypes.data_as(C.POINTER(C.c_uint64))
-        lib = self.ctx.lib
-        if wave_words is None:
-            st = lib.drx_decode_select(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), ip, n_sel, out.data_ptr(), stride)
-        else:
-            st = lib.drx_decode_select_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
-                                                       wave_words.data_ptr(), ip, n_sel, out.data_ptr(), stride)
-        self.ctx._check(st)
+        self._call_encoded("decode_select", words, chunk_word_off, wave_words, in_words,
+                           idx.ctypes.data_as(C.POINTER(C.c_uint64)), n_sel, out.data_ptr(), stride)
         return out
 
     def decode_select(self, enc: EncodedBatch, wave_idx, out: Optional[torch.Tensor] = None,
                       wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """decode_select_async on an EncodedBatch; waits, and raises like decode()."""
-        cur = torch.cuda.current_stream(self.ctx.device)
-        self.ctx.stream.wait_stream(cur)
-        y = self.decode_select_async(enc.words, enc.chunk_word_off, wave_idx, out, in_words=enc.total_words,
-                                     wave_words=wave_words)
-        self.finish()
-        return y
+        return self._blocking(self.decode_select_async, enc.words, enc.chunk_word_off, wave_idx, out, in_words=enc.total_words,
+                              wave_words=wave_words)
 
     def gather_encoded_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, wave_idx, chunk_waves: int,
                              out_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
@@ -424,10 +433,7 @@ class Plan:
         idx = _as_index_array(wave_idx)
         n_sel, cw = int(idx.size), int(chunk_waves)
         n_out = -(-n_sel // cw) if cw > 0 else 0
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._check_encoded(words, chunk_word_off, wave_words)
         if out_words is not None:
             self._dev_check(out_words, torch.int32, 0, "out_words")
         if out_chunk_word_off is None:
@@ -436,18 +442,9 @@ class Plan:
         if out_wave_words is None:
             out_wave_words = torch.empty(n_sel, dtype=torch.int32, device=self.ctx.device)
         self._dev_check(out_wave_words, torch.int32, n_sel, "out_wave_words")
-        n = words.numel() if in_words is None else int(in_words)
-        ip = idx.ctypes.data_as(C.POINTER(C.c_uint64))
         op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
-        lib = self.ctx.lib
-        if wave_words is None:
-            st = lib.drx_gather_encoded(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), ip, n_sel, cw, op, cap,
-                                        out_chunk_word_off.data_ptr(), out_wave_words.data_ptr() if n_sel else None)
-        else:
-            st = lib.drx_gather_encoded_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
-                                                        wave_words.data_ptr(), ip, n_sel, cw, op, cap,
-                                                        out_chunk_word_off.data_ptr(), out_wave_words.data_ptr() if n_sel else None)
-        self.ctx._check(st)
+        self._call_encoded("gather_encoded", words, chunk_word_off, wave_words, in_words, idx.ctypes.data_as(C.POINTER(C.c_uint64)),
+                           n_sel, cw, op, cap, out_chunk_word_off.data_ptr(), out_wave_words.data_ptr() if n_sel else None)
         return out_words, out_chunk_word_off, out_wave_words
 
     def gather_encoded(self, enc: EncodedBatch, wave_idx, chunk_waves: int, wave_words: Optional[torch.Tensor] = None,
@@ -481,39 +478,23 @@ class Plan:
         first occurrences; ``head``: the window of the last two columns, the first min(head, len) samples.  Nothing is decoded
         to memory.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).
         Launch only; finish() raises on device-side errors."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "wave_stats: the plan is closed")
+        self._open("wave_stats")
         head = int(head)
         if not 0 <= head < 1 << 32:
             raise DeltaRiceError(1, f"head: {head} is not a uint32")
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._check_encoded(words, chunk_word_off, wave_words)
         if out is None:
             out = torch.empty((self.total_waves, _lib.STAT_COLS), dtype=torch.int64, device=self.ctx.device)
         self._dev_check(out, torch.int64, self.total_waves * _lib.STAT_COLS, "out")
-        n = words.numel() if in_words is None else int(in_words)
-        lib = self.ctx.lib
-        if wave_words is None:
-            st = lib.drx_wave_stats(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), head, out.data_ptr())
-        else:
-            st = lib.drx_wave_stats_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
-                                                    wave_words.data_ptr(), head, out.data_ptr())
-        self.ctx._check(st)
+        self._call_encoded("wave_stats", words, chunk_word_off, wave_words, in_words, head, out.data_ptr())
         return out
 
     def wave_stats(self, enc: EncodedBatch, head: int = 0, out: Optional[torch.Tensor] = None,
                    wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """wave_stats_async on an EncodedBatch; waits, and raises like decode().  The cuts of an analysis come from its
         columns: ``plan.gather_encoded(enc, torch.nonzero(cut(stats)).flatten().cpu(), 2000)``."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "wave_stats: the plan is closed")
-        cur = torch.cuda.current_stream(self.ctx.device)
-        self.ctx.stream.wait_stream(cur)
-        s = self.wave_stats_async(enc.words, enc.chunk_word_off, head, out, wave_words, in_words=enc.total_words)
-        self.finish()
-        return s
+        self._open("wave_stats")
+        return self._blocking(self.wave_stats_async, enc.words, enc.chunk_word_off, head, out, wave_words, in_words=enc.total_words)
 
     def decode_window_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start, width: int, offset: int = 0,
                             pad: int = 0, out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None,
@@ -525,8 +506,7 @@ class Plan:
         passed as it is.  out: an int16 tensor that holds (total_waves - 1) * out_stride + width samples (out_stride: samples
         between rows, default width); the samples between rows keep what they held.  wave_words: the encoder's n_i table as
         decode_with_wave_words takes it (no header walk).  Launch only; finish() raises on device-side errors."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "decode_window: the plan is closed")
+        self._open("decode_window")
         width, offset, pad = int(width), int(offset), int(pad)
         if not 0 <= width < 1 << 32:
             raise DeltaRiceError(1, f"width: {width} is not a uint32")
@@ -542,10 +522,7 @@ class Plan:
             sp, ss = start.data_ptr(), (int(start.stride(0)) if self.total_waves > 1 else 1)
         if not -(1 << 63) <= offset < 1 << 63:
             raise DeltaRiceError(1, f"offset: {offset} is not an int64")
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._check_encoded(words, chunk_word_off, wave_words)
         stride = width if out_stride is None else int(out_stride)
         if stride < width:
             raise DeltaRiceError(1, f"out_stride: rows {stride} samples apart do not hold {width}")
@@ -553,31 +530,19 @@ class Plan:
         if out is None:
             out = torch.empty((self.total_waves, width) if stride == width else (need,), dtype=torch.int16, device=self.ctx.device)
         self._dev_check(out, torch.int16, need, "out")
-        n = words.numel() if in_words is None else int(in_words)
-        lib = self.ctx.lib
         if width == 0 or self.total_waves == 0:
             return out
-        if wave_words is None:
-            st = lib.drx_decode_window(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), sp, ss, offset, width, pad,
-                                       out.data_ptr(), stride)
-        else:
-            st = lib.drx_decode_window_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), wave_words.data_ptr(),
-                                                       sp, ss, offset, width, pad, out.data_ptr(), stride)
-        self.ctx._check(st)
+        self._call_encoded("decode_window", words, chunk_word_off, wave_words, in_words, sp, ss, offset, width, pad, out.data_ptr(),
+                           stride)
         return out
 
     def decode_window(self, enc: EncodedBatch, start, width: int, offset: int = 0, pad: int = 0,
                       out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """decode_window_async on an EncodedBatch -> int16 [total_waves, width]; waits, and raises like decode().  The samples
         around every pulse: ``plan.decode_window(enc, stats[:, STAT_ARGMAX], 256, offset=-64)``."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "decode_window: the plan is closed")
-        cur = torch.cuda.current_stream(self.ctx.device)
-        self.ctx.stream.wait_stream(cur)
-        y = self.decode_window_async(enc.words, enc.chunk_word_off, start, width, offset, pad, out, None, wave_words,
-                                     in_words=enc.total_words)
-        self.finish()
-        return y
+        self._open("decode_window")
+        return self._blocking(self.decode_window_async, enc.words, enc.chunk_word_off, start, width, offset, pad, out, None, wave_words,
+                              in_words=enc.total_words)
 
     def find_pulses_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, threshold, polarity: int = 1,
                           min_width: int = 1, max_pulses: int = 4, offset: int = 0, count: Optional[torch.Tensor] = None,
@@ -593,8 +558,7 @@ class Plan:
         count / out: an int32 tensor of total_waves and an int64 tensor of total_waves * max_pulses * PULSE_COLS elements to
         write to.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).  Launch only;
         finish() raises on device-side errors."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "find_pulses: the plan is closed")
+        self._open("find_pulses")
         polarity, min_width, max_pulses, offset = int(polarity), int(min_width), int(max_pulses), int(offset)
         if polarity == 0:
             raise DeltaRiceError(1, "polarity: 0 is neither above nor below")
@@ -612,10 +576,7 @@ class Plan:
             tp, ts = threshold.data_ptr(), (int(threshold.stride(0)) if self.total_waves > 1 else 1)
         if not -(1 << 63) <= offset < 1 << 63:
             raise DeltaRiceError(1, f"offset: {offset} is not an int64")
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._check_encoded(words, chunk_word_off, wave_words)
         W, need = self.total_waves, self.total_waves * max_pulses * _lib.PULSE_COLS
         if count is None:
             count = torch.empty(W, dtype=torch.int32, device=self.ctx.device)
@@ -623,17 +584,8 @@ class Plan:
         if out is None:
             out = torch.empty(need, dtype=torch.int64, device=self.ctx.device)
         self._dev_check(out, torch.int64, need, "out")
-        n = words.numel() if in_words is None else int(in_words)
-        lib = self.ctx.lib
-        op = out.data_ptr() if need else None
-        pol = 1 if polarity > 0 else -1
-        if wave_words is None:
-            st = lib.drx_find_pulses(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), tp, ts, offset, pol, min_width,
-                                     max_pulses, count.data_ptr(), op)
-        else:
-            st = lib.drx_find_pulses_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), wave_words.data_ptr(),
-                                                     tp, ts, offset, pol, min_width, max_pulses, count.data_ptr(), op)
-        self.ctx._check(st)
+        self._call_encoded("find_pulses", words, chunk_word_off, wave_words, in_words, tp, ts, offset, 1 if polarity > 0 else -1,
+                           min_width, max_pulses, count.data_ptr(), out.data_ptr() if need else None)
         return count.view(-1)[:W], out.view(-1)[:need].view(W, max_pulses, _lib.PULSE_COLS)
 
     def find_pulses(self, enc: EncodedBatch, threshold, polarity: int = 1, min_width: int = 1, max_pulses: int = 4,
@@ -641,25 +593,16 @@ class Plan:
                     wave_words: Optional[torch.Tensor] = None):
         """find_pulses_async on an EncodedBatch -> (count, pulses); waits, and raises like decode().  Forty counts above every
         waveform's own baseline: ``plan.find_pulses(enc, stats[:, STAT_HEAD_SUM] // 500, offset=40)``."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "find_pulses: the plan is closed")
-        cur = torch.cuda.current_stream(self.ctx.device)
-        self.ctx.stream.wait_stream(cur)
-        r = self.find_pulses_async(enc.words, enc.chunk_word_off, threshold, polarity, min_width, max_pulses, offset, count, out,
-                                   wave_words, in_words=enc.total_words)
-        self.finish()
-        return r
+        self._open("find_pulses")
+        return self._blocking(self.find_pulses_async, enc.words, enc.chunk_word_off, threshold, polarity, min_width, max_pulses, offset,
+                              count, out, wave_words, in_words=enc.total_words)
 
     def estimate_words_encoded(self, enc: EncodedBatch, wave_words: Optional[torch.Tensor] = None) -> np.ndarray:
         """estimate_words from the encoded stream: entry k is the total words transcode() gives at RiceParameter 2^k, k = 0..15;
         nothing is decoded to memory.  wave_words: the source's n_i table (no header walk).  Waits; raises DRX_ERR_CORRUPT for a
         stream that fails validation."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "estimate_words_encoded: the plan is closed")
-        self._dev_check(enc.words, torch.int32, 1, "words")
-        self._dev_check(enc.chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._open("estimate_words_encoded")
+        self._check_encoded(enc.words, enc.chunk_word_off, wave_words)
         self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
         out = (C.c_uint64 * 16)()
         self.ctx._check(self.ctx.lib.drx_estimate_words_encoded(self._h, enc.words.data_ptr(), int(enc.total_words),
@@ -675,13 +618,9 @@ class Plan:
         ``out_words`` (int32, its numel the capacity).  out_words None: the SIZING call, which writes the two tables only;
         finish() then returns the words needed.  -> (out_words, out_chunk_word_off int64 [n_chunks + 1], out_wave_words int32
         [total_waves]).  finish() raises on device-side errors (DRX_ERR_CAPACITY, DRX_ERR_CORRUPT: nothing was written)."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "transcode: the plan is closed")
+        self._open("transcode")
         k = parse_opts((int(rice_m),)).rice_k
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if wave_words is not None:
-            self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
+        self._check_encoded(words, chunk_word_off, wave_words)
         if out_words is not None:
             self._dev_check(out_words, torch.int32, 0, "out_words")
         if out_chunk_word_off is None:
@@ -690,16 +629,9 @@ class Plan:
         if out_wave_words is None:
             out_wave_words = torch.empty(self.total_waves, dtype=torch.int32, device=self.ctx.device)
         self._dev_check(out_wave_words, torch.int32, self.total_waves, "out_wave_words")
-        n = words.numel() if in_words is None else int(in_words)
         op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
-        lib = self.ctx.lib
-        if wave_words is None:
-            st = lib.drx_transcode(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), k, op, cap,
-                                   out_chunk_word_off.data_ptr(), out_wave_words.data_ptr())
-        else:
-            st = lib.drx_transcode_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(), wave_words.data_ptr(),
-                                                   k, op, cap, out_chunk_word_off.data_ptr(), out_wave_words.data_ptr())
-        self.ctx._check(st)
+        self._call_encoded("transcode", words, chunk_word_off, wave_words, in_words, k, op, cap, out_chunk_word_off.data_ptr(),
+                           out_wave_words.data_ptr())
         return out_words, out_chunk_word_off, out_wave_words
 
     def transcode(self, enc: EncodedBatch, rice_m: Optional[int] = None, wave_words: Optional[torch.Tensor] = None,
@@ -710,8 +642,7 @@ class Plan:
         sized by a first call and allocated exactly -- that costs a second sizes pass, so a caller that has a bound (the
         plan's max_encoded_words bounds any result) should pass out_words; otherwise DRX_ERR_CAPACITY if the result does not
         fit it.  Waits, and raises like decode()."""
-        if not getattr(self, "_h", None):
-            raise DeltaRiceError(1, "transcode: the plan is closed")
+        self._open("transcode")
         if rice_m is None:
             rice_m = 1 << int(np.argmin(self.estimate_words_encoded(enc, wave_words)))  # (argmin: the first of equals)
         self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))

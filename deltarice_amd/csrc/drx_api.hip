@@ -728,44 +728,60 @@ static drx_status route_scratch(drx_plan *p, const EncodeRoute &R) {
     return DRX_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Every call that launches opens with call_begin(), on the context's device: the resume key dropped (a no-op for the selection
+// calls, which drop it earlier -- before the early returns their argument checks leave them), the plan's status word cleared on
+// the stream, the debug flags copied.  The frame a call hands its launchers (drx_internal.h) is built from the plan behind it:
+// stream_call_begin() for the calls on an encoded batch, whose side-band form (d_sideband: the WHOLE batch's table) gets its
+// header tables here.  call_end(): what the plan remembers of its last call.
+// ---------------------------------------------------------------------------
+static drx_status call_begin(drx_plan *p) {
+    drx_ctx *ctx = p->ctx;
+    p->gat_last.valid = false;
+    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
+    p->G.dbg = ctx->debug_flags;
+    return DRX_OK;
+}
+static drx_status stream_call_begin(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                    const uint32_t *d_sideband, bool tables_ready, StreamCall *c) {
+    drx_ctx *ctx = p->ctx;
+    if (const drx_status st = call_begin(p)) return st;
+    // (d_pw was allocated with the plan; a plan whose filter was set to general taps afterwards simply does not take those paths)
+    *c = StreamCall{&p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, tables_ready || d_sideband, p->d_pw,
+                    p->d_status, ctx->profile ? p->ev : nullptr, ctx->stream};
+    if (d_sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
+        DRX_HIP(ctx, launch_sideband_tables(*c, d_sideband));
+    return DRX_OK;
+}
+static drx_status call_end(drx_plan *p, uint32_t path, bool encode = false) {
+    (encode ? p->last_enc_path : p->last_path) = path;
+    p->ev_valid = p->ctx->profile != 0;
+    p->last_was_encode = encode;
+    return DRX_OK;
+}
+
 drx_status drx_encode(drx_plan *p, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap_words,
                       uint64_t *d_chunk_word_off) {
     if (!p || !d_in || !d_out || !d_chunk_word_off) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
     DRX_ON_DEVICE(ctx);
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
+    if (const drx_status st = call_begin(p)) return st;
     // what the plan's last encode measured decides this one's kernel -- read from the word the encoders write to pinned host
     // memory, so that callers that never wait for an encode (bench.py's steps) are covered without a copy or an event
     if (const uint64_t w = *(volatile uint64_t *)p->G.host_words) p->enc_words_per_wave = p->G.total_waves ? w / p->G.total_waves : 0;
     const EncodeRoute R = route_encode(p, ctx->encode_impl, ctx->debug_flags);
     if (const drx_status st = route_scratch(p, R)) return st;
-    hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
+    const EncodeCall c{&p->G, d_in, EncOut{d_out, out_cap_words, d_chunk_word_off, p->d_wave_words}, p->d_status,
+                       ctx->profile ? p->ev : nullptr, ctx->stream};
     switch (R.enc) {
-    case DRX_ENC_STREAM_SEGS:
-        DRX_HIP(ctx, launch_encode_stream_segs(p->G, R.seg_target, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                               p->d_scan, p->d_status, ev, ctx->stream)); break;
-    case DRX_ENC_PIECES:
-        DRX_HIP(ctx, launch_encode_pieces(p->G, d_in, p->G.total_samples, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                          p->d_pc_scan, p->pc_wgs, p->d_status, ev, ctx->stream)); break;
-    case DRX_ENC_SEGMENTS:
-        DRX_HIP(ctx, launch_encode_long(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words, p->d_wave_rel,
-                                        p->d_chunk_words, p->d_seg_bits, p->d_seg_pos, p->d_status, ev, ctx->stream)); break;
-    case DRX_ENC_STREAM:
-        DRX_HIP(ctx, launch_encode_stream(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                          p->d_scan, p->d_status, ev, ctx->stream)); break;
-    case DRX_ENC_FUSED:
-        DRX_HIP(ctx, launch_encode_fused(p->G, R.wide, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                         p->d_scan, p->d_status, ev, ctx->stream)); break;
-    default:
-        DRX_HIP(ctx, launch_encode(p->G, d_in, d_out, out_cap_words, d_chunk_word_off, p->d_wave_words,
-                                   p->d_wave_rel, p->d_chunk_words, p->d_status, ev, ctx->stream));
+    case DRX_ENC_STREAM_SEGS: DRX_HIP(ctx, launch_encode_stream_segs(c, R.seg_target, p->d_scan)); break;
+    case DRX_ENC_PIECES: DRX_HIP(ctx, launch_encode_pieces(c, p->G.total_samples, p->d_pc_scan, p->pc_wgs)); break;
+    case DRX_ENC_SEGMENTS: DRX_HIP(ctx, launch_encode_long(c, p->d_wave_rel, p->d_chunk_words, p->d_seg_bits, p->d_seg_pos)); break;
+    case DRX_ENC_STREAM: DRX_HIP(ctx, launch_encode_stream(c, p->d_scan)); break;
+    case DRX_ENC_FUSED: DRX_HIP(ctx, launch_encode_fused(c, R.wide, p->d_scan)); break;
+    default: DRX_HIP(ctx, launch_encode(c, p->d_wave_rel, p->d_chunk_words));
     }
-    p->last_enc_path = R.enc;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = true;
-    return DRX_OK;
+    return call_end(p, R.enc, /*encode*/ true);
 }
 
 static drx_status decode_launch(drx_plan *p, const uint32_t *d_in, uint64_t in_words,
@@ -774,25 +790,13 @@ static drx_status decode_launch(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     if (!p || !d_in || !d_chunk_word_off || !d_out) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
     DRX_ON_DEVICE(ctx);
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
     // (in_words says nothing about how long a waveform's code is -- it may be, and in bench.py IS, the buffer's capacity; round 4
     // took it for the stream's length for a while and sent the headline batch to k_encode_fused)
-    if (d_sideband) {  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
-        tables_ready = true;
-    }
-    // (d_pw / d_blk were allocated with the plan; a plan whose filter was set to general taps afterwards simply does
-    // not take those paths)
-    DRX_HIP(ctx, launch_decode(p->G, d_in, in_words, d_chunk_word_off, d_out, p->d_wave_off,
-                               p->d_wave_words, p->d_scan, p->d_status,
-                               ctx->decode_impl, tables_ready, p->d_pw, p->d_blk, ctx->side.s ? &ctx->side : nullptr,
-                               ctx->profile ? p->ev : nullptr, ctx->stream, &p->last_path));
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, tables_ready, &c)) return st;
+    // (d_blk was allocated with the plan, like d_pw)
+    DRX_HIP(ctx, launch_decode(c, d_out, p->d_scan, ctx->decode_impl, p->d_blk, ctx->side.s ? &ctx->side : nullptr, &p->last_path));
+    return call_end(p, p->last_path);
 }
 
 drx_status drx_decode(drx_plan *p, const uint32_t *d_in, uint64_t in_words,
@@ -834,6 +838,60 @@ static drx_status sel_scratch(drx_plan *p, size_t bytes) {
     return DRX_OK;
 }
 
+// The gather's device-only scratch beside the selection's (gather_scratch_view(), drx_internal.h); grown like the selection's.
+static drx_status gather_scratch(drx_plan *p, size_t bytes) {
+    drx_ctx *ctx = p->ctx;
+    if (p->gat_cap >= bytes) return DRX_OK;
+    const size_t want = bytes + bytes / 4 + 4096;
+    void *d = nullptr;
+    const hipError_t e = p->mem.alloc(&d, want);
+    if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "gather scratch of %zu bytes: %s", want, hipGetErrorString(e));
+    DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier gather may still use the old one)
+    p->mem.release(p->d_gat);
+    p->d_gat = d;
+    p->gat_cap = want;
+    return DRX_OK;
+}
+
+// The front end of both selection calls.  The staging buffer: uint64 sel[n_sel] | uint32 chunk_n[n_out] (the gather's output
+// chunks; decode_select has none) | uint32 chunk lists[touched]; sel_staged() is its device copy's view.  sel_stage() grows the
+// scratch (gather_bytes != 0: the gather's too), waits until the last call's copy has left the staging buffer, fills it and sends
+// it across.  sel_walk(): the walk over the chunks the selection touches, between the call's events 0 and 1.
+struct SelStaged {
+    const uint64_t *d_sel;
+    const uint32_t *d_chunk_n, *d_lists;
+};
+static SelStaged sel_staged(const drx_plan *p, uint64_t n_sel, uint64_t n_out) {
+    const uint32_t *d_chunk_n = (const uint32_t *)((const char *)p->d_sel + n_sel * sizeof(uint64_t));
+    return SelStaged{(const uint64_t *)p->d_sel, d_chunk_n, d_chunk_n + n_out};
+}
+static drx_status sel_stage(drx_plan *p, const uint64_t *wave_idx, uint64_t n_sel, const std::vector<uint32_t> &chunk_n,
+                            const std::vector<uint32_t> &lists, size_t gather_bytes) {
+    drx_ctx *ctx = p->ctx;
+    const size_t sel_bytes = n_sel * sizeof(uint64_t), cn_bytes = chunk_n.size() * sizeof(uint32_t), ls_bytes = lists.size() * sizeof(uint32_t);
+    if (const drx_status st = sel_scratch(p, sel_bytes + cn_bytes + ls_bytes)) return st;
+    if (gather_bytes)
+        if (const drx_status st = gather_scratch(p, gather_bytes)) return st;
+    DRX_HIP(ctx, hipEventSynchronize(p->sel_copied));  // (the last call's copy out of the staging buffer)
+    memcpy(p->h_sel, wave_idx, sel_bytes);
+    if (cn_bytes) memcpy((char *)p->h_sel + sel_bytes, chunk_n.data(), cn_bytes);
+    memcpy((char *)p->h_sel + sel_bytes + cn_bytes, lists.data(), ls_bytes);
+    DRX_HIP(ctx, hipMemcpyAsync(p->d_sel, p->h_sel, sel_bytes + cn_bytes + ls_bytes, hipMemcpyHostToDevice, ctx->stream));
+    DRX_HIP(ctx, hipEventRecord(p->sel_copied, ctx->stream));
+    return DRX_OK;
+}
+static drx_status sel_walk(drx_plan *p, const StreamCall &c, const uint32_t *d_sideband, const uint32_t *d_lists, size_t n_lists,
+                           const uint32_t n_class[3]) {
+    drx_ctx *ctx = p->ctx;
+    mark(c.ev, 0, c.s);
+    if (d_sideband)
+        DRX_HIP(ctx, launch_sideband_tables(c, d_sideband, d_lists, (uint32_t)n_lists));
+    else
+        DRX_HIP(ctx, launch_select_walk(c, d_lists, n_class[0], n_class[1], n_class[2], p->d_sel_fail));
+    mark(c.ev, 1, c.s);
+    return DRX_OK;
+}
+
 static drx_status decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                 const uint32_t *d_sideband, bool sideband, const uint64_t *wave_idx, uint64_t n_sel,
                                 int16_t *d_out, uint64_t stride) {
@@ -843,7 +901,6 @@ static drx_status decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     if (!d_in || !d_chunk_word_off || !wave_idx || !d_out || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "decode_select: null pointer");
     if (sideband && d_sideband == p->d_wave_words) return fail(ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
     if (n_sel >= (1ull << 32)) return fail(ctx, DRX_ERR_ARG, "decode_select: %llu entries (at most 2^32 - 1)", (unsigned long long)n_sel);
-    const Geom &G = p->G;
     uint32_t longest = 0;
     uint32_t n_class[3];
     std::vector<uint32_t> lists;
@@ -855,33 +912,15 @@ static drx_status decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     p->gat_last.valid = false;
     if (stride < longest) return fail(ctx, DRX_ERR_ARG, "decode_select: row stride %llu below the longest selected waveform (%u)", (unsigned long long)stride, longest);
     DRX_ON_DEVICE(ctx);
-    const size_t sel_bytes = n_sel * sizeof(uint64_t), bytes = sel_bytes + lists.size() * sizeof(uint32_t);
-    if (const drx_status st = sel_scratch(p, bytes)) return st;
-    DRX_HIP(ctx, hipEventSynchronize(p->sel_copied));  // (the last call's copy out of the staging buffer)
-    memcpy(p->h_sel, wave_idx, sel_bytes);
-    memcpy((char *)p->h_sel + sel_bytes, lists.data(), lists.size() * sizeof(uint32_t));
-    DRX_HIP(ctx, hipMemcpyAsync(p->d_sel, p->h_sel, bytes, hipMemcpyHostToDevice, ctx->stream));
-    DRX_HIP(ctx, hipEventRecord(p->sel_copied, ctx->stream));
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
-    const uint64_t *d_sel = (const uint64_t *)p->d_sel;
-    const uint32_t *d_lists = (const uint32_t *)((const char *)p->d_sel + sel_bytes);
-    mark(ev, 0, ctx->stream);
-    if (sideband)
-        DRX_HIP(ctx, launch_sideband_tables(G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words, p->d_status,
-                                            ctx->stream, d_lists, (uint32_t)lists.size()));
-    else
-        DRX_HIP(ctx, launch_select_walk(G, d_in, in_words, d_chunk_word_off, d_lists, n_class[0], n_class[1], n_class[2], p->d_sel_fail,
-                                        p->d_wave_off, p->d_wave_words, p->d_status, ctx->stream));
-    mark(ev, 1, ctx->stream);
-    DRX_HIP(ctx, launch_decode_select(G, d_in, p->d_wave_off, p->d_wave_words, d_sel, n_sel, p->d_status, d_out, stride, ctx->stream));
-    mark(ev, 2, ctx->stream);
-    mark(ev, 3, ctx->stream);
-    p->last_path = DRX_PATH_SELECT;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    if (const drx_status st = sel_stage(p, wave_idx, n_sel, {}, lists, 0)) return st;
+    const SelStaged S = sel_staged(p, n_sel, 0);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, nullptr, false, &c)) return st;
+    if (const drx_status st = sel_walk(p, c, sideband ? d_sideband : nullptr, S.d_lists, lists.size(), n_class)) return st;
+    DRX_HIP(ctx, launch_decode_select(c, S.d_sel, n_sel, d_out, stride));
+    mark(c.ev, 2, c.s);
+    mark(c.ev, 3, c.s);
+    return call_end(p, DRX_PATH_SELECT);
 }
 
 drx_status drx_decode_select(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -902,22 +941,6 @@ drx_status drx_decode_select_with_wave_words(drx_plan *p, const uint32_t *d_in, 
 // ---------------------------------------------------------------------------
 // selected waveforms into a new encoded batch (drx_gather.hip)
 // ---------------------------------------------------------------------------
-// The gather's device-only scratch beside the selection's: uint64 ent_pos[n_sel] | uint64 block_sum[blocks + 2] | uint32
-// ent_words[n_sel] | uint32 ctrl[1]; grown like the selection's.
-static drx_status gather_scratch(drx_plan *p, size_t bytes) {
-    drx_ctx *ctx = p->ctx;
-    if (p->gat_cap >= bytes) return DRX_OK;
-    const size_t want = bytes + bytes / 4 + 4096;
-    void *d = nullptr;
-    const hipError_t e = p->mem.alloc(&d, want);
-    if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "gather scratch of %zu bytes: %s", want, hipGetErrorString(e));
-    DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier gather may still use the old one)
-    p->mem.release(p->d_gat);
-    p->d_gat = d;
-    p->gat_cap = want;
-    return DRX_OK;
-}
-
 // mean words per entry from which the copy is a wavefront per entry; below, a workgroup per run of entries
 constexpr uint64_t kGatherWavesFromWords = 192;
 
@@ -934,8 +957,8 @@ static drx_status gather_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_
         return fail(ctx, DRX_ERR_ARG, "the side-band table must be neither the plan's own nor the output's (copy it first)");
     if (n_sel >= (1ull << 32)) return fail(ctx, DRX_ERR_ARG, "gather_encoded: %llu entries (at most 2^32 - 1)", (unsigned long long)n_sel);
     const Geom &G = p->G;
-    const uint64_t n_out = (n_sel + cw - 1) / cw, blocks = gather_scan_blocks(n_sel);
-    const size_t sel_bytes = n_sel * sizeof(uint64_t), cn_bytes = n_out * sizeof(uint32_t);
+    const uint64_t n_out = (n_sel + cw - 1) / cw;
+    const EncOut out{d_out, out_cap, d_out_off, d_out_wave_words};
     // the copy's form by the batch's mean code length (in_words may be a capacity: a speed matter only, like the grid's shape)
     const uint64_t mean_words = in_words / G.total_waves;
     const bool tiles = (mean_words < kGatherWavesFromWords) != ((ctx->debug_flags & DRX_DBG_GATHER_OTHER_COPY) != 0);
@@ -945,22 +968,16 @@ static drx_status gather_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_
     const drx_plan::GatherKey K = p->gat_last;
     p->gat_last.valid = false;
     if (K.valid && d_out && K.d_in == d_in && K.in_words == in_words && K.d_off == d_chunk_word_off && K.d_sideband == (sideband ? d_sideband : nullptr) &&
-        K.n_sel == n_sel && K.cw == cw && memcmp(p->h_sel, wave_idx, sel_bytes) == 0) {
+        K.n_sel == n_sel && K.cw == cw && memcmp(p->h_sel, wave_idx, n_sel * sizeof(uint64_t)) == 0) {
         DRX_ON_DEVICE(ctx);
-        DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-        hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
-        uint64_t *d_ent_pos = (uint64_t *)p->d_gat, *d_block_sum = d_ent_pos + n_sel;
-        uint32_t *d_ent_words = (uint32_t *)(d_block_sum + blocks + 2), *d_ctrl = d_ent_words + n_sel;
-        mark(ev, 0, ctx->stream);
-        mark(ev, 1, ctx->stream);
-        DRX_HIP(ctx, launch_gather(G, d_in, p->d_wave_off, p->d_wave_words, (const uint64_t *)p->d_sel, n_sel, cw,
-                                   (const uint32_t *)((const char *)p->d_sel + sel_bytes), d_out, out_cap, d_out_off, d_out_wave_words, d_ent_words,
-                                   d_ent_pos, d_block_sum, d_ctrl, tiles, mean_words, /*resume*/ true, p->d_status, ev, ctx->stream));
-        mark(ev, 3, ctx->stream);
-        p->last_path = DRX_PATH_GATHER;
-        p->ev_valid = ctx->profile != 0;
-        p->last_was_encode = false;
-        return DRX_OK;
+        StreamCall c;
+        if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, nullptr, true, &c)) return st;
+        const SelStaged S = sel_staged(p, n_sel, n_out);
+        mark(c.ev, 0, c.s);
+        mark(c.ev, 1, c.s);
+        DRX_HIP(ctx, launch_gather(c, S.d_sel, n_sel, cw, S.d_chunk_n, out, gather_scratch_view(p->d_gat, n_sel), tiles, mean_words, /*resume*/ true));
+        mark(c.ev, 3, c.s);
+        return call_end(p, DRX_PATH_GATHER);
     }
     // every output chunk is a chunk under ONE WaveformLength (its first entry's; only its last entry may be shorter) of fewer
     // than 2^31 samples (src/deltaRice.c:389); chunk_n[c] = its sample count N_c
@@ -988,44 +1005,17 @@ static drx_status gather_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_
         }))
         return st;
     DRX_ON_DEVICE(ctx);
-    // staging: uint64 sel[n_sel] | uint32 chunk_n[n_out] | uint32 chunk lists[touched]
-    const size_t bytes = sel_bytes + cn_bytes + lists.size() * sizeof(uint32_t);
-    if (const drx_status st = sel_scratch(p, bytes)) return st;
-    const size_t pos_bytes = n_sel * sizeof(uint64_t), bs_bytes = blocks * sizeof(uint64_t), ew_bytes = n_sel * sizeof(uint32_t);
-    if (const drx_status st = gather_scratch(p, pos_bytes + bs_bytes + 2 * sizeof(uint64_t) + ew_bytes + sizeof(uint32_t))) return st;
-    DRX_HIP(ctx, hipEventSynchronize(p->sel_copied));  // (the last call's copy out of the staging buffer)
-    memcpy(p->h_sel, wave_idx, sel_bytes);
-    memcpy((char *)p->h_sel + sel_bytes, chunk_n.data(), cn_bytes);
-    memcpy((char *)p->h_sel + sel_bytes + cn_bytes, lists.data(), lists.size() * sizeof(uint32_t));
-    DRX_HIP(ctx, hipMemcpyAsync(p->d_sel, p->h_sel, bytes, hipMemcpyHostToDevice, ctx->stream));
-    DRX_HIP(ctx, hipEventRecord(p->sel_copied, ctx->stream));
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    hipEvent_t *ev = ctx->profile ? p->ev : nullptr;
-    const uint64_t *d_sel = (const uint64_t *)p->d_sel;
-    const uint32_t *d_chunk_n = (const uint32_t *)((const char *)p->d_sel + sel_bytes);
-    const uint32_t *d_lists = d_chunk_n + n_out;
-    uint64_t *d_ent_pos = (uint64_t *)p->d_gat, *d_block_sum = d_ent_pos + n_sel;
-    uint32_t *d_ent_words = (uint32_t *)(d_block_sum + blocks + 2), *d_ctrl = d_ent_words + n_sel;  // (block_sum[blocks .. +2): total, status)
-    mark(ev, 0, ctx->stream);
-    if (sideband)
-        DRX_HIP(ctx, launch_sideband_tables(G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words, p->d_status,
-                                            ctx->stream, d_lists, (uint32_t)lists.size()));
-    else
-        DRX_HIP(ctx, launch_select_walk(G, d_in, in_words, d_chunk_word_off, d_lists, n_class[0], n_class[1], n_class[2], p->d_sel_fail,
-                                        p->d_wave_off, p->d_wave_words, p->d_status, ctx->stream));
-    mark(ev, 1, ctx->stream);
-    DRX_HIP(ctx, launch_gather(G, d_in, p->d_wave_off, p->d_wave_words, d_sel, n_sel, cw, d_chunk_n, d_out, out_cap, d_out_off,
-                               d_out_wave_words, d_ent_words, d_ent_pos, d_block_sum, d_ctrl, tiles, mean_words, /*resume*/ false, p->d_status, ev,
-                               ctx->stream));
-    mark(ev, 3, ctx->stream);
+    if (const drx_status st = sel_stage(p, wave_idx, n_sel, chunk_n, lists, gather_scratch_view(nullptr, n_sel).bytes)) return st;
+    const SelStaged S = sel_staged(p, n_sel, n_out);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, nullptr, false, &c)) return st;
+    if (const drx_status st = sel_walk(p, c, sideband ? d_sideband : nullptr, S.d_lists, lists.size(), n_class)) return st;
+    DRX_HIP(ctx, launch_gather(c, S.d_sel, n_sel, cw, S.d_chunk_n, out, gather_scratch_view(p->d_gat, n_sel), tiles, mean_words, /*resume*/ false));
+    mark(c.ev, 3, c.s);
     p->gat_last.valid = d_out == nullptr;
     p->gat_last.d_in = d_in; p->gat_last.in_words = in_words; p->gat_last.d_off = d_chunk_word_off;
     p->gat_last.d_sideband = sideband ? d_sideband : nullptr; p->gat_last.n_sel = n_sel; p->gat_last.cw = cw;
-    p->last_path = DRX_PATH_GATHER;
-    p->ev_valid = ctx->profile != 0;
-    p->last_was_encode = false;
-    return DRX_OK;
+    return call_end(p, DRX_PATH_GATHER);
 }
 
 drx_status drx_gather_encoded(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -1049,31 +1039,12 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *p, const uint32_t *d_in,
 
 // ---------------------------------------------------------------------------
 // The calls that read the whole batch from the encoded stream without decoding it -- wave_stats, decode_window, find_pulses,
-// transcode, estimate_words_encoded -- share their first and last steps.  stream_call_args(): the pointers every one of them
-// takes (have_pointers: the caller's own included; who: its name in the message).  stream_call_begin(), on the context's device:
-// the plan's status word, debug flags and, for the side-band form, the header tables.  stream_call_end(): what the plan
-// remembers of its last call.
+// transcode, estimate_words_encoded -- open with stream_call_begin() and close with call_end() (above).  stream_call_args(): the
+// pointers every one of them takes (have_pointers: the caller's own included; who: its name in the message).
 // ---------------------------------------------------------------------------
 static drx_status stream_call_args(drx_plan *p, const char *who, bool have_pointers, const uint32_t *d_sideband, bool sideband) {
     if (!have_pointers || (sideband && !d_sideband)) return fail(p->ctx, DRX_ERR_ARG, "%s: null pointer", who);
     if (sideband && d_sideband == p->d_wave_words) return fail(p->ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
-    return DRX_OK;
-}
-static drx_status stream_call_begin(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                    const uint32_t *d_sideband, bool sideband) {
-    drx_ctx *ctx = p->ctx;
-    p->gat_last.valid = false;
-    DRX_HIP(ctx, hipMemsetAsync(p->d_status, 0, sizeof(DevStatus), ctx->stream));
-    p->G.dbg = ctx->debug_flags;
-    if (sideband)  // header positions from the caller's n_i table, checked against the stream (k_sideband_tables)
-        DRX_HIP(ctx, launch_sideband_tables(p->G, d_in, in_words, d_chunk_word_off, d_sideband, p->d_wave_off, p->d_wave_words,
-                                            p->d_status, ctx->stream));
-    return DRX_OK;
-}
-static drx_status stream_call_end(drx_plan *p, uint32_t path) {
-    p->last_path = path;
-    p->ev_valid = p->ctx->profile != 0;
-    p->last_was_encode = false;
     return DRX_OK;
 }
 
@@ -1086,12 +1057,12 @@ static drx_status wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_word
     drx_ctx *ctx = p->ctx;
     if (const drx_status st = stream_call_args(p, "wave_stats", d_in && d_chunk_word_off && d_out, d_sideband, sideband)) return st;
     DRX_ON_DEVICE(ctx);
-    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
     // the block form's accumulators and list belong to the plan: allocated by its first call that takes that form
     if (!p->d_sacc && stats_blocks_batch(p->G, p->d_blk)) DRX_HIP(ctx, p->mem.alloc(&p->d_sacc, stats_blocks_scratch_bytes(p->G)));
-    DRX_HIP(ctx, launch_wave_stats(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, p->d_blk,
-                                   p->d_sacc, head_len, p->d_status, d_out, ctx->profile ? p->ev : nullptr, ctx->stream, &p->last_stats_form));
-    return stream_call_end(p, DRX_PATH_STATS);
+    DRX_HIP(ctx, launch_wave_stats(c, p->d_blk, p->d_sacc, head_len, d_out, &p->last_stats_form));
+    return call_end(p, DRX_PATH_STATS);
 }
 
 drx_status drx_wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t head_len,
@@ -1118,11 +1089,10 @@ static drx_status decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     if (d_start && start_stride == 0) return fail(ctx, DRX_ERR_ARG, "decode_window: start_stride 0");
     if (width == 0) return DRX_OK;  // (no row receives a sample: nothing to launch)
     DRX_ON_DEVICE(ctx);
-    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
-    DRX_HIP(ctx, launch_decode_window(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, d_start,
-                                      start_stride, offset, width, pad, p->d_status, d_out, out_stride, ctx->profile ? p->ev : nullptr,
-                                      ctx->stream));
-    return stream_call_end(p, DRX_PATH_WINDOW);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    DRX_HIP(ctx, launch_decode_window(c, d_start, start_stride, offset, width, pad, d_out, out_stride));
+    return call_end(p, DRX_PATH_WINDOW);
 }
 
 drx_status drx_decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -1154,11 +1124,10 @@ static drx_status find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_wor
     if (min_width == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: min_width 0");
     if (d_thr && thr_stride == 0) return fail(ctx, DRX_ERR_ARG, "find_pulses: thr_stride 0");
     DRX_ON_DEVICE(ctx);
-    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
-    DRX_HIP(ctx, launch_find_pulses(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, d_thr,
-                                    thr_stride, thr, polarity < 0, min_width, max_pulses, p->d_status, d_count, d_out,
-                                    ctx->profile ? p->ev : nullptr, ctx->stream));
-    return stream_call_end(p, DRX_PATH_PULSES);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    DRX_HIP(ctx, launch_find_pulses(c, d_thr, thr_stride, thr, polarity < 0, min_width, max_pulses, d_count, d_out));
+    return call_end(p, DRX_PATH_PULSES);
 }
 
 drx_status drx_find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
@@ -1179,22 +1148,12 @@ drx_status drx_find_pulses_with_wave_words(drx_plan *p, const uint32_t *d_in, ui
 // ---------------------------------------------------------------------------
 // re-coding to another RiceParameter, and the sizes at every one, from the encoded stream (drx_transcode.hip)
 // ---------------------------------------------------------------------------
-struct TrcScratch {
-    uint64_t *chunk_words;
-    unsigned long long *est;
-    uint32_t *words, *rel;
-};
-static drx_status trc_scratch(drx_plan *p, TrcScratch *t) {
-    drx_ctx *ctx = p->ctx;
-    const uint64_t W = p->G.total_waves ? p->G.total_waves : 1, C = p->G.n_chunks + 1;
+static drx_status trc_scratch(drx_plan *p, TrcScratch *t) {  // (trc_scratch_view(), drx_internal.h; allocated by the first such call)
     if (!p->d_trc) {
-        const hipError_t e = p->mem.alloc(&p->d_trc, (C + 16) * sizeof(uint64_t) + 2 * W * sizeof(uint32_t));
-        if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "transcode scratch: %s", hipGetErrorString(e));
+        const hipError_t e = p->mem.alloc(&p->d_trc, trc_scratch_view(p->G, nullptr).bytes);
+        if (e != hipSuccess) return fail(p->ctx, DRX_ERR_NOMEM, "transcode scratch: %s", hipGetErrorString(e));
     }
-    t->chunk_words = (uint64_t *)p->d_trc;
-    t->est = (unsigned long long *)(t->chunk_words + C);
-    t->words = (uint32_t *)(t->est + 16);
-    t->rel = t->words + W;
+    *t = trc_scratch_view(p->G, p->d_trc);
     return DRX_OK;
 }
 
@@ -1211,11 +1170,10 @@ static drx_status transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words
     DRX_ON_DEVICE(ctx);
     TrcScratch t;
     if (const drx_status st = trc_scratch(p, &t)) return st;
-    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, sideband)) return st;
-    DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw, new_k,
-                                  t.words, t.rel, t.chunk_words, d_out, out_cap, d_out_off, d_out_wave_words, nullptr, p->d_status,
-                                  ctx->profile ? p->ev : nullptr, ctx->stream));
-    return stream_call_end(p, DRX_PATH_TRANSCODE);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    DRX_HIP(ctx, launch_transcode(c, new_k, t, EncOut{d_out, out_cap, d_out_off, d_out_wave_words}));
+    return call_end(p, DRX_PATH_TRANSCODE);
 }
 
 drx_status drx_transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t new_rice_k,
@@ -1240,11 +1198,10 @@ drx_status drx_estimate_words_encoded(drx_plan *p, const uint32_t *d_in, uint64_
     DRX_ON_DEVICE(ctx);
     TrcScratch t;
     if (const drx_status st = trc_scratch(p, &t)) return st;
-    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_wave_words, sideband)) return st;
-    DRX_HIP(ctx, launch_transcode(p->G, d_in, in_words, d_chunk_word_off, p->d_wave_off, p->d_wave_words, sideband, p->d_pw,
-                                  0u, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, t.est, p->d_status,
-                                  ctx->profile ? p->ev : nullptr, ctx->stream));
-    (void)stream_call_end(p, DRX_PATH_TRANSCODE);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_wave_words, false, &c)) return st;
+    DRX_HIP(ctx, launch_estimate_words_encoded(c, t.est));
+    (void)call_end(p, DRX_PATH_TRANSCODE);
     DRX_HIP(ctx, hipMemcpyAsync(words_out, t.est, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     return drx_plan_finish(p, nullptr);  // (waits; a stream that failed validation: DRX_ERR_CORRUPT, words_out undefined)
 }

@@ -264,14 +264,15 @@ hipError_t blocks_prepare(const Geom &G, uint64_t in_words, const uint32_t *d_wa
     return hipGetLastError();
 }
 
-hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
-                                const uint32_t *d_wave_words, void *d_blk, DevStatus *d_status, int16_t *d_out,
-                                const uint32_t **fail_out, const uint32_t **suspect_out, bool resid, hipStream_t s, bool *fused_out) {
+hipError_t launch_decode_blocks(const StreamCall &call, void *d_blk, int16_t *d_out, const uint32_t **fail_out,
+                                const uint32_t **suspect_out, bool resid, bool *fused_out) {
+    const Geom &G = *call.G;
+    const hipStream_t s = call.s;
     const BlkScratch L = blocks_layout(G, d_blk);
     hipError_t e = hipMemsetAsync(d_blk, 0, L.bytes, s);
     if (e != hipSuccess) return e;
     const uint32_t spw = blocks_slots_per_wave(G);
-    const uint64_t b10 = blk_bits10(G, in_words);
+    const uint64_t b10 = blk_bits10(G, call.in_words);
     const int sw = blk_segw_bits10(b10);
     // General filters: the inverse filter inside this kernel (FUSE) where its state can pass from a run's last block to the next
     // run's first without a chain of waits, i.e. where every launch has at least as many waveforms as resident workgroups (the
@@ -290,7 +291,7 @@ hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in
     if (fused_out) *fused_out = fuse;
     auto launch_class = [&](uint32_t cls, const uint32_t *list, uint32_t n_waves, int nt, uint32_t wave_len) {
         if (resid) nt = fuse ? nt_gen(nt) : 256;
-        const BlkClassLaunch c = blk_class_launch(L, cls, list, n_waves, nt, wave_len, sw, b10, spw, d_wave_words, s);
+        const BlkClassLaunch c = blk_class_launch(L, cls, list, n_waves, nt, wave_len, sw, b10, spw, call.d_wave_words, s);
         uint32_t *const info = c.info;
         const uint32_t run_len = c.run_len;
         auto go = [&](auto nt_tag, auto resid_tag, auto sw_tag) {
@@ -299,8 +300,8 @@ hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in
             const unsigned grid = c.grid;
             // the filter's tables for runs of this geometry's lane share (76 / 68 / 60 samples)
             const uint32_t *itab = G.blk_iir_tab ? G.blk_iir_tab + kRunTabWords * (blk_lane_cap(SW) == 76u ? 0u : (blk_lane_cap(SW) == 68u ? 1u : 2u)) : nullptr;
-            k_decode_blocks<NT, MODE != 0, SW, MODE == 2><<<grid, NT, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, info, spw, run_len, L.state, L.ends,
-                                                                             info + 2, L.fail, L.suspect, d_status, d_out, n_waves, itab, L.xstate, list);
+            k_decode_blocks<NT, MODE != 0, SW, MODE == 2><<<grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, info, spw, run_len,
+                                                                             L.state, L.ends, info + 2, L.fail, L.suspect, call.d_status, d_out, n_waves, itab, L.xstate, list);
         };
         auto by_sw = [&](auto nt_tag, auto resid_tag) {
             switch (sw) {

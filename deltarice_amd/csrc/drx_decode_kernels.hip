@@ -807,26 +807,26 @@ static DecodeRoute route_decode(const Geom &G, int impl, bool tables_ready, bool
     return R;
 }
 
-hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
-                         const uint64_t *d_chunk_word_off, int16_t *d_out, uint64_t *d_wave_off,
-                         uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl, bool tables_ready,
-                         void *d_pw, void *d_blk, const SideStream *side, hipEvent_t *ev, hipStream_t s, uint32_t *path_out) {
+hipError_t launch_decode(const StreamCall &c, int16_t *d_out, uint64_t *d_granules, int impl, void *d_blk, const SideStream *side,
+                         uint32_t *path_out) {
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
     uint32_t path_dummy = 0;
     uint32_t &path = path_out ? *path_out : path_dummy;
     path = 0;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
-    const DecodeRoute R = route_decode(G, impl, tables_ready, d_pw != nullptr, d_blk != nullptr, side && side->s);
+    mark(c.ev, 0, s);
+    const DecodeRoute R = route_decode(G, impl, c.tables_ready, c.d_pw != nullptr, d_blk != nullptr, side && side->s);
     const bool gen = R.gen;
     const unsigned nb_plain = blocks_for(G.total_waves, 64);
 
-    // the lane-per-waveform launch behind a walk (tables in wave_off / wave_words): `nb` wavefronts of view Gv
-    auto launch_lanes = [&](const Geom &Gv, unsigned nb, hipStream_t st_) {
+    // the lane-per-waveform launch behind a walk (tables in wave_off / wave_words): `nb` wavefronts of the frame's view and stream
+    auto launch_lanes = [&](const StreamCall &v, unsigned nb) {
         path |= DRX_PATH_LANES;
         if (gen)
-            k_decode_lanes<false, true><<<nb, 64, 0, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
+            k_decode_lanes<false, true><<<nb, 64, 0, v.s>>>(*v.G, v.d_in, v.in_words, v.d_chunk_word_off, v.d_wave_off, v.d_wave_words, nullptr, nullptr, v.d_status, d_out);
         else
-            k_decode_lanes<false><<<nb, 64, 0, st_>>>(Gv, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, nullptr, nullptr, d_status, d_out);
+            k_decode_lanes<false><<<nb, 64, 0, v.s>>>(*v.G, v.d_in, v.in_words, v.d_chunk_word_off, v.d_wave_off, v.d_wave_words, nullptr, nullptr, v.d_status, d_out);
     };
 
     // ---- the walk ----
@@ -836,7 +836,7 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         if (e != hipSuccess) return e;
     } else if (R.walk == Walk::Parallel) {
         const bool split = R.dec == Dec::LanesSplit;
-        hipError_t e = walk_scratch_reset(G, d_pw, s);
+        hipError_t e = walk_scratch_reset(G, c.d_pw, s);
         if (e != hipSuccess) return e;
         // a ragged batch has both kinds of chunk and the two walks touch different chunks: the chunk-wide walk goes to the
         // context's side stream while the block walk runs here (config 5: 0.18 ms of 0.6 off the critical path)
@@ -846,37 +846,36 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
             if ((e = hipEventRecord(side->fork, s)) != hipSuccess) return e;
             if ((e = hipStreamWaitEvent(side->s, side->fork, 0)) != hipSuccess) return e;
         }
-        if (R.par.chunk_wide)
-            launch_walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, R.par.by_chains, spw);
+        if (R.par.chunk_wide) launch_walk_chunk_wide(c.on(spw), R.par.by_chains);
         // ... and so does the decoding of the long-waveform chunks, whose tables are complete long before the block walk is
         // through: their wavefronts (the first rag_groups_long of the longest-first order) are launched behind the
         // chunk-wide walk on the side stream, the rest here behind the block walk
         if (split) {
             Geom Gl = G;
             Gl.rag_groups = G.rag_groups_long;
-            launch_lanes(Gl, Gl.rag_groups, spw);
+            launch_lanes(c.view(Gl).on(spw), Gl.rag_groups);
         }
         if (forked && (e = hipEventRecord(side->join, side->s)) != hipSuccess) {
             // the side stream's kernels write this call's tables and output: never return with them unordered
             (void)hipStreamSynchronize(side->s);
             return e;
         }
-        if (R.par.blocks) launch_walk_blocks(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
+        if (R.par.blocks) launch_walk_blocks(c);
         if (split) {
-            mark(ev, 1, s);  // (the block walk's end; the other stream is decoding already)
+            mark(c.ev, 1, s);  // (the block walk's end; the other stream is decoding already)
             Geom Gs = G;
             Gs.rag_order = G.rag_order + G.rag_groups_long;
             Gs.rag_groups = G.rag_groups - G.rag_groups_long;
-            launch_lanes(Gs, Gs.rag_groups, s);
+            launch_lanes(c.view(Gs), Gs.rag_groups);
         }
         if (forked && (e = hipStreamWaitEvent(s, side->join, 0)) != hipSuccess) {
             (void)hipStreamSynchronize(side->s);
             return e;
         }
     } else if (R.walk == Walk::Serial) {
-        launch_walk_serial(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, s);
+        launch_walk_serial(c);
     }
-    if (R.dec != Dec::LanesSplit) mark(ev, 1, s);
+    if (R.dec != Dec::LanesSplit) mark(c.ev, 1, s);
 
     // ---- the decoder ----
     switch (R.dec) {
@@ -897,9 +896,9 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         }
         path |= DRX_PATH_LANES_FUSED;
         if (gen)
-            k_decode_lanes<true, true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
+            k_decode_lanes<true, true><<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off, c.d_wave_words, d_granules, ticket, c.d_status, d_out);
         else
-            k_decode_lanes<true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_granules, ticket, d_status, d_out);
+            k_decode_lanes<true><<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off, c.d_wave_words, d_granules, ticket, c.d_status, d_out);
         break;
     }
     case Dec::Blocks: {
@@ -907,33 +906,33 @@ hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
         // workgroup each, by the kernel that also judges them
         const uint32_t *fail = nullptr, *suspect = nullptr;
         bool fused = false;
-        hipError_t e = launch_decode_blocks(G, d_in, in_words, d_wave_off, d_wave_words, d_blk, d_status, d_out, &fail, &suspect, gen, s, &fused);
+        hipError_t e = launch_decode_blocks(c, d_blk, d_out, &fail, &suspect, gen, &fused);
         if (e != hipSuccess) return e;
         path |= DRX_PATH_BLOCKS | (gen ? (fused ? DRX_PATH_IIR_FUSED : DRX_PATH_IIR) : 0u);
-        k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, fail, suspect, gen ? 1u : 0u);
+        k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, c.d_status, d_out, fail, suspect, gen ? 1u : 0u);
         if (gen) {
             // (not fused: residuals -> samples, in place;) then the waveforms the block decoder flagged, serially (a slope-1 ramp)
-            if (!fused && (e = launch_iir(G, G.iir_chunk_tile_base, G.iir_n_tiles, G.iir_tab, G.iir_state, fail, d_status, d_out, s)) != hipSuccess) return e;
-            k_decode_simple<<<nb_plain, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, fail);
+            if (!fused && (e = launch_iir(G, G.iir_chunk_tile_base, G.iir_n_tiles, G.iir_tab, G.iir_state, fail, c.d_status, d_out, s)) != hipSuccess) return e;
+            k_decode_simple<<<nb_plain, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, c.d_status, d_out, fail);
         }
         break;
     }
     case Dec::Long:  // (LONG_NOT_BLOCKS, or a long-waveform batch the block decoder does not take: one workgroup per waveform)
         path |= DRX_PATH_LONG;
-        k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, nullptr, nullptr, 0u);
+        k_decode_long<<<(unsigned)G.total_waves, kLongThreads, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, c.d_status, d_out, nullptr, nullptr, 0u);
         break;
     case Dec::Lanes:
-        launch_lanes(G, (!G.uniform && G.rag_order) ? G.rag_groups : nb_plain, s);  // (ragged: groups per chunk round up)
+        launch_lanes(c, (!G.uniform && G.rag_order) ? G.rag_groups : nb_plain);  // (ragged: groups per chunk round up)
         break;
     case Dec::LanesSplit:  // (both launches went out behind their walks)
         break;
     case Dec::Simple:
         path |= DRX_PATH_SIMPLE;
-        k_decode_simple<<<nb_plain, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_status, d_out, nullptr);
+        k_decode_simple<<<nb_plain, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, c.d_status, d_out, nullptr);
         break;
     }
-    mark(ev, 2, s);
-    mark(ev, 3, s);
+    mark(c.ev, 2, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

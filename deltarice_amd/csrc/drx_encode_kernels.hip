@@ -747,22 +747,22 @@ hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned lo
 
 // Single-pass encode (k_encode_fused).  d_scan: uint64[total_waves] + one uint32 ticket
 // word after it, zeroed here on the stream before every launch.
-hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                               uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
-                               DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_encode_fused(const EncodeCall &c, int wide, uint64_t *d_scan) {
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
+    mark(c.ev, 0, s);
     hipError_t e = hipMemsetAsync(d_scan, 0, (G.total_waves + 2) * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    mark(ev, 1, s);
-    mark(ev, 2, s);
+    mark(c.ev, 1, s);
+    mark(c.ev, 2, s);
     uint32_t *ticket = reinterpret_cast<uint32_t *>(d_scan + G.total_waves);
     auto go = [&](auto gen_tag, auto wv_tag, auto cap_tag) {
         constexpr bool GEN = decltype(gen_tag)::value;
         constexpr int WV = decltype(wv_tag)::value;
         constexpr uint32_t CAPW = decltype(cap_tag)::value;
-        k_encode_fused<GEN, WV, CAPW><<<blocks_for(G.total_waves, WV), 64 * WV, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words,
-                                                                                      d_scan, ticket, d_status);
+        k_encode_fused<GEN, WV, CAPW><<<blocks_for(G.total_waves, WV), 64 * WV, 0, s>>>(G, c.d_in, c.out.d_out, c.out.out_cap, c.out.d_chunk_word_off,
+                                                                                      c.out.d_wave_words, d_scan, ticket, c.d_status);
     };
     using std::integral_constant;
     const std::true_type T;
@@ -774,7 +774,7 @@ hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uin
         case 3: pick(integral_constant<int, 4>{}, integral_constant<uint32_t, kEncWide3Words>{}); break;
         default: pick(integral_constant<int, kEncWaves>{}, integral_constant<uint32_t, kEncCapWords>{}); break;
     }
-    mark(ev, 3, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 
@@ -788,20 +788,21 @@ hipError_t launch_chunk_offsets(const Geom &G, const uint32_t *d_wave_words, uin
     return hipGetLastError();
 }
 
-hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                         uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint32_t *d_wave_rel,
-                         uint64_t *d_chunk_words, DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_encode(const EncodeCall &c, uint32_t *d_wave_rel, uint64_t *d_chunk_words) {
+    const Geom &G = *c.G;
+    const EncOut &o = c.out;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
-    for_wave_slices(G.total_waves, [&](uint64_t g0, unsigned nb) { k_encode_sizes<<<nb, 256, 0, s>>>(G, g0, d_in, d_wave_words); });
-    mark(ev, 1, s);
-    k_chunk_scan<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, d_wave_words, d_wave_rel, d_chunk_words);
-    k_chunk_offsets<<<1, 1024, 0, s>>>(G.n_chunks, d_chunk_words, d_chunk_word_off, out_cap, d_status, G.host_words);
-    mark(ev, 2, s);
+    mark(c.ev, 0, s);
+    for_wave_slices(G.total_waves, [&](uint64_t g0, unsigned nb) { k_encode_sizes<<<nb, 256, 0, s>>>(G, g0, c.d_in, o.d_wave_words); });
+    mark(c.ev, 1, s);
+    k_chunk_scan<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, o.d_wave_words, d_wave_rel, d_chunk_words);
+    k_chunk_offsets<<<1, 1024, 0, s>>>(G.n_chunks, d_chunk_words, o.d_chunk_word_off, o.out_cap, c.d_status, G.host_words);
+    mark(c.ev, 2, s);
     for_wave_slices(G.total_waves, [&](uint64_t g0, unsigned nb) {
-        k_encode_pack<<<nb, 256, 0, s>>>(G, g0, d_in, d_wave_words, d_wave_rel, d_chunk_word_off, d_out, out_cap);
+        k_encode_pack<<<nb, 256, 0, s>>>(G, g0, c.d_in, o.d_wave_words, d_wave_rel, o.d_chunk_word_off, o.d_out, o.out_cap);
     });
-    mark(ev, 3, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 
@@ -840,25 +841,26 @@ std::vector<uint64_t> segments_plan_ragged(Geom &G, const ChunkDesc *d) {
 }
 
 // Encoder for few long waveforms.  d_seg_bits: uint32[total_waves * segments], d_seg_pos: uint64[same].
-hipError_t launch_encode_long(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                              uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint32_t *d_wave_rel,
-                              uint64_t *d_chunk_words, uint32_t *d_seg_bits, uint64_t *d_seg_pos, DevStatus *d_status,
-                              hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_encode_long(const EncodeCall &c, uint32_t *d_wave_rel, uint64_t *d_chunk_words, uint32_t *d_seg_bits,
+                              uint64_t *d_seg_pos) {
+    const Geom &G = *c.G;
+    const EncOut &o = c.out;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
     const uint32_t S = G.uniform ? segments_of(G.u_wave_len) : 0u;
     const uint64_t units = long_batch_units(G);
-    mark(ev, 0, s);
+    mark(c.ev, 0, s);
     const uint32_t upw = (G.uniform && S == 1u && G.u_wave_len <= 1024u) ? 8u : 1u;  // short waveforms: eight per wavefront
-    k_seg_sizes<<<blocks_for(units, 4 * upw), 256, 0, s>>>(G, d_in, S, units, upw, d_seg_bits);
-    mark(ev, 1, s);
-    k_seg_scan<<<(unsigned)G.total_waves, 64, 0, s>>>(G, S, d_seg_bits, d_seg_pos, d_wave_words);
-    k_chunk_scan<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, d_wave_words, d_wave_rel, d_chunk_words);
-    k_chunk_offsets<<<1, 1024, 0, s>>>(G.n_chunks, d_chunk_words, d_chunk_word_off, out_cap, d_status, G.host_words);
-    k_seg_zero<<<blocks_for(units, 256), 256, 0, s>>>(G, S, units, d_seg_pos, d_wave_rel, d_chunk_word_off, d_out, out_cap);
-    mark(ev, 2, s);
-    k_seg_pack<<<blocks_for(units, 4 * upw), 256, 0, s>>>(G, d_in, S, units, d_seg_pos, d_wave_words, d_wave_rel, d_chunk_word_off,
-                                                          d_out, out_cap, upw);
-    mark(ev, 3, s);
+    k_seg_sizes<<<blocks_for(units, 4 * upw), 256, 0, s>>>(G, c.d_in, S, units, upw, d_seg_bits);
+    mark(c.ev, 1, s);
+    k_seg_scan<<<(unsigned)G.total_waves, 64, 0, s>>>(G, S, d_seg_bits, d_seg_pos, o.d_wave_words);
+    k_chunk_scan<<<(unsigned)G.n_chunks, 256, 0, s>>>(G, o.d_wave_words, d_wave_rel, d_chunk_words);
+    k_chunk_offsets<<<1, 1024, 0, s>>>(G.n_chunks, d_chunk_words, o.d_chunk_word_off, o.out_cap, c.d_status, G.host_words);
+    k_seg_zero<<<blocks_for(units, 256), 256, 0, s>>>(G, S, units, d_seg_pos, d_wave_rel, o.d_chunk_word_off, o.d_out, o.out_cap);
+    mark(c.ev, 2, s);
+    k_seg_pack<<<blocks_for(units, 4 * upw), 256, 0, s>>>(G, c.d_in, S, units, d_seg_pos, o.d_wave_words, d_wave_rel, o.d_chunk_word_off,
+                                                          o.d_out, o.out_cap, upw);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

@@ -903,53 +903,55 @@ __global__ __launch_bounds__(64 * WV, 4) void k_encode_stream_segs(Geom G, uint3
 // ---------------------------------------------------------------------------
 // d_scan: uint64[2 * tickets + kEsCtrlWords] (tickets <= total_waves): total[tickets] | place[tickets] | control, zeroed here
 // on the stream before every launch.
-hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                                uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
-                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_encode_stream(const EncodeCall &c, uint64_t *d_scan) {
+    const Geom &G = *c.G;
+    const EncOut &o = c.out;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
     const uint64_t W = G.total_waves;
     const uint64_t tickets = (W + kEsWaves - 1) / kEsWaves;
-    mark(ev, 0, s);
+    mark(c.ev, 0, s);
     hipError_t e = hipMemsetAsync(d_scan, 0, (2 * tickets + kEsCtrlWords) * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    mark(ev, 1, s);
-    mark(ev, 2, s);
+    mark(c.ev, 1, s);
+    mark(c.ev, 2, s);
     uint64_t *size = d_scan, *place = d_scan + tickets;
     uint32_t *ctrl = reinterpret_cast<uint32_t *>(d_scan + 2 * tickets);
     const unsigned grid = es_grid(G, tickets);
     if (G.n_taps)
-        k_encode_stream<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words, size,
-                                                                              place, ctrl, d_status);
+        k_encode_stream<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, c.d_in, o.d_out, o.out_cap, o.d_chunk_word_off, o.d_wave_words,
+                                                                              size, place, ctrl, c.d_status);
     else
-        k_encode_stream<false, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, d_in, d_out, out_cap, d_chunk_word_off, d_wave_words, size,
-                                                                               place, ctrl, d_status);
-    mark(ev, 3, s);
+        k_encode_stream<false, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, c.d_in, o.d_out, o.out_cap, o.d_chunk_word_off, o.d_wave_words,
+                                                                               size, place, ctrl, c.d_status);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 
 // d_scan: uint64[3 * tickets + kEsCtrlWords]: total[tickets] | place[2 * tickets] | control, zeroed here before every launch.
 // The caller has checked the geometry (uniform, tickets below 2^32 - 2^16) and sized d_scan for the smallest segments.
-hipError_t launch_encode_stream_segs(const Geom &G, uint32_t seg_target, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                                     uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
-                                     DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_encode_stream_segs(const EncodeCall &c, uint32_t seg_target, uint64_t *d_scan) {
+    const Geom &G = *c.G;
+    const EncOut &o = c.out;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
     const EsSegShape sh = es_seg_shape(G.u_wave_len, seg_target);
     const uint64_t tickets = G.total_waves * sh.tpw;
-    mark(ev, 0, s);
+    mark(c.ev, 0, s);
     hipError_t e = hipMemsetAsync(d_scan, 0, (3 * tickets + kEsCtrlWords) * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    mark(ev, 1, s);
-    mark(ev, 2, s);
+    mark(c.ev, 1, s);
+    mark(c.ev, 2, s);
     uint64_t *size = d_scan, *place = d_scan + tickets;
     uint32_t *ctrl = reinterpret_cast<uint32_t *>(d_scan + 3 * tickets);
     const unsigned grid = es_grid(G, tickets);
     if (G.n_taps)
-        k_encode_stream_segs<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, sh.seg_len, sh.tpw, d_in, d_out, out_cap, d_chunk_word_off,
-                                                                                   d_wave_words, size, place, ctrl, d_status);
+        k_encode_stream_segs<true, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, sh.seg_len, sh.tpw, c.d_in, o.d_out, o.out_cap, o.d_chunk_word_off,
+                                                                                   o.d_wave_words, size, place, ctrl, c.d_status);
     else
-        k_encode_stream_segs<false, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, sh.seg_len, sh.tpw, d_in, d_out, out_cap, d_chunk_word_off,
-                                                                                    d_wave_words, size, place, ctrl, d_status);
-    mark(ev, 3, s);
+        k_encode_stream_segs<false, kEsWaves, kEsRing><<<grid, 64 * kEsWaves, 0, s>>>(G, sh.seg_len, sh.tpw, c.d_in, o.d_out, o.out_cap, o.d_chunk_word_off,
+                                                                                    o.d_wave_words, size, place, ctrl, c.d_status);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

@@ -248,31 +248,31 @@ __global__ __launch_bounds__(kGtThreads) void k_gather_tiles(uint64_t total_wave
 
 uint64_t gather_scan_blocks(uint64_t n_sel) { return (n_sel + kGsBlock - 1) / kGsBlock; }
 
-// d_ent_words: uint32[n_sel], d_ent_pos: uint64[n_sel], d_block_sum: uint64[gather_scan_blocks(n_sel) + 2], d_ctrl: uint32[1]: scratch.
-// tiles: the copy form for short entries; mean_words: the batch's words per waveform, roughly (sizes the wavefront form's grid)
-hipError_t launch_gather(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
-                         const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves, const uint32_t *d_chunk_samples,
-                         uint32_t *d_out, uint64_t out_cap, uint64_t *d_out_chunk_off, uint32_t *d_out_wave_words,
-                         uint32_t *d_ent_words, uint64_t *d_ent_pos, uint64_t *d_block_sum, uint32_t *d_ctrl, bool tiles,
-                         uint64_t mean_words, bool resume, DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+// t: gather_scratch_view(); tiles: the copy form for short entries
+hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves,
+                         const uint32_t *d_chunk_samples, const EncOut &out, const GatherScratch &t, bool tiles, uint64_t mean_words,
+                         bool resume) {
     if (!n_sel) return hipSuccess;
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
+    uint32_t *const d_out = out.d_out;
     const unsigned nb = (unsigned)gather_scan_blocks(n_sel);
-    if (!resume) k_gather_sizes<<<nb, kGsThreads, 0, s>>>(G.total_waves, d_wave_words, d_sel, n_sel, chunk_waves, d_ent_words, d_block_sum);
-    k_gather_scan<<<1, 1024, 0, s>>>(d_block_sum, nb, d_out, out_cap, d_status, d_ctrl, resume);
-    k_gather_offsets<<<nb, kGsThreads, 0, s>>>(d_ent_words, d_block_sum, n_sel, chunk_waves, d_chunk_samples, d_status, d_ctrl, d_ent_pos,
-                                               d_out_chunk_off, d_out_wave_words, d_out);
-    mark(ev, 2, s);
+    if (!resume) k_gather_sizes<<<nb, kGsThreads, 0, s>>>(G.total_waves, c.d_wave_words, d_sel, n_sel, chunk_waves, t.ent_words, t.block_sum);
+    k_gather_scan<<<1, 1024, 0, s>>>(t.block_sum, nb, d_out, out.out_cap, c.d_status, t.ctrl, resume);
+    k_gather_offsets<<<nb, kGsThreads, 0, s>>>(t.ent_words, t.block_sum, n_sel, chunk_waves, d_chunk_samples, c.d_status, t.ctrl, t.ent_pos,
+                                               out.d_chunk_word_off, out.d_wave_words, d_out);
+    mark(c.ev, 2, s);
     if (d_out) {
         if (tiles) {
-            k_gather_tiles<<<blocks_for(n_sel, kGtEntries), kGtThreads, 0, s>>>(G.total_waves, d_in, d_wave_off, d_sel, d_ent_words, d_ent_pos,
-                                                                                 n_sel, d_ctrl, d_out);
+            k_gather_tiles<<<blocks_for(n_sel, kGtEntries), kGtThreads, 0, s>>>(G.total_waves, c.d_in, c.d_wave_off, d_sel, t.ent_words, t.ent_pos,
+                                                                                 n_sel, t.ctrl, d_out);
         } else {
             // pieces of an entry side by side while the list alone does not fill the chip (256 CUs x 32 wavefronts)
             uint64_t slots = (mean_words + kGcPiece - 1) / kGcPiece;
             slots = std::max<uint64_t>(1, std::min<uint64_t>(slots, 1024));
             const uint64_t wgs = (n_sel * slots + 3) / 4;
-            k_gather_waves<<<(unsigned)std::min<uint64_t>(wgs, 1u << 20), 256, 0, s>>>(G.total_waves, d_in, d_wave_off, d_sel, d_ent_words,
-                                                                                     d_ent_pos, n_sel, (uint32_t)slots, d_ctrl, d_out);
+            k_gather_waves<<<(unsigned)std::min<uint64_t>(wgs, 1u << 20), 256, 0, s>>>(G.total_waves, c.d_in, c.d_wave_off, d_sel, t.ent_words,
+                                                                                     t.ent_pos, n_sel, (uint32_t)slots, t.ctrl, d_out);
         }
     }
     return hipGetLastError();

@@ -98,9 +98,47 @@ constexpr uint32_t kErrCapacity = 1u;
 constexpr uint32_t kErrCorrupt = 2u;
 constexpr uint32_t kErrInternal = 4u;
 
-hipError_t launch_encode(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                         uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint32_t *d_wave_rel,
-                         uint64_t *d_chunk_words, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+// ---------------------------------------------------------------------------
+// Call frames: what the host launchers below are given in front of a call's own arguments.  Plain aggregates that the C ABI
+// glue fills from the plan once per call (call_begin(), drx_api.hip); they stop at the <<< >>>, kernels take loose arguments.
+// ---------------------------------------------------------------------------
+// A call on an ENCODED batch.  tables_ready: wave_off / wave_words are already filled in (the one-chunk host path walks the
+// header chain on the CPU while the chunk is in flight to the device; the side-band forms derive them from the caller's
+// table): no walk
+struct StreamCall {
+    const Geom *G;
+    const uint32_t *d_in;  // the encoded batch: its words, their count, the chunk offsets
+    uint64_t in_words;
+    const uint64_t *d_chunk_word_off;
+    uint64_t *d_wave_off;  // the plan's header tables
+    uint32_t *d_wave_words;
+    bool tables_ready;
+    void *d_pw;  // scratch of the parallel walks (nullptr: the plan has none)
+    DevStatus *d_status;
+    hipEvent_t *ev;  // optional: the call's four profiling events
+    hipStream_t s;
+    // the same call on another stream, or over a view of its geometry (launch_decode(): side stream, split lanes launch)
+    StreamCall on(hipStream_t st) const { StreamCall c = *this; c.s = st; return c; }
+    StreamCall view(const Geom &Gv) const { StreamCall c = *this; c.G = &Gv; return c; }
+};
+// What the encoders, launch_gather() and launch_transcode() write: the words, the chunk offsets, the n_i table
+struct EncOut {
+    uint32_t *d_out;
+    uint64_t out_cap;
+    uint64_t *d_chunk_word_off;
+    uint32_t *d_wave_words;
+};
+// A call that encodes raw samples
+struct EncodeCall {
+    const Geom *G;
+    const int16_t *d_in;
+    EncOut out;
+    DevStatus *d_status;
+    hipEvent_t *ev;
+    hipStream_t s;
+};
+
+hipError_t launch_encode(const EncodeCall &c, uint32_t *d_wave_rel, uint64_t *d_chunk_words);
 
 // launch_decode() takes the workgroup-per-waveform decoder for uniform batches whose lane-per-waveform decode would leave most of
 // the 98 304 lane slots empty and the block decoder does not take: at most 16 384 waveforms of at least 65 536 samples, or at most
@@ -132,16 +170,19 @@ WalkRoute route_walk(const Geom &G, bool tables_ready, bool have_scratch);
 std::vector<uint32_t> walk_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 uint64_t walk_scratch_bytes(const Geom &G);  // d_pw of the launchers below (0: the batch takes neither parallel walk)
 hipError_t walk_scratch_reset(const Geom &G, void *d_pw, hipStream_t s);  // in front of the parallel walks of a call
-void launch_walk_chunk_wide(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                            uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, bool by_chains, hipStream_t s);
-void launch_walk_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s);
-void launch_walk_serial(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
+void launch_walk_chunk_wide(const StreamCall &c, bool by_chains);
+void launch_walk_blocks(const StreamCall &c);
+void launch_walk_serial(const StreamCall &c);
 // The walk in front of a call that reads the WHOLE batch behind it (drx_wave_stats, drx_decode_window, drx_find_pulses,
-// drx_transcode): route_walk()'s choice, all of it on the stream s
-hipError_t launch_batch_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                             uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s);
+// drx_transcode, drx_estimate_words_encoded): route_walk()'s choice, all of it on the call's stream
+hipError_t launch_batch_walk(const StreamCall &c);
+// ... as those calls open: event 0, the walk unless the tables are ready, event 1
+inline hipError_t batch_walk_prologue(const StreamCall &c) {
+    mark(c.ev, 0, c.s);
+    const hipError_t e = c.tables_ready ? hipSuccess : launch_batch_walk(c);
+    if (e == hipSuccess) mark(c.ev, 1, c.s);
+    return e;
+}
 // ... and the launches of those calls' kernels, a lane per waveform: the wavefronts of the batch -- rag_order's groups for a
 // ragged plan that has them under the kernels that follow it (by_rag_order: lane_wave(), drx_lane_stream.h), 64 consecutive
 // waveforms each otherwise -- in slices of at most 2^25 per launch (a launch carries fewer than 2^32 threads).
@@ -152,83 +193,102 @@ template <class F> inline void for_wavefront_slices(const Geom &G, bool by_rag_o
     for (uint64_t base = 0; base < n_wf; base += max_grid) go(base, (unsigned)(n_wf - base < max_grid ? n_wf - base : max_grid));
 }
 // ... no walk: the tables from the n_i table an encode left behind, checked against the stream
-hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,
-                                  const uint32_t *d_list = nullptr, uint32_t n_list = 0);  // d_list: these chunks only
+hipError_t launch_sideband_tables(const StreamCall &c, const uint32_t *d_n, const uint32_t *d_list = nullptr,
+                                  uint32_t n_list = 0);  // d_list: these chunks only
 // drx_decode_select (drx_select.hip): the walk over the chunks a selection touches (select_walk_class(): which of its three
 // lists a chunk belongs to), then a wavefront per selected waveform
 int select_walk_class(uint32_t n_waves, uint32_t wave_len);
-hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                              const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain, uint32_t *d_fail,
-                              uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s);
-hipError_t launch_decode_select(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
-                                const uint64_t *d_sel, uint64_t n_sel, DevStatus *d_status, int16_t *d_out, uint64_t stride,
-                                hipStream_t s);
+hipError_t launch_select_walk(const StreamCall &c, const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain,
+                              uint32_t *d_fail);
+hipError_t launch_decode_select(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, int16_t *d_out, uint64_t stride);
 // drx_gather_encoded (drx_gather.hip): behind the same walk, sizes + scan + offsets, then the copy of the entries' word ranges
 // (tiles: a workgroup per run of short entries; otherwise a wavefront per entry, or per piece of a long one; resume: the walk's
 // tables, the sizes and the scanned block sums of the last call with this list are still in place -- the call behind a sizing call)
 uint64_t gather_scan_blocks(uint64_t n_sel);
-hipError_t launch_gather(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
-                         const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves, const uint32_t *d_chunk_samples,
-                         uint32_t *d_out, uint64_t out_cap, uint64_t *d_out_chunk_off, uint32_t *d_out_wave_words,
-                         uint32_t *d_ent_words, uint64_t *d_ent_pos, uint64_t *d_block_sum, uint32_t *d_ctrl, bool tiles,
-                         uint64_t mean_words, bool resume, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+// its device-only scratch, a buffer of the plan: uint64 ent_pos[n_sel] | uint64 block_sum[blocks + 2] (the last two: total,
+// status) | uint32 ent_words[n_sel] | uint32 ctrl[1]
+struct GatherScratch {
+    uint64_t *ent_pos, *block_sum;
+    uint32_t *ent_words, *ctrl;
+    uint64_t bytes;
+};
+inline GatherScratch gather_scratch_view(void *base, uint64_t n_sel) {
+    GatherScratch t;
+    t.ent_pos = (uint64_t *)base;
+    t.block_sum = t.ent_pos + n_sel;
+    t.ent_words = (uint32_t *)(t.block_sum + gather_scan_blocks(n_sel) + 2);
+    t.ctrl = t.ent_words + n_sel;
+    t.bytes = (n_sel + gather_scan_blocks(n_sel) + 2) * sizeof(uint64_t) + (n_sel + 1) * sizeof(uint32_t);
+    return t;
+}
+// d_sel: the list; d_chunk_samples: N_c of every output chunk of chunk_waves entries; mean_words: the batch's words per
+// waveform, roughly (sizes the wavefront form's grid).  ev: {start, walk's end, offsets' end, end}, of which the caller
+// records all but the third
+hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves,
+                         const uint32_t *d_chunk_samples, const EncOut &out, const GatherScratch &t, bool tiles, uint64_t mean_words,
+                         bool resume);
 // drx_wave_stats (drx_stats.hip): behind the whole batch's walk (tables_ready: the side-band's tables are in place), a lane per
 // waveform that parses and reduces: int64 d_out[total_waves][DRX_STAT_COLS].  ev: {start, walk's end, kernel's end, end}
 // Few long waveforms under the delta filter (stats_blocks_batch(): d_blk = the block decoder's scratch, d_sacc = the plan's
 // stats_blocks_scratch_bytes() of accumulators and list) take the block form of drx_stats_blocks.hip instead, with the lane kernel
 // behind it for the waveforms it lists.  form_out: DRX_STATS_FORM_* of include/deltarice_hip.h
-hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, void *d_blk, void *d_sacc,
-                             uint32_t head_len, DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s, uint32_t *form_out);
+hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, uint32_t *form_out);
 bool stats_blocks_batch(const Geom &G, const void *d_blk);
 uint64_t stats_blocks_scratch_bytes(const Geom &G);
-hipError_t launch_stats_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
-                               const uint32_t *d_wave_words, void *d_blk, void *d_sacc, uint32_t head_len, DevStatus *d_status,
-                               int64_t *d_out, const uint32_t **listed_out, const uint32_t **n_listed_out, hipStream_t s);
+hipError_t launch_stats_blocks(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out,
+                               const uint32_t **listed_out, const uint32_t **n_listed_out);
 // drx_decode_window (drx_window.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
 // far as its window's end and writes `width` samples from start[g * start_stride] + offset on (pad outside the waveform) to row
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}
-hipError_t launch_decode_window(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw,
-                                const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
-                                DevStatus *d_status, int16_t *d_out, uint64_t out_stride, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_decode_window(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width,
+                                int16_t pad, int16_t *d_out, uint64_t out_stride);
 // drx_find_pulses (drx_pulses.hip): behind the whole batch's walk (tables_ready as above), the output zeroed by one memset, a lane
 // per waveform that parses, compares every sample with thr[g * thr_stride] + thr (d_thr == nullptr: 0; neg: below it, otherwise
 // above it) and writes the records of the first max_pulses runs of at least min_width samples to int64
 // d_out[total_waves][max_pulses][DRX_PULSE_COLS] and the number of all such runs to d_count[total_waves].
 // ev: {start, walk's end, kernel's end, end}
-hipError_t launch_find_pulses(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                              uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, const int64_t *d_thr,
-                              uint64_t thr_stride, int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses,
-                              DevStatus *d_status, uint32_t *d_count, int64_t *d_out, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_find_pulses(const StreamCall &c, const int64_t *d_thr, uint64_t thr_stride, int64_t thr, bool neg,
+                              uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 // k_chunk_scan + k_chunk_offsets (drx_encode_kernels.hip) over a table of n_i that is not an encode's: header positions relative
 // to the chunk, chunk offsets, DevStatus::total_words and kErrCapacity against out_cap
 hipError_t launch_chunk_offsets(const Geom &G, const uint32_t *d_wave_words, uint32_t *d_wave_rel, uint64_t *d_chunk_words,
                                 uint64_t *d_chunk_word_off, uint64_t out_cap, DevStatus *d_status, hipStream_t s);
-// drx_transcode / drx_estimate_words_encoded (drx_transcode.hip): behind the whole batch's walk, a lane per waveform that parses
-// and sizes at RiceParameter 2^k2, the scan above over the new table (d_new_*: scratch of the call), then a lane per waveform
-// that parses and packs.  d_out == nullptr: as far as the offsets.  d_est != nullptr: the words at every k alone (uint64[16]).
+// drx_transcode / drx_estimate_words_encoded (drx_transcode.hip).  Their scratch, a buffer of the plan: uint64
+// chunk_words[n_chunks + 1] | uint64 est[16] | uint32 n_i'[W] | uint32 header positions[W] of the RESULT (the plan's own tables
+// describe the source)
+struct TrcScratch {
+    uint64_t *chunk_words;
+    unsigned long long *est;
+    uint32_t *words, *rel;
+    uint64_t bytes;
+};
+inline TrcScratch trc_scratch_view(const Geom &G, void *base) {
+    const uint64_t W = G.total_waves ? G.total_waves : 1, C = G.n_chunks + 1;
+    TrcScratch t;
+    t.chunk_words = (uint64_t *)base;
+    t.est = (unsigned long long *)(t.chunk_words + C);
+    t.words = (uint32_t *)(t.est + 16);
+    t.rel = t.words + W;
+    t.bytes = (C + 16) * sizeof(uint64_t) + 2 * W * sizeof(uint32_t);
+    return t;
+}
+// Behind the whole batch's walk, a lane per waveform that parses and sizes at RiceParameter 2^k2, the scan above over the new
+// table, then a lane per waveform that parses and packs.  out.d_out == nullptr: as far as the offsets.
 // ev: {start, walk's end, offsets' end, end}
-hipError_t launch_transcode(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                            uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t k2,
-                            uint32_t *d_new_words, uint32_t *d_new_rel, uint64_t *d_new_chunk_words, uint32_t *d_out,
-                            uint64_t out_cap, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words,
-                            unsigned long long *d_est, DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_transcode(const StreamCall &c, uint32_t k2, const TrcScratch &t, const EncOut &out);
+// drx_estimate_words_encoded: behind the same walk, the words at every k alone (d_est: uint64[16], cleared here).
+// ev: {start, walk's end, kernel's end, end}
+hipError_t launch_estimate_words_encoded(const StreamCall &c, unsigned long long *d_est);
 
 // wide: fused_wide() as the route decided it
-hipError_t launch_encode_fused(const Geom &G, int wide, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                               uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
-                               DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_encode_fused(const EncodeCall &c, int wide, uint64_t *d_scan);
 
 // the persistent form of the single pass (drx_encode_stream.hip): a ring of kEsRingWords LDS words per wavefront, a scanner
 // wavefront.  d_scan: uint64[2 * tickets + 32], tickets <= total_waves (32 words of control)
 constexpr uint32_t kEsRingWords = 2496;
 constexpr uint64_t kEsMinUnits = 8192;  // waveforms (segments) from which the persistent forms suit a batch: its 4096 wavefronts a few each
-hipError_t launch_encode_stream(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                                uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
-                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_encode_stream(const EncodeCall &c, uint64_t *d_scan);
 
 // ... and its form for LONG waveforms (k_encode_stream_segs): the unit a wavefront codes into its ring is a SEGMENT of a
 // waveform, a ticket is kEsSegWaves consecutive segments of ONE waveform, places are bit positions.
@@ -264,9 +324,7 @@ inline bool stream_segs_admits(const Geom &G) { return G.uniform && (G.n_taps ==
                                                        G.total_waves * es_seg_shape(G.u_wave_len, kEsSegMinLen).tpw < 0xffff0000ull; }
 constexpr uint32_t kEsSegsFromLen = 20480;
 inline uint64_t segs_scan_words(const Geom &G, uint32_t seg_target) { return 3 * G.total_waves * es_seg_shape(G.u_wave_len, seg_target).tpw + 192; }
-hipError_t launch_encode_stream_segs(const Geom &G, uint32_t seg_target, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                                     uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan,
-                                     DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_encode_stream_segs(const EncodeCall &c, uint32_t seg_target, uint64_t *d_scan);
 
 // few long waveforms (WaveformLength = -1): a wavefront per 8192-sample segment, see drx_encode_kernels.hip.  Admission (the
 // encoder can run the batch) and preference (it is the default choice)
@@ -275,10 +333,8 @@ bool long_batch(const Geom &G);
 uint64_t long_batch_units(const Geom &G);
 // ragged plans: sets seg_units and returns seg_unit_base's host copy (empty: the encoder does not take the batch)
 std::vector<uint64_t> segments_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
-hipError_t launch_encode_long(const Geom &G, const int16_t *d_in, uint32_t *d_out, uint64_t out_cap,
-                              uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint32_t *d_wave_rel,
-                              uint64_t *d_chunk_words, uint32_t *d_seg_bits, uint64_t *d_seg_pos, DevStatus *d_status,
-                              hipEvent_t *ev, hipStream_t s);
+hipError_t launch_encode_long(const EncodeCall &c, uint32_t *d_wave_rel, uint64_t *d_chunk_words, uint32_t *d_seg_bits,
+                              uint64_t *d_seg_pos);
 
 // a second stream of the context, for kernels of one call that do not depend on each other (fork / join through events).
 // One per CONTEXT, shared by all its plans: it relies on the rule of include/deltarice_hip.h that a context and its plans are
@@ -288,13 +344,9 @@ struct SideStream {
     hipStream_t s;
     hipEvent_t fork, join;
 };
-// tables_ready: wave_off / wave_words are already filled in (the one-chunk host path walks the header chain on the CPU while the
-// chunk is in flight to the device; the side-band decode derives them from the caller's table): no walk
 // path_out (optional): which decoders the call used, DRX_PATH_* bits of include/deltarice_hip.h
-hipError_t launch_decode(const Geom &G, const uint32_t *d_in, uint64_t in_words,
-                         const uint64_t *d_chunk_word_off, int16_t *d_out, uint64_t *d_wave_off,
-                         uint32_t *d_wave_words, uint64_t *d_granules, DevStatus *d_status, int impl, bool tables_ready,
-                         void *d_pw, void *d_blk, const SideStream *side, hipEvent_t *ev, hipStream_t s, uint32_t *path_out = nullptr);
+hipError_t launch_decode(const StreamCall &c, int16_t *d_out, uint64_t *d_granules, int impl, void *d_blk, const SideStream *side,
+                         uint32_t *path_out = nullptr);
 // block-parallel decoder for batches of few waveforms (drx_blocks.hip): a workgroup per block of a waveform's stream
 bool blocks_batch(const Geom &G, double lane_us = 0.06);
 // ragged plans: decides rag_blocks / rag_blk_nt / rag_blk_slots and the classes from the host's chunk table (call once, when
@@ -303,9 +355,8 @@ std::vector<uint32_t> blocks_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 uint64_t blocks_scratch_bytes(const Geom &G);
 // resid: leave the residuals (not their running sums) in d_out: a general prediction filter's inverse follows (launch_iir)
 // fused_out: a general filter's inverse ran inside the kernel (no k_iir_tiles pass is needed behind it)
-hipError_t launch_decode_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
-                                const uint32_t *d_wave_words, void *d_blk, DevStatus *d_status, int16_t *d_out,
-                                const uint32_t **fail_out, const uint32_t **suspect_out, bool resid, hipStream_t s, bool *fused_out);
+hipError_t launch_decode_blocks(const StreamCall &c, void *d_blk, int16_t *d_out, const uint32_t **fail_out,
+                                const uint32_t **suspect_out, bool resid, bool *fused_out);
 // ... and for the other kernels of its scheme (drx_blocks.h; k_stats_blocks): the scratch's tables, and what one launch -- a
 // uniform batch, or one length class of a ragged one -- is given.  blocks_prepare() resets the scratch on the stream, chooses
 // the delta filter's geometry as launch_decode_blocks() does and has launched k_blk_max for every entry's info words.
@@ -422,9 +473,7 @@ uint64_t pieces_workgroups(const Geom &G);     // uniform batches it admits
 // the encoder does not take the batch)
 std::vector<uint32_t> pieces_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 uint64_t pieces_scan_words(const Geom &G, uint64_t total_wgs);  // uint64 words of its look-back state
-hipError_t launch_encode_pieces(const Geom &G, const int16_t *d_in, uint64_t in_samples, uint32_t *d_out, uint64_t out_cap,
-                                uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan, uint64_t total_wgs,
-                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s);
+hipError_t launch_encode_pieces(const EncodeCall &c, uint64_t in_samples, uint64_t *d_scan, uint64_t total_wgs);
 // in-place inverse of a general prediction filter over decoded residuals (drx_iir.hip): tiles of kIirThreads lanes x kIirRun
 // samples, decoupled look-back over kIirWin tiles per poll, tables of kIirTabWords uint32 per filter
 constexpr uint32_t kIirRun = 64, kIirThreads = 512, kIirTile = kIirRun * kIirThreads, kIirWin = 128;

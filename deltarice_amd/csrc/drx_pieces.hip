@@ -619,22 +619,24 @@ uint64_t pieces_scan_words(const Geom &G, uint64_t total_wgs) {
     return (pieces_super(G) ? G.total_waves + total_wgs : total_wgs) + 2u;
 }
 
-hipError_t launch_encode_pieces(const Geom &G, const int16_t *d_in, uint64_t in_samples, uint32_t *d_out, uint64_t out_cap,
-                                uint64_t *d_chunk_word_off, uint32_t *d_wave_words, uint64_t *d_scan, uint64_t total_wgs,
-                                DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_encode_pieces(const EncodeCall &c, uint64_t in_samples, uint64_t *d_scan, uint64_t total_wgs) {
+    const Geom &G = *c.G;
+    const EncOut &o = c.out;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0 || total_wgs == 0) return hipSuccess;
-    if (ev) (void)hipEventRecord(ev[0], s);
+    mark(c.ev, 0, s);
     // zeroed on the stream before every launch (an entry is its own ready flag)
     const uint64_t words = pieces_scan_words(G, total_wgs);
     hipError_t e = hipMemsetAsync(d_scan, 0, words * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
-    if (ev) { (void)hipEventRecord(ev[1], s); (void)hipEventRecord(ev[2], s); }
+    mark(c.ev, 1, s);
+    mark(c.ev, 2, s);
     uint32_t *ticket = reinterpret_cast<uint32_t *>(d_scan + words - 2u);
     auto go = [&](auto super_tag, auto gen_tag, auto packed_tag) {
         constexpr bool SUPER = decltype(super_tag)::value, GEN = decltype(gen_tag)::value, PACKED = decltype(packed_tag)::value;
         k_encode_pieces<SUPER, GEN, PACKED><<<(unsigned)total_wgs, 64 * kPcWaves, 0, s>>>(
-            G, d_in, in_samples, d_out, out_cap, d_chunk_word_off, d_wave_words, d_scan, SUPER ? d_scan + G.total_waves : nullptr, ticket,
-            (uint32_t)total_wgs, d_status);
+            G, c.d_in, in_samples, o.d_out, o.out_cap, o.d_chunk_word_off, o.d_wave_words, d_scan, SUPER ? d_scan + G.total_waves : nullptr, ticket,
+            (uint32_t)total_wgs, c.d_status);
     };
     const bool sup = pieces_super(G), gen = G.n_taps != 0, packed = pieces_packed(G);
     const std::true_type T;
@@ -642,7 +644,7 @@ hipError_t launch_encode_pieces(const Geom &G, const int16_t *d_in, uint64_t in_
     if (sup) { if (gen) go(T, T, F); else go(T, F, F); }
     else if (packed) { if (gen) go(F, T, T); else go(F, F, T); }
     else { if (gen) go(F, T, F); else go(F, F, F); }
-    if (ev) (void)hipEventRecord(ev[3], s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

@@ -234,35 +234,29 @@ __global__ __launch_bounds__(64) void k_find_pulses_serial(Geom G, const uint32_
     count_out[g] = P.count;
 }
 
-hipError_t launch_find_pulses(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                              uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, const int64_t *d_thr,
-                              uint64_t thr_stride, int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses,
-                              DevStatus *d_status, uint32_t *d_count, int64_t *d_out, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_find_pulses(const StreamCall &c, const int64_t *d_thr, uint64_t thr_stride, int64_t thr, bool neg,
+                              uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out) {
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
     // ---- the walk (drx_walk.hip): launch_batch_walk()
-    if (!tables_ready) {
-        const hipError_t e = launch_batch_walk(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
-        if (e != hipSuccess) return e;
-    }
-    mark(ev, 1, s);
+    hipError_t e = batch_walk_prologue(c);
+    if (e != hipSuccess) return e;
     // ---- the zero slots: the whole output, once (the lanes then store the records alone)
-    if (max_pulses) {
-        const hipError_t e = hipMemsetAsync(d_out, 0, (size_t)(G.total_waves * (uint64_t)max_pulses * DRX_PULSE_COLS * sizeof(int64_t)), s);
-        if (e != hipSuccess) return e;
-    }
+    if (max_pulses && (e = hipMemsetAsync(d_out, 0, (size_t)(G.total_waves * (uint64_t)max_pulses * DRX_PULSE_COLS * sizeof(int64_t)), s)) != hipSuccess)
+        return e;
     // ---- the kernel: a wavefront per 64 waveforms
     const bool serial = G.n_taps != 0;
     for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {
         if (serial)
-            k_find_pulses_serial<<<nb, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u, min_width,
-                                                   max_pulses, d_status, d_count, d_out);
+            k_find_pulses_serial<<<nb, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u, min_width,
+                                                   max_pulses, c.d_status, d_count, d_out);
         else
-            k_find_pulses<<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u,
-                                            min_width, max_pulses, d_status, d_count, d_out);
+            k_find_pulses<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u,
+                                            min_width, max_pulses, c.d_status, d_count, d_out);
     });
-    mark(ev, 2, s);
-    mark(ev, 3, s);
+    mark(c.ev, 2, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

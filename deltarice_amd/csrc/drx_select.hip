@@ -206,15 +206,14 @@ __global__ __launch_bounds__(64) void k_select_serial(Geom G, const uint32_t *__
 // A wavefront per entry up to kSelMaxGrid wavefronts (a selection of one launches one), which then stride over the list.
 constexpr uint64_t kSelMaxGrid = 1u << 20;
 
-hipError_t launch_decode_select(const Geom &G, const uint32_t *d_in, const uint64_t *d_wave_off, const uint32_t *d_wave_words,
-                                const uint64_t *d_sel, uint64_t n_sel, DevStatus *d_status, int16_t *d_out, uint64_t stride,
-                                hipStream_t s) {
+hipError_t launch_decode_select(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, int16_t *d_out, uint64_t stride) {
     if (!n_sel) return hipSuccess;
+    const Geom &G = *c.G;
     if (G.n_taps == 0)
-        k_decode_select<<<(unsigned)std::min<uint64_t>(n_sel, kSelMaxGrid), 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_sel, n_sel,
-                                                                                    d_status, d_out, stride);
+        k_decode_select<<<(unsigned)std::min<uint64_t>(n_sel, kSelMaxGrid), 64, 0, c.s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, d_sel, n_sel,
+                                                                                      c.d_status, d_out, stride);
     else
-        k_select_serial<<<blocks_for(n_sel, 64), 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, d_sel, n_sel, d_status, d_out, stride);
+        k_select_serial<<<blocks_for(n_sel, 64), 64, 0, c.s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, d_sel, n_sel, c.d_status, d_out, stride);
     return hipGetLastError();
 }
 

@@ -242,40 +242,33 @@ __global__ __launch_bounds__(64) void k_wave_stats_serial(Geom G, const uint32_t
     store_row(out, g, ((uintptr_t)out & 15u) == 0, v);
 }
 
-hipError_t launch_wave_stats(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                             uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, void *d_blk, void *d_sacc,
-                             uint32_t head_len, DevStatus *d_status, int64_t *d_out, hipEvent_t *ev, hipStream_t s, uint32_t *form_out) {
+hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, uint32_t *form_out) {
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
     const bool blocks = d_sacc != nullptr && stats_blocks_batch(G, d_blk);
     if (form_out) *form_out = blocks ? (DRX_STATS_FORM_BLOCKS | ((G.dbg & DRX_DBG_STATS_ALL_FALLBACK) ? DRX_STATS_FORM_FALLBACK_ALL : 0u)) : DRX_STATS_FORM_LANES;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
     // ---- the walk (drx_walk.hip), all of it on this stream: nothing here is worth a fork
-    if (!tables_ready) {
-        const hipError_t e = launch_batch_walk(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
-        if (e != hipSuccess) return e;
-    }
-    mark(ev, 1, s);
-    // ---- few long waveforms: a workgroup per block of a waveform's stream, then a lane per waveform that form lists (the
-    // launch is sized from here, at most a lane per waveform of the batch; the list's length is read on the device)
+    hipError_t e = batch_walk_prologue(c);
+    if (e != hipSuccess) return e;
     if (blocks) {
+        // ---- few long waveforms: a workgroup per block of a waveform's stream, then a lane per waveform that form lists (the
+        // launch is sized from here, at most a lane per waveform of the batch; the list's length is read on the device)
         const uint32_t *listed = nullptr, *n_listed = nullptr;
-        const hipError_t e = launch_stats_blocks(G, d_in, in_words, d_wave_off, d_wave_words, d_blk, d_sacc, head_len, d_status, d_out, &listed, &n_listed, s);
-        if (e != hipSuccess) return e;
-        k_wave_stats_serial<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, 0, head_len, d_status, d_out, listed, n_listed);
-        mark(ev, 2, s);
-        mark(ev, 3, s);
-        return hipGetLastError();
+        if ((e = launch_stats_blocks(c, d_blk, d_sacc, head_len, d_out, &listed, &n_listed)) != hipSuccess) return e;
+        k_wave_stats_serial<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, 0, head_len, c.d_status, d_out, listed, n_listed);
+    } else {
+        // ---- the kernel: a wavefront per 64 waveforms
+        const bool serial = G.n_taps != 0;
+        for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {
+            if (serial)
+                k_wave_stats_serial<<<nb, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, base, head_len, c.d_status, d_out, nullptr, nullptr);
+            else
+                k_wave_stats<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, head_len, c.d_status, d_out);
+        });
     }
-    // ---- the kernel: a wavefront per 64 waveforms
-    const bool serial = G.n_taps != 0;
-    for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {
-        if (serial)
-            k_wave_stats_serial<<<nb, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, base, head_len, d_status, d_out, nullptr, nullptr);
-        else
-            k_wave_stats<<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, head_len, d_status, d_out);
-    });
-    mark(ev, 2, s);
-    mark(ev, 3, s);
+    mark(c.ev, 2, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

@@ -124,23 +124,24 @@ bool stats_blocks_batch(const Geom &G, const void *d_blk) {
 // k_stats_blocks per launch of the block scheme, then k_stats_blocks_finish.  The block decoder's scratch is used as the decoder
 // uses it (calls on a plan are ordered on one stream) and reset on the stream first; d_sacc is the plan's scratch of this form.
 // listed_out / n_listed_out: the device list of the waveforms left to the lane kernel, and its length.
-hipError_t launch_stats_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_wave_off,
-                               const uint32_t *d_wave_words, void *d_blk, void *d_sacc, uint32_t head_len, DevStatus *d_status,
-                               int64_t *d_out, const uint32_t **listed_out, const uint32_t **n_listed_out, hipStream_t s) {
+hipError_t launch_stats_blocks(const StreamCall &call, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out,
+                               const uint32_t **listed_out, const uint32_t **n_listed_out) {
+    const Geom &G = *call.G;
+    const hipStream_t s = call.s;
     const StatsBlkScratch A = stats_blocks_layout(G, d_sacc);
     const unsigned nb = blocks_for(G.total_waves, 256);
     k_stats_blocks_reset<<<nb, 256, 0, s>>>(G.total_waves, A.acc, A.n_listed);
     BlkTables T;
     BlkClassLaunch cls[kBlkMaxClasses];
     uint32_t n_cls = 0;
-    const hipError_t e = blocks_prepare(G, in_words, d_wave_words, d_blk, s, &T, cls, &n_cls);
+    const hipError_t e = blocks_prepare(G, call.in_words, call.d_wave_words, d_blk, s, &T, cls, &n_cls);
     if (e != hipSuccess) return e;
     for (uint32_t i = 0; i < n_cls; ++i) {
         const BlkClassLaunch &c = cls[i];
         auto go = [&](auto nt_tag, auto sw_tag) {
             constexpr int NT = decltype(nt_tag)::value, SW = decltype(sw_tag)::value;
-            k_stats_blocks<NT, SW><<<c.grid, NT, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, c.info, c.spw, c.run_len, T.state, T.ends,
-                                                         c.info + 2, T.fail, T.suspect, d_status, head_len, A.acc, c.n_waves, c.list);
+            k_stats_blocks<NT, SW><<<c.grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, c.info, c.spw, c.run_len,
+                                                         T.state, T.ends, c.info + 2, T.fail, T.suspect, call.d_status, head_len, A.acc, c.n_waves, c.list);
         };
         auto by_sw = [&](auto nt_tag) {
             switch (c.sw) {
@@ -155,7 +156,7 @@ hipError_t launch_stats_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_
         else by_sw(std::integral_constant<int, 256>{});
     }
     k_stats_blocks_finish<<<nb, 256, 0, s>>>(G.total_waves, A.acc, T.fail, T.suspect, (G.dbg & DRX_DBG_STATS_ALL_FALLBACK) ? 1u : 0u, A.n_listed,
-                                             A.listed, d_status, d_out);
+                                             A.listed, call.d_status, d_out);
     *listed_out = A.listed;
     *n_listed_out = A.n_listed;
     return hipGetLastError();

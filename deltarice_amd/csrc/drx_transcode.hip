@@ -244,45 +244,43 @@ __global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__re
     for (uint32_t x = fl; x < ow; ++x) outB[x] = myout[(x & (uint32_t)(kOW - 1)) * 64u];
 }
 
-// ev: {start, walk's end, offsets' end, end}.  d_out == nullptr: as far as the offsets (the sizing call).  d_est != nullptr:
-// the estimate -- walk and k_recode_sizes<true> alone.
-hipError_t launch_transcode(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                            uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw, uint32_t k2,
-                            uint32_t *d_new_words, uint32_t *d_new_rel, uint64_t *d_new_chunk_words, uint32_t *d_out,
-                            uint64_t out_cap, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words,
-                            unsigned long long *d_est, DevStatus *d_status, hipEvent_t *ev, hipStream_t s) {
+// The estimate: the walk and k_recode_sizes<true> alone.  ev: {start, walk's end, kernel's end, end}
+hipError_t launch_estimate_words_encoded(const StreamCall &c, unsigned long long *d_est) {
+    const Geom &G = *c.G;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
+    hipError_t e = batch_walk_prologue(c);
+    if (e == hipSuccess) e = hipMemsetAsync(d_est, 0, 16 * sizeof(unsigned long long), c.s);
+    if (e != hipSuccess) return e;
+    for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
+        k_recode_sizes<true><<<nb, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, 0u, c.d_status, nullptr, nullptr, d_est);
+    });
+    mark(c.ev, 2, c.s);
+    mark(c.ev, 3, c.s);
+    return hipGetLastError();
+}
+
+// ev: {start, walk's end, offsets' end, end}.  out.d_out == nullptr: as far as the offsets (the sizing call).
+hipError_t launch_transcode(const StreamCall &c, uint32_t k2, const TrcScratch &t, const EncOut &out) {
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
+    if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip): launch_batch_walk()
-    if (!tables_ready) {
-        const hipError_t e = launch_batch_walk(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
-        if (e != hipSuccess) return e;
-    }
-    mark(ev, 1, s);
-    if (d_est) {
-        const hipError_t e = hipMemsetAsync(d_est, 0, 16 * sizeof(unsigned long long), s);
-        if (e != hipSuccess) return e;
-        for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
-            k_recode_sizes<true><<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, 0u, d_status, nullptr, nullptr, d_est);
-        });
-        mark(ev, 2, s);
-        mark(ev, 3, s);
-        return hipGetLastError();
-    }
+    hipError_t e = batch_walk_prologue(c);
+    if (e != hipSuccess) return e;
     // ---- sizes, scan, offsets
     for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
-        k_recode_sizes<false><<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, k2, d_status, d_new_words, d_out_wave_words, nullptr);
+        k_recode_sizes<false><<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, k2, c.d_status, t.words, out.d_wave_words, nullptr);
     });
-    hipError_t e = launch_chunk_offsets(G, d_new_words, d_new_rel, d_new_chunk_words, d_out_chunk_word_off, d_out ? out_cap : ~0ull, d_status, s);
+    e = launch_chunk_offsets(G, t.words, t.rel, t.chunk_words, out.d_chunk_word_off, out.d_out ? out.out_cap : ~0ull, c.d_status, s);
     if (e != hipSuccess) return e;
-    mark(ev, 2, s);
+    mark(c.ev, 2, s);
     // ---- pack
-    if (d_out) {
+    if (out.d_out) {
         for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
-            k_recode_pack<<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, k2, d_status, d_new_words, d_new_rel, d_out_chunk_word_off, d_out);
+            k_recode_pack<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, k2, c.d_status, t.words, t.rel, out.d_chunk_word_off, out.d_out);
         });
     }
-    mark(ev, 3, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

@@ -1071,43 +1071,41 @@ WalkRoute route_walk(const Geom &G, bool tables_ready, bool have_scratch) {
 // launchers.  Each sequence exists once and takes an optional chunk list (nullptr: every chunk of the batch); a failed launch
 // is the caller's hipGetLastError().
 // ---------------------------------------------------------------------------
-hipError_t launch_sideband_tables(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                  const uint32_t *d_n, uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s,
-                                  const uint32_t *d_list, uint32_t n_list) {
+hipError_t launch_sideband_tables(const StreamCall &c, const uint32_t *d_n, const uint32_t *d_list, uint32_t n_list) {
+    const Geom &G = *c.G;
     if (G.total_waves == 0 || (d_list && !n_list)) return hipSuccess;
-    k_sideband_tables<<<d_list ? n_list : (unsigned)G.n_chunks, 256, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_n, d_wave_off,
-                                                                          d_wave_words, d_status, d_list);
+    k_sideband_tables<<<d_list ? n_list : (unsigned)G.n_chunks, 256, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, d_n, c.d_wave_off,
+                                                                            c.d_wave_words, c.d_status, d_list);
     return hipGetLastError();
 }
 
 // The chunk-wide walk over n chunks, then the scalar walker for the chunks it flagged in fail (uint32[n_chunks], zeroed by the
 // caller), which also judges them.  chain_threads != 0: 64 chains per chunk chased in parallel from starts found by looking
 // forward from 64 cuts, by workgroups of so many threads (the chunk is not read); 0: the scan form, candidates in cand / cnt.
-static void walk_chunk_wide(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                            const uint32_t *d_list, uint32_t n, unsigned chain_threads, uint2 *cand, uint32_t *cnt, uint32_t *fail,
-                            uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
+static void walk_chunk_wide(const StreamCall &c, const uint32_t *d_list, uint32_t n, unsigned chain_threads, uint2 *cand, uint32_t *cnt,
+                            uint32_t *fail) {
+    const Geom &G = *c.G;
     if (chain_threads) {
-        k_walk_sparse<<<n, chain_threads, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, fail, d_list);
+        k_walk_sparse<<<n, chain_threads, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off, c.d_wave_words, fail, d_list);
     } else {
         const uint32_t parts = pw_parts(n);
-        k_pw_scan<<<(unsigned)(n * parts), 256, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_list, cand, cnt, parts);
-        k_walk_parallel<<<n, kPwThreads, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, fail, d_list, cand, cnt, parts);
+        k_pw_scan<<<(unsigned)(n * parts), 256, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, d_list, cand, cnt, parts);
+        k_walk_parallel<<<n, kPwThreads, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off, c.d_wave_words, fail, d_list, cand, cnt, parts);
     }
-    k_walk_scalar_only<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off,
-                                                                          d_wave_words, d_status, fail);
+    k_walk_scalar_only<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off,
+                                                                            c.d_wave_words, c.d_status, fail);
 }
-void launch_walk_chunk_wide(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                            uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, bool by_chains, hipStream_t s) {
-    const ParWalks P = par_walks(G, d_pw);
+void launch_walk_chunk_wide(const StreamCall &c, bool by_chains) {
+    const Geom &G = *c.G;
+    const ParWalks P = par_walks(G, c.d_pw);
     const unsigned chain_threads = (G.uniform && G.u_n_waves < 256u) ? 256u : (unsigned)kSwThreads;  // (few chains: few wavefronts)
-    walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, P.pw_list, P.n_pw, by_chains ? chain_threads : 0u, P.cand, P.cnt, P.pw_fail,
-                    d_wave_off, d_wave_words, d_status, s);
+    walk_chunk_wide(c, P.pw_list, P.n_pw, by_chains ? chain_threads : 0u, P.cand, P.cnt, P.pw_fail);
 }
 
 // The block-parallel walk over the batch's short-waveform chunks, then the LDS block walker for the chunks it flagged
-void launch_walk_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s) {
-    const ParWalks P = par_walks(G, d_pw);
+void launch_walk_blocks(const StreamCall &c) {
+    const Geom &G = *c.G;
+    const ParWalks P = par_walks(G, c.d_pw);
     const uint32_t *list = P.bw_list;
     const uint32_t n = P.n_bw;
     auto run_bw = [&](auto btag) {
@@ -1115,68 +1113,63 @@ void launch_walk_blocks(const Geom &G, const uint32_t *d_in, uint64_t in_words, 
         const uint32_t bmax = P.bw_blocks_max * (kWalkBlockWords / B);
         const unsigned grid = 256u * P.bw_waves_per_cu;
         if (P.hops)
-            k_bw_blocks<B, false, true><<<grid, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, list, n, bmax, P.info, nullptr, nullptr, nullptr, d_status, P.hops, P.bw_hop_cap);
+            k_bw_blocks<B, false, true><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, nullptr, nullptr, nullptr, c.d_status, P.hops, P.bw_hop_cap);
         else
-            k_bw_blocks<B, false><<<grid, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, list, n, bmax, P.info, nullptr, nullptr, nullptr, d_status, nullptr, 0u);
-        k_bw_scan<B><<<n, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, list, n, bmax, P.info, P.bw_fail);
+            k_bw_blocks<B, false><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, nullptr, nullptr, nullptr, c.d_status, nullptr, 0u);
+        k_bw_scan<B><<<n, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail);
         if (P.hops)
-            k_bw_emit<B><<<256u * 8u, 256, 0, s>>>(G, in_words, d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, P.hops, P.bw_hop_cap, d_wave_off, d_wave_words, d_status);
+            k_bw_emit<B><<<256u * 8u, 256, 0, c.s>>>(G, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, P.hops, P.bw_hop_cap, c.d_wave_off, c.d_wave_words, c.d_status);
         else
-            k_bw_blocks<B, true><<<grid, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, d_wave_off, d_wave_words, d_status, nullptr, 0u);
+            k_bw_blocks<B, true><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, c.d_wave_off, c.d_wave_words, c.d_status, nullptr, 0u);
     };
     if (P.bw_B == 1024u) run_bw(std::integral_constant<uint32_t, 1024>{});
     else if (P.bw_B == 2048u) run_bw(std::integral_constant<uint32_t, 2048>{});
     else run_bw(std::integral_constant<uint32_t, 4096>{});
-    k_walk_block_only<<<(unsigned)G.n_chunks, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, P.bw_fail);
+    k_walk_block_only<<<(unsigned)G.n_chunks, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off, c.d_wave_words, c.d_status, P.bw_fail);
 }
 
 // The serial walk: chunks of short waveforms streamed through LDS, a wavefront per chunk; chunks of long waveforms one
 // dependent load per hop, a lane per chunk (d_long == nullptr: every chunk of the batch, by scalar loads)
-static void walk_serial(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                        const uint32_t *d_short, uint32_t n_short, const uint32_t *d_long, uint32_t n_long,
-                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
+static void walk_serial(const StreamCall &c, const uint32_t *d_short, uint32_t n_short, const uint32_t *d_long, uint32_t n_long) {
+    const Geom &G = *c.G;
     if (n_short)
-        k_walk_block<<<n_short, 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_short, n_short, d_wave_off, d_wave_words, d_status);
+        k_walk_block<<<n_short, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, d_short, n_short, c.d_wave_off, c.d_wave_words, c.d_status);
     if (n_long && d_long)
-        k_walk_list<<<blocks_for(n_long, 64), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_long, n_long, d_wave_off, d_wave_words, d_status);
+        k_walk_list<<<blocks_for(n_long, 64), 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, d_long, n_long, c.d_wave_off, c.d_wave_words, c.d_status);
     else if (n_long)
-        k_walk_scalar<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, s>>>(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status);
+        k_walk_scalar<<<blocks_for(G.n_chunks, kWalkChains), 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, c.d_wave_off, c.d_wave_words, c.d_status);
 }
-void launch_walk_serial(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                        uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
-    if (!G.uniform) return walk_serial(G, d_in, in_words, d_chunk_word_off, G.walk_short, G.n_short, G.walk_long, G.n_long, d_wave_off, d_wave_words, d_status, s);
+void launch_walk_serial(const StreamCall &c) {
+    const Geom &G = *c.G;
+    if (!G.uniform) return walk_serial(c, G.walk_short, G.n_short, G.walk_long, G.n_long);
     const uint32_t n = (uint32_t)G.n_chunks, n_short = G.u_wave_len <= kWalkShortLen ? n : 0u;
-    walk_serial(G, d_in, in_words, d_chunk_word_off, nullptr, n_short, nullptr, n - n_short, d_wave_off, d_wave_words, d_status, s);
+    walk_serial(c, nullptr, n_short, nullptr, n - n_short);
 }
 
 // The walk in front of a call that reads the whole batch behind it, on one stream
-hipError_t launch_batch_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                             uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, void *d_pw, hipStream_t s) {
-    const WalkRoute R = route_walk(G, false, d_pw != nullptr);
+hipError_t launch_batch_walk(const StreamCall &c) {
+    const WalkRoute R = route_walk(*c.G, false, c.d_pw != nullptr);
     if (R.chunk_wide || R.blocks) {
-        const hipError_t e = walk_scratch_reset(G, d_pw, s);
+        const hipError_t e = walk_scratch_reset(*c.G, c.d_pw, c.s);
         if (e != hipSuccess) return e;
-        if (R.chunk_wide) launch_walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, R.by_chains, s);
-        if (R.blocks) launch_walk_blocks(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
+        if (R.chunk_wide) launch_walk_chunk_wide(c, R.by_chains);
+        if (R.blocks) launch_walk_blocks(c);
     } else {
-        launch_walk_serial(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, s);
+        launch_walk_serial(c);
     }
     return hipGetLastError();
 }
 
 // The walk in front of drx_decode_select: the chunks its selection touches and no others.  d_lists = the three lists of
 // select_walk_class() back to back; d_fail: uint32[n_chunks], cleared here.  Always by chains, in workgroups of kSwThreads.
-hipError_t launch_select_walk(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                              const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain, uint32_t *d_fail,
-                              uint64_t *d_wave_off, uint32_t *d_wave_words, DevStatus *d_status, hipStream_t s) {
+hipError_t launch_select_walk(const StreamCall &c, const uint32_t *d_lists, uint32_t n_sparse, uint32_t n_block, uint32_t n_chain,
+                              uint32_t *d_fail) {
     if (n_sparse) {
-        const hipError_t e = hipMemsetAsync(d_fail, 0, G.n_chunks * sizeof(uint32_t), s);
+        const hipError_t e = hipMemsetAsync(d_fail, 0, c.G->n_chunks * sizeof(uint32_t), c.s);
         if (e != hipSuccess) return e;
-        walk_chunk_wide(G, d_in, in_words, d_chunk_word_off, d_lists, n_sparse, kSwThreads, nullptr, nullptr, d_fail, d_wave_off, d_wave_words,
-                        d_status, s);
+        walk_chunk_wide(c, d_lists, n_sparse, kSwThreads, nullptr, nullptr, d_fail);
     }
-    walk_serial(G, d_in, in_words, d_chunk_word_off, d_lists + n_sparse, n_block, d_lists + n_sparse + n_block, n_chain, d_wave_off,
-                d_wave_words, d_status, s);
+    walk_serial(c, d_lists + n_sparse, n_block, d_lists + n_sparse + n_block, n_chain);
     return hipGetLastError();
 }
 

@@ -211,31 +211,27 @@ __global__ __launch_bounds__(64) void k_decode_window_serial(Geom G, const uint3
     if (w.e == r.len ? words != n : words > n) atomicOr(&st->err, kErrCorrupt);
 }
 
-hipError_t launch_decode_window(const Geom &G, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
-                                uint64_t *d_wave_off, uint32_t *d_wave_words, bool tables_ready, void *d_pw,
-                                const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
-                                DevStatus *d_status, int16_t *d_out, uint64_t out_stride, hipEvent_t *ev, hipStream_t s) {
+hipError_t launch_decode_window(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width,
+                                int16_t pad, int16_t *d_out, uint64_t out_stride) {
+    const Geom &G = *c.G;
+    const hipStream_t s = c.s;
     if (G.total_waves == 0) return hipSuccess;
-    mark(ev, 0, s);
     // ---- the walk (drx_walk.hip): launch_batch_walk()
-    if (!tables_ready) {
-        const hipError_t e = launch_batch_walk(G, d_in, in_words, d_chunk_word_off, d_wave_off, d_wave_words, d_status, d_pw, s);
-        if (e != hipSuccess) return e;
-    }
-    mark(ev, 1, s);
+    const hipError_t e = batch_walk_prologue(c);
+    if (e != hipSuccess) return e;
     // ---- the kernel: a wavefront per 64 waveforms
     const bool serial = G.n_taps != 0;
     const uint32_t pad2 = (uint32_t)(uint16_t)pad * 0x10001u;
     for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {
         if (serial)
-            k_decode_window_serial<<<nb, 64, 0, s>>>(G, d_in, d_wave_off, d_wave_words, base, d_start, start_stride, offset, width, pad2,
-                                                     d_status, d_out, out_stride);
+            k_decode_window_serial<<<nb, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, base, d_start, start_stride, offset, width, pad2,
+                                                     c.d_status, d_out, out_stride);
         else
-            k_decode_window<<<nb, 64, 0, s>>>(G, d_in, in_words, d_wave_off, d_wave_words, base, d_start, start_stride, offset, width,
-                                              pad2, d_status, d_out, out_stride);
+            k_decode_window<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, d_start, start_stride, offset, width,
+                                              pad2, c.d_status, d_out, out_stride);
     });
-    mark(ev, 2, s);
-    mark(ev, 3, s);
+    mark(c.ev, 2, s);
+    mark(c.ev, 3, s);
     return hipGetLastError();
 }
 

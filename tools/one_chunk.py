@@ -15,7 +15,7 @@ words = torch.empty(plan.max_encoded_words, dtype=torch.int32, device=ctx.device
 off = torch.empty(2, dtype=torch.int64, device=ctx.device)
 y = torch.empty_like(x)
 torch.cuda.synchronize()
-for impl in (8, 7, 1):
+for impl in (8, 7, 0):
     ctx.set_option("decode_impl", impl)
     for _ in range(3):
         t0 = time.perf_counter(); plan.encode_async(x, words, off); plan.finish(); t1 = time.perf_counter()
