@@ -47,8 +47,13 @@ DBG_WALK_BY_CHAINS = 16777216
 DBG_GATHER_OTHER_COPY = 33554432
 DBG_STATS_LANES = 67108864
 DBG_STATS_ALL_FALLBACK = 134217728
+DBG_PULSES_LANES = 268435456
+DBG_PULSES_ALL_FALLBACK = 536870912
 # DRX_STATS_FORM_*: drx_plan_last_stats_form (tests/test_wave_stats_blocks_abi.py holds them equal)
 STATS_FORM_LANES, STATS_FORM_BLOCKS, STATS_FORM_FALLBACK_ALL = 1, 2, 4
+# DRX_PULSES_FORM_*: drx_plan_last_pulses_form (tests/test_find_pulses_blocks_abi.py holds them equal)
+PULSES_FORM_LANES, PULSES_FORM_BLOCKS, PULSES_FORM_FALLBACK_ALL = 1, 2, 4
+PULSES_STAGE_CAP = 8  # DRX_PULSES_STAGE_CAP
 
 
 class DrxOpts(C.Structure):
@@ -90,6 +95,9 @@ SIGNATURES = {
     "drx_plan_last_decode_path": (C.c_uint32, [_vp]),
     "drx_plan_last_encode_path": (C.c_uint32, [_vp]),
     "drx_plan_last_stats_form": (C.c_uint32, [_vp]),
+    "drx_plan_last_pulses_form": (C.c_uint32, [_vp]),
+    "drx_plan_last_pulses_listed": (C.c_uint32, [_vp]),
+    "drx_plan_last_pulses_redone": (C.c_uint32, [_vp]),
     "drx_plan_read_wave_words": (C.c_int, [_vp, C.POINTER(_u32)]),
     "drx_encode": (C.c_int, [_vp, _vp, _vp, _u64, _vp]),
     "drx_decode": (C.c_int, [_vp, _vp, _u64, _vp, _vp]),

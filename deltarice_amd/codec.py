@@ -681,6 +681,22 @@ class Plan:
         per block of a waveform's stream (few long waveforms); 0 before the plan's first statistics call."""
         return int(self.ctx.lib.drx_plan_last_stats_form(self._h))
 
+    def last_pulses_form(self) -> int:
+        """DRX_PULSES_FORM_* (include/deltarice_hip.h): which form the last find_pulses took -- a lane per waveform, or a
+        workgroup per block of a waveform's stream with the runs stitched behind it (few long waveforms); 0 before the plan's
+        first pulse call."""
+        return int(self.ctx.lib.drx_plan_last_pulses_form(self._h))
+
+    def last_pulses_listed(self) -> int:
+        """After finish(): how many waveforms the last find_pulses' block form handed to the lane kernel behind it (flagged by the
+        block parse, or short of staged records); 0 for the lane form."""
+        return int(self.ctx.lib.drx_plan_last_pulses_listed(self._h))
+
+    def last_pulses_redone(self) -> int:
+        """After finish(): how many waveforms the last find_pulses' block form finished by its second launch of the blocks (a block
+        of theirs had staged fewer records than the waveform needs: max_pulses above PULSES_STAGE_CAP only); 0 for the lane form."""
+        return int(self.ctx.lib.drx_plan_last_pulses_redone(self._h))
+
     def last_encode_path(self) -> int:
         """DRX_ENC_* (include/deltarice_hip.h): the encoder the last encode used."""
         return int(self.ctx.lib.drx_plan_last_encode_path(self._h))

@@ -122,6 +122,10 @@ struct drx_plan {
     void *d_blk = nullptr;             // few waveforms: unit table, look-back state and flags of the block-parallel decoder
     void *d_sacc = nullptr;            // ... and drx_wave_stats' block form: accumulators and list, allocated by its first call
     uint32_t last_stats_form = 0;      // DRX_STATS_FORM_* of the last drx_wave_stats (0: none yet)
+    void *d_ptab = nullptr;            // ... and drx_find_pulses' block form: block summaries and list, allocated by its first call
+    void *d_pstage = nullptr;          // ... and the records its blocks stage, grown when a call needs more (pulses_staging())
+    size_t pstage_cap = 0;
+    uint32_t last_pulses_form = 0;     // DRX_PULSES_FORM_* of the last drx_find_pulses (0: none yet)
     DevStatus *d_status = nullptr;
     DevStatus *h_status = nullptr;  // pinned
     bool last_was_encode = false;
@@ -628,6 +632,9 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *p) { return p ? p->d_wave
 uint32_t drx_plan_last_decode_path(const drx_plan *p) { return p ? p->last_path : 0u; }
 uint32_t drx_plan_last_encode_path(const drx_plan *p) { return p ? p->last_enc_path : 0u; }
 uint32_t drx_plan_last_stats_form(const drx_plan *p) { return p ? p->last_stats_form : 0u; }
+uint32_t drx_plan_last_pulses_form(const drx_plan *p) { return p ? p->last_pulses_form : 0u; }
+uint32_t drx_plan_last_pulses_redone(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_PULSES) ? p->h_status->redone : 0u; }
+uint32_t drx_plan_last_pulses_listed(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_PULSES) ? p->h_status->listed : 0u; }
 
 drx_status drx_plan_read_wave_words(drx_plan *p, uint32_t *host_out) {
     if (!p || !host_out) return DRX_ERR_ARG;
@@ -1113,6 +1120,20 @@ drx_status drx_decode_window_with_wave_words(drx_plan *p, const uint32_t *d_in, 
 // ---------------------------------------------------------------------------
 // every pulse of every waveform: threshold discrimination (drx_pulses.hip)
 // ---------------------------------------------------------------------------
+// The block form's staging buffer (pulses_blocks_staging_bytes()); grown like the gather's scratch.
+static drx_status pulses_staging(drx_plan *p, size_t bytes) {
+    drx_ctx *ctx = p->ctx;
+    if (p->pstage_cap >= bytes) return DRX_OK;
+    void *d = nullptr;
+    const hipError_t e = p->mem.alloc(&d, bytes);
+    if (e != hipSuccess) return fail(ctx, DRX_ERR_NOMEM, "find_pulses: staging of %zu bytes: %s", bytes, hipGetErrorString(e));
+    DRX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still use the old one)
+    p->mem.release(p->d_pstage);
+    p->d_pstage = d;
+    p->pstage_cap = bytes;
+    return DRX_OK;
+}
+
 static drx_status find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                               const uint32_t *d_sideband, bool sideband, const int64_t *d_thr, uint64_t thr_stride, int64_t thr,
                               int32_t polarity, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out) {
@@ -1126,7 +1147,13 @@ static drx_status find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_wor
     DRX_ON_DEVICE(ctx);
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
-    DRX_HIP(ctx, launch_find_pulses(c, d_thr, thr_stride, thr, polarity < 0, min_width, max_pulses, d_count, d_out));
+    // the block form's summaries, list and staged records belong to the plan: allocated by its first call that takes that form
+    if (pulses_blocks_batch(p->G, p->d_blk)) {
+        if (!p->d_ptab) DRX_HIP(ctx, p->mem.alloc(&p->d_ptab, pulses_blocks_scratch_bytes(p->G)));
+        if (const drx_status st = pulses_staging(p, pulses_blocks_staging_bytes(p->G, max_pulses))) return st;
+    }
+    DRX_HIP(ctx, launch_find_pulses(c, p->d_blk, p->d_ptab, p->d_pstage, d_thr, thr_stride, thr, polarity < 0, min_width, max_pulses, d_count,
+                                    d_out, &p->last_pulses_form));
     return call_end(p, DRX_PATH_PULSES);
 }
 

@@ -1,8 +1,9 @@
 // drx_blocks.h -- the block-parallel parse shared by the kernels that give a WORKGROUP a block of a waveform's stream
 // (not installed): the block geometry, the parse, and (drx_blocks_body.inc) the body of k_decode_blocks (drx_blocks.hip: the samples,
-// in output order, to HBM) and of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics).
+// in output order, to HBM), of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics) and of
+// k_pulses_blocks (drx_pulses_blocks.hip: the runs of samples over a threshold, per block, stitched behind the kernel).
 // drx_blocks.hip's head comment describes the scheme.  A kernel that takes this route for another purpose adds its own
-// phase 2 behind the same phase 1, look-back and flags, as the STATS form does.
+// phase 2 behind the same phase 1, look-back and flags, as the STATS and PULSES forms do.
 #ifndef DRX_BLOCKS_H
 #define DRX_BLOCKS_H
 
@@ -13,6 +14,7 @@
 #include "drx_device.h"
 #include "drx_internal.h"
 #include "drx_iir_math.h"
+#include "drx_pulse_runs.h"
 
 namespace drx {
 
@@ -233,6 +235,25 @@ __device__ __forceinline__ void blk_skip_pairs(const uint32_t *W, uint32_t k, bo
 struct BlkStatsArgs {
     uint32_t head_len;        // DRX_STAT_HEAD_* cover the samples in front of min(head_len, len)
     unsigned long long *acc;  // [waveform][6]: min key, max key, sum, sum of squares, head sum, head sum of squares
+};
+// PULSES (delta filter only): phase 2 looks for runs of samples over the waveform's threshold instead (drx_pulses_blocks.hip):
+// the block's own pulses go to its staging slots, the runs that touch its first and its last sample into its summary.
+constexpr uint32_t kPulseTabWords = 8;  // uint64 words of a block's published summary (drx_pulses_blocks.hip has the layout)
+struct BlkPulseArgs {
+    const int64_t *thr_tab;  // per-waveform thresholds (nullptr: none), thr_stride entries apart, + thr
+    uint64_t thr_stride;
+    int64_t thr;
+    uint32_t neg, min_width;
+    uint32_t cap;       // records a block stages: min(max_pulses, kPulseStageCap); 0: the counting form
+    uint64_t *table;    // [block slot][kPulseTabWords]
+    int64_t *staging;   // [block slot][cap][DRX_PULSE_COLS]
+    // the second launch, over the waveforms whose blocks staged too few records (n_redo != nullptr): the launch's waveforms
+    // are wave_list[0 .. *n_redo), a count written on the device; word kPulseSegWords of a block's table entry holds the number
+    // of the block's first pulse in its waveform (k_pulses_stitch wrote it), and the block stores pulse r straight to slot
+    // first + r < max_pulses of the caller's records
+    const uint32_t *n_redo;
+    uint32_t max_pulses;
+    int64_t *out;
 };
 
 

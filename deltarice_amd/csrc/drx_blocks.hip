@@ -76,8 +76,9 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                                                       DevStatus *st, int16_t *__restrict__ out, uint32_t n_list,
                                                       const uint32_t *__restrict__ itab, uint64_t *__restrict__ xstate,
                                                       const uint32_t *__restrict__ wave_list) {
-    constexpr bool STATS = false;
+    constexpr bool STATS = false, PULSES = false;
     const BlkStatsArgs sa{0u, nullptr};
+    const BlkPulseArgs pa{};
 #include "drx_blocks_body.inc"
 }
 
@@ -207,6 +208,7 @@ static BlkScratch blocks_layout(const Geom &G, void *base) {
 }
 
 uint64_t blocks_scratch_bytes(const Geom &G) { return blocks_batch(G) ? blocks_layout(G, nullptr).bytes : 0; }
+uint64_t blocks_total_slots(const Geom &G) { return G.total_waves * blocks_slots_per_wave(G); }
 
 static unsigned blk_resident(int nt) { return 256u * (nt == 64 ? 12u : (nt == 128 ? 6u : 3u)); }  // workgroups per CU by LDS: 50 dwords per lane in every class
 // the block geometry of a call: by the stream's bits per sample as the caller states them (a wrong in_words costs speed, nothing else)

@@ -1,8 +1,8 @@
 // drx_blocks_body.inc -- the body of a kernel that gives a workgroup a block of a waveform's stream, included INSIDE the kernel's
-// definition (k_decode_blocks, drx_blocks.hip; k_stats_blocks, drx_stats_blocks.hip) behind its arguments: text, not a function,
-// because k_decode_blocks is sensitive to how its arguments reach it (an inlined function with the same body was compiled to
-// other code: other spills, another schedule).  The including kernel provides NT, RESID, SW, FUSE, STATS, the arguments of
-// k_decode_blocks by name, and `sa` (BlkStatsArgs).
+// definition (k_decode_blocks, drx_blocks.hip; k_stats_blocks, drx_stats_blocks.hip; k_pulses_blocks, drx_pulses_blocks.hip)
+// behind its arguments: text, not a function, because k_decode_blocks is sensitive to how its arguments reach it (an inlined
+// function with the same body was compiled to other code: other spills, another schedule).  The including kernel provides NT,
+// RESID, SW, FUSE, STATS, PULSES, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs) and `pa` (BlkPulseArgs).
     static_assert(!FUSE || RESID, "the fused inverse filter works on residuals");
     using BG = BlkGeom<NT, SW>;
     constexpr int kBlkSegW = SW;
@@ -38,7 +38,9 @@
     // four waits: ticket, image, predecessor's end, look-back (profiles/r02_notes.md).
     // the waveforms of THIS launch: all of the batch, or (ragged batches) those of one length class -- tickets are dealt
     // run-major over them, and a class whose waveforms differ by less than 2x in length wastes few tickets on empty runs
-    const uint32_t n_waves32 = wave_list ? n_list : (uint32_t)G.total_waves;
+    uint32_t n_waves32_ = wave_list ? n_list : (uint32_t)G.total_waves;
+    if constexpr (PULSES) { if (pa.n_redo) n_waves32_ = *pa.n_redo; }  // (a list whose length is known on the device alone)
+    const uint32_t n_waves32 = n_waves32_;
     const uint32_t max_runs = (info[0] + run_len - 1u) / run_len;
     const uint64_t total_units64 = (uint64_t)max_runs * n_waves32;
     const uint32_t total_units = total_units64 > 0xffffffffull ? 0xffffffffu : (uint32_t)total_units64;
@@ -246,6 +248,8 @@
         const uint32_t len = r.len;
         int16_t *y = out + r.sample_off;
         const uint32_t n_blocks = (n + BG::kWords - 1u) / BG::kWords;
+        [[maybe_unused]] int32_t p_tv = 0;  // PULSES: the waveform's clamped threshold, v > p_tv is over
+        if constexpr (PULSES) p_tv = pulse_threshold(pa.thr_tab != nullptr, pa.thr_tab ? pa.thr_tab[g * pa.thr_stride] : 0, pa.thr, pa.neg != 0u);
         RunRef nxt = cur;
         uint32_t next_unit = 0xffffffffu;
         if (blk_lo >= blk_hi) {  // an empty run (a waveform with fewer blocks than the longest): only the hand-over
@@ -513,7 +517,124 @@
                     xs = V3{(uint32_t)v & 0xffffu, (uint32_t)(v >> 16) & 0xffffu, (uint32_t)(v >> 32) & 0xffffu};
                 }
             }
-            if constexpr (STATS) {
+            if constexpr (PULSES) {
+                // ---- phase 2, pulses: every lane summarises the runs of over-threshold samples among its own samples
+                // (drx_pulse_runs.h), a scan over the lanes with pulse_combine() tells each what lies in front of it inside
+                // the block -- the run open there and how many of the block's pulses -- and a second pass over the same staged
+                // values stores the pulses that close in the lane's samples to the block's staging slots, numbered inside the
+                // block.  The runs that touch the block's first and last sample are nobody's pulse yet: they go out with the
+                // block's summary, and k_pulses_stitch joins them across blocks behind this kernel.  A lane's samples are read
+                // as the statistics form reads them: from the running sums phase 1 staged, or from a second parse.
+                const uint32_t base16 = (acc_base + pre_s + incl_s - sum) & 0xffffu;  // the running sum in front of my first sample
+                const uint32_t i0 = blk_first + rel0;                                 // its index in the waveform
+                const uint32_t fl = pa.neg ? 0xffffu : 0u;
+                const uint32_t mw = pa.min_width;
+                const bool reparse = wg_any(cnt > kBlkLaneCap);
+                auto samples = [&](auto &&take) __attribute__((always_inline)) {  // take(c, v): my sample c as v = y ^ flip
+                    if (!reparse) {
+                        for (uint32_t i = 0; 2u * i < todo; ++i) {
+                            const uint32_t d = my_stage[i];
+                            take(2u * i, (int32_t)(int16_t)(uint16_t)((base16 + (d & 0xffffu)) ^ fl));
+                            if (2u * i + 1u < todo) take(2u * i + 1u, (int32_t)(int16_t)(uint16_t)((base16 + (d >> 16)) ^ fl));
+                        }
+                    } else {
+                        uint32_t Qr = C - (todo ? f : B0), rs = 0;
+                        for (uint32_t c = 0; c < todo; ++c) {
+                            const BlkPair p = blk_pair<true>(W, k, Qr);
+                            rs += unzigzag(p.z1);
+                            Qr += p.nu1;
+                            take(c, (int32_t)(int16_t)(uint16_t)((base16 + rs) ^ fl));
+                        }
+                    }
+                };
+                // the fast reject, a lane at a time: a packed maximum over its staged pairs says that none of its samples is over
+                bool look = todo != 0u;
+                if (!reparse && todo != 0u) {
+                    typedef short s16x2 __attribute__((ext_vector_type(2)));
+                    typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+                    const u16x2 b2 = {(uint16_t)base16, (uint16_t)base16};
+                    const uint32_t pm = fl | (fl << 16);
+                    s16x2 gm = {-32768, -32768};
+                    for (uint32_t i = 0; 2u * i < todo; ++i) {
+                        uint32_t d = my_stage[i];
+                        if (2u * i + 1u >= todo) d = __builtin_amdgcn_perm(d, d, 0x05040504u);  // (my last sample twice: the high half is not mine)
+                        const uint32_t v2 = __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, d) + b2)) ^ pm;
+                        gm = __builtin_elementwise_max(gm, __builtin_bit_cast(s16x2, v2));
+                    }
+                    look = (gm.x > gm.y ? (int32_t)gm.x : (int32_t)gm.y) > p_tv;
+                }
+                // pass 1: my summary
+                PulseSeg S = pulse_seg_empty();
+                if (look) {
+                    samples([&](uint32_t c, int32_t v) __attribute__((always_inline)) { pulse_seg_step(S, v, p_tv, i0 + c, mw); });
+                    pulse_seg_finish(S);
+                } else {
+                    S.n = todo;
+                }
+                uint64_t *const tab = pa.table + (uint64_t)sidx * kPulseTabWords;
+                static_assert(kPulseSegWords <= (int)kPulseTabWords, "a block slot of the table holds a packed summary");
+                const bool redo = pa.n_redo != nullptr;  // the second launch: nothing is published, the pulses go to the caller's slots
+                const uint32_t first_no = redo ? (uint32_t)tab[kPulseSegWords] : 0u;  // (read only where the block holds a pulse: the stitch wrote it)
+                auto publish = [&](const PulseSeg &T) __attribute__((always_inline)) { if (!redo) pulse_seg_pack(T, tab); };
+                if (!wg_any((S.lead_w | S.trail_w | S.inner) != 0u)) {
+                    // nothing over that matters in the whole block (runs shorter than min_width inside one lane leave no trace)
+                    if (tid == 0u) {
+                        PulseSeg T = pulse_seg_empty();
+                        T.n = blk_count;
+                        publish(T);
+                    }
+                } else {
+                    // the scan: inside the wavefront by shuffles, across the wavefronts through s_e (its last reader is a barrier back)
+                    // (every lane shuffles, then selects: a shuffle under a condition reads nothing from the lanes the condition leaves out)
+                    auto up = [&](const PulseSeg &X, int d) __attribute__((always_inline)) {  // the summary `d` lanes down; the empty one below lane d
+                        const bool have = lane >= d;
+                        const uint32_t n_ = (uint32_t)__shfl_up((int)X.n, d), inner_ = (uint32_t)__shfl_up((int)X.inner, d);
+                        const uint32_t lead_w_ = (uint32_t)__shfl_up((int)X.lead_w, d), trail_w_ = (uint32_t)__shfl_up((int)X.trail_w, d);
+                        const uint32_t trail_s_ = (uint32_t)__shfl_up((int)X.trail_s, d);
+                        const int64_t lead_key_ = (int64_t)__shfl_up((long long)X.lead_key, d), lead_sum_ = (int64_t)__shfl_up((long long)X.lead_sum, d);
+                        const int64_t trail_key_ = (int64_t)__shfl_up((long long)X.trail_key, d), trail_sum_ = (int64_t)__shfl_up((long long)X.trail_sum, d);
+                        PulseSeg U;
+                        U.n = have ? n_ : 0u;
+                        U.inner = have ? inner_ : 0u;
+                        U.lead_w = have ? lead_w_ : 0u;
+                        U.trail_w = have ? trail_w_ : 0u;
+                        U.trail_s = have ? trail_s_ : 0u;
+                        U.lead_key = have ? lead_key_ : kPulseNoKey;
+                        U.lead_sum = have ? lead_sum_ : (int64_t)0;
+                        U.trail_key = have ? trail_key_ : kPulseNoKey;
+                        U.trail_sum = have ? trail_sum_ : (int64_t)0;
+                        return U;
+                    };
+                    PulseSeg I = S;
+#pragma unroll
+                    for (int dd = 0; dd < 6; ++dd) I = pulse_combine(up(I, 1 << dd), I, mw);
+                    const PulseSeg E = up(I, 1);  // what lies in front of me as far as my wavefront knows
+                    uint64_t *const s_seg = reinterpret_cast<uint64_t *>(s_e);  // [NW][kPulseSegWords]: 56 NW bytes of s_e's 4 NT
+                    if (lane == 63) pulse_seg_pack(I, s_seg + kPulseSegWords * wv);
+                    blk_barrier();
+                    auto wave_total = [&](int w) __attribute__((always_inline)) { return pulse_seg_unpack(s_seg + kPulseSegWords * w); };
+                    PulseSeg P = pulse_seg_empty();  // ... and in front of my wavefront
+                    for (int w = 0; w < wv; ++w) P = pulse_combine(P, wave_total(w), mw);
+                    // the block's summary: the last thread has every wavefront in front of its own, and its own from LDS (of its
+                    // own summary S only n, lead_w and inner are needed from here on: fewer registers across pass 2)
+                    if (tid == (uint32_t)NT - 1u) publish(pulse_combine(P, wave_total(wv), mw));
+                    P = pulse_combine(P, E, mw);
+                    // pass 2: the pulses that close among my samples.  None does where every sample of mine is over, or where no
+                    // run is open in front of me and my own summary holds none that closed
+                    if (todo != 0u && S.lead_w != S.n && (P.trail_w | S.lead_w | S.inner) != 0u) {
+                        PulseEmit em = pulse_emit_seed(P);
+                        int64_t *const slots = redo ? pa.out + (g * (uint64_t)pa.max_pulses + first_no) * (uint64_t)kPulseRecCols
+                                                    : pa.staging + (uint64_t)sidx * pa.cap * (uint64_t)kPulseRecCols;
+                        const uint32_t room = redo ? (pa.max_pulses > first_no ? pa.max_pulses - first_no : 0u) : pa.cap;
+                        samples([&](uint32_t c, int32_t v) __attribute__((always_inline)) {
+                            pulse_emit_step(em, v, p_tv, i0 + c, blk_first, mw,
+                                            [&](uint32_t r, uint32_t rs0, uint32_t rw, int64_t key, int64_t rsum) __attribute__((always_inline)) {
+                                                if (r < room) pulse_record(slots + (uint64_t)r * kPulseRecCols, rs0, rw, key, rsum, pa.neg != 0u);
+                                            });
+                        });
+                    }
+                }
+            } else if constexpr (STATS) {
                 // ---- phase 2, statistics: every lane reduces its own samples, the block folds the result into the waveform's
                 // accumulator.  Everything in front of a lane's first code is exact by now -- its index in the waveform, how many
                 // of its codes are samples, the running sum in front of them -- and has to be: samples wrap modulo 2^16, so an

@@ -90,8 +90,10 @@ struct Geom {
 
 struct DevStatus {
     uint32_t err;  // kErr* bits, OR-ed by kernels
-    uint32_t pad_;
+    uint32_t listed;  // drx_find_pulses, block form: the waveforms handed to the lane kernel behind the stitch
     uint64_t total_words;  // encode: words of the encoded batch
+    uint32_t redone;       // drx_find_pulses, block form: the waveforms whose blocks its second launch ran again
+    uint32_t pad_;
 };
 
 constexpr uint32_t kErrCapacity = 1u;
@@ -247,8 +249,19 @@ hipError_t launch_decode_window(const StreamCall &c, const int64_t *d_start, uin
 // above it) and writes the records of the first max_pulses runs of at least min_width samples to int64
 // d_out[total_waves][max_pulses][DRX_PULSE_COLS] and the number of all such runs to d_count[total_waves].
 // ev: {start, walk's end, kernel's end, end}
-hipError_t launch_find_pulses(const StreamCall &c, const int64_t *d_thr, uint64_t thr_stride, int64_t thr, bool neg,
-                              uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out);
+// Few long waveforms under the delta filter (pulses_blocks_batch(): d_blk = the block decoder's scratch, d_ptab = the plan's
+// pulses_blocks_scratch_bytes() of block summaries and list, d_pstage = its pulses_blocks_staging_bytes(max_pulses) of staged
+// records, which may be nullptr where that is 0) take the block form of drx_pulses_blocks.hip instead, with the lane kernel
+// behind it for the waveforms it lists.  form_out: DRX_PULSES_FORM_* of include/deltarice_hip.h
+hipError_t launch_find_pulses(const StreamCall &c, void *d_blk, void *d_ptab, void *d_pstage, const int64_t *d_thr, uint64_t thr_stride,
+                              int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out,
+                              uint32_t *form_out);
+bool pulses_blocks_batch(const Geom &G, const void *d_blk);
+uint64_t pulses_blocks_scratch_bytes(const Geom &G);
+uint64_t pulses_blocks_staging_bytes(const Geom &G, uint32_t max_pulses);
+hipError_t launch_pulses_blocks(const StreamCall &c, void *d_blk, void *d_ptab, void *d_pstage, const int64_t *d_thr, uint64_t thr_stride,
+                                int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out,
+                                const uint32_t **listed_out, const uint32_t **n_listed_out);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 // k_chunk_scan + k_chunk_offsets (drx_encode_kernels.hip) over a table of n_i that is not an encode's: header positions relative
 // to the chunk, chunk offsets, DevStatus::total_words and kErrCapacity against out_cap
@@ -353,6 +366,7 @@ bool blocks_batch(const Geom &G, double lane_us = 0.06);
 // the plan is made); returns rag_blk_list's host copy (empty: the decoder does not take the batch)
 std::vector<uint32_t> blocks_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
 uint64_t blocks_scratch_bytes(const Geom &G);
+uint64_t blocks_total_slots(const Geom &G);  // look-back slots of the whole batch: every waveform's blocks at 25 bits per sample
 // resid: leave the residuals (not their running sums) in d_out: a general prediction filter's inverse follows (launch_iir)
 // fused_out: a general filter's inverse ran inside the kernel (no k_iir_tiles pass is needed behind it)
 hipError_t launch_decode_blocks(const StreamCall &c, void *d_blk, int16_t *d_out, const uint32_t **fail_out,

@@ -15,10 +15,13 @@
 //                         (serial_wave()) with the filter's history in an LDS column and the same state machine.  Correct,
 //                         not tuned.
 //
-// Few long waveforms (the nEDM / NOPTREX shapes, the reference's default of one waveform per chunk) go through the same
-// lane-per-waveform kernels.  That is correct and slow, 50-60 ns per sample and lane whatever else runs, with most of the chip
-// idle.  A block form behind drx_blocks_body.inc, as drx_wave_stats has one, is not built here: a run spans block borders, so
-// the blocks' open runs would have to be stitched.
+// Few long waveforms (the nEDM / NOPTREX shapes, the reference's default of one waveform per chunk) under the delta filter do
+// NOT run here: a lane per waveform is 50-60 ns per sample and lane whatever else runs, with most of the chip idle.  The batches
+// that drx_wave_stats gives to its block form take the block form of drx_pulses_blocks.hip -- a workgroup per block of a
+// waveform's stream, the runs stitched across the blocks' borders behind it -- and this file's launcher runs
+// k_find_pulses_list, the delta filter's lane kernel over a list, behind that over the waveforms it lists (flagged or suspect
+// ones, and those whose blocks staged too few records: computed again and judged here, a lane each).  General filters, and batches under DRX_DBG_PULSES_LANES, stay a
+// lane per waveform whatever their shape (DESIGN.md section 4.2i has the measured rows).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,6 +30,7 @@
 #include "drx_internal.h"
 #include "drx_device.h"
 #include "drx_lane_stream.h"
+#include "drx_pulse_runs.h"
 
 namespace drx {
 
@@ -39,16 +43,7 @@ typedef short s16x2 __attribute__((ext_vector_type(2)));
 // [-32768, 32768] and then tv = -1 - t, the same range.  The sum d_thr + thr saturates at the int64 ends.
 __device__ __forceinline__ int32_t lane_threshold(const int64_t *__restrict__ thr_tab, uint64_t thr_stride, int64_t thr, bool neg,
                                                   uint64_t g) {
-    int64_t t = thr;
-    if (thr_tab) {
-        const int64_t v = thr_tab[g * thr_stride];
-        if (__builtin_add_overflow(v, thr, &t)) t = v < 0 ? INT64_MIN : INT64_MAX;
-    }
-    if (neg) {
-        t = t < -32768 ? -32768 : (t > 32768 ? 32768 : t);
-        return (int32_t)(-1 - t);
-    }
-    return (int32_t)(t < -32769 ? -32769 : (t > 32767 ? 32767 : t));
+    return pulse_threshold(thr_tab != nullptr, thr_tab ? thr_tab[g * thr_stride] : 0, thr, neg);  // (drx_pulse_runs.h: sum and clamp)
 }
 
 // A lane's state: whether a run is open, where it began, its largest v and the first place of that, the sum of its v, and
@@ -117,85 +112,25 @@ __global__ __launch_bounds__(64) void k_find_pulses(Geom G, const uint32_t *__re
                                                     const int64_t *__restrict__ thr_tab, uint64_t thr_stride, int64_t thr,
                                                     uint32_t neg, uint32_t min_width, uint32_t max_pulses, DevStatus *st,
                                                     uint32_t *__restrict__ count_out, int64_t *__restrict__ out) {
-    constexpr int GS = kGS;
-    __shared__ uint32_t ring_all[kInRingWords];
-    const int lane = lane_id();
-    const uint32_t k = G.k;
-    // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
-    if (st->err) return;
-    LANE_WAVE_G_ACTIVE_LEN(G, wf_base + blockIdx.x, lane)
-    uint32_t n = 0;
-    uint64_t S = 1;
-    PulseLane P;
-    P.tv = 32767;
-    P.min_width = min_width;
-    P.max_pulses = max_pulses;
-    P.flip = neg ? -1 : 0;
-    P.slots = out;
-    P.open = false;
-    P.s = P.apk = 0;
-    P.peak = 0;
-    P.sum = 0;
-    P.count = 0;
-    if (active) {
-        S = wave_off[g] + 1u;
-        n = wave_words[g];
-        P.tv = lane_threshold(thr_tab, thr_stride, thr, neg != 0u, g);
-        P.slots = out + g * (uint64_t)max_pulses * (uint64_t)DRX_PULSE_COLS;  // (never followed where max_pulses == 0)
-    }
-    const uint32_t pm = neg ? 0xffffffffu : 0u;  // flip of a pair
-    uint32_t *const ring = ring_all + 64;
-#include "drx_lane_reader.inc"
+    constexpr bool LIST = false;
+    const uint32_t *const list = nullptr, *const n_list = nullptr;
+#include "drx_pulses_lane_body.inc"
+}
 
-    const uint32_t steps = wave_max_u32(len);
-    int32_t acc = 0;  // running sum of the deltas: the sample in its low 16 bits
-    set_limits();
-    for (uint32_t i = 0; i < steps; i += (uint32_t)GS) {
-        group_refill();
-        if (i + (uint32_t)GS <= len) {
-            // ---- the unmasked group: eight pairs, two samples per ring access
-            uint32_t pr[GS / 2];  // the group's v, two to a register (the earlier one in the low half)
-#pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                LANE_PAIR(z1, z2)
-                acc += (int32_t)(z1 >> 1) ^ -(int32_t)(z1 & 1u);
-                const uint32_t a1 = (uint32_t)acc;
-                acc += (int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u);
-                pr[u / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u) ^ pm;  // low halves of the two running sums
-            }
-            s16x2 gm = __builtin_bit_cast(s16x2, pr[0]);
-#pragma unroll
-            for (int j = 1; j < GS / 2; ++j) gm = __builtin_elementwise_max(gm, __builtin_bit_cast(s16x2, pr[j]));
-            const int32_t gmax = gm.x > gm.y ? (int32_t)gm.x : (int32_t)gm.y;
-            if (P.open || gmax > P.tv) {
-                // the registers rotate: pr[0] is the pair in turn
-#pragma unroll 1
-                for (uint32_t u = 0; u < (uint32_t)GS; u += 2u) {
-                    const uint32_t p = pr[0];
-#pragma unroll
-                    for (int j = 0; j < GS / 2 - 1; ++j) pr[j] = pr[j + 1];
-                    P.step((int32_t)(int16_t)(uint16_t)p, i + u);
-                    P.step((int32_t)p >> 16, i + u + 1u);
-                }
-            }
-        } else if (i < len) {
-            // ---- the masked group: the lane's waveform ends inside it.  One sample per ring access.
-#pragma unroll 1
-            for (uint32_t u = 0; u < (uint32_t)GS; ++u) {
-                const uint32_t idx = i + u;
-                if (idx < len) {
-                    LANE_ONE(z)
-                    acc += (int32_t)(z >> 1) ^ -(int32_t)(z & 1u);
-                    P.step((int32_t)(int16_t)(uint16_t)((uint32_t)acc ^ pm), idx);
-                }
-            }
-        }
-        round_end(i);
-    }
-    if (!active) return;
-    if (P.open) P.close(len);  // a run still open at the last sample ends there
-    if (len && LANE_MISSES_LAST_WORD()) atomicOr(&st->err, kErrCorrupt);
-    count_out[g] = P.count;
+// The same kernel over the waveforms list[0 .. *n_list) instead of all of them (behind the block form, drx_pulses_blocks.hip: the
+// list and its length are written on the device by the kernel in front; the launch is sized for the whole batch).  Every lane
+// reads its own stream through its own ring column, so the lanes of a wavefront may hold any waveforms.  Lane 0 of the launch
+// leaves the list's length in the status word for drx_plan_last_pulses_listed.
+__global__ __launch_bounds__(64) void k_find_pulses_list(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                         const uint64_t *__restrict__ wave_off,
+                                                         const uint32_t *__restrict__ wave_words, uint64_t wf_base,
+                                                         const int64_t *__restrict__ thr_tab, uint64_t thr_stride, int64_t thr,
+                                                         uint32_t neg, uint32_t min_width, uint32_t max_pulses, DevStatus *st,
+                                                         uint32_t *__restrict__ count_out, int64_t *__restrict__ out,
+                                                         const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list) {
+    constexpr bool LIST = true;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->listed = *n_list;
+#include "drx_pulses_lane_body.inc"
 }
 
 // General prediction filters: a lane per waveform, serial_wave() (global loads); the last 64 outputs of every
@@ -234,10 +169,13 @@ __global__ __launch_bounds__(64) void k_find_pulses_serial(Geom G, const uint32_
     count_out[g] = P.count;
 }
 
-hipError_t launch_find_pulses(const StreamCall &c, const int64_t *d_thr, uint64_t thr_stride, int64_t thr, bool neg,
-                              uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out) {
+hipError_t launch_find_pulses(const StreamCall &c, void *d_blk, void *d_ptab, void *d_pstage, const int64_t *d_thr, uint64_t thr_stride,
+                              int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out,
+                              uint32_t *form_out) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;
+    const bool blocks = d_ptab != nullptr && (d_pstage != nullptr || max_pulses == 0u) && pulses_blocks_batch(G, d_blk);
+    if (form_out) *form_out = blocks ? (DRX_PULSES_FORM_BLOCKS | ((G.dbg & DRX_DBG_PULSES_ALL_FALLBACK) ? DRX_PULSES_FORM_FALLBACK_ALL : 0u)) : DRX_PULSES_FORM_LANES;
     if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip): launch_batch_walk()
     hipError_t e = batch_walk_prologue(c);
@@ -245,16 +183,29 @@ hipError_t launch_find_pulses(const StreamCall &c, const int64_t *d_thr, uint64_
     // ---- the zero slots: the whole output, once (the lanes then store the records alone)
     if (max_pulses && (e = hipMemsetAsync(d_out, 0, (size_t)(G.total_waves * (uint64_t)max_pulses * DRX_PULSE_COLS * sizeof(int64_t)), s)) != hipSuccess)
         return e;
-    // ---- the kernel: a wavefront per 64 waveforms
-    const bool serial = G.n_taps != 0;
-    for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {
-        if (serial)
-            k_find_pulses_serial<<<nb, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u, min_width,
-                                                   max_pulses, c.d_status, d_count, d_out);
-        else
-            k_find_pulses<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u,
-                                            min_width, max_pulses, c.d_status, d_count, d_out);
-    });
+    if (blocks) {
+        // ---- few long waveforms: a workgroup per block of a waveform's stream and the stitch behind it, then a lane per waveform
+        // that form lists (the launch is sized from here, at most a lane per waveform of the batch; the list's length is read on
+        // the device)
+        const uint32_t *listed = nullptr, *n_listed = nullptr;
+        if ((e = launch_pulses_blocks(c, d_blk, d_ptab, d_pstage, d_thr, thr_stride, thr, neg, min_width, max_pulses, d_count, d_out, &listed,
+                                      &n_listed)) != hipSuccess)
+            return e;
+        k_find_pulses_list<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, 0, d_thr, thr_stride, thr,
+                                                                       neg ? 1u : 0u, min_width, max_pulses, c.d_status, d_count, d_out, listed,
+                                                                       n_listed);
+    } else {
+        // ---- the kernel: a wavefront per 64 waveforms
+        const bool serial = G.n_taps != 0;
+        for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {
+            if (serial)
+                k_find_pulses_serial<<<nb, 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u, min_width,
+                                                       max_pulses, c.d_status, d_count, d_out);
+            else
+                k_find_pulses<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, d_thr, thr_stride, thr, neg ? 1u : 0u,
+                                                min_width, max_pulses, c.d_status, d_count, d_out);
+        });
+    }
     mark(c.ev, 2, s);
     mark(c.ev, 3, s);
     return hipGetLastError();

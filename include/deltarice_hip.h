@@ -322,7 +322,8 @@ drx_status drx_decode_window_with_wave_words(drx_plan *plan, const uint32_t *d_i
  * side-band, or the plan's own table passed as the side-band.
  *   Asynchronous on the context's stream like drx_decode; the call clears the plan's status word first and ends a pending
  * drx_gather_encoded sizing call's resume; errors found on the device arrive at drx_plan_finish.  drx_plan_last_decode_path
- * reports DRX_PATH_PULSES alone, drx_plan_last_timings { header-chain walk, pulse kernel, 0, whole call }.
+ * reports DRX_PATH_PULSES alone whichever form ran (drx_plan_last_pulses_form says which), drx_plan_last_timings
+ * { header-chain walk, memset and pulse kernels (block form: blocks, stitch and fallback), 0, whole call }.
  *   Validation is drx_wave_stats': the header chain of every chunk is walked and judged (the second form checks the table
  * against the stream instead), and a payload that ends before its samples do, or whose codes do not end in its last payload
  * word, is DRX_ERR_CORRUPT; the outputs are then undefined and the plan stays usable.
@@ -331,9 +332,23 @@ drx_status drx_decode_window_with_wave_words(drx_plan *plan, const uint32_t *d_i
  * written, and the result does not depend on what they held before; slot addressing is 64-bit.
  *   Every prediction filter the plan accepts: the delta filter a lane per waveform that parses as drx_wave_stats' lane kernel
  * does and keeps a small state machine (a group of 16 samples that holds nothing over the threshold costs one packed maximum
- * and one compare); any other filter a lane per waveform in a serial kernel, correct but not fast.  Few long waveforms go
- * through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow): a block form like drx_wave_stats'
- * is not built, since a run spans block borders and the blocks' open runs would have to be stitched. */
+ * and one compare); any other filter a lane per waveform in a serial kernel, correct but not fast.
+ *   Few long waveforms under the delta filter -- the batches drx_wave_stats gives to its block form, a long trace that holds
+ * many events among them -- take a block form: a workgroup per block of a waveform's stream parses as the block decoder does,
+ * finds the pulses that lie inside its block and publishes the runs that touch the block's first and last sample; a pass behind
+ * the blocks joins those runs across the borders, numbers every waveform's pulses by their start and fills the slots.  A block
+ * stages the records of at most min(max_pulses, DRX_PULSES_STAGE_CAP) of its own pulses (the staging buffer belongs to the plan:
+ * allocated by the first call of this form, grown when a later call asks for more pulses).  A waveform of which a block holds
+ * more pulses than that AND needs more than that many of them among its first max_pulses is finished by a second launch of the
+ * blocks over such waveforms alone: by then the pass behind the first launch has numbered every block's pulses, and the blocks
+ * write them straight to their slots.  The call then costs the blocks twice for those waveforms, not a lane per waveform
+ * (measured with one such waveform among 2048 of 500 000 samples: 1.67 ms against 1.32 without one, 24.1 a lane per waveform).
+ * Calls with max_pulses <= DRX_PULSES_STAGE_CAP, and the counting form, never need it and do not launch it.  A waveform that
+ * the block parse flags (a stream whose blocks do not fall into step) is computed again by the delta filter's lane kernel over
+ * a list, exact, at 48 ns per sample: noise and quiet data are never flagged.
+ * drx_plan_last_pulses_redone and drx_plan_last_pulses_listed say how many waveforms of the last call went either way.  The
+ * results of all forms are the same bit for bit.  DRX_DBG_PULSES_LANES: never the block form; DRX_DBG_PULSES_ALL_FALLBACK: the
+ * block form hands every waveform to the lane kernel behind it. */
 #define DRX_PULSE_START 0   /* first sample of the run, waveform-relative               */
 #define DRX_PULSE_WIDTH 1   /* samples in the run (time over threshold)                  */
 #define DRX_PULSE_PEAK 2    /* the extreme sample of the run in the polarity's direction */
@@ -343,6 +358,17 @@ drx_status drx_decode_window_with_wave_words(drx_plan *plan, const uint32_t *d_i
 drx_status drx_find_pulses(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                            const int64_t *d_thr, uint64_t thr_stride, int64_t thr, int32_t polarity, uint32_t min_width,
                            uint32_t max_pulses, uint32_t *d_count, int64_t *d_out);
+/* which form the plan's last drx_find_pulses took (0: none yet) */
+#define DRX_PULSES_FORM_LANES 1u        /* a lane per waveform */
+#define DRX_PULSES_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream, the stitch behind them */
+#define DRX_PULSES_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_PULSES_ALL_FALLBACK was in force */
+uint32_t drx_plan_last_pulses_form(const drx_plan *plan);
+#define DRX_PULSES_STAGE_CAP 8u /* records a block of the block form stages at most */
+/* ... and, behind drx_plan_finish, how many waveforms its block form handed to the lane kernel behind the stitch (flagged by the
+ * block parse, or all of them under DRX_DBG_PULSES_ALL_FALLBACK), and how many its second launch of the blocks finished
+ * (short of staged records); both 0 for the lane form */
+uint32_t drx_plan_last_pulses_listed(const drx_plan *plan);
+uint32_t drx_plan_last_pulses_redone(const drx_plan *plan);
 /* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
  * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
 drx_status drx_find_pulses_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
@@ -470,7 +496,9 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_wave_stats: ms = { header-chain walk, statistics kernels (block form: blocks + finish + fallback), 0, whole call }
  *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
  *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call }
- *   after drx_find_pulses: ms = { header-chain walk, pulse kernel, 0, whole call } */
+ *   after drx_find_pulses: ms = { header-chain walk, pulse kernel, 0, whole call }; "pulse kernel" is everything between the
+ *     walk and the call's end: the output's memset and the lane kernel, or in the block form the blocks, the stitch and the
+ *     lane kernel behind them */
 drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 
 /* Tuning / diagnostics.  Returns DRX_ERR_ARG for unknown keys or values.
@@ -503,6 +531,8 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 #define DRX_DBG_GATHER_OTHER_COPY 33554432u      /* drx_gather_encoded: the copy form the batch's code length does NOT choose (a workgroup per run of entries <-> a wavefront per entry) */
 #define DRX_DBG_STATS_LANES 67108864u           /* drx_wave_stats: never the block form (a lane per waveform whatever the batch) */
 #define DRX_DBG_STATS_ALL_FALLBACK 134217728u   /* drx_wave_stats, block form: every waveform is listed for the lane kernel behind the blocks */
+#define DRX_DBG_PULSES_LANES 268435456u         /* drx_find_pulses: never the block form (a lane per waveform whatever the batch) */
+#define DRX_DBG_PULSES_ALL_FALLBACK 536870912u  /* drx_find_pulses, block form: every waveform is listed for the lane kernel behind the stitch */
 drx_status drx_ctx_set_option(drx_ctx *ctx, const char *key, int64_t value);
 
 #ifdef __cplusplus

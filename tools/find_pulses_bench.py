@@ -9,10 +9,16 @@ one process and alternating, so that the yardsticks are taken in the same run; m
   headline        500 chunks of 2000 x 7000, m = 8, Gaussian sigma = 10 (seeded), a pulse of 3000 somewhere in every waveform
   headline-loud   the same with sigma = 400
   short           300 chunks of 8192 x 512
-  noptrex         2048 waveforms of 500 000 samples (few long waveforms: a lane each, reported, not gated)
+  noptrex         2048 waveforms of 500 000 samples  } few long waveforms: the block form of drx_pulses_blocks.hip
+  nedm            8192 waveforms of 81 920 samples   } (before it existed: a lane each)
+  long25          25 waveforms of 14 M samples       }
 
 and for each batch three cells: `5sigma` = threshold at 5 sigma, rare pulses, max_pulses 4; `2sigma` = threshold at 2 sigma,
-several pulses per waveform, max_pulses 8; `count` = the counting form (max_pulses 0) at 2 sigma.
+several pulses per waveform, max_pulses 8; `count` = the counting form (max_pulses 0) at 2 sigma.  Two more for the block form
+(--cells ...,cap,fallback; sigma = 10 batches): `cap` = threshold 2000, the one planted pulse per waveform, max_pulses 32 -- above
+what a block stages; `fallback` = threshold 1000 with max_pulses 32, where waveform 0's twenty pulses of 1500 within 2000
+samples make one block need more records than it staged: the blocks run a second time over that waveform.  Every line
+says which form the call took (drx_plan_last_pulses_form; `-` on a library that has no such query).
 
 usage: find_pulses_bench.py [--chunks 500] [--calls 20] [--warmup 5] [--only NAME[,NAME]] [--cells 5sigma,2sigma,count] [--no-yardstick]
 A line is "ok" when the call takes less time than `plan.decode` alone by more than that decode's min-to-max spread over the
@@ -35,13 +41,17 @@ from workload import geometry  # noqa: E402
 
 class Case:
     def __init__(self, ctx, n_chunks, N, L, sigma, m=8):
+        opts = (m, L) if L else (m,)  # (L = 0: the whole chunk is one waveform)
+        L = L or N
         self.ctx, self.L, self.sigma = ctx, L, sigma
         x = samples(ctx, n_chunks * N, sigma)
         W = n_chunks * (N // L)
         g = torch.Generator(device=ctx.device).manual_seed(7)
         at = torch.randint(0, L, (W,), device=ctx.device, generator=g) + torch.arange(W, device=ctx.device) * L
         x[at] = 3000  # a pulse in every waveform
-        self.plan = ctx.plan_uniform(n_chunks, N, (m, L))
+        if L >= 50000 and sigma < 100:  # the long shapes' `fallback` cell: twenty pulses of 1500 close together in waveform 0
+            x[torch.arange(1000, 3000, 100, device=ctx.device)] = 1500
+        self.plan = ctx.plan_uniform(n_chunks, N, opts)
         torch.cuda.synchronize()
         self.enc = self.plan.encode(x)
         del x, at
@@ -97,7 +107,9 @@ class Case:
         walk, kern = self.plan.last_timings()[:2]
         self.ctx.set_option("profile", 0)
         n = self.count.to(torch.int64)
-        head = (f"{label:14s} {cname:6s} threshold {thr:5d} max_pulses {max_pulses} {self.W:8d} waveforms stream {self.enc.total_words * 4 / 1e9:5.2f} GB "
+        form = getattr(self.plan, "last_pulses_form", None)
+        form = {None: "-", 1: "lanes", 2: "blocks", 6: "blocks+all"}.get(form() if form else None, "?")
+        head = (f"{label:14s} {cname:8s} form {form:6s} threshold {thr:5d} max_pulses {max_pulses} {self.W:8d} waveforms stream {self.enc.total_words * 4 / 1e9:5.2f} GB "
                 f"pulses {float(n.sum()) / self.W:7.2f} per waveform, {float((n > max_pulses).sum()) / self.W * 100:5.1f} % of rows overflow, "
                 f"records {out.numel() * 8 / 1e9:5.3f} GB  ")
         mine = f"find_pulses {np.median(tp):8.3f} [{tp.min():.3f} .. {tp.max():.3f}] (walk {walk:.3f} kernel {kern:.3f})"
@@ -128,14 +140,22 @@ def main():
         ("headline-loud", a.chunks, 2000 * 7000, 7000, 400.0),
         ("short", 300, 8192 * 512, 512, 10.0),
         ("noptrex", len(nN), nN[0], nL[0], 10.0),
+        ("nedm", 256, 32 * 81920, 81920, 10.0),
+        ("long25", 25, 14_000_000, 0, 10.0),
     ]
     for name, n_chunks, N, L, sigma in cases:
         if only and name not in only:
             continue
         c = Case(ctx, n_chunks, N, L, sigma)
         for cname in a.cells.split(","):
-            k, max_pulses = {"5sigma": (5, 4), "2sigma": (2, 8), "count": (2, 0)}[cname]
-            c.line(name, cname, int(k * sigma), max_pulses, a.calls, a.warmup, not a.no_yardstick)
+            if cname in ("cap", "fallback"):
+                if sigma >= 100 or (L and L < 50000):
+                    continue
+                thr, max_pulses = {"cap": (2000, 32), "fallback": (1000, 32)}[cname]
+            else:
+                k, max_pulses = {"5sigma": (5, 4), "2sigma": (2, 8), "count": (2, 0)}[cname]
+                thr = int(k * sigma)
+            c.line(name, cname, thr, max_pulses, a.calls, a.warmup, not a.no_yardstick)
         c.plan.close()
         del c
         torch.cuda.empty_cache()
