@@ -7,7 +7,7 @@ chunks over the GPUs of a node; ``optimise`` searches RiceParameter and encoding
 (docs/Optimization.md of the reference).  There is no CPU implementation in this package.
 """
 from ._lib import DeltaRiceError, LIB_PATH, PLUGIN_PATH  # noqa: F401
-from ._lib import (PATH_PULSES, PATH_STATS, PATH_TRANSCODE, PATH_WINDOW, PULSE_ARGPEAK, PULSE_COLS, PULSE_PEAK, PULSE_START,  # noqa: F401
+from ._lib import (PATH_PULSES, PATH_STATS, PATH_TRANSCODE, PATH_WINDOW, PATH_WINDOWS, PULSE_ARGPEAK, PULSE_COLS, PULSE_PEAK, PULSE_START,  # noqa: F401
                    PULSE_SUM, PULSE_WIDTH)
 from ._lib import (STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD_SUMSQ,  # noqa: F401
                    STAT_MAX, STAT_MIN, STAT_SUM, STAT_SUMSQ)

@@ -23,6 +23,7 @@ PATH_STATS = 512
 PATH_TRANSCODE = 1024
 PATH_WINDOW = 2048
 PATH_PULSES = 4096
+PATH_WINDOWS = 8192
 # DRX_STAT_*: the columns of a drx_wave_stats row (tests/test_wave_stats_abi.py holds them equal)
 STAT_MIN, STAT_ARGMIN, STAT_MAX, STAT_ARGMAX, STAT_SUM, STAT_SUMSQ, STAT_HEAD_SUM, STAT_HEAD_SUMSQ = range(8)
 STAT_COLS = 8
@@ -49,11 +50,15 @@ DBG_STATS_LANES = 67108864
 DBG_STATS_ALL_FALLBACK = 134217728
 DBG_PULSES_LANES = 268435456
 DBG_PULSES_ALL_FALLBACK = 536870912
+DBG_WINDOWS_LANES = 1073741824
+DBG_WINDOWS_ALL_FALLBACK = 2147483648
 # DRX_STATS_FORM_*: drx_plan_last_stats_form (tests/test_wave_stats_blocks_abi.py holds them equal)
 STATS_FORM_LANES, STATS_FORM_BLOCKS, STATS_FORM_FALLBACK_ALL = 1, 2, 4
 # DRX_PULSES_FORM_*: drx_plan_last_pulses_form (tests/test_find_pulses_blocks_abi.py holds them equal)
 PULSES_FORM_LANES, PULSES_FORM_BLOCKS, PULSES_FORM_FALLBACK_ALL = 1, 2, 4
 PULSES_STAGE_CAP = 8  # DRX_PULSES_STAGE_CAP
+# DRX_WINDOWS_FORM_*: drx_plan_last_windows_form (tests/test_decode_windows_abi.py holds them equal)
+WINDOWS_FORM_LANES, WINDOWS_FORM_BLOCKS, WINDOWS_FORM_FALLBACK_ALL = 1, 2, 4
 
 
 class DrxOpts(C.Structure):
@@ -96,6 +101,7 @@ SIGNATURES = {
     "drx_plan_last_encode_path": (C.c_uint32, [_vp]),
     "drx_plan_last_stats_form": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_form": (C.c_uint32, [_vp]),
+    "drx_plan_last_windows_form": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_redone": (C.c_uint32, [_vp]),
     "drx_plan_read_wave_words": (C.c_int, [_vp, C.POINTER(_u32)]),
@@ -110,6 +116,9 @@ SIGNATURES = {
     "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "drx_decode_window": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_decode_window_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
+    "drx_decode_windows": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _u32, C.c_int64, _u32, C.c_int16, _vp, _u64, _u64]),
+    "drx_decode_windows_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _u32, C.c_int64, _u32, C.c_int16, _vp, _u64,
+                                                     _u64]),
     "drx_find_pulses": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, C.c_int32, _u32, _u32, _vp, _vp]),
     "drx_find_pulses_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, C.c_int32, _u32, _u32, _vp, _vp]),
     "drx_transcode": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),

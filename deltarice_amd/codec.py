@@ -544,6 +544,65 @@ class Plan:
         return self._blocking(self.decode_window_async, enc.words, enc.chunk_word_off, start, width, offset, pad, out, None, wave_words,
                               in_words=enc.total_words)
 
+    def decode_windows_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start: torch.Tensor, width: int,
+                             count: Optional[torch.Tensor] = None, offset: int = 0, pad: int = 0,
+                             out: Optional[torch.Tensor] = None, out_strides: Optional[tuple] = None,
+                             wave_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None) -> torch.Tensor:
+        """Launches drx_decode_windows on the context's stream: int16 [total_waves, n_win, width], row (g, p) = the ``width``
+        samples of waveform g from sample ``start[g, p] + offset`` on, ``pad`` where that leaves the waveform -- and all over
+        the row where p >= min(count[g], n_win).  A payload is read no further than its last window's end and the batch is not
+        decoded to memory.  start: a 2-D int64 tensor [total_waves, n_win] on the plan's device with any positive element
+        strides -- ``pulses[:, :, PULSE_START]`` of find_pulses() is passed as it is, with its ``count``.  count: an int32
+        tensor of total_waves entries, or None (every slot is live).  Windows may come in any order and overlap; non-decreasing
+        starts are the fast case.  out: an int16 tensor that holds the rows at out_strides = (samples between waveforms, samples
+        between a waveform's rows), default (n_win * width, width); the samples between rows keep what they held.  wave_words:
+        the encoder's n_i table as decode_with_wave_words takes it (no header walk).  Launch only; finish() raises on
+        device-side errors."""
+        self._open("decode_windows")
+        width, offset, pad = int(width), int(offset), int(pad)
+        if not 0 <= width < 1 << 32:
+            raise DeltaRiceError(1, f"width: {width} is not a uint32")
+        if not -32768 <= pad <= 32767:
+            raise DeltaRiceError(1, f"pad: {pad} is not an int16")
+        if not -(1 << 63) <= offset < 1 << 63:
+            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+        W = self.total_waves
+        if (not isinstance(start, torch.Tensor) or start.dim() != 2 or start.device != self.ctx.device or
+                start.dtype != torch.int64 or start.shape[0] != W or not start.shape[1] < 1 << 32 or
+                (W > 1 and start.stride(0) < 1) or (start.shape[1] > 1 and start.stride(1) < 1)):
+            raise DeltaRiceError(1, f"start: need a 2-D int64 tensor [{W}, n_win] with positive strides on {self.ctx.device}")
+        K = int(start.shape[1])
+        s_wave = int(start.stride(0)) if W > 1 else max(1, int(start.stride(0)))
+        s_win = int(start.stride(1)) if K > 1 else max(1, int(start.stride(1)))
+        if count is not None:
+            self._dev_check(count, torch.int32, W, "count")
+        self._check_encoded(words, chunk_word_off, wave_words)
+        o_wave, o_win = (K * width, width) if out_strides is None else (int(out_strides[0]), int(out_strides[1]))
+        if o_win < width:
+            raise DeltaRiceError(1, f"out_strides: rows {o_win} samples apart do not hold {width}")
+        if K and o_wave < (K - 1) * o_win + width:
+            raise DeltaRiceError(1, f"out_strides: waveforms {o_wave} samples apart do not hold {K} rows {o_win} apart")
+        need = (W - 1) * o_wave + (K - 1) * o_win + width if W and K and width else 0
+        if out is None:
+            out = torch.empty(need, dtype=torch.int16, device=self.ctx.device)
+        self._dev_check(out, torch.int16, need, "out")
+        rows = out.view(-1).as_strided((W, K, width), (o_wave, o_win, 1)) if need else out.view(-1)[:0].view(W, K, width)
+        if need == 0:
+            return rows
+        self._call_encoded("decode_windows", words, chunk_word_off, wave_words, in_words, start.data_ptr(), s_wave, s_win,
+                           count.data_ptr() if count is not None else None, K, offset, width, pad, out.data_ptr(), o_wave, o_win)
+        return rows
+
+    def decode_windows(self, enc: EncodedBatch, start: torch.Tensor, width: int, count: Optional[torch.Tensor] = None,
+                       offset: int = 0, pad: int = 0, out: Optional[torch.Tensor] = None,
+                       wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """decode_windows_async on an EncodedBatch -> int16 [total_waves, n_win, width]; waits, and raises like decode().  The
+        samples around every pulse: ``n, pulses = plan.find_pulses(enc, thr, max_pulses=8)``, then
+        ``plan.decode_windows(enc, pulses[:, :, PULSE_START], 256, count=n, offset=-64)``."""
+        self._open("decode_windows")
+        return self._blocking(self.decode_windows_async, enc.words, enc.chunk_word_off, start, width, count, offset, pad, out, None,
+                              wave_words, in_words=enc.total_words)
+
     def find_pulses_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, threshold, polarity: int = 1,
                           min_width: int = 1, max_pulses: int = 4, offset: int = 0, count: Optional[torch.Tensor] = None,
                           out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None,
@@ -686,6 +745,11 @@ class Plan:
         workgroup per block of a waveform's stream with the runs stitched behind it (few long waveforms); 0 before the plan's
         first pulse call."""
         return int(self.ctx.lib.drx_plan_last_pulses_form(self._h))
+
+    def last_windows_form(self) -> int:
+        """DRX_WINDOWS_FORM_* (include/deltarice_hip.h): which form the last decode_windows took -- a lane per waveform, or a
+        workgroup per block of a waveform's stream (few long waveforms); 0 before the plan's first such call."""
+        return int(self.ctx.lib.drx_plan_last_windows_form(self._h))
 
     def last_pulses_listed(self) -> int:
         """After finish(): how many waveforms the last find_pulses' block form handed to the lane kernel behind it (flagged by the

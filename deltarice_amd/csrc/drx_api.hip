@@ -126,6 +126,8 @@ struct drx_plan {
     void *d_pstage = nullptr;          // ... and the records its blocks stage, grown when a call needs more (pulses_staging())
     size_t pstage_cap = 0;
     uint32_t last_pulses_form = 0;     // DRX_PULSES_FORM_* of the last drx_find_pulses (0: none yet)
+    void *d_wtab = nullptr;            // ... and drx_decode_windows' block form: its list, allocated by its first call
+    uint32_t last_windows_form = 0;    // DRX_WINDOWS_FORM_* of the last drx_decode_windows (0: none yet)
     DevStatus *d_status = nullptr;
     DevStatus *h_status = nullptr;  // pinned
     bool last_was_encode = false;
@@ -633,6 +635,7 @@ uint32_t drx_plan_last_decode_path(const drx_plan *p) { return p ? p->last_path 
 uint32_t drx_plan_last_encode_path(const drx_plan *p) { return p ? p->last_enc_path : 0u; }
 uint32_t drx_plan_last_stats_form(const drx_plan *p) { return p ? p->last_stats_form : 0u; }
 uint32_t drx_plan_last_pulses_form(const drx_plan *p) { return p ? p->last_pulses_form : 0u; }
+uint32_t drx_plan_last_windows_form(const drx_plan *p) { return p ? p->last_windows_form : 0u; }
 uint32_t drx_plan_last_pulses_redone(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_PULSES) ? p->h_status->redone : 0u; }
 uint32_t drx_plan_last_pulses_listed(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_PULSES) ? p->h_status->listed : 0u; }
 
@@ -1045,7 +1048,7 @@ drx_status drx_gather_encoded_with_wave_words(drx_plan *p, const uint32_t *d_in,
 }
 
 // ---------------------------------------------------------------------------
-// The calls that read the whole batch from the encoded stream without decoding it -- wave_stats, decode_window, find_pulses,
+// The calls that read the whole batch from the encoded stream without decoding it -- wave_stats, decode_window(s), find_pulses,
 // transcode, estimate_words_encoded -- open with stream_call_begin() and close with call_end() (above).  stream_call_args(): the
 // pointers every one of them takes (have_pointers: the caller's own included; who: its name in the message).
 // ---------------------------------------------------------------------------
@@ -1115,6 +1118,51 @@ drx_status drx_decode_window_with_wave_words(drx_plan *p, const uint32_t *d_in, 
                                              uint64_t out_stride_samples) {
     return decode_window(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_start, start_stride, offset, width, pad, d_out,
                          out_stride_samples);
+}
+
+// ---------------------------------------------------------------------------
+// several windows of every waveform, at per-window starts (drx_windows.hip)
+// ---------------------------------------------------------------------------
+static drx_status decode_windows(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                 const uint32_t *d_sideband, bool sideband, const int64_t *d_start, uint64_t start_wave_stride,
+                                 uint64_t start_win_stride, const uint32_t *d_count, uint32_t n_win, int64_t offset, uint32_t width,
+                                 int16_t pad, int16_t *d_out, uint64_t out_wave_stride, uint64_t out_win_stride) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (const drx_status st = stream_call_args(p, "decode_windows", d_in && d_chunk_word_off && d_start && d_out, d_sideband, sideband)) return st;
+    if (start_wave_stride == 0 || start_win_stride == 0) return fail(ctx, DRX_ERR_ARG, "decode_windows: a start stride of 0");
+    if (out_win_stride < width)
+        return fail(ctx, DRX_ERR_ARG, "decode_windows: rows %llu samples apart do not hold %u", (unsigned long long)out_win_stride, width);
+    // a waveform's rows must end in front of the next one's: (n_win - 1) * out_win_stride + width samples, in 128 bits
+    if (n_win && (unsigned __int128)(n_win - 1u) * out_win_stride + width > (unsigned __int128)out_wave_stride)
+        return fail(ctx, DRX_ERR_ARG, "decode_windows: waveforms %llu samples apart do not hold %u rows %llu apart",
+                    (unsigned long long)out_wave_stride, n_win, (unsigned long long)out_win_stride);
+    if (width == 0 || n_win == 0) return DRX_OK;  // (no row receives a sample: nothing to launch)
+    DRX_ON_DEVICE(ctx);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    // the block form's list belongs to the plan: allocated by its first call that takes that form
+    if (!p->d_wtab && windows_blocks_batch(p->G, p->d_blk)) DRX_HIP(ctx, p->mem.alloc(&p->d_wtab, windows_blocks_scratch_bytes(p->G)));
+    DRX_HIP(ctx, launch_decode_windows(c, p->d_blk, p->d_wtab, d_start, start_wave_stride, start_win_stride, d_count, n_win, offset, width, pad,
+                                       d_out, out_wave_stride, out_win_stride, &p->last_windows_form));
+    return call_end(p, DRX_PATH_WINDOWS);
+}
+
+drx_status drx_decode_windows(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const int64_t *d_start, uint64_t start_wave_stride, uint64_t start_win_stride, const uint32_t *d_count,
+                              uint32_t n_win, int64_t offset, uint32_t width, int16_t pad, int16_t *d_out, uint64_t out_wave_stride,
+                              uint64_t out_win_stride) {
+    return decode_windows(p, d_in, in_words, d_chunk_word_off, nullptr, false, d_start, start_wave_stride, start_win_stride, d_count, n_win,
+                          offset, width, pad, d_out, out_wave_stride, out_win_stride);
+}
+
+drx_status drx_decode_windows_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                              const uint32_t *d_wave_words, const int64_t *d_start, uint64_t start_wave_stride,
+                                              uint64_t start_win_stride, const uint32_t *d_count, uint32_t n_win, int64_t offset,
+                                              uint32_t width, int16_t pad, int16_t *d_out, uint64_t out_wave_stride,
+                                              uint64_t out_win_stride) {
+    return decode_windows(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_start, start_wave_stride, start_win_stride, d_count,
+                          n_win, offset, width, pad, d_out, out_wave_stride, out_win_stride);
 }
 
 // ---------------------------------------------------------------------------

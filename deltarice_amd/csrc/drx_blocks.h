@@ -1,7 +1,8 @@
 // drx_blocks.h -- the block-parallel parse shared by the kernels that give a WORKGROUP a block of a waveform's stream
 // (not installed): the block geometry, the parse, and (drx_blocks_body.inc) the body of k_decode_blocks (drx_blocks.hip: the samples,
-// in output order, to HBM), of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics) and of
-// k_pulses_blocks (drx_pulses_blocks.hip: the runs of samples over a threshold, per block, stitched behind the kernel).
+// in output order, to HBM), of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics), of
+// k_pulses_blocks (drx_pulses_blocks.hip: the runs of samples over a threshold, per block, stitched behind the kernel) and of
+// k_windows_blocks (drx_windows_blocks.hip: the samples, in output order, to the rows of the windows that meet the block).
 // drx_blocks.hip's head comment describes the scheme.  A kernel that takes this route for another purpose adds its own
 // phase 2 behind the same phase 1, look-back and flags, as the STATS and PULSES forms do.
 #ifndef DRX_BLOCKS_H
@@ -15,6 +16,7 @@
 #include "drx_internal.h"
 #include "drx_iir_math.h"
 #include "drx_pulse_runs.h"
+#include "drx_window_rows.h"
 
 namespace drx {
 
@@ -255,7 +257,12 @@ struct BlkPulseArgs {
     uint32_t max_pulses;
     int64_t *out;
 };
-
+// WINDOWS (delta filter only): phase 2 is the decoder's -- the block's samples in output order in LDS -- but only where a live
+// window of the waveform meets the block, and in place of the copy to the decoded batch every window that meets the staged
+// samples receives its share of them in its own row (drx_windows_blocks.hip); `out`, `itab` and `xstate` are not used.
+struct BlkWindowArgs {
+    WinList wl;  // drx_window_rows.h: the starts, the counts and the rows of drx_decode_windows
+};
 
 }  // namespace drx
 #endif

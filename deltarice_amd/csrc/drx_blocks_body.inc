@@ -1,8 +1,10 @@
 // drx_blocks_body.inc -- the body of a kernel that gives a workgroup a block of a waveform's stream, included INSIDE the kernel's
-// definition (k_decode_blocks, drx_blocks.hip; k_stats_blocks, drx_stats_blocks.hip; k_pulses_blocks, drx_pulses_blocks.hip)
+// definition (k_decode_blocks, drx_blocks.hip; k_stats_blocks, drx_stats_blocks.hip; k_pulses_blocks, drx_pulses_blocks.hip;
+// k_windows_blocks, drx_windows_blocks.hip)
 // behind its arguments: text, not a function, because k_decode_blocks is sensitive to how its arguments reach it (an inlined
 // function with the same body was compiled to other code: other spills, another schedule).  The including kernel provides NT,
-// RESID, SW, FUSE, STATS, PULSES, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs) and `pa` (BlkPulseArgs).
+// RESID, SW, FUSE, STATS, PULSES, WINDOWS, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs), `pa` (BlkPulseArgs) and
+// `wa` (BlkWindowArgs).
     static_assert(!FUSE || RESID, "the fused inverse filter works on residuals");
     using BG = BlkGeom<NT, SW>;
     constexpr int kBlkSegW = SW;
@@ -715,9 +717,41 @@
                 }
             } else {
                 // ---- phase 2: the samples in output order, whole lines to HBM ----
-                const uint32_t a0 = (uint32_t)((((uintptr_t)(y + blk_first)) >> 1) & 7u);  // kOutCap is a multiple of 8: the same every pass
+                // WINDOWS: only where a live window of the waveform meets the block's samples [blk_first, blk_first + blk_count) --
+                // the threads test the windows in parallel, the workgroup decides as one.  A block that no window meets puts nothing
+                // in order and stores nothing.
+                [[maybe_unused]] uint32_t w_live = 0;
+                if constexpr (WINDOWS) {
+                    w_live = wa.wl.live(g);
+                    bool hit = false;
+                    for (uint32_t q = tid; q < w_live; q += (uint32_t)NT) {
+                        const Win w = window_at(wa.wl.at(g, q), wa.wl.width, len);
+                        hit = hit || (w.e > blk_first && w.s < blk_first + blk_count);
+                    }
+                    if (!wg_any(hit)) {
+                        blk_barrier();  // (as at the end of a block: W, the staging buffer and the s_* words are rewritten by the next)
+                        continue;
+                    }
+                }
+                // (WINDOWS: the staged samples go to rows of any alignment: staged from element 0)
+                const uint32_t a0 = WINDOWS ? 0u : (uint32_t)((((uintptr_t)(y + blk_first)) >> 1) & 7u);  // kOutCap is a multiple of 8: the same every pass
                 auto copy_out = [&](uint32_t R0) __attribute__((always_inline)) {  // staged samples [R0, R0 + kOutCap) of the block -> HBM
                     const uint32_t nsamp = (blk_count - R0 < BG::kOutCap) ? blk_count - R0 : BG::kOutCap;
+                    if constexpr (WINDOWS) {
+                        // ... -> the rows of the windows they lie in: sample x of the waveform sits at obuf[x - lo], and goes to element
+                        // x - a of the row of every live window [a, a + width) that holds it.  The destinations come from the
+                        // window and `len` alone: a block whose start is later corrected may write wrong values into its own
+                        // waveform's rows (the waveform is then listed, and its rows written again), never outside them.
+                        const uint32_t lo = blk_first + R0, hi = lo + nsamp;
+                        for (uint32_t q = 0; q < w_live; ++q) {
+                            const Win w = window_at(wa.wl.at(g, q), wa.wl.width, len);
+                            const uint32_t is = w.s > lo ? w.s : lo, ie = w.e < hi ? w.e : hi;
+                            if (is >= ie) continue;
+                            g_u16 *const rs = (g_u16 *)(wa.wl.row(g, q) + ((int64_t)w.pf - (int64_t)w.s));  // sample x at rs[x]
+                            for (uint32_t x = is + tid; x < ie; x += (uint32_t)NT) rs[x] = obuf[x - lo];
+                        }
+                        return;
+                    }
                     g_u16 *gbase = (g_u16 *)(y + blk_first + R0) - a0;  // 16-byte aligned
                     // whole 16-byte pieces [p_lo, p_hi) without a test per piece; the up to seven samples in front of the first and
                     // behind the last one by sixteen lanes

@@ -244,6 +244,22 @@ hipError_t launch_stats_blocks(const StreamCall &c, void *d_blk, void *d_sacc, u
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}
 hipError_t launch_decode_window(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width,
                                 int16_t pad, int16_t *d_out, uint64_t out_stride);
+// drx_decode_windows (drx_windows.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
+// far as the end of its last live window and writes every window slot's row of `width` samples: slot p < min(d_count[g], n_win)
+// (d_count == nullptr: every slot) from d_start[g * start_wave_stride + p * start_win_stride] + offset on, pad outside the waveform
+// and all over a slot that is not live; row (g, p) = d_out + g * out_wave_stride + p * out_win_stride.
+// ev: {start, walk's end, kernels' end, end}
+// Few long waveforms under the delta filter (windows_blocks_batch(): d_blk = the block decoder's scratch, d_wtab = the plan's
+// windows_blocks_scratch_bytes() of list) take the block form of drx_windows_blocks.hip instead, with the lane kernel behind it for
+// the waveforms it lists.  form_out: DRX_WINDOWS_FORM_* of include/deltarice_hip.h
+struct WinList;  // drx_window_rows.h
+hipError_t launch_decode_windows(const StreamCall &c, void *d_blk, void *d_wtab, const int64_t *d_start, uint64_t start_wave_stride,
+                                 uint64_t start_win_stride, const uint32_t *d_count, uint32_t n_win, int64_t offset, uint32_t width,
+                                 int16_t pad, int16_t *d_out, uint64_t out_wave_stride, uint64_t out_win_stride, uint32_t *form_out);
+bool windows_blocks_batch(const Geom &G, const void *d_blk);
+uint64_t windows_blocks_scratch_bytes(const Geom &G);
+hipError_t launch_windows_blocks(const StreamCall &c, void *d_blk, void *d_wtab, const WinList &wl, const uint32_t **listed_out,
+                                 const uint32_t **n_listed_out);
 // drx_find_pulses (drx_pulses.hip): behind the whole batch's walk (tables_ready as above), the output zeroed by one memset, a lane
 // per waveform that parses, compares every sample with thr[g * thr_stride] + thr (d_thr == nullptr: 0; neg: below it, otherwise
 // above it) and writes the records of the first max_pulses runs of at least min_width samples to int64

@@ -17,7 +17,8 @@
 //
 // Few long waveforms (the nEDM / NOPTREX shapes: a few thousand waveforms of 10^5 - 10^6 samples) go through the same
 // lane-per-waveform kernels.  That is correct and slow, 50-60 ns per sample and lane whatever else runs, with most of the
-// chip idle: the open step drx_decode_select documents.  A wavefront or workgroup per long waveform is not built here.
+// chip idle.  drx_decode_windows with n_win = 1 (drx_windows_blocks.hip) is the form for such batches: a workgroup per block of
+// a waveform's stream.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -26,16 +27,15 @@
 #include "drx_internal.h"
 #include "drx_device.h"
 #include "drx_lane_stream.h"
+#include "drx_window_rows.h"
 
 namespace drx {
 
-// Samples [s, e) of the waveform go to row elements [pf, pf + e - s); pad fills [0, pf) and [pf + e - s, width).  A window
-// that holds no sample of the waveform is s = e = 0, pf = width: the lane parses nothing.
-struct Win {
-    uint32_t s, e, pf;
-};
+// Win, window_at() and fill_pad(): drx_window_rows.h (shared with drx_decode_windows' kernels)
 __device__ __forceinline__ Win window_of(const int64_t *__restrict__ start, uint64_t start_stride, int64_t offset, uint32_t width,
                                          uint64_t g, uint32_t len) {
+    // (window_at(window_start()) of that header, written out: through the two functions the kernels' prologues were scheduled
+    // another way, and this call keeps its instructions)
     int64_t a = offset;
     if (start) {
         const int64_t v = start[g * start_stride];
@@ -49,14 +49,6 @@ __device__ __forceinline__ Win window_of(const int64_t *__restrict__ start, uint
     w.s = a < 0 ? 0u : (uint32_t)a;
     w.pf = a < 0 ? (uint32_t)(0 - a) : 0u;  // (0 < -a < width here)
     return w;
-}
-
-// row elements [from, to) = pad: dword stores between a 2-byte store at either end where the address asks for one
-__device__ __forceinline__ void fill_pad(int16_t *row, uint32_t from, uint32_t to, uint32_t pad2) {
-    if (from >= to) return;
-    if ((((uintptr_t)row >> 1) + from) & 1u) row[from++] = (int16_t)pad2;
-    for (; from + 2u <= to; from += 2u) *(uint32_t *)(row + from) = pad2;
-    if (from < to) row[from] = (int16_t)pad2;
 }
 
 // Lanes map by LANE_WAVE_G_ACTIVE_LEN (drx_lane_stream.h).  wf_base: first wavefront of this launch (for_wavefront_slices()).

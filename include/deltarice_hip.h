@@ -289,8 +289,8 @@ uint32_t drx_plan_last_stats_form(const drx_plan *plan);
  * 64-bit (g * out_stride_samples may exceed 2^32 bytes).
  *   Every prediction filter the plan accepts: the delta filter a lane per waveform that parses as the lane decoder does and
  * writes its own row; any other filter a lane per waveform in a serial kernel that stops at the window's end, correct but not
- * fast.  Few long waveforms go through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow: a
- * wavefront or workgroup per long waveform is not built). */
+ * fast.  Few long waveforms go through the same lane-per-waveform kernels, 50-60 ns per sample and lane (correct, slow): for
+ * such batches drx_decode_windows with n_win = 1 is the fast form, a workgroup per block of a waveform's stream. */
 drx_status drx_decode_window(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                              const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad,
                              int16_t *d_out, uint64_t out_stride_samples);
@@ -300,6 +300,69 @@ drx_status drx_decode_window_with_wave_words(drx_plan *plan, const uint32_t *d_i
                                              const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, const int64_t *d_start,
                                              uint64_t start_stride, int64_t offset, uint32_t width, int16_t pad, int16_t *d_out,
                                              uint64_t out_stride_samples);
+
+/* SEVERAL WINDOWS of every waveform, at per-window starts, straight from the encoded stream: the samples around EVERY pulse
+ * that drx_find_pulses found, its records taken as it writes them -- no host round trip, no reshaping, and the batch is not
+ * decoded to memory.
+ *   The windows.  Waveform g (a global waveform index in the order of drx_plan_wave_words) has window slots p = 0 .. n_win - 1.
+ * Slot p is LIVE when p < min(d_count[g], n_win); d_count == NULL: every slot is live.  d_count: uint32[total_waves] on the device,
+ * any 4-byte alignment -- drx_find_pulses' count as written, which may exceed max_pulses: the min handles that.  A live window
+ * starts at a = d_start[g * start_wave_stride + p * start_win_stride] + offset; the sum saturates at the int64 ends, as in
+ * drx_decode_window.  d_start: int64 on the device, any 8-byte alignment; both strides count int64 elements.  The DRX_PULSE_START
+ * or DRX_PULSE_ARGPEAK column of drx_find_pulses' [total_waves][max_pulses][DRX_PULSE_COLS] output goes in as it is: the pointer is
+ * d_pulses + column, the strides are DRX_PULSE_COLS * max_pulses and DRX_PULSE_COLS.
+ *   The rows.  Row (g, p) is d_out + g * out_wave_stride + p * out_win_stride and receives exactly `width` samples.  A live row
+ * holds y[a + j] where 0 <= a + j < len_g (the int16 drx_decode would write there) and `pad` elsewhere; a row that is not live is
+ * all pad; the samples between rows keep what they held.  Row addressing is 64-bit.
+ *   Order and overlap.  The live windows of a waveform may come in any order and may overlap, nest or coincide: every row is what
+ * it would be alone.  Non-decreasing starts, as drx_find_pulses numbers its pulses, are the fast case: the lane kernel then keeps
+ * a cursor, and a group of 16 samples that touches no window costs one compare.  An unsorted list costs a scan of all live
+ * windows of the waveform per group of 16 samples.
+ *   Extent and verdict.  Let e_g be the largest min(a + width, len_g) over the live windows of g, or 0 when no window holds a
+ * sample.  Neither the rows nor the verdict depend on payload bits behind sample e_g.  A waveform with e_g == len_g gets
+ * drx_wave_stats' end-of-payload check; a payload that runs out of words before the windows' codes do is DRX_ERR_CORRUPT.  The
+ * header chain of every chunk is walked and judged as drx_decode does (the second form checks the table against the stream
+ * instead).  After a corrupt verdict the rows are undefined and the plan stays usable.  All of this holds in every form.
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: a NULL pointer among d_in, d_chunk_word_off, d_start, d_out;
+ * start_wave_stride == 0 or start_win_stride == 0; out_win_stride < width; out_wave_stride < (n_win - 1) * out_win_stride + width
+ * (rows would overlap); in the second form a NULL side-band, or the plan's own table passed as the side-band.  width == 0 or
+ * n_win == 0 returns DRX_OK with nothing launched.
+ *   Asynchronous on the context's stream like drx_decode_window; the call clears the plan's status word first and ends a pending
+ * drx_gather_encoded sizing call's resume; errors found on the device arrive at drx_plan_finish.  drx_plan_last_decode_path
+ * reports DRX_PATH_WINDOWS alone whichever form ran (drx_plan_last_windows_form says which), drx_plan_last_timings
+ * { header-chain walk, everything between the walk and the call's end, 0, whole call }.
+ *   The buffers rule at the top of this file holds: any 4-byte alignment of d_in, any 2-byte alignment of d_out; no load leaves
+ * [0, in_words); nothing is written outside the total_waves x n_win rows of width samples, and the result does not depend on what
+ * the rows held before.
+ *   Every prediction filter the plan accepts, a lane per waveform: the delta filter in drx_decode_window's lane kernel with a
+ * window list (a lane ends behind e_g), any other filter in a serial kernel that loops over the live windows per sample, correct
+ * but not fast.  Few long waveforms under the delta filter -- the batches drx_wave_stats gives to its block form -- take a block
+ * form: a workgroup per block of a waveform's stream parses as the block decoder does, and puts its samples in order and stores
+ * them only where a live window meets the block, so sparse windows cost the parse alone and a window deep in a long trace does
+ * not cost a lane the whole trace in front of it.  A waveform that the block parse flags, or whose payload fails the blocks'
+ * end-of-payload check (they parse every waveform to its end), has all its rows written again and is judged, to e_g, by the lane
+ * kernel over a list: a waveform damaged only behind its last window ends with the lane form's verdict.  The list's scratch
+ * belongs to the plan and is allocated by the first call of this form.  The results of all forms are the same bit for bit.
+ * DRX_DBG_WINDOWS_LANES: never the block form; DRX_DBG_WINDOWS_ALL_FALLBACK: the block form lists every waveform for the lane
+ * kernel behind it; DRX_DBG_NO_LONG_PATHS and DRX_DBG_LONG_NOT_BLOCKS keep the call on lanes as they do for statistics and pulses.
+ *   One window of short waveforms: drx_decode_window's kernel stores whole dwords at either row parity and is the one to prefer
+ * there (DESIGN.md section 4.2j has the measured rows). */
+drx_status drx_decode_windows(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                              const int64_t *d_start, uint64_t start_wave_stride, uint64_t start_win_stride, const uint32_t *d_count,
+                              uint32_t n_win, int64_t offset, uint32_t width, int16_t pad, int16_t *d_out, uint64_t out_wave_stride,
+                              uint64_t out_win_stride);
+/* which form the plan's last drx_decode_windows took (0: none yet) */
+#define DRX_WINDOWS_FORM_LANES 1u        /* a lane per waveform */
+#define DRX_WINDOWS_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream, the lane kernel behind it for listed waveforms */
+#define DRX_WINDOWS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_WINDOWS_ALL_FALLBACK was in force */
+uint32_t drx_plan_last_windows_form(const drx_plan *plan);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
+ * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_decode_windows_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                              const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, const int64_t *d_start,
+                                              uint64_t start_wave_stride, uint64_t start_win_stride, const uint32_t *d_count,
+                                              uint32_t n_win, int64_t offset, uint32_t width, int16_t pad, int16_t *d_out,
+                                              uint64_t out_wave_stride, uint64_t out_win_stride);
 
 /* EVERY PULSE of every waveform, straight from the encoded stream: threshold discrimination -- time over threshold, the number
  * of pulses, and the start, width, peak and integral of each -- without decoding the batch to memory.  What drx_wave_stats (one
@@ -432,7 +495,7 @@ drx_status drx_estimate_words(drx_plan *plan, const int16_t *d_in, uint64_t word
 
 /* Waits for the plan's last encode/decode, reports device-side errors and (for
  * encode) the number of words produced.  total_words may be NULL.
- *   It reports the plan's LAST encode, decode, select, gather, statistics, transcode, window or pulse call only: every such call (a select or gather of no entries
+ *   It reports the plan's LAST encode, decode, select, gather, statistics, transcode, window, windows or pulse call only: every such call (a select or gather of no entries
  * and a window of no width excepted, which launch nothing) starts by clearing the plan's one status word, on the stream, so the device-side error
  * (and the word count) of an earlier call that was never finished is not kept.  drx_estimate_words,
  * drx_plan_read_wave_words and drx_plan_set_filter leave the status word as it is: a finish behind them still reports the
@@ -459,6 +522,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_TRANSCODE 1024u /* drx_transcode / drx_estimate_words_encoded: a lane per waveform that parses and re-codes; reported alone */
 #define DRX_PATH_WINDOW 2048u   /* drx_decode_window: a lane per waveform that parses to its window's end; reported alone */
 #define DRX_PATH_PULSES 4096u   /* drx_find_pulses: a lane per waveform that parses and discriminates; reported alone */
+#define DRX_PATH_WINDOWS 8192u  /* drx_decode_windows: several windows per waveform, lanes or blocks; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -496,6 +560,8 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_wave_stats: ms = { header-chain walk, statistics kernels (block form: blocks + finish + fallback), 0, whole call }
  *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
  *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call }
+ *   after drx_decode_windows: ms = { header-chain walk, everything between the walk and the call's end (block form: pads,
+ *     blocks, finish and the lane kernel behind them), 0, whole call }
  *   after drx_find_pulses: ms = { header-chain walk, pulse kernel, 0, whole call }; "pulse kernel" is everything between the
  *     walk and the call's end: the output's memset and the lane kernel, or in the block form the blocks, the stitch and the
  *     lane kernel behind them */
@@ -533,6 +599,8 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 #define DRX_DBG_STATS_ALL_FALLBACK 134217728u   /* drx_wave_stats, block form: every waveform is listed for the lane kernel behind the blocks */
 #define DRX_DBG_PULSES_LANES 268435456u         /* drx_find_pulses: never the block form (a lane per waveform whatever the batch) */
 #define DRX_DBG_PULSES_ALL_FALLBACK 536870912u  /* drx_find_pulses, block form: every waveform is listed for the lane kernel behind the stitch */
+#define DRX_DBG_WINDOWS_LANES 1073741824u        /* drx_decode_windows: never the block form (a lane per waveform whatever the batch) */
+#define DRX_DBG_WINDOWS_ALL_FALLBACK 2147483648u /* drx_decode_windows, block form: every waveform is listed for the lane kernel behind the blocks */
 drx_status drx_ctx_set_option(drx_ctx *ctx, const char *key, int64_t value);
 
 #ifdef __cplusplus
