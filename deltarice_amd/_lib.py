@@ -102,6 +102,7 @@ SIGNATURES = {
     "drx_plan_last_stats_form": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_form": (C.c_uint32, [_vp]),
     "drx_plan_last_windows_form": (C.c_uint32, [_vp]),
+    "drx_plan_last_windows_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_redone": (C.c_uint32, [_vp]),
     "drx_plan_read_wave_words": (C.c_int, [_vp, C.POINTER(_u32)]),

@@ -751,6 +751,11 @@ class Plan:
         workgroup per block of a waveform's stream (few long waveforms); 0 before the plan's first such call."""
         return int(self.ctx.lib.drx_plan_last_windows_form(self._h))
 
+    def last_windows_listed(self) -> int:
+        """After finish(): how many waveforms the last decode_windows' block form handed to the lane kernel behind it (flagged or
+        judged suspect by the block parse; their rows are written again and judged there); 0 for the lane form."""
+        return int(self.ctx.lib.drx_plan_last_windows_listed(self._h))
+
     def last_pulses_listed(self) -> int:
         """After finish(): how many waveforms the last find_pulses' block form handed to the lane kernel behind it (flagged by the
         block parse, or short of staged records); 0 for the lane form."""

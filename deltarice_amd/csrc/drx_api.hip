@@ -638,6 +638,7 @@ uint32_t drx_plan_last_pulses_form(const drx_plan *p) { return p ? p->last_pulse
 uint32_t drx_plan_last_windows_form(const drx_plan *p) { return p ? p->last_windows_form : 0u; }
 uint32_t drx_plan_last_pulses_redone(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_PULSES) ? p->h_status->redone : 0u; }
 uint32_t drx_plan_last_pulses_listed(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_PULSES) ? p->h_status->listed : 0u; }
+uint32_t drx_plan_last_windows_listed(const drx_plan *p) { return (p && p->h_status && p->last_path == DRX_PATH_WINDOWS) ? p->h_status->listed : 0u; }
 
 drx_status drx_plan_read_wave_words(drx_plan *p, uint32_t *host_out) {
     if (!p || !host_out) return DRX_ERR_ARG;

@@ -90,7 +90,7 @@ struct Geom {
 
 struct DevStatus {
     uint32_t err;  // kErr* bits, OR-ed by kernels
-    uint32_t listed;  // drx_find_pulses, block form: the waveforms handed to the lane kernel behind the stitch
+    uint32_t listed;  // drx_find_pulses / drx_decode_windows, block form: the waveforms handed to the lane kernel behind the blocks
     uint64_t total_words;  // encode: words of the encoded batch
     uint32_t redone;       // drx_find_pulses, block form: the waveforms whose blocks its second launch ran again
     uint32_t pad_;

@@ -74,13 +74,15 @@ __global__ __launch_bounds__(64) void k_decode_windows(Geom G, const uint32_t *_
 
 // The same kernel over the waveforms list[0 .. *n_list) instead of all of them (behind the block form: the list and its length
 // are written on the device by the kernel in front; the launch is sized for the whole batch).  Every lane reads its own stream
-// through its own ring column, so the lanes of a wavefront may hold any waveforms.
+// through its own ring column, so the lanes of a wavefront may hold any waveforms.  Lane 0 of the launch leaves the list's length
+// in the status word for drx_plan_last_windows_listed.
 __global__ __launch_bounds__(64) void k_decode_windows_list(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
                                                             const uint64_t *__restrict__ wave_off,
                                                             const uint32_t *__restrict__ wave_words, uint64_t wf_base, WinList wl,
                                                             DevStatus *st, const uint32_t *__restrict__ list,
                                                             const uint32_t *__restrict__ n_list) {
     constexpr bool LIST = true;
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->listed = *n_list;
 #include "drx_windows_lane_body.inc"
 }
 

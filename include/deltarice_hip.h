@@ -356,6 +356,10 @@ drx_status drx_decode_windows(drx_plan *plan, const uint32_t *d_in, uint64_t in_
 #define DRX_WINDOWS_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream, the lane kernel behind it for listed waveforms */
 #define DRX_WINDOWS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_WINDOWS_ALL_FALLBACK was in force */
 uint32_t drx_plan_last_windows_form(const drx_plan *plan);
+/* ... and, behind drx_plan_finish while drx_plan_last_decode_path is DRX_PATH_WINDOWS, how many waveforms its block form handed
+ * to the lane kernel behind the blocks (flagged or judged suspect by the block parse, or all of them under
+ * DRX_DBG_WINDOWS_ALL_FALLBACK): their rows were written again, all of them, and judged there; 0 for the lane form */
+uint32_t drx_plan_last_windows_listed(const drx_plan *plan);
 /* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
  * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
 drx_status drx_decode_windows_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,

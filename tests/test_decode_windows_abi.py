@@ -46,6 +46,16 @@ def test_a_null_plan_is_an_argument_error():
     assert lib.drx_plan_last_windows_form(None) == 0
 
 
+def test_the_listed_query():
+    from deltarice_amd import _lib, codec
+    lib = _lib.load()
+    txt = open(os.path.join(ROOT, "include", "deltarice_hip.h")).read()
+    assert re.search(r"^uint32_t drx_plan_last_windows_listed\(const drx_plan \*plan\);", txt, flags=re.M)
+    assert "drx_plan_last_windows_listed" in _lib.SIGNATURES
+    assert hasattr(lib, "drx_plan_last_windows_listed") and lib.drx_plan_last_windows_listed(None) == 0
+    assert callable(codec.Plan.last_windows_listed)
+
+
 class _Ctx:
     lib = None
 

@@ -5,6 +5,8 @@ The streams are the oracle's (oracle.encode_chunk), the expected rows numpy's ov
 (tests/decode_windows_reference.py; for a filter whose lead is not +-1, over the oracle's decode of that stream), the
 comparison torch.equal.  Every cell asserts DRX_PATH_WINDOWS alone, plan.finish() == 0 and the form, through the walk and
 through the side-band."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -45,9 +47,25 @@ def dev(ctx, a, dtype):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype))).to(ctx.device)
 
 
-def check(ctx, st, y, cases, form=LANES, flags=0, sidebands=(False, True), what=""):
-    """Every (starts [W, K], counts or None, offset, width, pad) x {walk, side-band} on st against numpy over the samples y."""
+SENTINELS = (0x5A5A, -1)  # what an output holds before a call: alternating, and never the call's pad
+_calls = itertools.count()
+
+
+def prefilled(ctx, shape, pad):
+    """An int16 output of `shape`, every element a sentinel that differs from `pad`: the rows must not depend on what they held."""
+    s = SENTINELS[next(_calls) % 2]
+    if s == int(pad):
+        s = SENTINELS[0] if s == SENTINELS[1] else SENTINELS[1]
+    assert s != int(pad)
+    return torch.full(tuple(shape), s, dtype=torch.int16, device=ctx.device)
+
+
+def check(ctx, st, y, cases, form=LANES, flags=0, sidebands=(False, True), what="", listed=None):
+    """Every (starts [W, K], counts or None, offset, width, pad) x {walk, side-band} on st against numpy over the samples y, into
+    a pre-filled output.  listed: what plan.last_windows_listed() must say behind every call (a number, or a predicate).
+    Returns the rows of every call, in order."""
     geom = (st.start, st.length, st.chunk)
+    gots = []
     ctx.set_option("debug_flags", flags)
     try:
         for starts, counts, offset, width, pad in cases:
@@ -55,9 +73,14 @@ def check(ctx, st, y, cases, form=LANES, flags=0, sidebands=(False, True), what=
             sd, cd = dev(ctx, starts, np.int64), dev(ctx, counts, np.int32)
             for sideband in sidebands:
                 cell = (what, flags, tuple(np.shape(starts)), counts is not None, offset, width, pad, sideband)
-                got = st.plan.decode_windows(st.enc, sd, width, count=cd, offset=offset, pad=pad, wave_words=st.table if sideband else None)
+                out = prefilled(ctx, want.shape, pad)
+                got = st.plan.decode_windows(st.enc, sd, width, count=cd, offset=offset, pad=pad, out=out, wave_words=st.table if sideband else None)
+                assert got.data_ptr() == out.data_ptr() or got.numel() == 0, cell
                 assert st.plan.last_decode_path() == D.PATH_WINDOWS and st.plan.finish() == 0, cell
                 assert st.plan.last_windows_form() == form, (cell, st.plan.last_windows_form())
+                if listed is not None:
+                    n = st.plan.last_windows_listed()
+                    assert listed(n) if callable(listed) else n == listed, (cell, "listed", n)
                 assert got.dtype == torch.int16 and got.shape == want.shape, cell
                 if not torch.equal(got, want):
                     bad = torch.nonzero((got != want).flatten(1).any(dim=1)).flatten()
@@ -65,9 +88,11 @@ def check(ctx, st, y, cases, form=LANES, flags=0, sidebands=(False, True), what=
                     p = int(torch.nonzero((got[g] != want[g]).any(dim=1)).flatten()[0])
                     j = int(torch.nonzero(got[g, p] != want[g, p]).flatten()[0])
                     raise AssertionError((cell, f"{bad.numel()} waveforms differ; waveform {g} slot {p} from column {j}",
-                                          np.asarray(starts)[g].tolist(), got[g, p, j:j + 8].tolist(), want[g, p, j:j + 8].tolist()))
+                                          np.asarray(starts)[g, max(p - 2, 0):p + 3].tolist(), got[g, p, j:j + 8].tolist(), want[g, p, j:j + 8].tolist()))
+                gots.append(got)
     finally:
         ctx.set_option("debug_flags", 0)
+    return gots
 
 
 def random_starts(rng, st, K, lo=-50, hi=50):
