@@ -1058,6 +1058,10 @@ static drx_status stream_call_args(drx_plan *p, const char *who, bool have_point
     if (sideband && d_sideband == p->d_wave_words) return fail(p->ctx, DRX_ERR_ARG, "the side-band table must not be the plan's own (copy it first)");
     return DRX_OK;
 }
+// A block form's scratch (*d) belongs to the plan and is allocated by the first call that takes that form (BlkFormRule, drx_internal.h)
+static hipError_t form_scratch(drx_plan *p, const BlkFormRule &r, void **d, uint64_t (*bytes)(const Geom &)) {
+    return (!*d && blocks_form_batch(p->G, p->d_blk, r)) ? p->mem.alloc(d, bytes(p->G)) : hipSuccess;
+}
 
 // ---------------------------------------------------------------------------
 // per-waveform statistics from the encoded stream (drx_stats.hip)
@@ -1070,8 +1074,7 @@ static drx_status wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_word
     DRX_ON_DEVICE(ctx);
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
-    // the block form's accumulators and list belong to the plan: allocated by its first call that takes that form
-    if (!p->d_sacc && stats_blocks_batch(p->G, p->d_blk)) DRX_HIP(ctx, p->mem.alloc(&p->d_sacc, stats_blocks_scratch_bytes(p->G)));
+    DRX_HIP(ctx, form_scratch(p, kStatsForm, &p->d_sacc, stats_blocks_scratch_bytes));  // accumulators and list
     DRX_HIP(ctx, launch_wave_stats(c, p->d_blk, p->d_sacc, head_len, d_out, &p->last_stats_form));
     return call_end(p, DRX_PATH_STATS);
 }
@@ -1142,8 +1145,7 @@ static drx_status decode_windows(drx_plan *p, const uint32_t *d_in, uint64_t in_
     DRX_ON_DEVICE(ctx);
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
-    // the block form's list belongs to the plan: allocated by its first call that takes that form
-    if (!p->d_wtab && windows_blocks_batch(p->G, p->d_blk)) DRX_HIP(ctx, p->mem.alloc(&p->d_wtab, windows_blocks_scratch_bytes(p->G)));
+    DRX_HIP(ctx, form_scratch(p, kWindowsForm, &p->d_wtab, windows_blocks_scratch_bytes));  // the list
     DRX_HIP(ctx, launch_decode_windows(c, p->d_blk, p->d_wtab, d_start, start_wave_stride, start_win_stride, d_count, n_win, offset, width, pad,
                                        d_out, out_wave_stride, out_win_stride, &p->last_windows_form));
     return call_end(p, DRX_PATH_WINDOWS);
@@ -1196,11 +1198,10 @@ static drx_status find_pulses(drx_plan *p, const uint32_t *d_in, uint64_t in_wor
     DRX_ON_DEVICE(ctx);
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
-    // the block form's summaries, list and staged records belong to the plan: allocated by its first call that takes that form
-    if (pulses_blocks_batch(p->G, p->d_blk)) {
-        if (!p->d_ptab) DRX_HIP(ctx, p->mem.alloc(&p->d_ptab, pulses_blocks_scratch_bytes(p->G)));
+    DRX_HIP(ctx, form_scratch(p, kPulsesForm, &p->d_ptab, pulses_blocks_scratch_bytes));  // summaries and lists
+    // ... and the records its blocks stage: as many as this call needs
+    if (blocks_form_batch(p->G, p->d_blk, kPulsesForm))
         if (const drx_status st = pulses_staging(p, pulses_blocks_staging_bytes(p->G, max_pulses))) return st;
-    }
     DRX_HIP(ctx, launch_find_pulses(c, p->d_blk, p->d_ptab, p->d_pstage, d_thr, thr_stride, thr, polarity < 0, min_width, max_pulses, d_count,
                                     d_out, &p->last_pulses_form));
     return call_end(p, DRX_PATH_PULSES);

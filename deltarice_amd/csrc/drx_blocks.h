@@ -5,6 +5,10 @@
 // k_windows_blocks (drx_windows_blocks.hip: the samples, in output order, to the rows of the windows that meet the block).
 // drx_blocks.hip's head comment describes the scheme.  A kernel that takes this route for another purpose adds its own
 // phase 2 behind the same phase 1, look-back and flags, as the STATS and PULSES forms do.
+// The host side of such a kernel is shared too: blocks_prepare() (drx_blocks.hip: the scratch reset and one BlkClassLaunch per
+// launch of the scheme, from blk_classes()), blk_dispatch() (the NT x SW instantiation of a launch), BlkFormRule with
+// blocks_form_batch() / blocks_form_word() (which batches take a call's block form, and its form word), BlkFallbackList (the
+// waveforms left to the lane kernel behind the blocks; all drx_internal.h) and, below, blk_listed() / blk_list_append().
 #ifndef DRX_BLOCKS_H
 #define DRX_BLOCKS_H
 
@@ -263,6 +267,18 @@ struct BlkPulseArgs {
 struct BlkWindowArgs {
     WinList wl;  // drx_window_rows.h: the starts, the counts and the rows of drx_decode_windows
 };
+
+// The fallback list (BlkFallbackList), in the kernel behind the blocks: waveform g goes to the lane kernel if every waveform does
+// (all_listed: the form's *_ALL_FALLBACK flag), if the blocks flagged it, or -- where the caller asks -- if no block has judged
+// it: unjudged(), the caller's test for "samples and no payload word", evaluated last.
+__device__ __forceinline__ bool blk_listed(uint32_t all_listed, const uint32_t *fail, const uint32_t *suspect, uint64_t g) {
+    return all_listed || fail[g] || suspect[g];
+}
+template <class F>
+__device__ __forceinline__ bool blk_listed(uint32_t all_listed, const uint32_t *fail, const uint32_t *suspect, uint64_t g, F unjudged) {
+    return blk_listed(all_listed, fail, suspect, g) || unjudged();
+}
+__device__ __forceinline__ void blk_list_append(uint32_t *n_listed, uint32_t *listed, uint32_t g) { listed[atomicAdd(n_listed, 1u)] = g; }
 
 }  // namespace drx
 #endif

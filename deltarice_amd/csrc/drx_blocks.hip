@@ -215,31 +215,63 @@ static unsigned blk_resident(int nt) { return 256u * (nt == 64 ? 12u : (nt == 12
 // the block geometry of a call: by the stream's bits per sample as the caller states them (a wrong in_words costs speed, nothing else)
 static uint64_t blk_bits10(const Geom &G, uint64_t in_words) { return G.total_samples ? 320ull * in_words / G.total_samples : 65ull; }
 
-// One launch of a kernel of this scheme -- a uniform batch, or one length class of a ragged one -- at `nt` lanes and `sw` words
-// per lane: k_blk_max for its info words, the run length and the resident grid.
-static BlkClassLaunch blk_class_launch(const BlkScratch &L, uint32_t cls, const uint32_t *list, uint32_t n_waves, int nt, uint32_t wave_len,
-                                       int sw, uint64_t b10, uint32_t spw, const uint32_t *d_wave_words, hipStream_t s) {
+// What a call of the scheme begins with: the scratch, reset on the stream, and the geometry the stream's bits per sample choose
+struct BlkCall {
+    BlkScratch L;
+    uint32_t spw;  // look-back slots per waveform
+    uint64_t b10;
+    int sw;
+};
+static hipError_t blk_call_begin(const Geom &G, uint64_t in_words, void *d_blk, hipStream_t s, BlkCall *B) {
+    B->L = blocks_layout(G, d_blk);
+    B->spw = blocks_slots_per_wave(G);
+    B->b10 = blk_bits10(G, in_words);
+    B->sw = blk_segw_bits10(B->b10);
+    return hipMemsetAsync(d_blk, 0, B->L.bytes, s);
+}
+// The launches of the scheme for a batch: one for a uniform batch, one per length class of a ragged one, with the lanes per
+// block that suit the class's longest WaveformLength.  Returns their number (at most kBlkMaxClasses)
+struct BlkClass {
+    const uint32_t *list;  // the launch's waveforms (nullptr: all of the batch)
+    uint32_t n_waves;
+    int nt;
+    uint32_t wave_len;
+};
+static uint32_t blk_classes(const Geom &G, BlkClass *cls) {
+    if (G.uniform) {
+        cls[0] = BlkClass{nullptr, (uint32_t)G.total_waves, blocks_nt(G), G.u_wave_len};
+        return 1u;
+    }
+    for (uint32_t c = 0; c < G.rag_blk_classes; ++c)
+        cls[c] = BlkClass{G.rag_blk_list + G.rag_blk_class_off[c], G.rag_blk_class_off[c + 1] - G.rag_blk_class_off[c],
+                          nt_for_len(G.rag_blk_class_len[c], G.k), G.rag_blk_class_len[c]};
+    return G.rag_blk_classes;
+}
+
+// One launch of a kernel of this scheme, class `cls` of the batch at `nt` lanes per block: k_blk_max for its info words, the run
+// length and the resident grid.
+static BlkClassLaunch blk_class_launch(const BlkCall &B, uint32_t cls, const BlkClass &k, int nt, const uint32_t *d_wave_words, hipStream_t s) {
     BlkClassLaunch c;
-    c.info = L.info + 4u * cls;
-    c.list = list;
-    c.n_waves = n_waves;
+    c.info = B.L.info + 4u * cls;
+    c.list = k.list;
+    c.n_waves = k.n_waves;
     c.nt = nt;
-    c.sw = sw;
-    c.spw = spw;
-    const uint32_t words_per_block = (uint32_t)nt * (uint32_t)sw;
-    k_blk_max<<<1, 1024, 0, s>>>(n_waves, d_wave_words, words_per_block, c.info, list);
-    const uint64_t units = (uint64_t)n_waves * spw;
+    c.sw = B.sw;
+    c.spw = B.spw;
+    const uint32_t words_per_block = (uint32_t)nt * (uint32_t)B.sw;
+    k_blk_max<<<1, 1024, 0, s>>>(k.n_waves, d_wave_words, words_per_block, c.info, k.list);
+    const uint64_t units = (uint64_t)k.n_waves * B.spw;
     // Runs of several blocks only when two runs of one waveform are RARELY in flight together (see the kernel): at least
     // as many waveforms as resident workgroups.  (Ticket order does not exclude it -- a slow workgroup holding ticket t may
     // still run when ticket t + n_waves is drawn; the later run's look-back then simply waits on the lower ticket.)  Then as long as the launch keeps kBlkRounds tickets per workgroup (the
     // tail of the last round), up to the whole waveform: only a run's first block waits for other workgroups (nEDM, 6
     // blocks per waveform: one run; NOPTREX, 36: three runs of 12: 1.40 / 0.98 ms against 1.43 / 1.00 with round 2's fixed 4).
     const uint32_t resident = blk_resident(nt);
-    const uint64_t typ_words = ((uint64_t)wave_len * b10) / 320u;
+    const uint64_t typ_words = ((uint64_t)k.wave_len * B.b10) / 320u;
     const uint64_t bpw = (typ_words + words_per_block - 1u) / words_per_block;
-    uint64_t rl = ((uint64_t)n_waves * bpw) / ((uint64_t)kBlkRounds * resident);
+    uint64_t rl = ((uint64_t)k.n_waves * bpw) / ((uint64_t)kBlkRounds * resident);
     rl = rl > bpw ? bpw : rl;
-    c.run_len = n_waves >= resident ? (uint32_t)(rl < 1u ? 1u : rl) : 1u;
+    c.run_len = k.n_waves >= resident ? (uint32_t)(rl < 1u ? 1u : rl) : 1u;
     c.grid = (unsigned)(units < resident ? units : resident);  // resident: never more workgroups than there are units
     return c;
 }
@@ -248,88 +280,62 @@ static BlkClassLaunch blk_class_launch(const BlkScratch &L, uint32_t cls, const 
 // launch_decode_blocks() does, and one BlkClassLaunch per launch
 hipError_t blocks_prepare(const Geom &G, uint64_t in_words, const uint32_t *d_wave_words, void *d_blk, hipStream_t s, BlkTables *T,
                           BlkClassLaunch *launches, uint32_t *n_launches) {
-    const BlkScratch L = blocks_layout(G, d_blk);
-    const hipError_t e = hipMemsetAsync(d_blk, 0, L.bytes, s);
+    BlkCall B;
+    const hipError_t e = blk_call_begin(G, in_words, d_blk, s, &B);
     if (e != hipSuccess) return e;
-    const uint32_t spw = blocks_slots_per_wave(G);
-    const uint64_t b10 = blk_bits10(G, in_words);
-    const int sw = blk_segw_bits10(b10);
-    *T = BlkTables{L.fail, L.suspect, L.ends, L.state};
-    if (G.uniform) {
-        launches[0] = blk_class_launch(L, 0u, nullptr, (uint32_t)G.total_waves, blocks_nt(G), G.u_wave_len, sw, b10, spw, d_wave_words, s);
-        *n_launches = 1u;
-    } else {
-        for (uint32_t c = 0; c < G.rag_blk_classes; ++c)
-            launches[c] = blk_class_launch(L, c, G.rag_blk_list + G.rag_blk_class_off[c], G.rag_blk_class_off[c + 1] - G.rag_blk_class_off[c],
-                                           nt_for_len(G.rag_blk_class_len[c], G.k), G.rag_blk_class_len[c], sw, b10, spw, d_wave_words, s);
-        *n_launches = G.rag_blk_classes;
-    }
+    *T = BlkTables{B.L.fail, B.L.suspect, B.L.ends, B.L.state};
+    BlkClass cls[kBlkMaxClasses];
+    *n_launches = blk_classes(G, cls);
+    for (uint32_t i = 0; i < *n_launches; ++i) launches[i] = blk_class_launch(B, i, cls[i], cls[i].nt, d_wave_words, s);
     return hipGetLastError();
+}
+
+// Which batches take a call's block form, and the call's form word (drx_internal.h)
+bool blocks_form_batch(const Geom &G, const void *d_blk, const BlkFormRule &r) {
+    if (G.n_taps != 0 || !d_blk || !blocks_batch(G, r.lane_us)) return false;
+    return !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS | r.lanes_flag));
+}
+uint32_t blocks_form_word(const Geom &G, bool blocks, const BlkFormRule &r) {
+    return blocks ? (DRX_STATS_FORM_BLOCKS | ((G.dbg & r.all_fallback_flag) ? DRX_STATS_FORM_FALLBACK_ALL : 0u)) : DRX_STATS_FORM_LANES;
 }
 
 hipError_t launch_decode_blocks(const StreamCall &call, void *d_blk, int16_t *d_out, const uint32_t **fail_out,
                                 const uint32_t **suspect_out, bool resid, bool *fused_out) {
     const Geom &G = *call.G;
     const hipStream_t s = call.s;
-    const BlkScratch L = blocks_layout(G, d_blk);
-    hipError_t e = hipMemsetAsync(d_blk, 0, L.bytes, s);
+    BlkCall B;
+    const hipError_t e = blk_call_begin(G, call.in_words, d_blk, s, &B);
     if (e != hipSuccess) return e;
-    const uint32_t spw = blocks_slots_per_wave(G);
-    const uint64_t b10 = blk_bits10(G, call.in_words);
-    const int sw = blk_segw_bits10(b10);
+    const BlkScratch &L = B.L;
+    BlkClass cls[kBlkMaxClasses];
+    const uint32_t n_cls = blk_classes(G, cls);
     // General filters: the inverse filter inside this kernel (FUSE) where its state can pass from a run's last block to the next
     // run's first without a chain of waits, i.e. where every launch has at least as many waveforms as resident workgroups (the
     // condition under which runs are longer than one block); else residuals now and k_iir_tiles behind (DRX_DBG_IIR_SEPARATE: always).
-    auto resident_of = [](int nt) { return blk_resident(nt); };
     // (General filters run at 128 or 256 lanes per block when fused and at 256 when not: 12 of the 36 instantiations of the
     // kernel are not built; a block larger than the class's choice costs short waveforms some empty lanes, nothing else.)
     auto nt_gen = [](int nt) { return nt < 128 ? 128 : nt; };
     bool fuse = resid && G.blk_iir_tab != nullptr && !(G.dbg & DRX_DBG_IIR_SEPARATE);
-    if (fuse) {
-        if (G.uniform) fuse = G.total_waves >= resident_of(nt_gen(blocks_nt(G)));
-        else
-            for (uint32_t c = 0; c < G.rag_blk_classes; ++c)
-                fuse = fuse && (G.rag_blk_class_off[c + 1] - G.rag_blk_class_off[c]) >= resident_of(nt_gen(nt_for_len(G.rag_blk_class_len[c], G.k)));
-    }
+    for (uint32_t i = 0; i < n_cls; ++i) fuse = fuse && cls[i].n_waves >= blk_resident(nt_gen(cls[i].nt));
     if (fused_out) *fused_out = fuse;
-    auto launch_class = [&](uint32_t cls, const uint32_t *list, uint32_t n_waves, int nt, uint32_t wave_len) {
-        if (resid) nt = fuse ? nt_gen(nt) : 256;
-        const BlkClassLaunch c = blk_class_launch(L, cls, list, n_waves, nt, wave_len, sw, b10, spw, call.d_wave_words, s);
-        uint32_t *const info = c.info;
-        const uint32_t run_len = c.run_len;
-        auto go = [&](auto nt_tag, auto resid_tag, auto sw_tag) {
+    for (uint32_t i = 0; i < n_cls; ++i) {
+        // (k_blk_max of a class immediately in front of the class's kernel)
+        const BlkClassLaunch c = blk_class_launch(B, i, cls[i], resid ? (fuse ? nt_gen(cls[i].nt) : 256) : cls[i].nt, call.d_wave_words, s);
+        blk_dispatch(c.nt, c.sw, [&](auto nt_tag, auto sw_tag) {
             constexpr int NT = decltype(nt_tag)::value, SW = decltype(sw_tag)::value;
-            constexpr int MODE = decltype(resid_tag)::value;  // 0 delta filter, 1 residuals (k_iir_tiles follows), 2 inverse filter fused
-            const unsigned grid = c.grid;
-            // the filter's tables for runs of this geometry's lane share (76 / 68 / 60 samples)
-            const uint32_t *itab = G.blk_iir_tab ? G.blk_iir_tab + kRunTabWords * (blk_lane_cap(SW) == 76u ? 0u : (blk_lane_cap(SW) == 68u ? 1u : 2u)) : nullptr;
-            k_decode_blocks<NT, MODE != 0, SW, MODE == 2><<<grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, info, spw, run_len,
-                                                                             L.state, L.ends, info + 2, L.fail, L.suspect, call.d_status, d_out, n_waves, itab, L.xstate, list);
-        };
-        auto by_sw = [&](auto nt_tag, auto resid_tag) {
-            switch (sw) {
-                case 9: go(nt_tag, resid_tag, std::integral_constant<int, 9>{}); break;
-                case 11: go(nt_tag, resid_tag, std::integral_constant<int, 11>{}); break;
-                case 15: go(nt_tag, resid_tag, std::integral_constant<int, 15>{}); break;
-                default: go(nt_tag, resid_tag, std::integral_constant<int, 19>{}); break;
-            }
-        };
-        auto by_resid = [&](auto nt_tag) {
-            if (fuse) by_sw(nt_tag, std::integral_constant<int, 2>{});
-            else if (resid) by_sw(nt_tag, std::integral_constant<int, 1>{});
-            else by_sw(nt_tag, std::integral_constant<int, 0>{});
-        };
-        auto delta_only = [&](auto nt_tag) { by_sw(nt_tag, std::integral_constant<int, 0>{}); };
-        if (nt == 64) delta_only(std::integral_constant<int, 64>{});
-        else if (nt == 128) { if (fuse) by_sw(std::integral_constant<int, 128>{}, std::integral_constant<int, 2>{}); else delta_only(std::integral_constant<int, 128>{}); }
-        else by_resid(std::integral_constant<int, 256>{});
-    };
-    if (G.uniform) {
-        launch_class(0u, nullptr, (uint32_t)G.total_waves, blocks_nt(G), G.u_wave_len);
-    } else {
-        for (uint32_t c = 0; c < G.rag_blk_classes; ++c)
-            launch_class(c, G.rag_blk_list + G.rag_blk_class_off[c], G.rag_blk_class_off[c + 1] - G.rag_blk_class_off[c],
-                         nt_for_len(G.rag_blk_class_len[c], G.k), G.rag_blk_class_len[c]);
+            auto go = [&](auto mode_tag) {
+                constexpr int MODE = decltype(mode_tag)::value;  // 0 delta filter, 1 residuals (k_iir_tiles follows), 2 inverse filter fused
+                // the filter's tables for runs of this geometry's lane share (76 / 68 / 60 samples)
+                const uint32_t *itab = G.blk_iir_tab ? G.blk_iir_tab + kRunTabWords * (blk_lane_cap(SW) == 76u ? 0u : (blk_lane_cap(SW) == 68u ? 1u : 2u)) : nullptr;
+                k_decode_blocks<NT, MODE != 0, SW, MODE == 2><<<c.grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, c.info, c.spw,
+                                                                                 c.run_len, L.state, L.ends, c.info + 2, L.fail, L.suspect, call.d_status, d_out,
+                                                                                 c.n_waves, itab, L.xstate, c.list);
+            };
+            // the combinations that cannot occur (see nt_gen above) are not instantiated
+            if (fuse) { if constexpr (NT >= 128) go(std::integral_constant<int, 2>{}); }
+            else if (resid) { if constexpr (NT == 256) go(std::integral_constant<int, 1>{}); }
+            else go(std::integral_constant<int, 0>{});
+        });
     }
     *fail_out = L.fail;
     *suspect_out = L.suspect;

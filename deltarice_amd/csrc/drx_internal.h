@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <vector>
 
 #include "../../include/deltarice_hip.h"
@@ -229,16 +230,49 @@ inline GatherScratch gather_scratch_view(void *base, uint64_t n_sel) {
 hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves,
                          const uint32_t *d_chunk_samples, const EncOut &out, const GatherScratch &t, bool tiles, uint64_t mean_words,
                          bool resume);
+// The block forms of drx_wave_stats, drx_find_pulses and drx_decode_windows (drx_*_blocks.hip): few long waveforms under the delta
+// filter give a workgroup a block of a waveform's stream, as the block decoder does (d_blk = its scratch), with the call's lane
+// kernel behind the blocks for the waveforms they list.  One rule says which batches: the decoder's own test, blocks against
+// lanes by their cost (blocks_batch(), drx_blocks.hip), with the rate of THIS call's lane kernel, on a plan that has d_blk, unless
+// a debug flag keeps the batch on lanes (DRX_DBG_NO_LONG_PATHS, DRX_DBG_LONG_NOT_BLOCKS, the call's own lanes_flag).  A ragged
+// plan's choice was made from the host's chunk table when the plan was created: the decoder's.  Each form's scratch beyond d_blk
+// belongs to the plan and is allocated by the first call that takes the form (form_scratch(), drx_api.hip).
+struct BlkFormRule {
+    double lane_us;  // what the call's lane kernel takes per sample
+    uint32_t lanes_flag, all_fallback_flag;  // DRX_DBG_*: never the block form; the block form lists every waveform
+};
+// k_wave_stats takes 52 ns per sample and lane where k_decode_lanes takes 60, so a uniform batch at the
+// decoder's break-even -- 4 chunks of 2100 x 7000: one block per waveform, 393 us of blocks against 420 us of decoding lanes, but
+// 364 us of reducing lanes -- stays a lane per waveform there
+constexpr double kStatsLaneUs = 0.052;
+constexpr BlkFormRule kStatsForm{kStatsLaneUs, DRX_DBG_STATS_LANES, DRX_DBG_STATS_ALL_FALLBACK};
+// k_find_pulses on rare pulses takes 24.1 ms for a lane of 500 000 samples (profiles/find_pulses_bench.txt): 0.048 us per sample
+constexpr double kPulsesLaneUs = 0.048;
+constexpr BlkFormRule kPulsesForm{kPulsesLaneUs, DRX_DBG_PULSES_LANES, DRX_DBG_PULSES_ALL_FALLBACK};
+// k_decode_windows on sparse windows takes 25.7 ms for a lane of 500 000 samples, 700 ms for one of 14 M and 4.67 ms for one of
+// 81 920 (profiles/decode_windows_bench.txt): 0.050 - 0.057 us per sample, the NOPTREX shape's 0.051 taken
+constexpr double kWindowsLaneUs = 0.051;
+constexpr BlkFormRule kWindowsForm{kWindowsLaneUs, DRX_DBG_WINDOWS_LANES, DRX_DBG_WINDOWS_ALL_FALLBACK};
+bool blocks_form_batch(const Geom &G, const void *d_blk, const BlkFormRule &r);
+// the form word of a call, one set of values under three names: LANES, or BLOCKS | FALLBACK_ALL under the rule's all_fallback_flag
+static_assert(DRX_STATS_FORM_LANES == DRX_PULSES_FORM_LANES && DRX_STATS_FORM_LANES == DRX_WINDOWS_FORM_LANES &&
+                  DRX_STATS_FORM_BLOCKS == DRX_PULSES_FORM_BLOCKS && DRX_STATS_FORM_BLOCKS == DRX_WINDOWS_FORM_BLOCKS &&
+                  DRX_STATS_FORM_FALLBACK_ALL == DRX_PULSES_FORM_FALLBACK_ALL && DRX_STATS_FORM_FALLBACK_ALL == DRX_WINDOWS_FORM_FALLBACK_ALL,
+              "blocks_form_word() serves the three calls");
+uint32_t blocks_form_word(const Geom &G, bool blocks, const BlkFormRule &r);
+// The waveforms a block form leaves to the lane kernel behind it, a list on the device, part of the form's scratch:
+// u32 n_listed (+ pad to 8 bytes) | u32 listed[W].  (blk_listed() and blk_list_append(), drx_blocks.h, fill it.)
+struct BlkFallbackList {
+    uint32_t *n_listed, *listed;
+    static constexpr uint64_t bytes(uint64_t W) { return 8u + 4u * W; }
+    static BlkFallbackList at(void *base) { return {reinterpret_cast<uint32_t *>(base), reinterpret_cast<uint32_t *>(base) + 2}; }
+};
 // drx_wave_stats (drx_stats.hip): behind the whole batch's walk (tables_ready: the side-band's tables are in place), a lane per
 // waveform that parses and reduces: int64 d_out[total_waves][DRX_STAT_COLS].  ev: {start, walk's end, kernel's end, end}
-// Few long waveforms under the delta filter (stats_blocks_batch(): d_blk = the block decoder's scratch, d_sacc = the plan's
-// stats_blocks_scratch_bytes() of accumulators and list) take the block form of drx_stats_blocks.hip instead, with the lane kernel
-// behind it for the waveforms it lists.  form_out: DRX_STATS_FORM_* of include/deltarice_hip.h
+// form_out: DRX_STATS_FORM_* of include/deltarice_hip.h.  The block form: d_sacc = stats_blocks_scratch_bytes() of accumulators and list
 hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, uint32_t *form_out);
-bool stats_blocks_batch(const Geom &G, const void *d_blk);
 uint64_t stats_blocks_scratch_bytes(const Geom &G);
-hipError_t launch_stats_blocks(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out,
-                               const uint32_t **listed_out, const uint32_t **n_listed_out);
+hipError_t launch_stats_blocks(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, BlkFallbackList *list_out);
 // drx_decode_window (drx_window.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
 // far as its window's end and writes `width` samples from start[g * start_stride] + offset on (pad outside the waveform) to row
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}
@@ -249,35 +283,28 @@ hipError_t launch_decode_window(const StreamCall &c, const int64_t *d_start, uin
 // (d_count == nullptr: every slot) from d_start[g * start_wave_stride + p * start_win_stride] + offset on, pad outside the waveform
 // and all over a slot that is not live; row (g, p) = d_out + g * out_wave_stride + p * out_win_stride.
 // ev: {start, walk's end, kernels' end, end}
-// Few long waveforms under the delta filter (windows_blocks_batch(): d_blk = the block decoder's scratch, d_wtab = the plan's
-// windows_blocks_scratch_bytes() of list) take the block form of drx_windows_blocks.hip instead, with the lane kernel behind it for
-// the waveforms it lists.  form_out: DRX_WINDOWS_FORM_* of include/deltarice_hip.h
+// form_out: DRX_WINDOWS_FORM_* of include/deltarice_hip.h.  The block form: d_wtab = windows_blocks_scratch_bytes() of list
 struct WinList;  // drx_window_rows.h
 hipError_t launch_decode_windows(const StreamCall &c, void *d_blk, void *d_wtab, const int64_t *d_start, uint64_t start_wave_stride,
                                  uint64_t start_win_stride, const uint32_t *d_count, uint32_t n_win, int64_t offset, uint32_t width,
                                  int16_t pad, int16_t *d_out, uint64_t out_wave_stride, uint64_t out_win_stride, uint32_t *form_out);
-bool windows_blocks_batch(const Geom &G, const void *d_blk);
 uint64_t windows_blocks_scratch_bytes(const Geom &G);
-hipError_t launch_windows_blocks(const StreamCall &c, void *d_blk, void *d_wtab, const WinList &wl, const uint32_t **listed_out,
-                                 const uint32_t **n_listed_out);
+hipError_t launch_windows_blocks(const StreamCall &c, void *d_blk, void *d_wtab, const WinList &wl, BlkFallbackList *list_out);
 // drx_find_pulses (drx_pulses.hip): behind the whole batch's walk (tables_ready as above), the output zeroed by one memset, a lane
 // per waveform that parses, compares every sample with thr[g * thr_stride] + thr (d_thr == nullptr: 0; neg: below it, otherwise
 // above it) and writes the records of the first max_pulses runs of at least min_width samples to int64
 // d_out[total_waves][max_pulses][DRX_PULSE_COLS] and the number of all such runs to d_count[total_waves].
 // ev: {start, walk's end, kernel's end, end}
-// Few long waveforms under the delta filter (pulses_blocks_batch(): d_blk = the block decoder's scratch, d_ptab = the plan's
-// pulses_blocks_scratch_bytes() of block summaries and list, d_pstage = its pulses_blocks_staging_bytes(max_pulses) of staged
-// records, which may be nullptr where that is 0) take the block form of drx_pulses_blocks.hip instead, with the lane kernel
-// behind it for the waveforms it lists.  form_out: DRX_PULSES_FORM_* of include/deltarice_hip.h
+// form_out: DRX_PULSES_FORM_* of include/deltarice_hip.h.  The block form: d_ptab = pulses_blocks_scratch_bytes() of block summaries
+// and lists, d_pstage = pulses_blocks_staging_bytes(max_pulses) of staged records, which may be nullptr where that is 0
 hipError_t launch_find_pulses(const StreamCall &c, void *d_blk, void *d_ptab, void *d_pstage, const int64_t *d_thr, uint64_t thr_stride,
                               int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out,
                               uint32_t *form_out);
-bool pulses_blocks_batch(const Geom &G, const void *d_blk);
 uint64_t pulses_blocks_scratch_bytes(const Geom &G);
 uint64_t pulses_blocks_staging_bytes(const Geom &G, uint32_t max_pulses);
 hipError_t launch_pulses_blocks(const StreamCall &c, void *d_blk, void *d_ptab, void *d_pstage, const int64_t *d_thr, uint64_t thr_stride,
                                 int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out,
-                                const uint32_t **listed_out, const uint32_t **n_listed_out);
+                                BlkFallbackList *list_out);
 hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned long long *d_words16, hipStream_t s);
 // k_chunk_scan + k_chunk_offsets (drx_encode_kernels.hip) over a table of n_i that is not an encode's: header positions relative
 // to the chunk, chunk offsets, DevStatus::total_words and kErrCapacity against out_cap
@@ -403,6 +430,20 @@ struct BlkClassLaunch {
     uint32_t spw, run_len; // look-back slots per waveform, blocks per ticket
     unsigned grid;         // resident workgroups
 };
+// The kernels of the scheme are templates over both: f(lanes per block, words per lane) as std::integral_constant tags
+template <class F> inline void blk_dispatch(int nt, int sw, F f) {
+    auto by_sw = [&](auto nt_tag) {
+        switch (sw) {
+            case 9: f(nt_tag, std::integral_constant<int, 9>{}); break;
+            case 11: f(nt_tag, std::integral_constant<int, 11>{}); break;
+            case 15: f(nt_tag, std::integral_constant<int, 15>{}); break;
+            default: f(nt_tag, std::integral_constant<int, 19>{}); break;
+        }
+    };
+    if (nt == 64) by_sw(std::integral_constant<int, 64>{});
+    else if (nt == 128) by_sw(std::integral_constant<int, 128>{});
+    else by_sw(std::integral_constant<int, 256>{});
+}
 hipError_t blocks_prepare(const Geom &G, uint64_t in_words, const uint32_t *d_wave_words, void *d_blk, hipStream_t s, BlkTables *T,
                           BlkClassLaunch *launches, uint32_t *n_launches);
 uint32_t blocks_iir_tab_words();

@@ -174,8 +174,8 @@ hipError_t launch_find_pulses(const StreamCall &c, void *d_blk, void *d_ptab, vo
                               uint32_t *form_out) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;
-    const bool blocks = d_ptab != nullptr && (d_pstage != nullptr || max_pulses == 0u) && pulses_blocks_batch(G, d_blk);
-    if (form_out) *form_out = blocks ? (DRX_PULSES_FORM_BLOCKS | ((G.dbg & DRX_DBG_PULSES_ALL_FALLBACK) ? DRX_PULSES_FORM_FALLBACK_ALL : 0u)) : DRX_PULSES_FORM_LANES;
+    const bool blocks = d_ptab != nullptr && (d_pstage != nullptr || max_pulses == 0u) && blocks_form_batch(G, d_blk, kPulsesForm);
+    if (form_out) *form_out = blocks_form_word(G, blocks, kPulsesForm);
     if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip): launch_batch_walk()
     hipError_t e = batch_walk_prologue(c);
@@ -187,13 +187,12 @@ hipError_t launch_find_pulses(const StreamCall &c, void *d_blk, void *d_ptab, vo
         // ---- few long waveforms: a workgroup per block of a waveform's stream and the stitch behind it, then a lane per waveform
         // that form lists (the launch is sized from here, at most a lane per waveform of the batch; the list's length is read on
         // the device)
-        const uint32_t *listed = nullptr, *n_listed = nullptr;
-        if ((e = launch_pulses_blocks(c, d_blk, d_ptab, d_pstage, d_thr, thr_stride, thr, neg, min_width, max_pulses, d_count, d_out, &listed,
-                                      &n_listed)) != hipSuccess)
+        BlkFallbackList fl;
+        if ((e = launch_pulses_blocks(c, d_blk, d_ptab, d_pstage, d_thr, thr_stride, thr, neg, min_width, max_pulses, d_count, d_out, &fl)) != hipSuccess)
             return e;
         k_find_pulses_list<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, 0, d_thr, thr_stride, thr,
-                                                                       neg ? 1u : 0u, min_width, max_pulses, c.d_status, d_count, d_out, listed,
-                                                                       n_listed);
+                                                                       neg ? 1u : 0u, min_width, max_pulses, c.d_status, d_count, d_out, fl.listed,
+                                                                       fl.n_listed);
     } else {
         // ---- the kernel: a wavefront per 64 waveforms
         const bool serial = G.n_taps != 0;

@@ -2,7 +2,7 @@
 //
 // A lane per waveform (k_find_pulses, drx_pulses.hip) takes 50-60 ns per sample whatever else runs; a long trace that holds many
 // events is the shape the call is for and the one on which a lane per waveform leaves the chip idle.  The batches that
-// drx_wave_stats gives to its block form (pulses_blocks_batch()) take this form:
+// drx_wave_stats gives to its block form (blocks_form_batch() under kPulsesForm) take this form:
 //
 //   k_pulses_blocks   the block decoder's phase 1, look-back and flags, word for word (drx_blocks_body.inc), and a third phase 2
 //                     (`if constexpr (PULSES)` there): a fast reject -- no lane of the block holds an over sample, which on
@@ -88,8 +88,8 @@ __global__ __launch_bounds__(64) void k_pulses_stitch(Geom G, const uint32_t *__
     const uint32_t n = wave_words[g];
     const uint32_t n_blocks = (n + words_per_block - 1u) / words_per_block;
     // (a waveform with samples and no payload word has had no block to judge it: the lane kernel does)
-    if (all_listed || fail[g] || suspect[g] || (n_blocks == 0u && locate(G, g).len != 0u)) {
-        listed[atomicAdd(n_listed, 1u)] = (uint32_t)g;
+    if (blk_listed(all_listed, fail, suspect, g, [&G, g, n_blocks] { return n_blocks == 0u && locate(G, g).len != 0u; })) {
+        blk_list_append(n_listed, listed, (uint32_t)g);
         return;
     }
     const uint64_t slot0 = g * (uint64_t)slots_per_wave;
@@ -129,26 +129,25 @@ __global__ __launch_bounds__(64) void k_pulses_redo_check(uint32_t n_classes, co
     }
     if (j >= n_redo[cls]) return;
     const uint32_t g = redo[class_off + j];
-    if (fail[g] || suspect[g]) listed[atomicAdd(n_listed, 1u)] = g;
+    if (blk_listed(0u, fail, suspect, g)) blk_list_append(n_listed, listed, g);
 }
 
-// the plan's scratch of this form: u64 table[block slots][kPulseTabWords] | u32 n_listed (+ pad to 8 bytes) | u32 listed[W] |
-// u32 n_redo[kBlkMaxClasses] | u32 redo[W] (class by class, as the launches' own lists lie); the staging buffer is another (it
-// depends on max_pulses)
+// the plan's scratch of this form: u64 table[block slots][kPulseTabWords] | the fallback list | u32 n_redo[kBlkMaxClasses] |
+// u32 redo[W] (class by class, as the launches' own lists lie); the staging buffer is another (it depends on max_pulses)
 struct PulseBlkScratch {
     uint64_t *table;
-    uint32_t *n_listed, *listed, *n_redo, *redo;
+    BlkFallbackList list;
+    uint32_t *n_redo, *redo;
     uint64_t bytes;
 };
 static PulseBlkScratch pulses_blocks_layout(const Geom &G, void *base) {
     const uint64_t slots = blocks_total_slots(G);
     PulseBlkScratch L;
     L.table = reinterpret_cast<uint64_t *>(base);
-    L.n_listed = reinterpret_cast<uint32_t *>(L.table + slots * kPulseTabWords);
-    L.listed = L.n_listed + 2;
-    L.n_redo = L.listed + G.total_waves;
+    L.list = BlkFallbackList::at(L.table + slots * kPulseTabWords);
+    L.n_redo = L.list.listed + G.total_waves;
     L.redo = L.n_redo + kBlkMaxClasses;
-    L.bytes = slots * kPulseTabWords * 8u + 8u + 4u * (2u * G.total_waves + kBlkMaxClasses);
+    L.bytes = slots * kPulseTabWords * 8u + BlkFallbackList::bytes(G.total_waves) + 4u * (G.total_waves + kBlkMaxClasses);
     return L;
 }
 uint64_t pulses_blocks_scratch_bytes(const Geom &G) { return pulses_blocks_layout(G, nullptr).bytes; }
@@ -157,23 +156,15 @@ uint64_t pulses_blocks_staging_bytes(const Geom &G, uint32_t max_pulses) {
     return blocks_total_slots(G) * stage_cap(max_pulses) * (uint64_t)kPulseRecCols * sizeof(int64_t);
 }
 
-// The batches of this form: those launch_wave_stats() gives to blocks, with the rate of THIS call's lane kernel -- k_find_pulses
-// on rare pulses takes 24.1 ms for a lane of 500 000 samples (profiles/find_pulses_bench.txt): 0.048 us per sample.
-constexpr double kPulsesLaneUs = 0.048;
-bool pulses_blocks_batch(const Geom &G, const void *d_blk) {
-    if (G.n_taps != 0 || !d_blk || !blocks_batch(G, kPulsesLaneUs)) return false;
-    return !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS | DRX_DBG_PULSES_LANES));
-}
-
 // k_pulses_blocks and k_pulses_stitch per launch of the block scheme.  The block decoder's scratch is used as the decoder uses it
 // (calls on a plan are ordered on one stream) and reset on the stream first.
 hipError_t launch_pulses_blocks(const StreamCall &call, void *d_blk, void *d_ptab, void *d_pstage, const int64_t *d_thr, uint64_t thr_stride,
                                 int64_t thr, bool neg, uint32_t min_width, uint32_t max_pulses, uint32_t *d_count, int64_t *d_out,
-                                const uint32_t **listed_out, const uint32_t **n_listed_out) {
+                                BlkFallbackList *list_out) {
     const Geom &G = *call.G;
     const hipStream_t s = call.s;
     const PulseBlkScratch A = pulses_blocks_layout(G, d_ptab);
-    hipError_t e = hipMemsetAsync(A.n_listed, 0, 8, s);
+    hipError_t e = hipMemsetAsync(A.list.n_listed, 0, 8, s);
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(A.n_redo, 0, 4u * kBlkMaxClasses, s)) != hipSuccess) return e;
     BlkTables T;
@@ -190,29 +181,18 @@ hipError_t launch_pulses_blocks(const StreamCall &call, void *d_blk, void *d_pta
         BlkPulseArgs a = pa;
         if (again) a.n_redo = A.n_redo + i;
         const uint32_t *list = again ? A.redo + class_off(c) : c.list;
-        auto go = [&](auto nt_tag, auto sw_tag) {
+        blk_dispatch(c.nt, c.sw, [&](auto nt_tag, auto sw_tag) {
             constexpr int NT = decltype(nt_tag)::value, SW = decltype(sw_tag)::value;
             k_pulses_blocks<NT, SW><<<c.grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, c.info, c.spw, c.run_len,
                                                           T.state, T.ends, c.info + 2, T.fail, T.suspect, call.d_status, a, c.n_waves, list);
-        };
-        auto by_sw = [&](auto nt_tag) {
-            switch (c.sw) {
-                case 9: go(nt_tag, std::integral_constant<int, 9>{}); break;
-                case 11: go(nt_tag, std::integral_constant<int, 11>{}); break;
-                case 15: go(nt_tag, std::integral_constant<int, 15>{}); break;
-                default: go(nt_tag, std::integral_constant<int, 19>{}); break;
-            }
-        };
-        if (c.nt == 64) by_sw(std::integral_constant<int, 64>{});
-        else if (c.nt == 128) by_sw(std::integral_constant<int, 128>{});
-        else by_sw(std::integral_constant<int, 256>{});
+        });
     };
     for (uint32_t i = 0; i < n_cls; ++i) blocks(i, false);
     for (uint32_t i = 0; i < n_cls; ++i) {
         const BlkClassLaunch &c = cls[i];
         k_pulses_stitch<<<blocks_for(c.n_waves, 64), 64, 0, s>>>(G, call.d_wave_words, c.n_waves, c.list, (uint32_t)c.nt * (uint32_t)c.sw, c.spw, A.table,
                                                                 pa.staging, pa.cap, pa.neg, min_width, max_pulses, T.fail, T.suspect,
-                                                                (G.dbg & DRX_DBG_PULSES_ALL_FALLBACK) ? 1u : 0u, A.n_listed, A.listed, A.n_redo + i,
+                                                                (G.dbg & kPulsesForm.all_fallback_flag) ? 1u : 0u, A.list.n_listed, A.list.listed, A.n_redo + i,
                                                                 A.redo + class_off(c), call.d_status, d_count, d_out);
     }
     // The second launch, where a block can have staged too few records at all (max_pulses above the cap): the block scheme's
@@ -222,11 +202,10 @@ hipError_t launch_pulses_blocks(const StreamCall &call, void *d_blk, void *d_pta
         if ((e = blocks_prepare(G, call.in_words, call.d_wave_words, d_blk, s, &T, cls, &n_cls)) != hipSuccess) return e;
         for (uint32_t i = 0; i < n_cls; ++i) blocks(i, true);
         for (uint32_t i = 0; i < n_cls; ++i)
-            k_pulses_redo_check<<<blocks_for(cls[i].n_waves, 64), 64, 0, s>>>(n_cls, A.n_redo, A.redo, class_off(cls[i]), i, T.fail, T.suspect, A.n_listed,
-                                                                             A.listed, call.d_status);
+            k_pulses_redo_check<<<blocks_for(cls[i].n_waves, 64), 64, 0, s>>>(n_cls, A.n_redo, A.redo, class_off(cls[i]), i, T.fail, T.suspect, A.list.n_listed,
+                                                                             A.list.listed, call.d_status);
     }
-    *listed_out = A.listed;
-    *n_listed_out = A.n_listed;
+    *list_out = A.list;
     return hipGetLastError();
 }
 

@@ -245,8 +245,8 @@ __global__ __launch_bounds__(64) void k_wave_stats_serial(Geom G, const uint32_t
 hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, uint32_t *form_out) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;
-    const bool blocks = d_sacc != nullptr && stats_blocks_batch(G, d_blk);
-    if (form_out) *form_out = blocks ? (DRX_STATS_FORM_BLOCKS | ((G.dbg & DRX_DBG_STATS_ALL_FALLBACK) ? DRX_STATS_FORM_FALLBACK_ALL : 0u)) : DRX_STATS_FORM_LANES;
+    const bool blocks = d_sacc != nullptr && blocks_form_batch(G, d_blk, kStatsForm);
+    if (form_out) *form_out = blocks_form_word(G, blocks, kStatsForm);
     if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip), all of it on this stream: nothing here is worth a fork
     hipError_t e = batch_walk_prologue(c);
@@ -254,9 +254,9 @@ hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uin
     if (blocks) {
         // ---- few long waveforms: a workgroup per block of a waveform's stream, then a lane per waveform that form lists (the
         // launch is sized from here, at most a lane per waveform of the batch; the list's length is read on the device)
-        const uint32_t *listed = nullptr, *n_listed = nullptr;
-        if ((e = launch_stats_blocks(c, d_blk, d_sacc, head_len, d_out, &listed, &n_listed)) != hipSuccess) return e;
-        k_wave_stats_serial<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, 0, head_len, c.d_status, d_out, listed, n_listed);
+        BlkFallbackList fl;
+        if ((e = launch_stats_blocks(c, d_blk, d_sacc, head_len, d_out, &fl)) != hipSuccess) return e;
+        k_wave_stats_serial<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.d_wave_off, c.d_wave_words, 0, head_len, c.d_status, d_out, fl.listed, fl.n_listed);
     } else {
         // ---- the kernel: a wavefront per 64 waveforms
         const bool serial = G.n_taps != 0;

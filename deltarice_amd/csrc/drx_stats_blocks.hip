@@ -72,8 +72,9 @@ __global__ __launch_bounds__(256) void k_stats_blocks_finish(uint64_t total_wave
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (st->err) return;  // (as k_stats_blocks)
     if (g >= total_waves) return;
-    if (all_listed || fail[g] || suspect[g]) {
-        listed[atomicAdd(n_listed, 1u)] = (uint32_t)g;
+    // (a waveform with samples and no payload word is not asked about here, as it is in the other forms)
+    if (blk_listed(all_listed, fail, suspect, g)) {
+        blk_list_append(n_listed, listed, (uint32_t)g);
         return;
     }
     const unsigned long long *a = acc + 6u * g;
@@ -95,44 +96,30 @@ __global__ __launch_bounds__(256) void k_stats_blocks_finish(uint64_t total_wave
     }
 }
 
-// the plan's scratch of this form: u64 acc[W][6] | u32 n_listed (+ pad to 8 bytes) | u32 listed[W]
+// the plan's scratch of this form: u64 acc[W][6] | the fallback list
 struct StatsBlkScratch {
     unsigned long long *acc;
-    uint32_t *n_listed, *listed;
+    BlkFallbackList list;
     uint64_t bytes;
 };
 static StatsBlkScratch stats_blocks_layout(const Geom &G, void *base) {
     StatsBlkScratch L;
     L.acc = reinterpret_cast<unsigned long long *>(base);
-    L.n_listed = reinterpret_cast<uint32_t *>(L.acc + 6u * G.total_waves);
-    L.listed = L.n_listed + 2;
-    L.bytes = 48u * G.total_waves + 8u + 4u * G.total_waves;
+    L.list = BlkFallbackList::at(L.acc + 6u * G.total_waves);
+    L.bytes = 48u * G.total_waves + BlkFallbackList::bytes(G.total_waves);
     return L;
 }
 uint64_t stats_blocks_scratch_bytes(const Geom &G) { return stats_blocks_layout(G, nullptr).bytes; }
 
-// The batches of this form: those drx_decode gives to the block decoder, under the delta filter, on a plan that has the block
-// decoder's scratch (d_blk), unless a debug flag keeps the batch on the lane kernels.  The decoder's own test, blocks against
-// lanes by their cost, with the rate of THIS call's lane kernel: k_wave_stats takes 52 ns per sample and lane where
-// k_decode_lanes takes 60, so a uniform batch at the decoder's break-even -- 4 chunks of 2100 x 7000: one
-// block per waveform, 393 us of blocks against 420 us of decoding lanes, but 364 us of reducing lanes -- stays a lane per
-// waveform here.  (A ragged plan's choice was made from the host's chunk table when the plan was created: the decoder's.)
-constexpr double kStatsLaneUs = 0.052;
-bool stats_blocks_batch(const Geom &G, const void *d_blk) {
-    if (G.n_taps != 0 || !d_blk || !blocks_batch(G, kStatsLaneUs)) return false;
-    return !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS | DRX_DBG_STATS_LANES));
-}
-
 // k_stats_blocks per launch of the block scheme, then k_stats_blocks_finish.  The block decoder's scratch is used as the decoder
 // uses it (calls on a plan are ordered on one stream) and reset on the stream first; d_sacc is the plan's scratch of this form.
-// listed_out / n_listed_out: the device list of the waveforms left to the lane kernel, and its length.
-hipError_t launch_stats_blocks(const StreamCall &call, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out,
-                               const uint32_t **listed_out, const uint32_t **n_listed_out) {
+// list_out: the device list of the waveforms left to the lane kernel.
+hipError_t launch_stats_blocks(const StreamCall &call, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, BlkFallbackList *list_out) {
     const Geom &G = *call.G;
     const hipStream_t s = call.s;
     const StatsBlkScratch A = stats_blocks_layout(G, d_sacc);
     const unsigned nb = blocks_for(G.total_waves, 256);
-    k_stats_blocks_reset<<<nb, 256, 0, s>>>(G.total_waves, A.acc, A.n_listed);
+    k_stats_blocks_reset<<<nb, 256, 0, s>>>(G.total_waves, A.acc, A.list.n_listed);
     BlkTables T;
     BlkClassLaunch cls[kBlkMaxClasses];
     uint32_t n_cls = 0;
@@ -140,27 +127,15 @@ hipError_t launch_stats_blocks(const StreamCall &call, void *d_blk, void *d_sacc
     if (e != hipSuccess) return e;
     for (uint32_t i = 0; i < n_cls; ++i) {
         const BlkClassLaunch &c = cls[i];
-        auto go = [&](auto nt_tag, auto sw_tag) {
+        blk_dispatch(c.nt, c.sw, [&](auto nt_tag, auto sw_tag) {
             constexpr int NT = decltype(nt_tag)::value, SW = decltype(sw_tag)::value;
             k_stats_blocks<NT, SW><<<c.grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, c.info, c.spw, c.run_len,
                                                          T.state, T.ends, c.info + 2, T.fail, T.suspect, call.d_status, head_len, A.acc, c.n_waves, c.list);
-        };
-        auto by_sw = [&](auto nt_tag) {
-            switch (c.sw) {
-                case 9: go(nt_tag, std::integral_constant<int, 9>{}); break;
-                case 11: go(nt_tag, std::integral_constant<int, 11>{}); break;
-                case 15: go(nt_tag, std::integral_constant<int, 15>{}); break;
-                default: go(nt_tag, std::integral_constant<int, 19>{}); break;
-            }
-        };
-        if (c.nt == 64) by_sw(std::integral_constant<int, 64>{});
-        else if (c.nt == 128) by_sw(std::integral_constant<int, 128>{});
-        else by_sw(std::integral_constant<int, 256>{});
+        });
     }
-    k_stats_blocks_finish<<<nb, 256, 0, s>>>(G.total_waves, A.acc, T.fail, T.suspect, (G.dbg & DRX_DBG_STATS_ALL_FALLBACK) ? 1u : 0u, A.n_listed,
-                                             A.listed, call.d_status, d_out);
-    *listed_out = A.listed;
-    *n_listed_out = A.n_listed;
+    k_stats_blocks_finish<<<nb, 256, 0, s>>>(G.total_waves, A.acc, T.fail, T.suspect, (G.dbg & kStatsForm.all_fallback_flag) ? 1u : 0u, A.list.n_listed,
+                                             A.list.listed, call.d_status, d_out);
+    *list_out = A.list;
     return hipGetLastError();
 }
 

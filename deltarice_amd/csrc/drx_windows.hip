@@ -119,8 +119,8 @@ hipError_t launch_decode_windows(const StreamCall &c, void *d_blk, void *d_wtab,
                                  int16_t pad, int16_t *d_out, uint64_t out_wave_stride, uint64_t out_win_stride, uint32_t *form_out) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;
-    const bool blocks = d_wtab != nullptr && windows_blocks_batch(G, d_blk);
-    if (form_out) *form_out = blocks ? (DRX_WINDOWS_FORM_BLOCKS | ((G.dbg & DRX_DBG_WINDOWS_ALL_FALLBACK) ? DRX_WINDOWS_FORM_FALLBACK_ALL : 0u)) : DRX_WINDOWS_FORM_LANES;
+    const bool blocks = d_wtab != nullptr && blocks_form_batch(G, d_blk, kWindowsForm);
+    if (form_out) *form_out = blocks_form_word(G, blocks, kWindowsForm);
     if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip): launch_batch_walk()
     hipError_t e = batch_walk_prologue(c);
@@ -130,10 +130,10 @@ hipError_t launch_decode_windows(const StreamCall &c, void *d_blk, void *d_wtab,
     if (blocks) {
         // ---- few long waveforms: the pads, a workgroup per block of a waveform's stream, then a lane per waveform that form lists
         // (the launch is sized from here, at most a lane per waveform of the batch; the list's length is read on the device)
-        const uint32_t *listed = nullptr, *n_listed = nullptr;
-        if ((e = launch_windows_blocks(c, d_blk, d_wtab, wl, &listed, &n_listed)) != hipSuccess) return e;
+        BlkFallbackList fl;
+        if ((e = launch_windows_blocks(c, d_blk, d_wtab, wl, &fl)) != hipSuccess) return e;
         k_decode_windows_list<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, 0, wl, c.d_status,
-                                                                          listed, n_listed);
+                                                                          fl.listed, fl.n_listed);
     } else {
         // ---- the kernel: a wavefront per 64 waveforms
         const bool serial = G.n_taps != 0;

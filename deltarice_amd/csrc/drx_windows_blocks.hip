@@ -2,7 +2,7 @@
 //
 // A lane per waveform (k_decode_windows, drx_windows.hip) takes about 50 ns per sample whatever else runs, and a window deep in a
 // long trace costs the whole trace in front of it.  The batches that drx_wave_stats gives to its block form
-// (windows_blocks_batch()) take this form:
+// (blocks_form_batch() under kWindowsForm) take this form:
 //
 //   k_windows_pads           every row of the call, whole, is filled with `pad`: the blocks overwrite what the windows hold of
 //                            their waveforms.
@@ -69,40 +69,20 @@ __global__ __launch_bounds__(256) void k_windows_blocks_finish(Geom G, const uin
     const uint64_t g = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (st->err) return;  // (as k_windows_blocks)
     if (g >= G.total_waves) return;
-    if (all_listed || fail[g] || suspect[g] || (wave_words[g] == 0u && locate(G, g).len != 0u)) listed[atomicAdd(n_listed, 1u)] = (uint32_t)g;
+    if (blk_listed(all_listed, fail, suspect, g, [&] { return wave_words[g] == 0u && locate(G, g).len != 0u; }))
+        blk_list_append(n_listed, listed, (uint32_t)g);
 }
 
-// the plan's scratch of this form: u32 n_listed (+ pad to 8 bytes) | u32 listed[W]
-struct WindowsBlkScratch {
-    uint32_t *n_listed, *listed;
-    uint64_t bytes;
-};
-static WindowsBlkScratch windows_blocks_layout(const Geom &G, void *base) {
-    WindowsBlkScratch L;
-    L.n_listed = reinterpret_cast<uint32_t *>(base);
-    L.listed = L.n_listed + 2;
-    L.bytes = 8u + 4u * G.total_waves;
-    return L;
-}
-uint64_t windows_blocks_scratch_bytes(const Geom &G) { return windows_blocks_layout(G, nullptr).bytes; }
-
-// The batches of this form: those launch_wave_stats() gives to blocks, with the rate of THIS call's lane kernel -- k_decode_windows
-// on sparse windows takes 25.7 ms for a lane of 500 000 samples, 700 ms for one of 14 M and 4.67 ms for one of 81 920
-// (profiles/decode_windows_bench.txt): 0.050 - 0.057 us per sample, the NOPTREX shape's 0.051 taken.
-constexpr double kWindowsLaneUs = 0.051;
-bool windows_blocks_batch(const Geom &G, const void *d_blk) {
-    if (G.n_taps != 0 || !d_blk || !blocks_batch(G, kWindowsLaneUs)) return false;
-    return !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS | DRX_DBG_WINDOWS_LANES));
-}
+// the plan's scratch of this form: the fallback list
+uint64_t windows_blocks_scratch_bytes(const Geom &G) { return BlkFallbackList::bytes(G.total_waves); }
 
 // k_windows_pads, k_windows_blocks per launch of the block scheme, then k_windows_blocks_finish.  The block decoder's scratch is
 // used as the decoder uses it (calls on a plan are ordered on one stream) and reset on the stream first; d_wtab is the plan's
-// scratch of this form.  listed_out / n_listed_out: the device list of the waveforms left to the lane kernel, and its length.
-hipError_t launch_windows_blocks(const StreamCall &call, void *d_blk, void *d_wtab, const WinList &wl, const uint32_t **listed_out,
-                                 const uint32_t **n_listed_out) {
+// scratch of this form.  list_out: the device list of the waveforms left to the lane kernel.
+hipError_t launch_windows_blocks(const StreamCall &call, void *d_blk, void *d_wtab, const WinList &wl, BlkFallbackList *list_out) {
     const Geom &G = *call.G;
     const hipStream_t s = call.s;
-    const WindowsBlkScratch A = windows_blocks_layout(G, d_wtab);
+    const BlkFallbackList A = BlkFallbackList::at(d_wtab);
     const uint64_t rows = G.total_waves * (uint64_t)wl.n_win;
     k_windows_pads<<<(unsigned)(rows < (1ull << 20) ? rows : (1ull << 20)), 256, 0, s>>>(G.total_waves, wl, A.n_listed, call.d_status);
     BlkTables T;
@@ -113,28 +93,16 @@ hipError_t launch_windows_blocks(const StreamCall &call, void *d_blk, void *d_wt
     const BlkWindowArgs wa{wl};
     for (uint32_t i = 0; i < n_cls; ++i) {
         const BlkClassLaunch &c = cls[i];
-        auto go = [&](auto nt_tag, auto sw_tag) {
+        blk_dispatch(c.nt, c.sw, [&](auto nt_tag, auto sw_tag) {
             constexpr int NT = decltype(nt_tag)::value, SW = decltype(sw_tag)::value;
             k_windows_blocks<NT, SW><<<c.grid, NT, 0, s>>>(G, call.d_in, call.in_words, call.d_wave_off, call.d_wave_words, c.info, c.spw, c.run_len,
                                                            T.state, T.ends, c.info + 2, T.fail, T.suspect, call.d_status, wa, c.n_waves, c.list);
-        };
-        auto by_sw = [&](auto nt_tag) {
-            switch (c.sw) {
-                case 9: go(nt_tag, std::integral_constant<int, 9>{}); break;
-                case 11: go(nt_tag, std::integral_constant<int, 11>{}); break;
-                case 15: go(nt_tag, std::integral_constant<int, 15>{}); break;
-                default: go(nt_tag, std::integral_constant<int, 19>{}); break;
-            }
-        };
-        if (c.nt == 64) by_sw(std::integral_constant<int, 64>{});
-        else if (c.nt == 128) by_sw(std::integral_constant<int, 128>{});
-        else by_sw(std::integral_constant<int, 256>{});
+        });
     }
     k_windows_blocks_finish<<<blocks_for(G.total_waves, 256), 256, 0, s>>>(G, call.d_wave_words, T.fail, T.suspect,
-                                                                           (G.dbg & DRX_DBG_WINDOWS_ALL_FALLBACK) ? 1u : 0u, A.n_listed, A.listed,
+                                                                           (G.dbg & kWindowsForm.all_fallback_flag) ? 1u : 0u, A.n_listed, A.listed,
                                                                            call.d_status);
-    *listed_out = A.listed;
-    *n_listed_out = A.n_listed;
+    *list_out = A;
     return hipGetLastError();
 }
 
