@@ -22,7 +22,7 @@ struct ChunkDesc {
     uint32_t pad_;
 };
 
-// Passed to kernels by value.  Its device tables are buffers of the plan (drx_api.hip), which keeps no other pointer to them;
+// Passed to kernels by value.  Its device tables are buffers of the plan (drx_api.h), which keeps no other pointer to them;
 // a ragged plan's tables are what each path's planner (*_plan_ragged() below) computed from the host's chunk table.
 struct Geom {
     const ChunkDesc *chunks;  // device pointer, n_chunks entries (unused when uniform)
@@ -45,7 +45,7 @@ struct Geom {
     uint32_t enc_t[4];
     uint64_t total_samples;  // of the batch
     // pinned host word (device-visible) that every encoder writes the batch's encoded word count to beside DevStatus: the host
-    // reads it -- without waiting for anything -- when it chooses the NEXT encode's kernel (drx_api.hip, stream_encoder_suits())
+    // reads it -- without waiting for anything -- when it chooses the NEXT encode's kernel (drx_api_encode.hip, stream_encoder_suits())
     uint64_t *host_words;
     uint32_t dbg;  // "debug_flags" context option (DRX_DBG_* of include/deltarice_hip.h); 0 in normal use
     // ragged batches, walk inside the decode launch: chunk indices, short-waveform chunks first
@@ -103,7 +103,7 @@ constexpr uint32_t kErrInternal = 4u;
 
 // ---------------------------------------------------------------------------
 // Call frames: what the host launchers below are given in front of a call's own arguments.  Plain aggregates that the C ABI
-// glue fills from the plan once per call (call_begin(), drx_api.hip); they stop at the <<< >>>, kernels take loose arguments.
+// glue fills from the plan once per call (call_begin(), drx_api.h); they stop at the <<< >>>, kernels take loose arguments.
 // ---------------------------------------------------------------------------
 // A call on an ENCODED batch.  tables_ready: wave_off / wave_words are already filled in (the one-chunk host path walks the
 // header chain on the CPU while the chunk is in flight to the device; the side-band forms derive them from the caller's
@@ -236,7 +236,7 @@ hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_
 // lanes by their cost (blocks_batch(), drx_blocks.hip), with the rate of THIS call's lane kernel, on a plan that has d_blk, unless
 // a debug flag keeps the batch on lanes (DRX_DBG_NO_LONG_PATHS, DRX_DBG_LONG_NOT_BLOCKS, the call's own lanes_flag).  A ragged
 // plan's choice was made from the host's chunk table when the plan was created: the decoder's.  Each form's scratch beyond d_blk
-// belongs to the plan and is allocated by the first call that takes the form (form_scratch(), drx_api.hip).
+// belongs to the plan and is allocated by the first call that takes the form (form_scratch(), drx_api_stream.hip).
 struct BlkFormRule {
     double lane_us;  // what the call's lane kernel takes per sample
     uint32_t lanes_flag, all_fallback_flag;  // DRX_DBG_*: never the block form; the block form lists every waveform

@@ -633,7 +633,7 @@ def async_chains():
     return chains
 
 
-# (encode_impl, debug_flags) under which the `short` geometry takes each encoder DRX_ENC_* 1 ... 6 (route_encode(), drx_api.hip)
+# (encode_impl, debug_flags) under which the `short` geometry takes each encoder DRX_ENC_* 1 ... 6 (route_encode(), drx_api_encode.hip)
 TOUR_ENCODERS = {1: (0, 0), 2: (2, D.DBG_NO_PIECES), 3: (1, D.DBG_NO_LONG_PATHS | D.DBG_NO_PIECES | D.DBG_FORCE_STREAM), 4: (2, 0),
                  5: (2, D.DBG_FORCE_STREAM), 6: (2, D.DBG_FORCE_STREAM_SEGS)}
 # (plan of the tour, context settings, DRX_PATH_* bits the decode must report): the decoders `short` does not reach
@@ -695,4 +695,21 @@ def filter_cycle():
         M.gather(0, size=64)
         M.gather_decode(0, len(M.steps) - 1)
         M.estimate(0)
+    return M.geoms, M.steps
+
+
+def scratch_growth():
+    """One plan of `short` through the scratch that a later call may need larger (Buffers::reserve(), csrc/drx_api.h), each
+    time smaller, larger, smaller: the selection's staging pair (a list of 1, of 3000, of 1: the first pair holds some 4 KB);
+    the gather's scratch beside it, regrown by a SIZING call whose gather then resumes; and a sizing call, a larger selection
+    -- which fills the staging pair with its own list -- then the gather the sizing call was for, which must not resume."""
+    M = Model(["short"], "growth")
+    for n in (1, 3000, 1):
+        M.select(0, size=n, sideband=False)
+    M.gather(0, size=1)
+    M.gather(0, size=3000, op="gather_after_sizing")
+    M.gather(0, size=3)
+    sized = M.gather_size_only(0, size=64)
+    M.select(0, size=5000)
+    M.gather(0, same_as=sized)
     return M.geoms, M.steps

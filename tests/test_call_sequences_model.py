@@ -22,6 +22,7 @@ def all_schedules():
         yield f"chain[{name}]", steps
     yield "tour", CS.route_tour()[1]
     yield "filters", CS.filter_cycle()[1]
+    yield "growth", CS.scratch_growth()[1]
     for seed in (0, 1, 2):
         yield f"host[{seed}]", CS.host_sequence(seed)
 

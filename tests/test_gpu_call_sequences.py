@@ -369,6 +369,50 @@ def test_host_path_between_geometries(ctx, O):
     assert not errors, errors[:3]
 
 
+def test_scratch_grows_and_is_kept(ctx, O):
+    """A new plan through CS.scratch_growth(): a list of 1, of 3000, of 1 through the selection's staging pair; a sizing call
+    that regrows the gather's scratch, and the gather that resumes from it; a sizing call, a larger selection, then the
+    gather the sizing call was for."""
+    geoms, steps = CS.scratch_growth()
+    Runner(ctx, geoms).run_all(steps)
+
+
+@pytest.mark.parametrize("wave_len", [0, 300, 400])
+def test_host_path_buffers_grow_and_are_kept(O, wave_len):
+    """A NEW context's one-chunk path at 1000, then 200 000, then 1000 samples, forward and reverse: its device buffers are
+    replaced by the second size and kept by the third, its cached plan is replaced each time.  WaveformLength 300 gives the large
+    chunk 667 waveforms, more than the 512 up to which the header chain is walked on the CPU; 400 gives it 500, whose tables
+    need a larger pinned buffer than the one the first call left."""
+    import deltarice_amd as dr
+    c = dr.Context(0)
+    try:
+        for n in (1000, 200_000, 1000):
+            e = CS.Expect((n,), (wave_len,), 8, None, "gauss10", CS._seed("host growth", n, wave_len))
+            opts = CS.opts_of(8, wave_len, None)
+            assert c.filter_chunk(e.x, opts) == e.words.tobytes(), (n, wave_len, "forward")
+            assert c.filter_chunk(e.words, opts, reverse=True) == e.x.tobytes(), (n, wave_len, "reverse")
+    finally:
+        c.close()
+
+
+def test_host_staging_grows_and_is_kept():
+    """drx_ctx_host_staging on a NEW context at 1000, then 200 000, then 1000 bytes: every byte asked for is the caller's to
+    write, and the buffer the second call made serves the third."""
+    import deltarice_amd as dr
+    c = dr.Context(0)
+    try:
+        at = []
+        for n in (1000, 200_000, 1000):
+            p = C.c_void_p()
+            assert c.lib.drx_ctx_host_staging(c._h, n, C.byref(p)) == 0 and p.value, n
+            C.memset(p, 0x5A, n)
+            assert C.string_at(p.value + n - 4, 4) == b"\x5a" * 4
+            at.append(p.value)
+        assert at[2] == at[1], at
+    finally:
+        c.close()
+
+
 def test_routes_seen_over_the_module(ctx, O):
     """Every encoder and every decode path has run in this module, and every encoder has been followed, on the same plan,
     by another encoder, a decode with the header walk inside the launch, a decode behind a parallel walk and

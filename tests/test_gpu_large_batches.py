@@ -9,7 +9,7 @@ of 1 + W + sum n_i (uint64), five spot chunks against the oracle's bytes (chunk 
 the chunk after that, the last), the whole stream against the first cell's word for word, last_encode_path(); per decoder
 cell: torch.equal with x[:T] and last_decode_path().  RiceParameter 8 throughout.
 
-The expected paths are what route_encode() (drx_api.hip), route_decode() (drx_decode_kernels.hip) and route_walk()
+The expected paths are what route_encode() (drx_api_encode.hip), route_decode() (drx_decode_kernels.hip) and route_walk()
 (drx_walk.hip) say for these geometries, with 309 chunks (271 of the long waveforms) and k = 3:
   runs-512     L 512 is no packed run (a multiple of 8 BELOW 512) but 14 waveforms make a run of the pieces encoder: PIECES for
                encode_impl 2 and 1.  309 chunks are more than the 224 the block-parallel walk reads: the walk runs inside the

@@ -65,7 +65,7 @@ CELLS = {
 # behind the side-band's tables no walk runs and nothing is fused into the lanes launch
 SIDE_PATH = {"stream": D.PATH_BLOCKS, "short": D.PATH_LANES, "runs-512": D.PATH_LANES, "long": D.PATH_BLOCKS,
              "iir": D.PATH_BLOCKS | D.PATH_IIR_FUSED, "fir5": D.PATH_SIMPLE, "ragged": D.PATH_LANES, "whole-chunk": D.PATH_BLOCKS}
-# (encode_impl, debug flags, DRX_ENC_* expected): route_encode() in drx_api.hip
+# (encode_impl, debug flags, DRX_ENC_* expected): route_encode() in drx_api_encode.hip
 ENCODE = {
     "stream": [(2, 0, D.ENC_FUSED), (2, D.DBG_FORCE_STREAM, D.ENC_STREAM), (2, D.DBG_FORCE_STREAM_SEGS, D.ENC_STREAM_SEGS),
                (2, D.DBG_FORCE_PIECES, D.ENC_PIECES), (2, D.DBG_FORCE_SEGMENTS, D.ENC_SEGMENTS), (0, 0, D.ENC_TWO_PASS)],

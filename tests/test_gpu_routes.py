@@ -1,5 +1,5 @@
 """Where each encode_impl and debug flag sends a batch: drx_plan_last_encode_path / drx_plan_last_decode_path over a table
-of small batches (route_encode() in drx_api.hip, route_decode() in drx_decode_kernels.hip and, for the walk in front of the
+of small batches (route_encode() in drx_api_encode.hip, route_decode() in drx_decode_kernels.hip and, for the walk in front of the
 decoder, route_walk() in drx_walk.hip), with the round trip of every case."""
 import numpy as np
 import pytest

@@ -25,7 +25,7 @@ def source(name):
 NAMED = {
     "drx_select.hip": ("kSelSeg", "kSelSegBits", "kSelBlockWords", "kSelMaxGrid"),
     "drx_gather.hip": ("kGsThreads", "kGsPer", "kGsBlock", "kGcPiece"),
-    "drx_api.hip": ("kGatherWavesFromWords",),
+    "drx_api_select.hip": ("kGatherWavesFromWords",),
     "drx_walk.hip": ("kSwSegs", "kSwCap"),
     "drx_walk.h": ("kWalkShortLen",),
 }
@@ -62,9 +62,9 @@ def launch_constants():
     m = re.search(r"slots\s*=\s*\(mean_words \+ kGcPiece - 1\)\s*/\s*kGcPiece;\s*slots\s*=\s*std::max<uint64_t>\(1,\s*std::min<uint64_t>\(slots,\s*(\d+)\)\);", g)
     assert m, "drx_gather.hip: how launch_gather() gets `slots` from mean_words"
     K["slots_max"] = int(m.group(1))
-    api = source("drx_api.hip")
-    assert re.search(r"mean_words\s*=\s*in_words\s*/\s*G\.total_waves;", api), "drx_api.hip: mean_words"
-    assert re.search(r"tiles\s*=\s*\(mean_words < kGatherWavesFromWords\)\s*!=", api), "drx_api.hip: the choice of the copy form"
+    api = source("drx_api_select.hip")
+    assert re.search(r"mean_words\s*=\s*in_words\s*/\s*G\.total_waves;", api), "drx_api_select.hip: mean_words"
+    assert re.search(r"tiles\s*=\s*\(mean_words < kGatherWavesFromWords\)\s*!=", api), "drx_api_select.hip: the choice of the copy form"
     w = source("drx_walk.hip")  # k_walk_sparse: the number of chains, their cuts, what flags a chunk
     assert re.search(r"uint32_t S = W / 8u;\s*S = S > kSwSegs \? kSwSegs : \(S < 1u \? 1u : S\);\s*if \(len_w / W > 8192u\) S = 1u;", w), "drx_walk.hip: chains per chunk"
     assert re.search(r"from = 1u \+ \(uint32_t\)\(\(\(uint64_t\)\(len_w - 1u\) \* sg\) / S\);", w), "drx_walk.hip: a chain's cut"
