@@ -33,9 +33,11 @@ PULSE_COLS = 5
 ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
 DBG_NO_LONG_PATHS = 256
 DBG_LONG_NOT_BLOCKS = 512
+DBG_TRANSCODE_LANES = 1024
 DBG_NO_PARALLEL_WALKS = 2048
 DBG_NO_PIECES = 4096
 DBG_FORCE_SEGMENTS = 8192
+DBG_TRANSCODE_ALL_FALLBACK = 16384
 DBG_FORCE_PIECES = 32768
 DBG_NO_WIDE_FUSED = 65536
 DBG_RAGGED_ONE_LANES_LAUNCH = 131072
@@ -59,6 +61,8 @@ PULSES_FORM_LANES, PULSES_FORM_BLOCKS, PULSES_FORM_FALLBACK_ALL = 1, 2, 4
 PULSES_STAGE_CAP = 8  # DRX_PULSES_STAGE_CAP
 # DRX_WINDOWS_FORM_*: drx_plan_last_windows_form (tests/test_decode_windows_abi.py holds them equal)
 WINDOWS_FORM_LANES, WINDOWS_FORM_BLOCKS, WINDOWS_FORM_FALLBACK_ALL = 1, 2, 4
+# DRX_TRANSCODE_FORM_*: drx_plan_last_transcode_form (tests/test_transcode_blocks_abi.py holds them equal)
+TRANSCODE_FORM_LANES, TRANSCODE_FORM_BLOCKS, TRANSCODE_FORM_FALLBACK_ALL = 1, 2, 4
 
 
 class DrxOpts(C.Structure):
@@ -103,6 +107,8 @@ SIGNATURES = {
     "drx_plan_last_pulses_form": (C.c_uint32, [_vp]),
     "drx_plan_last_windows_form": (C.c_uint32, [_vp]),
     "drx_plan_last_windows_listed": (C.c_uint32, [_vp]),
+    "drx_plan_last_transcode_form": (C.c_uint32, [_vp]),
+    "drx_plan_last_transcode_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_redone": (C.c_uint32, [_vp]),
     "drx_plan_read_wave_words": (C.c_int, [_vp, C.POINTER(_u32)]),

@@ -756,6 +756,17 @@ class Plan:
         judged suspect by the block parse; their rows are written again and judged there); 0 for the lane form."""
         return int(self.ctx.lib.drx_plan_last_windows_listed(self._h))
 
+    def last_transcode_form(self) -> int:
+        """DRX_TRANSCODE_FORM_* (include/deltarice_hip.h): which form the last transcode (the sizing call included) or
+        estimate_words_encoded took -- a lane per waveform, or a workgroup per block of a waveform's stream (few long waveforms,
+        any prediction filter); 0 before the plan's first such call."""
+        return int(self.ctx.lib.drx_plan_last_transcode_form(self._h))
+
+    def last_transcode_listed(self) -> int:
+        """After finish(): how many waveforms the last transcode's block form handed to the lane kernels behind it (flagged or
+        judged suspect by the block parse, or with samples and no payload word); 0 for the lane form."""
+        return int(self.ctx.lib.drx_plan_last_transcode_listed(self._h))
+
     def last_pulses_listed(self) -> int:
         """After finish(): how many waveforms the last find_pulses' block form handed to the lane kernel behind it (flagged by the
         block parse, or short of staged records); 0 for the lane form."""

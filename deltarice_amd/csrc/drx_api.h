@@ -184,7 +184,8 @@ struct drx_plan {
     } pulses;
     // drx_transcode / drx_estimate_words_encoded: uint64 chunk_words[n_chunks + 1] | uint64 est[16] | uint32 n_i'[W] | uint32
     // header positions[W] of the RESULT (the plan's own tables describe the source); first call
-    struct Transcode { void *d = nullptr; } trc;
+    // ... and the block form's own scratch and form word (trc_blocks_scratch_bytes(): accumulators, list, block-slot table)
+    struct Transcode { void *d = nullptr; BlockForm blocks; } trc;
     // drx_decode_select and the gather's front end
     struct Selection {
         Grown h, d;  // uint64 sel[n_sel] | uint32 chunk_n[n_out] | uint32 chunk lists[touched]: pinned staging and its device copy

@@ -430,6 +430,8 @@ uint32_t drx_plan_last_encode_path(const drx_plan *p) { return p ? p->enc.last_p
 uint32_t drx_plan_last_stats_form(const drx_plan *p) { return p ? p->stats.last_form : 0u; }
 uint32_t drx_plan_last_pulses_form(const drx_plan *p) { return p ? p->pulses.last_form : 0u; }
 uint32_t drx_plan_last_windows_form(const drx_plan *p) { return p ? p->windows.last_form : 0u; }
+uint32_t drx_plan_last_transcode_form(const drx_plan *p) { return p ? p->trc.blocks.last_form : 0u; }
+uint32_t drx_plan_last_transcode_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_TRANSCODE) ? p->h_status->listed : 0u; }
 uint32_t drx_plan_last_pulses_redone(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_PULSES) ? p->h_status->redone : 0u; }
 uint32_t drx_plan_last_pulses_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_PULSES) ? p->h_status->listed : 0u; }
 uint32_t drx_plan_last_windows_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_WINDOWS) ? p->h_status->listed : 0u; }

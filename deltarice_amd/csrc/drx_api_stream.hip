@@ -131,7 +131,8 @@ static drx_status transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words
     if (const drx_status st = trc_scratch(p, &t)) return st;
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
-    DRX_HIP(ctx, launch_transcode(c, new_k, t, EncOut{d_out, out_cap, d_out_off, d_out_wave_words}));
+    DRX_HIP(ctx, form_scratch(p, kTranscodeForm, p->trc.blocks, trc_blocks_scratch_bytes));
+    DRX_HIP(ctx, launch_transcode(c, new_k, t, EncOut{d_out, out_cap, d_out_off, d_out_wave_words}, p->dec.d_blk, p->trc.blocks.d, &p->trc.blocks.last_form));
     return call_end(p, DRX_PATH_TRANSCODE);
 }
 
@@ -230,7 +231,8 @@ drx_status drx_estimate_words_encoded(drx_plan *p, const uint32_t *d_in, uint64_
     if (const drx_status st = trc_scratch(p, &t)) return st;
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_wave_words, false, &c)) return st;
-    DRX_HIP(ctx, launch_estimate_words_encoded(c, t.est));
+    DRX_HIP(ctx, form_scratch(p, kTranscodeForm, p->trc.blocks, trc_blocks_scratch_bytes));
+    DRX_HIP(ctx, launch_estimate_words_encoded(c, t.est, p->dec.d_blk, p->trc.blocks.d, &p->trc.blocks.last_form));
     (void)call_end(p, DRX_PATH_TRANSCODE);
     DRX_HIP(ctx, hipMemcpyAsync(words_out, t.est, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     return drx_plan_finish(p, nullptr);  // (waits; a stream that failed validation: DRX_ERR_CORRUPT, words_out undefined)

@@ -1,8 +1,9 @@
 // drx_blocks.h -- the block-parallel parse shared by the kernels that give a WORKGROUP a block of a waveform's stream
 // (not installed): the block geometry, the parse, and (drx_blocks_body.inc) the body of k_decode_blocks (drx_blocks.hip: the samples,
 // in output order, to HBM), of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics), of
-// k_pulses_blocks (drx_pulses_blocks.hip: the runs of samples over a threshold, per block, stitched behind the kernel) and of
-// k_windows_blocks (drx_windows_blocks.hip: the samples, in output order, to the rows of the windows that meet the block).
+// k_pulses_blocks (drx_pulses_blocks.hip: the runs of samples over a threshold, per block, stitched behind the kernel), of
+// k_windows_blocks (drx_windows_blocks.hip: the samples, in output order, to the rows of the windows that meet the block) and of
+// k_trc_blocks (drx_transcode_blocks.hip: the residuals sized, then re-coded, at another RiceParameter).
 // drx_blocks.hip's head comment describes the scheme.  A kernel that takes this route for another purpose adds its own
 // phase 2 behind the same phase 1, look-back and flags, as the STATS and PULSES forms do.
 // The host side of such a kernel is shared too: blocks_prepare() (drx_blocks.hip: the scratch reset and one BlkClassLaunch per
@@ -267,6 +268,39 @@ struct BlkPulseArgs {
 struct BlkWindowArgs {
     WinList wl;  // drx_window_rows.h: the starts, the counts and the rows of drx_decode_windows
 };
+
+// TRANSCODE (any filter: RESID, nothing is filtered): phase 2 sizes or re-codes the block's residuals at another RiceParameter
+// (drx_transcode_blocks.hip).  The scheme runs twice.  The SIZES launch is the full scheme; a block leaves in its slot of a table
+// its bit count at the new parameter and everything its second run needs to start without its neighbours: where its first code
+// starts, its first sample's index, its sample count.  The PACK launch (pack != 0) takes those from the slot -- lane 0's start is
+// exact, nothing is looked back for, no end is waited for, nothing is flagged -- and skips the waveforms that `keep` does not
+// name; `out`, `itab` and `xstate` are not used.
+constexpr uint32_t kTrcSlotWords = 6;  // u32 per block slot: bit offset in the waveform's payload (lo, hi; the sizes launch: bits, 0),
+                                       // bits, first code's start in bits behind the block's first, first sample's index, samples
+struct BlkTrcArgs {
+    static constexpr bool kAllK = false;
+    uint32_t k2;    // the new parameter
+    uint32_t pack;  // 0: the sizes launch, 1: the pack launch
+    uint32_t *slots;             // [block slot][kTrcSlotWords]
+    uint32_t *n_blocks;          // [waveform]: written by its last block (the sizes launch)
+    unsigned long long *acc16;   // kAllK: [waveform][16] bits at every parameter
+    const uint32_t *keep;        // pack: [waveform] != 0: the blocks write it
+    const uint32_t *new_rel;     // pack: the result's header positions relative to the chunk, its chunk offsets, its words
+    const uint64_t *out_chunk_off;
+    uint32_t *outw;
+};
+struct BlkTrcAllKArgs : BlkTrcArgs { static constexpr bool kAllK = true; };  // the sizes launch with sixteen counts per lane (the estimate)
+
+// a residual's canonical zig-zag value (what the lane kernels' canon() gives: wide foreign codes folded, small escapes ordinary)
+__device__ __forceinline__ uint32_t trc_canon16(uint32_t d16) {
+    const int32_t d = (int32_t)(int16_t)(uint16_t)d16;
+    return (((uint32_t)d << 1) ^ (uint32_t)(d >> 15)) & 0xffffu;
+}
+// length of z's code at parameter k2
+__device__ __forceinline__ uint32_t trc_code_bits(uint32_t z, uint32_t k2) {
+    const uint32_t q = z >> k2;
+    return q < 8u ? q + 1u + k2 : 25u;
+}
 
 // The fallback list (BlkFallbackList), in the kernel behind the blocks: waveform g goes to the lane kernel if every waveform does
 // (all_listed: the form's *_ALL_FALLBACK flag), if the blocks flagged it, or -- where the caller asks -- if no block has judged

@@ -76,10 +76,11 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                                                       DevStatus *st, int16_t *__restrict__ out, uint32_t n_list,
                                                       const uint32_t *__restrict__ itab, uint64_t *__restrict__ xstate,
                                                       const uint32_t *__restrict__ wave_list) {
-    constexpr bool STATS = false, PULSES = false, WINDOWS = false;
+    constexpr bool STATS = false, PULSES = false, WINDOWS = false, TRANSCODE = false;
     const BlkStatsArgs sa{0u, nullptr};
     const BlkPulseArgs pa{};
     const BlkWindowArgs wa{};
+    const BlkTrcArgs ta{};
 #include "drx_blocks_body.inc"
 }
 
@@ -116,8 +117,8 @@ static double blocks_us_of(double weighted_blocks, int nt, uint32_t k) {
 // most 24 576 waveforms", sent 25 chunks of 854 x 16 384 here: two blocks per waveform, the second a fifth full, 1.46 ms
 // where the lane kernel takes 0.98.)  Ragged batches: decided once from the host's chunk table, blocks_plan_ragged().
 // lane_us: what the lane-per-waveform kernel the caller would run instead takes per sample (the decoder's 0.06; drx_wave_stats' 0.052)
-bool blocks_batch(const Geom &G, double lane_us) {
-    if (G.n_taps != 0 && !G.fast_taps) return false;
+bool blocks_batch(const Geom &G, double lane_us, bool any_filter) {
+    if (!any_filter && G.n_taps != 0 && !G.fast_taps) return false;
     if (!G.uniform) return G.rag_blocks != 0;
     if (!(G.total_waves <= 98304u && G.u_wave_len >= 2048u)) return false;
     const int nt = blocks_nt(G);
@@ -292,7 +293,7 @@ hipError_t blocks_prepare(const Geom &G, uint64_t in_words, const uint32_t *d_wa
 
 // Which batches take a call's block form, and the call's form word (drx_internal.h)
 bool blocks_form_batch(const Geom &G, const void *d_blk, const BlkFormRule &r) {
-    if (G.n_taps != 0 || !d_blk || !blocks_batch(G, r.lane_us)) return false;
+    if ((G.n_taps != 0 && !r.any_filter) || !d_blk || !blocks_batch(G, r.lane_us, r.any_filter)) return false;
     return !(G.dbg & (DRX_DBG_NO_LONG_PATHS | DRX_DBG_LONG_NOT_BLOCKS | r.lanes_flag));
 }
 uint32_t blocks_form_word(const Geom &G, bool blocks, const BlkFormRule &r) {

@@ -1,10 +1,10 @@
 // drx_blocks_body.inc -- the body of a kernel that gives a workgroup a block of a waveform's stream, included INSIDE the kernel's
 // definition (k_decode_blocks, drx_blocks.hip; k_stats_blocks, drx_stats_blocks.hip; k_pulses_blocks, drx_pulses_blocks.hip;
-// k_windows_blocks, drx_windows_blocks.hip)
+// k_windows_blocks, drx_windows_blocks.hip; k_trc_blocks, drx_transcode_blocks.hip)
 // behind its arguments: text, not a function, because k_decode_blocks is sensitive to how its arguments reach it (an inlined
 // function with the same body was compiled to other code: other spills, another schedule).  The including kernel provides NT,
-// RESID, SW, FUSE, STATS, PULSES, WINDOWS, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs), `pa` (BlkPulseArgs) and
-// `wa` (BlkWindowArgs).
+// RESID, SW, FUSE, STATS, PULSES, WINDOWS, TRANSCODE, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs), `pa`
+// (BlkPulseArgs), `wa` (BlkWindowArgs) and `ta` (BlkTrcArgs).
     static_assert(!FUSE || RESID, "the fused inverse filter works on residuals");
     using BG = BlkGeom<NT, SW>;
     constexpr int kBlkSegW = SW;
@@ -28,6 +28,9 @@
     const int lane = lane_id(), wv = (int)(tid >> 6);
     uint32_t k = G.k;
     asm volatile("" : "+v"(k));  // in a VGPR for good: the parse selects between k and 16 per code, and re-materialised it per pair
+    // TRANSCODE: the pack launch -- a block's start comes from its slot of the table, no block waits for another (drx_blocks.h)
+    [[maybe_unused]] bool t_pack = false;
+    if constexpr (TRANSCODE) t_pack = ta.pack != 0u;
     // A ticket is a RUN of run_len consecutive blocks of one waveform, dealt run-major: run 0 of every waveform, then run 1
     // of every waveform, ...  Inside a run only its first block talks to other workgroups (where the predecessor's
     // stream ended, the look-back for samples and sum in front of it); the others start exactly where the block before
@@ -85,6 +88,7 @@
         const uint32_t n_blocks = (q.n + BG::kWords - 1u) / BG::kWords;
         q.blk_lo = run * run_len;
         q.blk_hi = (q.blk_lo + run_len < n_blocks) ? q.blk_lo + run_len : n_blocks;  // (blk_lo >= n_blocks: an empty run)
+        if constexpr (TRANSCODE) { if (t_pack && !ta.keep[q.g]) q.blk_hi = q.blk_lo; }  // (a listed waveform: the lane kernel packs it)
         return q;
     };
     // image of block b: words [b kWords - kBlkPre, (b + 1) kWords + kBlkTail) of the payload, from a 16-byte boundary
@@ -283,8 +287,10 @@
             const bool active = bj < bend;
             const uint32_t lim = (bj + kSegBits < bend) ? bj + kSegBits : bend;
             // lane 0 knows its start when the block is the waveform's first (bit 0) or follows one of this run
-            const bool exact0 = tid == 0 && (blk == 0 || !first_of_run);
-            const uint32_t start0 = B0 + (first_of_run ? 0u : carry_rel);
+            [[maybe_unused]] uint32_t t_rel0 = 0u;  // TRANSCODE, pack: a run's first block starts where the sizes launch found its first code
+            if constexpr (TRANSCODE) { if (t_pack && first_of_run) t_rel0 = ta.slots[(uint64_t)sidx * kTrcSlotWords + 3u]; }
+            const bool exact0 = tid == 0 && (blk == 0 || !first_of_run || (TRANSCODE && t_pack));
+            const uint32_t start0 = B0 + (first_of_run ? t_rel0 : carry_rel);
             uint32_t Qp = C - (exact0 ? start0 : (active ? bj - kBlkGuessBits : B0));
             uint32_t cnt = 0, sum = 0;
             blk_skip_pairs(W, k, active && !exact0, Qp, C - bj);
@@ -368,7 +374,7 @@
             // the end of this run = the start of the next one, published as soon as it is known
             if (tid == 0 && last_of_run && !defer)
                 __hip_atomic_store(ends + sidx, 0x80000000u | (e_last0 - bend), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (first_of_run && blk > 0) {
+            if (first_of_run && blk > 0 && !(TRANSCODE && t_pack)) {
                 if (tid == 0) {
                     uint32_t v = 0, spins = 0;
                     for (;;) {
@@ -427,6 +433,11 @@
                 if (blk == 0) {
                     ex_c = 0;
                     ex_s = 0;
+                } else if (TRANSCODE && t_pack) {
+                    if (first_of_run) {  // (the sizes launch left it in the block's slot; a re-code needs no running sum)
+                        if constexpr (TRANSCODE) ex_c = ta.slots[(uint64_t)sidx * kTrcSlotWords + 4u];
+                        ex_s = 0;
+                    }
                 } else if (first_of_run) {
                     // decoupled look-back over the blocks of the waveform in front of this one
                     ex_c = 0;
@@ -519,7 +530,9 @@
                     xs = V3{(uint32_t)v & 0xffffu, (uint32_t)(v >> 16) & 0xffffu, (uint32_t)(v >> 32) & 0xffffu};
                 }
             }
-            if constexpr (PULSES) {
+            if constexpr (TRANSCODE) {
+#include "drx_blocks_trc.inc"
+            } else if constexpr (PULSES) {
                 // ---- phase 2, pulses: every lane summarises the runs of over-threshold samples among its own samples
                 // (drx_pulse_runs.h), a scan over the lanes with pulse_combine() tells each what lies in front of it inside
                 // the block -- the run open there and how many of the block's pulses -- and a second pass over the same staged

@@ -91,7 +91,7 @@ struct Geom {
 
 struct DevStatus {
     uint32_t err;  // kErr* bits, OR-ed by kernels
-    uint32_t listed;  // drx_find_pulses / drx_decode_windows, block form: the waveforms handed to the lane kernel behind the blocks
+    uint32_t listed;  // drx_find_pulses / drx_decode_windows / drx_transcode, block form: the waveforms handed to the lane kernel(s) behind the blocks
     uint64_t total_words;  // encode: words of the encoded batch
     uint32_t redone;       // drx_find_pulses, block form: the waveforms whose blocks its second launch ran again
     uint32_t pad_;
@@ -230,8 +230,8 @@ inline GatherScratch gather_scratch_view(void *base, uint64_t n_sel) {
 hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves,
                          const uint32_t *d_chunk_samples, const EncOut &out, const GatherScratch &t, bool tiles, uint64_t mean_words,
                          bool resume);
-// The block forms of drx_wave_stats, drx_find_pulses and drx_decode_windows (drx_*_blocks.hip): few long waveforms under the delta
-// filter give a workgroup a block of a waveform's stream, as the block decoder does (d_blk = its scratch), with the call's lane
+// The block forms of drx_wave_stats, drx_find_pulses, drx_decode_windows and drx_transcode (drx_*_blocks.hip): few long waveforms under
+// the delta filter (any_filter: under every filter) give a workgroup a block of a waveform's stream, as the block decoder does (d_blk = its scratch), with the call's lane
 // kernel behind the blocks for the waveforms they list.  One rule says which batches: the decoder's own test, blocks against
 // lanes by their cost (blocks_batch(), drx_blocks.hip), with the rate of THIS call's lane kernel, on a plan that has d_blk, unless
 // a debug flag keeps the batch on lanes (DRX_DBG_NO_LONG_PATHS, DRX_DBG_LONG_NOT_BLOCKS, the call's own lanes_flag).  A ragged
@@ -240,6 +240,7 @@ hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_
 struct BlkFormRule {
     double lane_us;  // what the call's lane kernel takes per sample
     uint32_t lanes_flag, all_fallback_flag;  // DRX_DBG_*: never the block form; the block form lists every waveform
+    bool any_filter = false;  // the form works on residuals: every prediction filter the plan accepts, not the delta filter alone
 };
 // k_wave_stats takes 52 ns per sample and lane where k_decode_lanes takes 60, so a uniform batch at the
 // decoder's break-even -- 4 chunks of 2100 x 7000: one block per waveform, 393 us of blocks against 420 us of decoding lanes, but
@@ -253,12 +254,25 @@ constexpr BlkFormRule kPulsesForm{kPulsesLaneUs, DRX_DBG_PULSES_LANES, DRX_DBG_P
 // 81 920 (profiles/decode_windows_bench.txt): 0.050 - 0.057 us per sample, the NOPTREX shape's 0.051 taken
 constexpr double kWindowsLaneUs = 0.051;
 constexpr BlkFormRule kWindowsForm{kWindowsLaneUs, DRX_DBG_WINDOWS_LANES, DRX_DBG_WINDOWS_ALL_FALLBACK};
+// drx_transcode / drx_estimate_words_encoded: the re-code has no filter arithmetic, so its form admits every filter.  Its lane
+// kernels parse twice and emit once: 102.3 ms for lanes of 500 000 samples, 0.2045 us per sample (profiles/transcode_blocks_bench.txt,
+// row `noptrex`, lane form; 0.204 on `nedm`, 0.211 on `long25`).  blocks_batch() prices the DECODER's blocks, and this form runs
+// the blocks twice and re-codes every sample in the second run (a second parse and the emission): the same row's block form takes
+// 4.06 ms where the block decoder takes 1.26 - 1.31 ms for that batch, 3.2 times as long at m' = 16.  Four
+// times a decoder's block is charged (a smaller m' expands the result and the pack drains it in more passes: not measured) -- the
+// rule is given a quarter of the lane rate, and "blocks < lanes" is then the comparison of 4 x the decoder's blocks with this
+// call's lanes.
+constexpr double kTranscodeLaneUs = 0.2045;
+constexpr double kTranscodeBlockFactor = 4.0;
+constexpr BlkFormRule kTranscodeForm{kTranscodeLaneUs / kTranscodeBlockFactor, DRX_DBG_TRANSCODE_LANES, DRX_DBG_TRANSCODE_ALL_FALLBACK, true};
 bool blocks_form_batch(const Geom &G, const void *d_blk, const BlkFormRule &r);
-// the form word of a call, one set of values under three names: LANES, or BLOCKS | FALLBACK_ALL under the rule's all_fallback_flag
+// the form word of a call, one set of values under four names: LANES, or BLOCKS | FALLBACK_ALL under the rule's all_fallback_flag
 static_assert(DRX_STATS_FORM_LANES == DRX_PULSES_FORM_LANES && DRX_STATS_FORM_LANES == DRX_WINDOWS_FORM_LANES &&
                   DRX_STATS_FORM_BLOCKS == DRX_PULSES_FORM_BLOCKS && DRX_STATS_FORM_BLOCKS == DRX_WINDOWS_FORM_BLOCKS &&
-                  DRX_STATS_FORM_FALLBACK_ALL == DRX_PULSES_FORM_FALLBACK_ALL && DRX_STATS_FORM_FALLBACK_ALL == DRX_WINDOWS_FORM_FALLBACK_ALL,
-              "blocks_form_word() serves the three calls");
+                  DRX_STATS_FORM_FALLBACK_ALL == DRX_PULSES_FORM_FALLBACK_ALL && DRX_STATS_FORM_FALLBACK_ALL == DRX_WINDOWS_FORM_FALLBACK_ALL &&
+                  DRX_STATS_FORM_LANES == DRX_TRANSCODE_FORM_LANES && DRX_STATS_FORM_BLOCKS == DRX_TRANSCODE_FORM_BLOCKS &&
+                  DRX_STATS_FORM_FALLBACK_ALL == DRX_TRANSCODE_FORM_FALLBACK_ALL,
+              "blocks_form_word() serves the four calls");
 uint32_t blocks_form_word(const Geom &G, bool blocks, const BlkFormRule &r);
 // The waveforms a block form leaves to the lane kernel behind it, a list on the device, part of the form's scratch:
 // u32 n_listed (+ pad to 8 bytes) | u32 listed[W].  (blk_listed() and blk_list_append(), drx_blocks.h, fill it.)
@@ -332,10 +346,20 @@ inline TrcScratch trc_scratch_view(const Geom &G, void *base) {
 // Behind the whole batch's walk, a lane per waveform that parses and sizes at RiceParameter 2^k2, the scan above over the new
 // table, then a lane per waveform that parses and packs.  out.d_out == nullptr: as far as the offsets.
 // ev: {start, walk's end, offsets' end, end}
-hipError_t launch_transcode(const StreamCall &c, uint32_t k2, const TrcScratch &t, const EncOut &out);
+// form_out: DRX_TRANSCODE_FORM_* of include/deltarice_hip.h.  The block form (drx_transcode_blocks.hip): d_blk = the block
+// decoder's scratch, d_tb = trc_blocks_scratch_bytes() of accumulators, list and block-slot table
+hipError_t launch_transcode(const StreamCall &c, uint32_t k2, const TrcScratch &t, const EncOut &out, void *d_blk, void *d_tb, uint32_t *form_out);
 // drx_estimate_words_encoded: behind the same walk, the words at every k alone (d_est: uint64[16], cleared here).
 // ev: {start, walk's end, kernel's end, end}
-hipError_t launch_estimate_words_encoded(const StreamCall &c, unsigned long long *d_est);
+hipError_t launch_estimate_words_encoded(const StreamCall &c, unsigned long long *d_est, void *d_blk, void *d_tb, uint32_t *form_out);
+uint64_t trc_blocks_scratch_bytes(const Geom &G);
+// The block form's launches in front of the scan: the blocks' sizes launch and the kernel behind it.  d_est == nullptr: the
+// waveforms it keeps have n_i' in t.words / d_out_wave_words and their blocks' bit offsets in the slot table; otherwise they
+// have added their words at every k to d_est.  list_out: the waveforms left to k_recode_sizes
+hipError_t launch_trc_blocks_sizes(const StreamCall &c, void *d_blk, void *d_tb, uint32_t k2, const TrcScratch &t, uint32_t *d_out_wave_words,
+                                   unsigned long long *d_est, BlkFallbackList *list_out);
+// ... and behind it (and behind no error): the headers, the words blocks share cleared, and the blocks' pack launch
+hipError_t launch_trc_blocks_pack(const StreamCall &c, void *d_blk, void *d_tb, uint32_t k2, const TrcScratch &t, const EncOut &out);
 
 // wide: fused_wide() as the route decided it
 hipError_t launch_encode_fused(const EncodeCall &c, int wide, uint64_t *d_scan);
@@ -404,7 +428,7 @@ struct SideStream {
 hipError_t launch_decode(const StreamCall &c, int16_t *d_out, uint64_t *d_granules, int impl, void *d_blk, const SideStream *side,
                          uint32_t *path_out = nullptr);
 // block-parallel decoder for batches of few waveforms (drx_blocks.hip): a workgroup per block of a waveform's stream
-bool blocks_batch(const Geom &G, double lane_us = 0.06);
+bool blocks_batch(const Geom &G, double lane_us = 0.06, bool any_filter = false);  // any_filter: no test of the plan's filter
 // ragged plans: decides rag_blocks / rag_blk_nt / rag_blk_slots and the classes from the host's chunk table (call once, when
 // the plan is made); returns rag_blk_list's host copy (empty: the decoder does not take the batch)
 std::vector<uint32_t> blocks_plan_ragged(Geom &G, const ChunkDesc *host_chunks);

@@ -6,6 +6,7 @@
 // The header tables (wave_off / wave_words) are valid for the whole batch: the host runs the walk in front of these launches
 // (launch_transcode(): the walks of drx_walk.hip, or the side-band's tables), as launch_wave_stats() does.
 //
+//   (k_recode_sizes_list / k_recode_pack_list: the same bodies over a device list of waveforms, behind the block form)
 //   k_recode_sizes<false>  one LANE per waveform, the stream side the shared reader's (drx_lane_reader.inc) with its
 //                          end-of-payload check.  Adds the length of every z at the new parameter and stores
 //                          n_i' = ceil(bits / 32).
@@ -22,8 +23,11 @@
 // A residual is the int16 the decoders take from its code, in canonical form: an ordinary code whose value exceeds 65535
 // (k >= 13 in a foreign stream) folds as drx_decode folds it, an escape that holds a small value comes out as an ordinary code.
 //
-// Few long waveforms go through the same lane-per-waveform kernels: correct and slow, as drx_wave_stats is there (a wavefront or
-// workgroup per long waveform is not built).
+// Few long waveforms (the batches blocks_form_batch() admits under kTranscodeForm, whatever the plan's filter) take the block form
+// of drx_transcode_blocks.hip: a workgroup per block of a waveform's stream for the sizes and again for the pack, with these lane
+// kernels behind each for the waveforms the blocks list (LIST: lane j of the launch takes waveform list[j], j < *n_list, a list
+// and a length written on the device; the launch is sized for the whole batch).  The listed waveforms get their n_i' -- or their
+// sixteen sums -- and their verdict here, and k_recode_pack writes every word of their regions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,6 +36,7 @@
 #include "drx_internal.h"
 #include "drx_device.h"
 #include "drx_lane_stream.h"
+#include "drx_blocks.h"
 
 namespace drx {
 
@@ -92,30 +97,41 @@ __device__ __forceinline__ bool parse_lane(uint32_t *__restrict__ ring, const ui
     return !(len && LANE_MISSES_LAST_WORD());
 }
 
-// length of z's code at parameter k2
-__device__ __forceinline__ uint32_t code_bits(uint32_t z, uint32_t k2) {
-    const uint32_t q = z >> k2;
-    return q < 8u ? q + 1u + k2 : 25u;
+// which waveform a lane takes: lane_wave(), or (LIST) entry 64 * wavefront + lane of the list
+template <bool LIST>
+__device__ __forceinline__ bool recode_lane_wave(const Geom &G, uint64_t wf, int lane, const uint32_t *list, const uint32_t *n_list, LaneWave &w) {
+    if (!LIST) return lane_wave(G, wf, lane, w);
+    const uint64_t j = wf * 64u + (uint32_t)lane;
+    w.g = 0; w.chunk = 0; w.idx = 0; w.len = 0; w.n_samples = 0;
+    w.active = j < (uint64_t)*n_list;
+    if (w.active) {
+        w.g = list[j];
+        const WaveRef r = locate(G, w.g);
+        w.chunk = r.chunk; w.idx = r.idx; w.len = r.len; w.n_samples = r.n_samples;
+    }
+    return true;
 }
 
 }  // namespace
 
 // Sizes.  ALLK = false: new_words[g] (and out_wave_words[g], where given) = n_i' at k2.  ALLK = true: est[k] += the batch's
 // words at k, headers included.  A lane whose payload fails the end check raises kErrCorrupt (what it stored is then undefined).
-template <bool ALLK>
-__global__ __launch_bounds__(64) void k_recode_sizes(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                     const uint64_t *__restrict__ wave_off,
-                                                     const uint32_t *__restrict__ wave_words, uint64_t wf_base, uint32_t k2,
-                                                     DevStatus *st, uint32_t *__restrict__ new_words,
-                                                     uint32_t *__restrict__ out_wave_words,
-                                                     unsigned long long *__restrict__ est) {
+// LIST: lane 0 of the launch leaves the list's length in the status word for drx_plan_last_transcode_listed.
+// (The body of k_recode_sizes and k_recode_sizes_list; the kernels below are its two instantiations per ALLK.)
+template <bool ALLK, bool LIST>
+__device__ __forceinline__ void recode_sizes(const Geom &G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                             const uint64_t *__restrict__ wave_off, const uint32_t *__restrict__ wave_words,
+                                             uint64_t wf_base, uint32_t k2, DevStatus *st, uint32_t *__restrict__ new_words,
+                                             uint32_t *__restrict__ out_wave_words, unsigned long long *__restrict__ est,
+                                             const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list) {
     constexpr int NK = ALLK ? 16 : 1;
     __shared__ uint32_t ring_all[kInRingWords];
     const int lane = lane_id();
+    if (LIST && blockIdx.x == 0 && threadIdx.x == 0) st->listed = *n_list;
     // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
     if (st->err) return;
     LaneWave w;
-    if (!lane_wave(G, wf_base + blockIdx.x, lane, w)) return;
+    if (!recode_lane_wave<LIST>(G, wf_base + blockIdx.x, lane, list, n_list, w)) return;
     uint64_t S = 1;
     uint32_t n = 0;
     if (w.active) {
@@ -129,7 +145,7 @@ __global__ __launch_bounds__(64) void k_recode_sizes(Geom G, const uint32_t *__r
     const bool ok = parse_lane(ring_all + 64, in, in_words, S, n, w.len, G.k, lane,
         [&](uint32_t z) __attribute__((always_inline)) {
 #pragma unroll
-            for (int j = 0; j < NK; ++j) gb[j] += code_bits(z, ALLK ? (uint32_t)j : k2);
+            for (int j = 0; j < NK; ++j) gb[j] += trc_code_bits(z, ALLK ? (uint32_t)j : k2);
         },
         [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -151,20 +167,41 @@ __global__ __launch_bounds__(64) void k_recode_sizes(Geom G, const uint32_t *__r
     }
 }
 
+template <bool ALLK>
+__global__ __launch_bounds__(64) void k_recode_sizes(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                     const uint64_t *__restrict__ wave_off,
+                                                     const uint32_t *__restrict__ wave_words, uint64_t wf_base, uint32_t k2,
+                                                     DevStatus *st, uint32_t *__restrict__ new_words,
+                                                     uint32_t *__restrict__ out_wave_words,
+                                                     unsigned long long *__restrict__ est) {
+    recode_sizes<ALLK, false>(G, in, in_words, wave_off, wave_words, wf_base, k2, st, new_words, out_wave_words, est, nullptr, nullptr);
+}
+template <bool ALLK>
+__global__ __launch_bounds__(64) void k_recode_sizes_list(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                          const uint64_t *__restrict__ wave_off,
+                                                          const uint32_t *__restrict__ wave_words, uint32_t k2, DevStatus *st,
+                                                          uint32_t *__restrict__ new_words, uint32_t *__restrict__ out_wave_words,
+                                                          unsigned long long *__restrict__ est, const uint32_t *__restrict__ list,
+                                                          const uint32_t *__restrict__ n_list) {
+    recode_sizes<ALLK, true>(G, in, in_words, wave_off, wave_words, 0u, k2, st, new_words, out_wave_words, est, list, n_list);
+}
+
 // Pack.  new_words / new_rel / out_chunk_off: the sizes pass's table and what k_chunk_scan / k_chunk_offsets made of it.
 // Nothing is written where the status word holds an error (a walker's or the sizes pass's kErrCorrupt, kErrCapacity).
-__global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                    const uint64_t *__restrict__ wave_off,
-                                                    const uint32_t *__restrict__ wave_words, uint64_t wf_base, uint32_t k2,
-                                                    const DevStatus *st, const uint32_t *__restrict__ new_words,
-                                                    const uint32_t *__restrict__ new_rel,
-                                                    const uint64_t *__restrict__ out_chunk_off, uint32_t *__restrict__ out) {
+// (The body of k_recode_pack and k_recode_pack_list, below.)
+template <bool LIST>
+__device__ __forceinline__ void recode_pack(const Geom &G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                            const uint64_t *__restrict__ wave_off, const uint32_t *__restrict__ wave_words,
+                                            uint64_t wf_base, uint32_t k2, const DevStatus *st, const uint32_t *__restrict__ new_words,
+                                            const uint32_t *__restrict__ new_rel, const uint64_t *__restrict__ out_chunk_off,
+                                            uint32_t *__restrict__ out, const uint32_t *__restrict__ list,
+                                            const uint32_t *__restrict__ n_list) {
     __shared__ uint32_t ring_all[kInRingWords];
     __shared__ __attribute__((aligned(16))) uint32_t oring_all[kOutRingWords];
     const int lane = lane_id();
     if (st->err) return;
     LaneWave w;
-    if (!lane_wave(G, wf_base + blockIdx.x, lane, w)) return;
+    if (!recode_lane_wave<LIST>(G, wf_base + blockIdx.x, lane, list, n_list, w)) return;
     uint64_t S = 1;
     uint32_t n = 0, n2 = 0;
     uint64_t pos = 0;  // of the lane's header word in out
@@ -244,38 +281,79 @@ __global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__re
     for (uint32_t x = fl; x < ow; ++x) outB[x] = myout[(x & (uint32_t)(kOW - 1)) * 64u];
 }
 
-// The estimate: the walk and k_recode_sizes<true> alone.  ev: {start, walk's end, kernel's end, end}
-hipError_t launch_estimate_words_encoded(const StreamCall &c, unsigned long long *d_est) {
+__global__ __launch_bounds__(64) void k_recode_pack(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                    const uint64_t *__restrict__ wave_off,
+                                                    const uint32_t *__restrict__ wave_words, uint64_t wf_base, uint32_t k2,
+                                                    const DevStatus *st, const uint32_t *__restrict__ new_words,
+                                                    const uint32_t *__restrict__ new_rel,
+                                                    const uint64_t *__restrict__ out_chunk_off, uint32_t *__restrict__ out) {
+    recode_pack<false>(G, in, in_words, wave_off, wave_words, wf_base, k2, st, new_words, new_rel, out_chunk_off, out, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64) void k_recode_pack_list(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                         const uint64_t *__restrict__ wave_off,
+                                                         const uint32_t *__restrict__ wave_words, uint32_t k2, const DevStatus *st,
+                                                         const uint32_t *__restrict__ new_words, const uint32_t *__restrict__ new_rel,
+                                                         const uint64_t *__restrict__ out_chunk_off, uint32_t *__restrict__ out,
+                                                         const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list) {
+    recode_pack<true>(G, in, in_words, wave_off, wave_words, 0u, k2, st, new_words, new_rel, out_chunk_off, out, list, n_list);
+}
+
+// The estimate: the walk and k_recode_sizes<true> alone, or (the block form) the blocks' sizes launch with sixteen counts and
+// k_recode_sizes<true> over the waveforms it lists.  ev: {start, walk's end, kernel's end, end}
+hipError_t launch_estimate_words_encoded(const StreamCall &c, unsigned long long *d_est, void *d_blk, void *d_tb, uint32_t *form_out) {
     const Geom &G = *c.G;
+    const bool blocks = d_tb != nullptr && blocks_form_batch(G, d_blk, kTranscodeForm);
+    if (form_out) *form_out = blocks_form_word(G, blocks, kTranscodeForm);
     if (G.total_waves == 0) return hipSuccess;
     hipError_t e = batch_walk_prologue(c);
     if (e == hipSuccess) e = hipMemsetAsync(d_est, 0, 16 * sizeof(unsigned long long), c.s);
     if (e != hipSuccess) return e;
-    for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
-        k_recode_sizes<true><<<nb, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, 0u, c.d_status, nullptr, nullptr, d_est);
-    });
+    if (blocks) {
+        BlkFallbackList fl;
+        if ((e = launch_trc_blocks_sizes(c, d_blk, d_tb, 0u, TrcScratch{}, nullptr, d_est, &fl)) != hipSuccess) return e;
+        k_recode_sizes_list<true><<<blocks_for(G.total_waves, 64), 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, 0u, c.d_status,
+                                                                                 nullptr, nullptr, d_est, fl.listed, fl.n_listed);
+    } else {
+        for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
+            k_recode_sizes<true><<<nb, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, 0u, c.d_status, nullptr, nullptr, d_est);
+        });
+    }
     mark(c.ev, 2, c.s);
     mark(c.ev, 3, c.s);
     return hipGetLastError();
 }
 
 // ev: {start, walk's end, offsets' end, end}.  out.d_out == nullptr: as far as the offsets (the sizing call).
-hipError_t launch_transcode(const StreamCall &c, uint32_t k2, const TrcScratch &t, const EncOut &out) {
+hipError_t launch_transcode(const StreamCall &c, uint32_t k2, const TrcScratch &t, const EncOut &out, void *d_blk, void *d_tb, uint32_t *form_out) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;
+    const bool blocks = d_tb != nullptr && blocks_form_batch(G, d_blk, kTranscodeForm);
+    if (form_out) *form_out = blocks_form_word(G, blocks, kTranscodeForm);
     if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip): launch_batch_walk()
     hipError_t e = batch_walk_prologue(c);
     if (e != hipSuccess) return e;
-    // ---- sizes, scan, offsets
-    for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
-        k_recode_sizes<false><<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, k2, c.d_status, t.words, out.d_wave_words, nullptr);
-    });
+    // ---- sizes, scan, offsets (the block form: the blocks, then the lane kernel over the waveforms they list; the launch is sized
+    // from here, at most a lane per waveform of the batch, and the list's length is read on the device)
+    BlkFallbackList fl{};
+    if (blocks) {
+        if ((e = launch_trc_blocks_sizes(c, d_blk, d_tb, k2, t, out.d_wave_words, nullptr, &fl)) != hipSuccess) return e;
+        k_recode_sizes_list<false><<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, k2, c.d_status,
+                                                                                t.words, out.d_wave_words, nullptr, fl.listed, fl.n_listed);
+    } else {
+        for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
+            k_recode_sizes<false><<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, k2, c.d_status, t.words, out.d_wave_words, nullptr);
+        });
+    }
     e = launch_chunk_offsets(G, t.words, t.rel, t.chunk_words, out.d_chunk_word_off, out.d_out ? out.out_cap : ~0ull, c.d_status, s);
     if (e != hipSuccess) return e;
     mark(c.ev, 2, s);
     // ---- pack
-    if (out.d_out) {
+    if (out.d_out && blocks) {
+        if ((e = launch_trc_blocks_pack(c, d_blk, d_tb, k2, t, out)) != hipSuccess) return e;
+        k_recode_pack_list<<<blocks_for(G.total_waves, 64), 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, k2, c.d_status, t.words,
+                                                                        t.rel, out.d_chunk_word_off, out.d_out, fl.listed, fl.n_listed);
+    } else if (out.d_out) {
         for_wavefront_slices(G, true, [&](uint64_t base, unsigned nb) {
             k_recode_pack<<<nb, 64, 0, s>>>(G, c.d_in, c.in_words, c.d_wave_off, c.d_wave_words, base, k2, c.d_status, t.words, t.rel, out.d_chunk_word_off, out.d_out);
         });

@@ -474,8 +474,18 @@ drx_status drx_find_pulses_with_wave_words(drx_plan *plan, const uint32_t *d_in,
  * for both tables; nothing is written outside [d_out, d_out + total), the n_chunks + 1 offsets and the total_waves table entries;
  * no load leaves [0, in_words); the result does not depend on what the outputs held before.  d_out must not overlap d_in (not
  * checked).
- *   A lane per waveform for every geometry: few long waveforms go through the same kernels, correct and slow as in
- * drx_wave_stats (a wavefront or workgroup per long waveform is not built). */
+ *   Few long waveforms -- the batches drx_wave_stats gives to its block form, here under EVERY prediction filter the plan
+ * accepts, since a re-code has no filter arithmetic -- take a workgroup per block of a waveform's stream, twice: a sizes launch
+ * (the block decoder's parse on residuals; a block adds the code lengths of its samples at the new parameter and leaves its bit
+ * count, where its first code starts, its first sample's index and its sample count in a table of the plan), a kernel that
+ * turns every waveform's bit counts into n_i' and bit offsets or lists the waveform for the lane kernels (flagged and suspect
+ * waveforms, waveforms with samples and no payload word), the lane kernels over that list for their n_i' and their verdict, the
+ * scan, then a pack launch in which every block re-codes its samples to its own bit position from the table alone -- no block
+ * waits for another there, so the result does not depend on which waveforms a launch flagged -- and the lane pack kernel over the
+ * list.  Words that two blocks share are OR-ed into words a kernel of this call has cleared, inside [d_out, d_out + total) and
+ * under no error only.  All forms give the same words, tables and verdicts bit for bit.  drx_plan_last_decode_path reports
+ * DRX_PATH_TRANSCODE alone whichever form ran (drx_plan_last_transcode_form says which), drx_plan_last_timings keeps its four
+ * entries.  DRX_DBG_TRANSCODE_LANES: never the block form; DRX_DBG_TRANSCODE_ALL_FALLBACK: the block form lists every waveform. */
 drx_status drx_transcode(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                          uint32_t new_rice_k, uint32_t *d_out, uint64_t out_cap_words, uint64_t *d_out_chunk_word_off,
                          uint32_t *d_out_wave_words);
@@ -484,11 +494,20 @@ drx_status drx_transcode(drx_plan *plan, const uint32_t *d_in, uint64_t in_words
 drx_status drx_transcode_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                          const uint32_t *d_wave_words, uint32_t new_rice_k, uint32_t *d_out, uint64_t out_cap_words,
                                          uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
+/* Which form the plan's last drx_transcode (the sizing call included) or drx_estimate_words_encoded took; 0 before the first */
+#define DRX_TRANSCODE_FORM_LANES 1u        /* a lane per waveform */
+#define DRX_TRANSCODE_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream, the lane kernels behind it for listed waveforms */
+#define DRX_TRANSCODE_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_TRANSCODE_ALL_FALLBACK was in force */
+uint32_t drx_plan_last_transcode_form(const drx_plan *plan);
+/* ... and, valid behind drx_plan_finish, how many waveforms its block form handed to the lane kernels (flagged or suspect
+ * waveforms, waveforms with samples and no payload word, all of them under DRX_DBG_TRANSCODE_ALL_FALLBACK); 0 for the lane form */
+uint32_t drx_plan_last_transcode_listed(const drx_plan *plan);
 /* drx_estimate_words' sixteen numbers from the STREAM: words_out[k] (host array of 16) is the total words drx_transcode would
  * produce at new_rice_k = k; the plan's filter enters only through the stream.  For a canonical stream the entry at the plan's
  * own k is the stream's total words.  d_wave_words: the source's side-band, or NULL to walk.  SYNCHRONOUS: it clears the status
  * word as a decode does, waits, and returns the verdict itself (a stream that fails drx_transcode's validation:
- * DRX_ERR_CORRUPT, words_out undefined). */
+ * DRX_ERR_CORRUPT, words_out undefined).  Few long waveforms take drx_transcode's block form: the sizes launch with sixteen
+ * counts per block, the lane kernel behind it for the waveforms the blocks list. */
 drx_status drx_estimate_words_encoded(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                       const uint32_t *d_wave_words, uint64_t words_out[16]);
 
@@ -523,7 +542,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_SELECT 128u    /* drx_decode_select: a wavefront (general filters: a lane) per selected waveform; reported alone */
 #define DRX_PATH_GATHER 256u    /* drx_gather_encoded: word ranges copied, nothing decoded; reported alone */
 #define DRX_PATH_STATS 512u     /* drx_wave_stats: a lane per waveform that parses and reduces; reported alone */
-#define DRX_PATH_TRANSCODE 1024u /* drx_transcode / drx_estimate_words_encoded: a lane per waveform that parses and re-codes; reported alone */
+#define DRX_PATH_TRANSCODE 1024u /* drx_transcode / drx_estimate_words_encoded: the stream parsed and re-coded, lanes or blocks; reported alone */
 #define DRX_PATH_WINDOW 2048u   /* drx_decode_window: a lane per waveform that parses to its window's end; reported alone */
 #define DRX_PATH_PULSES 4096u   /* drx_find_pulses: a lane per waveform that parses and discriminates; reported alone */
 #define DRX_PATH_WINDOWS 8192u  /* drx_decode_windows: several windows per waveform, lanes or blocks; reported alone */
@@ -586,9 +605,11 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
  *                  a forcing flag takes its encoder wherever that encoder can run the batch */
 #define DRX_DBG_NO_LONG_PATHS 256u              /* never the long-waveform paths (segment encoders, block and long decoders) */
 #define DRX_DBG_LONG_NOT_BLOCKS 512u            /* long waveforms: one workgroup per waveform, never the block decoder */
+#define DRX_DBG_TRANSCODE_LANES 1024u            /* drx_transcode / drx_estimate_words_encoded: never the block form (a lane per waveform whatever the batch) */
 #define DRX_DBG_NO_PARALLEL_WALKS 2048u         /* never the parallel header walks */
 #define DRX_DBG_NO_PIECES 4096u                 /* never the pieces encoder nor the segment form by default */
 #define DRX_DBG_FORCE_SEGMENTS 8192u            /* the two-pass segment encoder */
+#define DRX_DBG_TRANSCODE_ALL_FALLBACK 16384u   /* drx_transcode / drx_estimate_words_encoded, block form: every waveform is listed for the lane kernels behind the blocks */
 #define DRX_DBG_FORCE_PIECES 32768u             /* the pieces encoder, also where a wavefront per waveform is the default */
 #define DRX_DBG_NO_WIDE_FUSED 65536u            /* never the single-pass encoder's larger-buffer geometries (m above 8) */
 #define DRX_DBG_RAGGED_ONE_LANES_LAUNCH 131072u /* ragged batches: one decode launch behind both header walks */

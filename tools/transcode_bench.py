@@ -8,6 +8,12 @@ median [min .. max] of --calls calls behind --warmup.
   headline-loud   the same with sigma = 400
   short           300 chunks of 8192 x 512
   config5         BASELINE's mixed-length config 5 (ragged: 512 / 2048 / 7000 / 16384)
+  nedm, noptrex, long25, noptrex_fir4
+                  few long waveforms (the geometries of tools/workload.py; _fir4: under taps [1,-1,1,-1]): the block form of
+                  drx_transcode_blocks.hip.  Columns: transcode as the library routes it (its form named), the lane form under
+                  DRX_DBG_TRANSCODE_LANES in the same process, alternating (long25: 3 calls behind 1, a lane call takes seconds;
+                  elsewhere --calls behind --warmup), decode + encode, the sizing call, the estimate.  These rows also run on a
+                  library that has no block form (the form query is looked up): there both transcode columns are the lane form.
 
 Columns: decode + encode; transcode into a given buffer, split as last_timings() splits it (walk, sizes + scan + offsets,
 pack); the sizing call alone; `estimate_words_encoded` against decode + `estimate_words`; peak device bytes of each route
@@ -30,7 +36,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import deltarice_amd as dr  # noqa: E402
 from wave_stats_bench import samples  # noqa: E402
-from workload import geometry  # noqa: E402
+from workload import FIR4, geometry  # noqa: E402
 
 
 def med(t):
@@ -39,16 +45,19 @@ def med(t):
 
 
 class Case:
-    def __init__(self, ctx, Ns, Ls, sigma, m=8):
+    def __init__(self, ctx, Ns, Ls, sigma, m=8, taps=None):
         self.ctx, self.m = ctx, m
         self.uniform = len(set(Ns)) == 1 and len(set(Ls)) == 1
-        self.mk = lambda mm: ctx.plan_uniform(len(Ns), Ns[0], (mm, Ls[0])) if self.uniform else ctx.plan(Ns, Ls, mm)
+        ftaps = (len(taps),) + tuple(int(t) & 0xFFFFFFFF for t in taps) if taps else ()
+        opts = lambda mm: (mm, Ls[0] if Ls[0] > 0 else 0xFFFFFFFF) + ftaps  # noqa: E731
+        self.mk = lambda mm: ctx.plan_uniform(len(Ns), Ns[0], opts(mm)) if self.uniform else ctx.plan(Ns, Ls, mm, taps)
+        self.taps = taps
         self.plan = self.mk(m)
         x = samples(ctx, sum(Ns), sigma)
         torch.cuda.synchronize()
         self.enc = self.plan.encode(x)
         self.est = self.plan.estimate_words_encoded(self.enc)
-        assert self.est.tolist() == self.plan.estimate_words(x).tolist(), "the two estimates differ"
+        assert taps is not None or self.est.tolist() == self.plan.estimate_words(x).tolist(), "the two estimates differ"
         del x
         self.m2 = 1 << int(np.argmin(self.est))
         self.total2 = int(self.est.min())
@@ -131,6 +140,43 @@ class Case:
               f"peak {p_tr / 1e9:.2f} GB against {p_pair / 1e9:.2f} GB  {verdict}{'' if match else '  MISMATCH'}", flush=True)
 
 
+    def line_long(self, label, calls, warmup):
+        """The rows of few long waveforms: the library's route and the lane form, alternating in one process."""
+        dev, plan, plan2 = self.ctx.device, self.plan, self.plan2
+        lanes_flag = getattr(dr._lib, "DBG_TRANSCODE_LANES", 1024)
+        form_of = getattr(plan, "last_transcode_form", lambda: 0)
+        out = torch.empty(self.total2, dtype=torch.int32, device=dev)
+        out_l = torch.empty(self.total2, dtype=torch.int32, device=dev)
+        out_y = torch.empty(self.total2, dtype=torch.int32, device=dev)
+        off = torch.empty(plan.n_chunks + 1, dtype=torch.int64, device=dev)
+        tab = torch.empty(plan.total_waves, dtype=torch.int32, device=dev)
+        y = torch.empty(plan.total_samples, dtype=torch.int16, device=dev)
+        tb, tl, tp, tsz, te = [], [], [], [], []
+        form = 0
+        for i in range(warmup + calls):
+            tb.append(self.timed(lambda: self.transcode(out, off, tab), (plan,))[0])
+            form = form_of()
+            self.ctx.set_option("debug_flags", lanes_flag)
+            tl.append(self.timed(lambda: self.transcode(out_l, off, tab), (plan,))[0])
+            self.ctx.set_option("debug_flags", 0)
+            tp.append(self.timed(lambda: self.pair(y, out_y), (plan, plan2))[0])
+            tsz.append(self.timed(lambda: self.transcode(None, off, tab), (plan,))[0])
+            te.append(self.timed(lambda: plan.estimate_words_encoded(self.enc), ())[0])
+            if i == 0:
+                match = torch.equal(out, out_l) and (self.taps is not None or torch.equal(out, out_y))
+        tb, tl, tp, tsz, te = (np.array(t[warmup:]) for t in (tb, tl, tp, tsz, te))
+        name = {0: "no form query", 1: "LANES", 2: "BLOCKS"}.get(form, str(form))
+        print(f"{label:14s} {plan.total_waves:8d} waveforms {plan.total_samples / 1e9:6.2f} GS  m {self.m} -> {self.m2}  "
+              f"stream {self.enc.total_words * 4 / 1e9:5.2f} -> {self.total2 * 4 / 1e9:5.2f} GB\n    "
+              f"transcode ({name}) {med(tb)}  lane form {med(tl)}  x{np.median(tl) / np.median(tb):.1f} "
+              f"(lane form {np.median(tl) * 1e3 / max(plan.longest_wave(), 1):.4f} us per sample of the longest waveform)\n    "
+              f"decode+encode {med(tp)}  sizing call {med(tsz)}  estimate_words_encoded {med(te)}"
+              f"{'' if match else '  MISMATCH'}", flush=True)
+
+
+LONG_ROWS = {"nedm": None, "noptrex": None, "long25": None, "noptrex_fir4": FIR4}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=500)
@@ -148,6 +194,16 @@ def main():
         ("short", lambda: ([8192 * 512] * 300, [512] * 300), 10.0),
         ("config5", lambda: geometry("config5"), 10.0),
     ]
+    for name, taps in LONG_ROWS.items():
+        if name not in only:  # (these rows run where they are asked for)
+            continue
+        Ns, Ls = geometry(name)
+        c = Case(ctx, list(Ns), list(Ls), 10.0, taps=taps)
+        c.line_long(name, *((3, 1) if name == "long25" else (a.calls, a.warmup)))
+        c.plan.close()
+        c.plan2.close()
+        del c
+        torch.cuda.empty_cache()
     for name, geom, sigma in cases:
         if only and name not in only:
             continue
