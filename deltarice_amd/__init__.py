@@ -12,6 +12,8 @@ from ._lib import (PATH_PULSES, PATH_STATS, PATH_TRANSCODE, PATH_WINDOW, PATH_WI
 from ._lib import (STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD_SUMSQ,  # noqa: F401
                    STAT_MAX, STAT_MIN, STAT_SUM, STAT_SUMSQ)
 
+from ._lib import DBG_REFILTER_SERIAL, TRANSCODE_FORM_REFILTER, TRANSCODE_FORM_REFILTER_SERIAL  # noqa: F401
+
 H5FILTER = 32025
 
 
@@ -20,4 +22,7 @@ def __getattr__(name):
     if name in ("Context", "Plan", "EncodedBatch", "Gathered", "Transcoded", "parse_opts"):
         from . import codec
         return getattr(codec, name)
+    if name == "optimise_encoded":  # (optimise() itself stays `from deltarice_amd.optimise import optimise`: the module has its name)
+        from .optimise import optimise_encoded
+        return optimise_encoded
     raise AttributeError(name)

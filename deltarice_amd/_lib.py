@@ -43,6 +43,7 @@ DBG_NO_WIDE_FUSED = 65536
 DBG_RAGGED_ONE_LANES_LAUNCH = 131072
 DBG_STREAM_THREE_WGS = 262144
 DBG_FORCE_STREAM = 524288
+DBG_REFILTER_SERIAL = 1048576
 DBG_IIR_SEPARATE = 2097152
 DBG_FORCE_STREAM_SEGS = 4194304
 DBG_WALK_BY_SCAN = 8388608
@@ -63,6 +64,8 @@ PULSES_STAGE_CAP = 8  # DRX_PULSES_STAGE_CAP
 WINDOWS_FORM_LANES, WINDOWS_FORM_BLOCKS, WINDOWS_FORM_FALLBACK_ALL = 1, 2, 4
 # DRX_TRANSCODE_FORM_*: drx_plan_last_transcode_form (tests/test_transcode_blocks_abi.py holds them equal)
 TRANSCODE_FORM_LANES, TRANSCODE_FORM_BLOCKS, TRANSCODE_FORM_FALLBACK_ALL = 1, 2, 4
+# ... or-ed in by the re-filter calls (tests/test_refilter_abi.py holds them equal)
+TRANSCODE_FORM_REFILTER, TRANSCODE_FORM_REFILTER_SERIAL = 8, 16
 
 
 class DrxOpts(C.Structure):
@@ -131,6 +134,9 @@ SIGNATURES = {
     "drx_transcode": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp, _vp]),
     "drx_transcode_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
     "drx_estimate_words_encoded": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "drx_transcode_filter": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _u32, C.POINTER(C.c_int32), _vp, _u64, _vp, _vp]),
+    "drx_transcode_filter_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, C.POINTER(C.c_int32), _vp, _u64, _vp, _vp]),
+    "drx_estimate_words_encoded_filter": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, C.POINTER(C.c_int32), C.POINTER(_u64)]),
     "drx_estimate_words": (C.c_int, [_vp, _vp, C.POINTER(_u64)]),
     "drx_plan_last_timings": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "drx_plan_finish": (C.c_int, [_vp, C.POINTER(_u64)]),

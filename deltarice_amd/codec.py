@@ -158,16 +158,17 @@ class Gathered:
 
 @dataclass
 class Transcoded:
-    """What Plan.transcode returns: the source batch re-coded at another RiceParameter, and all that is needed to use it."""
+    """What Plan.transcode and Plan.refilter return: the source batch re-coded at another RiceParameter (refilter: and under
+    another prediction filter), and all that is needed to use it."""
     enc: EncodedBatch             # the chunks, back to back, with their offset table
     wave_words: torch.Tensor      # int32 [total_waves] on the device: n_i of every waveform, the result's side-band
     rice_m: int                   # the RiceParameter of the result ...
-    taps: Optional[tuple]         # ... and the source plan's prediction filter (None: delta)
+    taps: Optional[tuple]         # ... and its prediction filter: the source plan's, or refilter's target (None: delta)
     chunk_samples: np.ndarray     # int64 [n_chunks]: the source plan's geometry (what Context.plan() takes)
     wave_lens: np.ndarray
 
     def plan(self, ctx: "Context") -> "Plan":
-        """The plan of the result: the source's geometry and filter, the new RiceParameter."""
+        """The plan of the result: the source's geometry, the result's filter and RiceParameter."""
         N, L = np.asarray(self.chunk_samples, dtype=np.int64), np.asarray(self.wave_lens, dtype=np.int64)
         if N.size == 0:
             raise DeltaRiceError(1, "an empty batch has no plan")
@@ -713,6 +714,79 @@ class Plan:
         return Transcoded(EncodedBatch(out_words, off, self.finish()), tab, int(rice_m), self._taps,
                           self._chunk_samples.copy(), self._wave_lens.copy())
 
+    @staticmethod
+    def _target_taps(taps: Optional[Sequence[int]]):
+        """(ctypes int32 array, its length, the taps as Transcoded carries them: None for (1, -1)) of a target filter"""
+        t = (1, -1) if taps is None else tuple(int(v) for v in taps)
+        if not 1 <= len(t) <= _lib.DRX_MAX_TAPS:
+            raise DeltaRiceError(1, f"taps: {len(t)} values (1 .. {_lib.DRX_MAX_TAPS})")
+        if any(not -(1 << 31) <= v < 1 << 31 for v in t):
+            raise DeltaRiceError(1, "taps: a value is not an int32")
+        return (C.c_int32 * len(t))(*t), len(t), (None if t == (1, -1) else t)
+
+    def estimate_words_refiltered(self, enc: EncodedBatch, taps: Optional[Sequence[int]],
+                                  wave_words: Optional[torch.Tensor] = None) -> np.ndarray:
+        """estimate_words_encoded under ANOTHER prediction filter: entry k is the total words refilter() gives with ``taps`` at
+        RiceParameter 2^k, k = 0..15 -- what estimate_words(x) of a plan with that filter gives for the decoded samples x, with
+        nothing decoded to memory.  Waits; raises DRX_ERR_CORRUPT for a stream that fails validation."""
+        self._open("estimate_words_refiltered")
+        arr, n, _ = self._target_taps(taps)
+        self._check_encoded(enc.words, enc.chunk_word_off, wave_words)
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        out = (C.c_uint64 * 16)()
+        self.ctx._check(self.ctx.lib.drx_estimate_words_encoded_filter(self._h, enc.words.data_ptr(), int(enc.total_words),
+                                                                       enc.chunk_word_off.data_ptr(),
+                                                                       wave_words.data_ptr() if wave_words is not None else None,
+                                                                       n, arr, out))
+        return np.array(list(out), dtype=np.uint64)
+
+    def refilter_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, taps: Optional[Sequence[int]], rice_m: int,
+                       out_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
+                       wave_words: Optional[torch.Tensor] = None, out_chunk_word_off: Optional[torch.Tensor] = None,
+                       out_wave_words: Optional[torch.Tensor] = None):
+        """Launches drx_transcode_filter on the context's stream: transcode_async with a change of prediction filter -- the
+        batch re-coded under ``taps`` (None or (1, -1): the delta filter) at RiceParameter ``rice_m``, not decoded to memory.
+        The plan's own filter and RiceParameter describe the source and stay.  Arguments, the sizing call, the result and
+        finish() as transcode_async."""
+        self._open("refilter")
+        k = parse_opts((int(rice_m),)).rice_k
+        arr, n, _ = self._target_taps(taps)
+        self._check_encoded(words, chunk_word_off, wave_words)
+        if out_words is not None:
+            self._dev_check(out_words, torch.int32, 0, "out_words")
+        if out_chunk_word_off is None:
+            out_chunk_word_off = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=self.ctx.device)
+        self._dev_check(out_chunk_word_off, torch.int64, self.n_chunks + 1, "out_chunk_word_off")
+        if out_wave_words is None:
+            out_wave_words = torch.empty(self.total_waves, dtype=torch.int32, device=self.ctx.device)
+        self._dev_check(out_wave_words, torch.int32, self.total_waves, "out_wave_words")
+        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
+        self._call_encoded("transcode_filter", words, chunk_word_off, wave_words, in_words, k, n, arr, op, cap,
+                           out_chunk_word_off.data_ptr(), out_wave_words.data_ptr())
+        return out_words, out_chunk_word_off, out_wave_words
+
+    def refilter(self, enc: EncodedBatch, taps: Optional[Sequence[int]], rice_m: Optional[int] = None,
+                 wave_words: Optional[torch.Tensor] = None, out_words: Optional[torch.Tensor] = None) -> "Transcoded":
+        """The batch re-coded under the prediction filter ``taps`` at RiceParameter ``rice_m`` without decoding it to memory:
+        byte for byte what a plan with that filter and parameter encodes from decode(enc).  rice_m None: the parameter of the
+        smallest total of estimate_words_refiltered() (on a tie the smaller).  out_words as in transcode().  The result's
+        ``taps`` are the target's (None for (1, -1)), so ``result.plan(ctx)`` decodes it.  Waits, and raises like decode().
+        Always a lane per waveform, also for the few long waveforms transcode() gives to its block form.  It is SLOWER than
+        decode(), set_filter(), encode(), set_filter() back -- 21.2 against 13.4 ms on 1 M waveforms of 7000 samples
+        (profiles/refilter_notes.md) -- and saves the decoded intermediate: 7.4 instead of 21.4 GB of peak device memory there."""
+        self._open("refilter")
+        _, _, carried = self._target_taps(taps)
+        if rice_m is None:
+            rice_m = 1 << int(np.argmin(self.estimate_words_refiltered(enc, taps, wave_words)))  # (argmin: the first of equals)
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        off = tab = None
+        if out_words is None:
+            _, off, tab = self.refilter_async(enc.words, enc.chunk_word_off, taps, rice_m, None, enc.total_words, wave_words)
+            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
+        _, off, tab = self.refilter_async(enc.words, enc.chunk_word_off, taps, rice_m, out_words, enc.total_words, wave_words, off, tab)
+        return Transcoded(EncodedBatch(out_words, off, self.finish()), tab, int(rice_m), carried,
+                          self._chunk_samples.copy(), self._wave_lens.copy())
+
     def estimate_words(self, x: torch.Tensor) -> np.ndarray:
         """Exact encoded size (uint32 words) of this batch for RiceParameter 2^k, k = 0..15 -- the
         optimisation the reference's docs/Optimization.md describes; argmin gives the best m."""
@@ -726,7 +800,7 @@ class Plan:
     def last_timings(self):
         """Kernel times (ms) of the last call, HIP events on the context's stream; needs
         ctx.set_option("profile", 1).  encode: (sizes, scan, pack, total); decode, wave_stats, decode_window and find_pulses: (walk, kernel, 0, total);
-        transcode: (walk, sizes + scan + offsets, pack, total)."""
+        transcode and refilter: (walk, sizes + scan + offsets, pack, total)."""
         ms = (C.c_float * 4)()
         self.ctx._check(self.ctx.lib.drx_plan_last_timings(self._h, ms))
         return tuple(float(v) for v in ms)
@@ -759,7 +833,8 @@ class Plan:
     def last_transcode_form(self) -> int:
         """DRX_TRANSCODE_FORM_* (include/deltarice_hip.h): which form the last transcode (the sizing call included) or
         estimate_words_encoded took -- a lane per waveform, or a workgroup per block of a waveform's stream (few long waveforms,
-        any prediction filter); 0 before the plan's first such call."""
+        any prediction filter); refilter and estimate_words_refiltered report LANES | REFILTER, and REFILTER_SERIAL where their
+        serial kernels ran; 0 before the plan's first such call."""
         return int(self.ctx.lib.drx_plan_last_transcode_form(self._h))
 
     def last_transcode_listed(self) -> int:

@@ -1,5 +1,5 @@
 // drx_api_stream.hip -- C ABI glue (drx_api.h): the calls that read the whole batch from the encoded stream -- decode, and
-// without decoding it wave_stats, decode_window(s), find_pulses, transcode, estimate_words_encoded.  Each checks its pointers
+// without decoding it wave_stats, decode_window(s), find_pulses, transcode(_filter), estimate_words_encoded(_filter).  Each checks its pointers
 // with stream_call_args(), opens with stream_call_begin() and closes with call_end().  Host code only.
 #include "drx_api.h"
 
@@ -116,16 +116,33 @@ static drx_status trc_scratch(drx_plan *p, TrcScratch *t) {  // (trc_scratch_vie
     return DRX_OK;
 }
 
+// (what drx_transcode and drx_transcode_filter refuse alike, with nothing launched)
+static drx_status transcode_args(drx_plan *p, const char *who, const uint32_t *d_in, const uint64_t *d_chunk_word_off, const uint32_t *d_sideband,
+                                 bool sideband, uint32_t new_k, const uint32_t *d_out, uint64_t out_cap, const uint64_t *d_out_off,
+                                 const uint32_t *d_out_wave_words) {
+    drx_ctx *ctx = p->ctx;
+    if (new_k > 15u) return fail(ctx, DRX_ERR_ARG, "%s: new_rice_k %u (0..15)", who, new_k);
+    if (!d_in || !d_chunk_word_off || !d_out_off || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "%s: null pointer", who);
+    if (!d_out && out_cap) return fail(ctx, DRX_ERR_ARG, "%s: no output buffer but a capacity of %llu words", who, (unsigned long long)out_cap);
+    if (sideband && (d_sideband == p->d_wave_words || d_out_wave_words == d_sideband))
+        return fail(ctx, DRX_ERR_ARG, "the side-band table must be neither the plan's own nor the output's (copy it first)");
+    return DRX_OK;
+}
+// ... and what every call that names a target filter refuses
+static drx_status target_filter_args(drx_plan *p, const char *who, uint32_t n_taps, const int32_t *taps) {
+    if (n_taps == 0 || n_taps > DRX_MAX_TAPS) return fail(p->ctx, DRX_ERR_ARG, "%s: new_n_taps %u (1..%d)", who, n_taps, DRX_MAX_TAPS);
+    if (!taps) return fail(p->ctx, DRX_ERR_ARG, "%s: null pointer", who);
+    if (taps[0] == 0) return fail(p->ctx, DRX_ERR_ARG, "%s: new_taps[0] must not be 0 (the inverse filter divides by it)", who);
+    return DRX_OK;
+}
+
 static drx_status transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                             const uint32_t *d_sideband, bool sideband, uint32_t new_k, uint32_t *d_out, uint64_t out_cap,
                             uint64_t *d_out_off, uint32_t *d_out_wave_words) {
     if (!p) return DRX_ERR_ARG;
     drx_ctx *ctx = p->ctx;
-    if (new_k > 15u) return fail(ctx, DRX_ERR_ARG, "transcode: new_rice_k %u (0..15)", new_k);
-    if (!d_in || !d_chunk_word_off || !d_out_off || (sideband && !d_sideband)) return fail(ctx, DRX_ERR_ARG, "transcode: null pointer");
-    if (!d_out && out_cap) return fail(ctx, DRX_ERR_ARG, "transcode: no output buffer but a capacity of %llu words", (unsigned long long)out_cap);
-    if (sideband && (d_sideband == p->d_wave_words || d_out_wave_words == d_sideband))
-        return fail(ctx, DRX_ERR_ARG, "the side-band table must be neither the plan's own nor the output's (copy it first)");
+    if (const drx_status st = transcode_args(p, "transcode", d_in, d_chunk_word_off, d_sideband, sideband, new_k, d_out, out_cap, d_out_off, d_out_wave_words))
+        return st;
     DRX_ON_DEVICE(ctx);
     TrcScratch t;
     if (const drx_status st = trc_scratch(p, &t)) return st;
@@ -133,6 +150,26 @@ static drx_status transcode(drx_plan *p, const uint32_t *d_in, uint64_t in_words
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
     DRX_HIP(ctx, form_scratch(p, kTranscodeForm, p->trc.blocks, trc_blocks_scratch_bytes));
     DRX_HIP(ctx, launch_transcode(c, new_k, t, EncOut{d_out, out_cap, d_out_off, d_out_wave_words}, p->dec.d_blk, p->trc.blocks.d, &p->trc.blocks.last_form));
+    return call_end(p, DRX_PATH_TRANSCODE);
+}
+
+// ... to another prediction filter as well (drx_refilter.hip): the plan's filter is the source's.  Always the lane form
+static drx_status transcode_filter(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                   const uint32_t *d_sideband, bool sideband, uint32_t new_k, uint32_t new_n_taps, const int32_t *new_taps,
+                                   uint32_t *d_out, uint64_t out_cap, uint64_t *d_out_off, uint32_t *d_out_wave_words) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (const drx_status st = target_filter_args(p, "transcode_filter", new_n_taps, new_taps)) return st;
+    if (const drx_status st = transcode_args(p, "transcode_filter", d_in, d_chunk_word_off, d_sideband, sideband, new_k, d_out, out_cap, d_out_off,
+                                             d_out_wave_words))
+        return st;
+    DRX_ON_DEVICE(ctx);
+    TrcScratch t;
+    if (const drx_status st = trc_scratch(p, &t)) return st;
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    DRX_HIP(ctx, launch_refilter(c, new_k, RefilterTarget{new_n_taps, new_taps}, t, EncOut{d_out, out_cap, d_out_off, d_out_wave_words},
+                                 &p->trc.blocks.last_form));
     return call_end(p, DRX_PATH_TRANSCODE);
 }
 
@@ -236,6 +273,40 @@ drx_status drx_estimate_words_encoded(drx_plan *p, const uint32_t *d_in, uint64_
     (void)call_end(p, DRX_PATH_TRANSCODE);
     DRX_HIP(ctx, hipMemcpyAsync(words_out, t.est, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     return drx_plan_finish(p, nullptr);  // (waits; a stream that failed validation: DRX_ERR_CORRUPT, words_out undefined)
+}
+
+drx_status drx_transcode_filter(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, uint32_t new_rice_k,
+                                uint32_t new_n_taps, const int32_t *new_taps, uint32_t *d_out, uint64_t out_cap_words,
+                                uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words) {
+    return transcode_filter(p, d_in, in_words, d_chunk_word_off, nullptr, false, new_rice_k, new_n_taps, new_taps, d_out, out_cap_words,
+                            d_out_chunk_word_off, d_out_wave_words);
+}
+
+drx_status drx_transcode_filter_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                                const uint32_t *d_wave_words, uint32_t new_rice_k, uint32_t new_n_taps,
+                                                const int32_t *new_taps, uint32_t *d_out, uint64_t out_cap_words,
+                                                uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words) {
+    return transcode_filter(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, new_rice_k, new_n_taps, new_taps, d_out, out_cap_words,
+                            d_out_chunk_word_off, d_out_wave_words);
+}
+
+drx_status drx_estimate_words_encoded_filter(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                             const uint32_t *d_wave_words, uint32_t new_n_taps, const int32_t *new_taps,
+                                             uint64_t words_out[16]) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    const bool sideband = d_wave_words != nullptr;
+    if (const drx_status st = target_filter_args(p, "estimate_words_encoded_filter", new_n_taps, new_taps)) return st;
+    if (const drx_status st = stream_call_args(p, "estimate_words_encoded_filter", d_in && d_chunk_word_off && words_out, d_wave_words, sideband)) return st;
+    DRX_ON_DEVICE(ctx);
+    TrcScratch t;
+    if (const drx_status st = trc_scratch(p, &t)) return st;
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_wave_words, false, &c)) return st;
+    DRX_HIP(ctx, launch_estimate_words_refiltered(c, RefilterTarget{new_n_taps, new_taps}, t.est, &p->trc.blocks.last_form));
+    (void)call_end(p, DRX_PATH_TRANSCODE);
+    DRX_HIP(ctx, hipMemcpyAsync(words_out, t.est, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    return drx_plan_finish(p, nullptr);  // (waits, as drx_estimate_words_encoded does)
 }
 
 }  // extern "C"

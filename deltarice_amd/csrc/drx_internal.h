@@ -360,6 +360,16 @@ hipError_t launch_trc_blocks_sizes(const StreamCall &c, void *d_blk, void *d_tb,
                                    unsigned long long *d_est, BlkFallbackList *list_out);
 // ... and behind it (and behind no error): the headers, the words blocks share cleared, and the blocks' pack launch
 hipError_t launch_trc_blocks_pack(const StreamCall &c, void *d_blk, void *d_tb, uint32_t k2, const TrcScratch &t, const EncOut &out);
+// drx_transcode_filter / drx_estimate_words_encoded_filter (drx_refilter.hip): launch_transcode()'s steps, tables and events with
+// the change of filter between the parse and the sink -- the plan's filter is the source's, T the target's (host memory, read
+// before the launcher returns).  Always a lane per waveform: form_out = DRX_TRANSCODE_FORM_LANES | _REFILTER, and
+// _REFILTER_SERIAL where the pair of filters (or DRX_DBG_REFILTER_SERIAL) takes the serial kernels
+struct RefilterTarget {
+    uint32_t n_taps;  // 1 .. DRX_MAX_TAPS, taps[0] != 0
+    const int32_t *taps;
+};
+hipError_t launch_refilter(const StreamCall &c, uint32_t k2, const RefilterTarget &T, const TrcScratch &t, const EncOut &out, uint32_t *form_out);
+hipError_t launch_estimate_words_refiltered(const StreamCall &c, const RefilterTarget &T, unsigned long long *d_est, uint32_t *form_out);
 
 // wide: fused_wide() as the route decided it
 hipError_t launch_encode_fused(const EncodeCall &c, int wide, uint64_t *d_scan);

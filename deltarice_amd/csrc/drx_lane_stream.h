@@ -1,6 +1,6 @@
 // drx_lane_stream.h -- the stream side of the kernels that read an encoded batch a LANE per waveform without decoding it to
 // memory: k_wave_stats (drx_stats.hip), k_decode_window (drx_window.hip), k_find_pulses (drx_pulses.hip) and the re-code
-// kernels (drx_transcode.hip).  The reader's constants, which waveform a lane takes (lane_wave()), and the serial parse of the
+// and re-filter kernels (drx_transcode.hip, drx_refilter.hip: their shared bodies are drx_recode.h).  The reader's constants, which waveform a lane takes (lane_wave()), and the serial parse of the
 // general prediction filters' kernels (serial_wave()); the reader itself -- the lane's LDS ring and its two extractions -- is
 // the text of drx_lane_reader.inc, included in each kernel's body.  What a kernel does with a group's sixteen samples stays in
 // its own file.  k_decode_lanes (drx_decode_kernels.hip) has a ring of its own: it carries the transposition buffer, the

@@ -611,7 +611,14 @@ out:
 /* File -> file: every stored chunk of one dataset re-coded at another RiceParameter, never decoded. */
 drx_status drx_h5_recompress(drx_ctx *ctx, const char *src_file, const char *src_name, const char *dst_file, const char *dst_name,
                              unsigned rice_m, drx_h5_stats *st) {
+    return drx_h5_recompress_filtered(ctx, src_file, src_name, dst_file, dst_name, rice_m, 0, NULL, st);
+}
+
+/* ... and, with n_taps != 0, under another prediction filter (drx_transcode_filter): never decoded to memory. */
+drx_status drx_h5_recompress_filtered(drx_ctx *ctx, const char *src_file, const char *src_name, const char *dst_file, const char *dst_name,
+                                      unsigned rice_m, unsigned n_taps, const int32_t *taps, drx_h5_stats *st) {
     if (!ctx || !src_file || !src_name || !dst_file || !dst_name) return DRX_ERR_ARG;
+    if (n_taps > DRX_MAX_TAPS || (n_taps && (!taps || taps[0] == 0))) return DRX_ERR_ARG;
     unsigned k2 = 0;
     if (rice_m && log2_m(rice_m, &k2)) return DRX_ERR_ARG;
     {
@@ -661,14 +668,18 @@ drx_status drx_h5_recompress(drx_ctx *ctx, const char *src_file, const char *src
     if ((rc = drx_plan_set_filter(plan, ds.o.n_taps, ds.o.taps)) != DRX_OK) goto out;
     if (!rice_m) {
         uint64_t est[16];
-        if ((rc = drx_estimate_words_encoded(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, NULL, est)) != DRX_OK) goto out;
+        rc = n_taps ? drx_estimate_words_encoded_filter(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, NULL, n_taps, taps, est)
+                    : drx_estimate_words_encoded(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, NULL, est);
+        if (rc != DRX_OK) goto out;
         for (unsigned k = 1; k < 16; ++k) if (est[k] < est[k2]) k2 = k;  /* (on a tie the smaller) */
         cap = est[k2];
     } else {
         cap = drx_plan_max_encoded_words(plan);
     }
     if (hipMalloc(&d_out, cap * 4) != hipSuccess || hipMalloc((void **)&d_out_off, (n_chunks + 1) * 8) != hipSuccess) { rc = DRX_ERR_NOMEM; goto out; }
-    if ((rc = drx_transcode(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, k2, (uint32_t *)d_out, cap, d_out_off, NULL)) != DRX_OK) goto out;
+    rc = n_taps ? drx_transcode_filter(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, k2, n_taps, taps, (uint32_t *)d_out, cap, d_out_off, NULL)
+                : drx_transcode(plan, (const uint32_t *)fx.d_words, fx.words, fx.d_off, k2, (uint32_t *)d_out, cap, d_out_off, NULL);
+    if (rc != DRX_OK) goto out;
     if ((rc = drx_plan_finish(plan, &words)) != DRX_OK) goto out;
     s.t_gpu = now() - t0;
 
@@ -693,6 +704,17 @@ drx_status drx_h5_recompress(drx_ctx *ctx, const char *src_file, const char *src
     if (H5Pget_filter_by_id2(ds.pl, FILTER_ID, &flags, &ncd, cd, sizeof fname, fname, &fcfg) < 0) goto out;
     if (ncd == 0) ncd = 1;  /* (a dataset stored under the default RiceParameter names none) */
     cd[0] = 1u << k2;
+    if (n_taps) {
+        /* the new filter: (m, WaveformLength, nTaps, taps...) as drx_h5_write_filtered stores them, the delta filter as (m, WaveformLength) */
+        const int delta = n_taps == 2 && taps[0] == 1 && taps[1] == -1;
+        cd[1] = ds.o.wave_len < 0 ? 0xffffffffu : (unsigned)ds.o.wave_len;
+        ncd = 2;
+        if (!delta) {
+            cd[2] = n_taps;
+            for (unsigned j = 0; j < n_taps; ++j) cd[3 + j] = (unsigned)taps[j];
+            ncd = 3 + n_taps;
+        }
+    }
     {
         hid_t sty = H5Dget_type(ds.d);
         ty = H5Tcopy(sty);

@@ -43,6 +43,9 @@ def _load():
                                        C.c_char_p, C.c_uint64, C.POINTER(Stats)]
         L.drx_h5_recompress.restype = C.c_int
         L.drx_h5_recompress.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint, C.POINTER(Stats)]
+        L.drx_h5_recompress_filtered.restype = C.c_int
+        L.drx_h5_recompress_filtered.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint, C.c_uint,
+                                                 C.POINTER(C.c_int32), C.POINTER(Stats)]
         L.drx_h5_write.restype = C.c_int
         L.drx_h5_write.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                    C.c_uint64, C.c_uint, C.c_uint, C.POINTER(Stats)]
@@ -107,17 +110,25 @@ def copy_rows(ctx: Context, src: str, name: str, rows, dst: str, dst_name: str |
     return st.as_dict()
 
 
-def recompress(ctx: Context, src: str, name: str, dst: str, dst_name: str | None = None, rice_m: int | None = None) -> dict:
+def recompress(ctx: Context, src: str, name: str, dst: str, dst_name: str | None = None, rice_m: int | None = None,
+               taps=None) -> dict:
     """File -> file: dataset ``name`` of ``src`` becomes dataset ``dst_name`` (None: ``name``) of the new file ``dst`` with
     every stored chunk re-coded at RiceParameter ``rice_m`` (None: the one that makes the dataset smallest) on the GPU as
     encoded words (drx_transcode), not decoded; shape, element type, chunking and the rest of the compression_opts are the
-    source's.  Returns the stats: n_chunks / stored_bytes = fetched."""
+    source's.  taps: ANOTHER prediction filter for the new dataset ((1, -1): the delta filter; drx_transcode_filter, still no
+    decoded sample in memory) -- its compression_opts then carry the new taps, a delta target the two-value form; None: the
+    source's filter.  Returns the stats: n_chunks / stored_bytes = fetched."""
     st = Stats()
     ctx.stream.wait_stream(torch.cuda.current_stream(ctx.device))
-    rc = _load().drx_h5_recompress(ctx._h, os.fsencode(src), name.encode(), os.fsencode(dst),
-                                   (name if dst_name is None else dst_name).encode(), 0 if rice_m is None else int(rice_m), C.byref(st))
+    t = None if taps is None else [int(v) for v in taps]
+    if t is not None and not 1 <= len(t) <= _lib.DRX_MAX_TAPS:
+        raise _lib.DeltaRiceError(1, f"taps: {len(t)} values (1 .. {_lib.DRX_MAX_TAPS})")
+    tarr = (C.c_int32 * len(t))(*t) if t else None
+    rc = _load().drx_h5_recompress_filtered(ctx._h, os.fsencode(src), name.encode(), os.fsencode(dst),
+                                            (name if dst_name is None else dst_name).encode(), 0 if rice_m is None else int(rice_m),
+                                            len(t) if t else 0, tarr, C.byref(st))
     if rc != _lib.DRX_OK:
-        raise _lib.DeltaRiceError(rc, f"drx_h5_recompress({src!r}, {name!r} -> {dst!r})")
+        raise _lib.DeltaRiceError(rc, f"drx_h5_recompress({src!r}, {name!r} -> {dst!r}" + (f", taps={tuple(t)})" if t else ")"))
     return st.as_dict()
 
 

@@ -70,6 +70,14 @@ drx_status drx_h5_copy_rows(drx_ctx *ctx, const char *src_file, const char *src_
  * represents. */
 drx_status drx_h5_recompress(drx_ctx *ctx, const char *src_file, const char *src_name, const char *dst_file, const char *dst_name,
                              unsigned rice_m, drx_h5_stats *stats);
+/* ... and another prediction filter: taps[n_taps] (1 <= n_taps <= DRX_MAX_TAPS, taps[0] != 0; {1, -1}: the delta filter) replaces
+ * the source's; n_taps == 0 is drx_h5_recompress.  One drx_estimate_words_encoded_filter (if rice_m is 0) and one
+ * drx_transcode_filter take the place of the estimate and the transcode: no decoded sample is held in memory.  The new dataset's
+ * cd_values carry the new RiceParameter and the new taps as drx_h5_write_filtered stores them -- (m, WaveformLength, n_taps,
+ * taps...), a delta target the two-value form (m, WaveformLength) -- and every stored chunk is the bytes the filter would write
+ * for the source's DECODED data under them. */
+drx_status drx_h5_recompress_filtered(drx_ctx *ctx, const char *src_file, const char *src_name, const char *dst_file, const char *dst_name,
+                                      unsigned rice_m, unsigned n_taps, const int32_t *taps, drx_h5_stats *stats);
 
 /* VRAM -> file: encodes d_in (device int16[rows*cols]) and writes it as dataset `name` (file is
  * created/truncated).  rice_m, wave_len: compression_opts (RiceParameter, WaveformLength). */

@@ -494,10 +494,47 @@ drx_status drx_transcode(drx_plan *plan, const uint32_t *d_in, uint64_t in_words
 drx_status drx_transcode_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                          const uint32_t *d_wave_words, uint32_t new_rice_k, uint32_t *d_out, uint64_t out_cap_words,
                                          uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
-/* Which form the plan's last drx_transcode (the sizing call included) or drx_estimate_words_encoded took; 0 before the first */
+/* Re-coding under ANOTHER PREDICTION FILTER as well, still without decoding to memory: d_out receives, byte for byte, what
+ * drx_encode writes under the filter new_taps at RiceParameter 2^new_rice_k for the samples drx_decode produces from d_in under the
+ * plan's filter and RiceParameter (in the reference's terms: every chunk decoded with the source's options, encoded with the
+ * target's, the chunks laid back to back).  The plan describes the SOURCE -- geometry, filter, RiceParameter -- and neither its
+ * filter nor its RiceParameter changes.  new_taps: a HOST array of new_n_taps values, 1 <= new_n_taps <= DRX_MAX_TAPS,
+ * new_taps[0] != 0, consumed before the call returns; {1, -1} is the delta filter.  A source whose lead is not +-1 decodes with
+ * the reference's division towards zero; the result is the encode of those samples, whatever they are.
+ *   Everything else is drx_transcode's: the framing, both output tables, the sizing call (d_out == NULL, capacity 0),
+ * DRX_ERR_CAPACITY at drx_plan_finish with the total needed and not one word written, drx_wave_stats's validation,
+ * DRX_ERR_CORRUPT with d_out untouched, the buffers rule (any 4-byte alignment, every output word stored exactly once, no load
+ * outside [0, in_words)), the end of a pending gather resume, DRX_PATH_TRANSCODE reported alone, and drx_plan_last_timings'
+ * { walk, sizes + scan + offsets, pack, total }.
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: new_n_taps of 0 or above DRX_MAX_TAPS, new_taps NULL,
+ * new_taps[0] == 0, new_rice_k > 15, and drx_transcode's NULL-pointer cases.
+ *   Kernels.  A source that is the delta filter or has at most 4 taps with lead +-1, and a target of at most 4 taps with any
+ * non-zero lead, take the fast pair: drx_transcode's lane kernels with three samples of history in registers and the two filters
+ * as multiply-adds mod 2^16 between the parse and the sink.  Every other pair takes the serial pair (a lane per waveform, global
+ * loads, the last 64 samples in LDS; correct, not tuned); DRX_DBG_REFILTER_SERIAL sends every pair there.  Both give the same
+ * words, tables and verdicts bit for bit.
+ *   ALWAYS a lane per waveform: drx_transcode's block form works on residuals and has no samples at a block's start, so a plan
+ * whose geometry takes the block form for drx_transcode takes these lane kernels for a re-filter (the form word is
+ * LANES | REFILTER, never BLOCKS).  A waveform of millions of samples in one lane is slow; how slow has not been measured.
+ *   Cost (profiles/refilter_notes.md): SLOWER than the route it replaces.  On 1 M waveforms of 7000 samples, delta at m = 8 to
+ * {1, -1, 1, -1} at m = 8: 21.2 ms, where drx_decode + drx_plan_set_filter + drx_encode + drx_plan_set_filter back take 13.4 ms.
+ * What it saves is the decoded intermediate (14 GB there: 7.4 GB of peak device memory above the source instead of 21.4 GB) and
+ * a plan that is never re-filtered (drx_plan_set_filter waits for the stream). */
+drx_status drx_transcode_filter(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                uint32_t new_rice_k, uint32_t new_n_taps, const int32_t *new_taps, uint32_t *d_out,
+                                uint64_t out_cap_words, uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
+/* ... with the SOURCE's side-band, as drx_transcode_with_wave_words takes it */
+drx_status drx_transcode_filter_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words,
+                                                const uint64_t *d_chunk_word_off, const uint32_t *d_wave_words, uint32_t new_rice_k,
+                                                uint32_t new_n_taps, const int32_t *new_taps, uint32_t *d_out, uint64_t out_cap_words,
+                                                uint64_t *d_out_chunk_word_off, uint32_t *d_out_wave_words);
+/* Which form the plan's last drx_transcode / drx_transcode_filter (the sizing calls included), drx_estimate_words_encoded or
+ * drx_estimate_words_encoded_filter took; 0 before the first */
 #define DRX_TRANSCODE_FORM_LANES 1u        /* a lane per waveform */
 #define DRX_TRANSCODE_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream, the lane kernels behind it for listed waveforms */
 #define DRX_TRANSCODE_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_TRANSCODE_ALL_FALLBACK was in force */
+#define DRX_TRANSCODE_FORM_REFILTER 8u     /* or-ed: the call changed the prediction filter (drx_transcode_filter, drx_estimate_words_encoded_filter) */
+#define DRX_TRANSCODE_FORM_REFILTER_SERIAL 16u /* or-ed: ... and its serial kernels ran */
 uint32_t drx_plan_last_transcode_form(const drx_plan *plan);
 /* ... and, valid behind drx_plan_finish, how many waveforms its block form handed to the lane kernels (flagged or suspect
  * waveforms, waveforms with samples and no payload word, all of them under DRX_DBG_TRANSCODE_ALL_FALLBACK); 0 for the lane form */
@@ -510,6 +547,13 @@ uint32_t drx_plan_last_transcode_listed(const drx_plan *plan);
  * counts per block, the lane kernel behind it for the waveforms the blocks list. */
 drx_status drx_estimate_words_encoded(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                       const uint32_t *d_wave_words, uint64_t words_out[16]);
+/* ... under another prediction filter: words_out[k] is the total words drx_transcode_filter would produce with these taps at
+ * new_rice_k = k, headers included, k = 0..15.  d_wave_words: the source's side-band, or NULL to walk.  new_taps as
+ * drx_transcode_filter takes them (DRX_ERR_ARG likewise).  SYNCHRONOUS like drx_estimate_words_encoded; the sizes kernels of
+ * drx_transcode_filter with sixteen counts per lane. */
+drx_status drx_estimate_words_encoded_filter(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                             const uint32_t *d_wave_words, uint32_t new_n_taps, const int32_t *new_taps,
+                                             uint64_t words_out[16]);
 
 /* RiceParameter optimiser (docs/Optimization.md:5-19 of the reference describes one, the tree does not
  * contain it): exact number of uint32 words drx_encode would emit for this batch with RiceParameter
@@ -615,6 +659,7 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
 #define DRX_DBG_RAGGED_ONE_LANES_LAUNCH 131072u /* ragged batches: one decode launch behind both header walks */
 #define DRX_DBG_STREAM_THREE_WGS 262144u        /* the persistent encoders on three workgroups (every wavefront goes around its ring) */
 #define DRX_DBG_FORCE_STREAM 524288u            /* the persistent encoder (encode_impl 2) whatever the batch's size and code length */
+#define DRX_DBG_REFILTER_SERIAL 1048576u         /* drx_transcode_filter / drx_estimate_words_encoded_filter: the serial kernels also for filter pairs the fast kernels take */
 #define DRX_DBG_IIR_SEPARATE 2097152u           /* general filters behind the block decoder: always the separate inverse-filter pass */
 #define DRX_DBG_FORCE_STREAM_SEGS 4194304u      /* the persistent encoder's segment form (encode_impl 2, uniform), segments of ~1024 samples */
 #define DRX_DBG_WALK_BY_SCAN 8388608u           /* the chunk-wide header walk by reading the whole chunk instead of chasing 64 chains */
