@@ -13,6 +13,8 @@ from ._lib import (STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD
                    STAT_MAX, STAT_MIN, STAT_SUM, STAT_SUMSQ)
 
 from ._lib import DBG_REFILTER_SERIAL, TRANSCODE_FORM_REFILTER, TRANSCODE_FORM_REFILTER_SERIAL  # noqa: F401
+from ._lib import (BIN_COLS, BIN_MAX, BIN_MIN, BIN_SUM, BIN_SUMSQ, BINS_FORM_BLOCKS, BINS_FORM_FALLBACK_ALL, BINS_FORM_LANES,  # noqa: F401
+                   DBG_BINS_ALL_FALLBACK, DBG_BINS_LANES, PATH_BINS)
 
 H5FILTER = 32025
 

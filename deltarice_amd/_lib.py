@@ -24,6 +24,10 @@ PATH_TRANSCODE = 1024
 PATH_WINDOW = 2048
 PATH_PULSES = 4096
 PATH_WINDOWS = 8192
+PATH_BINS = 16384
+# DRX_BIN_*: the columns of a drx_wave_bins row (tests/test_wave_bins_abi.py holds them equal)
+BIN_SUM, BIN_SUMSQ, BIN_MIN, BIN_MAX = range(4)
+BIN_COLS = 4
 # DRX_STAT_*: the columns of a drx_wave_stats row (tests/test_wave_stats_abi.py holds them equal)
 STAT_MIN, STAT_ARGMIN, STAT_MAX, STAT_ARGMAX, STAT_SUM, STAT_SUMSQ, STAT_HEAD_SUM, STAT_HEAD_SUMSQ = range(8)
 STAT_COLS = 8
@@ -31,6 +35,8 @@ STAT_COLS = 8
 PULSE_START, PULSE_WIDTH, PULSE_PEAK, PULSE_ARGPEAK, PULSE_SUM = range(5)
 PULSE_COLS = 5
 ENC_TWO_PASS, ENC_SEGMENTS, ENC_FUSED, ENC_PIECES, ENC_STREAM, ENC_STREAM_SEGS = 1, 2, 3, 4, 5, 6
+DBG_BINS_LANES = 64
+DBG_BINS_ALL_FALLBACK = 128
 DBG_NO_LONG_PATHS = 256
 DBG_LONG_NOT_BLOCKS = 512
 DBG_TRANSCODE_LANES = 1024
@@ -62,6 +68,8 @@ PULSES_FORM_LANES, PULSES_FORM_BLOCKS, PULSES_FORM_FALLBACK_ALL = 1, 2, 4
 PULSES_STAGE_CAP = 8  # DRX_PULSES_STAGE_CAP
 # DRX_WINDOWS_FORM_*: drx_plan_last_windows_form (tests/test_decode_windows_abi.py holds them equal)
 WINDOWS_FORM_LANES, WINDOWS_FORM_BLOCKS, WINDOWS_FORM_FALLBACK_ALL = 1, 2, 4
+# DRX_BINS_FORM_*: drx_plan_last_bins_form (tests/test_wave_bins_abi.py holds them equal)
+BINS_FORM_LANES, BINS_FORM_BLOCKS, BINS_FORM_FALLBACK_ALL = 1, 2, 4
 # DRX_TRANSCODE_FORM_*: drx_plan_last_transcode_form (tests/test_transcode_blocks_abi.py holds them equal)
 TRANSCODE_FORM_LANES, TRANSCODE_FORM_BLOCKS, TRANSCODE_FORM_FALLBACK_ALL = 1, 2, 4
 # ... or-ed in by the re-filter calls (tests/test_refilter_abi.py holds them equal)
@@ -110,6 +118,8 @@ SIGNATURES = {
     "drx_plan_last_pulses_form": (C.c_uint32, [_vp]),
     "drx_plan_last_windows_form": (C.c_uint32, [_vp]),
     "drx_plan_last_windows_listed": (C.c_uint32, [_vp]),
+    "drx_plan_last_bins_form": (C.c_uint32, [_vp]),
+    "drx_plan_last_bins_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_transcode_form": (C.c_uint32, [_vp]),
     "drx_plan_last_transcode_listed": (C.c_uint32, [_vp]),
     "drx_plan_last_pulses_listed": (C.c_uint32, [_vp]),
@@ -124,6 +134,8 @@ SIGNATURES = {
     "drx_gather_encoded_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _u64, _u64, _vp, _u64, _vp, _vp]),
     "drx_wave_stats": (C.c_int, [_vp, _vp, _u64, _vp, _u32, _vp]),
     "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
+    "drx_wave_bins": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, _u32, _vp, _u64]),
+    "drx_wave_bins_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, _u32, _vp, _u64]),
     "drx_decode_window": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_decode_window_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_decode_windows": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _u32, C.c_int64, _u32, C.c_int16, _vp, _u64, _u64]),

@@ -497,6 +497,51 @@ class Plan:
         self._open("wave_stats")
         return self._blocking(self.wave_stats_async, enc.words, enc.chunk_word_off, head, out, wave_words, in_words=enc.total_words)
 
+    def wave_bins_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, bin: int, n_bins: Optional[int] = None,
+                        start: Optional[torch.Tensor] = None, offset: int = 0, out: Optional[torch.Tensor] = None,
+                        wave_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None) -> torch.Tensor:
+        """Launches drx_wave_bins on the context's stream: int64 [total_waves, n_bins, BIN_COLS], row (g, b) = (sum, sum of
+        squares, min, max) of the samples of waveform g with index in [a + b * bin, a + (b + 1) * bin), a = start[g] + offset,
+        over the int16 samples decode() would give, exact.  A bin that holds no sample is (0, 0, 32767, -32768), so neighbouring
+        bins merge by add, add, min, max.  Nothing is decoded to memory.  n_bins None: enough bins to cover the plan's longest
+        waveform from ``offset``.  start: None, or a 1-D int64 tensor of total_waves entries on the plan's device with any
+        element stride -- ``stats[:, STAT_ARGMAX]`` is passed as it is, as decode_window takes it.  out: a contiguous int64
+        tensor of total_waves * n_bins * BIN_COLS elements.  wave_words: the encoder's n_i table as decode_with_wave_words
+        takes it (no header walk).  Launch only; finish() raises on device-side errors."""
+        self._open("wave_bins")
+        bin, offset = int(bin), int(offset)
+        if not 1 <= bin < 1 << 32:
+            raise DeltaRiceError(1, f"bin: {bin} is not a uint32 above 0")
+        if not -(1 << 63) <= offset < 1 << 63:
+            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+        n_bins = max(0, -(-(self.longest_wave() - offset) // bin)) if n_bins is None else int(n_bins)
+        if not 0 <= n_bins < 1 << 32:
+            raise DeltaRiceError(1, f"n_bins: {n_bins} is not a uint32")
+        sp, ss = None, 0
+        if start is not None:
+            if (not isinstance(start, torch.Tensor) or start.dim() != 1 or start.device != self.ctx.device or
+                    start.dtype != torch.int64 or start.shape[0] != self.total_waves or (self.total_waves > 1 and start.stride(0) < 1)):
+                raise DeltaRiceError(1, f"start: need a 1-D int64 tensor of {self.total_waves} entries on {self.ctx.device}")
+            sp, ss = start.data_ptr(), (int(start.stride(0)) if self.total_waves > 1 else 1)
+        self._check_encoded(words, chunk_word_off, wave_words)
+        if out is None:
+            out = torch.empty((self.total_waves, n_bins, _lib.BIN_COLS), dtype=torch.int64, device=self.ctx.device)
+        self._dev_check(out, torch.int64, self.total_waves * n_bins * _lib.BIN_COLS, "out")
+        if n_bins == 0 or self.total_waves == 0:
+            return out
+        self._call_encoded("wave_bins", words, chunk_word_off, wave_words, in_words, sp, ss, offset, bin, n_bins, out.data_ptr(),
+                           n_bins * _lib.BIN_COLS)
+        return out
+
+    def wave_bins(self, enc: EncodedBatch, bin: int, n_bins: Optional[int] = None, start: Optional[torch.Tensor] = None,
+                  offset: int = 0, out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """wave_bins_async on an EncodedBatch -> int64 [total_waves, n_bins, BIN_COLS]; waits, and raises like wave_stats().  The
+        charge in eight gates of 250 samples around every waveform's peak:
+        ``plan.wave_bins(enc, 250, 8, start=stats[:, STAT_ARGMAX], offset=-500)[:, :, BIN_SUM]``."""
+        self._open("wave_bins")
+        return self._blocking(self.wave_bins_async, enc.words, enc.chunk_word_off, bin, n_bins, start, offset, out, wave_words,
+                              in_words=enc.total_words)
+
     def decode_window_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start, width: int, offset: int = 0,
                             pad: int = 0, out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None,
                             wave_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None) -> torch.Tensor:
@@ -829,6 +874,18 @@ class Plan:
         """After finish(): how many waveforms the last decode_windows' block form handed to the lane kernel behind it (flagged or
         judged suspect by the block parse; their rows are written again and judged there); 0 for the lane form."""
         return int(self.ctx.lib.drx_plan_last_windows_listed(self._h))
+
+    def last_bins_form(self) -> int:
+        """DRX_BINS_FORM_* (include/deltarice_hip.h): which form the last wave_bins took -- a lane per waveform for every batch
+        today (there is no block form yet); 0 before the plan's first such call."""
+        self._open("last_bins_form")
+        return int(self.ctx.lib.drx_plan_last_bins_form(self._h))
+
+    def last_bins_listed(self) -> int:
+        """After finish(): how many waveforms the last wave_bins' block form handed to the lane kernel behind it; 0 for the
+        lane form."""
+        self._open("last_bins_listed")
+        return int(self.ctx.lib.drx_plan_last_bins_listed(self._h))
 
     def last_transcode_form(self) -> int:
         """DRX_TRANSCODE_FORM_* (include/deltarice_hip.h): which form the last transcode (the sizing call included) or

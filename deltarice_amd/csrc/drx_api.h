@@ -179,6 +179,7 @@ struct drx_plan {
     };
     BlockForm stats;    // drx_wave_stats: accumulators and list
     BlockForm windows;  // drx_decode_windows: its list
+    BlockForm bins;     // drx_wave_bins: the form word alone (no block form yet, no scratch)
     struct Pulses : BlockForm {  // drx_find_pulses: block summaries and list ...
         Grown stage;             // ... and the records its blocks stage: as many as the call needs (pulses_blocks_staging_bytes())
     } pulses;

@@ -6,7 +6,7 @@
 //   drx_api_plan.hip    this file
 //   drx_api_encode.hip  how an encode is routed, drx_encode, drx_estimate_words
 //   drx_api_select.hip  drx_decode_select, drx_gather_encoded
-//   drx_api_stream.hip  the calls that read an encoded batch: decode, wave_stats, decode_window(s), find_pulses, transcode
+//   drx_api_stream.hip  the calls that read an encoded batch: decode, wave_stats, wave_bins, decode_window(s), find_pulses, transcode
 //   drx_api_host.hip    one chunk through host memory (the H5Z callback's body)
 #include <cstdarg>
 #include <cstdio>
@@ -434,6 +434,8 @@ uint32_t drx_plan_last_transcode_form(const drx_plan *p) { return p ? p->trc.blo
 uint32_t drx_plan_last_transcode_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_TRANSCODE) ? p->h_status->listed : 0u; }
 uint32_t drx_plan_last_pulses_redone(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_PULSES) ? p->h_status->redone : 0u; }
 uint32_t drx_plan_last_pulses_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_PULSES) ? p->h_status->listed : 0u; }
+uint32_t drx_plan_last_bins_form(const drx_plan *p) { return p ? p->bins.last_form : 0u; }
+uint32_t drx_plan_last_bins_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_BINS) ? p->h_status->listed : 0u; }
 uint32_t drx_plan_last_windows_listed(const drx_plan *p) { return (p && p->h_status && p->dec.last_path == DRX_PATH_WINDOWS) ? p->h_status->listed : 0u; }
 
 drx_status drx_plan_read_wave_words(drx_plan *p, uint32_t *host_out) {

@@ -1,5 +1,5 @@
 // drx_api_stream.hip -- C ABI glue (drx_api.h): the calls that read the whole batch from the encoded stream -- decode, and
-// without decoding it wave_stats, decode_window(s), find_pulses, transcode(_filter), estimate_words_encoded(_filter).  Each checks its pointers
+// without decoding it wave_stats, wave_bins, decode_window(s), find_pulses, transcode(_filter), estimate_words_encoded(_filter).  Each checks its pointers
 // with stream_call_args(), opens with stream_call_begin() and closes with call_end().  Host code only.
 #include "drx_api.h"
 
@@ -37,6 +37,25 @@ static drx_status wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_word
     DRX_HIP(ctx, form_scratch(p, kStatsForm, p->stats, stats_blocks_scratch_bytes));
     DRX_HIP(ctx, launch_wave_stats(c, p->dec.d_blk, p->stats.d, head_len, d_out, &p->stats.last_form));
     return call_end(p, DRX_PATH_STATS);
+}
+
+// binned statistics of every waveform from the encoded stream (drx_bins.hip)
+static drx_status wave_bins(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                            const uint32_t *d_sideband, bool sideband, const int64_t *d_start, uint64_t start_stride, int64_t offset,
+                            uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (const drx_status st = stream_call_args(p, "wave_bins", d_in && d_chunk_word_off && d_out, d_sideband, sideband)) return st;
+    if (bin == 0) return fail(ctx, DRX_ERR_ARG, "wave_bins: bin 0");
+    if (d_start && start_stride == 0) return fail(ctx, DRX_ERR_ARG, "wave_bins: start_stride 0");
+    if (out_wave_stride < (uint64_t)n_bins * DRX_BIN_COLS)
+        return fail(ctx, DRX_ERR_ARG, "wave_bins: waveforms %llu int64 apart do not hold %u rows", (unsigned long long)out_wave_stride, n_bins);
+    if (n_bins == 0) return DRX_OK;  // (no row to write: nothing to launch)
+    DRX_ON_DEVICE(ctx);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    DRX_HIP(ctx, launch_wave_bins(c, d_start, start_stride, offset, bin, n_bins, d_out, out_wave_stride, &p->bins.last_form));
+    return call_end(p, DRX_PATH_BINS);
 }
 
 // a window of every waveform, at per-waveform offsets (drx_window.hip)
@@ -195,6 +214,18 @@ drx_status drx_wave_stats(drx_plan *p, const uint32_t *d_in, uint64_t in_words, 
 drx_status drx_wave_stats_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
                                           const uint32_t *d_wave_words, uint32_t head_len, int64_t *d_out) {
     return wave_stats(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, head_len, d_out);
+}
+
+drx_status drx_wave_bins(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, const int64_t *d_start,
+                         uint64_t start_stride, int64_t offset, uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride) {
+    return wave_bins(p, d_in, in_words, d_chunk_word_off, nullptr, false, d_start, start_stride, offset, bin, n_bins, d_out, out_wave_stride);
+}
+
+drx_status drx_wave_bins_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                         const uint32_t *d_wave_words, const int64_t *d_start, uint64_t start_stride, int64_t offset,
+                                         uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride) {
+    return wave_bins(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_start, start_stride, offset, bin, n_bins, d_out,
+                     out_wave_stride);
 }
 
 drx_status drx_decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,

@@ -265,14 +265,21 @@ constexpr BlkFormRule kWindowsForm{kWindowsLaneUs, DRX_DBG_WINDOWS_LANES, DRX_DB
 constexpr double kTranscodeLaneUs = 0.2045;
 constexpr double kTranscodeBlockFactor = 4.0;
 constexpr BlkFormRule kTranscodeForm{kTranscodeLaneUs / kTranscodeBlockFactor, DRX_DBG_TRANSCODE_LANES, DRX_DBG_TRANSCODE_ALL_FALLBACK, true};
+// drx_wave_bins has no block form yet: its rule is here for the form word and the flags' names, and no launcher asks
+// blocks_form_batch() with it, so every batch stays a lane per waveform (DRX_DBG_BINS_ALL_FALLBACK has nothing to act on).
+// k_wave_bins takes 28.53 ms for a lane of 500 000 samples at 1000 bins (profiles/wave_bins_bench.txt, row `noptrex`): 0.057 us
+// per sample
+constexpr double kBinsLaneUs = 0.057;
+constexpr BlkFormRule kBinsForm{kBinsLaneUs, DRX_DBG_BINS_LANES, DRX_DBG_BINS_ALL_FALLBACK};
 bool blocks_form_batch(const Geom &G, const void *d_blk, const BlkFormRule &r);
-// the form word of a call, one set of values under four names: LANES, or BLOCKS | FALLBACK_ALL under the rule's all_fallback_flag
+// the form word of a call, one set of values under five names: LANES, or BLOCKS | FALLBACK_ALL under the rule's all_fallback_flag
 static_assert(DRX_STATS_FORM_LANES == DRX_PULSES_FORM_LANES && DRX_STATS_FORM_LANES == DRX_WINDOWS_FORM_LANES &&
                   DRX_STATS_FORM_BLOCKS == DRX_PULSES_FORM_BLOCKS && DRX_STATS_FORM_BLOCKS == DRX_WINDOWS_FORM_BLOCKS &&
                   DRX_STATS_FORM_FALLBACK_ALL == DRX_PULSES_FORM_FALLBACK_ALL && DRX_STATS_FORM_FALLBACK_ALL == DRX_WINDOWS_FORM_FALLBACK_ALL &&
                   DRX_STATS_FORM_LANES == DRX_TRANSCODE_FORM_LANES && DRX_STATS_FORM_BLOCKS == DRX_TRANSCODE_FORM_BLOCKS &&
-                  DRX_STATS_FORM_FALLBACK_ALL == DRX_TRANSCODE_FORM_FALLBACK_ALL,
-              "blocks_form_word() serves the four calls");
+                  DRX_STATS_FORM_FALLBACK_ALL == DRX_TRANSCODE_FORM_FALLBACK_ALL && DRX_STATS_FORM_LANES == DRX_BINS_FORM_LANES &&
+                  DRX_STATS_FORM_BLOCKS == DRX_BINS_FORM_BLOCKS && DRX_STATS_FORM_FALLBACK_ALL == DRX_BINS_FORM_FALLBACK_ALL,
+              "blocks_form_word() serves the five calls");
 uint32_t blocks_form_word(const Geom &G, bool blocks, const BlkFormRule &r);
 // The waveforms a block form leaves to the lane kernel behind it, a list on the device, part of the form's scratch:
 // u32 n_listed (+ pad to 8 bytes) | u32 listed[W].  (blk_listed() and blk_list_append(), drx_blocks.h, fill it.)
@@ -287,6 +294,13 @@ struct BlkFallbackList {
 hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, uint32_t *form_out);
 uint64_t stats_blocks_scratch_bytes(const Geom &G);
 hipError_t launch_stats_blocks(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, BlkFallbackList *list_out);
+// drx_wave_bins (drx_bins.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses and
+// reduces bin by bin: row (g, b) = d_out + g * out_wave_stride + b * DRX_BIN_COLS holds the samples of waveform g with index in
+// [a + b * bin, a + (b + 1) * bin), a = d_start[g * start_stride] + offset (saturating; d_start == nullptr: 0); every one of
+// the n_bins rows of every waveform is written, an empty bin as (0, 0, 32767, -32768).  ev: {start, walk's end, kernel's end, end}
+// form_out: DRX_BINS_FORM_* of include/deltarice_hip.h
+hipError_t launch_wave_bins(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t bin,
+                            uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride, uint32_t *form_out);
 // drx_decode_window (drx_window.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
 // far as its window's end and writes `width` samples from start[g * start_stride] + offset on (pad outside the waveform) to row
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}

@@ -263,6 +263,61 @@ drx_status drx_wave_stats_with_wave_words(drx_plan *plan, const uint32_t *d_in, 
 #define DRX_STATS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_STATS_ALL_FALLBACK was in force */
 uint32_t drx_plan_last_stats_form(const drx_plan *plan);
 
+/* BINNED statistics of every waveform straight from the encoded stream: the sum, the sum of squares, the minimum and the maximum
+ * of every stretch of `bin` samples from a per-waveform origin -- the overview of a long trace (min, max and mean per 1/1000 of
+ * it; the RMS per time bin of a decaying signal), the charge in gates around a pulse, a baseline that drifts -- without decoding
+ * the batch to memory.  drx_wave_stats' two HEAD columns generalised to any number of equal windows.
+ *   Bins.  Waveform g (a global waveform index in the order of drx_plan_wave_words) has samples y[0 .. len_g), the int16
+ * drx_decode would write.  Its origin is a_g = (d_start ? d_start[g * start_stride] : 0) + offset; the sum saturates at the int64
+ * ends, as in drx_decode_window.  d_start: int64 on the device, any 8-byte alignment; start_stride counts int64 elements, so a
+ * column of drx_wave_stats' output or of drx_find_pulses' records goes in as it is.  Bin b, 0 <= b < n_bins, holds the samples
+ * with index in [a_g + b * bin, a_g + (b + 1) * bin) and in [0, len_g).
+ *   Rows.  Row (g, b) is d_out + g * out_wave_stride + b * DRX_BIN_COLS: four int64, the DRX_BIN_* columns.  An empty bin -- one
+ * outside the waveform, one beyond the short last waveform of a chunk -- is (0, 0, 32767, -32768), the identities of the four
+ * reductions: neighbouring bins merge by add, add, min, max with no special case, and the bins that cover a waveform merge to
+ * drx_wave_stats' SUM, SUMSQ, MIN, MAX.  Everything is exact (a waveform has fewer than 2^31 samples).
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: a NULL pointer among d_in, d_chunk_word_off, d_out; bin == 0;
+ * start_stride == 0 with d_start != NULL; out_wave_stride < n_bins * DRX_BIN_COLS; in the second form a NULL side-band, or the
+ * plan's own table passed as the side-band.  n_bins == 0 returns DRX_OK with nothing launched.
+ *   Validation is drx_wave_stats': the header chain of every chunk is walked and judged (the second form checks the table
+ * against the stream instead), and EVERY waveform is parsed to its end whatever its bins cover: a payload that ends before its
+ * samples do, or whose codes do not end in its last payload word, is DRX_ERR_CORRUPT at drx_plan_finish; the rows are then
+ * undefined and the plan stays usable.
+ *   The buffers rule at the top of this file holds: any 4-byte alignment of d_in, any 8-byte alignment of d_start and d_out; no
+ * load leaves [0, in_words); exactly total_waves x n_bins rows of four int64 are written, nothing between the rows of different
+ * waveforms is touched, and the result does not depend on what the rows held before; row addressing is 64-bit.
+ *   Asynchronous on the context's stream like drx_wave_stats; the call clears the plan's status word first and ends a pending
+ * drx_gather_encoded sizing call's resume; errors found on the device arrive at drx_plan_finish.  drx_plan_last_decode_path
+ * reports DRX_PATH_BINS alone whichever form ran (drx_plan_last_bins_form says which), drx_plan_last_timings
+ * { header-chain walk, everything behind the walk, 0, whole call }.
+ *   Every prediction filter the plan accepts, a lane per waveform: the delta filter parses as drx_wave_stats' lane kernel does
+ * and splits a group of 16 samples that holds a bin's end in registers (bins shorter than 16 samples take a sample-at-a-time
+ * path: correct, several times slower); any other filter runs a serial kernel, correct but not fast.  There is NO block form
+ * yet: few long waveforms -- the batches drx_wave_stats gives to its block form -- stay a lane per waveform, 50-60 ns per sample
+ * and lane, and drx_plan_last_bins_form says DRX_BINS_FORM_LANES for every batch.  DRX_DBG_BINS_LANES and
+ * DRX_DBG_BINS_ALL_FALLBACK are reserved for that form and change nothing today. */
+#define DRX_BIN_SUM 0     /* sum of y[i] over the bin                     */
+#define DRX_BIN_SUMSQ 1   /* sum of y[i]^2                                */
+#define DRX_BIN_MIN 2     /* smallest sample;  32767 for an empty bin     */
+#define DRX_BIN_MAX 3     /* largest sample;  -32768 for an empty bin     */
+#define DRX_BIN_COLS 4
+drx_status drx_wave_bins(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                         const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t bin, uint32_t n_bins,
+                         int64_t *d_out, uint64_t out_wave_stride);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
+ * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_wave_bins_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                         const uint32_t *d_wave_words, const int64_t *d_start, uint64_t start_stride,
+                                         int64_t offset, uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride);
+/* which form the plan's last drx_wave_bins took (0: none yet) */
+#define DRX_BINS_FORM_LANES 1u        /* a lane per waveform */
+#define DRX_BINS_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream (reserved: no batch takes it yet) */
+#define DRX_BINS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_BINS_ALL_FALLBACK was in force (reserved likewise) */
+uint32_t drx_plan_last_bins_form(const drx_plan *plan);
+/* ... and, behind drx_plan_finish while drx_plan_last_decode_path is DRX_PATH_BINS, how many waveforms a block form handed to
+ * the lane kernel behind the blocks, as drx_plan_last_windows_listed; 0 for the lane form */
+uint32_t drx_plan_last_bins_listed(const drx_plan *plan);
+
 /* A WINDOW of every waveform, at per-waveform offsets, straight from the encoded stream: the samples around a pulse that
  * drx_wave_stats found, or the first few hundred samples of each waveform, without decoding the batch to memory and -- unlike
  * every other stream call -- without reading a payload beyond its window.
@@ -590,6 +645,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_WINDOW 2048u   /* drx_decode_window: a lane per waveform that parses to its window's end; reported alone */
 #define DRX_PATH_PULSES 4096u   /* drx_find_pulses: a lane per waveform that parses and discriminates; reported alone */
 #define DRX_PATH_WINDOWS 8192u  /* drx_decode_windows: several windows per waveform, lanes or blocks; reported alone */
+#define DRX_PATH_BINS 16384u    /* drx_wave_bins: a lane per waveform that parses and reduces bin by bin; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -625,6 +681,7 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_decode: ms = { header-chain walk, decode kernel, 0, whole call }
  *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
  *   after drx_wave_stats: ms = { header-chain walk, statistics kernels (block form: blocks + finish + fallback), 0, whole call }
+ *   after drx_wave_bins: ms = { header-chain walk, everything behind the walk, 0, whole call }
  *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
  *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call }
  *   after drx_decode_windows: ms = { header-chain walk, everything between the walk and the call's end (block form: pads,
@@ -647,6 +704,8 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
  *        0            simple kernel (also: general filters the staged kernel does not take)
  *   "debug_flags"  DRX_DBG_* bits: dispatch overrides that force an alternative (still bit-exact) path, for tests and A/B timing;
  *                  a forcing flag takes its encoder wherever that encoder can run the batch */
+#define DRX_DBG_BINS_LANES 64u                   /* drx_wave_bins: never a block form (reserved: every batch is a lane per waveform today) */
+#define DRX_DBG_BINS_ALL_FALLBACK 128u          /* drx_wave_bins, block form: every waveform is listed for the lane kernel behind the blocks (reserved) */
 #define DRX_DBG_NO_LONG_PATHS 256u              /* never the long-waveform paths (segment encoders, block and long decoders) */
 #define DRX_DBG_LONG_NOT_BLOCKS 512u            /* long waveforms: one workgroup per waveform, never the block decoder */
 #define DRX_DBG_TRANSCODE_LANES 1024u            /* drx_transcode / drx_estimate_words_encoded: never the block form (a lane per waveform whatever the batch) */
