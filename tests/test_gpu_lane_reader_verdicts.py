@@ -1,5 +1,6 @@
-"""GPU: the end-of-payload verdict of the four calls that read the stream a lane per waveform through the shared reader
-(csrc/drx_lane_reader.inc): drx_wave_stats, drx_decode_window, drx_find_pulses, drx_transcode.
+"""GPU: the end-of-payload verdict of the seven calls that read the stream a lane per waveform through the shared reader
+(csrc/drx_lane_reader.inc): drx_wave_stats, drx_wave_bins, drx_decode_window, drx_decode_windows, drx_find_pulses,
+drx_transcode, drx_transcode_filter.
 
 The shape is the smallest that reaches every branch of the reader: 2 chunks of 70 waveforms x 100 samples, m = 8 -- three
 wavefronts, the last partly filled, a wavefront whose lanes lie in two chunks, a masked last group (100 = 6 x 16 + 4) -- and
@@ -9,15 +10,19 @@ runs the serial kernels (a general prediction filter).
 One waveform's payload is made a word too SHORT (its last word cut: the codes end after it) or a word too LONG (a zero word
 appended: the codes end before it), its header word and the chunk offsets mended, so that every walk accepts the chain and it
 is the lane that has to notice.  Each call then reports DRX_ERR_CORRUPT -- except drx_decode_window with a head window, which
-reads no payload beyond its window's last code: it reports nothing and its rows are numpy's over the oracle's input.  The
-undamaged streams are held to the numpy models of the three calls and to the oracle's stream at the new parameter."""
+reads no payload beyond its window's last code: it reports nothing and its rows are numpy's over the oracle's input.
+drx_wave_bins parses every waveform to its end whatever its bins cover, and drx_decode_windows is given a window that reaches
+every waveform's end.  The undamaged streams are held to the numpy models of the five calls and to the oracle's stream at the
+new parameter and under the new filter."""
 import numpy as np
 import pytest
 
 from decode_window_reference import windows
+from decode_windows_reference import windows_multi
 from deltarice_amd import _lib as D
 from find_pulses_reference import find_pulses
 from test_gpu_select import Stream, header_table
+from wave_bins_reference import wave_bins
 from wave_stats_reference import wave_stats_heads
 
 pytestmark = pytest.mark.gpu
@@ -79,8 +84,19 @@ def damaged(ctx, st, c, i, by):
     return enc, table
 
 
+FIR4 = (1, -1, 1, -1)  # the target of drx_transcode_filter: the fast kernels behind the delta source, the serial ones behind `serial`
+
+
+def two_windows(plan):
+    """starts [W, 2] of drx_decode_windows: sample 60 and sample 0 -- with a width of 100 the second reaches every waveform's end"""
+    return torch.tensor([[60, 0]], dtype=torch.int64, device=plan.ctx.device).repeat(plan.total_waves, 1)
+
+
 CALLS = {
     "wave_stats": lambda plan, enc, kw: plan.wave_stats(enc, head=40, **kw),
+    "wave_bins": lambda plan, enc, kw: plan.wave_bins(enc, 10, 2, **kw),  # (the bins end at sample 20)
+    "decode_windows": lambda plan, enc, kw: plan.decode_windows(enc, two_windows(plan), 100, **kw),
+    "refilter": lambda plan, enc, kw: plan.refilter(enc, FIR4, 32, **kw),
     "decode_window": lambda plan, enc, kw: plan.decode_window(enc, None, 100, **kw),  # (every waveform to its end)
     "find_pulses": lambda plan, enc, kw: plan.find_pulses(enc, 20, 1, 1, 3, **kw),
     "transcode": lambda plan, enc, kw: plan.transcode(enc, 32, **kw),
@@ -100,6 +116,20 @@ def test_clean_stream(ctx, O, streams, shape):
         n, p = find_pulses(x, Ns, Ls, 20, 1, 1, 3, None, geom)
         gn, gp = st.plan.find_pulses(st.enc, 20, 1, 1, 3, **kw)
         assert torch.equal(gn, torch.from_numpy(n).to(ctx.device)) and torch.equal(gp, torch.from_numpy(p).to(ctx.device))
+        for bin, n_bins in ((10, 2), (16, 7), (17, 3)):
+            assert torch.equal(st.plan.wave_bins(st.enc, bin, n_bins, **kw), torch.from_numpy(wave_bins(x, Ns, Ls, bin, n_bins)).to(ctx.device)), bin
+        starts = two_windows(st.plan)
+        assert torch.equal(st.plan.decode_windows(st.enc, starts, 100, pad=-3, **kw),
+                           torch.from_numpy(windows_multi(x, Ns, Ls, starts.cpu().numpy(), None, 0, 100, -3, geom)).to(ctx.device))
+        # (the oracle's stream of the same samples under the new filter, byte for byte: the sources' leads are +-1)
+        t = st.plan.refilter(st.enc, FIR4, 32, **kw)
+        want, at = [], 0
+        for N, L in zip(Ns, Ls):
+            want.append(O.encode_chunk(x[at:at + N], (32, L, len(FIR4)) + tuple(v & 0xFFFFFFFF for v in FIR4)))
+            at += N
+        want = np.concatenate(want)
+        assert t.enc.total_words == want.size
+        assert np.array_equal(t.enc.words[:want.size].cpu().numpy().view(np.uint32), want)
         if taps is None:  # (the oracle's stream at the new parameter, byte for byte: a filter with lead +-1)
             t = st.plan.transcode(st.enc, 32, **kw)
             want, at = [], 0

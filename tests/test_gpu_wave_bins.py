@@ -11,8 +11,9 @@ from deltarice_amd import _lib as D
 from test_gpu_placement import FF, PLACEMENTS, SLACK, run, window
 from test_gpu_routes import BATCHES
 from test_gpu_select import Stream, geometry, header_table  # noqa: F401  (Stream builds its side-band with header_table)
-from test_gpu_wave_stats import flipped_payload
+from test_gpu_wave_stats import FILTERS, flipped_payload, samples_of
 from wave_bins_reference import default_n_bins, wave_bins
+from wave_stats_reference import wave_stats_heads
 
 pytestmark = pytest.mark.gpu
 
@@ -276,3 +277,124 @@ def test_bins_verdicts(ctx, O):
         assert plan.wave_bins(good, bin, 0).shape == (plan.total_waves, 0, D.BIN_COLS)
     finally:
         plan.close()
+
+
+# --------------------------------------------------------------------------- 6. RiceParameter
+@pytest.mark.parametrize("m", [1, 2, 64, 32768])
+def test_bins_rice_parameters(ctx, O, m):
+    """The lane kernel's code-length arithmetic at the ends of k and beside them (every other cell of this module is m = 8):
+    the shape and the data of test_gpu_wave_stats.py::test_stats_rice_parameters."""
+    Ns, Ls = [65 * 300] * 2, [300] * 2
+    for sigma in (10, 400):
+        x = np.random.default_rng(m + sigma).normal(0, sigma, sum(Ns)).astype(np.int16)
+        st = Stream(ctx, O, x, Ns, Ls, m)
+        try:
+            start = torch.from_numpy(np.random.default_rng(m).integers(-50, 351, st.plan.total_waves)).to(ctx.device)
+            for bin in (16, 17, 250):
+                full = default_n_bins(Ns, Ls, bin)
+                for origin in (None, start):
+                    check(ctx, st, x, bin, None, origin, 0, what=(m, sigma))
+                    check(ctx, st, x, bin, max(full * 2 // 5, 1), origin, 0, what=(m, sigma))  # (stops mid-waveform)
+        finally:
+            st.plan.close()
+
+
+# --------------------------------------------------------------------------- 7. the serial kernel under every kind of filter
+@pytest.mark.parametrize("fname", list(FILTERS))
+def test_bins_serial_filters(ctx, O, fname):
+    """k_wave_bins_serial under a lead of -1, a lead that divides (held to the oracle's DECODE of its stream), three, five and
+    64 taps."""
+    taps = FILTERS[fname]
+    Ns, Ls = [65 * 300] * 2, [300] * 2
+    x = np.random.default_rng(len(taps)).normal(0, 10, sum(Ns)).astype(np.int16)
+    st = Stream(ctx, O, x, Ns, Ls, 8, taps)
+    try:
+        y = samples_of(O, st, x, 8, taps)
+        start = torch.from_numpy(np.random.default_rng(14).integers(-50, 351, st.plan.total_waves)).to(ctx.device)
+        for bin in (1, 64, 300):
+            full = default_n_bins(Ns, Ls, bin)
+            check(ctx, st, y, bin, None, None, 0, what=fname)
+            check(ctx, st, y, bin, full + 5, start, -7, what=fname)
+            check(ctx, st, y, bin, max(full * 2 // 5, 1), start, 0, what=fname)
+    finally:
+        st.plan.close()
+
+
+# --------------------------------------------------------------------------- 8. waveforms of one or two groups
+SHORT_LS = (1, 15, 16, 17, 31, 32, 33)
+
+
+def test_bins_short_waveforms(ctx, O):
+    """Waveforms that are a first group alone, a first and a last, and one unmasked group between them: a chunk per length, 70
+    waveforms each (a wavefront and a partial one) with a shorter last one wherever a length has one; then the batch of one
+    sample."""
+    Ls = list(SHORT_LS)
+    Ns = [69 * L + max(1, L // 2) for L in Ls]
+    x = np.random.default_rng(15).normal(0, 400, sum(Ns)).astype(np.int16)
+    st = Stream(ctx, O, x, Ns, Ls, 8)
+    try:
+        assert st.plan.total_waves == 70 * len(Ls) and int(st.length[-1]) == 16
+        rng = np.random.default_rng(16)
+        per_wave_L = np.array(Ls, np.int64)[st.chunk]
+        start = torch.from_numpy(rng.integers(-20, per_wave_L + 21)).to(ctx.device)
+        for bin in (1, 16, 17):
+            full = default_n_bins(Ns, Ls, bin)
+            check(ctx, st, x, bin, None, None, 0, what="short")
+            check(ctx, st, x, bin, full + 2, start, 0, what="short")
+            check(ctx, st, x, bin, max(full * 2 // 5, 1), start, -3, what="short")
+    finally:
+        st.plan.close()
+    x = np.array([-123], np.int16)
+    st = Stream(ctx, O, x, [1], [0], 8)
+    try:
+        for bin in (1, 16, 17):
+            check(ctx, st, x, bin, None, None, 0, what="one sample")
+            check(ctx, st, x, bin, 3, torch.tensor([-1], dtype=torch.int64, device=ctx.device), 0, what="one sample")
+    finally:
+        st.plan.close()
+
+
+# --------------------------------------------------------------------------- 9. a waveform that becomes wide in its middle
+PLATEAU = 48
+PLATEAU_VALUES = (16383, 16384, -16384, -32768, 20000)  # the first stays narrow: 16 x 16383^2 < 2^32
+PLATEAU_STARTS = (5, 16, 23, 160, 167, 650)  # in the masked first group; group-aligned; inside a group; reaching the masked last group
+WIDE_L = 700
+
+
+def plateau_rows():
+    """int16 [30, 700]: quiet rows (sigma 10), each with one plateau of 48 samples -- every value at every start."""
+    rng = np.random.default_rng(17)
+    x = rng.normal(0, 10, (len(PLATEAU_VALUES) * len(PLATEAU_STARTS), WIDE_L)).astype(np.int16)
+    for r in range(x.shape[0]):
+        s = PLATEAU_STARTS[r % len(PLATEAU_STARTS)]
+        x[r, s:s + PLATEAU] = PLATEAU_VALUES[r // len(PLATEAU_STARTS)]
+    return x
+
+
+def test_bins_and_stats_narrow_to_wide(ctx, O):
+    """The sticky `narrow` flag of k_wave_bins and k_wave_stats: while it holds, a group's sixteen squares are summed in 32
+    bits.  Every row here starts quiet and meets a plateau later; at +-16384 sixteen squares sum to exactly 2^32, which a
+    32-bit chain returns as 0.  The 16383 rows are the control: they must stay on the 32-bit chain and be right."""
+    x = plateau_rows()
+    W, L = x.shape
+    # the case proves something only if a wide row holds a whole 16-aligned group whose squares reach 2^32, and a narrow row none
+    sq = (x.astype(np.int64) ** 2)[:, :L // 16 * 16].reshape(W, -1, 16).sum(axis=2)
+    wide = np.repeat(np.array([abs(v) > 16383 for v in PLATEAU_VALUES]), len(PLATEAU_STARTS))
+    assert ((sq >= 1 << 32).any(axis=1) == wide).all() and wide.sum() == 4 * len(PLATEAU_STARTS)
+    assert (sq[np.repeat(np.array([abs(v) == 16384 for v in PLATEAU_VALUES]), len(PLATEAU_STARTS))] == 1 << 32).sum() >= 2 * 2 * len(PLATEAU_STARTS)
+    Ns, Ls = [W * L], [L]
+    st = Stream(ctx, O, x.reshape(-1), Ns, Ls, 8)
+    try:
+        start = torch.from_numpy(np.random.default_rng(18).integers(-40, L, W)).to(ctx.device)
+        for bin in (16, 17, 64, 250):
+            check(ctx, st, x.reshape(-1), bin, None, None, 0, what="plateaus")
+            check(ctx, st, x.reshape(-1), bin, None, start, 0, what="plateaus")
+        want = torch.from_numpy(wave_stats_heads(x.reshape(-1), Ns, Ls, [100])[0]).to(ctx.device)
+        for sideband in (False, True):
+            got = st.plan.wave_stats(st.enc, head=100, wave_words=st.table if sideband else None)
+            assert st.plan.last_decode_path() == D.PATH_STATS and st.plan.last_stats_form() == D.STATS_FORM_LANES, sideband
+            if not torch.equal(got, want):
+                g = int(torch.nonzero((got != want).any(dim=1)).flatten()[0])
+                raise AssertionError(("wave_stats", sideband, f"row {g}", got[g].tolist(), want[g].tolist()))
+    finally:
+        st.plan.close()
