@@ -31,11 +31,7 @@
 
 namespace drx {
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s16x2 as_pair(uint32_t v) { return __builtin_bit_cast(s16x2, v); }
-__device__ __forceinline__ uint32_t as_word(s16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-constexpr int32_t kNarrow = 16383;  // sixteen squares of samples within +-kNarrow sum to less than 2^32 (as in drx_stats.hip)
-static_assert(16ll * kNarrow * kNarrow < (1ll << 32), "a narrow group's sum of squares fits 32 bits");
+// (s16x2, as_pair(), as_word(), kNarrow: drx_lane_stream.h, as in drx_stats.hip)
 constexpr uint32_t kNoBorder = 0xffffffffu;  // (a waveform has fewer than 2^31 samples)
 constexpr uint32_t kMnId = 0x7fff7fffu, kMxId = 0x80008000u;  // the packed identities of min and max
 
@@ -89,7 +85,8 @@ __device__ __forceinline__ void bins_border(BinCursor &c, uint32_t bin, uint32_t
 }
 
 // a bin's row: four int64, by 16-byte stores where the row allows them, by 8-byte stores otherwise (the ABI asks 8-byte
-// alignment of d_out; rows are 32 bytes, so a waveform's rows are aligned alike)
+// alignment of d_out; rows are 32 bytes, so a waveform's rows are aligned alike).  Not store_i64_row() (drx_device.h): through
+// it the two sign extensions move in front of the branch and k_wave_bins is no longer the kernel that was measured
 __device__ __forceinline__ void store_bin(int64_t *__restrict__ rows, bool vec, uint32_t b, int64_t sum, uint64_t sq, int32_t mn, int32_t mx) {
     int64_t *row = rows + (uint64_t)b * (uint64_t)DRX_BIN_COLS;
     static_assert(DRX_BIN_SUM == 0 && DRX_BIN_SUMSQ == 1 && DRX_BIN_MIN == 2 && DRX_BIN_MAX == 3 && DRX_BIN_COLS == 4, "the row's order");
@@ -177,15 +174,7 @@ __global__ __launch_bounds__(64) void k_wave_bins(Geom G, const uint32_t *__rest
         group_refill();
         if (wide && i != 0u && i + (uint32_t)GS <= len) {
             // ---- the unmasked group: eight pairs, two samples per ring access
-            uint32_t pr[GS / 2];  // the group's samples, two to a register (the earlier one in the low half)
-#pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                LANE_PAIR(z1, z2)
-                acc += (int32_t)(z1 >> 1) ^ -(int32_t)(z1 & 1u);
-                const uint32_t a1 = (uint32_t)acc;
-                acc += (int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u);
-                pr[u / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u);  // low halves of the two running sums
-            }
+            LANE_GROUP_PAIRS(acc, pr, 0u)  // the group's samples, two to a register (the earlier one in the low half)
             const uint32_t s = c.nb - i;  // (every border in front of i has been passed: nb >= i)
             if (s >= (uint32_t)GS) {
                 // ---- no border: the whole group belongs to the current stretch
@@ -297,6 +286,7 @@ __global__ __launch_bounds__(64) void k_wave_bins(Geom G, const uint32_t *__rest
 
 // General prediction filters: a lane per waveform, serial_wave() (global loads); the last 64 outputs of every
 // lane in an LDS column (taps <= DRX_MAX_TAPS = 64).  The same cursor, a border test per sample.
+// Not on serial_frame() (drx_lane_stream.h): through it this kernel was measured 0.4 % slower, profiles/serial_frame_refactor_ab.txt.
 __global__ __launch_bounds__(64) void k_wave_bins_serial(Geom G, const uint32_t *__restrict__ in, const uint64_t *__restrict__ wave_off,
                                                          const uint32_t *__restrict__ wave_words, uint64_t wf_base,
                                                          const int64_t *__restrict__ start, uint64_t start_stride, int64_t offset,

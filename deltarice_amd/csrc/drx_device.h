@@ -74,6 +74,24 @@ __device__ __forceinline__ uint32_t ffbh(uint32_t x) {
     return r;
 }
 
+// A row of N int64 results: by 16-byte stores where the caller found the row 16-byte aligned (vec), by 8-byte stores
+// otherwise (the ABI asks 8-byte alignment of such outputs)
+template <int N>
+__device__ __forceinline__ void store_i64_row(int64_t *__restrict__ row, bool vec, const int64_t (&v)[N]) {
+    static_assert(N % 2 == 0, "whole 16-byte stores");
+    if (vec) {
+        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+        typedef u32x4v __attribute__((address_space(1))) g_uint4;
+        g_uint4 *dst = (g_uint4 *)row;
+#pragma unroll
+        for (int j = 0; j < N / 2; ++j)
+            dst[j] = (u32x4v){(uint32_t)v[2 * j], (uint32_t)((uint64_t)v[2 * j] >> 32), (uint32_t)v[2 * j + 1], (uint32_t)((uint64_t)v[2 * j + 1] >> 32)};
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) row[j] = v[j];
+    }
+}
+
 struct WaveRef {
     uint64_t chunk;       // chunk index
     uint64_t sample_off;  // first sample of this waveform in the raw batch

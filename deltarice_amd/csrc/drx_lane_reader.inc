@@ -14,6 +14,7 @@
 //   set_limits()                 once, in front of the loop over groups of kGS samples, i = 0, kGS, ...
 //   group_refill()               in front of every group
 //   LANE_PAIR(z1, z2)            two zig-zag values per ring access (an escape leaves 8 << 16 above its bit 15) ...
+//   LANE_GROUP_PAIRS(acc, pr, f) ... eight of those: an unmasked group's samples, packed into pr[kGS / 2] ...
 //   LANE_ONE(z)                  ... or the masked form's one
 //   round_end(i)                 behind every group
 //   LANE_MISSES_LAST_WORD()      the verdict of a lane that parsed its whole waveform
@@ -166,6 +167,18 @@ auto round_end = [&](uint32_t at) __attribute__((always_inline)) {
         asm("v_add3_u32 %0, %1, %2, %3" : "=v"(Q) : "v"(Q), "v"(nu1_), "v"(nu2_));         \
         z1 = (q1_ << kk1_) + __builtin_amdgcn_ubfe(winA_, nu1_, kk1_);                     \
         z2 = (q2_ << kk2_) + __builtin_amdgcn_ubfe(win2_, nu2_, kk2_);                     \
+    }
+// The unmasked group of the kernels that keep samples: eight pairs, two samples per ring access.  acc: the lane's running sum
+// of the deltas (int32_t, the sample in its low 16 bits).  Declares pr[kGS / 2]: the group's samples two to a register, the
+// earlier one in the low half, every register ^ flip (0u: the samples as they are).
+#define LANE_GROUP_PAIRS(acc, pr, flip)                                                                                          \
+    uint32_t pr[kGS / 2];                                                                                                        \
+    _Pragma("unroll") for (int u_ = 0; u_ < kGS; u_ += 2) {                                                                      \
+        LANE_PAIR(z1_, z2_)                                                                                                      \
+        acc += (int32_t)(z1_ >> 1) ^ -(int32_t)(z1_ & 1u);                                                                       \
+        const uint32_t a1_ = (uint32_t)acc;                                                                                      \
+        acc += (int32_t)(z2_ >> 1) ^ -(int32_t)(z2_ & 1u);                                                                       \
+        pr[u_ / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1_, 0x05040100u) ^ (flip); /* low halves of the two running sums */   \
     }
 // the masked form: one code per ring access (win == 0 only past the end of a corrupt stream)
 #define LANE_ONE(z)                                                                        \

@@ -1,10 +1,17 @@
 // drx_lane_stream.h -- the stream side of the kernels that read an encoded batch a LANE per waveform without decoding it to
-// memory: k_wave_stats (drx_stats.hip), k_decode_window (drx_window.hip), k_find_pulses (drx_pulses.hip) and the re-code
-// and re-filter kernels (drx_transcode.hip, drx_refilter.hip: their shared bodies are drx_recode.h).  The reader's constants, which waveform a lane takes (lane_wave()), and the serial parse of the
-// general prediction filters' kernels (serial_wave()); the reader itself -- the lane's LDS ring and its two extractions -- is
-// the text of drx_lane_reader.inc, included in each kernel's body.  What a kernel does with a group's sixteen samples stays in
-// its own file.  k_decode_lanes (drx_decode_kernels.hip) has a ring of its own: it carries the transposition buffer, the
-// start delay and the in-launch walkers.  Not installed.
+// memory.  Two families use it:
+//   the delta filter's tuned kernels, over the shared reader -- the lane's LDS ring and its two extractions, the text of
+//     drx_lane_reader.inc included in each kernel's body: k_wave_stats (drx_stats.hip), k_wave_bins (drx_bins.hip),
+//     k_decode_window (drx_window.hip), k_decode_windows and k_decode_windows_list (drx_windows.hip), k_find_pulses and
+//     k_find_pulses_list (drx_pulses.hip), k_recode_sizes and k_recode_pack (drx_transcode.hip), k_refilter_sizes and
+//     k_refilter_pack (drx_refilter.hip; the shared bodies of those four are drx_recode.h);
+//   the general prediction filters' serial kernels, over serial_wave(): k_wave_stats_serial, k_decode_windows_serial and
+//     k_select_serial (drx_select.hip) inside one frame, serial_frame(); k_wave_bins_serial, k_decode_window_serial,
+//     k_find_pulses_serial, k_refilter_sizes_serial and k_refilter_pack_serial with a frame of their own, for the reasons
+//     given at serial_frame().
+// Here: the reader's constants, which waveform a lane takes (lane_wave()), the packed-pair helpers, the serial parse and its
+// frame.  What a kernel does with its samples stays in its own file.  k_decode_lanes (drx_decode_kernels.hip) has a ring of its
+// own: it carries the transposition buffer, the start delay and the in-launch walkers.  Not installed.
 #ifndef DRX_LANE_STREAM_H
 #define DRX_LANE_STREAM_H
 
@@ -29,6 +36,13 @@ static_assert(kT % kGS == 0 && kRW - kLW >= kGS + 2, "round length / ring slack"
 // consecutive words: rows r + 1, r, r - 1).  A lane reads and writes its own column only.  The kernel declares
 // __shared__ uint32_t ring_all[kInRingWords] -- all the LDS the reader needs, 16 896 bytes -- and ring = ring_all + 64.
 constexpr int kInRingWords = (kRW + 2) * 64;
+
+// A group's samples two to a register (pr[] of LANE_GROUP_PAIRS, drx_lane_reader.inc), as the packed reductions take them
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ s16x2 as_pair(uint32_t v) { return __builtin_bit_cast(s16x2, v); }
+__device__ __forceinline__ uint32_t as_word(s16x2 v) { return __builtin_bit_cast(uint32_t, v); }
+constexpr int32_t kNarrow = 16383;  // sixteen squares of samples within +-kNarrow sum to less than 2^32
+static_assert(16ll * kNarrow * kNarrow < (1ll << 32), "a narrow group's sum of squares fits 32 bits");
 
 // Which waveform a lane takes.  Lanes map plainly, g = 64 * wavefront + lane (chunks need no alignment to wavefronts: a
 // wavefront's lanes may lie in two chunks, and the short last waveform of a chunk is a lane like any other); a ragged plan that
@@ -126,6 +140,47 @@ __device__ __forceinline__ uint64_t serial_wave(const Geom &G, const uint32_t *_
         have -= used;
     }
     return (32ull * wi - have + 31u) >> 5;
+}
+
+// The frame of a serial kernel: everything round serial_wave() but what the call does with a sample.  Lane j = 64 * (wf_base +
+// workgroup) + lane of the launch takes waveform g = j, or g = list[j], j < n_list, where the launch has a list (the waveforms
+// a block form lists; a caller's selection).  Nothing is followed into the stream once st->err is set -- whatever a walker
+// reported, the tables of a batch that failed validation are not valid -- and no table is indexed with a g outside the batch.
+// The filter's history, the last 64 outputs of every lane, is an LDS column here (8192 bytes; taps <= DRX_MAX_TAPS = 64).
+// What the call supplies:
+//   begin(g, r)   in front of the parse -- pads, empty rows, the lane's state; returns e, the samples to parse from the
+//                 waveform's first.  e == 0: the lane parses nothing, reads no header table entry and makes no verdict.
+//   sample(i, y)  the sample drx_decode writes, for i = 0 .. e - 1 in order
+//   end(g, r)     behind the parse and the verdict: the row or count store, a run still open closed at r.len
+// The verdict, once: a valid waveform's codes end inside its last payload word, so a lane that parsed to its waveform's end
+// asks words == n_i; one that stopped early asks only that its codes lay inside the payload, words <= n_i (nothing behind
+// its last code is looked at).
+// Not on this frame: k_refilter_sizes_serial (its lanes without a waveform stay for the wavefront's sums, and its sink reads the
+// history column) and k_refilter_pack_serial (no verdict of its own -- the sizes pass has made it -- and an OutRing beside the
+// column); k_wave_bins_serial, k_decode_window_serial and k_find_pulses_serial, which fit it and were measured 0.4, 0.9 and
+// 2.8 % slower through it (profiles/serial_frame_refactor_ab.txt: the same loop instructions at other addresses), so they
+// keep the bodies they had.  A new serial kernel starts on the frame.
+template <typename T, typename Begin, typename Sample, typename End>
+__device__ __forceinline__ void serial_frame(const Geom &G, const uint32_t *__restrict__ in, const uint64_t *__restrict__ wave_off,
+                                             const uint32_t *__restrict__ wave_words, uint64_t wf_base, const T *__restrict__ list,
+                                             uint64_t n_list, DevStatus *st, Begin &&begin, Sample &&sample, End &&end) {
+    __shared__ int16_t hist[64][64];  // [sample mod 64][lane]
+    const uint32_t lane = threadIdx.x;
+    uint64_t g = (wf_base + blockIdx.x) * 64u + lane;
+    if (st->err) return;
+    if (list) {
+        if (g >= n_list) return;
+        g = list[g];
+    }
+    if (g >= G.total_waves) return;
+    const WaveRef r = locate(G, g);
+    const uint32_t e = begin(g, r);
+    if (e) {
+        const uint32_t n = wave_words[g];
+        const uint64_t words = serial_wave(G, in + wave_off[g] + 1, n, e, &hist[0][lane], 64u, sample);
+        if (e == r.len ? words != n : words > n) atomicOr(&st->err, kErrCorrupt);
+    }
+    end(g, r);
 }
 
 }  // namespace drx

@@ -34,8 +34,6 @@
 
 namespace drx {
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
 // One polarity.  A sample y enters the state machine as v = y ^ flip, flip = 0 for positive polarity and -1 for negative:
 // ~y = -1 - y reverses the order of the int16 values without leaving them, so "y < t" is "v > -1 - t" and the minimum of a run
 // is the complement of the maximum of its v.  The lane's threshold tv is clamped so that it compares as an int32 with any
@@ -135,6 +133,7 @@ __global__ __launch_bounds__(64) void k_find_pulses_list(Geom G, const uint32_t 
 
 // General prediction filters: a lane per waveform, serial_wave() (global loads); the last 64 outputs of every
 // lane in an LDS column (taps <= DRX_MAX_TAPS = 64).
+// Not on serial_frame() (drx_lane_stream.h): through it this kernel was measured 2.8 % slower, profiles/serial_frame_refactor_ab.txt.
 __global__ __launch_bounds__(64) void k_find_pulses_serial(Geom G, const uint32_t *__restrict__ in,
                                                            const uint64_t *__restrict__ wave_off,
                                                            const uint32_t *__restrict__ wave_words, uint64_t wf_base,

@@ -45,18 +45,10 @@
         group_refill();
         if (i + (uint32_t)GS <= len) {
             // ---- the unmasked group: eight pairs, two samples per ring access
-            uint32_t pr[GS / 2];  // the group's v, two to a register (the earlier one in the low half)
+            LANE_GROUP_PAIRS(acc, pr, pm)  // the group's v, two to a register (the earlier one in the low half)
+            s16x2 gm = as_pair(pr[0]);
 #pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                LANE_PAIR(z1, z2)
-                acc += (int32_t)(z1 >> 1) ^ -(int32_t)(z1 & 1u);
-                const uint32_t a1 = (uint32_t)acc;
-                acc += (int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u);
-                pr[u / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u) ^ pm;  // low halves of the two running sums
-            }
-            s16x2 gm = __builtin_bit_cast(s16x2, pr[0]);
-#pragma unroll
-            for (int j = 1; j < GS / 2; ++j) gm = __builtin_elementwise_max(gm, __builtin_bit_cast(s16x2, pr[j]));
+            for (int j = 1; j < GS / 2; ++j) gm = __builtin_elementwise_max(gm, as_pair(pr[j]));
             const int32_t gmax = gm.x > gm.y ? (int32_t)gm.x : (int32_t)gm.y;
             if (P.open || gmax > P.tv) {
                 // the registers rotate: pr[0] is the pair in turn

@@ -8,8 +8,8 @@
 //                     method of k_decode_long (a lane per 16-word segment of a 1024-word block: guess, re-synchronise from
 //                     the predecessor's end until no start changes, prefix sums, emit), with the workgroup's barriers
 //                     and LDS exchanges replaced by what a single wavefront has: lock step, DPP scans, lane reads.
-//   k_select_serial   every other prediction filter: one LANE per selected waveform, the serial parse of drx_lane_stream.h
-//                     (serial_wave()) with the filter's history in LDS.  Correct, not tuned.
+//   k_select_serial   every other prediction filter: one LANE per selected waveform, the serial parse inside the serial
+//                     kernels' frame (serial_frame(), drx_lane_stream.h).  Correct, not tuned.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -181,26 +181,17 @@ __global__ __launch_bounds__(64) void k_decode_select(Geom G, const uint32_t *__
     }
 }
 
-// General prediction filters: a lane per selected waveform, serial_wave() (global loads, 2-byte stores); the
-// last 64 outputs of every lane in an LDS column (taps <= DRX_MAX_TAPS = 64).
+// General prediction filters: serial_frame() (drx_lane_stream.h) over the selection as its list -- lane e of the launch takes
+// waveform sel[e] (the host checked the list; never index the tables with anything else) and writes row e by 2-byte stores.
 __global__ __launch_bounds__(64) void k_select_serial(Geom G, const uint32_t *__restrict__ in,
                                                       const uint64_t *__restrict__ wave_off,
                                                       const uint32_t *__restrict__ wave_words,
                                                       const uint64_t *__restrict__ sel, uint64_t n_sel, DevStatus *st,
                                                       int16_t *__restrict__ out, uint64_t stride) {
-    __shared__ int16_t hist[64][64];  // [sample mod 64][lane]
-    const uint32_t lane = threadIdx.x;
-    const uint64_t e = (uint64_t)blockIdx.x * 64u + lane;
-    if (st->err) return;  // (as k_decode_select)
-    if (e >= n_sel) return;
-    const uint64_t g = sel[e];
-    if (g >= G.total_waves) return;
-    const WaveRef r = locate(G, g);
-    const uint32_t *s = in + wave_off[g] + 1;
-    const uint32_t n = wave_words[g];
-    int16_t *y = out + e * stride;
-    const uint64_t words = serial_wave(G, s, n, r.len, &hist[0][lane], 64u, [&](uint32_t i, int16_t v) __attribute__((always_inline)) { y[i] = v; });
-    if (r.len && words != n) atomicOr(&st->err, kErrCorrupt);
+    int16_t *const y = out + ((uint64_t)blockIdx.x * 64u + threadIdx.x) * stride;
+    serial_frame(
+        G, in, wave_off, wave_words, 0u, sel, n_sel, st, [](uint64_t, const WaveRef &r) { return r.len; },
+        [&](uint32_t i, int16_t v) __attribute__((always_inline)) { y[i] = v; }, [](uint64_t, const WaveRef &) {});
 }
 
 // A wavefront per entry up to kSelMaxGrid wavefronts (a selection of one launches one), which then stride over the list.

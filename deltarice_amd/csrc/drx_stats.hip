@@ -8,8 +8,8 @@
 //   k_wave_stats         delta filter: one LANE per waveform, 64 waveforms per wavefront, the stream side the shared reader's
 //                        (drx_lane_reader.inc): a lane starts at its first sample and stops behind its last, and
 //                        the reader's ring (16 896 bytes) is all the LDS there is.
-//   k_wave_stats_serial  every other prediction filter: one lane per waveform, the serial parse of the same header
-//                        (serial_wave()) with the filter's history in an LDS column.  Correct, not tuned.
+//   k_wave_stats_serial  every other prediction filter: one lane per waveform, the serial parse of the same header inside the
+//                        serial kernels' frame (serial_frame(), drx_lane_stream.h).  Correct, not tuned.
 //
 // Few long waveforms (the nEDM / NOPTREX shapes, the reference's default one waveform per chunk) under the delta filter do NOT
 // run here: a lane per waveform is 50-60 ns per sample and lane whatever else runs, with most of the chip idle (2048 waveforms of
@@ -28,29 +28,7 @@
 
 namespace drx {
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s16x2 as_pair(uint32_t v) { return __builtin_bit_cast(s16x2, v); }
-__device__ __forceinline__ uint32_t as_word(s16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-constexpr int32_t kNarrow = 16383;  // sixteen squares of samples within +-kNarrow sum to less than 2^32
-static_assert(16ll * kNarrow * kNarrow < (1ll << 32), "a narrow group's sum of squares fits 32 bits");
-
-// a lane's row: eight int64, by 16-byte stores where the caller's buffer allows them (a row is 64 bytes, so every row of a
-// 16-byte aligned buffer is), by 8-byte stores otherwise (the ABI asks 8-byte alignment of d_out)
-__device__ __forceinline__ void store_row(int64_t *__restrict__ out, uint64_t g, bool vec, const int64_t (&v)[DRX_STAT_COLS]) {
-    int64_t *row = out + g * (uint64_t)DRX_STAT_COLS;
-    if (vec) {
-        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-        typedef u32x4v __attribute__((address_space(1))) g_uint4;
-        g_uint4 *dst = (g_uint4 *)row;
-#pragma unroll
-        for (int j = 0; j < DRX_STAT_COLS / 2; ++j)
-            dst[j] = (u32x4v){(uint32_t)v[2 * j], (uint32_t)((uint64_t)v[2 * j] >> 32), (uint32_t)v[2 * j + 1], (uint32_t)((uint64_t)v[2 * j + 1] >> 32)};
-    } else {
-#pragma unroll
-        for (int j = 0; j < DRX_STAT_COLS; ++j) row[j] = v[j];
-    }
-}
-
+// (a lane's row, eight int64: store_i64_row() of drx_device.h; s16x2, as_pair(), as_word(), kNarrow: drx_lane_stream.h)
 // Lanes map by LANE_WAVE_G_ACTIVE_LEN (drx_lane_stream.h).  wf_base: first wavefront of this launch (a batch whose wavefronts one launch cannot carry goes
 // out in slices: for_wavefront_slices()).
 //
@@ -110,15 +88,7 @@ __global__ __launch_bounds__(64) void k_wave_stats(Geom G, const uint32_t *__res
         group_refill();
         if (i != 0u && i + (uint32_t)GS <= len && h - i >= (uint32_t)GS) {  // (h < i wraps: the window ended earlier)
             // ---- the unmasked group: eight pairs, two samples per ring access
-            uint32_t pr[GS / 2];  // the group's samples, two to a register (the earlier one in the low half)
-#pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                LANE_PAIR(z1, z2)
-                acc += (int32_t)(z1 >> 1) ^ -(int32_t)(z1 & 1u);
-                const uint32_t a1 = (uint32_t)acc;
-                acc += (int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u);
-                pr[u / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u);  // low halves of the two running sums
-            }
+            LANE_GROUP_PAIRS(acc, pr, 0u)  // the group's samples, two to a register (the earlier one in the low half)
             s16x2 nmn = rmn, nmx = rmx;
             int32_t gsum = 0, gsq = 0;
 #pragma unroll
@@ -199,11 +169,11 @@ __global__ __launch_bounds__(64) void k_wave_stats(Geom G, const uint32_t *__res
     if (h == len) { hsum = sum; hsq = sq; }  // the window holds the whole waveform
     if (len && LANE_MISSES_LAST_WORD()) atomicOr(&st->err, kErrCorrupt);
     const int64_t v[DRX_STAT_COLS] = {(int64_t)mn, (int64_t)amn, (int64_t)mx, (int64_t)amx, sum, (int64_t)sq, hsum, (int64_t)hsq};
-    store_row(out, g, ((uintptr_t)out & 15u) == 0, v);
+    const bool vec = ((uintptr_t)out & 15u) == 0;  // (in front of the row's address: the kernel keeps its instructions)
+    store_i64_row(out + g * (uint64_t)DRX_STAT_COLS, vec, v);
 }
 
-// General prediction filters: a lane per waveform, serial_wave() (global loads); the last 64 outputs of every
-// lane in an LDS column (taps <= DRX_MAX_TAPS = 64).
+// General prediction filters: serial_frame() (drx_lane_stream.h) with the same eight reductions, a sample at a time.
 // list != nullptr: the waveforms list[0 .. *n_list) instead of all of them (behind the block form, drx_stats_blocks.hip: the
 // list and its length are written on the device by the kernel in front; the launch is sized for the whole batch).
 __global__ __launch_bounds__(64) void k_wave_stats_serial(Geom G, const uint32_t *__restrict__ in,
@@ -211,35 +181,30 @@ __global__ __launch_bounds__(64) void k_wave_stats_serial(Geom G, const uint32_t
                                                           const uint32_t *__restrict__ wave_words, uint64_t wf_base,
                                                           uint32_t head_len, DevStatus *st, int64_t *__restrict__ out,
                                                           const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list) {
-    __shared__ int16_t hist[64][64];  // [sample mod 64][lane]
-    const uint32_t lane = threadIdx.x;
-    uint64_t g = (wf_base + blockIdx.x) * 64u + lane;
-    if (st->err) return;  // (as k_wave_stats)
-    if (list) {
-        if (g >= (uint64_t)*n_list) return;
-        g = list[g];
-    }
-    if (g >= G.total_waves) return;
-    const WaveRef r = locate(G, g);
-    const uint32_t *s = in + wave_off[g] + 1;
-    const uint32_t n = wave_words[g];
-    const uint32_t h = head_len < r.len ? head_len : r.len;
+    uint32_t h = 0;  // the head window ends in front of sample h
     int32_t mn = 0x7fffffff, mx = -0x7fffffff - 1;
     uint32_t amn = 0, amx = 0;
     int64_t sum = 0, hsum = 0;
     uint64_t sq = 0, hsq = 0;
-    const uint64_t words = serial_wave(G, s, n, r.len, &hist[0][lane], 64u, [&](uint32_t i, int16_t y16) __attribute__((always_inline)) {
-        if (i == h) { hsum = sum; hsq = sq; }
-        const int32_t y = y16;
-        sum += y;
-        sq += (uint64_t)(uint32_t)(y * y);
-        if (y < mn) { mn = y; amn = i; }
-        if (y > mx) { mx = y; amx = i; }
-    });
-    if (h == r.len) { hsum = sum; hsq = sq; }
-    if (r.len && words != n) atomicOr(&st->err, kErrCorrupt);
-    const int64_t v[DRX_STAT_COLS] = {(int64_t)mn, (int64_t)amn, (int64_t)mx, (int64_t)amx, sum, (int64_t)sq, hsum, (int64_t)hsq};
-    store_row(out, g, ((uintptr_t)out & 15u) == 0, v);
+    serial_frame(
+        G, in, wave_off, wave_words, wf_base, list, list ? (uint64_t)*n_list : 0u, st,
+        [&](uint64_t, const WaveRef &r) __attribute__((always_inline)) {
+            h = head_len < r.len ? head_len : r.len;
+            return r.len;
+        },
+        [&](uint32_t i, int16_t y16) __attribute__((always_inline)) {
+            if (i == h) { hsum = sum; hsq = sq; }
+            const int32_t y = y16;
+            sum += y;
+            sq += (uint64_t)(uint32_t)(y * y);
+            if (y < mn) { mn = y; amn = i; }
+            if (y > mx) { mx = y; amx = i; }
+        },
+        [&](uint64_t g, const WaveRef &r) __attribute__((always_inline)) {
+            if (h == r.len) { hsum = sum; hsq = sq; }
+            const int64_t v[DRX_STAT_COLS] = {(int64_t)mn, (int64_t)amn, (int64_t)mx, (int64_t)amx, sum, (int64_t)sq, hsum, (int64_t)hsq};
+            store_i64_row(out + g * (uint64_t)DRX_STAT_COLS, ((uintptr_t)out & 15u) == 0, v);
+        });
 }
 
 hipError_t launch_wave_stats(const StreamCall &c, void *d_blk, void *d_sacc, uint32_t head_len, int64_t *d_out, uint32_t *form_out) {

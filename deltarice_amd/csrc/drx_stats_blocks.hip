@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_stats_blocks_reset(uint64_t total_waves
     a[2] = a[3] = a[4] = a[5] = 0ull;
 }
 
-// A thread per waveform: its row from its accumulator (the stores of drx_stats.hip's store_row), or its place on the list of
+// A thread per waveform: its row from its accumulator (the stores of drx_stats.hip's rows), or its place on the list of
 // the waveforms that the lane kernel behind this one computes and judges.  all_listed: DRX_DBG_STATS_ALL_FALLBACK.
 __global__ __launch_bounds__(256) void k_stats_blocks_finish(uint64_t total_waves, const unsigned long long *__restrict__ acc,
                                                              const uint32_t *__restrict__ fail, const uint32_t *__restrict__ suspect,
@@ -83,18 +83,8 @@ __global__ __launch_bounds__(256) void k_stats_blocks_finish(uint64_t total_wave
     const int64_t v[DRX_STAT_COLS] = {(int64_t)(int32_t)(uint32_t)(kmin >> 32), (int64_t)(uint32_t)kmin,
                                       (int64_t)(int32_t)(uint32_t)(kmax >> 32), (int64_t)(0x7fffffffu - (uint32_t)kmax),
                                       (int64_t)a[2], (int64_t)a[3], (int64_t)a[4], (int64_t)a[5]};
-    int64_t *row = out + g * (uint64_t)DRX_STAT_COLS;
-    if (((uintptr_t)out & 15u) == 0) {  // a row is 64 bytes: every row of a 16-byte aligned buffer is aligned
-        typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-        typedef u32x4v __attribute__((address_space(1))) g_uint4;
-        g_uint4 *dst = (g_uint4 *)row;
-#pragma unroll
-        for (int j = 0; j < DRX_STAT_COLS / 2; ++j)
-            dst[j] = (u32x4v){(uint32_t)v[2 * j], (uint32_t)((uint64_t)v[2 * j] >> 32), (uint32_t)v[2 * j + 1], (uint32_t)((uint64_t)v[2 * j + 1] >> 32)};
-    } else {
-#pragma unroll
-        for (int j = 0; j < DRX_STAT_COLS; ++j) row[j] = v[j];
-    }
+    // (a row is 64 bytes: every row of a 16-byte aligned buffer is aligned)
+    store_i64_row(out + g * (uint64_t)DRX_STAT_COLS, ((uintptr_t)out & 15u) == 0, v);
 }
 
 // the plan's scratch of this form: u64 acc[W][6] | the fallback list

@@ -114,15 +114,7 @@ __global__ __launch_bounds__(64) void k_decode_window(Geom G, const uint32_t *__
         group_refill();
         if (i + (uint32_t)GS <= e) {
             // ---- the unmasked group: eight pairs, two samples per ring access
-            uint32_t pr[GS / 2];  // the group's samples, two to a register (the earlier one in the low half)
-#pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                LANE_PAIR(z1, z2)
-                acc += (int32_t)(z1 >> 1) ^ -(int32_t)(z1 & 1u);
-                const uint32_t a1 = (uint32_t)acc;
-                acc += (int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u);
-                pr[u / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u);  // low halves of the two running sums
-            }
+            LANE_GROUP_PAIRS(acc, pr, 0u)  // the group's samples, two to a register (the earlier one in the low half)
             if (i + (uint32_t)GS > s) {  // some of the group lies in the window
                 const bool last = i + 2u * (uint32_t)GS > e;  // the lane's last unmasked group: nobody takes its carry
                 if (i >= s + p) {
@@ -177,6 +169,7 @@ __global__ __launch_bounds__(64) void k_decode_window(Geom G, const uint32_t *__
 
 // General prediction filters: a lane per waveform, serial_wave() (global loads); the last 64 outputs of every
 // lane in an LDS column (taps <= DRX_MAX_TAPS = 64).  2-byte stores.
+// Not on serial_frame() (drx_lane_stream.h): through it this kernel was measured 0.9 % slower, profiles/serial_frame_refactor_ab.txt.
 __global__ __launch_bounds__(64) void k_decode_window_serial(Geom G, const uint32_t *__restrict__ in,
                                                              const uint64_t *__restrict__ wave_off,
                                                              const uint32_t *__restrict__ wave_words, uint64_t wf_base,

@@ -18,8 +18,9 @@
 //                            concerned, and every group of an UNSORTED list a scan of all live windows.
 //   k_decode_windows_list    the same kernel over a device list of waveforms: behind the block form (drx_windows_blocks.hip),
 //                            which lists the waveforms it flagged; their rows are written again, all of them, and judged here.
-//   k_decode_windows_serial  every other prediction filter: one lane per waveform, the serial parse of the same header
-//                            (serial_wave()) to e_g, with a sink that loops over the live windows.  Correct, not tuned.
+//   k_decode_windows_serial  every other prediction filter: one lane per waveform, the serial parse of the same header to e_g
+//                            inside the serial kernels' frame (serial_frame(), drx_lane_stream.h), with a sink that loops
+//                            over the live windows.  Correct, not tuned.
 //
 // Few long waveforms under the delta filter (the batches drx_wave_stats gives to its block form) take the block form of
 // drx_windows_blocks.hip: a workgroup per block of a waveform's stream, which puts its samples in order only where a window
@@ -86,32 +87,29 @@ __global__ __launch_bounds__(64) void k_decode_windows_list(Geom G, const uint32
 #include "drx_windows_lane_body.inc"
 }
 
-// General prediction filters: a lane per waveform, serial_wave() (global loads); the last 64 outputs of every
-// lane in an LDS column (taps <= DRX_MAX_TAPS = 64).  2-byte stores, a loop over the live windows per sample.
+// General prediction filters: serial_frame() (drx_lane_stream.h) to e_g behind the lane's prologue; 2-byte stores, a loop over
+// the live windows per sample.
 __global__ __launch_bounds__(64) void k_decode_windows_serial(Geom G, const uint32_t *__restrict__ in,
                                                               const uint64_t *__restrict__ wave_off,
                                                               const uint32_t *__restrict__ wave_words, uint64_t wf_base, WinList wl,
                                                               DevStatus *st) {
-    __shared__ int16_t hist[64][64];  // [sample mod 64][lane]
-    const uint32_t lane = threadIdx.x;
-    const uint64_t g = (wf_base + blockIdx.x) * 64u + lane;
-    if (st->err) return;  // (as k_decode_windows)
-    if (g >= G.total_waves) return;
-    const WaveRef r = locate(G, g);
-    uint32_t nlive;
+    uint64_t g = 0;
+    uint32_t len = 0, nlive = 0;
     bool sorted;
-    const uint32_t e = windows_prologue(wl, g, r.len, nlive, sorted);
-    if (!e) return;
-    const uint32_t *s = in + wave_off[g] + 1;
-    const uint32_t n = wave_words[g];
-    // the sample drx_decode writes; the payload words the codes took
-    const uint64_t words = serial_wave(G, s, n, e, &hist[0][lane], 64u, [&](uint32_t i, int16_t y) __attribute__((always_inline)) {
-        for (uint32_t p = 0; p < nlive; ++p) {
-            const Win w = window_at(wl.at(g, p), wl.width, r.len);
-            if (i >= w.s && i < w.e) wl.row(g, p)[(int64_t)w.pf + ((int64_t)i - (int64_t)w.s)] = y;
-        }
-    });
-    if (e == r.len ? words != n : words > n) atomicOr(&st->err, kErrCorrupt);
+    serial_frame(
+        G, in, wave_off, wave_words, wf_base, (const uint32_t *)nullptr, 0u, st,
+        [&](uint64_t g_, const WaveRef &r) __attribute__((always_inline)) {
+            g = g_;
+            len = r.len;
+            return windows_prologue(wl, g, len, nlive, sorted);
+        },
+        [&](uint32_t i, int16_t y) __attribute__((always_inline)) {
+            for (uint32_t p = 0; p < nlive; ++p) {
+                const Win w = window_at(wl.at(g, p), wl.width, len);
+                if (i >= w.s && i < w.e) wl.row(g, p)[(int64_t)w.pf + ((int64_t)i - (int64_t)w.s)] = y;
+            }
+        },
+        [](uint64_t, const WaveRef &) {});
 }
 
 hipError_t launch_decode_windows(const StreamCall &c, void *d_blk, void *d_wtab, const int64_t *d_start, uint64_t start_wave_stride,

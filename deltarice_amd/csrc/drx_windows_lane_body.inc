@@ -72,15 +72,7 @@
         group_refill();
         if (i + (uint32_t)GS <= e) {
             // ---- the unmasked group: eight pairs, two samples per ring access
-            uint32_t pr[GS / 2];  // the group's samples, two to a register (the earlier one in the low half)
-#pragma unroll
-            for (int u = 0; u < GS; u += 2) {
-                LANE_PAIR(z1, z2)
-                acc += (int32_t)(z1 >> 1) ^ -(int32_t)(z1 & 1u);
-                const uint32_t a1 = (uint32_t)acc;
-                acc += (int32_t)(z2 >> 1) ^ -(int32_t)(z2 & 1u);
-                pr[u / 2] = __builtin_amdgcn_perm((uint32_t)acc, a1, 0x05040100u);  // low halves of the two running sums
-            }
+            LANE_GROUP_PAIRS(acc, pr, 0u)  // the group's samples, two to a register (the earlier one in the low half)
             // a sorted list: one compare says that the group touches no window.  An unsorted one: every live window, every group.
             if (!sorted || i + (uint32_t)GS > cs) {
                 uint32_t q = sorted ? cur : 0u, s_ = cs, e_ = ce;

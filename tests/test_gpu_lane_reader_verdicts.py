@@ -4,8 +4,8 @@ drx_transcode, drx_transcode_filter.
 
 The shape is the smallest that reaches every branch of the reader: 2 chunks of 70 waveforms x 100 samples, m = 8 -- three
 wavefronts, the last partly filled, a wavefront whose lanes lie in two chunks, a masked last group (100 = 6 x 16 + 4) -- and
-the same ragged: chunk 2 with WaveformLength 37 and a last waveform of 11 samples (rag_order's wavefronts).  A third stream
-runs the serial kernels (a general prediction filter).
+the same ragged: chunk 2 with WaveformLength 37 and a last waveform of 11 samples (rag_order's wavefronts).  Both geometries
+run the serial kernels as well (a general prediction filter: csrc/drx_lane_stream.h's serial_frame()).
 
 One waveform's payload is made a word too SHORT (its last word cut: the codes end after it) or a word too LONG (a zero word
 appended: the codes end before it), its header word and the chunk offsets mended, so that every walk accepts the chain and it
@@ -34,6 +34,7 @@ SHAPES = {  # name -> (Ns, Ls, taps)
     "uniform": ([70 * 100] * 2, [100] * 2, None),
     "ragged": ([70 * 100, 69 * 37 + 11], [100, 37], None),
     "serial": ([70 * 100] * 2, [100] * 2, (1, -2, 1)),
+    "serial_ragged": ([70 * 100, 69 * 37 + 11], [100, 37], (1, -2, 1)),
 }
 # (chunk, waveform): an ordinary lane of the first wavefront, the two lanes either side of the chunk border, the batch's last
 # waveform (in the ragged shape the short one)
