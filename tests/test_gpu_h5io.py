@@ -137,3 +137,24 @@ def test_direct_path_with_unaligned_guarded_views(env, h5tool, tmp_path):
         h5io.read(ctx, str(f), "test", dst[g + off:g + off + n + extra])
         assert np.array_equal(dst[g + off:g + off + n].cpu().numpy(), x), off
         assert bool((dst[:g + off] == 0x5A5A).all()) and bool((dst[g + off + n:] == 0x5A5A).all()), off
+
+
+def test_write_to_a_dataset_that_cannot_be_created(env, h5tool, tmp_path):
+    """H5Dcreate2 refuses a name under a group that does not exist, with the encoders launched and the file created: the
+    context then writes and reads as before."""
+    import deltarice_amd as dr
+    ctx, h5io = env
+    x = np.random.default_rng(16).normal(0, 10, (16, 1000)).astype(np.int16)
+    xd = torch.from_numpy(x.reshape(-1)).to(ctx.device)
+    for rows in (16, 14):  # whole chunks; a padded last chunk
+        f = tmp_path / f"w{rows}.h5"
+        with pytest.raises(dr.DeltaRiceError) as e:
+            h5io.write(ctx, str(f), "nogroup/x", xd, rows, 1000, 4, 8, 1000)
+        assert e.value.status == 1
+        st = h5io.write(ctx, str(f), "test", xd, rows, 1000, 4, 8, 1000)
+        assert st["n_chunks"] == 4 and st["rows"] == rows
+        y = torch.full_like(xd, 0x5A5A)
+        h5io.read(ctx, str(f), "test", y)
+        assert torch.equal(y[:rows * 1000], xd[:rows * 1000]) and bool((y[rows * 1000:] == 0x5A5A).all())
+        h5tool("read", f, tmp_path / "back.bin")  # ... and the filter callback reads the file
+        assert np.array_equal(np.fromfile(tmp_path / "back.bin", np.int16), x.reshape(-1)[:rows * 1000])

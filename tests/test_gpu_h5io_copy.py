@@ -121,3 +121,56 @@ def test_copy_rows_refusals(env, h5tool, tmp_path):
     h5io.copy_rows(ctx, str(good), "test", [5, 1, 5], str(tmp_path / "out.h5"), dst_name="picked", chunk_rows=2)
     st = h5io.copy_rows(ctx, str(good), "test", [5, 1], str(tmp_path / "out2.h5"))  # None: the source's 4 rows, but only 2 exist
     assert st["chunk_rows"] == 2 and st["rows"] == 2
+
+
+def check_small_copy(ctx, h5io, h5tool, h5info, tmp_path, src, x, sel, dcr, dst):
+    """what check_copies holds a copy to, for the rows sel of small_file's dataset in chunks of dcr rows"""
+    from oracle import oracle as O
+    st = h5io.copy_rows(ctx, str(src), "test", sel, str(dst), chunk_rows=dcr)
+    assert st["n_chunks"] == len({r // 4 for r in sel}) and st["rows"] == len(sel) and st["chunk_rows"] == dcr
+    want = x[np.array(sel)]
+    y = torch.empty(want.size, dtype=torch.int16, device=ctx.device)
+    h5io.read(ctx, str(dst), "test", y)
+    assert np.array_equal(y.cpu().numpy().reshape(want.shape), want)
+    n_dst = int(h5tool("chunks", dst, tmp_path / "dst").stdout)
+    assert n_dst == -(-len(sel) // dcr)
+    padded = np.zeros((n_dst * dcr, 1000), np.int16)
+    padded[:len(sel)] = want
+    for c in range(n_dst):
+        got = np.fromfile(f"{tmp_path}/dst.{c}", np.uint32)
+        assert got.tobytes() == O.encode_chunk(padded[c * dcr:(c + 1) * dcr], (8, 500)).tobytes(), c
+    a, b = h5info(src, "test").split(" | "), h5info(dst, "test").split(" | ")
+    assert a[1:] == b[1:]
+    assert b[0].split() == [str(len(sel)), "1000", str(dcr), "1000"] + a[0].split()[4:]
+
+
+def test_copy_rows_to_a_dataset_that_cannot_be_created(env, h5tool, h5info, tmp_path):
+    """H5Dcreate2 refuses a name under a group that does not exist: by then the destination file has been created."""
+    import deltarice_amd as dr
+    from test_gpu_h5io_rows import small_file
+    ctx, h5io = env
+    src, x = small_file(h5tool, tmp_path)
+    before = src.read_bytes()
+    dst = tmp_path / "copy.h5"
+    for sel, dcr in (([5, 1, 9, 9], 2), ([5, 1, 9], 2)):  # whole chunks; a padded last chunk
+        with pytest.raises(dr.DeltaRiceError) as e:
+            h5io.copy_rows(ctx, str(src), "test", sel, str(dst), dst_name="nogroup/x", chunk_rows=dcr)
+        assert e.value.status == 1 and not dst.exists()
+        assert src.read_bytes() == before
+        check_small_copy(ctx, h5io, h5tool, h5info, tmp_path, src, x, sel, dcr, dst)  # the same context, the same file name
+        dst.unlink()
+
+
+def test_copy_rows_out_of_a_damaged_chunk(env, h5tool, h5info, tmp_path):
+    import deltarice_amd as dr
+    from test_gpu_h5io_rows import small_file
+    ctx, h5io = env
+    src, x = small_file(h5tool, tmp_path, damaged_chunk=2)  # rows 8 .. 11
+    dst = tmp_path / "copy.h5"
+    with pytest.raises(dr.DeltaRiceError) as e:  # two whole chunks of sound rows, the padded last chunk out of the damaged one
+        h5io.copy_rows(ctx, str(src), "test", [0, 1, 4, 5, 9], str(dst), chunk_rows=2)
+    assert e.value.status == 4 and not dst.exists()
+    with pytest.raises(dr.DeltaRiceError) as e:  # ... and a whole chunk out of it
+        h5io.copy_rows(ctx, str(src), "test", [0, 9], str(dst), chunk_rows=2)
+    assert e.value.status == 4 and not dst.exists()
+    check_small_copy(ctx, h5io, h5tool, h5info, tmp_path, src, x, [0, 1, 4, 5, 13], 2, dst)  # the other chunks: neither read nor validated

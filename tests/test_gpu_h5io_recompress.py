@@ -69,6 +69,60 @@ def test_recompress_a_directly_written_file(env, h5tool, h5info, tmp_path):  # n
     assert e.value.status == 1 and not (tmp_path / "bad.h5").exists()
 
 
+def test_recompress_to_a_dataset_that_cannot_be_created(env, h5tool, h5info, tmp_path):  # noqa: F811
+    """H5Dcreate2 refuses a name under a group that does not exist: by then the destination file has been created."""
+    import deltarice_amd as dr
+    from test_gpu_h5io_rows import small_file
+    ctx, h5io = env
+    src, x = small_file(h5tool, tmp_path)
+    before = src.read_bytes()
+    for rice_m, tag in ((16, "m16"), (None, "best")):
+        dst = tmp_path / f"re_{tag}.h5"  # (the file check_recompressed then writes)
+        with pytest.raises(dr.DeltaRiceError) as e:
+            h5io.recompress(ctx, str(src), "test", str(dst), dst_name="nogroup/x", rice_m=rice_m)
+        assert e.value.status == 1 and not dst.exists()
+        assert src.read_bytes() == before
+        check_recompressed(ctx, h5io, h5tool, h5info, tmp_path, src, x, 4, (8, 500), rice_m, tag)
+
+
+def test_recompress_a_damaged_chunk(env, h5tool, h5info, tmp_path):  # noqa: F811
+    import deltarice_amd as dr
+    from test_gpu_h5io_rows import small_file
+    ctx, h5io = env
+    src, _ = small_file(h5tool, tmp_path, damaged_chunk=2)
+    for kw in ({"rice_m": 16}, {"rice_m": None}, {"rice_m": 16, "taps": (1, -1, 1, -1)}):
+        with pytest.raises(dr.DeltaRiceError) as e:
+            h5io.recompress(ctx, str(src), "test", str(tmp_path / "re.h5"), **kw)
+        assert e.value.status == 4 and not (tmp_path / "re.h5").exists(), kw
+    good, x = small_file(h5tool, tmp_path, name="sound.h5")  # the context after the refusals
+    check_recompressed(ctx, h5io, h5tool, h5info, tmp_path, good, x, 4, (8, 500), 32, "after")
+
+
+def test_recompress_a_dataset_stored_with_default_options(env, h5tool, h5info, tmp_path):  # noqa: F811
+    """No cd_values at all (RiceParameter 8, the whole chunk one waveform): the new dataset names its RiceParameter alone."""
+    from oracle import oracle as O
+    ctx, h5io = env
+    x = np.random.default_rng(5).normal(0, 40, (16, 1000)).astype(np.int16)
+    raw, src, dst = tmp_path / "raw.bin", tmp_path / "default.h5", tmp_path / "re.h5"
+    x.tofile(raw)
+    h5tool("write", src, raw, 16, 1000, 4)
+    a = h5info(src, "test").split(" | ")
+    assert a[1].split()[2:] == ["0"]
+    sizes = [sum(O.encode_chunk(x[c * 4:(c + 1) * 4], (1 << k,)).size for c in range(4)) for k in range(16)]
+    m = 1 << int(np.argmin(sizes))
+    assert m != 8  # (sigma 40: the default is not the best)
+    st = h5io.recompress(ctx, str(src), "test", str(dst))
+    assert st["n_chunks"] == 4 and st["rows"] == 16 and st["chunk_rows"] == 4 and st["raw_bytes"] == x.nbytes
+    b = h5info(dst, "test").split(" | ")
+    assert a[0] == b[0] and b[1].split() == a[1].split()[:2] + ["1", str(m)]
+    assert int(h5tool("chunks", dst, tmp_path / "dst").stdout) == 4
+    for c in range(4):
+        assert np.fromfile(f"{tmp_path}/dst.{c}", np.uint32).tobytes() == O.encode_chunk(x[c * 4:(c + 1) * 4], (m,)).tobytes(), c
+    y = torch.empty(x.size, dtype=torch.int16, device=ctx.device)
+    h5io.read(ctx, str(dst), "test", y)
+    assert y.cpu().numpy().tobytes() == x.tobytes()
+
+
 def test_recompress_keeps_a_general_filter(env, h5tool, h5info, tmp_path):  # noqa: F811
     ctx, h5io = env
     rows, cols, crows, taps = 330, 3000, 50, (1, -1, 1, -1)  # two waveforms per row, a padded last chunk

@@ -73,3 +73,19 @@ def test_refilter_a_delta_dataset(env, h5tool, h5info, tmp_path):  # noqa: F811
         with pytest.raises(dr.DeltaRiceError) as e:
             h5io.recompress(ctx, str(f), "test", str(tmp_path / "bad.h5"), taps=bad)
         assert e.value.status == 1 and not (tmp_path / "bad.h5").exists()
+
+
+def test_refilter_to_a_dataset_that_cannot_be_created(env, h5tool, h5info, tmp_path):  # noqa: F811
+    """H5Dcreate2 refuses a name under a group that does not exist: by then the destination file has been created."""
+    import deltarice_amd as dr
+    from test_gpu_h5io_rows import small_file
+    ctx, h5io = env
+    src, x = small_file(h5tool, tmp_path)
+    before = src.read_bytes()
+    for rice_m, tag in ((16, "m16"), (None, "best")):
+        dst = tmp_path / f"re_{tag}.h5"  # (the file check_refiltered then writes)
+        with pytest.raises(dr.DeltaRiceError) as e:
+            h5io.recompress(ctx, str(src), "test", str(dst), dst_name="nogroup/x", rice_m=rice_m, taps=FIR4)
+        assert e.value.status == 1 and not dst.exists()
+        assert src.read_bytes() == before
+        check_refiltered(ctx, h5io, h5tool, h5info, tmp_path, src, x, 4, 500, FIR4, rice_m, tag)

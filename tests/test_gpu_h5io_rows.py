@@ -43,6 +43,23 @@ def row_sets(rows, crows, rng):
     return {"one": one, "three": three, "all": every}
 
 
+def small_file(h5tool, tmp_path, name="small.h5", damaged_chunk=None):
+    """16 x 1000 int16 in chunks of 4 rows, RiceParameter 8, WaveformLength 500, its four chunks the CPU oracle's bytes
+    (H5Dwrite_chunk) -> (path, x).  damaged_chunk: that chunk with ONE word changed, the length header n_i of its second
+    waveform plus one (tests/call_sequences.py's "n_plus"): the header chain no longer ends at the chunk's end, which every
+    call that walks the chunk must answer with DRX_ERR_CORRUPT (a changed code word may decode to anything)."""
+    from oracle import oracle as O
+    x = np.random.default_rng(16).normal(0, 10, (16, 1000)).astype(np.int16)
+    prefix = tmp_path / (name + ".chunk")
+    for c in range(4):
+        w = O.encode_chunk(x[c * 4:(c + 1) * 4], (8, 500))
+        if c == damaged_chunk:
+            w[1 + int(w[1]) + 1] += 1
+        w.tofile(f"{prefix}.{c}")
+    h5tool("writeraw", tmp_path / name, 16, 1000, 4, 8, 500, prefix)
+    return tmp_path / name, x
+
+
 def check_file(ctx, h5io, h5tool, tmp_path, path, x, crows):
     rows, cols = x.shape
     n = int(h5tool("chunks", path, tmp_path / "stored").stdout)
@@ -108,3 +125,17 @@ def test_read_rows_needs_whole_waveforms_per_row(env, h5tool, tmp_path):
         y = torch.empty(16 * 1000, dtype=torch.int16, device=ctx.device)
         h5io.read(ctx, str(f), "test", y)  # the whole-dataset path reads such a file
         assert np.array_equal(y.cpu().numpy(), x.reshape(-1))
+
+
+def test_read_and_read_rows_of_a_damaged_chunk(env, h5tool, tmp_path):
+    import deltarice_amd as dr
+    ctx, h5io = env
+    f, x = small_file(h5tool, tmp_path, damaged_chunk=2)  # rows 8 .. 11
+    y = torch.empty(x.size, dtype=torch.int16, device=ctx.device)
+    for call in (lambda: h5io.read(ctx, str(f), "test", y), lambda: h5io.read_rows(ctx, str(f), "test", [1, 9])):
+        with pytest.raises(dr.DeltaRiceError) as e:
+            call()
+        assert e.value.status == 4
+    sel = [15, 0, 7, 12, 0]  # the other chunks are not validated: their rows are delivered
+    got, st = h5io.read_rows(ctx, str(f), "test", sel)
+    assert np.array_equal(got.cpu().numpy(), x[sel]) and st["n_chunks"] == 3
