@@ -8,6 +8,7 @@ parsed at src/deltaRice.c:248-291): ``(RiceParameter[, WaveformLength[, nTaps, t
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -20,16 +21,49 @@ from ._lib import DeltaRiceError, DrxOpts
 H5FILTER = 32025  # H5Z_FILTER_DELTARICE (reference src/deltaRice.h:7)
 
 
+def _cd_values(opts: Sequence[int]):
+    """compression_opts as the cd_values array the library takes beside len(opts)"""
+    return (C.c_uint * max(len(opts), 1))(*[int(v) & 0xFFFFFFFF for v in opts])
+
+
 def parse_opts(opts: Sequence[int] = ()) -> DrxOpts:
     """compression_opts -> parsed options; raises DeltaRiceError like the reference rejects
     (stderr + failure, src/deltaRice.c:114-136)."""
     lib = _lib.load()
-    cd = (C.c_uint * max(len(opts), 1))(*[int(v) & 0xFFFFFFFF for v in opts])
     o = DrxOpts()
-    st = lib.drx_parse_cd_values(len(opts), cd, C.byref(o))
+    st = lib.drx_parse_cd_values(len(opts), _cd_values(opts), C.byref(o))
     if st != _lib.DRX_OK:
         raise DeltaRiceError(st, f"compression_opts={tuple(opts)}")
     return o
+
+
+# The scalar arguments of the stream calls, by the type the library takes them as: int(v), or DRX_ERR_ARG naming it.
+def _uint32(v, name: str, least: int = 0) -> int:
+    v = int(v)
+    if not least <= v < 1 << 32:
+        raise DeltaRiceError(1, f"{name}: {v} is not a uint32" + (f" of at least {least}" if least else ""))
+    return v
+
+
+def _int16(v, name: str) -> int:
+    v = int(v)
+    if not -32768 <= v <= 32767:
+        raise DeltaRiceError(1, f"{name}: {v} is not an int16")
+    return v
+
+
+def _int64(v, name: str) -> int:
+    v = int(v)
+    if not -(1 << 63) <= v < 1 << 63:
+        raise DeltaRiceError(1, f"{name}: {v} is not an int64")
+    return v
+
+
+def _stride(t: torch.Tensor, d: int) -> Optional[int]:
+    """The element stride of dimension d as the library takes one: positive, or None; where the dimension has no second entry
+    to step to, any stride will do, and one below 1 is passed as 1."""
+    s = int(t.stride(d))
+    return s if s >= 1 else (1 if t.shape[d] <= 1 else None)
 
 
 def _is_delta(o: DrxOpts) -> bool:
@@ -147,13 +181,7 @@ class Gathered:
 
     def plan(self, ctx: "Context") -> "Plan":
         """The plan of the result: its own geometry, the source's RiceParameter and filter."""
-        N, L = self.chunk_samples, self.wave_lens
-        if N.size == 0:
-            raise DeltaRiceError(1, "an empty selection has no plan")
-        if (N == N[0]).all() and (L == L[0]).all():
-            ftaps = (len(self.taps),) + tuple(int(t) & 0xFFFFFFFF for t in self.taps) if self.taps else ()
-            return ctx.plan_uniform(int(N.size), int(N[0]), (self.rice_m, int(L[0])) + ftaps)
-        return ctx.plan(N.tolist(), L.tolist(), self.rice_m, self.taps)
+        return _result_plan(ctx, self.chunk_samples, self.wave_lens, self.rice_m, self.taps, "an empty selection has no plan")
 
 
 @dataclass
@@ -169,13 +197,19 @@ class Transcoded:
 
     def plan(self, ctx: "Context") -> "Plan":
         """The plan of the result: the source's geometry, the result's filter and RiceParameter."""
-        N, L = np.asarray(self.chunk_samples, dtype=np.int64), np.asarray(self.wave_lens, dtype=np.int64)
-        if N.size == 0:
-            raise DeltaRiceError(1, "an empty batch has no plan")
-        if (N == N[0]).all() and (L == L[0]).all():
-            ftaps = (len(self.taps),) + tuple(int(t) & 0xFFFFFFFF for t in self.taps) if self.taps else ()
-            return ctx.plan_uniform(int(N.size), int(N[0]), (self.rice_m, int(L[0]) if L[0] > 0 else 0xFFFFFFFF) + ftaps)
-        return ctx.plan(N.tolist(), L.tolist(), self.rice_m, self.taps)
+        return _result_plan(ctx, self.chunk_samples, self.wave_lens, self.rice_m, self.taps, "an empty batch has no plan")
+
+
+def _result_plan(ctx: "Context", chunk_samples, wave_lens, rice_m: int, taps: Optional[tuple], empty: str) -> "Plan":
+    """The plan of a Gathered or a Transcoded: a uniform plan where every chunk is alike, a ragged one otherwise; a WaveformLength
+    of 0 or less is the whole chunk (a gathered batch has none); ``empty``: what to say of a batch without a chunk."""
+    N, L = np.asarray(chunk_samples, dtype=np.int64), np.asarray(wave_lens, dtype=np.int64)
+    if N.size == 0:
+        raise DeltaRiceError(1, empty)
+    if (N == N[0]).all() and (L == L[0]).all():
+        ftaps = (len(taps),) + tuple(int(t) & 0xFFFFFFFF for t in taps) if taps else ()
+        return ctx.plan_uniform(int(N.size), int(N[0]), (rice_m, int(L[0]) if L[0] > 0 else 0xFFFFFFFF) + ftaps)
+    return ctx.plan(N.tolist(), L.tolist(), rice_m, taps)
 
 
 class Context:
@@ -218,8 +252,7 @@ class Context:
         plan = Plan(self, h, np.full(n_chunks, chunk_samples, dtype=np.int64), np.full(n_chunks, L, dtype=np.int64))
         plan._rice_m = 1 << o.rice_k
         if not _is_delta(o):  # general prediction filter: GPU FIR/IIR kernels (correct, not tuned)
-            self._check(self.lib.drx_plan_set_filter(h, o.n_taps, o.taps))
-            plan._taps = tuple(int(o.taps[i]) for i in range(o.n_taps))
+            plan._taps = plan._apply_filter(o.taps[:o.n_taps])
         return plan
 
     def plan(self, chunk_samples: Sequence[int], wave_lens: Sequence[int], rice_m: int = 8,
@@ -237,20 +270,17 @@ class Context:
         plan = Plan(self, h, list(cs), list(wl))
         plan._rice_m = 1 << o.rice_k
         if taps is not None:
-            t = (C.c_int32 * len(taps))(*[int(v) for v in taps])
-            self._check(self.lib.drx_plan_set_filter(h, len(taps), t))
-            plan._taps = tuple(int(v) for v in t)
+            plan._taps = plan._apply_filter(taps)
         return plan
 
     def filter_chunk(self, data: bytes | np.ndarray, opts: Sequence[int] = (), reverse: bool = False) -> bytes:
         """One chunk through host memory with the H5Z callback's semantics
         (reference src/deltaRice.c:468-490): bytes in, bytes out."""
         raw = data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
-        cd = (C.c_uint * max(len(opts), 1))(*[int(v) & 0xFFFFFFFF for v in opts])
         out = C.c_void_p()
         nout = C.c_size_t()
         buf = C.create_string_buffer(raw, len(raw))
-        self._check(self.lib.drx_filter_chunk_host(self._h, 1 if reverse else 0, len(opts), cd, buf, len(raw),
+        self._check(self.lib.drx_filter_chunk_host(self._h, 1 if reverse else 0, len(opts), _cd_values(opts), buf, len(raw),
                                                    C.byref(out), C.byref(nout)))
         res = C.string_at(out.value, nout.value)
         C.CDLL(None).free(C.c_void_p(out.value))
@@ -282,15 +312,38 @@ class Plan:
     def set_filter(self, taps: Optional[Sequence[int]] = None):
         """Another prediction filter for this plan, which may have been used (waits for the context's stream); None or
         (1, -1): the delta filter again.  Gathered.plan() carries over the filter set here."""
-        t = (1, -1) if taps is None else tuple(int(v) for v in taps)
-        arr = (C.c_int32 * max(len(t), 1))(*t)
-        self.ctx._check(self.ctx.lib.drx_plan_set_filter(self._h, len(t), arr))
-        t = tuple(int(v) for v in arr[:len(t)])
+        t = self._apply_filter((1, -1) if taps is None else tuple(taps))
         self._taps = None if t == (1, -1) else t
+
+    def _apply_filter(self, taps: Sequence[int]) -> tuple:
+        """Sets the plan's prediction filter -> the taps as the library took them (int32), for the plan to remember"""
+        arr = (C.c_int32 * max(len(taps), 1))(*[int(v) for v in taps])
+        self.ctx._check(self.ctx.lib.drx_plan_set_filter(self._h, len(taps), arr))
+        return tuple(int(v) for v in arr[:len(taps)])
 
     def _dev_check(self, t: torch.Tensor, dtype, n: int, name: str):
         if t.device != self.ctx.device or t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
             raise DeltaRiceError(1, f"{name}: need contiguous {dtype} tensor of >= {n} elements on {self.ctx.device}")
+
+    def _out(self, t: Optional[torch.Tensor], dtype, shape, name: str) -> torch.Tensor:
+        """The caller's tensor, or a new one of ``shape`` (a tuple, or a count): contiguous, of ``dtype``, on the plan's device,
+        and holding what ``shape`` holds at least"""
+        shape = (shape,) if isinstance(shape, int) else shape
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=self.ctx.device)
+        self._dev_check(t, dtype, math.prod(shape), name)
+        return t
+
+    def _column(self, t: Optional[torch.Tensor], name: str):
+        """(pointer, element stride) of one int64 per waveform: a 1-D tensor of total_waves entries on the plan's device with any
+        positive stride (a column of wave_stats() as it is), the stride 1 where there is one waveform at most; None: (NULL, 0)"""
+        if t is None:
+            return None, 0
+        W = self.total_waves
+        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.device != self.ctx.device or t.dtype != torch.int64 or
+                t.shape[0] != W or _stride(t, 0) is None):
+            raise DeltaRiceError(1, f"{name}: need a 1-D int64 tensor of {W} entries on {self.ctx.device}")
+        return t.data_ptr(), (_stride(t, 0) if W > 1 else 1)
 
     # What the calls on an encoded batch share: the closed-plan check, the checks of the batch's tensors, the choice between
     # drx_X and drx_X_with_wave_words (the side-band table goes in front of the call's own arguments), and the blocking form.
@@ -313,22 +366,49 @@ class Plan:
                                                                       wave_words.data_ptr(), *args)
         self.ctx._check(st)
 
-    def _blocking(self, launch, *args, **kw):
+    def _blocking(self, launch, enc: "EncodedBatch", *args, **kw):
+        """launch -- an *_async entry -- on the batch ``enc`` behind the caller's stream, and finish()"""
+        self._open(launch.__name__.removesuffix("_async"))
         self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
-        r = launch(*args, **kw)
+        r = launch(enc.words, enc.chunk_word_off, *args, in_words=enc.total_words, **kw)
         self.finish()
         return r
+
+    def _batch_call(self, name: str, words, chunk_word_off, wave_words, in_words, own: tuple, out_words, out_chunk_word_off,
+                    n_out_chunks: int, out_wave_words, n_out_waves: int):
+        """The calls that write a new encoded batch, drx_<name>(the batch, *own, d_out, out_cap_words, d_out_chunk_word_off,
+        d_out_wave_words): out_words None or empty is the sizing call (NULL, 0); the two tables are the caller's or new ones."""
+        self._check_encoded(words, chunk_word_off, wave_words)
+        if out_words is not None:
+            self._dev_check(out_words, torch.int32, 0, "out_words")
+        off = self._out(out_chunk_word_off, torch.int64, n_out_chunks + 1, "out_chunk_word_off")
+        tab = self._out(out_wave_words, torch.int32, n_out_waves, "out_wave_words")
+        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
+        self._call_encoded(name, words, chunk_word_off, wave_words, in_words, *own, op, cap, off.data_ptr(),
+                           tab.data_ptr() if n_out_waves else None)
+        return out_words, off, tab
+
+    def _sized(self, launch, enc: "EncodedBatch", own: tuple, wave_words, out_words):
+        """launch -- gather_encoded_async, transcode_async or refilter_async, ``own`` its arguments in front of out_words -- into
+        the caller's out_words, or into an exact one: a sizing call, finish() for the words needed, and the call again, which
+        resumes from the first one's tables, all behind the caller's stream -> (EncodedBatch, out_wave_words)"""
+        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
+        off = tab = None
+        if out_words is None:
+            _, off, tab = launch(enc.words, enc.chunk_word_off, *own, None, enc.total_words, wave_words)
+            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
+        _, off, tab = launch(enc.words, enc.chunk_word_off, *own, out_words, enc.total_words, wave_words, off, tab)
+        return EncodedBatch(out_words, off, self.finish()), tab
 
     def encode_async(self, x: torch.Tensor, out_words: Optional[torch.Tensor] = None,
                      chunk_word_off: Optional[torch.Tensor] = None, capacity_words: Optional[int] = None):
         """Launches the encode on the context's stream; no host sync."""
+        self._open("encode")
         self._dev_check(x, torch.int16, self.total_samples, "x")
         if out_words is None:
             cap = self.max_encoded_words if capacity_words is None else int(capacity_words)
             out_words = torch.empty(cap, dtype=torch.int32, device=self.ctx.device)
-        if chunk_word_off is None:
-            chunk_word_off = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
+        chunk_word_off = self._out(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
         self.ctx._check(self.ctx.lib.drx_encode(self._h, x.data_ptr(), out_words.data_ptr(), out_words.numel(),
                                                 chunk_word_off.data_ptr()))
         return out_words, chunk_word_off
@@ -349,37 +429,29 @@ class Plan:
 
     def decode_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, out: Optional[torch.Tensor] = None,
                      in_words: Optional[int] = None):
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        if out is None:
-            out = torch.empty(self.total_samples, dtype=torch.int16, device=self.ctx.device)
-        self._dev_check(out, torch.int16, self.total_samples, "out")
-        n = words.numel() if in_words is None else int(in_words)
-        self.ctx._check(self.ctx.lib.drx_decode(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
-                                                out.data_ptr()))
+        self._open("decode")
+        return self._decode(words, chunk_word_off, None, out, in_words)
+
+    def _decode(self, words, chunk_word_off, wave_words, out, in_words):
+        self._check_encoded(words, chunk_word_off, wave_words)
+        out = self._out(out, torch.int16, self.total_samples, "out")
+        self._call_encoded("decode", words, chunk_word_off, wave_words, in_words, out.data_ptr())
         return out
 
     def decode_with_wave_words(self, words: torch.Tensor, chunk_word_off: torch.Tensor, wave_words: torch.Tensor,
                                out: Optional[torch.Tensor] = None, in_words: Optional[int] = None) -> torch.Tensor:
         """Decode with the encoder's n_i table as a side-band (int32 tensor [total_waves] on the device): no header walk.
         Launch only; finish() raises DRX_ERR_CORRUPT if the table does not belong to the stream."""
-        self._dev_check(words, torch.int32, 1, "words")
-        self._dev_check(chunk_word_off, torch.int64, self.n_chunks + 1, "chunk_word_off")
-        self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")
-        if out is None:
-            out = torch.empty(self.total_samples, dtype=torch.int16, device=self.ctx.device)
-        self._dev_check(out, torch.int16, self.total_samples, "out")
-        n = words.numel() if in_words is None else int(in_words)
-        self.ctx._check(self.ctx.lib.drx_decode_with_wave_words(self._h, words.data_ptr(), n, chunk_word_off.data_ptr(),
-                                                                wave_words.data_ptr(), out.data_ptr()))
-        return out
+        self._open("decode_with_wave_words")
+        self._dev_check(wave_words, torch.int32, self.total_waves, "wave_words")  # (this form has no walk to fall back to)
+        return self._decode(words, chunk_word_off, wave_words, out, in_words)
 
     def wave_words_device(self) -> torch.Tensor:
         """A device copy of n_i of every waveform from the last encode/decode (the side-band of decode_with_wave_words)."""
         return torch.from_numpy(self.wave_words().view(np.int32)).to(self.ctx.device)
 
     def decode(self, enc: EncodedBatch, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._blocking(self.decode_async, enc.words, enc.chunk_word_off, out, in_words=enc.total_words)
+        return self._blocking(self.decode_async, enc, out)
 
     def wave_lengths(self, wave_idx) -> np.ndarray:
         """len_i of the waveforms ``wave_idx`` names: WaveformLength, or less for the last waveform of a chunk."""
@@ -399,6 +471,7 @@ class Plan:
         samples per row are written; None: a new tensor whose stride is the plan's longest waveform, zero behind a shorter
         one.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).
         Launch only; finish() raises on device-side errors."""
+        self._open("decode_select")
         idx = _as_index_array(wave_idx)
         n_sel = int(idx.size)
         self._check_encoded(words, chunk_word_off, wave_words)
@@ -419,8 +492,7 @@ class Plan:
     def decode_select(self, enc: EncodedBatch, wave_idx, out: Optional[torch.Tensor] = None,
                       wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """decode_select_async on an EncodedBatch; waits, and raises like decode()."""
-        return self._blocking(self.decode_select_async, enc.words, enc.chunk_word_off, wave_idx, out, in_words=enc.total_words,
-                              wave_words=wave_words)
+        return self._blocking(self.decode_select_async, enc, wave_idx, out, wave_words=wave_words)
 
     def gather_encoded_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, wave_idx, chunk_waves: int,
                              out_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
@@ -431,22 +503,13 @@ class Plan:
         out_words None: the SIZING call, which writes the two tables only; finish() then returns the words needed.
         -> (out_words, out_chunk_word_off int64 [n_out_chunks + 1], out_wave_words int32 [n_sel]).  finish() raises on
         device-side errors (DRX_ERR_CAPACITY: nothing was written; DRX_ERR_CORRUPT: a touched chunk failed validation)."""
+        self._open("gather_encoded")
         idx = _as_index_array(wave_idx)
         n_sel, cw = int(idx.size), int(chunk_waves)
         n_out = -(-n_sel // cw) if cw > 0 else 0
-        self._check_encoded(words, chunk_word_off, wave_words)
-        if out_words is not None:
-            self._dev_check(out_words, torch.int32, 0, "out_words")
-        if out_chunk_word_off is None:
-            out_chunk_word_off = torch.empty(n_out + 1, dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(out_chunk_word_off, torch.int64, n_out + 1, "out_chunk_word_off")
-        if out_wave_words is None:
-            out_wave_words = torch.empty(n_sel, dtype=torch.int32, device=self.ctx.device)
-        self._dev_check(out_wave_words, torch.int32, n_sel, "out_wave_words")
-        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
-        self._call_encoded("gather_encoded", words, chunk_word_off, wave_words, in_words, idx.ctypes.data_as(C.POINTER(C.c_uint64)),
-                           n_sel, cw, op, cap, out_chunk_word_off.data_ptr(), out_wave_words.data_ptr() if n_sel else None)
-        return out_words, out_chunk_word_off, out_wave_words
+        return self._batch_call("gather_encoded", words, chunk_word_off, wave_words, in_words,
+                                (idx.ctypes.data_as(C.POINTER(C.c_uint64)), n_sel, cw), out_words, out_chunk_word_off, n_out,
+                                out_wave_words, n_sel)
 
     def gather_encoded(self, enc: EncodedBatch, wave_idx, chunk_waves: int, wave_words: Optional[torch.Tensor] = None,
                        out_words: Optional[torch.Tensor] = None) -> Gathered:
@@ -457,19 +520,13 @@ class Plan:
         DRX_ERR_CAPACITY if the result does not fit it.  Waits, and raises like decode()."""
         idx = _as_index_array(wave_idx)
         N, L = gather_geometry(self._chunk_samples, self._wave_lens, idx, chunk_waves)
-        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
         if idx.size == 0:
             off = torch.zeros(1, dtype=torch.int64, device=self.ctx.device)
             tab = torch.empty(0, dtype=torch.int32, device=self.ctx.device)
             out_words = torch.empty(0, dtype=torch.int32, device=self.ctx.device) if out_words is None else out_words
             return Gathered(EncodedBatch(out_words, off, 0), N, L, tab, self._rice_m, self._taps)
-        off = tab = None
-        if out_words is None:
-            _, off, tab = self.gather_encoded_async(enc.words, enc.chunk_word_off, idx, chunk_waves, None, enc.total_words, wave_words)
-            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
-        _, off, tab = self.gather_encoded_async(enc.words, enc.chunk_word_off, idx, chunk_waves, out_words, enc.total_words,
-                                                wave_words, off, tab)
-        return Gathered(EncodedBatch(out_words, off, self.finish()), N, L, tab, self._rice_m, self._taps)
+        res, tab = self._sized(self.gather_encoded_async, enc, (idx, chunk_waves), wave_words, out_words)
+        return Gathered(res, N, L, tab, self._rice_m, self._taps)
 
     def wave_stats_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, head: int = 0,
                          out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None,
@@ -480,13 +537,9 @@ class Plan:
         to memory.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).
         Launch only; finish() raises on device-side errors."""
         self._open("wave_stats")
-        head = int(head)
-        if not 0 <= head < 1 << 32:
-            raise DeltaRiceError(1, f"head: {head} is not a uint32")
+        head = _uint32(head, "head")
         self._check_encoded(words, chunk_word_off, wave_words)
-        if out is None:
-            out = torch.empty((self.total_waves, _lib.STAT_COLS), dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(out, torch.int64, self.total_waves * _lib.STAT_COLS, "out")
+        out = self._out(out, torch.int64, (self.total_waves, _lib.STAT_COLS), "out")
         self._call_encoded("wave_stats", words, chunk_word_off, wave_words, in_words, head, out.data_ptr())
         return out
 
@@ -494,8 +547,7 @@ class Plan:
                    wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """wave_stats_async on an EncodedBatch; waits, and raises like decode().  The cuts of an analysis come from its
         columns: ``plan.gather_encoded(enc, torch.nonzero(cut(stats)).flatten().cpu(), 2000)``."""
-        self._open("wave_stats")
-        return self._blocking(self.wave_stats_async, enc.words, enc.chunk_word_off, head, out, wave_words, in_words=enc.total_words)
+        return self._blocking(self.wave_stats_async, enc, head, out, wave_words)
 
     def wave_bins_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, bin: int, n_bins: Optional[int] = None,
                         start: Optional[torch.Tensor] = None, offset: int = 0, out: Optional[torch.Tensor] = None,
@@ -509,24 +561,11 @@ class Plan:
         tensor of total_waves * n_bins * BIN_COLS elements.  wave_words: the encoder's n_i table as decode_with_wave_words
         takes it (no header walk).  Launch only; finish() raises on device-side errors."""
         self._open("wave_bins")
-        bin, offset = int(bin), int(offset)
-        if not 1 <= bin < 1 << 32:
-            raise DeltaRiceError(1, f"bin: {bin} is not a uint32 above 0")
-        if not -(1 << 63) <= offset < 1 << 63:
-            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
-        n_bins = max(0, -(-(self.longest_wave() - offset) // bin)) if n_bins is None else int(n_bins)
-        if not 0 <= n_bins < 1 << 32:
-            raise DeltaRiceError(1, f"n_bins: {n_bins} is not a uint32")
-        sp, ss = None, 0
-        if start is not None:
-            if (not isinstance(start, torch.Tensor) or start.dim() != 1 or start.device != self.ctx.device or
-                    start.dtype != torch.int64 or start.shape[0] != self.total_waves or (self.total_waves > 1 and start.stride(0) < 1)):
-                raise DeltaRiceError(1, f"start: need a 1-D int64 tensor of {self.total_waves} entries on {self.ctx.device}")
-            sp, ss = start.data_ptr(), (int(start.stride(0)) if self.total_waves > 1 else 1)
+        bin, offset = _uint32(bin, "bin", 1), _int64(offset, "offset")
+        n_bins = _uint32(max(0, -(-(self.longest_wave() - offset) // bin)) if n_bins is None else n_bins, "n_bins")
+        sp, ss = self._column(start, "start")
         self._check_encoded(words, chunk_word_off, wave_words)
-        if out is None:
-            out = torch.empty((self.total_waves, n_bins, _lib.BIN_COLS), dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(out, torch.int64, self.total_waves * n_bins * _lib.BIN_COLS, "out")
+        out = self._out(out, torch.int64, (self.total_waves, n_bins, _lib.BIN_COLS), "out")
         if n_bins == 0 or self.total_waves == 0:
             return out
         self._call_encoded("wave_bins", words, chunk_word_off, wave_words, in_words, sp, ss, offset, bin, n_bins, out.data_ptr(),
@@ -538,9 +577,7 @@ class Plan:
         """wave_bins_async on an EncodedBatch -> int64 [total_waves, n_bins, BIN_COLS]; waits, and raises like wave_stats().  The
         charge in eight gates of 250 samples around every waveform's peak:
         ``plan.wave_bins(enc, 250, 8, start=stats[:, STAT_ARGMAX], offset=-500)[:, :, BIN_SUM]``."""
-        self._open("wave_bins")
-        return self._blocking(self.wave_bins_async, enc.words, enc.chunk_word_off, bin, n_bins, start, offset, out, wave_words,
-                              in_words=enc.total_words)
+        return self._blocking(self.wave_bins_async, enc, bin, n_bins, start, offset, out, wave_words)
 
     def decode_window_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start, width: int, offset: int = 0,
                             pad: int = 0, out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None,
@@ -553,29 +590,17 @@ class Plan:
         between rows, default width); the samples between rows keep what they held.  wave_words: the encoder's n_i table as
         decode_with_wave_words takes it (no header walk).  Launch only; finish() raises on device-side errors."""
         self._open("decode_window")
-        width, offset, pad = int(width), int(offset), int(pad)
-        if not 0 <= width < 1 << 32:
-            raise DeltaRiceError(1, f"width: {width} is not a uint32")
-        if not -32768 <= pad <= 32767:
-            raise DeltaRiceError(1, f"pad: {pad} is not an int16")
-        sp, ss = None, 0
+        width, pad = _uint32(width, "width"), _int16(pad, "pad")
         if start is not None and not isinstance(start, torch.Tensor):
-            offset += int(start)
-        elif start is not None:
-            if (start.dim() != 1 or start.device != self.ctx.device or start.dtype != torch.int64 or
-                    start.shape[0] != self.total_waves or (self.total_waves > 1 and start.stride(0) < 1)):
-                raise DeltaRiceError(1, f"start: need a 1-D int64 tensor of {self.total_waves} entries on {self.ctx.device}")
-            sp, ss = start.data_ptr(), (int(start.stride(0)) if self.total_waves > 1 else 1)
-        if not -(1 << 63) <= offset < 1 << 63:
-            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+            start, offset = None, int(offset) + int(start)
+        sp, ss = self._column(start, "start")
+        offset = _int64(offset, "offset")
         self._check_encoded(words, chunk_word_off, wave_words)
         stride = width if out_stride is None else int(out_stride)
         if stride < width:
             raise DeltaRiceError(1, f"out_stride: rows {stride} samples apart do not hold {width}")
         need = (self.total_waves - 1) * stride + width if self.total_waves else 0
-        if out is None:
-            out = torch.empty((self.total_waves, width) if stride == width else (need,), dtype=torch.int16, device=self.ctx.device)
-        self._dev_check(out, torch.int16, need, "out")
+        out = self._out(out, torch.int16, (self.total_waves, width) if stride == width else need, "out")
         if width == 0 or self.total_waves == 0:
             return out
         self._call_encoded("decode_window", words, chunk_word_off, wave_words, in_words, sp, ss, offset, width, pad, out.data_ptr(),
@@ -586,9 +611,7 @@ class Plan:
                       out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """decode_window_async on an EncodedBatch -> int16 [total_waves, width]; waits, and raises like decode().  The samples
         around every pulse: ``plan.decode_window(enc, stats[:, STAT_ARGMAX], 256, offset=-64)``."""
-        self._open("decode_window")
-        return self._blocking(self.decode_window_async, enc.words, enc.chunk_word_off, start, width, offset, pad, out, None, wave_words,
-                              in_words=enc.total_words)
+        return self._blocking(self.decode_window_async, enc, start, width, offset, pad, out, None, wave_words)
 
     def decode_windows_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start: torch.Tensor, width: int,
                              count: Optional[torch.Tensor] = None, offset: int = 0, pad: int = 0,
@@ -605,21 +628,13 @@ class Plan:
         the encoder's n_i table as decode_with_wave_words takes it (no header walk).  Launch only; finish() raises on
         device-side errors."""
         self._open("decode_windows")
-        width, offset, pad = int(width), int(offset), int(pad)
-        if not 0 <= width < 1 << 32:
-            raise DeltaRiceError(1, f"width: {width} is not a uint32")
-        if not -32768 <= pad <= 32767:
-            raise DeltaRiceError(1, f"pad: {pad} is not an int16")
-        if not -(1 << 63) <= offset < 1 << 63:
-            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+        width, offset, pad = _uint32(width, "width"), _int64(offset, "offset"), _int16(pad, "pad")
         W = self.total_waves
         if (not isinstance(start, torch.Tensor) or start.dim() != 2 or start.device != self.ctx.device or
                 start.dtype != torch.int64 or start.shape[0] != W or not start.shape[1] < 1 << 32 or
-                (W > 1 and start.stride(0) < 1) or (start.shape[1] > 1 and start.stride(1) < 1)):
+                _stride(start, 0) is None or _stride(start, 1) is None):
             raise DeltaRiceError(1, f"start: need a 2-D int64 tensor [{W}, n_win] with positive strides on {self.ctx.device}")
-        K = int(start.shape[1])
-        s_wave = int(start.stride(0)) if W > 1 else max(1, int(start.stride(0)))
-        s_win = int(start.stride(1)) if K > 1 else max(1, int(start.stride(1)))
+        K, s_wave, s_win = int(start.shape[1]), _stride(start, 0), _stride(start, 1)
         if count is not None:
             self._dev_check(count, torch.int32, W, "count")
         self._check_encoded(words, chunk_word_off, wave_words)
@@ -629,10 +644,8 @@ class Plan:
         if K and o_wave < (K - 1) * o_win + width:
             raise DeltaRiceError(1, f"out_strides: waveforms {o_wave} samples apart do not hold {K} rows {o_win} apart")
         need = (W - 1) * o_wave + (K - 1) * o_win + width if W and K and width else 0
-        if out is None:
-            out = torch.empty(need, dtype=torch.int16, device=self.ctx.device)
-        self._dev_check(out, torch.int16, need, "out")
-        rows = out.view(-1).as_strided((W, K, width), (o_wave, o_win, 1)) if need else out.view(-1)[:0].view(W, K, width)
+        out = self._out(out, torch.int16, need, "out")
+        rows =out.view(-1).as_strided((W, K, width), (o_wave, o_win, 1)) if need else out.view(-1)[:0].view(W, K, width)
         if need == 0:
             return rows
         self._call_encoded("decode_windows", words, chunk_word_off, wave_words, in_words, start.data_ptr(), s_wave, s_win,
@@ -645,9 +658,7 @@ class Plan:
         """decode_windows_async on an EncodedBatch -> int16 [total_waves, n_win, width]; waits, and raises like decode().  The
         samples around every pulse: ``n, pulses = plan.find_pulses(enc, thr, max_pulses=8)``, then
         ``plan.decode_windows(enc, pulses[:, :, PULSE_START], 256, count=n, offset=-64)``."""
-        self._open("decode_windows")
-        return self._blocking(self.decode_windows_async, enc.words, enc.chunk_word_off, start, width, count, offset, pad, out, None,
-                              wave_words, in_words=enc.total_words)
+        return self._blocking(self.decode_windows_async, enc, start, width, count, offset, pad, out, None, wave_words)
 
     def find_pulses_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, threshold, polarity: int = 1,
                           min_width: int = 1, max_pulses: int = 4, offset: int = 0, count: Optional[torch.Tensor] = None,
@@ -664,31 +675,18 @@ class Plan:
         write to.  wave_words: the encoder's n_i table as decode_with_wave_words takes it (no header walk).  Launch only;
         finish() raises on device-side errors."""
         self._open("find_pulses")
-        polarity, min_width, max_pulses, offset = int(polarity), int(min_width), int(max_pulses), int(offset)
+        polarity = int(polarity)
         if polarity == 0:
             raise DeltaRiceError(1, "polarity: 0 is neither above nor below")
-        if not 1 <= min_width < 1 << 32:
-            raise DeltaRiceError(1, f"min_width: {min_width} is not in 1 .. 2^32 - 1")
-        if not 0 <= max_pulses < 1 << 32:
-            raise DeltaRiceError(1, f"max_pulses: {max_pulses} is not a uint32")
-        tp, ts = None, 0
+        min_width, max_pulses = _uint32(min_width, "min_width", 1), _uint32(max_pulses, "max_pulses")
         if not isinstance(threshold, torch.Tensor):
-            offset += int(threshold)
-        else:
-            if (threshold.dim() != 1 or threshold.device != self.ctx.device or threshold.dtype != torch.int64 or
-                    threshold.shape[0] != self.total_waves or (self.total_waves > 1 and threshold.stride(0) < 1)):
-                raise DeltaRiceError(1, f"threshold: need a 1-D int64 tensor of {self.total_waves} entries on {self.ctx.device}")
-            tp, ts = threshold.data_ptr(), (int(threshold.stride(0)) if self.total_waves > 1 else 1)
-        if not -(1 << 63) <= offset < 1 << 63:
-            raise DeltaRiceError(1, f"offset: {offset} is not an int64")
+            threshold, offset = None, int(offset) + int(threshold)
+        tp, ts = self._column(threshold, "threshold")
+        offset = _int64(offset, "offset")
         self._check_encoded(words, chunk_word_off, wave_words)
         W, need = self.total_waves, self.total_waves * max_pulses * _lib.PULSE_COLS
-        if count is None:
-            count = torch.empty(W, dtype=torch.int32, device=self.ctx.device)
-        self._dev_check(count, torch.int32, W, "count")
-        if out is None:
-            out = torch.empty(need, dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(out, torch.int64, need, "out")
+        count = self._out(count, torch.int32, W, "count")
+        out = self._out(out, torch.int64, need, "out")
         self._call_encoded("find_pulses", words, chunk_word_off, wave_words, in_words, tp, ts, offset, 1 if polarity > 0 else -1,
                            min_width, max_pulses, count.data_ptr(), out.data_ptr() if need else None)
         return count.view(-1)[:W], out.view(-1)[:need].view(W, max_pulses, _lib.PULSE_COLS)
@@ -698,21 +696,22 @@ class Plan:
                     wave_words: Optional[torch.Tensor] = None):
         """find_pulses_async on an EncodedBatch -> (count, pulses); waits, and raises like decode().  Forty counts above every
         waveform's own baseline: ``plan.find_pulses(enc, stats[:, STAT_HEAD_SUM] // 500, offset=40)``."""
-        self._open("find_pulses")
-        return self._blocking(self.find_pulses_async, enc.words, enc.chunk_word_off, threshold, polarity, min_width, max_pulses, offset,
-                              count, out, wave_words, in_words=enc.total_words)
+        return self._blocking(self.find_pulses_async, enc, threshold, polarity, min_width, max_pulses, offset, count, out, wave_words)
 
     def estimate_words_encoded(self, enc: EncodedBatch, wave_words: Optional[torch.Tensor] = None) -> np.ndarray:
         """estimate_words from the encoded stream: entry k is the total words transcode() gives at RiceParameter 2^k, k = 0..15;
         nothing is decoded to memory.  wave_words: the source's n_i table (no header walk).  Waits; raises DRX_ERR_CORRUPT for a
         stream that fails validation."""
         self._open("estimate_words_encoded")
+        return self._estimate("drx_estimate_words_encoded", enc, wave_words)
+
+    def _estimate(self, symbol: str, enc: EncodedBatch, wave_words, *target):
+        """The sixteen totals of drx_estimate_words_encoded, or of its _filter form with the ``target`` taps (n, array)"""
         self._check_encoded(enc.words, enc.chunk_word_off, wave_words)
         self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
         out = (C.c_uint64 * 16)()
-        self.ctx._check(self.ctx.lib.drx_estimate_words_encoded(self._h, enc.words.data_ptr(), int(enc.total_words),
-                                                                enc.chunk_word_off.data_ptr(),
-                                                                wave_words.data_ptr() if wave_words is not None else None, out))
+        self.ctx._check(getattr(self.ctx.lib, symbol)(self._h, enc.words.data_ptr(), int(enc.total_words), enc.chunk_word_off.data_ptr(),
+                                                      wave_words.data_ptr() if wave_words is not None else None, *target, out))
         return np.array(list(out), dtype=np.uint64)
 
     def transcode_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, rice_m: int,
@@ -725,19 +724,8 @@ class Plan:
         [total_waves]).  finish() raises on device-side errors (DRX_ERR_CAPACITY, DRX_ERR_CORRUPT: nothing was written)."""
         self._open("transcode")
         k = parse_opts((int(rice_m),)).rice_k
-        self._check_encoded(words, chunk_word_off, wave_words)
-        if out_words is not None:
-            self._dev_check(out_words, torch.int32, 0, "out_words")
-        if out_chunk_word_off is None:
-            out_chunk_word_off = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(out_chunk_word_off, torch.int64, self.n_chunks + 1, "out_chunk_word_off")
-        if out_wave_words is None:
-            out_wave_words = torch.empty(self.total_waves, dtype=torch.int32, device=self.ctx.device)
-        self._dev_check(out_wave_words, torch.int32, self.total_waves, "out_wave_words")
-        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
-        self._call_encoded("transcode", words, chunk_word_off, wave_words, in_words, k, op, cap, out_chunk_word_off.data_ptr(),
-                           out_wave_words.data_ptr())
-        return out_words, out_chunk_word_off, out_wave_words
+        return self._batch_call("transcode", words, chunk_word_off, wave_words, in_words, (k,), out_words, out_chunk_word_off,
+                                self.n_chunks, out_wave_words, self.total_waves)
 
     def transcode(self, enc: EncodedBatch, rice_m: Optional[int] = None, wave_words: Optional[torch.Tensor] = None,
                   out_words: Optional[torch.Tensor] = None) -> "Transcoded":
@@ -750,14 +738,8 @@ class Plan:
         self._open("transcode")
         if rice_m is None:
             rice_m = 1 << int(np.argmin(self.estimate_words_encoded(enc, wave_words)))  # (argmin: the first of equals)
-        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
-        off = tab = None
-        if out_words is None:
-            _, off, tab = self.transcode_async(enc.words, enc.chunk_word_off, rice_m, None, enc.total_words, wave_words)
-            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
-        _, off, tab = self.transcode_async(enc.words, enc.chunk_word_off, rice_m, out_words, enc.total_words, wave_words, off, tab)
-        return Transcoded(EncodedBatch(out_words, off, self.finish()), tab, int(rice_m), self._taps,
-                          self._chunk_samples.copy(), self._wave_lens.copy())
+        res, tab = self._sized(self.transcode_async, enc, (rice_m,), wave_words, out_words)
+        return Transcoded(res, tab, int(rice_m), self._taps, self._chunk_samples.copy(), self._wave_lens.copy())
 
     @staticmethod
     def _target_taps(taps: Optional[Sequence[int]]):
@@ -776,14 +758,7 @@ class Plan:
         nothing decoded to memory.  Waits; raises DRX_ERR_CORRUPT for a stream that fails validation."""
         self._open("estimate_words_refiltered")
         arr, n, _ = self._target_taps(taps)
-        self._check_encoded(enc.words, enc.chunk_word_off, wave_words)
-        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
-        out = (C.c_uint64 * 16)()
-        self.ctx._check(self.ctx.lib.drx_estimate_words_encoded_filter(self._h, enc.words.data_ptr(), int(enc.total_words),
-                                                                       enc.chunk_word_off.data_ptr(),
-                                                                       wave_words.data_ptr() if wave_words is not None else None,
-                                                                       n, arr, out))
-        return np.array(list(out), dtype=np.uint64)
+        return self._estimate("drx_estimate_words_encoded_filter", enc, wave_words, n, arr)
 
     def refilter_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, taps: Optional[Sequence[int]], rice_m: int,
                        out_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None,
@@ -796,19 +771,8 @@ class Plan:
         self._open("refilter")
         k = parse_opts((int(rice_m),)).rice_k
         arr, n, _ = self._target_taps(taps)
-        self._check_encoded(words, chunk_word_off, wave_words)
-        if out_words is not None:
-            self._dev_check(out_words, torch.int32, 0, "out_words")
-        if out_chunk_word_off is None:
-            out_chunk_word_off = torch.empty(self.n_chunks + 1, dtype=torch.int64, device=self.ctx.device)
-        self._dev_check(out_chunk_word_off, torch.int64, self.n_chunks + 1, "out_chunk_word_off")
-        if out_wave_words is None:
-            out_wave_words = torch.empty(self.total_waves, dtype=torch.int32, device=self.ctx.device)
-        self._dev_check(out_wave_words, torch.int32, self.total_waves, "out_wave_words")
-        op, cap = (out_words.data_ptr(), out_words.numel()) if out_words is not None and out_words.numel() else (None, 0)
-        self._call_encoded("transcode_filter", words, chunk_word_off, wave_words, in_words, k, n, arr, op, cap,
-                           out_chunk_word_off.data_ptr(), out_wave_words.data_ptr())
-        return out_words, out_chunk_word_off, out_wave_words
+        return self._batch_call("transcode_filter", words, chunk_word_off, wave_words, in_words, (k, n, arr), out_words,
+                                out_chunk_word_off, self.n_chunks, out_wave_words, self.total_waves)
 
     def refilter(self, enc: EncodedBatch, taps: Optional[Sequence[int]], rice_m: Optional[int] = None,
                  wave_words: Optional[torch.Tensor] = None, out_words: Optional[torch.Tensor] = None) -> "Transcoded":
@@ -823,14 +787,8 @@ class Plan:
         _, _, carried = self._target_taps(taps)
         if rice_m is None:
             rice_m = 1 << int(np.argmin(self.estimate_words_refiltered(enc, taps, wave_words)))  # (argmin: the first of equals)
-        self.ctx.stream.wait_stream(torch.cuda.current_stream(self.ctx.device))
-        off = tab = None
-        if out_words is None:
-            _, off, tab = self.refilter_async(enc.words, enc.chunk_word_off, taps, rice_m, None, enc.total_words, wave_words)
-            out_words = torch.empty(self.finish(), dtype=torch.int32, device=self.ctx.device)
-        _, off, tab = self.refilter_async(enc.words, enc.chunk_word_off, taps, rice_m, out_words, enc.total_words, wave_words, off, tab)
-        return Transcoded(EncodedBatch(out_words, off, self.finish()), tab, int(rice_m), carried,
-                          self._chunk_samples.copy(), self._wave_lens.copy())
+        res, tab = self._sized(self.refilter_async, enc, (taps, rice_m), wave_words, out_words)
+        return Transcoded(res, tab, int(rice_m), carried, self._chunk_samples.copy(), self._wave_lens.copy())
 
     def estimate_words(self, x: torch.Tensor) -> np.ndarray:
         """Exact encoded size (uint32 words) of this batch for RiceParameter 2^k, k = 0..15 -- the

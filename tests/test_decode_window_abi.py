@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from decode_window_reference import windows, windows_loop
+from plan_standin import plan as _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,23 +36,6 @@ def test_a_null_plan_is_an_argument_error():
     lib = _lib.load()
     assert lib.drx_decode_window(None, None, 0, None, None, 0, 0, 16, 0, None, 16) == 1
     assert lib.drx_decode_window_with_wave_words(None, None, 0, None, None, None, 0, 0, 16, 0, None, 16) == 1
-
-
-class _Ctx:
-    lib = None
-
-    def __init__(self, device):
-        self.device = device
-
-
-def _plan(total_waves=3):
-    """A plan as far as the Python entry's own checks go (no GPU here): they all come in front of the library call."""
-    import torch
-    from deltarice_amd import codec
-    plan = object.__new__(codec.Plan)
-    plan.ctx, plan._h = _Ctx(torch.device("cpu")), 1
-    plan.total_waves, plan.n_chunks = total_waves, 1
-    return plan
 
 
 def test_python_entry_refusals():

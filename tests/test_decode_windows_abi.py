@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from decode_windows_reference import extents, windows_multi, windows_multi_loop
+from plan_standin import plan as _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
@@ -56,23 +57,6 @@ def test_the_listed_query():
     assert callable(codec.Plan.last_windows_listed)
 
 
-class _Ctx:
-    lib = None
-
-    def __init__(self, device):
-        self.device = device
-
-
-def _plan(total_waves=3):
-    """A plan as far as the Python entry's own checks go (no GPU here): they all come in front of the library call."""
-    import torch
-    from deltarice_amd import codec
-    plan = object.__new__(codec.Plan)
-    plan.ctx, plan._h = _Ctx(torch.device("cpu")), 1
-    plan.total_waves, plan.n_chunks = total_waves, 1
-    return plan
-
-
 def test_python_entry_refusals():
     import torch
     from deltarice_amd import DeltaRiceError
@@ -112,7 +96,7 @@ def test_python_entry_refusals():
         with pytest.raises(DeltaRiceError) as e:
             plan.decode_windows_async(w, off, start, width, **kw)
         assert e.value.status == 1, what
-    # no width and no window slot: empty results, and the library is not called (this stand-in has none)
+    # no width and no window slot: empty results, and the library is not called (tests/test_codec_calls.py holds the stand-in's record to that)
     assert plan.decode_windows_async(words, off, good, 0).shape == (3, 2, 0)
     assert plan.decode_windows_async(words, off, torch.zeros((3, 0), dtype=torch.int64), 16).shape == (3, 0, 16)
     # a closed plan, in both entries

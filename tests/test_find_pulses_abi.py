@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from find_pulses_reference import find_pulses, find_pulses_loop
+from plan_standin import plan as _plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
@@ -42,23 +43,6 @@ def test_a_null_plan_is_an_argument_error():
     lib = _lib.load()
     assert lib.drx_find_pulses(None, None, 0, None, None, 0, 0, 1, 1, 4, None, None) == 1
     assert lib.drx_find_pulses_with_wave_words(None, None, 0, None, None, None, 0, 0, 1, 1, 4, None, None) == 1
-
-
-class _Ctx:
-    lib = None
-
-    def __init__(self, device):
-        self.device = device
-
-
-def _plan(total_waves=3):
-    """A plan as far as the Python entry's own checks go (no GPU here): they all come in front of the library call."""
-    import torch
-    from deltarice_amd import codec
-    plan = object.__new__(codec.Plan)
-    plan.ctx, plan._h = _Ctx(torch.device("cpu")), 1
-    plan.total_waves, plan.n_chunks = total_waves, 1
-    return plan
 
 
 def test_python_entry_refusals():

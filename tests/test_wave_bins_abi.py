@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from plan_standin import plan as _plan
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -63,25 +65,6 @@ def test_a_null_plan():
     assert lib.drx_plan_last_bins_listed(None) == 0
 
 
-class _Ctx:
-    lib = None
-
-    def __init__(self, device):
-        self.device = device
-
-
-def _plan(total_waves=3):
-    """A plan as far as the Python entry's own checks go (no GPU here): they all come in front of the library call."""
-    import numpy as np
-    import torch
-    from deltarice_amd import codec
-    plan = object.__new__(codec.Plan)
-    plan.ctx, plan._h = _Ctx(torch.device("cpu")), 1
-    plan.total_waves, plan.n_chunks = total_waves, 1
-    plan._chunk_samples, plan._wave_lens = np.array([250]), np.array([100])
-    return plan
-
-
 def test_python_entry_refusals_and_a_closed_plan():
     import torch
     from deltarice_amd import DeltaRiceError, _lib
@@ -111,7 +94,7 @@ def test_python_entry_refusals_and_a_closed_plan():
         with pytest.raises(DeltaRiceError) as e:
             plan.wave_bins_async(w, off, b, **kw)
         assert e.value.status == 1, what
-    # no bin: an empty result, and the library is not called (this stand-in has none)
+    # no bin: an empty result, and the library is not called (tests/test_codec_calls.py holds the stand-in's record to that)
     assert plan.wave_bins_async(words, off, 10, 0).shape == (3, 0, _lib.BIN_COLS)
     # the default n_bins covers the plan's longest waveform (100 samples) from the offset
     assert plan.wave_bins_async(words, off, 10, offset=100).shape == (3, 0, _lib.BIN_COLS)
