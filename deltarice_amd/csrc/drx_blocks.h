@@ -63,6 +63,11 @@ struct BlkGeom {
 
 __host__ __device__ inline uint32_t blk_words(uint32_t nt, uint32_t k) { return nt * (uint32_t)blk_segw_plan(k); }  // plan-time estimates
 __host__ __device__ inline uint32_t blk_words_min(uint32_t nt) { return nt * (uint32_t)kBlkSegWMin; }               // scratch sizing
+inline int nt_for_len(uint32_t wave_len, uint32_t k) {
+    // lanes per block: a waveform of about (k + 3.5) bits per sample should fill most of its last block
+    const uint64_t typ_words = ((uint64_t)wave_len * (2u * k + 7u)) >> 6;
+    return typ_words <= blk_words(64, k) ? 64 : (typ_words <= blk_words(128, k) ? 128 : 256);
+}
 
 // Workgroup barrier for data exchanged through LDS only.  __syncthreads() also fences global memory, i.e. waits for
 // every global load and store the wave has in flight (s_waitcnt vmcnt(0)): the image and the ticket fetched ahead and

@@ -87,11 +87,6 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static int nt_for_len(uint32_t wave_len, uint32_t k) {
-    // lanes per block: a waveform of about (k + 3.5) bits per sample should fill most of its last block
-    const uint64_t typ_words = ((uint64_t)wave_len * (2u * k + 7u)) >> 6;
-    return typ_words <= blk_words(64, k) ? 64 : (typ_words <= blk_words(128, k) ? 128 : 256);
-}
 static int blocks_nt(const Geom &G) { return G.uniform ? nt_for_len(G.u_wave_len, G.k) : (int)G.rag_blk_nt; }
 
 // blocks of `waves` waveforms of `wave_len` samples, weighted by what a block of theirs costs (1.7 for waveforms of one or two
