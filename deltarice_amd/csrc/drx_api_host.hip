@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "drx_api.h"
+#include "drx_device.h"
 
 using namespace drx;
 
@@ -11,13 +12,13 @@ static bool walk_chunk_host(const uint32_t *w, uint64_t n_words, uint32_t n_samp
                             uint64_t *wave_off, uint32_t *wave_words) {
     if (n_words < 2 || w[0] != n_samples) return false;
     const uint32_t L = wave_len ? wave_len : n_samples;
-    const uint64_t W = ((uint64_t)n_samples + L - 1) / L;
+    const uint64_t W = ((uint64_t)n_samples + L - 1) / L;  // (< 2^31: n_samples is)
+    const HeaderBounds hb = header_bounds(L, n_samples, (uint32_t)W, k);
     uint64_t at = 1;
     for (uint64_t i = 0; i < W; ++i) {
         if (at >= n_words) return false;
         const uint32_t n = w[at];
-        const uint64_t len = (i + 1 == W) ? (uint64_t)n_samples - i * L : L;
-        if (n > ((len * 25u + 31u) >> 5) || n < ((len * (k + 1u) + 31u) >> 5) || at + 1u + n > n_words) return false;
+        if (!hb.ok(n, i + 1 == W) || at + 1u + n > n_words) return false;
         wave_off[i] = at;
         wave_words[i] = n;
         at += (uint64_t)n + 1u;

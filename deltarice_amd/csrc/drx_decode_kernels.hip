@@ -379,8 +379,8 @@ __global__ __launch_bounds__(64, 1) void k_decode_lanes(Geom G, const uint32_t *
             }
         }
         if (active) {
-            n = (uint32_t)(gr >> 32) & 0x7fffffffu;
-            S = chunk_word_off[c] + (uint32_t)gr + 1u;
+            n = granule_words(gr);
+            S = chunk_word_off[c] + granule_pos(gr) + 1u;
         }
     } else if (!G.uniform && G.rag_order) {
         // ragged batch: wavefronts in order of decreasing WaveformLength (longest processing time first).  A lane takes

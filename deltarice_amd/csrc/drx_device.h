@@ -65,6 +65,20 @@ __host__ __device__ __forceinline__ uint32_t max_payload_words(uint32_t len) { r
 __host__ __device__ __forceinline__ uint32_t min_payload_words(uint32_t len, uint32_t k) {
     return (uint32_t)(((uint64_t)len * (k + 1u) + 31u) >> 5);
 }
+// ... of the headers of one chunk of W waveforms of L samples, N in all: the full waveforms' and the shorter last one's
+struct HeaderBounds {
+    uint32_t min_full, max_full, min_last, max_last;
+    __host__ __device__ __forceinline__ bool ok(uint32_t n, bool is_last) const {
+        return !(n > (is_last ? max_last : max_full) || n < (is_last ? min_last : min_full));
+    }
+};
+__host__ __device__ __forceinline__ HeaderBounds header_bounds(uint32_t L, uint32_t N, uint32_t W, uint32_t k) {
+    // (a chunk without waveforms has no last one.  The guard stands on the two RESULTS: on last_len the compiler turns ok() into
+    // the bounds of a selected length, worked out again for every header: the LDS block walker's hop 0.13 -> 0.15 us, profiles/walk_refactor_ab.txt section 3b)
+    const uint32_t last_len = N - (W - 1u) * L;
+    return HeaderBounds{min_payload_words(L, k), max_payload_words(L), W ? min_payload_words(last_len, k) : 0u,
+                        W ? max_payload_words(last_len) : 0u};
+}
 
 // count-leading-zeros with the ISA's result for 0 (-1) instead of the source language's undefined behaviour: the
 // decoders meet an all-zero window only past the end of a corrupt stream, where any value will do, but it has to BE a value
@@ -131,6 +145,17 @@ __device__ __forceinline__ WaveRef locate(const Geom &G, uint64_t g) {
     r.sample_off = soff + (uint64_t)r.idx * L;
     r.len = (r.idx + 1 == W) ? (r.n_samples - r.idx * L) : L;  // trailing partial waveform (:420-425)
     return r;
+}
+// chunk c -> its frame: W waveforms of L samples (the last one shorter), N samples in all, `base` = its first waveform's index
+// in the batch's tables.  (The walks' one spelling of the uniform / ragged branch; the other kernels still carry their own.)
+struct ChunkGeom {
+    uint32_t W, L, N;
+    uint64_t base;
+};
+__device__ __forceinline__ ChunkGeom chunk_geom(const Geom &G, uint64_t c) {
+    if (G.uniform) return ChunkGeom{G.u_n_waves, G.u_wave_len, G.u_n_samples, c * G.u_n_waves};
+    const ChunkDesc d = G.chunks[c];
+    return ChunkGeom{d.n_waves, d.wave_len, d.n_samples, d.wave_base};
 }
 // the same for a wave-uniform g: the result in scalar registers (the ragged form reads the chunk table)
 __device__ __forceinline__ WaveRef locate_uniform(const Geom &G, uint64_t g) {

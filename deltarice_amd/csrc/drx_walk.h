@@ -1,6 +1,7 @@
 // drx_walk.h -- the header-chain walkers that run INSIDE a kernel (scalar chains, one lane per chunk; the LDS block walker, a
 // wave per chunk of short waveforms): device functions and their constants, shared by drx_walk.hip (the walk kernels in front
 // of the decoders and all the host decides about the walk) and drx_decode_kernels.hip (k_decode_lanes' first tickets walk).
+// In front of them what every walker shares: the extent rule with its two limits, the granule's layout, the table entry.
 #ifndef DRX_WALK_H
 #define DRX_WALK_H
 #include <hip/hip_runtime.h>
@@ -13,44 +14,64 @@
 
 namespace drx {
 
-// Header chain walk (:320-325) with validation; one lane per chunk.
+// A chunk's extent [begin, end) of the stream is usable by a walker if it lies inside the stream, holds the sample count and
+// one header at least, and is no longer than max_words.  The parallel walks keep 32-bit positions and add a header's n + 1 to
+// them before they look at the sum, so they stop at 2^31 - 1 words; the serial walkers count in 64 bits and are held to
+// 2^32 - 1 only by the granule's 32-bit position -- a chunk in between is flagged by a parallel walk and judged by its serial fallback.
+constexpr uint64_t kParWalkMaxWords = 0x7fffffffull, kSerialWalkMaxWords = 0xffffffffull;
+__device__ __forceinline__ bool chunk_extent_usable(uint64_t begin, uint64_t end, uint64_t in_words, uint64_t max_words) {
+    return !(end > in_words || begin + 2 > end || end - begin > max_words);
+}
+
 // granules (optional): one 8-byte word per waveform, {valid:1 | n_i:31 | header position relative to
 // the chunk start:32}, stored with one agent-scope relaxed atomic each -- the word is its own flag
 // (it is zero until written), so a decoder wave in the SAME launch can consume waveform w of a
 // chunk while the walk of that chunk is still at waveform w+1.
 constexpr uint64_t kGranValid = 1ull << 63;
+__device__ __forceinline__ uint32_t granule_words(uint64_t gr) { return (uint32_t)(gr >> 32) & 0x7fffffffu; }
+__device__ __forceinline__ uint32_t granule_pos(uint64_t gr) { return (uint32_t)gr; }
 
+// Waveform i's table entry: its header at word `here` of the stream, n payload words (and its granule, the chunk starting at `begin`)
+__device__ __forceinline__ void store_entry(uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
+                                            uint64_t *__restrict__ granules, uint64_t i, uint64_t begin, uint64_t here, uint32_t n) {
+    wave_off[i] = here;
+    wave_words[i] = n;
+    if (granules)
+        __hip_atomic_store(granules + i, kGranValid | ((uint64_t)n << 32) | (uint64_t)(uint32_t)(here - begin), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+// ... of a rejected waveform: it points at the chunk's own header with no words (keeps later loads in bounds; decoded as zero
+// words), its granule a bare kGranValid
+__device__ __forceinline__ void store_rejected(uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
+                                               uint64_t *__restrict__ granules, uint64_t i, uint64_t begin) {
+    store_entry(wave_off, wave_words, granules, i, begin, begin, 0u);
+}
+
+// Header chain walk (:320-325) with validation; one lane per chunk.
 __device__ __forceinline__ void walk_chunk(const Geom &G, uint64_t c, const uint32_t *__restrict__ in,
                                            uint64_t in_words, const uint64_t *__restrict__ chunk_word_off,
                                            uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
                                            uint64_t *__restrict__ granules, DevStatus *st) {
-    uint64_t base;
-    uint32_t W, L, N;
-    if (G.uniform) { base = c * G.u_n_waves; W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; }
-    else { const ChunkDesc d = G.chunks[c]; base = d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples; }
+    const ChunkGeom f = chunk_geom(G, c);
+    const HeaderBounds hb = header_bounds(f.L, f.N, f.W, G.k);
     const uint64_t begin = chunk_word_off[c];
     uint64_t end = chunk_word_off[c + 1];
     bool bad = false;
-    if (end > in_words || begin + 2 > end || end - begin > 0xffffffffull) { bad = true; end = begin; }
-    if (!bad && in[begin] != N) bad = true;  // :306 totalNumberPoints
+    if (!chunk_extent_usable(begin, end, in_words, kSerialWalkMaxWords)) { bad = true; end = begin; }
+    if (!bad && in[begin] != f.N) bad = true;  // :306 totalNumberPoints
     uint64_t at = begin + 1;
-    for (uint32_t w = 0; w < W; ++w) {
+    for (uint32_t w = 0; w < f.W; ++w) {
         uint32_t n = 0;
         uint64_t here = at;
         if (!bad && at < end) {
             n = in[at];
-            const uint32_t len = (w + 1 == W) ? (N - w * L) : L;
-            if (n > max_payload_words(len) || n < min_payload_words(len, G.k) || at + 1u + n > end) { bad = true; n = 0; }
+            if (!hb.ok(n, w + 1 == f.W) || at + 1u + n > end) { bad = true; n = 0; }
             else at += (uint64_t)n + 1u;
         } else {
             bad = true;
-            here = begin;  // keeps later loads in bounds; decoded as zero words
+            here = begin;
         }
-        wave_off[base + w] = here;
-        wave_words[base + w] = n;
-        if (granules)
-            __hip_atomic_store(granules + base + w, kGranValid | ((uint64_t)n << 32) | (uint64_t)(uint32_t)(here - begin),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        store_entry(wave_off, wave_words, granules, f.base + w, begin, here, n);
     }
     if (!bad && at != end) bad = true;
     if (bad) atomicOr(&st->err, kErrCorrupt);
@@ -77,27 +98,20 @@ __device__ __forceinline__ void walk_chunks_scalar(const Geom &G, uint64_t c0, c
     const uint64_t c = mine ? (list ? (uint64_t)list[e] : e) : 0;
     if (only && mine && !only[c]) mine = false;
     if (only && !__any(mine)) return;
-    uint32_t W = 0, L = 1, N = 0;
-    uint64_t base = 0;
-    if (mine) {
-        if (G.uniform) { W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; base = c * W; }
-        else { const ChunkDesc d = G.chunks[c]; W = d.n_waves; L = d.wave_len; N = d.n_samples; base = d.wave_base; }
-    }
+    const ChunkGeom f = mine ? chunk_geom(G, c) : ChunkGeom{0u, 1u, 0u, 0ull};
+    const uint32_t W = f.W;
+    const HeaderBounds hb = header_bounds(f.L, f.N, W, G.k);
     const uint32_t W_max = wave_max_u32(W);
     uint64_t begin = 0, end = 0;
     bool bad = false;
     if (mine) {
         begin = chunk_word_off[c];
         end = chunk_word_off[c + 1];
-        if (end > in_words || begin + 2 > end || end - begin > 0xffffffffull) { bad = true; end = begin; }
+        if (!chunk_extent_usable(begin, end, in_words, kSerialWalkMaxWords)) { bad = true; end = begin; }
     }
     if (in_words == 0) {  // nothing to load from (every chunk is bad)
         if (mine) {
-            for (uint32_t w = 0; w < W; ++w) {
-                wave_off[base + w] = begin;
-                wave_words[base + w] = 0;
-                if (granules) __hip_atomic_store(granules + base + w, kGranValid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            for (uint32_t w = 0; w < W; ++w) store_rejected(wave_off, wave_words, granules, f.base + w, begin);
             atomicOr(&st->err, kErrCorrupt);
         }
         return;
@@ -128,7 +142,7 @@ __device__ __forceinline__ void walk_chunks_scalar(const Geom &G, uint64_t c0, c
         return r;
     };
     const uint32_t head = sload((mine && !bad) ? begin : 0ull);
-    if (mine && !bad && head != N) bad = true;  // :306 totalNumberPoints
+    if (mine && !bad && head != f.N) bad = true;  // :306 totalNumberPoints
     uint64_t at = begin + 1;
     for (uint32_t w = 0; w < W_max; ++w) {
         const bool live = mine && w < W;  // chunks of a ragged batch differ in their number of waveforms
@@ -138,20 +152,13 @@ __device__ __forceinline__ void walk_chunks_scalar(const Geom &G, uint64_t c0, c
         uint64_t here = at;
         if (can) {
             n = nn;
-            const uint32_t len = (w + 1 == W) ? (N - w * L) : L;
-            if (n > max_payload_words(len) || n < min_payload_words(len, G.k) || at + 1u + n > end) { bad = true; n = 0; }
+            if (!hb.ok(n, w + 1 == W) || at + 1u + n > end) { bad = true; n = 0; }
             else at += (uint64_t)n + 1u;
         } else if (live) {
             bad = true;
             here = begin;
         }
-        if (live) {
-            wave_off[base + w] = here;
-            wave_words[base + w] = n;
-            if (granules)
-                __hip_atomic_store(granules + base + w, kGranValid | ((uint64_t)n << 32) | (uint64_t)(uint32_t)(here - begin),
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (live) store_entry(wave_off, wave_words, granules, f.base + w, begin, here, n);
     }
     if (mine && !bad && at != end) bad = true;
     if (mine && bad) atomicOr(&st->err, kErrCorrupt);
@@ -166,8 +173,11 @@ constexpr uint32_t kWalkBlockWords = 4096;
 constexpr uint32_t kWalkShortLen = 2048;  // WaveformLength up to which a chunk is walked through LDS
 
 constexpr uint32_t kWalkHopCap = 1024;   // hops buffered in LDS between coalesced flushes
+constexpr int kChasePad = 15;            // k_walk_block, k_walk_block_only: PAD of walk_chunk_block()
 
 // blk: kWalkBlockWords words (16-byte aligned), hop: kWalkHopCap entries, both in LDS and private to the wave.
+// PAD >= 0 holds the chase loop where it is fast (below: the two kernels of drx_walk.hip); -1: left to the compiler (k_decode_lanes).
+template <int PAD = -1>
 __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, const uint32_t *__restrict__ in,
                                                  uint64_t in_words, const uint64_t *__restrict__ chunk_word_off,
                                                  uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
@@ -175,18 +185,15 @@ __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, cons
     constexpr uint32_t B = kWalkBlockWords;
     constexpr int NV = B / 256;  // 16-byte loads per lane and block
     const int lane = lane_id();
-    uint64_t base;
-    uint32_t W, L, N;
-    if (G.uniform) { base = c * G.u_n_waves; W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; }
-    else { const ChunkDesc d = G.chunks[c]; base = d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples; }
+    const ChunkGeom f = chunk_geom(G, c);
+    const uint32_t W = f.W;
+    const uint64_t base = f.base;
+    const HeaderBounds hb = header_bounds(f.L, f.N, W, G.k);
     const uint64_t begin = chunk_word_off[c];
     uint64_t end = chunk_word_off[c + 1];
     bool bad = false;
-    if (end > in_words || begin + 2 > end || end - begin > 0xffffffffull) { bad = true; end = begin; }
-    if (!bad && in[begin] != N) bad = true;
-    const uint32_t max_full = (uint32_t)(((uint64_t)L * 25u + 31u) >> 5);
-    const uint32_t max_last = W ? (uint32_t)(((uint64_t)(N - (W - 1) * L) * 25u + 31u) >> 5) : 0u;
-    const uint32_t min_full = min_payload_words(L, G.k), min_last = W ? min_payload_words(N - (W - 1) * L, G.k) : 0u;
+    if (!chunk_extent_usable(begin, end, in_words, kSerialWalkMaxWords)) { bad = true; end = begin; }
+    if (!bad && in[begin] != f.N) bad = true;
     // blocks on a fixed grid from g0 (16-byte aligned when the stream is), so that block k + 1 can be
     // requested before the chase through block k starts
     const bool vec_ok = ((uintptr_t)in & 15u) == 0;
@@ -214,6 +221,11 @@ __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, cons
         }
     };
     if (!bad) request(g0);
+    // Where the chase below lies in a 64-byte line of code decides its speed: k_walk_block takes 3.55 ms with the loop's backward
+    // branch landing 56 bytes into a line, 3.87 with it four bytes earlier (25 chunks of 14 M samples at L = 512; measured,
+    // profiles/walk_refactor_ab.txt section 3c), and left to the compiler the place moves with any change in front of it.  PAD
+    // >= 0: the code from here on starts on a line of its own plus PAD s_nop, run once per chunk (tests/test_walk_build.py).
+    if constexpr (PAD >= 0) asm volatile(".p2align 6\n\t.rept %0\n\ts_nop 0\n\t.endr" : : "n"(PAD));
     while (w < W && !bad && at < end) {
         const uint64_t b0 = g0 + (at - g0) / B * B;
         if (pre_b0 != b0) request(b0);  // a hop longer than a block skipped the requested one
@@ -222,7 +234,8 @@ __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, cons
         wave_sync();
         if (b0 + B < end) request(b0 + B);
         const uint32_t blk_len = (end - b0 < B) ? (uint32_t)(end - b0) : B;
-        const uint32_t end_rel = (end - b0 < 0xffffffffull) ? (uint32_t)(end - b0) : 0xffffffffu;
+        // the chunk's end relative to the block, clamped to 32 bits (b0 may lie three words below begin)
+        const uint32_t end_rel = (end - b0 < 0xffffffffu) ? (uint32_t)(end - b0) : 0xffffffffu;
         uint32_t rel = (uint32_t)(at - b0);
         while (w < W && rel < blk_len && !bad) {
             // chase up to kWalkHopCap hops inside the block; every value here is wave uniform (SGPRs)
@@ -230,8 +243,7 @@ __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, cons
             uint32_t hops = 0;
             while (w < W && rel < blk_len && hops < kWalkHopCap) {
                 const uint32_t n = __builtin_amdgcn_readfirstlane(blk[rel]);
-                const uint32_t lim = (w + 1 == W) ? max_last : max_full, lim_lo = (w + 1 == W) ? min_last : min_full;
-                if (n > lim || n < lim_lo || rel + 1u + n > end_rel) { bad = true; break; }
+                if (!hb.ok(n, w + 1 == W) || rel + 1u + n > end_rel) { bad = true; break; }
                 hop[hops] = make_uint2(rel, n);
                 rel += n + 1u;
                 ++w;
@@ -240,12 +252,7 @@ __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, cons
             wave_sync();
             for (uint32_t i = lane; i < hops; i += 64) {
                 const uint2 h = hop[i];
-                wave_off[base + w0 + i] = b0 + h.x;
-                wave_words[base + w0 + i] = h.y;
-                if (granules)
-                    __hip_atomic_store(granules + base + w0 + i,
-                                       kGranValid | ((uint64_t)h.y << 32) | (uint64_t)(uint32_t)(b0 + h.x - begin),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                store_entry(wave_off, wave_words, granules, base + w0 + i, begin, b0 + h.x, h.y);
             }
             wave_sync();
         }
@@ -254,11 +261,7 @@ __device__ __forceinline__ void walk_chunk_block(const Geom &G, uint64_t c, cons
     if (w < W) bad = true;
     if (!bad && at != end) bad = true;
     if (bad) {
-        for (uint32_t i = w + lane; i < W; i += 64) {
-            wave_off[base + i] = begin;
-            wave_words[base + i] = 0;
-            if (granules) __hip_atomic_store(granules + base + i, kGranValid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        for (uint32_t i = w + lane; i < W; i += 64) store_rejected(wave_off, wave_words, granules, base + i, begin);
         if (lane == 0) atomicOr(&st->err, kErrCorrupt);
     }
 }

@@ -6,9 +6,13 @@
 //   LDS block walker  chunks of short waveforms streamed through LDS by a whole wave;
 //   chunk-wide walk   k_walk_sparse (64 chains per chunk, the chunk is not read) or k_pw_scan + k_walk_parallel (candidate
 //                     headers, binary lifting): chunks of long waveforms;
-//   block-parallel    k_bw_blocks / k_bw_scan / k_bw_emit: every B-word block of a chunk of short waveforms holds a header;
+//   block-parallel    k_bw_blocks, k_bw_scan, then k_bw_emit or k_bw_chase: every B-word block of a chunk of short waveforms
+//                     holds a header (both passes over the blocks sit on one streamer, bw_stream_blocks());
 //   side-band         k_sideband_tables: no walk, the caller's n_i table checked against the stream.
-// Every walker validates while it walks (sample count, n_i bounds, the chain ends at the chunk's end).
+// Every walker validates while it walks (sample count, n_i bounds, the chain ends at the chunk's end), and every one spells
+// the format's rules through the same few helpers: a chunk's frame chunk_geom() and its headers' bounds header_bounds()
+// (drx_device.h), the extent rule chunk_extent_usable() and the table entry store_entry() / store_rejected() (drx_walk.h), the
+// list prefix wave_running_prefix() and its search slot_of() (here).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,6 +24,42 @@
 #include "drx_walk.h"
 
 namespace drx {
+
+// The serial walkers (drx_walk.h) as kernels of their own.  (The LDS block walker's chase loop is held to its place in a line
+// of code -- kChasePad, walk_chunk_block() -- which is worth 9 % of k_walk_block; profiles/walk_refactor_ab.txt section 3c.)
+__global__ __launch_bounds__(64) void k_walk_block(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                   const uint64_t *__restrict__ chunk_word_off,
+                                                   const uint32_t *__restrict__ chunk_list, uint32_t n_list,
+                                                   uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
+                                                   DevStatus *st) {
+    __shared__ __attribute__((aligned(16))) uint32_t blk[kWalkBlockWords];
+    __shared__ __attribute__((aligned(8))) uint2 hop[kWalkHopCap];  // {position in the block, n}
+    if (blockIdx.x >= n_list) return;
+    const uint64_t c = chunk_list ? chunk_list[blockIdx.x] : blockIdx.x;
+    walk_chunk_block<kChasePad>(G, c, in, in_words, chunk_word_off, wave_off, wave_words, nullptr, st, blk, hop);
+}
+
+// ... for the chunks the block-parallel walk flagged in `only`
+__global__ __launch_bounds__(64) void k_walk_block_only(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                        const uint64_t *__restrict__ chunk_word_off,
+                                                        uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
+                                                        DevStatus *st, const uint32_t *__restrict__ only) {
+    __shared__ __attribute__((aligned(16))) uint32_t blk[kWalkBlockWords];
+    __shared__ __attribute__((aligned(8))) uint2 hop[kWalkHopCap];
+    const uint64_t c = blockIdx.x;
+    if (c >= G.n_chunks || !only[c]) return;
+    walk_chunk_block<kChasePad>(G, c, in, in_words, chunk_word_off, wave_off, wave_words, nullptr, st, blk, hop);
+}
+
+__global__ __launch_bounds__(64) void k_walk_list(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                  const uint64_t *__restrict__ chunk_word_off,
+                                                  const uint32_t *__restrict__ chunk_list, uint32_t n_list,
+                                                  uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
+                                                  DevStatus *st) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n_list) return;
+    walk_chunk(G, chunk_list[i], in, in_words, chunk_word_off, wave_off, wave_words, nullptr, st);
+}
 
 __global__ __launch_bounds__(64) void k_walk_scalar(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
                                                     const uint64_t *__restrict__ chunk_word_off,
@@ -35,6 +75,23 @@ __global__ __launch_bounds__(64) void k_walk_scalar_only(Geom G, const uint32_t 
                                                          DevStatus *st, const uint32_t *__restrict__ only) {
     walk_chunks_scalar(G, (uint64_t)blockIdx.x * kWalkChains, nullptr, G.n_chunks, in, in_words, chunk_word_off, wave_off,
                        wave_words, nullptr, st, only);
+}
+
+// What the parallel walks share.  A running prefix over a list, 64 entries a step by one wavefront: -> the inclusive prefix of
+// this lane's entry v; `run` (wave uniform) carries the steps' total on.
+__device__ __forceinline__ uint32_t wave_running_prefix(uint32_t v, uint32_t &run) {
+    const uint32_t incl = wave_incl_scan_dpp(v), r = run + incl;
+    run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    return r;
+}
+// ... and the slot of such a prefix that holds unit u: pre[slot] <= u < pre[slot + 1], for pre[0] <= u < pre[n]
+__device__ __forceinline__ uint32_t slot_of(const uint32_t *pre, uint32_t n, uint32_t u) {
+    uint32_t lo = 0, hi = n;  // invariant: pre[lo] <= u < pre[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pre[mid] <= u) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 
 // The header chain WITHOUT its 2000 dependent round trips, for batches of a handful of chunks (where nothing hides
@@ -53,10 +110,9 @@ constexpr uint32_t kPwCap = 4096;      // candidates per chunk
 constexpr uint32_t kPwMaxParts = 128;  // slices of a chunk (pw_parts())
 constexpr uint32_t kPwStride = kPwCap + kPwMaxParts;  // a chunk's scratch: its candidates, then {first, count} of every slice
 constexpr int kPwLevels = 12;
-// (kPwMaxWaves, kPwMaxChunks: with the host side below)
-
-// workgroups that scan one chunk: enough of them to fill the chip when the chunks are few (one chunk of 2000 x 7000, what an
-// H5Z call brings: 128 instead of 16 took the walk from 0.113 to 0.070 ms, k_pw_scan itself 9 us)
+constexpr uint32_t kPwMaxWaves = 3584;  // waveforms per chunk this form takes (leaves room for impostors)
+constexpr uint64_t kPwMaxChunks = 224;  // the walks that READ the chunks (this form behind DRX_DBG_WALK_BY_SCAN, the block-parallel
+                                        // walk): more chunks hide the serial walk behind the decoding
 
 // 1. candidates of one slice of a chunk -> the chunk's list in global memory (cand: kPwCap x {pos, val} per chunk,
 //    cand_count: one counter per chunk, zeroed before the launch)
@@ -66,10 +122,9 @@ __global__ __launch_bounds__(256) void k_pw_scan(Geom G, const uint32_t *__restr
     const uint64_t c = list ? (uint64_t)list[blockIdx.x / parts] : blockIdx.x / parts;  // scratch is indexed by chunk
     const uint32_t part = blockIdx.x % parts, tid = threadIdx.x;
     const uint64_t begin = chunk_word_off[c], end = chunk_word_off[c + 1];
-    if (end > in_words || begin + 2 > end || end - begin > 0x7fffffffull) return;  // k_walk_parallel flags the chunk
+    if (!chunk_extent_usable(begin, end, in_words, kParWalkMaxWords)) return;  // k_walk_parallel flags the chunk
     const uint32_t len_w = (uint32_t)(end - begin);
-    const uint32_t wl = G.uniform ? G.u_wave_len : G.chunks[c].wave_len;
-    const uint32_t max_full = (uint32_t)(((uint64_t)wl * 25u + 31u) >> 5);
+    const uint32_t max_full = max_payload_words(chunk_geom(G, c).L);
     uint2 *clist = cand + c * kPwStride;
     // the slice's candidates are collected in LDS and appended with ONE global atomic (2000 atomics on one counter
     // cost 0.2 ms: same-address atomics serialise in the L2)
@@ -153,21 +208,17 @@ __global__ __launch_bounds__(kPwThreads) void k_walk_parallel(Geom G, const uint
     __shared__ uint32_t s_bad, s_start, s_first[kPwMaxParts], s_pre[kPwMaxParts + 1];
     const uint32_t tid = threadIdx.x;
     const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
-    uint32_t W, L, N;
-    uint64_t base;
-    if (G.uniform) { W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; base = c * W; }
-    else { const ChunkDesc d = G.chunks[c]; W = d.n_waves; L = d.wave_len; N = d.n_samples; base = d.wave_base; }
+    const ChunkGeom f = chunk_geom(G, c);
+    const uint32_t W = f.W;
+    const HeaderBounds hb = header_bounds(f.L, f.N, W, G.k);
     const uint64_t begin = chunk_word_off[c];
     const uint64_t end = chunk_word_off[c + 1];
     if (tid == 0) { s_bad = 0; s_start = 0xffffffffu; }
     __syncthreads();
-    bool ok = !(end > in_words || begin + 2 > end || end - begin > 0x7fffffffull);
-    if (ok && in[begin] != N) ok = false;
+    bool ok = chunk_extent_usable(begin, end, in_words, kParWalkMaxWords);
+    if (ok && in[begin] != f.N) ok = false;
     if (!ok) { if (tid == 0) fail[c] = 1u; return; }  // (uniform across the workgroup)
     const uint32_t len_w = (uint32_t)(end - begin);  // words in the chunk
-    const uint32_t max_full = (uint32_t)(((uint64_t)L * 25u + 31u) >> 5);
-    const uint32_t max_last = (uint32_t)(((uint64_t)(N - (W - 1) * L) * 25u + 31u) >> 5);
-    const uint32_t min_full = min_payload_words(L, G.k), min_last = min_payload_words(N - (W - 1) * L, G.k);
     const uint32_t nc = cand_count[c];
     if (nc > kPwCap - 2u || nc < W) { if (tid == 0) fail[c] = 1u; return; }
     // the candidates in position order: k_pw_scan's slices cover the chunk in order and each wrote its own in order, so the
@@ -178,9 +229,8 @@ __global__ __launch_bounds__(kPwThreads) void k_walk_parallel(Geom G, const uint
             const uint32_t sl = s0 + tid;
             uint2 e = make_uint2(0u, 0u);
             if (sl < parts) e = cand[c * kPwStride + kPwCap + sl];
-            const uint32_t incl = wave_incl_scan_dpp(e.y);
-            if (sl < parts) { s_first[sl] = e.x; s_pre[sl + 1u] = run + incl; }
-            run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            const uint32_t incl = wave_running_prefix(e.y, run);
+            if (sl < parts) { s_first[sl] = e.x; s_pre[sl + 1u] = incl; }
         }
         if (tid == 0) s_pre[0] = 0;
     }
@@ -191,9 +241,8 @@ __global__ __launch_bounds__(kPwThreads) void k_walk_parallel(Geom G, const uint
     for (uint32_t i = tid; i < n_pad; i += kPwThreads) {
         uint2 e = make_uint2(0xffffffffu, 0u);
         if (i < nc) {
-            uint32_t lo = 0, hi = parts;  // invariant: s_pre[lo] <= i < s_pre[hi]
-            while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (s_pre[mid] <= i) lo = mid; else hi = mid; }
-            e = cand[c * kPwStride + s_first[lo] + (i - s_pre[lo])];
+            const uint32_t sl = slot_of(s_pre, parts, i);
+            e = cand[c * kPwStride + s_first[sl] + (i - s_pre[sl])];
         }
         pos[i] = e.x;
         val[i] = e.y;
@@ -234,10 +283,10 @@ __global__ __launch_bounds__(kPwThreads) void k_walk_parallel(Geom G, const uint
             if ((w >> k) & 1u) node = up[k][node];
         if (node >= nc) { bad = true; continue; }
         const uint32_t n = val[node];
-        if (n > ((w + 1u == W) ? max_last : max_full) || n < ((w + 1u == W) ? min_last : min_full)) { bad = true; continue; }
+        if (!hb.ok(n, w + 1u == W)) { bad = true; continue; }
         if (w + 1u == W && up[0][node] != END) { bad = true; continue; }
-        wave_off[base + w] = begin + pos[node];
-        wave_words[base + w] = n;
+        wave_off[f.base + w] = begin + pos[node];
+        wave_words[f.base + w] = n;
     }
     if (bad) atomicOr(&s_bad, 1u);
     __syncthreads();
@@ -245,7 +294,7 @@ __global__ __launch_bounds__(kPwThreads) void k_walk_parallel(Geom G, const uint
 }
 
 // ---------------------------------------------------------------------------
-// The chunk-wide walk WITHOUT reading the chunk (round 4): 64 chains per chunk, chased in parallel
+// The chunk-wide walk WITHOUT reading the chunk: 64 chains per chunk, chased in parallel
 // ---------------------------------------------------------------------------
 // k_pw_scan reads every word of a chunk to find the ~2000 that are headers -- a second pass over the whole stream, 0.26 ms in
 // front of a 1.2 ms decode at 100 chunks, 0.48 at 224.  A chain needs none of that: a header says where the next one is.  What
@@ -261,6 +310,10 @@ constexpr int kSwThreads = 1024;     // (at most: chunks of few waveforms get 25
 constexpr uint32_t kSwSegs = 64;    // chains per chunk
 constexpr uint32_t kSwCap = 192;    // headers a chain may collect: chains are equal in WORDS, so one through quiet waveforms holds more than
                                     // the average W / 64 <= 56 -- up to 3.4 x (W = 2000: 6 x) before the scalar walker has to take the chunk; 48 KB of LDS
+// it costs ~60 us per 512 chunks whatever their size: every uniform batch of long waveforms takes it, the headline's 500 chunks
+// included (4.74 + 0.08 ms against 5.33 with the walk inside the launch)
+constexpr uint64_t kSwMaxChunks = 1u << 20;
+constexpr uint32_t kSwMinWaves = 8, kSwMaxWaves = 8192;  // ... chunks of 8 ... 8192 waveforms (the scan form: 64 ... kPwMaxWaves)
 
 __global__ __launch_bounds__(kSwThreads) void k_walk_sparse(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
                                                             const uint64_t *__restrict__ chunk_word_off,
@@ -274,20 +327,17 @@ __global__ __launch_bounds__(kSwThreads) void k_walk_sparse(Geom G, const uint32
     const int lane = lane_id();
     const uint32_t wv = (uint32_t)wave_id();
     const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
-    uint32_t W, L, N;
-    uint64_t base;
-    if (G.uniform) { W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; base = c * W; }
-    else { const ChunkDesc d = G.chunks[c]; W = d.n_waves; L = d.wave_len; N = d.n_samples; base = d.wave_base; }
+    const ChunkGeom f = chunk_geom(G, c);
+    const uint32_t W = f.W;
     const uint64_t begin = chunk_word_off[c];
     const uint64_t end = chunk_word_off[c + 1];
     if (tid == 0) s_bad = 0;
-    bool ok = !(end > in_words || begin + 2 > end || end - begin > 0x7fffffffull);
-    if (ok && in[begin] != N) ok = false;
+    bool ok = chunk_extent_usable(begin, end, in_words, kParWalkMaxWords);
+    if (ok && in[begin] != f.N) ok = false;
     if (!ok) { if (tid == 0) fail[c] = 1u; return; }  // (uniform across the workgroup)
     const uint32_t len_w = (uint32_t)(end - begin);
-    const uint32_t last_len = N - (W - 1u) * L;
-    const uint32_t max_full = max_payload_words(L), min_full = min_payload_words(L, G.k);
-    const uint32_t max_last = max_payload_words(last_len), min_last = min_payload_words(last_len, G.k);
+    const HeaderBounds hb = header_bounds(f.L, f.N, W, G.k);
+    const uint32_t min_full = hb.min_full, max_full = hb.max_full, min_last = hb.min_last, max_last = hb.max_last;
     const uint32_t lo_any = min_full < min_last ? min_full : min_last, hi_any = max_full > max_last ? max_full : max_last;
     // chains: as many as give each a few waveforms -- and only where finding a start (half a waveform's code, read by one wavefront
     // 512 words at a time) costs less than the hops it saves: chunks of 32 x 500 000 samples are one chain of 32 hops
@@ -370,36 +420,14 @@ __global__ __launch_bounds__(kSwThreads) void k_walk_sparse(Geom G, const uint32
             const uint32_t at = s_list[sg][i];
             const uint32_t n = (i + 1u < cnt ? s_list[sg][i + 1u] : s_a[sg + 1u]) - at - 1u;  // (the chain arrived at the next one's start)
             const uint32_t w = b0 + i;
-            if (n > ((w + 1u == W) ? max_last : max_full) || n < ((w + 1u == W) ? min_last : min_full)) bad = true;
-            wave_off[base + w] = begin + at;
-            wave_words[base + w] = n;
+            if (!hb.ok(n, w + 1u == W)) bad = true;
+            wave_off[f.base + w] = begin + at;
+            wave_words[f.base + w] = n;
         }
     }
     if (bad) atomicOr(&s_bad, 1u);
     __syncthreads();
     if (tid == 0 && s_bad) fail[c] = 1u;
-}
-
-__global__ __launch_bounds__(64) void k_walk_list(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                  const uint64_t *__restrict__ chunk_word_off,
-                                                  const uint32_t *__restrict__ chunk_list, uint32_t n_list,
-                                                  uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
-                                                  DevStatus *st) {
-    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n_list) return;
-    walk_chunk(G, chunk_list[i], in, in_words, chunk_word_off, wave_off, wave_words, nullptr, st);
-}
-
-__global__ __launch_bounds__(64) void k_walk_block(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                   const uint64_t *__restrict__ chunk_word_off,
-                                                   const uint32_t *__restrict__ chunk_list, uint32_t n_list,
-                                                   uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
-                                                   DevStatus *st) {
-    __shared__ __attribute__((aligned(16))) uint32_t blk[kWalkBlockWords];
-    __shared__ __attribute__((aligned(8))) uint2 hop[kWalkHopCap];  // {position in the block, n}
-    if (blockIdx.x >= n_list) return;
-    const uint64_t c = chunk_list ? chunk_list[blockIdx.x] : blockIdx.x;
-    walk_chunk_block(G, c, in, in_words, chunk_word_off, wave_off, wave_words, nullptr, st, blk, hop);
 }
 
 // The same idea for chunks of SHORT waveforms (tens of thousands of headers per chunk: too many for one
@@ -409,7 +437,7 @@ __global__ __launch_bounds__(64) void k_walk_block(Geom G, const uint32_t *__res
 // [1, max_words] as the block's entry header, chases the chain through LDS to the block's end (if the chain breaks,
 // the entry was an impostor: try the next small word), and reports {entry, headers, exit}.  k_bw_scan checks per
 // chunk that every block's exit is the next block's entry (and word 1 / the chunk end at the two ends) and
-// turns the counts into first-waveform indices; k_bw_blocks then runs again and writes the table.  A chunk
+// turns the counts into first-waveform indices; a second pass writes the table (k_bw_emit from the first pass's header lists, k_bw_chase by chasing again).  A chunk
 // that does not stitch is flagged and walked by k_walk_block.
 // Launch shape.  How many blocks a chunk really has is only known on the device (chunk_word_off), while the host can only
 // bound it by 25 bits per sample, four times the usual: a grid with a workgroup per POSSIBLE block spent most of its time
@@ -439,63 +467,51 @@ __device__ __forceinline__ void bw_block_prefix(const uint64_t *__restrict__ chu
         if (sl < n_list) {
             const uint64_t c = list ? (uint64_t)list[sl] : sl;
             const uint64_t begin = chunk_word_off[c], end = chunk_word_off[c + 1];
-            const bool bad = end > in_words || begin + 2 > end || end - begin > 0x7fffffffull;
-            if (!bad) nb = (uint32_t)((end - begin + B - 1u) / B);
+            if (chunk_extent_usable(begin, end, in_words, kParWalkMaxWords)) nb = (uint32_t)((end - begin + B - 1u) / B);
             if (nb > blocks_max) nb = blocks_max;
         }
-        const uint32_t incl = wave_incl_scan_dpp(nb);
-        if (sl < n_list) pre[sl + 1u] = run + incl;
-        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t incl = wave_running_prefix(nb, run);
+        if (sl < n_list) pre[sl + 1u] = incl;
     }
     if (lane == 0) pre[0] = 0;
     wave_sync();
 }
 
-template <uint32_t B, bool EMIT, bool LIST = false>
-__global__ __launch_bounds__(64) void k_bw_blocks(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                  const uint64_t *__restrict__ chunk_word_off, const uint32_t *__restrict__ list,
-                                                  uint32_t n_list, uint32_t blocks_max,
-                                                  BwBlock *__restrict__ info, const uint32_t *__restrict__ fail,
-                                                  uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
-                                                  DevStatus *st, uint32_t *__restrict__ hops, uint32_t hop_cap) {
+// The block streamer of both passes.  A wavefront strides over the real blocks (pre[]: kBwMaxList + 1 words of LDS), a block at
+// a time in blk (B words of LDS, 16-byte aligned) with the NEXT block's words in flight (registers) while body(unit, u) works
+// on the current one: without that a unit was a chain of dependent latencies -- chunk table, 8 KB of loads, the LDS work, the
+// stores -- of ~3.5 us, and 84 units per wavefront were the kernel's 0.3 ms on config 5 whatever the chase cost
+// (profiles/r04_notes.md).  fail (optional): the chunks k_bw_scan gave up on, whose blocks are passed over.
+struct BwUnit {
+    bool ok;
+    uint64_t begin;  // the chunk's first word
+    ChunkGeom f;
+    uint32_t b, b0, len_w, blk_len;  // block b of the chunk = its words [b0, b0 + blk_len), of len_w
+};
+template <uint32_t B, class Body>
+__device__ __forceinline__ void bw_stream_blocks(const Geom &G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                 const uint64_t *__restrict__ chunk_word_off, const uint32_t *__restrict__ list,
+                                                 uint32_t n_list, uint32_t blocks_max, const uint32_t *__restrict__ fail,
+                                                 uint32_t *blk, uint32_t *pre, Body body) {
     constexpr int NV = B / 256;
-    __shared__ __attribute__((aligned(16))) uint32_t blk[B];
-    __shared__ uint16_t hop[EMIT ? B / 2 : 2];  // header positions inside the block (a waveform has at least one payload word)
-    __shared__ uint16_t cand[EMIT ? 2 : kBwCandCap];  // the fast path's candidates, in position order
-    __shared__ uint32_t pre[kBwMaxList + 1];
     const int lane = lane_id();
     bw_block_prefix<B>(chunk_word_off, in_words, list, n_list, blocks_max, pre, lane);
     const uint32_t total = pre[n_list];
-    // A block at a time per wavefront, the NEXT block's words in flight (registers) while the current one is worked on in LDS:
-    // without that a unit was a chain of dependent latencies -- chunk table, 8 KB of loads, the LDS work, the stores --
-    // of ~3.5 us, and 84 units per wavefront were the kernel's 0.3 ms on config 5 whatever the chase cost (round 4).
-    struct Unit {
-        bool ok;
-        uint64_t c, begin, wbase;
-        uint32_t b, b0, len_w, blk_len, W, L, n_samples;
-    };
     uint32_t cached_slot = 0xffffffffu;
-    Unit cached{};
+    BwUnit cached{};
     auto locate_unit = [&](uint32_t unit) __attribute__((always_inline)) {
-        uint32_t lo = 0, hi = n_list;  // invariant: pre[lo] <= unit < pre[hi]
-        while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (pre[mid] <= unit) lo = mid; else hi = mid;
-        }
-        const uint32_t slot = lo;
+        const uint32_t slot = slot_of(pre, n_list, unit);
         if (slot != cached_slot) {  // (a wavefront's consecutive units mostly lie in one chunk: its table entry is read once)
             cached_slot = slot;
             const uint64_t cc = list ? (uint64_t)list[slot] : slot;
-            cached.c = cc;
-            if (G.uniform) { cached.W = G.u_n_waves; cached.L = G.u_wave_len; cached.n_samples = G.u_n_samples; cached.wbase = cc * cached.W; }
-            else { const ChunkDesc d = G.chunks[cc]; cached.W = d.n_waves; cached.L = d.wave_len; cached.n_samples = d.n_samples; cached.wbase = d.wave_base; }
+            cached.f = chunk_geom(G, cc);
             cached.begin = chunk_word_off[cc];
             cached.len_w = (uint32_t)(chunk_word_off[cc + 1] - cached.begin);  // (a chunk with an unusable extent has no blocks)
-            cached.ok = !(EMIT && fail[cc]);
+            cached.ok = !(fail && fail[cc]);
         }
-        Unit u = cached;
+        BwUnit u = cached;
         u.b = unit - pre[slot];
-        u.b0 = u.b * B;  // block = words [b0, b0 + B) of the chunk
+        u.b0 = u.b * B;
         if (u.b0 >= u.len_w) u.ok = false;  // (only a chunk cut at the host's bound; flagged by k_bw_scan)
         u.blk_len = u.ok ? (u.len_w - u.b0 < B ? u.len_w - u.b0 : B) : 0u;
         return u;
@@ -503,7 +519,7 @@ __global__ __launch_bounds__(64) void k_bw_blocks(Geom G, const uint32_t *__rest
     // the block's words: unconditional 16-byte loads (any 4-byte alignment: a chunk starts anywhere) from an address clamped
     // into the stream; what the clamp moved and what lies behind the block is sorted out when the registers go to LDS
     const int64_t a_max = (int64_t)in_words - 4;
-    auto fetch = [&](const Unit &u, uint4 (&v)[NV]) __attribute__((always_inline)) {
+    auto fetch = [&](const BwUnit &u, uint4 (&v)[NV]) __attribute__((always_inline)) {
         const int64_t a0 = (int64_t)(u.begin + u.b0);
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -512,7 +528,7 @@ __global__ __launch_bounds__(64) void k_bw_blocks(Geom G, const uint32_t *__rest
             v[j] = *reinterpret_cast<const uint4 *>(in + ac);
         }
     };
-    auto store = [&](const Unit &u, const uint4 (&v)[NV]) __attribute__((always_inline)) {
+    auto store = [&](const BwUnit &u, const uint4 (&v)[NV]) __attribute__((always_inline)) {
         const uint64_t a0 = u.begin + u.b0;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
@@ -530,166 +546,174 @@ __global__ __launch_bounds__(64) void k_bw_blocks(Geom G, const uint32_t *__rest
         }
     };
     uint4 img[NV];
-    Unit cur{};
+    BwUnit cur{};
     cur.ok = false;
     if (blockIdx.x < total) { cur = locate_unit(blockIdx.x); if (cur.ok) fetch(cur, img); }
     for (uint32_t unit = blockIdx.x; unit < total; unit += gridDim.x) {
         wave_sync();  // (the previous block's LDS reads are done)
-        const Unit me_u = cur;
-        if (me_u.ok) store(me_u, img);
+        const BwUnit me = cur;
+        if (me.ok) store(me, img);
         if (unit + gridDim.x < total) { cur = locate_unit(unit + gridDim.x); if (cur.ok) fetch(cur, img); }
-        if (!me_u.ok) continue;
-        const uint64_t c = me_u.c, begin = me_u.begin, wbase = me_u.wbase;
-        const uint32_t b = me_u.b, b0 = me_u.b0, len_w = me_u.len_w, blk_len = me_u.blk_len, W = me_u.W, L = me_u.L, n_samples = me_u.n_samples;
-        const uint32_t max_full = (uint32_t)(((uint64_t)L * 25u + 31u) >> 5);
-        const uint32_t min_words = min_payload_words(L, G.k);
-        (void)c; (void)wbase; (void)W; (void)n_samples; (void)begin; (void)min_words;
+        if (!me.ok) continue;
         wave_sync();
-        if (!EMIT) {
-            // FAST PATH (round 4).  A payload word is 32 bits of dense code: it lies in [1, max_words] (400 for WaveformLength
-            // 512) about once in ten million words, so the block's words in that range ARE its headers, nearly always.  All of
-            // them are found at once (the block is read 16 bytes per lane and step, as below), put in position order by ballots,
-            // and held to the chain's own equalities in parallel: every candidate's position + n + 1 must be the next
-            // candidate's position, the last one's must leave the block.  One impostor (or a header beyond the list's room)
-            // and the block takes the chase below, as before.  The chase is one lane following ~20 dependent LDS reads per
-            // 2048-word block while 63 lanes wait: 0.13 us per hop, 0.33 ms for config 5's 278 000 blocks (profiles/r04_notes.md section 5).
-            {
-                const uint32_t from0 = b == 0 ? 1u : 0u;
-                uint32_t ncand = 0;
-                bool overflow = false;
-                for (uint32_t base = 0; base < blk_len; base += 256u) {
-                    const uint32_t i = base + 4u * (uint32_t)lane;
-                    const uint4 v = *reinterpret_cast<const uint4 *>(blk + i);  // (all B words were written above)
-                    const bool f0 = i + 0u >= from0 && i + 0u < blk_len && v.x - 1u < max_full;
-                    const bool f1 = i + 1u >= from0 && i + 1u < blk_len && v.y - 1u < max_full;
-                    const bool f2 = i + 2u >= from0 && i + 2u < blk_len && v.z - 1u < max_full;
-                    const bool f3 = i + 3u >= from0 && i + 3u < blk_len && v.w - 1u < max_full;
-                    const uint64_t m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2), m3 = __ballot(f3);
-                    if ((m0 | m1 | m2 | m3) == 0ull) continue;
-                    const uint64_t below = (1ull << lane) - 1ull;
-                    // candidates of lower lanes come first, then this lane's own in component order
-                    uint32_t r = ncand + (uint32_t)(__builtin_popcountll(m0 & below) + __builtin_popcountll(m1 & below) +
-                                                    __builtin_popcountll(m2 & below) + __builtin_popcountll(m3 & below));
-                    if (f0) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 0u); ++r; }
-                    if (f1) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 1u); ++r; }
-                    if (f2) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 2u); ++r; }
-                    if (f3) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 3u); ++r; }
-                    ncand += (uint32_t)(__builtin_popcountll(m0) + __builtin_popcountll(m1) + __builtin_popcountll(m2) + __builtin_popcountll(m3));
-                    overflow = overflow || ncand > kBwCandCap;
-                }
-                wave_sync();
-                bool fast = ncand != 0u && !overflow && (!LIST || ncand <= hop_cap);
-                uint32_t exit_rel = 0;
-                if (fast) {
-                    bool bad = false;
-                    for (uint32_t j0 = 0; j0 < ncand; j0 += 64u) {
-                        const uint32_t j = j0 + (uint32_t)lane;
-                        if (j < ncand) {
-                            const uint32_t pos = cand[j], n = blk[pos], nxt = pos + n + 1u;
-                            // (as in the chase: the waveform must end inside the chunk; LIST: not below 1 + k bits per sample
-                            // unless it is the chunk's last)
-                            if ((uint64_t)b0 + nxt > len_w) bad = true;
-                            if (LIST && n < min_words && b0 + nxt != len_w) bad = true;
-                            if (j + 1u < ncand) { if (nxt != (uint32_t)cand[j + 1u]) bad = true; }
-                            else { if (nxt < blk_len) bad = true; exit_rel = nxt; }
-                        }
-                    }
-                    fast = !__any(bad);
-                }
-                if (fast) {
-                    exit_rel = (uint32_t)__builtin_amdgcn_readlane((int)exit_rel, (int)((ncand - 1u) & 63u));
-                    if (LIST) {
-                        for (uint32_t j = (uint32_t)lane; j < ncand; j += 64u) {
-                            const uint32_t pos = cand[j];
-                            hops[(uint64_t)unit * hop_cap + j] = pos | (blk[pos] << 12);
-                        }
-                    }
-                    if (lane == 0) {
-                        BwBlock o;
-                        o.entry = b0 + (uint32_t)cand[0];
-                        o.count = ncand;
-                        o.exit = b0 + exit_rel;
-                        o.base = 0;
-                        info[unit] = o;
-                    }
-                    continue;
-                }
-            }
-            // candidates in position order: the first word in [1, max_words] at or after `from` (word 0 of the chunk is its
-            // sample count: block 0 starts at word 1), 256 words per step.  Never 0: a waveform has at least one payload
-            // word, while the zero-padded LAST word of a waveform is all zeros whenever its final code ends in zero bits --
-            // an impostor that would chain straight into the real header behind it
-            uint32_t from = b == 0 ? 1u : 0u;
-            uint32_t entry = 0xffffffffu, count = 0, exit_pos = 0;
-            bool found = false;
-            for (uint32_t t = 0; t < kBwTries && !found; ++t) {
-                uint32_t first = 0xffffffffu;
-                for (uint32_t base = from & ~255u; base < blk_len; base += 256u) {
-                    const uint32_t i = base + 4u * (uint32_t)lane;
-                    const uint4 v = *reinterpret_cast<const uint4 *>(blk + i);  // (all B words were written above)
-                    uint32_t f = 0xffffffffu;
-                    if (i + 3u >= from && i + 3u < blk_len && v.w - 1u < max_full) f = i + 3u;
-                    if (i + 2u >= from && i + 2u < blk_len && v.z - 1u < max_full) f = i + 2u;
-                    if (i + 1u >= from && i + 1u < blk_len && v.y - 1u < max_full) f = i + 1u;
-                    if (i + 0u >= from && i + 0u < blk_len && v.x - 1u < max_full) f = i + 0u;
-                    first = ~wave_max_u32(~f);  // minimum over the wave
-                    if (first != 0xffffffffu) break;
-                }
-                if (first == 0xffffffffu) break;
-                // chase from `first` to the block's end
-                uint32_t rel = first, cnt = 0;
-                bool ok = true;
-                while (rel < blk_len) {
-                    const uint32_t n = __builtin_amdgcn_readfirstlane(blk[rel]);
-                    // (n == 0 is no waveform: at least one bit per sample; it also bounds the headers of a block by B / 2)
-                    if (n - 1u >= max_full || (uint64_t)b0 + rel + 1u + n > len_w) { ok = false; break; }
-                    if (LIST) {
-                        // the header list for k_bw_emit: {position in the block, n}.  Its capacity counts on at least 1 + k
-                        // bits per sample (min_words) for every waveform but the chunk's last, shorter one
-                        if ((n < min_words && b0 + rel + 1u + n != len_w) || cnt >= hop_cap) { ok = false; break; }
-                        if (lane == 0) hops[(uint64_t)unit * hop_cap + cnt] = rel | (n << 12);
-                    }
-                    rel += n + 1u;
-                    ++cnt;
-                }
-                if (ok) { found = true; entry = first; count = cnt; exit_pos = b0 + rel; }
-                else from = first + 1u;
-            }
-            if (lane == 0) {
-                BwBlock o;
-                o.entry = found ? b0 + entry : 0xffffffffu;
-                o.count = count;
-                o.exit = exit_pos;
-                o.base = 0;
-                info[unit] = o;
-            }
-            continue;
-        }
-        // EMIT: chase again from the accepted entry, then write the block's part of the table
-        const BwBlock me = info[unit];
-        if (me.entry == 0xffffffffu) continue;  // a last block without a header (k_bw_scan)
-        uint32_t rel = me.entry - b0, hops = 0;
-        while (rel < blk_len) {
-            const uint32_t n = __builtin_amdgcn_readfirstlane(blk[rel]);
-            if (lane == 0) hop[hops] = (uint16_t)rel;
-            rel += n + 1u;
-            ++hops;
-        }
-        wave_sync();
-        for (uint32_t i = (uint32_t)lane; i < hops; i += 64u) {
-            const uint32_t pos = hop[i], n = blk[pos], wi = me.base + i;  // (k_bw_scan accepted the chunk: wi < W)
-            wave_off[wbase + wi] = begin + b0 + pos;
-            wave_words[wbase + wi] = n;
-            // the chunk's last waveform may be shorter than the rest: its header has tighter bounds; and no
-            // header may be below the minimum of 1 + k bits per sample (the chase only checked the upper bound)
-            if (wi + 1u == W) {
-                const uint32_t last_len = n_samples - (W - 1u) * L;
-                if (n > max_payload_words(last_len) || n < min_payload_words(last_len, G.k)) atomicOr(&st->err, kErrCorrupt);
-            } else if (n < min_payload_words(L, G.k)) {
-                atomicOr(&st->err, kErrCorrupt);
-            }
-        }
+        body(unit, me);
     }
+}
+
+// Which of the four words v at positions i ... i + 3 of a block may be headers: in [1, max_full], at or behind `from`.  Never
+// 0: a waveform has at least one payload word, while the zero-padded LAST word of a waveform is all zeros whenever its final
+// code ends in zero bits -- an impostor that would chain straight into the real header behind it
+struct Small4 { bool x, y, z, w; };
+__device__ __forceinline__ Small4 small_words(const uint4 &v, uint32_t i, uint32_t from, uint32_t blk_len, uint32_t max_full) {
+    auto small = [&](uint32_t word, uint32_t at) { return at >= from && at < blk_len && word - 1u < max_full; };
+    return Small4{small(v.x, i + 0u), small(v.y, i + 1u), small(v.z, i + 2u), small(v.w, i + 3u)};
+}
+
+// First pass: a block's entry header, the number of its headers and where its chain leaves it -> info[unit]; LIST: its
+// headers, {position in the block | n << 12}, -> hops[unit * hop_cap ...] for k_bw_emit
+template <uint32_t B, bool LIST>
+__global__ __launch_bounds__(64) void k_bw_blocks(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                  const uint64_t *__restrict__ chunk_word_off, const uint32_t *__restrict__ list,
+                                                  uint32_t n_list, uint32_t blocks_max, BwBlock *__restrict__ info,
+                                                  uint32_t *__restrict__ hops, uint32_t hop_cap) {
+    __shared__ __attribute__((aligned(16))) uint32_t blk[B];
+    __shared__ uint16_t cand[kBwCandCap];  // the fast path's candidates, in position order
+    __shared__ uint32_t pre[kBwMaxList + 1];
+    const int lane = lane_id();
+    bw_stream_blocks<B>(G, in, in_words, chunk_word_off, list, n_list, blocks_max, nullptr, blk, pre, [&](uint32_t unit, const BwUnit &u) __attribute__((always_inline)) {
+        const uint32_t b0 = u.b0, len_w = u.len_w, blk_len = u.blk_len;
+        const uint32_t max_full = max_payload_words(u.f.L), min_words = min_payload_words(u.f.L, G.k);
+        const uint32_t from0 = u.b == 0 ? 1u : 0u;  // (word 0 of the chunk is its sample count: block 0 starts at word 1)
+        // FAST PATH.  A payload word is 32 bits of dense code: it lies in [1, max_words] (400 for WaveformLength
+        // 512) about once in ten million words, so the block's words in that range ARE its headers, nearly always.  All of
+        // them are found at once (the block is read 16 bytes per lane and step, as below), put in position order by ballots,
+        // and held to the chain's own equalities in parallel: every candidate's position + n + 1 must be the next
+        // candidate's position, the last one's must leave the block.  One impostor (or a header beyond the list's room)
+        // and the block takes the chase below.  The chase is one lane following ~20 dependent LDS reads per
+        // 2048-word block while 63 lanes wait: 0.13 us per hop, 0.33 ms for config 5's 278 000 blocks (profiles/r04_notes.md section 5).
+        uint32_t ncand = 0;
+        bool overflow = false;
+        for (uint32_t base = 0; base < blk_len; base += 256u) {
+            const uint32_t i = base + 4u * (uint32_t)lane;
+            const uint4 v = *reinterpret_cast<const uint4 *>(blk + i);  // (all B words were written by the streamer)
+            const Small4 f = small_words(v, i, from0, blk_len, max_full);
+            const uint64_t m0 = __ballot(f.x), m1 = __ballot(f.y), m2 = __ballot(f.z), m3 = __ballot(f.w);
+            if ((m0 | m1 | m2 | m3) == 0ull) continue;
+            const uint64_t below = (1ull << lane) - 1ull;
+            // candidates of lower lanes come first, then this lane's own in component order
+            uint32_t r = ncand + (uint32_t)(__builtin_popcountll(m0 & below) + __builtin_popcountll(m1 & below) +
+                                            __builtin_popcountll(m2 & below) + __builtin_popcountll(m3 & below));
+            if (f.x) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 0u); ++r; }
+            if (f.y) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 1u); ++r; }
+            if (f.z) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 2u); ++r; }
+            if (f.w) { if (r < kBwCandCap) cand[r] = (uint16_t)(i + 3u); ++r; }
+            ncand += (uint32_t)(__builtin_popcountll(m0) + __builtin_popcountll(m1) + __builtin_popcountll(m2) + __builtin_popcountll(m3));
+            overflow = overflow || ncand > kBwCandCap;
+        }
+        wave_sync();
+        bool fast = ncand != 0u && !overflow && (!LIST || ncand <= hop_cap);
+        uint32_t exit_rel = 0;
+        if (fast) {
+            bool bad = false;
+            for (uint32_t j0 = 0; j0 < ncand; j0 += 64u) {
+                const uint32_t j = j0 + (uint32_t)lane;
+                if (j < ncand) {
+                    const uint32_t pos = cand[j], n = blk[pos], nxt = pos + n + 1u;
+                    // (as in the chase: the waveform must end inside the chunk; LIST: not below 1 + k bits per sample
+                    // unless it is the chunk's last)
+                    if ((uint64_t)b0 + nxt > len_w) bad = true;
+                    if (LIST && n < min_words && b0 + nxt != len_w) bad = true;
+                    if (j + 1u < ncand) { if (nxt != (uint32_t)cand[j + 1u]) bad = true; }
+                    else { if (nxt < blk_len) bad = true; exit_rel = nxt; }
+                }
+            }
+            fast = !__any(bad);
+        }
+        if (fast) {
+            exit_rel = (uint32_t)__builtin_amdgcn_readlane((int)exit_rel, (int)((ncand - 1u) & 63u));
+            if (LIST) {
+                for (uint32_t j = (uint32_t)lane; j < ncand; j += 64u) {
+                    const uint32_t pos = cand[j];
+                    hops[(uint64_t)unit * hop_cap + j] = pos | (blk[pos] << 12);
+                }
+            }
+            if (lane == 0) info[unit] = BwBlock{b0 + (uint32_t)cand[0], ncand, b0 + exit_rel, 0u};
+            return;
+        }
+        // THE CHASE.  Candidates in position order: the first small word at or after `from`, 256 words per step
+        uint32_t from = from0;
+        uint32_t entry = 0xffffffffu, count = 0, exit_pos = 0;
+        bool found = false;
+        for (uint32_t t = 0; t < kBwTries && !found; ++t) {
+            uint32_t first = 0xffffffffu;
+            for (uint32_t base = from & ~255u; base < blk_len; base += 256u) {
+                const uint32_t i = base + 4u * (uint32_t)lane;
+                const Small4 s = small_words(*reinterpret_cast<const uint4 *>(blk + i), i, from, blk_len, max_full);
+                uint32_t f = 0xffffffffu;
+                if (s.w) f = i + 3u;
+                if (s.z) f = i + 2u;
+                if (s.y) f = i + 1u;
+                if (s.x) f = i + 0u;
+                first = ~wave_max_u32(~f);  // minimum over the wave
+                if (first != 0xffffffffu) break;
+            }
+            if (first == 0xffffffffu) break;
+            // chase from `first` to the block's end
+            uint32_t rel = first, cnt = 0;
+            bool ok = true;
+            while (rel < blk_len) {
+                const uint32_t n = __builtin_amdgcn_readfirstlane(blk[rel]);
+                // (n == 0 is no waveform: at least one bit per sample; it also bounds the headers of a block by B / 2)
+                if (n - 1u >= max_full || (uint64_t)b0 + rel + 1u + n > len_w) { ok = false; break; }
+                if (LIST) {
+                    // the header list for k_bw_emit: {position in the block, n}.  Its capacity counts on at least 1 + k
+                    // bits per sample (min_words) for every waveform but the chunk's last, shorter one
+                    if ((n < min_words && b0 + rel + 1u + n != len_w) || cnt >= hop_cap) { ok = false; break; }
+                    if (lane == 0) hops[(uint64_t)unit * hop_cap + cnt] = rel | (n << 12);
+                }
+                rel += n + 1u;
+                ++cnt;
+            }
+            if (ok) { found = true; entry = first; count = cnt; exit_pos = b0 + rel; }
+            else from = first + 1u;
+        }
+        if (lane == 0) info[unit] = BwBlock{found ? b0 + entry : 0xffffffffu, count, exit_pos, 0u};
+    });
+}
+
+// Second pass where the first one kept no header lists: chase again from the entry k_bw_scan accepted, then write the
+// block's part of the table
+template <uint32_t B>
+__global__ __launch_bounds__(64) void k_bw_chase(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
+                                                 const uint64_t *__restrict__ chunk_word_off, const uint32_t *__restrict__ list,
+                                                 uint32_t n_list, uint32_t blocks_max, const BwBlock *__restrict__ info,
+                                                 const uint32_t *__restrict__ fail, uint64_t *__restrict__ wave_off,
+                                                 uint32_t *__restrict__ wave_words, DevStatus *st) {
+    __shared__ __attribute__((aligned(16))) uint32_t blk[B];
+    __shared__ uint16_t hop[B / 2];  // header positions inside the block (a waveform has at least one payload word)
+    __shared__ uint32_t pre[kBwMaxList + 1];
+    const int lane = lane_id();
+    bw_stream_blocks<B>(G, in, in_words, chunk_word_off, list, n_list, blocks_max, fail, blk, pre, [&](uint32_t unit, const BwUnit &u) __attribute__((always_inline)) {
+        const BwBlock me = info[unit];
+        if (me.entry == 0xffffffffu) return;  // a last block without a header (k_bw_scan)
+        const HeaderBounds hb = header_bounds(u.f.L, u.f.N, u.f.W, G.k);
+        uint32_t rel = me.entry - u.b0, n_hops = 0;
+        while (rel < u.blk_len) {
+            const uint32_t n = __builtin_amdgcn_readfirstlane(blk[rel]);
+            if (lane == 0) hop[n_hops] = (uint16_t)rel;
+            rel += n + 1u;
+            ++n_hops;
+        }
+        wave_sync();
+        for (uint32_t i = (uint32_t)lane; i < n_hops; i += 64u) {
+            const uint32_t pos = hop[i], n = blk[pos], wi = me.base + i;  // (k_bw_scan accepted the chunk: wi < W)
+            wave_off[u.f.base + wi] = u.begin + u.b0 + pos;
+            wave_words[u.f.base + wi] = n;
+            // the first pass held n to [1, max_words] only: no header may be below the minimum of 1 + k bits per sample, and the
+            // chunk's last waveform may be shorter than the rest, with tighter bounds
+            if (!hb.ok(n, wi + 1u == u.f.W)) atomicOr(&st->err, kErrCorrupt);
+        }
+    });
 }
 
 // one wavefront per chunk: stitch the blocks, first-waveform index of every block, verdict
@@ -703,12 +727,10 @@ __global__ __launch_bounds__(64) void k_bw_scan(Geom G, const uint32_t *__restri
     bw_block_prefix<B>(chunk_word_off, in_words, list, n_list, blocks_max, pre, lane);
     const uint64_t slot = blockIdx.x;
     const uint64_t c = list ? (uint64_t)list[slot] : slot;
-    uint32_t W, L, N;
-    if (G.uniform) { W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; }
-    else { const ChunkDesc d = G.chunks[c]; W = d.n_waves; L = d.wave_len; N = d.n_samples; }
+    const ChunkGeom f = chunk_geom(G, c);
     const uint64_t begin = chunk_word_off[c], end = chunk_word_off[c + 1];
-    bool bad = end > in_words || begin + 2 > end || end - begin > 0x7fffffffull;
-    if (!bad && in[begin] != N) bad = true;
+    bool bad = !chunk_extent_usable(begin, end, in_words, kParWalkMaxWords);
+    if (!bad && in[begin] != f.N) bad = true;
     const uint32_t len_w = bad ? 0u : (uint32_t)(end - begin);
     const uint32_t n_blocks = (len_w + B - 1u) / B;
     if (n_blocks > blocks_max) bad = true;
@@ -750,15 +772,13 @@ __global__ __launch_bounds__(64) void k_bw_scan(Geom G, const uint32_t *__restri
                 }
             }
             if (__any(lane_bad)) { bad = true; break; }
-            const uint32_t inc = wave_incl_scan_dpp(b < n_blocks ? o.count : 0u);
-            if (b < n_blocks) my[b].base = run + inc - o.count;
-            run += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+            const uint32_t inc = wave_running_prefix(b < n_blocks ? o.count : 0u, run);
+            if (b < n_blocks) my[b].base = inc - o.count;
         }
     }
-    if (!bad && run != W) bad = true;
-    // the last waveform may be shorter: its header has a tighter bound than the blocks checked
+    if (!bad && run != f.W) bad = true;
+    // (the last waveform may be shorter: its header has a tighter bound than the blocks checked; the second pass holds it to it)
     if (lane == 0) fail[c] = bad ? 1u : 0u;
-    (void)L;
 }
 
 // Second pass where the first one left the header list (bw_hop_cap() != 0): a wavefront per block, striding over the real
@@ -776,49 +796,27 @@ __global__ __launch_bounds__(256) void k_bw_emit(Geom G, uint64_t in_words, cons
     if (wv == 0) bw_block_prefix<B>(chunk_word_off, in_words, list, n_list, blocks_max, pre, lane);
     __syncthreads();
     const uint32_t total = pre[n_list];
-    // A LANE per block (round 4; a wavefront per block before): a block holds ~20 headers, so 44 lanes of a wavefront had
+    // A LANE per block (a wavefront per block before): a block holds ~20 headers, so 44 lanes of a wavefront had
     // nothing to do, and every block paid its chain of dependent loads (list, table entry, info) alone -- 0.12-0.14 ms on
-    // config 5 for 11 MB of table.  64 blocks' chains now travel together.
+    // config 5 for 11 MB of table.  64 blocks' chains now travel together (profiles/r04_notes.md).
     for (uint32_t unit = blockIdx.x * 256u + threadIdx.x; unit < total; unit += gridDim.x * 256u) {
-        uint32_t lo = 0, hi = n_list;  // invariant: pre[lo] <= unit < pre[hi]
-        while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (pre[mid] <= unit) lo = mid; else hi = mid;
-        }
-        const uint32_t slot = lo, b = unit - pre[lo];
+        const uint32_t slot = slot_of(pre, n_list, unit), b = unit - pre[slot];
         const uint64_t c = list ? (uint64_t)list[slot] : slot;
         if (fail[c]) continue;
         const BwBlock me = info[unit];
         if (me.entry == 0xffffffffu) continue;  // a last block without a header (k_bw_scan)
-        uint32_t W, L, n_samples;
-        uint64_t wbase;
-        if (G.uniform) { W = G.u_n_waves; L = G.u_wave_len; n_samples = G.u_n_samples; wbase = c * W; }
-        else { const ChunkDesc d = G.chunks[c]; W = d.n_waves; L = d.wave_len; n_samples = d.n_samples; wbase = d.wave_base; }
+        const ChunkGeom f = chunk_geom(G, c);
         const uint64_t at = chunk_word_off[c] + (uint64_t)b * B;
         const uint32_t *hp = hops + (uint64_t)unit * hop_cap;
         for (uint32_t i = 0; i < me.count; ++i) {
             const uint32_t h = hp[i], pos = h & 0xfffu, n = h >> 12, wi = me.base + i;
-            wave_off[wbase + wi] = at + pos;
-            wave_words[wbase + wi] = n;
+            wave_off[f.base + wi] = at + pos;
+            wave_words[f.base + wi] = n;
             // the chunk's last waveform may be shorter than the rest: its header has tighter bounds (the others were held
-            // to [min, max] by the chase)
-            if (wi + 1u == W) {
-                const uint32_t last_len = n_samples - (W - 1u) * L;
-                if (n > max_payload_words(last_len) || n < min_payload_words(last_len, G.k)) atomicOr(&st->err, kErrCorrupt);
-            }
+            // to [min, max] by the first pass)
+            if (wi + 1u == f.W && !header_bounds(f.L, f.N, f.W, G.k).ok(n, true)) atomicOr(&st->err, kErrCorrupt);
         }
     }
-}
-
-__global__ __launch_bounds__(64) void k_walk_block_only(Geom G, const uint32_t *__restrict__ in, uint64_t in_words,
-                                                        const uint64_t *__restrict__ chunk_word_off,
-                                                        uint64_t *__restrict__ wave_off, uint32_t *__restrict__ wave_words,
-                                                        DevStatus *st, const uint32_t *__restrict__ only) {
-    __shared__ __attribute__((aligned(16))) uint32_t blk[kWalkBlockWords];
-    __shared__ __attribute__((aligned(8))) uint2 hop[kWalkHopCap];
-    const uint64_t c = blockIdx.x;
-    if (c >= G.n_chunks || !only[c]) return;
-    walk_chunk_block(G, c, in, in_words, chunk_word_off, wave_off, wave_words, nullptr, st, blk, hop);
 }
 
 // Side-band decode (drx_decode_with_wave_words): the caller hands over the n_i table an encode left behind (SURVEY section 7:
@@ -835,21 +833,21 @@ __global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t 
     __shared__ uint64_t wsum[4];
     const uint64_t c = list ? (uint64_t)list[blockIdx.x] : blockIdx.x;
     const int lane = lane_id(), wv = wave_id();
-    uint64_t base;
-    uint32_t W, L, N;
-    if (G.uniform) { base = c * G.u_n_waves; W = G.u_n_waves; L = G.u_wave_len; N = G.u_n_samples; }
-    else { const ChunkDesc d = G.chunks[c]; base = d.wave_base; W = d.n_waves; L = d.wave_len; N = d.n_samples; }
+    const ChunkGeom f = chunk_geom(G, c);
+    const uint32_t W = f.W;
+    const uint64_t base = f.base;
+    const HeaderBounds hb = header_bounds(f.L, f.N, W, G.k);
     const uint64_t off0 = chunk_word_off[c], off1 = chunk_word_off[c + 1];
+    // (its own, weaker extent test -- not chunk_extent_usable(): every position is checked against [off0, off1) below)
     bool bad = off1 > in_words || off0 >= off1;  // (the same in every lane here; block-wide after every round below)
     uint64_t run = 1;  // the chunk header word
     for (uint32_t i0 = 0; i0 < W; i0 += 256) {
         const uint32_t i = i0 + threadIdx.x;
         const uint32_t n = (i < W) ? n_in[base + i] : 0u;
-        const uint32_t len = (i < W) ? ((i + 1u == W) ? N - i * L : L) : 0u;
         // An entry outside the bounds of its waveform never enters the prefix sum (64-bit: 256 entries of up to 25 bits per
         // sample of a 2^31-sample waveform do not fit 32), so no later position can wrap below off0 or past 2^64; and the
         // whole chunk is rejected before any lane looks at the stream.
-        const bool n_ok = i >= W || (n <= max_payload_words(len) && n >= min_payload_words(len, G.k));
+        const bool n_ok = i >= W || hb.ok(n, i + 1u == W);
         const uint64_t v = (i < W && n_ok) ? (uint64_t)n + 1u : 0u;
         uint64_t inc = v;
 #pragma unroll
@@ -875,7 +873,7 @@ __global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t 
         run += all;
         bad = __syncthreads_or(mine_bad) != 0;  // (also keeps wsum until every lane has read it)
     }
-    if (threadIdx.x == 0 && !bad && (off0 + run != off1 || in[off0] != N)) bad = true;
+    if (threadIdx.x == 0 && !bad && (off0 + run != off1 || in[off0] != f.N)) bad = true;
     if (bad && threadIdx.x == 0) atomicOr(&st->err, kErrCorrupt);
 }
 
@@ -883,15 +881,7 @@ __global__ __launch_bounds__(256) void k_sideband_tables(Geom G, const uint32_t 
 // ---------------------------------------------------------------------------
 // host side: which walk takes a batch, the parallel walks' scratch, the launchers
 // ---------------------------------------------------------------------------
-// limits of the parallel header walks (see k_walk_parallel / k_bw_blocks)
-constexpr uint32_t kPwMaxWaves = 3584;   // waveforms per chunk the chunk-wide walk's scan form takes (leaves room for impostors)
-constexpr uint64_t kPwMaxChunks = 224;  // the walks that READ the chunks (block-parallel; the chunk-wide walk's scan form,
-                                        // DRX_DBG_WALK_BY_SCAN): more chunks hide the serial walk behind the decoding
-// the chunk-wide walk by chains (k_walk_sparse) costs ~60 us per 512 chunks whatever their size: every uniform batch of
-// long waveforms takes it, the headline's 500 chunks included (4.74 + 0.08 ms against 5.33 with the walk inside the launch)
-constexpr uint64_t kSwMaxChunks = 1u << 20;
-constexpr uint32_t kSwMinWaves = 8, kSwMaxWaves = 8192;  // ... chunks of 8 ... 8192 waveforms (its scan form: 64 ... kPwMaxWaves)
-
+// (the limits of each parallel walk: with its kernels above)
 // The chunk-wide walk takes such a chunk: the one place that spells its range
 static bool chunk_wide_walk_takes(uint32_t n_waves, uint32_t wave_len) {
     return wave_len > kWalkShortLen && n_waves >= kSwMinWaves && n_waves <= kSwMaxWaves;
@@ -1112,15 +1102,17 @@ void launch_walk_blocks(const StreamCall &c) {
         constexpr uint32_t B = decltype(btag)::value;
         const uint32_t bmax = P.bw_blocks_max * (kWalkBlockWords / B);
         const unsigned grid = 256u * P.bw_waves_per_cu;
+        // (one argument list for both forms of the first pass: without lists P.hops is nullptr and P.bw_hop_cap 0, a placeholder
+        // that stays -- a kernel without the two parameters would be a second signature for the same body)
         if (P.hops)
-            k_bw_blocks<B, false, true><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, nullptr, nullptr, nullptr, c.d_status, P.hops, P.bw_hop_cap);
+            k_bw_blocks<B, true><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.hops, P.bw_hop_cap);
         else
-            k_bw_blocks<B, false><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, nullptr, nullptr, nullptr, c.d_status, nullptr, 0u);
+            k_bw_blocks<B, false><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.hops, P.bw_hop_cap);
         k_bw_scan<B><<<n, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail);
         if (P.hops)
             k_bw_emit<B><<<256u * 8u, 256, 0, c.s>>>(G, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, P.hops, P.bw_hop_cap, c.d_wave_off, c.d_wave_words, c.d_status);
         else
-            k_bw_blocks<B, true><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, c.d_wave_off, c.d_wave_words, c.d_status, nullptr, 0u);
+            k_bw_chase<B><<<grid, 64, 0, c.s>>>(G, c.d_in, c.in_words, c.d_chunk_word_off, list, n, bmax, P.info, P.bw_fail, c.d_wave_off, c.d_wave_words, c.d_status);
     };
     if (P.bw_B == 1024u) run_bw(std::integral_constant<uint32_t, 1024>{});
     else if (P.bw_B == 2048u) run_bw(std::integral_constant<uint32_t, 2048>{});
