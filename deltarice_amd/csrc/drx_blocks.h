@@ -20,6 +20,7 @@
 #include "drx_device.h"
 #include "drx_internal.h"
 #include "drx_iir_math.h"
+#include "drx_lookback.h"
 #include "drx_pulse_runs.h"
 #include "drx_window_rows.h"
 
@@ -45,6 +46,7 @@ __host__ __device__ constexpr uint32_t blk_lane_cap(int segw) { return segw <= 1
 constexpr uint32_t kBlkPre = 8;          // words kept in front of a block: lane 0's run-up
 constexpr uint32_t kBlkGuessBits = 128;  // run-up in front of a segment (a parse is in step after a few codes; 96, 128,
                                          // 160 and 224 bits measured: within 4 % of one another, profiles/r02_notes.md)
+constexpr int kBlkGateSleep = 4;         // s_sleep between two polls of the nearest predecessor's entry (drx_lookback.h)
 constexpr uint32_t kBlkRounds = 8;       // tickets per resident workgroup a launch should at least have (see run_len)
 constexpr uint32_t kBlkTail = 4;         // words behind a block: a code that starts inside may end 24 bits behind it,
                                          // and a window reads three words

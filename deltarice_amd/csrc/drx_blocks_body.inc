@@ -439,50 +439,19 @@
                         ex_s = 0;
                     }
                 } else if (first_of_run) {
-                    // decoupled look-back over the blocks of the waveform in front of this one
+                    // lookback_walk (drx_lookback.h): entry sidx = {samples << 16 | 16-bit residual sum} of a block, scanned from
+                    // block 0 of this waveform, the two fields summed apart
                     ex_c = 0;
                     ex_s = 0;
-                    if (lane == 0) __hip_atomic_store(state + sidx, kScanAgg | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const int64_t first = (int64_t)sidx - (int64_t)blk;  // block 0 of this waveform
-                    int64_t base = (int64_t)sidx - 1;
-                    uint32_t spins = 0;
-                    // the nearest predecessor alone first (one 8-byte load per poll, not a window from every waiting workgroup)
-                    for (;;) {
-                        uint64_t v = 0;
-                        if (lane == 0) v = __hip_atomic_load(state + base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 62)) != 0) break;
-                        __builtin_amdgcn_s_sleep(4);
-                        if (++spins > (1u << 22)) break;  // (the window loop below reports it)
-                    }
-                    for (;;) {
-                        // lane l looks at predecessors base - l (nearer) and base - 64 - l (farther)
-                        const int64_t i0 = base - lane, i1 = base - 64 - lane;
-                        uint64_t s0v = kScanPrefix, s1v = kScanPrefix;  // in front of block 0: an empty prefix
-                        if (i0 >= first) s0v = __hip_atomic_load(state + i0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (i1 >= first) s1v = __hip_atomic_load(state + i1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const uint32_t st0 = (uint32_t)(s0v >> 62), st1 = (uint32_t)(s1v >> 62);
-                        const uint64_t p0 = __ballot(st0 == 2u), z0 = __ballot(st0 == 0u);
-                        const uint64_t p1 = __ballot(st1 == 2u), z1 = __ballot(st1 == 0u);
-                        const int fp = p0 ? __builtin_ctzll(p0) : (p1 ? 64 + __builtin_ctzll(p1) : 128);  // nearest prefix
-                        const uint64_t near0 = fp >= 64 ? ~0ull : ((1ull << fp) - 1ull);
-                        const uint64_t near1 = fp >= 128 ? ~0ull : (fp > 64 ? ((1ull << (fp - 64)) - 1ull) : 0ull);
-                        if ((z0 & near0) | (z1 & near1)) {  // a nearer predecessor has not published yet
-                            __builtin_amdgcn_s_sleep(1);
-                            if (++spins > (1u << 22)) { if (lane == 0) atomicOr(&st->err, kErrInternal); break; }
-                            continue;
-                        }
-                        const uint64_t v0 = (lane <= fp) ? (s0v & kScanValMask) : 0ull;
-                        const uint64_t v1 = (64 + lane <= fp) ? (s1v & kScanValMask) : 0ull;
+                    scan_publish(state, sidx, kScanAgg | mine, lane);
+                    lookback_walk<kBlkGateSleep>(state, sidx, (int64_t)sidx - (int64_t)blk, lane, st, [&](uint64_t s0, uint64_t s1, bool in0, bool in1) {
+                        const uint64_t v0 = in0 ? (s0 & kScanValMask) : 0ull, v1 = in1 ? (s1 & kScanValMask) : 0ull;
                         ex_c += wave_sum_u64((v0 >> 16) + (v1 >> 16));
                         ex_s += wave_sum_u64((v0 & 0xffffull) + (v1 & 0xffffull));
-                        if (fp < 128) break;
-                        base -= 128;
-                    }
+                    });
                 }
                 // everything in front of this block is known now: its successors find a prefix here
-                if (lane == 0)
-                    __hip_atomic_store(state + sidx, kScanPrefix | ((((ex_c + tot_c) << 16) | ((ex_s + tot_s) & 0xffffull)) & kScanValMask),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                scan_publish(state, sidx, kScanPrefix | ((((ex_c + tot_c) << 16) | ((ex_s + tot_s) & 0xffffull)) & kScanValMask), lane);
                 if (lane == 0) { s_b[0] = ex_c; s_b[1] = ex_s; }
             }
             blk_barrier();

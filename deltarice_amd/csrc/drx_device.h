@@ -187,9 +187,6 @@ __device__ __forceinline__ uint32_t wave_shr1_carry(uint32_t v, uint32_t first) 
     return r;
 }
 
-// decoupled look-back entries: 2 status bits on top of the value (the word is its own flag; zero = not yet)
-constexpr uint64_t kScanAgg = 1ull << 62, kScanPrefix = 2ull << 62, kScanValMask = (1ull << 62) - 1ull;
-
 __device__ __forceinline__ uint32_t lds_addr(const uint32_t *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)p;
 }

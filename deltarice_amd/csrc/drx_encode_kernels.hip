@@ -22,6 +22,7 @@
 #include "drx_internal.h"
 #include "drx_device.h"
 #include "drx_encode.h"
+#include "drx_lookback.h"
 
 namespace drx {
 
@@ -313,7 +314,6 @@ __global__ __launch_bounds__(256) void k_encode_pack(Geom G, uint64_t g0, const 
 // (the packed tile code: drx_encode.h)
 
 constexpr int kEncWaves = 8;      // waveforms (wavefronts) per workgroup = per ticket
-constexpr int kLbWin = 2;         // look-back window of k_encode_fused in units of 64 entries
 constexpr int kEncGateSleep = 8;  // s_sleep between two polls of the nearest predecessor's entry
 
 // WV x CAPW: waveforms per workgroup x LDS words per waveform.  8 x 2048 (9.3 bits per sample at WaveformLength 7000) is the
@@ -389,12 +389,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
     wave_sync();
 
     // ---- position of this waveform ----
-    // Prefix sum over v_j = 1 + n_j (+1 for a chunk's first waveform).  The kEncWaves waveforms of
-    // this workgroup are summed through LDS; wave 0 then runs a decoupled look-back over ONE entry
-    // per workgroup, 128 entries per poll.  (One entry per waveform and 64 per poll capped the whole
-    // encoder at ~64 waveforms per memory round trip, i.e. ~9 ms for 1M waveforms: a predecessor's
-    // prefix is published one round trip after its aggregate, so the frontier of known prefixes
-    // advances by at most one window per round trip.)
+    // Prefix sum over v_j = 1 + n_j (+1 for a chunk's first waveform).  The kEncWaves waveforms of this workgroup are summed
+    // through LDS; wave 0 then runs the decoupled look-back over ONE entry per workgroup.
     const uint64_t mine = live ? 1ull + n + (r.idx == 0 ? 1ull : 0ull) : 0ull;
     if (lane == 0) s_mine[wv] = mine;
     __syncthreads();
@@ -402,69 +398,8 @@ __global__ __launch_bounds__(64 * WV, 1) void k_encode_fused(Geom G, const int16
         uint64_t block_sum = 0;
 #pragma unroll
         for (int i = 0; i < kEncWaves; ++i) block_sum += rfl64(s_mine[i]);
-        const uint64_t T = rfl(s_ticket);
-        uint64_t excl_blk = 0;
-        if (T == 0) {
-            if (lane == 0) __hip_atomic_store(scan_state + T, kScanPrefix | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            if (lane == 0) __hip_atomic_store(scan_state + T, kScanAgg | block_sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int64_t base = (int64_t)T - 1;
-            uint32_t spins = 0;
-            // Wait for the NEAREST predecessor alone first: one 8-byte load per poll instead of a whole window from every
-            // waiting workgroup.  Workgroups finish roughly in ticket order, so when T - 1 has published, the window behind it
-            // has too; and ~500 workgroups polling 128 entries each were a fabric load of their own beside the encoder's
-            // streaming reads (agent-scope loads are served by the memory side, not by L2).
-            for (;;) {
-                uint64_t v = 0;
-                if (lane == 0) v = __hip_atomic_load(scan_state + base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 62)) != 0) break;
-                __builtin_amdgcn_s_sleep(kEncGateSleep);
-                if (++spins > (1u << 22)) break;  // (the window loop below reports it)
-            }
-            // kLbWin x 64 entries per poll.  The frontier of known prefixes advances one window per hop (a hop = an
-            // agent-scope store becoming visible + an agent-scope load, 3-5 us under the encoder's own streaming loads), so
-            // the window bounds the rate of the whole kernel: 128 entries carried ~25 workgroups per microsecond, just what
-            // 1M waveforms in 6 ms need (round 3: without the look-back the kernel took 4.5 ms instead of 6.0)
-            for (;;) {
-                // lane l looks at predecessors base - 64 j - l, j = 0 (nearest) .. kLbWin - 1
-                uint64_t sv[kLbWin];
-                int fp = 64 * kLbWin;          // position of the nearest prefix in the window (0 = nearest predecessor)
-                bool hole = false;             // an entry nearer than that prefix has not been published yet
-#pragma unroll
-                for (int j = 0; j < kLbWin; ++j) {
-                    const int64_t i = base - 64 * j - lane;
-                    sv[j] = kScanPrefix;  // before the first workgroup: an empty prefix
-                    if (i >= 0) sv[j] = __hip_atomic_load(scan_state + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-#pragma unroll
-                for (int j = 0; j < kLbWin; ++j) {
-                    const uint32_t stj = (uint32_t)(sv[j] >> 62);
-                    const uint64_t pj = __ballot(stj == 2u), zj = __ballot(stj == 0u);
-                    if (fp == 64 * kLbWin) {  // no prefix found in the nearer groups
-                        const int f = pj ? __builtin_ctzll(pj) : 64;
-                        const uint64_t nearer = f >= 64 ? ~0ull : ((1ull << f) - 1ull);
-                        hole = hole || (zj & nearer) != 0;
-                        if (pj) fp = 64 * j + f;
-                    }
-                }
-                if (hole) {  // a nearer predecessor has not published yet
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > (1u << 22)) {  // cannot happen with a zeroed scan_state; never hang the GPU
-                        if (lane == 0) atomicOr(&st->err, kErrInternal);
-                        break;
-                    }
-                    continue;
-                }
-                uint64_t c = 0;
-#pragma unroll
-                for (int j = 0; j < kLbWin; ++j) c += (64 * j + lane <= fp) ? (sv[j] & kScanValMask) : 0ull;
-                excl_blk += wave_sum_u64(c);
-                if (fp < 64 * kLbWin) break;
-                base -= 64 * kLbWin;
-            }
-            if (lane == 0)
-                __hip_atomic_store(scan_state + T, kScanPrefix | (excl_blk + block_sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        // lookback_scan_sum (drx_lookback.h): entry T = the words of workgroup T's waveforms, scanned from workgroup 0
+        const uint64_t excl_blk = lookback_scan_sum<kEncGateSleep>(scan_state, (int64_t)rfl(s_ticket), 0, block_sum, lane, st);
         if (lane == 0) s_excl = excl_blk;
     }
     __syncthreads();
@@ -745,8 +680,8 @@ hipError_t launch_estimate_words(const Geom &G, const int16_t *d_in, unsigned lo
     return hipGetLastError();
 }
 
-// Single-pass encode (k_encode_fused).  d_scan: uint64[total_waves] + one uint32 ticket
-// word after it, zeroed here on the stream before every launch.
+// Single-pass encode (k_encode_fused).  d_scan: uint64[total_waves + 2], zeroed here on the stream before every launch: the
+// look-back entries, one per WORKGROUP (the first ceil(total_waves / WV) words), and the uint32 ticket in word total_waves.
 hipError_t launch_encode_fused(const EncodeCall &c, int wide, uint64_t *d_scan) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;

@@ -31,9 +31,11 @@
 #include "drx_device.h"
 #include "drx_internal.h"
 #include "drx_iir_math.h"
+#include "drx_lookback.h"
 
 namespace drx {
 
+constexpr int kIirGateSleep = 4;  // s_sleep between two polls of the nearest predecessor's entry (drx_lookback.h)
 // table layout (uint32 each): PL[7][9] = A^(M * 2^d), d = 0..6 | PLANE[64][9] = A^(M l) | PTP[kIirWin + 1][9] = P^j | c1 c2 c3 sgn
 constexpr uint32_t kIirPL = 0, kIirPLANE = 7 * 9, kIirPTP = kIirPLANE + 64 * 9, kIirC = kIirPTP + (kIirWin + 1) * 9;
 static_assert(kIirC + 4 == kIirTabWords, "table layout");
@@ -174,57 +176,28 @@ __global__ __launch_bounds__(kIirThreads) void k_iir_tiles(Geom G, const uint64_
         for (int w = 0; w < NWV; ++w) B = lo16(add(mul(PW, B), V3{s_F[w][0], s_F[w][1], s_F[w][2]}));
         const uint64_t bval = (uint64_t)B.x | ((uint64_t)B.y << 16) | ((uint64_t)B.z << 32);
         V3 x{0u, 0u, 0u};
-        if (q.t == 0) {
-            if (lane == 0) __hip_atomic_store(state + u, kScanPrefix | bval, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else {
-            if (lane == 0) __hip_atomic_store(state + u, kScanAgg | bval, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int64_t first = (int64_t)u - (int64_t)q.first_dist;  // tile 0 of this waveform
-            int64_t base = (int64_t)u - 1;
-            M3 R;  // P^(kIirWin * windows walked so far)
+        // lookback_scan (drx_lookback.h): entry u = a tile's zero-state response (aggregate) or the full state behind it (prefix),
+        // 3 x 16 bits, scanned from tile 0 of this waveform.  A tile at distance dist contributes P^dist x its value: P^(distance
+        // inside the window) from the table, R = P^(kIirWin * windows walked so far) on top.
+        M3 R;
 #pragma unroll
-            for (int i = 0; i < 9; ++i) R.m[i] = (i % 4 == 0) ? 1u : 0u;
-            const M3 Pwin = load_m3(tab + kIirPTP + 9 * kIirWin);
-            uint32_t spins = 0;
-            for (;;) {  // the nearest predecessor alone first: one 8-byte load per poll (see k_encode_fused)
-                uint64_t v = 0;
-                if (lane == 0) v = __hip_atomic_load(state + base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 62)) != 0) break;
-                __builtin_amdgcn_s_sleep(4);
-                if (++spins > (1u << 22)) break;  // (the window loop below reports it)
-            }
-            for (;;) {
-                // lane l looks at predecessors base - l (nearer) and base - 64 - l (farther); in front of tile 0 the state is zero
-                const int64_t j0 = base - lane, j1 = base - 64 - lane;
-                uint64_t s0v = kScanPrefix, s1v = kScanPrefix;
-                if (j0 >= first) s0v = __hip_atomic_load(state + j0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (j1 >= first) s1v = __hip_atomic_load(state + j1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t st0 = (uint32_t)(s0v >> 62), st1 = (uint32_t)(s1v >> 62);
-                const uint64_t p0 = __ballot(st0 == 2u), z0 = __ballot(st0 == 0u);
-                const uint64_t p1 = __ballot(st1 == 2u), z1 = __ballot(st1 == 0u);
-                const int fp = p0 ? __builtin_ctzll(p0) : (p1 ? 64 + __builtin_ctzll(p1) : 128);  // nearest full state
-                const uint64_t near0 = fp >= 64 ? ~0ull : ((1ull << fp) - 1ull);
-                const uint64_t near1 = fp >= 128 ? ~0ull : (fp > 64 ? ((1ull << (fp - 64)) - 1ull) : 0ull);
-                if ((z0 & near0) | (z1 & near1)) {  // a nearer predecessor has not published yet
-                    __builtin_amdgcn_s_sleep(1);
-                    if (++spins > (1u << 22)) { if (lane == 0) atomicOr(&st->err, kErrInternal); break; }  // cannot happen; never hang
-                    continue;
-                }
-                // a tile at distance dist contributes P^dist x its value (aggregate, or the full state that ends the sum)
+        for (int i = 0; i < 9; ++i) R.m[i] = (i % 4 == 0) ? 1u : 0u;
+        const M3 Pwin = load_m3(tab + kIirPTP + 9 * kIirWin);
+        auto v3_of = [](uint64_t e) { return V3{(uint32_t)e, (uint32_t)(e >> 16), (uint32_t)(e >> 32)}; };
+        lookback_scan<kIirGateSleep>(
+            state, (int64_t)u, (int64_t)u - (int64_t)q.first_dist, bval, lane, st,
+            [&](uint64_t s0, uint64_t s1, bool in0, bool in1) {
                 V3 c{0u, 0u, 0u};
-                if (lane <= fp) c = mul(load_m3(tab + kIirPTP + 9 * lane), V3{(uint32_t)s0v, (uint32_t)(s0v >> 16), (uint32_t)(s0v >> 32)});
-                if (64 + lane <= fp) c = add(c, mul(load_m3(tab + kIirPTP + 9 * (64 + lane)), V3{(uint32_t)s1v, (uint32_t)(s1v >> 16), (uint32_t)(s1v >> 32)}));
+                if (in0) c = mul(load_m3(tab + kIirPTP + 9 * lane), v3_of(s0));
+                if (in1) c = add(c, mul(load_m3(tab + kIirPTP + 9 * (64 + lane)), v3_of(s1)));
                 c = mul(R, lo16(c));
                 x = lo16(add(x, V3{wave_sum_u32(c.x), wave_sum_u32(c.y), wave_sum_u32(c.z)}));
-                if (fp < 128) break;
-                base -= 128;
                 R = mul(Pwin, R);
-            }
-            // the full state behind this tile: its successors stop here
-            const V3 X = lo16(add(mul(load_m3(tab + kIirPTP + 9), x), B));
-            if (lane == 0)
-                __hip_atomic_store(state + u, kScanPrefix | ((uint64_t)X.x | ((uint64_t)X.y << 16) | ((uint64_t)X.z << 32)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        }
+            },
+            [&] {  // the full state behind this tile: its successors stop here
+                const V3 X = lo16(add(mul(load_m3(tab + kIirPTP + 9), x), B));
+                return (uint64_t)X.x | ((uint64_t)X.y << 16) | ((uint64_t)X.z << 32);
+            });
         if (lane == 0) { s_x[0] = x.x; s_x[1] = x.y; s_x[2] = x.z; }
     }
     __syncthreads();

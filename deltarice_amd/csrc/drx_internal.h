@@ -385,7 +385,7 @@ struct RefilterTarget {
 hipError_t launch_refilter(const StreamCall &c, uint32_t k2, const RefilterTarget &T, const TrcScratch &t, const EncOut &out, uint32_t *form_out);
 hipError_t launch_estimate_words_refiltered(const StreamCall &c, const RefilterTarget &T, unsigned long long *d_est, uint32_t *form_out);
 
-// wide: fused_wide() as the route decided it
+// wide: fused_wide() as the route decided it.  d_scan: uint64[total_waves + 2] (one look-back entry per workgroup, the ticket behind them)
 hipError_t launch_encode_fused(const EncodeCall &c, int wide, uint64_t *d_scan);
 
 // the persistent form of the single pass (drx_encode_stream.hip): a ring of kEsRingWords LDS words per wavefront, a scanner
@@ -591,10 +591,11 @@ uint64_t pieces_workgroups(const Geom &G);     // uniform batches it admits
 // ragged plans: sets pc_super / pc_packed and returns pc_wg_base's host copy, whose last entry is the workgroup total (empty:
 // the encoder does not take the batch)
 std::vector<uint32_t> pieces_plan_ragged(Geom &G, const ChunkDesc *host_chunks);
-uint64_t pieces_scan_words(const Geom &G, uint64_t total_wgs);  // uint64 words of its look-back state
+uint64_t pieces_scan_words(const Geom &G, uint64_t total_wgs);  // uint64 words of its look-back state, the two of its ticket included
 hipError_t launch_encode_pieces(const EncodeCall &c, uint64_t in_samples, uint64_t *d_scan, uint64_t total_wgs);
 // in-place inverse of a general prediction filter over decoded residuals (drx_iir.hip): tiles of kIirThreads lanes x kIirRun
-// samples, decoupled look-back over kIirWin tiles per poll, tables of kIirTabWords uint32 per filter
+// samples, decoupled look-back over kIirWin tiles per poll (drx_lookback.h: its window), tables of kIirTabWords uint32 per filter;
+// d_state: uint64[n_tiles + 1], the ticket in the last word
 constexpr uint32_t kIirRun = 64, kIirThreads = 512, kIirTile = kIirRun * kIirThreads, kIirWin = 128;
 constexpr uint32_t kIirTabWords = (7 + 64 + (kIirWin + 1)) * 9 + 4;
 void iir_tables(const uint32_t fast_nt[3], uint32_t t0neg, uint32_t *tab);

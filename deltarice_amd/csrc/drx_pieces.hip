@@ -37,6 +37,7 @@
 #include "drx_internal.h"
 #include "drx_device.h"
 #include "drx_encode.h"
+#include "drx_lookback.h"
 
 namespace drx {
 
@@ -80,52 +81,7 @@ __device__ __forceinline__ PcChunk pc_locate(const Geom &G, uint32_t T, bool pac
     return q;
 }
 
-// Decoupled look-back, the reading half: sum of the values of entries [first, idx), 128 entries per poll.  Owners publish
-// kScanAgg | value, later kScanPrefix | sum of [first, own]; a zero entry is not there yet.  One wavefront calls this.
-__device__ __forceinline__ uint64_t lookback_sum(const uint64_t *state, int64_t idx, int64_t first, int lane, DevStatus *st) {
-    uint64_t sum = 0;
-    int64_t base = idx - 1;
-    uint32_t spins = 0;
-    // the nearest predecessor alone first, one 8-byte load per poll: hundreds of waiting workgroups polling whole windows
-    // were a fabric load of their own (k_encode_fused: 5.86 -> 5.43 ms, profiles/r03_notes.md)
-    while (base >= first) {
-        uint64_t v = 0;
-        if (lane == 0) v = __hip_atomic_load(state + base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 62)) != 0) break;
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > (1u << 22)) break;  // (the window loop below reports it)
-    }
-    for (;;) {
-        const int64_t i0 = base - lane, i1 = base - 64 - lane;
-        uint64_t s0v = kScanPrefix, s1v = kScanPrefix;  // in front of `first`: an empty prefix
-        if (i0 >= first) s0v = __hip_atomic_load(state + i0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (i1 >= first) s1v = __hip_atomic_load(state + i1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t st0 = (uint32_t)(s0v >> 62), st1 = (uint32_t)(s1v >> 62);
-        const uint64_t p0 = __ballot(st0 == 2u), z0 = __ballot(st0 == 0u);
-        const uint64_t p1 = __ballot(st1 == 2u), z1 = __ballot(st1 == 0u);
-        const int fp = p0 ? __builtin_ctzll(p0) : (p1 ? 64 + __builtin_ctzll(p1) : 128);
-        const uint64_t near0 = fp >= 64 ? ~0ull : ((1ull << fp) - 1ull);
-        const uint64_t near1 = fp >= 128 ? ~0ull : (fp > 64 ? ((1ull << (fp - 64)) - 1ull) : 0ull);
-        if ((z0 & near0) | (z1 & near1)) {  // a nearer predecessor has not published yet
-            __builtin_amdgcn_s_sleep(1);
-            if (++spins > (1u << 22)) {  // cannot happen with zeroed state (ticket holders' predecessors run); never hang the GPU
-                if (lane == 0) atomicOr(&st->err, kErrInternal);
-                break;
-            }
-            continue;
-        }
-        const uint64_t c0 = (lane <= fp) ? (s0v & kScanValMask) : 0ull;
-        const uint64_t c1 = (64 + lane <= fp) ? (s1v & kScanValMask) : 0ull;
-        sum += wave_sum_u64(c0 + c1);
-        if (fp < 128) break;
-        base -= 128;
-    }
-    return sum;
-}
-
-__device__ __forceinline__ void scan_publish(uint64_t *state, int64_t idx, uint64_t tagged, int lane) {
-    if (lane == 0) __hip_atomic_store(state + idx, tagged, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+constexpr int kPcGateSleep = 8;  // s_sleep between two polls of the nearest predecessor's entry (drx_lookback.h)
 
 }  // namespace
 
@@ -421,39 +377,19 @@ __global__ __launch_bounds__(64 * kPcWaves) void k_encode_pieces(Geom G, const i
     if (wv == 0) {
         uint64_t excl_words = 0, sum_words = block_sum;
         if (!SUPER) {
-            // decoupled look-back over one entry per workgroup (as in k_encode_fused)
-            if (T == 0) {
-                scan_publish(scan_state, T, kScanPrefix | block_sum, lane);
-            } else {
-                scan_publish(scan_state, T, kScanAgg | block_sum, lane);
-                excl_words = lookback_sum(scan_state, T, 0, lane, st);
-                scan_publish(scan_state, T, kScanPrefix | (excl_words + block_sum), lane);
-            }
+            // lookback_scan_sum (drx_lookback.h): entry T = the words of workgroup T's pieces, scanned from workgroup 0
+            excl_words = lookback_scan_sum<kPcGateSleep>(scan_state, T, 0, block_sum, lane, st);
         } else {
-            // bits of the waveform in front of this part: look-back over the waveform's parts (workgroups T - part .. T)
-            uint64_t excl_bits = 0;
-            if (part == 0u) {
-                scan_publish(part_state, T, kScanPrefix | (uint64_t)part_bits, lane);
-            } else {
-                scan_publish(part_state, T, kScanAgg | (uint64_t)part_bits, lane);
-                excl_bits = lookback_sum(part_state, T, (int64_t)T - (int64_t)part, lane, st);
-                scan_publish(part_state, T, kScanPrefix | (excl_bits + part_bits), lane);
-            }
-            // words in front of the waveform: look-back over one entry per WAVEFORM, which its last part publishes
+            // part_state entry T = the bits of part `part` of the waveform, scanned from its part 0 (workgroup T - part)
+            const uint64_t excl_bits = lookback_scan_sum<kPcGateSleep>(part_state, T, (int64_t)T - (int64_t)part, part_bits, lane, st);
+            // scan_state entry U = the words of WAVEFORM U, scanned from waveform 0; its last part publishes it, the others read
             const int64_t U = (int64_t)(q.wave_base + w0);
             const uint64_t n_total = (excl_bits + part_bits + 31u) >> 5;  // (last part: the waveform's payload words)
             sum_words = 1ull + n_total + (w0 == 0u ? 1ull : 0ull);
-            if (last_part) {
-                if (U == 0) {
-                    scan_publish(scan_state, U, kScanPrefix | sum_words, lane);
-                } else {
-                    scan_publish(scan_state, U, kScanAgg | sum_words, lane);
-                    excl_words = lookback_sum(scan_state, U, 0, lane, st);
-                    scan_publish(scan_state, U, kScanPrefix | (excl_words + sum_words), lane);
-                }
-            } else if (U != 0) {
-                excl_words = lookback_sum(scan_state, U, 0, lane, st);
-            }
+            if (last_part)
+                excl_words = lookback_scan_sum<kPcGateSleep>(scan_state, U, 0, sum_words, lane, st);
+            else
+                excl_words = lookback_sum<kPcGateSleep>(scan_state, U, 0, lane, st);
             if (lane == 0) { s_excl_bits = excl_bits; s_wf_words = n_total; }
         }
         if (lane == 0) {
