@@ -576,7 +576,9 @@ class Plan:
                   offset: int = 0, out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
         """wave_bins_async on an EncodedBatch -> int64 [total_waves, n_bins, BIN_COLS]; waits, and raises like wave_stats().  The
         charge in eight gates of 250 samples around every waveform's peak:
-        ``plan.wave_bins(enc, 250, 8, start=stats[:, STAT_ARGMAX], offset=-500)[:, :, BIN_SUM]``."""
+        ``plan.wave_bins(enc, 250, 8, start=stats[:, STAT_ARGMAX], offset=-500)[:, :, BIN_SUM]``.  Few long waveforms (the
+        reference's default of one waveform per chunk) are much faster by the block form, which the context option takes:
+        ``ctx.set_option("bins_impl", 1)``; the rows are the same, last_bins_form() says which form ran."""
         return self._blocking(self.wave_bins_async, enc, bin, n_bins, start, offset, out, wave_words)
 
     def decode_window_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start, width: int, offset: int = 0,
@@ -834,14 +836,15 @@ class Plan:
         return int(self.ctx.lib.drx_plan_last_windows_listed(self._h))
 
     def last_bins_form(self) -> int:
-        """DRX_BINS_FORM_* (include/deltarice_hip.h): which form the last wave_bins took -- a lane per waveform for every batch
-        today (there is no block form yet); 0 before the plan's first such call."""
+        """DRX_BINS_FORM_* (include/deltarice_hip.h): which form the last wave_bins took -- a lane per waveform (every batch under
+        the context's default ``bins_impl`` 0), or under ``ctx.set_option("bins_impl", 1)`` a workgroup per block of a waveform's
+        stream (few long waveforms); 0 before the plan's first such call."""
         self._open("last_bins_form")
         return int(self.ctx.lib.drx_plan_last_bins_form(self._h))
 
     def last_bins_listed(self) -> int:
-        """After finish(): how many waveforms the last wave_bins' block form handed to the lane kernel behind it; 0 for the
-        lane form."""
+        """After finish(): how many waveforms the last wave_bins' block form handed to the lane kernel behind it (flagged or
+        judged suspect by the block parse; all their rows are written again and judged there); 0 for the lane form."""
         self._open("last_bins_listed")
         return int(self.ctx.lib.drx_plan_last_bins_listed(self._h))
 

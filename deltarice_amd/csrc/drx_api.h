@@ -105,6 +105,8 @@ struct drx_ctx {
                            // walk kernel, 0 = simple kernel
     int encode_impl = 2;  // 2: single pass, persistent (k_encode_stream) where the standard geometry applies; 1: single pass with
                           // look-back (k_encode_fused) everywhere; 0: size pass + scan + pack pass
+    int bins_impl = 0;    // launch_wave_bins(): 0 = a lane per waveform whatever the batch (default), 1 = the block form where
+                          // blocks_form_batch() admits the batch under kBinsForm (drx_bins_blocks.hip)
     int profile = 0;      // bracket kernels with HIP events (drx_plan_last_timings)
     uint32_t debug_flags = 0;  // Geom::dbg
     std::string last_error;
@@ -179,7 +181,7 @@ struct drx_plan {
     };
     BlockForm stats;    // drx_wave_stats: accumulators and list
     BlockForm windows;  // drx_decode_windows: its list
-    BlockForm bins;     // drx_wave_bins: the form word alone (no block form yet, no scratch)
+    BlockForm bins;     // drx_wave_bins: its list (allocated under bins_impl 1 only)
     struct Pulses : BlockForm {  // drx_find_pulses: block summaries and list ...
         Grown stage;             // ... and the records its blocks stage: as many as the call needs (pulses_blocks_staging_bytes())
     } pulses;

@@ -350,6 +350,11 @@ drx_status drx_ctx_set_option(drx_ctx *c, const char *key, int64_t value) {
         c->encode_impl = (int)value;
         return DRX_OK;
     }
+    if (!strcmp(key, "bins_impl")) {
+        if (value != 0 && value != 1) return DRX_ERR_ARG;
+        c->bins_impl = (int)value;
+        return DRX_OK;
+    }
     if (!strcmp(key, "debug_flags")) {
         c->debug_flags = (uint32_t)value;
         return DRX_OK;

@@ -54,7 +54,9 @@ static drx_status wave_bins(drx_plan *p, const uint32_t *d_in, uint64_t in_words
     DRX_ON_DEVICE(ctx);
     StreamCall c;
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
-    DRX_HIP(ctx, launch_wave_bins(c, d_start, start_stride, offset, bin, n_bins, d_out, out_wave_stride, &p->bins.last_form));
+    if (ctx->bins_impl == 1) DRX_HIP(ctx, form_scratch(p, kBinsForm, p->bins, bins_blocks_scratch_bytes));
+    DRX_HIP(ctx, launch_wave_bins(c, p->dec.d_blk, p->bins.d, ctx->bins_impl, d_start, start_stride, offset, bin, n_bins, d_out, out_wave_stride,
+                                  &p->bins.last_form));
     return call_end(p, DRX_PATH_BINS);
 }
 

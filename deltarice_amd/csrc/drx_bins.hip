@@ -18,8 +18,9 @@
 // cursor (BinCursor) of the next BORDER -- the sample index at which the current stretch ends -- and the row that is due;
 // both depend on the geometry alone, never on the stream, so a corrupt stream cannot move a store.
 //
-// Few long waveforms go through the same lane-per-waveform kernels: correct, and 50-60 ns per sample and lane whatever else
-// runs.  There is no block form of this call yet (kBinsForm, drx_internal.h).
+// Few long waveforms go through the same lane-per-waveform kernels by default: correct, and 50-60 ns per sample and lane whatever
+// else runs.  Under the context option "bins_impl" = 1 they take the block form instead (drx_bins_blocks.hip; kBinsForm,
+// drx_internal.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -27,62 +28,15 @@
 
 #include "drx_internal.h"
 #include "drx_device.h"
+#include "drx_bin_cursor.h"
 #include "drx_lane_stream.h"
 
 namespace drx {
 
 // (s16x2, as_pair(), as_word(), kNarrow: drx_lane_stream.h, as in drx_stats.hip)
-constexpr uint32_t kNoBorder = 0xffffffffu;  // (a waveform has fewer than 2^31 samples)
 constexpr uint32_t kMnId = 0x7fff7fffu, kMxId = 0x80008000u;  // the packed identities of min and max
 
-// a_g = start[g * stride] + offset; the sum saturates (as drx_decode_window's)
-__device__ __forceinline__ int64_t bins_origin(const int64_t *__restrict__ start, uint64_t start_stride, int64_t offset, uint64_t g) {
-    int64_t a = offset;
-    if (start) {
-        const int64_t v = start[g * start_stride];
-        if (__builtin_add_overflow(v, offset, &a)) a = v < 0 ? INT64_MIN : INT64_MAX;
-    }
-    return a;
-}
-
-// Where a lane is among its bins.  live: the current stretch of samples is bin `cur`; otherwise it lies in front of bin 0
-// (cur == 0, the border is a_g) or behind the last bin (no border is left).  cur is the next row to be written.
-struct BinCursor {
-    uint32_t nb;   // the sample index at which the current stretch ends; kNoBorder: at the waveform's end
-    uint32_t cur;
-    bool live;
-};
-// ... at sample 0.  Returns the empty rows in front of the first bin that receives a sample (n_bins: no bin receives one).
-// The ends are formed in 64 bits from values below 2^63 + 2^32: nothing wraps.
-__device__ __forceinline__ uint32_t bins_begin(BinCursor &c, int64_t a, uint32_t bin, uint32_t n_bins, uint32_t len) {
-    c.nb = kNoBorder;
-    c.cur = n_bins;
-    c.live = false;
-    if (a >= (int64_t)len) return n_bins;  // (len == 0 included)
-    c.cur = 0;
-    if (a > 0) {  // samples [0, a) belong to no bin
-        c.nb = (uint32_t)a;
-        return 0u;
-    }
-    const uint64_t ua = 0u - (uint64_t)a;  // (2^63 for INT64_MIN)
-    const uint64_t b0 = ua / bin;
-    if (b0 >= n_bins) {
-        c.cur = n_bins;
-        return n_bins;
-    }
-    const uint64_t end = (b0 + 1u) * bin - ua;  // in (0, bin]
-    c.cur = (uint32_t)b0;
-    c.live = true;
-    c.nb = end < len ? (uint32_t)end : kNoBorder;
-    return (uint32_t)b0;
-}
-// ... at the border, behind the store of the bin that ends there
-__device__ __forceinline__ void bins_border(BinCursor &c, uint32_t bin, uint32_t n_bins, uint32_t len) {
-    const uint64_t end = (uint64_t)c.nb + bin;
-    if (c.live) ++c.cur;  // (cur < n_bins while live)
-    c.live = c.cur < n_bins;
-    c.nb = (c.live && end < len) ? (uint32_t)end : kNoBorder;
-}
+// (kNoBorder, bins_origin(), BinCursor, bins_begin() -- here from sample 0 -- and bins_border(): drx_bin_cursor.h)
 
 // a bin's row: four int64, by 16-byte stores where the row allows them, by 8-byte stores otherwise (the ABI asks 8-byte
 // alignment of d_out; rows are 32 bytes, so a waveform's rows are aligned alike).  Not store_i64_row() (drx_device.h): through
@@ -147,7 +101,7 @@ __global__ __launch_bounds__(64) void k_wave_bins(Geom G, const uint32_t *__rest
         n = wave_words[g];
         rows = out + g * out_wave_stride;
         vec = ((uintptr_t)rows & 15u) == 0;
-        store_empty_bins(rows, vec, 0u, bins_begin(c, bins_origin(start, start_stride, offset, g), bin, n_bins, len));
+        store_empty_bins(rows, vec, 0u, bins_begin(c, bins_origin(start, start_stride, offset, g), bin, n_bins, len, 0u));
     }
     uint32_t *const ring = ring_all + 64;
 #include "drx_lane_reader.inc"
@@ -303,7 +257,7 @@ __global__ __launch_bounds__(64) void k_wave_bins_serial(Geom G, const uint32_t 
     int64_t *rows = out + g * out_wave_stride;
     const bool vec = ((uintptr_t)rows & 15u) == 0;
     BinCursor c;
-    store_empty_bins(rows, vec, 0u, bins_begin(c, bins_origin(start, start_stride, offset, g), bin, n_bins, r.len));
+    store_empty_bins(rows, vec, 0u, bins_begin(c, bins_origin(start, start_stride, offset, g), bin, n_bins, r.len, 0u));
     int32_t mn = 32767, mx = -32768;
     int64_t sum = 0;
     uint64_t sq = 0;
@@ -327,15 +281,26 @@ __global__ __launch_bounds__(64) void k_wave_bins_serial(Geom G, const uint32_t 
     store_empty_bins(rows, vec, c.cur + (c.live ? 1u : 0u), n_bins);
 }
 
-hipError_t launch_wave_bins(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t bin,
-                            uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride, uint32_t *form_out) {
+hipError_t launch_wave_bins(const StreamCall &c, void *d_blk, void *d_list, int bins_impl, const int64_t *d_start, uint64_t start_stride,
+                            int64_t offset, uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride, uint32_t *form_out) {
     const Geom &G = *c.G;
     const hipStream_t s = c.s;
-    if (form_out) *form_out = blocks_form_word(G, false, kBinsForm);  // (no block form yet: a lane per waveform whatever the batch)
+    // bins_impl 0 (the default): a lane per waveform whatever the batch, and the form's debug flags are inert
+    const bool blocks = bins_impl == 1 && d_list != nullptr && blocks_form_batch(G, d_blk, kBinsForm);
+    if (form_out) *form_out = blocks_form_word(G, blocks, kBinsForm);
     if (G.total_waves == 0) return hipSuccess;
     // ---- the walk (drx_walk.hip): launch_batch_walk()
     const hipError_t e = batch_walk_prologue(c);
     if (e != hipSuccess) return e;
+    if (blocks) {
+        // ---- few long waveforms: the identity rows, a workgroup per block of a waveform's stream, then a lane per waveform that
+        // form lists (drx_bins_blocks.hip)
+        const hipError_t eb = launch_bins_blocks(c, d_blk, d_list, d_start, start_stride, offset, bin, n_bins, d_out, out_wave_stride);
+        if (eb != hipSuccess) return eb;
+        mark(c.ev, 2, s);
+        mark(c.ev, 3, s);
+        return hipGetLastError();
+    }
     // ---- the kernel: a wavefront per 64 waveforms
     const bool serial = G.n_taps != 0;
     for_wavefront_slices(G, !serial, [&](uint64_t base, unsigned nb) {

@@ -3,7 +3,8 @@
 // in output order, to HBM), of k_stats_blocks (drx_stats_blocks.hip: the samples reduced to a waveform's statistics), of
 // k_pulses_blocks (drx_pulses_blocks.hip: the runs of samples over a threshold, per block, stitched behind the kernel), of
 // k_windows_blocks (drx_windows_blocks.hip: the samples, in output order, to the rows of the windows that meet the block) and of
-// k_trc_blocks (drx_transcode_blocks.hip: the residuals sized, then re-coded, at another RiceParameter).
+// k_trc_blocks (drx_transcode_blocks.hip: the residuals sized, then re-coded, at another RiceParameter), and of k_bins_blocks
+// (drx_bins_blocks.hip: the samples reduced bin by bin into the caller's rows).
 // drx_blocks.hip's head comment describes the scheme.  A kernel that takes this route for another purpose adds its own
 // phase 2 behind the same phase 1, look-back and flags, as the STATS and PULSES forms do.
 // The host side of such a kernel is shared too: blocks_prepare() (drx_blocks.hip: the scratch reset and one BlkClassLaunch per
@@ -17,6 +18,7 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "drx_bin_cursor.h"
 #include "drx_device.h"
 #include "drx_internal.h"
 #include "drx_iir_math.h"
@@ -274,6 +276,18 @@ struct BlkPulseArgs {
 // samples receives its share of them in its own row (drx_windows_blocks.hip); `out`, `itab` and `xstate` are not used.
 struct BlkWindowArgs {
     WinList wl;  // drx_window_rows.h: the starts, the counts and the rows of drx_decode_windows
+};
+
+// BINS (delta filter only): phase 2 reduces the block's samples bin by bin and merges the partial rows into the caller's
+// rows, which a fill kernel has set to the identity in front of the blocks (drx_bins_blocks.hip, drx_blocks_bins.inc); `out`,
+// `itab` and `xstate` are not used.
+struct BlkBinsArgs {
+    const int64_t *start;  // per-waveform origins (nullptr: none), start_stride entries apart, + offset (drx_bin_cursor.h)
+    uint64_t start_stride;
+    int64_t offset;
+    uint32_t bin, n_bins;
+    int64_t *rows;  // row (g, b) = rows + g * wave_stride + b * DRX_BIN_COLS
+    uint64_t wave_stride;
 };
 
 // TRANSCODE (any filter: RESID, nothing is filtered): phase 2 sizes or re-codes the block's residuals at another RiceParameter

@@ -76,11 +76,12 @@ __global__ __launch_bounds__(NT) void k_decode_blocks(Geom G, const uint32_t *__
                                                       DevStatus *st, int16_t *__restrict__ out, uint32_t n_list,
                                                       const uint32_t *__restrict__ itab, uint64_t *__restrict__ xstate,
                                                       const uint32_t *__restrict__ wave_list) {
-    constexpr bool STATS = false, PULSES = false, WINDOWS = false, TRANSCODE = false;
+    constexpr bool STATS = false, PULSES = false, WINDOWS = false, TRANSCODE = false, BINS = false;
     const BlkStatsArgs sa{0u, nullptr};
     const BlkPulseArgs pa{};
     const BlkWindowArgs wa{};
     const BlkTrcArgs ta{};
+    const BlkBinsArgs ba{};
 #include "drx_blocks_body.inc"
 }
 

@@ -1,10 +1,10 @@
 // drx_blocks_body.inc -- the body of a kernel that gives a workgroup a block of a waveform's stream, included INSIDE the kernel's
 // definition (k_decode_blocks, drx_blocks.hip; k_stats_blocks, drx_stats_blocks.hip; k_pulses_blocks, drx_pulses_blocks.hip;
-// k_windows_blocks, drx_windows_blocks.hip; k_trc_blocks, drx_transcode_blocks.hip)
+// k_windows_blocks, drx_windows_blocks.hip; k_trc_blocks, drx_transcode_blocks.hip; k_bins_blocks, drx_bins_blocks.hip)
 // behind its arguments: text, not a function, because k_decode_blocks is sensitive to how its arguments reach it (an inlined
 // function with the same body was compiled to other code: other spills, another schedule).  The including kernel provides NT,
-// RESID, SW, FUSE, STATS, PULSES, WINDOWS, TRANSCODE, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs), `pa`
-// (BlkPulseArgs), `wa` (BlkWindowArgs) and `ta` (BlkTrcArgs).
+// RESID, SW, FUSE, STATS, PULSES, WINDOWS, TRANSCODE, BINS, the arguments of k_decode_blocks by name, `sa` (BlkStatsArgs), `pa`
+// (BlkPulseArgs), `wa` (BlkWindowArgs), `ta` (BlkTrcArgs) and `ba` (BlkBinsArgs).
     static_assert(!FUSE || RESID, "the fused inverse filter works on residuals");
     using BG = BlkGeom<NT, SW>;
     constexpr int kBlkSegW = SW;
@@ -501,6 +501,8 @@
             }
             if constexpr (TRANSCODE) {
 #include "drx_blocks_trc.inc"
+            } else if constexpr (BINS) {
+#include "drx_blocks_bins.inc"
             } else if constexpr (PULSES) {
                 // ---- phase 2, pulses: every lane summarises the runs of over-threshold samples among its own samples
                 // (drx_pulse_runs.h), a scan over the lanes with pulse_combine() tells each what lies in front of it inside

@@ -91,7 +91,7 @@ struct Geom {
 
 struct DevStatus {
     uint32_t err;  // kErr* bits, OR-ed by kernels
-    uint32_t listed;  // drx_find_pulses / drx_decode_windows / drx_transcode, block form: the waveforms handed to the lane kernel(s) behind the blocks
+    uint32_t listed;  // drx_find_pulses / drx_decode_windows / drx_transcode / drx_wave_bins, block form: the waveforms handed to the lane kernel(s) behind the blocks
     uint64_t total_words;  // encode: words of the encoded batch
     uint32_t redone;       // drx_find_pulses, block form: the waveforms whose blocks its second launch ran again
     uint32_t pad_;
@@ -230,7 +230,7 @@ inline GatherScratch gather_scratch_view(void *base, uint64_t n_sel) {
 hipError_t launch_gather(const StreamCall &c, const uint64_t *d_sel, uint64_t n_sel, uint64_t chunk_waves,
                          const uint32_t *d_chunk_samples, const EncOut &out, const GatherScratch &t, bool tiles, uint64_t mean_words,
                          bool resume);
-// The block forms of drx_wave_stats, drx_find_pulses, drx_decode_windows and drx_transcode (drx_*_blocks.hip): few long waveforms under
+// The block forms of drx_wave_stats, drx_find_pulses, drx_decode_windows, drx_transcode and drx_wave_bins (drx_*_blocks.hip): few long waveforms under
 // the delta filter (any_filter: under every filter) give a workgroup a block of a waveform's stream, as the block decoder does (d_blk = its scratch), with the call's lane
 // kernel behind the blocks for the waveforms they list.  One rule says which batches: the decoder's own test, blocks against
 // lanes by their cost (blocks_batch(), drx_blocks.hip), with the rate of THIS call's lane kernel, on a plan that has d_blk, unless
@@ -265,12 +265,19 @@ constexpr BlkFormRule kWindowsForm{kWindowsLaneUs, DRX_DBG_WINDOWS_LANES, DRX_DB
 constexpr double kTranscodeLaneUs = 0.2045;
 constexpr double kTranscodeBlockFactor = 4.0;
 constexpr BlkFormRule kTranscodeForm{kTranscodeLaneUs / kTranscodeBlockFactor, DRX_DBG_TRANSCODE_LANES, DRX_DBG_TRANSCODE_ALL_FALLBACK, true};
-// drx_wave_bins has no block form yet: its rule is here for the form word and the flags' names, and no launcher asks
-// blocks_form_batch() with it, so every batch stays a lane per waveform (DRX_DBG_BINS_ALL_FALLBACK has nothing to act on).
+// drx_wave_bins: the block form (drx_bins_blocks.hip) is taken only under the context option "bins_impl" = 1 -- launch_wave_bins()
+// asks blocks_form_batch() with this rule only then, and with the default 0 every batch stays a lane per waveform and the rule's
+// two flags are inert (the form word of today's calls is pinned by tests; making the block form the default is a follow-up).
 // k_wave_bins takes 28.53 ms for a lane of 500 000 samples at 1000 bins (profiles/wave_bins_bench.txt, row `noptrex`): 0.057 us
 // per sample
 constexpr double kBinsLaneUs = 0.057;
-constexpr BlkFormRule kBinsForm{kBinsLaneUs, DRX_DBG_BINS_LANES, DRX_DBG_BINS_ALL_FALLBACK};
+// blocks_batch() prices the DECODER's blocks, and this form costs 1.40 (NOPTREX), 1.71 (nEDM) and 1.32 (25 x 14 M) times what
+// plan.decode takes for the same batch in the same process (profiles/wave_bins_bench.txt, the rows `impl 1`): the fill, the walk
+// over the bins and the merge.  Near break-even that misroutes: 4 chunks of 2100 x 7000 are 393 us of decoder's blocks against 399
+// us of these lanes, and would take a block form that costs 520 us or more.  The smallest of the three ratios is charged (row
+// `long25 impl 1`: 0.780 / 0.592) -- the rule is given the lane rate divided by it, as kTranscodeForm's is.
+constexpr double kBinsBlockFactor = 1.32;
+constexpr BlkFormRule kBinsForm{kBinsLaneUs / kBinsBlockFactor, DRX_DBG_BINS_LANES, DRX_DBG_BINS_ALL_FALLBACK};
 bool blocks_form_batch(const Geom &G, const void *d_blk, const BlkFormRule &r);
 // the form word of a call, one set of values under five names: LANES, or BLOCKS | FALLBACK_ALL under the rule's all_fallback_flag
 static_assert(DRX_STATS_FORM_LANES == DRX_PULSES_FORM_LANES && DRX_STATS_FORM_LANES == DRX_WINDOWS_FORM_LANES &&
@@ -298,9 +305,13 @@ hipError_t launch_stats_blocks(const StreamCall &c, void *d_blk, void *d_sacc, u
 // reduces bin by bin: row (g, b) = d_out + g * out_wave_stride + b * DRX_BIN_COLS holds the samples of waveform g with index in
 // [a + b * bin, a + (b + 1) * bin), a = d_start[g * start_stride] + offset (saturating; d_start == nullptr: 0); every one of
 // the n_bins rows of every waveform is written, an empty bin as (0, 0, 32767, -32768).  ev: {start, walk's end, kernel's end, end}
-// form_out: DRX_BINS_FORM_* of include/deltarice_hip.h
-hipError_t launch_wave_bins(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t bin,
-                            uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride, uint32_t *form_out);
+// form_out: DRX_BINS_FORM_* of include/deltarice_hip.h.  bins_impl (drx_ctx): 0 a lane per waveform whatever the batch, 1 the block
+// form where blocks_form_batch() admits the batch under kBinsForm: d_list = bins_blocks_scratch_bytes() of list
+hipError_t launch_wave_bins(const StreamCall &c, void *d_blk, void *d_list, int bins_impl, const int64_t *d_start, uint64_t start_stride,
+                            int64_t offset, uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride, uint32_t *form_out);
+uint64_t bins_blocks_scratch_bytes(const Geom &G);
+hipError_t launch_bins_blocks(const StreamCall &c, void *d_blk, void *d_list, const int64_t *d_start, uint64_t start_stride, int64_t offset,
+                              uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride);
 // drx_decode_window (drx_window.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
 // far as its window's end and writes `width` samples from start[g * start_stride] + offset on (pad outside the waveform) to row
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}

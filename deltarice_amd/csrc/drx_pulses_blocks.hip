@@ -57,7 +57,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void k_
                                                       uint32_t *__restrict__ fail, uint32_t *__restrict__ suspect,
                                                       DevStatus *st, BlkPulseArgs pa, uint32_t n_list,
                                                       const uint32_t *__restrict__ wave_list) {
-    constexpr bool RESID = false, FUSE = false, STATS = false, PULSES = true, WINDOWS = false, TRANSCODE = false;
+    constexpr bool RESID = false, FUSE = false, STATS = false, PULSES = true, WINDOWS = false, TRANSCODE = false, BINS = false;
     // what the decoder's phase 2, its fused inverse filter and the statistics form take: not used here
     int16_t *const out = nullptr;
     const uint32_t *const itab = nullptr;
@@ -65,6 +65,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(3))) void k_
     const BlkStatsArgs sa{0u, nullptr};
     const BlkWindowArgs wa{};
     const BlkTrcArgs ta{};
+    const BlkBinsArgs ba{};
     // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
     if (st->err) return;
 #include "drx_blocks_body.inc"

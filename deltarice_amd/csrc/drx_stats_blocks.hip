@@ -37,7 +37,7 @@ __global__ __launch_bounds__(NT) void k_stats_blocks(Geom G, const uint32_t *__r
                                                      uint32_t *__restrict__ fail, uint32_t *__restrict__ suspect,
                                                      DevStatus *st, uint32_t head_len, unsigned long long *__restrict__ acc,
                                                      uint32_t n_list, const uint32_t *__restrict__ wave_list) {
-    constexpr bool RESID = false, FUSE = false, STATS = true, PULSES = false, WINDOWS = false, TRANSCODE = false;
+    constexpr bool RESID = false, FUSE = false, STATS = true, PULSES = false, WINDOWS = false, TRANSCODE = false, BINS = false;
     // what the decoder's phase 2 and its fused inverse filter take: not used here
     int16_t *const out = nullptr;
     const uint32_t *const itab = nullptr;
@@ -46,6 +46,7 @@ __global__ __launch_bounds__(NT) void k_stats_blocks(Geom G, const uint32_t *__r
     const BlkPulseArgs pa{};
     const BlkWindowArgs wa{};
     const BlkTrcArgs ta{};
+    const BlkBinsArgs ba{};
     // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
     if (st->err) return;
 #include "drx_blocks_body.inc"

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(NT) void k_trc_blocks(Geom G, const uint32_t *__res
                                                    uint32_t *__restrict__ ends, uint32_t *__restrict__ ticket,
                                                    uint32_t *__restrict__ fail, uint32_t *__restrict__ suspect,
                                                    DevStatus *st, TA ta_, uint32_t n_list, const uint32_t *__restrict__ wave_list) {
-    constexpr bool RESID = true, FUSE = false, STATS = false, PULSES = false, WINDOWS = false, TRANSCODE = true;
+    constexpr bool RESID = true, FUSE = false, STATS = false, PULSES = false, WINDOWS = false, TRANSCODE = true, BINS = false;
     // what the decoder's phase 2 and its fused inverse filter take: not used here
     int16_t *const out = nullptr;
     const uint32_t *const itab = nullptr;
@@ -57,6 +57,7 @@ __global__ __launch_bounds__(NT) void k_trc_blocks(Geom G, const uint32_t *__res
     const BlkPulseArgs pa{};
     const BlkWindowArgs wa{};
     const TA ta = ta_;
+    const BlkBinsArgs ba{};
     // whatever a walker reported, and (the pack launch) kErrCorrupt or kErrCapacity: then no word of the result is written
     if (st->err) return;
 #include "drx_blocks_body.inc"

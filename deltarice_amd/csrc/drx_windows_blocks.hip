@@ -34,7 +34,7 @@ __global__ __launch_bounds__(NT) void k_windows_blocks(Geom G, const uint32_t *_
                                                        uint32_t *__restrict__ fail, uint32_t *__restrict__ suspect,
                                                        DevStatus *st, BlkWindowArgs wa, uint32_t n_list,
                                                        const uint32_t *__restrict__ wave_list) {
-    constexpr bool RESID = false, FUSE = false, STATS = false, PULSES = false, WINDOWS = true, TRANSCODE = false;
+    constexpr bool RESID = false, FUSE = false, STATS = false, PULSES = false, WINDOWS = true, TRANSCODE = false, BINS = false;
     // what the decoder's copy-out, its fused inverse filter, the statistics and the pulse form take: not used here
     int16_t *const out = nullptr;
     const uint32_t *const itab = nullptr;
@@ -42,6 +42,7 @@ __global__ __launch_bounds__(NT) void k_windows_blocks(Geom G, const uint32_t *_
     const BlkStatsArgs sa{0u, nullptr};
     const BlkPulseArgs pa{};
     const BlkTrcArgs ta{};
+    const BlkBinsArgs ba{};
     // whatever a walker reported: the tables of a batch that failed validation are not followed into the stream
     if (st->err) return;
 #include "drx_blocks_body.inc"

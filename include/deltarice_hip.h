@@ -292,10 +292,16 @@ uint32_t drx_plan_last_stats_form(const drx_plan *plan);
  * { header-chain walk, everything behind the walk, 0, whole call }.
  *   Every prediction filter the plan accepts, a lane per waveform: the delta filter parses as drx_wave_stats' lane kernel does
  * and splits a group of 16 samples that holds a bin's end in registers (bins shorter than 16 samples take a sample-at-a-time
- * path: correct, several times slower); any other filter runs a serial kernel, correct but not fast.  There is NO block form
- * yet: few long waveforms -- the batches drx_wave_stats gives to its block form -- stay a lane per waveform, 50-60 ns per sample
- * and lane, and drx_plan_last_bins_form says DRX_BINS_FORM_LANES for every batch.  DRX_DBG_BINS_LANES and
- * DRX_DBG_BINS_ALL_FALLBACK are reserved for that form and change nothing today. */
+ * path: correct, several times slower); any other filter runs a serial kernel, correct but not fast.
+ *   Few long waveforms -- the batches drx_wave_stats gives to its block form -- stay a lane per waveform BY DEFAULT, 50-60 ns per
+ * sample and lane.  The context option "bins_impl" = 1 (drx_ctx_set_option) gives them a workgroup per block of the waveform's
+ * stream instead, under the delta filter: the rows are first set to the identity, the blocks merge their partial rows into them
+ * with 64-bit integer atomics (the same answer in any order: the result is exact and reproducible), and the waveforms the blocks
+ * flag are written again, every row, and judged by a lane each (drx_plan_last_bins_listed counts them).  The same rows, the same
+ * verdicts, the same buffers rule; drx_plan_last_bins_form says which form ran.  Bins of a few samples are correct there and not
+ * tuned.  With "bins_impl" 0 drx_plan_last_bins_form says DRX_BINS_FORM_LANES for every batch and DRX_DBG_BINS_LANES and
+ * DRX_DBG_BINS_ALL_FALLBACK change nothing; with 1 they mean what the other calls' flags mean.  (The block form is an option and
+ * not the default because the form word of a default call is part of what the tests pin; making it the default is a follow-up.) */
 #define DRX_BIN_SUM 0     /* sum of y[i] over the bin                     */
 #define DRX_BIN_SUMSQ 1   /* sum of y[i]^2                                */
 #define DRX_BIN_MIN 2     /* smallest sample;  32767 for an empty bin     */
@@ -311,8 +317,8 @@ drx_status drx_wave_bins_with_wave_words(drx_plan *plan, const uint32_t *d_in, u
                                          int64_t offset, uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride);
 /* which form the plan's last drx_wave_bins took (0: none yet) */
 #define DRX_BINS_FORM_LANES 1u        /* a lane per waveform */
-#define DRX_BINS_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream (reserved: no batch takes it yet) */
-#define DRX_BINS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_BINS_ALL_FALLBACK was in force (reserved likewise) */
+#define DRX_BINS_FORM_BLOCKS 2u       /* a workgroup per block of a waveform's stream ("bins_impl" 1) */
+#define DRX_BINS_FORM_FALLBACK_ALL 4u /* or-ed: DRX_DBG_BINS_ALL_FALLBACK was in force */
 uint32_t drx_plan_last_bins_form(const drx_plan *plan);
 /* ... and, behind drx_plan_finish while drx_plan_last_decode_path is DRX_PATH_BINS, how many waveforms a block form handed to
  * the lane kernel behind the blocks, as drx_plan_last_windows_listed; 0 for the lane form */
@@ -702,10 +708,13 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
  *                     otherwise the header walk inside the launch where the batch is large enough to hide it
  *        7            always behind a separate walk kernel
  *        0            simple kernel (also: general filters the staged kernel does not take)
+ *   "bins_impl"    0 (default): drx_wave_bins runs a lane per waveform whatever the batch;
+ *                  1: the block form (a workgroup per block of a waveform's stream) for the batches drx_wave_stats gives to its
+ *                  block form, a lane per waveform elsewhere; the rows are the same (drx_wave_bins above)
  *   "debug_flags"  DRX_DBG_* bits: dispatch overrides that force an alternative (still bit-exact) path, for tests and A/B timing;
  *                  a forcing flag takes its encoder wherever that encoder can run the batch */
-#define DRX_DBG_BINS_LANES 64u                   /* drx_wave_bins: never a block form (reserved: every batch is a lane per waveform today) */
-#define DRX_DBG_BINS_ALL_FALLBACK 128u          /* drx_wave_bins, block form: every waveform is listed for the lane kernel behind the blocks (reserved) */
+#define DRX_DBG_BINS_LANES 64u                   /* drx_wave_bins under "bins_impl" 1: never the block form */
+#define DRX_DBG_BINS_ALL_FALLBACK 128u          /* drx_wave_bins, block form: every waveform is listed for the lane kernel behind the blocks */
 #define DRX_DBG_NO_LONG_PATHS 256u              /* never the long-waveform paths (segment encoders, block and long decoders) */
 #define DRX_DBG_LONG_NOT_BLOCKS 512u            /* long waveforms: one workgroup per waveform, never the block decoder */
 #define DRX_DBG_TRANSCODE_LANES 1024u            /* drx_transcode / drx_estimate_words_encoded: never the block form (a lane per waveform whatever the batch) */

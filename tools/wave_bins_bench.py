@@ -12,11 +12,14 @@ of --calls calls behind --warmup.  Run one shape per process (--only NAME).
   noptrex      2048 waveforms of 500 000 samples, 1000 bins across the trace
   nedm         256 chunks of 32 x 81 920, 1000 bins across the trace
   long25       25 chunks of ONE 14 M-sample waveform, 1000 bins across the trace
-               the long shapes against plan.decode alone (there is no block form of wave_bins yet: a lane per waveform)
+               the long shapes against plan.decode alone and plan.wave_stats (its block form), under --impl 0 (a lane per
+               waveform) and --impl 1 (the context option "bins_impl": the block form); the form that ran and the waveforms
+               its blocks listed for the lane kernel are printed beside each time.  --bin N: bins of N samples across the trace
+               instead of 1000 bins
 
 Peak bytes: torch's peak allocation during one call that allocates its own results, above what the encoded batch occupies.
 
-usage: wave_bins_bench.py --only NAME [--chunks 500] [--calls 20] [--warmup 5]"""
+usage: wave_bins_bench.py --only NAME [--impl {0,1}] [--bin N] [--chunks 500] [--calls 20] [--warmup 5]"""
 import argparse
 import os
 import sys
@@ -113,7 +116,7 @@ class Case:
                     match = torch.equal(got, want)
                 del want
             del got
-        form = {0: "?", 1: "lanes", 2: "blocks"}[self.plan.last_bins_form() & 3]
+        form = {0: "?", 1: "lanes", 2: "blocks"}[self.plan.last_bins_form() & 3] + f", listed {self.plan.last_bins_listed()}"
         self.ctx.set_option("profile", 1)
         self.timed(lambda: self.bins(bin, n_bins, start, offset))
         walk, kern = self.plan.last_timings()[:2]
@@ -147,8 +150,11 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--only", required=True)
+    ap.add_argument("--impl", type=int, choices=(0, 1), default=0, help='the context option "bins_impl"')
+    ap.add_argument("--bin", type=int, default=0, help="long shapes: bins of this many samples instead of 1000 bins")
     a = ap.parse_args()
     ctx = dr.Context(0)
+    ctx.set_option("bins_impl", a.impl)
     print(f"times in ms: median [min .. max] of {a.calls} calls behind {a.warmup}")
     if a.only == "headline":
         c = Case(ctx, [2000 * 7000] * a.chunks, [7000] * a.chunks, 10.0)
@@ -159,7 +165,8 @@ def main():
     else:
         Ns, Ls = geometry(a.only)
         c = Case(ctx, list(Ns), list(Ls), 10.0)
-        c.line(a.only, a.calls, a.warmup, -(-c.L // 1000), 1000, reduces=False, with_stats=True)
+        bin = a.bin if a.bin else -(-c.L // 1000)
+        c.line(f"{a.only} impl {a.impl}", a.calls, a.warmup, bin, -(-c.L // bin), reduces=False, with_stats=True)
     c.plan.close()
 
 
