@@ -12,7 +12,7 @@ HIPFLAGS  ?= -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-funct
 CSRC      := deltarice_amd/csrc
 HIP_LIB   := deltarice_amd/libdeltarice_hip.so
 PLUGIN    := deltarice_amd/plugin/libh5deltarice.so
-HIP_SRCS  := $(CSRC)/drx_encode_kernels.hip $(CSRC)/drx_encode_stream.hip $(CSRC)/drx_walk.hip $(CSRC)/drx_decode_kernels.hip $(CSRC)/drx_blocks.hip $(CSRC)/drx_pieces.hip $(CSRC)/drx_iir.hip $(CSRC)/drx_select.hip $(CSRC)/drx_gather.hip $(CSRC)/drx_stats.hip $(CSRC)/drx_stats_blocks.hip $(CSRC)/drx_bins.hip $(CSRC)/drx_bins_blocks.hip $(CSRC)/drx_transcode.hip $(CSRC)/drx_transcode_blocks.hip $(CSRC)/drx_refilter.hip $(CSRC)/drx_window.hip $(CSRC)/drx_windows.hip $(CSRC)/drx_windows_blocks.hip $(CSRC)/drx_pulses.hip $(CSRC)/drx_pulses_blocks.hip $(CSRC)/drx_api_plan.hip $(CSRC)/drx_api_encode.hip $(CSRC)/drx_api_select.hip $(CSRC)/drx_api_stream.hip $(CSRC)/drx_api_host.hip
+HIP_SRCS  := $(CSRC)/drx_encode_kernels.hip $(CSRC)/drx_encode_stream.hip $(CSRC)/drx_walk.hip $(CSRC)/drx_decode_kernels.hip $(CSRC)/drx_blocks.hip $(CSRC)/drx_pieces.hip $(CSRC)/drx_iir.hip $(CSRC)/drx_select.hip $(CSRC)/drx_gather.hip $(CSRC)/drx_stats.hip $(CSRC)/drx_stats_blocks.hip $(CSRC)/drx_bins.hip $(CSRC)/drx_bins_blocks.hip $(CSRC)/drx_stack.hip $(CSRC)/drx_transcode.hip $(CSRC)/drx_transcode_blocks.hip $(CSRC)/drx_refilter.hip $(CSRC)/drx_window.hip $(CSRC)/drx_windows.hip $(CSRC)/drx_windows_blocks.hip $(CSRC)/drx_pulses.hip $(CSRC)/drx_pulses_blocks.hip $(CSRC)/drx_api_plan.hip $(CSRC)/drx_api_encode.hip $(CSRC)/drx_api_select.hip $(CSRC)/drx_api_stream.hip $(CSRC)/drx_api_host.hip
 HIP_OBJS  := $(HIP_SRCS:.hip=.o)
 HIP_HDRS  := $(CSRC)/drx_internal.h $(CSRC)/drx_api.h $(CSRC)/drx_sel_survey.h $(CSRC)/drx_device.h $(CSRC)/drx_encode.h $(CSRC)/drx_walk.h $(CSRC)/drx_iir_math.h $(CSRC)/drx_lookback.h $(CSRC)/drx_blocks.h $(CSRC)/drx_blocks_body.inc $(CSRC)/drx_blocks_trc.inc $(CSRC)/drx_blocks_bins.inc $(CSRC)/drx_bin_cursor.h $(CSRC)/drx_pulse_runs.h $(CSRC)/drx_pulses_lane_body.inc $(CSRC)/drx_window_rows.h $(CSRC)/drx_windows_lane_body.inc $(CSRC)/drx_lane_stream.h $(CSRC)/drx_lane_reader.inc $(CSRC)/drx_recode.h include/deltarice_hip.h
 

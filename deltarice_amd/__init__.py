@@ -15,6 +15,7 @@ from ._lib import (STAT_ARGMAX, STAT_ARGMIN, STAT_COLS, STAT_HEAD_SUM, STAT_HEAD
 from ._lib import DBG_REFILTER_SERIAL, TRANSCODE_FORM_REFILTER, TRANSCODE_FORM_REFILTER_SERIAL  # noqa: F401
 from ._lib import (BIN_COLS, BIN_MAX, BIN_MIN, BIN_SUM, BIN_SUMSQ, BINS_FORM_BLOCKS, BINS_FORM_FALLBACK_ALL, BINS_FORM_LANES,  # noqa: F401
                    DBG_BINS_ALL_FALLBACK, DBG_BINS_LANES, PATH_BINS)
+from ._lib import PATH_STACK, STACK_COLS, STACK_COUNT, STACK_SUM, STACK_SUMSQ  # noqa: F401
 
 H5FILTER = 32025
 

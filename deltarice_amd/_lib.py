@@ -25,6 +25,10 @@ PATH_WINDOW = 2048
 PATH_PULSES = 4096
 PATH_WINDOWS = 8192
 PATH_BINS = 16384
+PATH_STACK = 32768
+# DRX_STACK_*: the columns of a drx_wave_stack row (tests/test_wave_stack_abi.py holds them equal)
+STACK_COUNT, STACK_SUM, STACK_SUMSQ = range(3)
+STACK_COLS = 3
 # DRX_BIN_*: the columns of a drx_wave_bins row (tests/test_wave_bins_abi.py holds them equal)
 BIN_SUM, BIN_SUMSQ, BIN_MIN, BIN_MAX = range(4)
 BIN_COLS = 4
@@ -136,6 +140,8 @@ SIGNATURES = {
     "drx_wave_stats_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "drx_wave_bins": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, _u32, _vp, _u64]),
     "drx_wave_bins_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, _u32, _vp, _u64]),
+    "drx_wave_stack": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, _vp, _vp, _u64]),
+    "drx_wave_stack_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, _vp, _vp, _u64]),
     "drx_decode_window": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_decode_window_with_wave_words": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.c_int64, _u32, C.c_int16, _vp, _u64]),
     "drx_decode_windows": (C.c_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u64, _vp, _u32, C.c_int64, _u32, C.c_int16, _vp, _u64, _u64]),

@@ -581,6 +581,48 @@ class Plan:
         ``ctx.set_option("bins_impl", 1)``; the rows are the same, last_bins_form() says which form ran."""
         return self._blocking(self.wave_bins_async, enc, bin, n_bins, start, offset, out, wave_words)
 
+    def wave_stack_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, width: Optional[int] = None,
+                         start: Optional[torch.Tensor] = None, offset: int = 0, select: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None, wave_words: Optional[torch.Tensor] = None,
+                         in_words: Optional[int] = None) -> torch.Tensor:
+        """Launches drx_wave_stack on the context's stream: int64 [width, STACK_COLS], row j = (how many, their sum, the sum of
+        their squares) over the samples ``start[g] + offset + j`` of the selected waveforms g that have one, over the int16
+        samples decode() would give, exact; a position nobody reaches is (0, 0, 0), and results of several batches add.
+        Nothing is decoded to memory and a waveform is read no further than its window's end.  width None: the positions that
+        some waveform of the plan reaches from ``offset`` with origins 0 (wave_bins' default n_bins at bin 1).  start: as
+        wave_bins takes it -- ``stats[:, STAT_ARGMAX]`` is passed as it is.  select: None (every waveform), or a bool or uint8
+        tensor of total_waves entries on the plan's device (nonzero: selected); a waveform that is not selected is not read.
+        out: a contiguous int64 tensor of width * STACK_COLS elements.  wave_words: the encoder's n_i table as
+        decode_with_wave_words takes it (no header walk).  Launch only; finish() raises on device-side errors."""
+        self._open("wave_stack")
+        offset = _int64(offset, "offset")
+        width = _uint32(max(0, self.longest_wave() - offset) if width is None else width, "width")
+        sp, ss = self._column(start, "start")
+        if select is not None:
+            if not isinstance(select, torch.Tensor) or select.dim() != 1 or select.dtype not in (torch.bool, torch.uint8):
+                raise DeltaRiceError(1, f"select: need a 1-D bool or uint8 tensor of {self.total_waves} entries on {self.ctx.device}")
+            self._dev_check(select, select.dtype, self.total_waves, "select")
+        self._check_encoded(words, chunk_word_off, wave_words)
+        out = self._out(out, torch.int64, (width, _lib.STACK_COLS), "out")
+        if width == 0:
+            return out
+        if self.total_waves == 0:
+            with torch.cuda.stream(self.ctx.stream):
+                out.view(-1)[:width * _lib.STACK_COLS].zero_()  # (no waveform: the rows nobody reaches)
+            return out
+        self._call_encoded("wave_stack", words, chunk_word_off, wave_words, in_words, sp, ss, offset, width,
+                           select.data_ptr() if select is not None else None, out.data_ptr(), _lib.STACK_COLS)
+        return out
+
+    def wave_stack(self, enc: EncodedBatch, width: Optional[int] = None, start: Optional[torch.Tensor] = None, offset: int = 0,
+                   select: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   wave_words: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """wave_stack_async on an EncodedBatch -> int64 [width, STACK_COLS]; waits, and raises like wave_stats().  The average
+        pulse of the waveforms that passed a cut, aligned on the maximum, and its variance:
+        ``r = plan.wave_stack(enc, 512, start=stats[:, STAT_ARGMAX], offset=-64, select=cut(stats))``, then
+        ``mean = r[:, STACK_SUM] / r[:, STACK_COUNT]``.  General prediction filters and few long waveforms are correct and slow."""
+        return self._blocking(self.wave_stack_async, enc, width, start, offset, select, out, wave_words)
+
     def decode_window_async(self, words: torch.Tensor, chunk_word_off: torch.Tensor, start, width: int, offset: int = 0,
                             pad: int = 0, out: Optional[torch.Tensor] = None, out_stride: Optional[int] = None,
                             wave_words: Optional[torch.Tensor] = None, in_words: Optional[int] = None) -> torch.Tensor:

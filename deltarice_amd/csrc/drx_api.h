@@ -107,6 +107,7 @@ struct drx_ctx {
                           // look-back (k_encode_fused) everywhere; 0: size pass + scan + pack pass
     int bins_impl = 0;    // launch_wave_bins(): 0 = a lane per waveform whatever the batch (default), 1 = the block form where
                           // blocks_form_batch() admits the batch under kBinsForm (drx_bins_blocks.hip)
+    uint32_t stack_workgroups = 0;  // launch_wave_stack(): 0 = the resident grid (default), n = at most n persistent workgroups per tile
     int profile = 0;      // bracket kernels with HIP events (drx_plan_last_timings)
     uint32_t debug_flags = 0;  // Geom::dbg
     std::string last_error;
@@ -189,6 +190,7 @@ struct drx_plan {
     // header positions[W] of the RESULT (the plan's own tables describe the source); first call
     // ... and the block form's own scratch and form word (trc_blocks_scratch_bytes(): accumulators, list, block-slot table)
     struct Transcode { void *d = nullptr; BlockForm blocks; } trc;
+    void *stack_list = nullptr;  // drx_wave_stack under a selection: the listed waveforms (stack_list_bytes(), drx_internal.h); first call
     // drx_decode_select and the gather's front end
     struct Selection {
         Grown h, d;  // uint64 sel[n_sel] | uint32 chunk_n[n_out] | uint32 chunk lists[touched]: pinned staging and its device copy

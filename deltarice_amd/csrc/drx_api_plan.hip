@@ -355,6 +355,11 @@ drx_status drx_ctx_set_option(drx_ctx *c, const char *key, int64_t value) {
         c->bins_impl = (int)value;
         return DRX_OK;
     }
+    if (!strcmp(key, "stack_workgroups")) {
+        if (value < 0 || value > 0xffffffffll) return DRX_ERR_ARG;
+        c->stack_workgroups = (uint32_t)value;
+        return DRX_OK;
+    }
     if (!strcmp(key, "debug_flags")) {
         c->debug_flags = (uint32_t)value;
         return DRX_OK;

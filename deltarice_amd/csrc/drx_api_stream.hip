@@ -1,5 +1,5 @@
 // drx_api_stream.hip -- C ABI glue (drx_api.h): the calls that read the whole batch from the encoded stream -- decode, and
-// without decoding it wave_stats, wave_bins, decode_window(s), find_pulses, transcode(_filter), estimate_words_encoded(_filter).  Each checks its pointers
+// without decoding it wave_stats, wave_bins, wave_stack, decode_window(s), find_pulses, transcode(_filter), estimate_words_encoded(_filter).  Each checks its pointers
 // with stream_call_args(), opens with stream_call_begin() and closes with call_end().  Host code only.
 #include "drx_api.h"
 
@@ -76,6 +76,25 @@ static drx_status decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_w
     if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
     DRX_HIP(ctx, launch_decode_window(c, d_start, start_stride, offset, width, pad, d_out, out_stride));
     return call_end(p, DRX_PATH_WINDOW);
+}
+
+// the sum of selected, aligned waveforms (drx_stack.hip)
+static drx_status wave_stack(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                             const uint32_t *d_sideband, bool sideband, const int64_t *d_start, uint64_t start_stride, int64_t offset,
+                             uint32_t width, const uint8_t *d_select, int64_t *d_out, uint64_t out_stride) {
+    if (!p) return DRX_ERR_ARG;
+    drx_ctx *ctx = p->ctx;
+    if (const drx_status st = stream_call_args(p, "wave_stack", d_in && d_chunk_word_off && d_out, d_sideband, sideband)) return st;
+    if (d_start && start_stride == 0) return fail(ctx, DRX_ERR_ARG, "wave_stack: start_stride 0");
+    if (out_stride < (uint64_t)DRX_STACK_COLS)
+        return fail(ctx, DRX_ERR_ARG, "wave_stack: rows %llu int64 apart do not hold %d", (unsigned long long)out_stride, DRX_STACK_COLS);
+    if (width == 0) return DRX_OK;  // (no row to write: nothing to launch)
+    DRX_ON_DEVICE(ctx);
+    StreamCall c;
+    if (const drx_status st = stream_call_begin(p, d_in, in_words, d_chunk_word_off, d_sideband, false, &c)) return st;
+    if (d_select) DRX_HIP(ctx, p->mem.once(&p->stack_list, stack_list_bytes(p->G)));
+    DRX_HIP(ctx, launch_wave_stack(c, p->stack_list, ctx->stack_workgroups, d_start, start_stride, offset, width, d_select, d_out, out_stride));
+    return call_end(p, DRX_PATH_STACK);
 }
 
 // several windows of every waveform, at per-window starts (drx_windows.hip)
@@ -228,6 +247,18 @@ drx_status drx_wave_bins_with_wave_words(drx_plan *p, const uint32_t *d_in, uint
                                          uint32_t bin, uint32_t n_bins, int64_t *d_out, uint64_t out_wave_stride) {
     return wave_bins(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_start, start_stride, offset, bin, n_bins, d_out,
                      out_wave_stride);
+}
+
+drx_status drx_wave_stack(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off, const int64_t *d_start,
+                          uint64_t start_stride, int64_t offset, uint32_t width, const uint8_t *d_select, int64_t *d_out, uint64_t out_stride) {
+    return wave_stack(p, d_in, in_words, d_chunk_word_off, nullptr, false, d_start, start_stride, offset, width, d_select, d_out, out_stride);
+}
+
+drx_status drx_wave_stack_with_wave_words(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                          const uint32_t *d_wave_words, const int64_t *d_start, uint64_t start_stride, int64_t offset,
+                                          uint32_t width, const uint8_t *d_select, int64_t *d_out, uint64_t out_stride) {
+    return wave_stack(p, d_in, in_words, d_chunk_word_off, d_wave_words, true, d_start, start_stride, offset, width, d_select, d_out,
+                      out_stride);
 }
 
 drx_status drx_decode_window(drx_plan *p, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,

@@ -317,6 +317,16 @@ hipError_t launch_bins_blocks(const StreamCall &c, void *d_blk, void *d_list, co
 // g of d_out, rows out_stride samples apart.  d_start == nullptr: 0.  ev: {start, walk's end, kernel's end, end}
 hipError_t launch_decode_window(const StreamCall &c, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width,
                                 int16_t pad, int16_t *d_out, uint64_t out_stride);
+// drx_wave_stack (drx_stack.hip): behind the whole batch's walk (tables_ready as above), the `width` rows of DRX_STACK_COLS int64,
+// out_stride elements apart, set to zero; COUNT from the geometry, the origins (as drx_wave_bins takes them) and the selection
+// (d_select: uint8[total_waves], nullptr: every waveform) alone; then persistent workgroups of lanes that parse every selected
+// waveform as far as its window's end and add SUM and SUMSQ through an accumulator in LDS.  ev: {start, walk's end, kernels' end, end}
+// d_list: stack_list_bytes() of scratch where d_select != nullptr (u64 n_listed | u64 listed[W]: the selected waveforms that add
+// something, for the delta filter's lanes), which may be nullptr otherwise
+inline uint64_t stack_list_bytes(const Geom &G) { return 8u * (G.total_waves + 1u); }
+// max_wgs: the context option "stack_workgroups" (0: the resident grid; otherwise at most so many workgroups per tile of positions)
+hipError_t launch_wave_stack(const StreamCall &c, void *d_list, uint32_t max_wgs, const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width,
+                             const uint8_t *d_select, int64_t *d_out, uint64_t out_stride);
 // drx_decode_windows (drx_windows.hip): behind the whole batch's walk (tables_ready as above), a lane per waveform that parses as
 // far as the end of its last live window and writes every window slot's row of `width` samples: slot p < min(d_count[g], n_win)
 // (d_count == nullptr: every slot) from d_start[g * start_wave_stride + p * start_win_stride] + offset on, pad outside the waveform

@@ -324,6 +324,56 @@ uint32_t drx_plan_last_bins_form(const drx_plan *plan);
  * the lane kernel behind the blocks, as drx_plan_last_windows_listed; 0 for the lane form */
 uint32_t drx_plan_last_bins_listed(const drx_plan *plan);
 
+/* The STACK of selected, aligned waveforms straight from the encoded stream: per position, how many waveforms have a sample
+ * there, the sum of those samples and the sum of their squares -- the average pulse (the template of pulse-shape fits, optimal
+ * filters and pile-up models) and its per-sample variance, over the waveforms that passed the cuts, aligned on the trigger or on
+ * the maximum -- without decoding the batch to memory and with no temporary larger than the result.  The first stream call that
+ * reduces ACROSS waveforms.
+ *   Contributions.  Waveform g (a global waveform index in the order of drx_plan_wave_words) has samples y[0 .. len_g), the int16
+ * drx_decode would write.  Its origin is a_g = (d_start ? d_start[g * start_stride] : 0) + offset; the sum saturates at the int64
+ * ends, as in drx_decode_window.  d_start is drx_wave_bins': int64 on the device, any 8-byte alignment, start_stride in int64
+ * elements, so a column of drx_wave_stats' output or of drx_find_pulses' records goes in as it is.  Waveform g is selected when
+ * d_select == NULL or d_select[g] != 0; d_select: uint8[total_waves] on the device, any alignment.  Position j, 0 <= j < width,
+ * receives y[a_g + j] from every selected g with 0 <= a_g + j < len_g.
+ *   Rows.  Row j is d_out + j * out_stride, out_stride >= DRX_STACK_COLS in int64 elements, any 8-byte alignment of d_out: the
+ * three DRX_STACK_* columns over those contributions, exact.  A position nobody reaches is (0, 0, 0).  Exactly `width` rows are
+ * written and nothing between them is touched; the result does not depend on what the rows held before (the call sets them
+ * itself), and it is the same in any execution order, because the adds are integer adds.  Outputs of several batches or several
+ * GPUs add.  Row addressing is 64-bit.
+ *   DRX_ERR_ARG, with nothing launched and the status word as it was: a NULL pointer among d_in, d_chunk_word_off, d_out;
+ * start_stride == 0 with d_start != NULL; out_stride < DRX_STACK_COLS; in the second form a NULL side-band, or the plan's own
+ * table passed as the side-band.  width == 0 returns DRX_OK with nothing launched.
+ *   Validation and trust are drx_decode_window's.  The header chain of every chunk is walked and judged (the second form checks
+ * the table against the stream instead).  A selected waveform is parsed no further than the last code of its window, a waveform
+ * that is not selected is not parsed at all, and neither the result nor the verdict depends on bits that were not parsed.  A
+ * window that reaches the waveform's last sample makes the end-of-payload check; a payload that runs out before the window does
+ * is DRX_ERR_CORRUPT at drx_plan_finish, the rows are then undefined and the plan stays usable.  No store's address depends on
+ * the stream.
+ *   Asynchronous on the context's stream like drx_wave_stats; the call clears the plan's status word first and ends a pending
+ * drx_gather_encoded sizing call's resume; errors found on the device arrive at drx_plan_finish.  drx_plan_last_decode_path
+ * reports DRX_PATH_STACK alone, drx_plan_last_timings { header-chain walk, everything behind the walk, 0, whole call }.
+ *   Every prediction filter the plan accepts, uniform and ragged plans.  Under the delta filter a lane per waveform parses, in
+ * persistent workgroups that keep the sums of a tile of positions (512, or 7168) in LDS across many waveforms and add them to
+ * the rows once, with 64-bit integer atomics; COUNT comes from the geometry alone; under a selection the lanes take a list of
+ * the selected waveforms (8 bytes per waveform of plan scratch, allocated by the first such call).  What is slow: any other filter runs a serial
+ * kernel that adds every sample to its row by atomics, correct and not tuned; and few long waveforms (the reference's default of
+ * one waveform per chunk) stay a lane per waveform, 50-60 ns per sample and lane, parsed once per tile of 7168 positions, until
+ * a block form exists.  A width far beyond the reach of every window costs what its rows cost -- every tile of positions is
+ * launched and COUNT's scan is one workgroup over all `width` cells: seconds at the 2^32 - 1 the type allows. */
+#define DRX_STACK_COUNT 0   /* selected waveforms that have a sample at this position */
+#define DRX_STACK_SUM   1   /* sum of those samples                                   */
+#define DRX_STACK_SUMSQ 2   /* sum of their squares                                   */
+#define DRX_STACK_COLS  3
+drx_status drx_wave_stack(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                          const int64_t *d_start, uint64_t start_stride, int64_t offset, uint32_t width,
+                          const uint8_t *d_select, int64_t *d_out, uint64_t out_stride);
+/* ... with the encoder's side-band as drx_decode_with_wave_words takes it (d_wave_words: uint32[total_waves] on the device, not
+ * the plan's own table): no walk; a table that does not belong to the stream is DRX_ERR_CORRUPT. */
+drx_status drx_wave_stack_with_wave_words(drx_plan *plan, const uint32_t *d_in, uint64_t in_words, const uint64_t *d_chunk_word_off,
+                                          const uint32_t *d_wave_words, const int64_t *d_start, uint64_t start_stride,
+                                          int64_t offset, uint32_t width, const uint8_t *d_select, int64_t *d_out,
+                                          uint64_t out_stride);
+
 /* A WINDOW of every waveform, at per-waveform offsets, straight from the encoded stream: the samples around a pulse that
  * drx_wave_stats found, or the first few hundred samples of each waveform, without decoding the batch to memory and -- unlike
  * every other stream call -- without reading a payload beyond its window.
@@ -652,6 +702,7 @@ const uint64_t *drx_plan_wave_word_off(const drx_plan *plan);
 #define DRX_PATH_PULSES 4096u   /* drx_find_pulses: a lane per waveform that parses and discriminates; reported alone */
 #define DRX_PATH_WINDOWS 8192u  /* drx_decode_windows: several windows per waveform, lanes or blocks; reported alone */
 #define DRX_PATH_BINS 16384u    /* drx_wave_bins: a lane per waveform that parses and reduces bin by bin; reported alone */
+#define DRX_PATH_STACK 32768u   /* drx_wave_stack: lanes that parse and add across waveforms through LDS; reported alone */
 uint32_t drx_plan_last_decode_path(const drx_plan *plan);
 /* ... and which encoder its last drx_encode used (one value; bench.py names the kernel it prices by this, and the tests
  * hold the dispatch to it: the headline batch must take DRX_ENC_STREAM whatever in_words its decodes were given) */
@@ -688,6 +739,7 @@ drx_status drx_filter_chunk_host(drx_ctx *ctx, int reverse, size_t cd_nelmts,
  *   after drx_gather_encoded: ms = { header-chain walk, sizes + scan + offsets, copy, whole call }
  *   after drx_wave_stats: ms = { header-chain walk, statistics kernels (block form: blocks + finish + fallback), 0, whole call }
  *   after drx_wave_bins: ms = { header-chain walk, everything behind the walk, 0, whole call }
+ *   after drx_wave_stack: ms = { header-chain walk, everything behind the walk, 0, whole call }
  *   after drx_transcode: ms = { header-chain walk, sizes + scan + offsets, pack, whole call }
  *   after drx_decode_window: ms = { header-chain walk, window kernel, 0, whole call }
  *   after drx_decode_windows: ms = { header-chain walk, everything between the walk and the call's end (block form: pads,
@@ -711,6 +763,9 @@ drx_status drx_plan_last_timings(drx_plan *plan, float ms[4]);
  *   "bins_impl"    0 (default): drx_wave_bins runs a lane per waveform whatever the batch;
  *                  1: the block form (a workgroup per block of a waveform's stream) for the batches drx_wave_stats gives to its
  *                  block form, a lane per waveform elsewhere; the rows are the same (drx_wave_bins above)
+ *   "stack_workgroups"  0 (default): drx_wave_stack's lane kernel runs as many persistent workgroups per tile of positions as
+ *                  the chip holds; n >= 1: at most n, each walking more waveforms between two flushes of its sums -- the rows
+ *                  are the same; for tests of the periodic flush (one workgroup meets it beyond 65 280 waveforms)
  *   "debug_flags"  DRX_DBG_* bits: dispatch overrides that force an alternative (still bit-exact) path, for tests and A/B timing;
  *                  a forcing flag takes its encoder wherever that encoder can run the batch */
 #define DRX_DBG_BINS_LANES 64u                   /* drx_wave_bins under "bins_impl" 1: never the block form */
